@@ -660,6 +660,8 @@ def marlin_bench(args, ctx, dist, rank, world, real_stdout):
            "proof_constraints_per_s": round(n * K / dt, 1), "proof_bytes": len(proof_bytes),
            "setup_s": round(t_setup, 2), "proof_sha": __import__("hashlib").sha256(proof_bytes).hexdigest()[:16], **verdict}
     out["hbm_in_use_gb"] = hbm_in_use_gb()
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, proof_bytes)
     if dist is not None:
         out["bytes_sent_per_party"] = int(party.bytes_sent)
         out["bytes_sent_per_party_per_proof"] = int(sent_timed // max(K, 1))
@@ -751,7 +753,20 @@ def one_prover_bench(args, real_stdout):
            "single_context_isolated_ms": round(t_single * 1e3, 3),
            "proof_matches_prediction": pred, "setup_s": round(t_setup, 2), "proof_sha": hashlib.sha256(proof).hexdigest()[:16],
            "devices": [int(c.device) for c in ctxs], "hbm_in_use_gb": hbm_in_use_gb()}
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, proof)
     os.write(real_stdout, (json.dumps(out) + "\n").encode())
+
+
+def dump_outputs(dirname, proof: bytes) -> dict:
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step -- the proof's bytes (Groth16: A || B || C,
+    192 B; Marlin: its serialization) -- as DIR/proof.npy, one float64 per byte (exact), so that two builds run with the same
+    arguments (hence the same seeded inputs) can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"proof": np.frombuffer(bytes(proof), dtype=np.uint8).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "arrays": {name: list(a.shape) for name, a in arrays.items()}, "dtype": "float64"}
 
 
 def hbm_in_use_gb():
@@ -1006,7 +1021,11 @@ def main():
                          "of N parties; total work fixed (strong scaling); add --one-gpu for a functional run on one device")
     ap.add_argument("--marlin", action="store_true",
                     help="prove with Marlin/KZG instead of Groth16 (BASELINE configs 4 and 5: --gpus 1, or --gpus 8 --spdz --log-constraints 22)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64; e.g. DIR = bench_outputs, which git ignores)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout must carry exactly ONE JSON line: libraries (RCCL prints a version banner on stdout at communicator
     # creation) are redirected to stderr for the whole run and the JSON is written to the saved descriptor.
@@ -1422,6 +1441,8 @@ def main():
             "roofline": roof,
             "hbm_in_use_gb": hbm_in_use_gb(),
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, proof)
         try:      # which tables carry window multiples, in which layout -- or why not (a skipped table costs 16 digits per scalar instead of 13)
             wm = {}
             for which in ("a", "b_g1", "b_g2", "h", "l"):

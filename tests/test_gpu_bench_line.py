@@ -36,6 +36,30 @@ def test_single_gpu_line_small():
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] in ("port", "reference")
 
 
+@pytest.mark.parametrize("extra", [[], ["--marlin"]])
+def test_dump_outputs_is_the_last_timed_proof_and_repeats(tmp_path, extra):
+    """--dump-outputs DIR: the last timed step's proof bytes as DIR/proof.npy (float64, one value per byte); the same arguments
+    give the same inputs, hence the same file, run after run."""
+    import hashlib
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        d = _line([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--log-constraints", "12", "--no-extras", "--no-micro",
+                   "--no-cpu-baseline", "--no-predict", "--dump-outputs", str(out)] + extra)
+        assert d["steps"] == 3 and d["dump_outputs"]["arrays"] == {"proof": [d.get("proof_bytes", 192)]}
+        a = np.load(out / "proof.npy")
+        assert a.dtype == np.float64 and np.all((a >= 0) & (a <= 255) & (a == np.floor(a)))
+        assert hashlib.sha256(a.astype(np.uint8).tobytes()).hexdigest()[:16] == d["proof_sha"]
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 @pytest.mark.parametrize("world,extra", [(2, []), (3, ["--spdz"]), (2, ["--marlin"])])
 def test_n_party_line_over_gloo_on_one_gpu(world, extra):
     from helpers import free_port
