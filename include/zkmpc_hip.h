@@ -651,6 +651,18 @@ int zk_diag_int_mad_peak(zk_ctx* ctx, int launches, double* best_mads_per_s, dou
  * two_adic_root_of_unity() (arkworks/curves/bls12_377/src/fields/tests.rs:352-370) and the same relation of fr.rs's constants. */
 int zk_diag_fq_pow_dev(zk_ctx* ctx, const zk_fq* base, const uint64_t exp[6], int lazy, zk_fq* out);
 int zk_diag_fr_pow_dev(zk_ctx* ctx, const zk_fr* base, const uint64_t exp[4], int lazy, zk_fr* out);
+/* Test hooks: the lazy-domain arithmetic as the DEVICE code object runs it -- n_cases cases in one launch, raw 29-bit limbs in and out
+ * (the top limb of an element may be wide).  csrc/diag.hip lists the ops and their layouts.  ZK_ERR_ARG for an unknown op, a null
+ * pointer or n_cases outside 1 .. 2^20.
+ *   zk_diag_fq_lazy_dev   the ops of zk_fq_lazy_raw (0 - 12), 13 words per Fq element, one case per lane
+ *   zk_diag_fr_lazy_dev   the ops of zk_fr_lazy_raw (0 - 10), 9 words per Fr element, one case per lane
+ *   zk_diag_fq2_pair_dev  the G2 lane-pair Fq2 arithmetic of msm_g2pair.hip (0 - 6; an Fq2 element is 2 x 13 words) and the G1
+ *                         lane-pair point additions of msm.hip (7, 8; 13 words per element), one case per lane pair or quad
+ *   zk_diag_f7l_dev       the lazy MNT4-753 field of the SHE transforms (she.hip, 0 - 8), 26 words per element, one case per lane */
+int zk_diag_fq_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in13s, uint32_t* out13s, size_t n_cases);
+int zk_diag_fr_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in9s, uint32_t* out9s, size_t n_cases);
+int zk_diag_fq2_pair_dev(zk_ctx* ctx, int op, const uint32_t* in13s, uint32_t* out13s, size_t n_cases);
+int zk_diag_f7l_dev(zk_ctx* ctx, int op, const uint32_t* in26s, uint32_t* out26s, size_t n_cases);
 /* Diagnostic: k * a in G1 through the curve's endomorphism (hostfield64.hpp: host64_scalar_mul_glv: k split at lambda = z^2 - 1, one
  * joint chain) -- what the host tail of a Groth16 proof runs for keys made by zk_groth16_setup.  Equal to zk_g1_mul for every point of
  * the prime-order subgroup; kept apart from it because ProjectiveCurve::mul (zk_g1_mul) is defined on the whole curve. */

@@ -11,6 +11,8 @@ import zkref as O
 import zk_mpc_amd as Z
 import zk_mpc_amd.convert as cv
 from zk_mpc_amd import _lib
+from lazy_cases import (EPS, FQ_ENDS, FQ_SPARSE, FR_ENDS, M29, Q, RI14, RI9, RR, _l9, _limbs_wide, _normalised, _spread, _val,
+                        neg5_cases, worst_columns as _worst_columns)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -244,14 +246,7 @@ def test_neg5_almost_range_and_congruence():
     q = O.Q_MOD
     limbs = lambda v: np.array([(v >> (29 * i)) & ((1 << 29) - 1) for i in range(13)], dtype=np.uint32)
     val = lambda a: sum(int(x) << (29 * i) for i, x in enumerate(a))
-    rnd = random.Random(5)
-    ptop = q >> 348
-    cases = [0, 1, 2, q - 1, q - 2, ptop << 348, (ptop << 348) - 1, (ptop - 1) << 348, (1 << 348) - 1, 1 << 348]
-    for j in range(1, 6):
-        t = ((j * q) // 5) >> 348
-        cases += [v for v in [(j * q) // 5 + d for d in range(-3, 4)] if 0 <= v < q]
-        cases += [v for v in [((t + dt) << 348) + low for dt in (-1, 0, 1) for low in (0, (1 << 348) - 1)] if 0 <= v < q]
-    cases += [rnd.randrange(q) for _ in range(3000)]
+    cases = neg5_cases(random.Random(5))
     for a in cases:
         out = np.zeros(13, dtype=np.uint32)
         assert lib.zk_fq_neg5_almost_raw(limbs(a).ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) == 0
@@ -262,21 +257,6 @@ def test_neg5_almost_range_and_congruence():
 
 # ---- the lazy domain of Fq (fp29.cuh): representatives in [0, ~7 q], no conditional subtractions -----------------------------
 
-Q = O.Q_MOD
-RI14 = 1 << (29 * 14)
-EPS = 1 << 354
-
-
-def _limbs_wide(v):
-    """13 limbs: 12 of 29 bits and a top limb holding the rest (< 2^32)."""
-    assert 0 <= v < (1 << (29 * 12 + 32))
-    return [(v >> (29 * i)) & ((1 << 29) - 1) for i in range(12)] + [v >> (29 * 12)]
-
-
-def _val(a):
-    return sum(int(x) << (29 * i) for i, x in enumerate(a))
-
-
 def _lazy(op, *vals, n_out=1):
     import ctypes as C
     lib = Z.load()
@@ -284,40 +264,6 @@ def _lazy(op, *vals, n_out=1):
     out = np.zeros(13 * n_out, dtype=np.uint32)
     assert lib.zk_fq_lazy_raw(op, inp.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) == 0
     return [out[13 * k:13 * k + 13] for k in range(n_out)]
-
-
-def _normalised(a, top_bits=29):
-    return all(int(x) < (1 << 29) for x in a[:12]) and int(a[12]) < (1 << top_bits)
-
-
-def _worst_columns(tops, split_top=False):
-    """Worst-case column sums (in the order the kernels accumulate them) of the product scanning with every low limb at
-    2^29 - 1, the given top limbs per operand ((a, b) or (a, b, c, d)) and every Montgomery digit at its maximum (2^29 for the
-    first one, fp29.cuh::fp_redc_column).  The m_i p_0 terms stand for the "+ 1" carries the kernels never add: an upper bound."""
-    L, LR = 13, 14
-    pl = [(Q >> (29 * i)) & ((1 << 29) - 1) for i in range(13)]
-    mmax = (1 << 29) - 1
-    ops = [[(1 << 29) - 1] * 12 + [t] for t in tops]
-    carry, cols = 0, []
-    for k in range(LR + L - 1):
-        col, up = carry, 0
-        for i in range(L):
-            j = k - i
-            if 0 <= j < L:
-                col += ops[0][i] * ops[1][j]
-                if len(ops) == 4:
-                    t = ops[2][i] * ops[3][j]
-                    if split_top and k == 2 * L - 2:
-                        col += t & ((1 << 29) - 1)
-                        up = t >> 29
-                    else:
-                        col += t
-        for i in range(LR):
-            if 0 <= k - i < L:
-                col += (mmax + 1 if i == 0 else mmax) * pl[k - i]
-        cols.append(col)
-        carry = (col >> 29) + up
-    return cols
 
 
 def test_lazy_domain_column_bounds():
@@ -341,7 +287,7 @@ def test_lazy_domain_primitives_against_big_integers():
     at the range ends (0, q, 2q .. 7q + eps) and random ones."""
     import random
     rnd = random.Random(99)
-    ends = [0, 1, Q - 1, Q, Q + EPS - 1, 2 * Q, 3 * Q + EPS, 5 * Q + EPS - 1, 7 * Q + EPS - 1, 7 * Q + 2 * EPS - 1]
+    ends = FQ_ENDS
     wide = ends + [rnd.randrange(7 * Q + EPS) for _ in range(40)]
     inv = pow(RI14, -1, Q)
     for a in wide:
@@ -356,7 +302,7 @@ def test_lazy_domain_primitives_against_big_integers():
         assert _val(c) == a % Q and _normalised(c)
     # operands whose low limbs are zero: the first column(s) of the product are already clear, the first Montgomery digit is
     # 2^29 (fp29.cuh::fp_redc_column: never 0, so that every carry is at least 1) and the following columns start from a bare 1
-    sparse = [1 << (29 * k) for k in (1, 2, 5, 12)] + [3 << 87, (Q >> 58) << 58, ((7 * Q) >> 29) << 29, 1 << 376]
+    sparse = FQ_SPARSE
     for a in sparse + [0]:
         for b in sparse + [0, 1, Q, rnd.randrange(7 * Q)]:
             (r,) = _lazy(0, a, b)
@@ -432,11 +378,6 @@ def test_lazy_madd_matches_the_group_law():
 
 
 # ---- the lazy Fr domain of the NTT butterflies (csrc/frlazy.cuh) -----------------------------------------------------------
-RR = O.R_MOD
-RI9 = 1 << 261
-M29 = (1 << 29) - 1
-
-
 def _fr_lazy(op, *elems, n_out=1):
     """elems: lists of nine u32 limbs (any limb width)."""
     import ctypes as C
@@ -445,23 +386,6 @@ def _fr_lazy(op, *elems, n_out=1):
     out = np.zeros(9 * n_out, dtype=np.uint32)
     assert lib.zk_fr_lazy_raw(op, inp.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) == 0
     return [[int(x) for x in out[9 * k:9 * k + 9]] for k in range(n_out)]
-
-
-def _l9(v):
-    assert 0 <= v < RI9
-    return [(v >> (29 * i)) & M29 for i in range(9)]
-
-
-def _spread(v, rnd, limb_cap):
-    """The same value with limbs pushed above 29 bits where the value allows: limb i borrows from limb i + 1."""
-    l = _l9(v)
-    for i in range(8):
-        k = min(l[i + 1], (limb_cap - l[i]) >> 29)
-        k = rnd.randrange(k + 1) if k > 0 else 0
-        l[i] += k << 29
-        l[i + 1] -= k
-    assert sum(x << (29 * i) for i, x in enumerate(l)) == v and all(0 <= x < (1 << 32) for x in l)
-    return l
 
 
 def test_fr_lazy_domain_column_bounds():
@@ -586,7 +510,7 @@ def test_fr_lazy_primitives_against_big_integers():
     import random
     rnd = random.Random(7)
     inv = pow(RI9, -1, RR)
-    ends = [0, 1, RR - 1, RR, 2 * RR, 21 * RR // 10, 42 * RR // 10, 84 * RR // 10, 92 * RR // 10 - 1, 16 * RR, 438 * RR, RI9 - 1]
+    ends = FR_ENDS
     for v in ends + [rnd.randrange(RI9) for _ in range(200)] + [rnd.randrange(10 * RR) for _ in range(200)]:
         for limbs in (_l9(v), _spread(v, rnd, (1 << 32) - (1 << 10))):
             (r,) = _fr_lazy(0, limbs)

@@ -9,8 +9,15 @@
 // Montgomery products through the same fp29.cuh templates the kernels run, in the exact or in the lazy domain.  They exist so that
 // the two long-chain known answers the reference's own tests hold (GENERATOR^T == TWO_ADIC_ROOT_OF_UNITY:
 // arkworks/curves/bls12_377/src/fields/tests.rs:352-370 for Fq, the same relation from fr.rs's constants for Fr) run on the GPU.
+//
+// zk_diag_fq_lazy_dev / zk_diag_fr_lazy_dev / zk_diag_fq2_pair_dev / zk_diag_f7l_dev: the lazy-domain arithmetic of the kernels as the
+// device code object compiles it (fp29.cuh's PIN is on only there), a batch of cases in one small launch, raw 29-bit limbs in and
+// out -- the device counterparts of hostapi.hip's zk_fq_lazy_raw / zk_fr_lazy_raw, for tests that put every range end through it.
+// Every case array is padded to whole waves of 64 lanes with all-zero cases: the lane-pair and lane-quad forms exchange operands by
+// DPP, and a pair or quad whose partner were an inactive lane would read nothing from it.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
+#include "ec.cuh"
 #include "frlazy.cuh"
 #include "internal.hpp"
 #include <algorithm>
@@ -129,5 +136,152 @@ extern "C" int zk_diag_fq_pow_dev(zk_ctx* ctx, const zk_fq* base, const uint64_t
 extern "C" int zk_diag_fr_pow_dev(zk_ctx* ctx, const zk_fr* base, const uint64_t exp[4], int lazy, zk_fr* out) {
     ZK_API_BEGIN(ctx)
     return diag_pow<4>(ctx, base ? base->l : nullptr, exp, lazy, out ? out->l : nullptr);
+    ZK_API_END
+}
+
+// ---- the lazy-domain test hooks --------------------------------------------------------------------------------------------------
+namespace {
+
+// Fq, op numbering of zk_fq_lazy_raw, each with the template arguments the kernels use (the products with PIN: FqField::mul_l /
+// sqr_l, mulsub_l and msm_g2pair.hip::mulp_l); element k of a case at words [13 k, +13)
+template <int OP>
+__global__ void __launch_bounds__(64) k_diag_fq_lazy(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int nin, int nout) {
+    using F = FqField;
+    constexpr int L = FqParams::L;
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t* w = in + (size_t)c * nin * L;
+    uint32_t* o = out + (size_t)c * nout * L;
+    auto ld = [&](int k) { Fq a; for (int i = 0; i < L; i++) a.l[i] = w[k * L + i]; return a; };
+    auto st = [&](int k, const Fq& a) { for (int i = 0; i < L; i++) o[k * L + i] = a.l[i]; };
+    auto st8 = [&](const XYZZ<F>& r) {
+        const XYZZ<F> cn = xyzz_canon_lazy<F>(r);
+        st(0, r.x); st(1, r.y); st(2, r.zz); st(3, r.zzz); st(4, cn.x); st(5, cn.y); st(6, cn.zz); st(7, cn.zzz);
+    };
+    if constexpr (OP == 0) st(0, F::mul_l(ld(0), ld(1)));
+    if constexpr (OP == 1) st(0, F::sqr_l(ld(0)));
+    if constexpr (OP == 2) st(0, fp_mul2_lazy<FqParams, false, true>(ld(0), ld(1), ld(2), ld(3)));
+    if constexpr (OP == 11) st(0, fp_mul2_lazy<FqParams, true, true>(ld(0), ld(1), ld(2), ld(3)));
+    if constexpr (OP == 3) st(0, F::sub_kp<2>(ld(0), ld(1)));
+    if constexpr (OP == 4) st(0, F::sub_kp<4>(ld(0), ld(1)));
+    if constexpr (OP == 5) st(0, F::sub_kp<6>(ld(0), ld(1)));
+    if constexpr (OP == 6) st(0, F::x3_l(ld(0), ld(1), ld(2)));
+    if constexpr (OP == 7) st(0, F::canon(ld(0)));
+    if constexpr (OP == 8) st(0, F::kp_minus<1>(ld(0)));
+    if constexpr (OP == 9) st(0, fp_neg5_almost<FqParams>(ld(0)));
+    if constexpr (OP == 10) st8(xyzz_madd_lazy<F>(XYZZ<F>{ld(0), ld(1), ld(2), ld(3)}, Affine<F>{ld(4), ld(5)}));
+    if constexpr (OP == 12) st8(xyzz_add_lazy<F>(XYZZ<F>{ld(0), ld(1), ld(2), ld(3)}, XYZZ<F>{ld(4), ld(5), ld(6), ld(7)}));
+}
+
+// Fr, op numbering of zk_fr_lazy_raw; element k of a case at words [9 k, +9)
+template <int OP>
+__global__ void __launch_bounds__(64) k_diag_fr_lazy(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int nin, int nout) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t* w = in + (size_t)c * nin * 9;
+    uint32_t* o = out + (size_t)c * nout * 9;
+    auto ld = [&](int k) { Fr a; for (int i = 0; i < 9; i++) a.l[i] = w[k * 9 + i]; return a; };
+    auto st = [&](int k, const Fr& a) { for (int i = 0; i < 9; i++) o[k * 9 + i] = a.l[i]; };
+    if constexpr (OP == 0) st(0, frl_reduce(ld(0)));
+    if constexpr (OP == 1) st(0, frl_norm(ld(0)));
+    if constexpr (OP == 2) st(0, frl_sub<2>(ld(0), ld(1)));
+    if constexpr (OP == 3) st(0, frl_sub<3>(ld(0), ld(1)));
+    if constexpr (OP == 4) st(0, frl_sub<5>(ld(0), ld(1)));
+    if constexpr (OP == 5) st(0, frl_mul(ld(0), ld(1)));
+    if constexpr (OP == 6) st(0, frl_canon(ld(0)));
+    if constexpr (OP == 7 || OP == 8) {
+        Fr x0 = ld(0), x1 = ld(1), x2 = ld(2), x3 = ld(3);
+        frl_radix4<OP == 7>(x0, x1, x2, x3, ld(4), ld(5), ld(6));
+        st(0, x0); st(1, x1); st(2, x2); st(3, x3);
+    }
+    if constexpr (OP == 9) { Fr x0 = ld(0), x1 = ld(1); frl_radix2(x0, x1, ld(2)); st(0, x0); st(1, x1); }
+    if constexpr (OP == 10) st(0, fr_mul32(ld(0)));
+}
+
+#define ZK_DIAG_CASE(KERN, N) case N: hipLaunchKernelGGL(KERN<N>, blocks, 64, 0, st, in, out, nin, nout); break;
+void launch_fq_lazy(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes, int nin, int nout) {
+    const unsigned blocks = lanes / 64;
+    switch (op) {
+        ZK_DIAG_CASE(k_diag_fq_lazy, 0) ZK_DIAG_CASE(k_diag_fq_lazy, 1) ZK_DIAG_CASE(k_diag_fq_lazy, 2) ZK_DIAG_CASE(k_diag_fq_lazy, 3)
+        ZK_DIAG_CASE(k_diag_fq_lazy, 4) ZK_DIAG_CASE(k_diag_fq_lazy, 5) ZK_DIAG_CASE(k_diag_fq_lazy, 6) ZK_DIAG_CASE(k_diag_fq_lazy, 7)
+        ZK_DIAG_CASE(k_diag_fq_lazy, 8) ZK_DIAG_CASE(k_diag_fq_lazy, 9) ZK_DIAG_CASE(k_diag_fq_lazy, 10) ZK_DIAG_CASE(k_diag_fq_lazy, 11)
+        ZK_DIAG_CASE(k_diag_fq_lazy, 12)
+        default: break;
+    }
+}
+void launch_fr_lazy(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes, int nin, int nout) {
+    const unsigned blocks = lanes / 64;
+    switch (op) {
+        ZK_DIAG_CASE(k_diag_fr_lazy, 0) ZK_DIAG_CASE(k_diag_fr_lazy, 1) ZK_DIAG_CASE(k_diag_fr_lazy, 2) ZK_DIAG_CASE(k_diag_fr_lazy, 3)
+        ZK_DIAG_CASE(k_diag_fr_lazy, 4) ZK_DIAG_CASE(k_diag_fr_lazy, 5) ZK_DIAG_CASE(k_diag_fr_lazy, 6) ZK_DIAG_CASE(k_diag_fr_lazy, 7)
+        ZK_DIAG_CASE(k_diag_fr_lazy, 8) ZK_DIAG_CASE(k_diag_fr_lazy, 9) ZK_DIAG_CASE(k_diag_fr_lazy, 10)
+        default: break;
+    }
+}
+#undef ZK_DIAG_CASE
+
+// elements in / out per case and lanes per case, by op (0 0 = no such op)
+struct DiagShape { int nin, nout, lanes; };
+constexpr DiagShape FQ_SHAPES[] = {{2, 1, 1}, {1, 1, 1}, {4, 1, 1}, {2, 1, 1}, {2, 1, 1}, {2, 1, 1}, {3, 1, 1},
+                                   {1, 1, 1}, {1, 1, 1}, {1, 1, 1}, {6, 8, 1}, {4, 1, 1}, {8, 8, 1}};
+constexpr DiagShape FR_SHAPES[] = {{1, 1, 1}, {1, 1, 1}, {2, 1, 1}, {2, 1, 1}, {2, 1, 1}, {2, 1, 1}, {1, 1, 1},
+                                   {7, 4, 1}, {7, 4, 1}, {3, 2, 1}, {1, 1, 1}};
+// ops 0 - 6: Fq2 elements (two components of 13 words) on lane pairs / quads; 7, 8: G1 (Fq elements) on lane pairs
+constexpr DiagShape PAIR_SHAPES[] = {{2, 1, 2}, {2, 1, 2}, {2, 1, 2}, {6, 8, 2}, {2, 4, 2}, {8, 8, 4}, {6, 8, 4}, {8, 8, 2}, {6, 8, 2}};
+constexpr DiagShape F7_SHAPES[] = {{1, 1, 1}, {2, 1, 1}, {2, 1, 1}, {2, 1, 1}, {2, 1, 1}, {1, 1, 1}, {2, 2, 1}, {3, 2, 1}, {1, 1, 1}};
+constexpr size_t DIAG_MAX_CASES = (size_t)1 << 20;
+
+// pads the case array to whole waves (all-zero cases), runs one launch, copies the n_cases results back
+template <class Launch>
+int diag_batch(zk_ctx* ctx, const DiagShape& sh, int words, const uint32_t* in, uint32_t* out, size_t n_cases, Launch launch) {
+    const size_t lanes = (n_cases * sh.lanes + 63) / 64 * 64, padded = lanes / sh.lanes;
+    const size_t in_w = (size_t)sh.nin * words, out_w = (size_t)sh.nout * words;
+    uint32_t *din, *dout;
+    ZK_TRY(zk_scratch(ctx, "diag_lazy_in", padded * in_w * 4, (void**)&din));
+    ZK_TRY(zk_scratch(ctx, "diag_lazy_out", padded * out_w * 4, (void**)&dout));
+    ZK_HIP(ctx, hipMemsetAsync(din, 0, padded * in_w * 4, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(din, in, n_cases * in_w * 4, hipMemcpyHostToDevice, ctx->stream));
+    launch(ctx->stream, din, dout, (unsigned)lanes);
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipMemcpyAsync(out, dout, n_cases * out_w * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+
+}  // namespace
+
+extern "C" int zk_diag_fq_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n_cases) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !in || !out || op < 0 || op > 12 || n_cases < 1 || n_cases > DIAG_MAX_CASES) return ZK_ERR_ARG;
+    const DiagShape sh = FQ_SHAPES[op];
+    return diag_batch(ctx, sh, FqParams::L, in, out, n_cases, [&](hipStream_t st, const uint32_t* i, uint32_t* o, unsigned lanes) {
+        launch_fq_lazy(st, op, i, o, lanes, sh.nin, sh.nout);
+    });
+    ZK_API_END
+}
+extern "C" int zk_diag_fr_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n_cases) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !in || !out || op < 0 || op > 10 || n_cases < 1 || n_cases > DIAG_MAX_CASES) return ZK_ERR_ARG;
+    const DiagShape sh = FR_SHAPES[op];
+    return diag_batch(ctx, sh, 9, in, out, n_cases, [&](hipStream_t st, const uint32_t* i, uint32_t* o, unsigned lanes) {
+        launch_fr_lazy(st, op, i, o, lanes, sh.nin, sh.nout);
+    });
+    ZK_API_END
+}
+extern "C" int zk_diag_fq2_pair_dev(zk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n_cases) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !in || !out || op < 0 || op > 8 || n_cases < 1 || n_cases > DIAG_MAX_CASES) return ZK_ERR_ARG;
+    const DiagShape sh = PAIR_SHAPES[op];
+    return diag_batch(ctx, sh, op <= 6 ? 2 * FqParams::L : FqParams::L, in, out, n_cases,
+                      [&](hipStream_t st, const uint32_t* i, uint32_t* o, unsigned lanes) {
+                          if (op <= 6) zk_diag_launch_fq2_pair(st, op, i, o, lanes);
+                          else zk_diag_launch_g1_dual(st, op, i, o, lanes);
+                      });
+    ZK_API_END
+}
+extern "C" int zk_diag_f7l_dev(zk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n_cases) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !in || !out || op < 0 || op > 8 || n_cases < 1 || n_cases > DIAG_MAX_CASES) return ZK_ERR_ARG;
+    return diag_batch(ctx, F7_SHAPES[op], 26, in, out, n_cases, [&](hipStream_t st, const uint32_t* i, uint32_t* o, unsigned lanes) {
+        zk_diag_launch_f7l(st, op, i, o, lanes);
+    });
     ZK_API_END
 }

@@ -193,6 +193,11 @@ int zk_msm_early_finish(zk_ctx* ctx, ZkEarlyMsm* em, void* const* outs);      //
 // msm_g2pair.hip: the G2 accumulate kernel with two lanes per point addition
 void zk_launch_accum_g2pair(hipStream_t st, size_t segments, const uint32_t* bases, const uint32_t* sorted, const void* desc,
                             const uint32_t* order, const uint32_t* ctr, uint32_t* sums, bool quads);
+// test hooks (diag.hip): one small launch over a padded case array, the real device functions of the file that defines it.
+// `lanes` is a whole number of waves; in / out hold in_w / out_w words per case (diag.hip documents the layouts).
+void zk_diag_launch_fq2_pair(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes);   // msm_g2pair.hip
+void zk_diag_launch_g1_dual(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes);    // msm.hip
+void zk_diag_launch_f7l(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes);        // she.hip
 struct ZkG2PairReduce {   // the arguments of msm.hip's reduce chain
     const void *heavy, *heavy2; const uint32_t* ctr; uint32_t* done;
     uint32_t *sums, *rowP, *colP, *bits;

@@ -1629,6 +1629,29 @@ int msm_host_t(zk_ctx* ctx, const void* bases_host, size_t nb, const ZkAffineLay
     return msm_table_run_t<F>(ctx, host_table(group, bases_host, layout), nu, 1, sc, n, outs, scalars_fingerprint(scalars, n));
 }
 
+
+// ---- test hook (diag.hip: zk_diag_fq2_pair_dev ops 7, 8): the G1 pair form of ec_dual.cuh on a case array, one case per lane pair,
+// both lanes reading the whole case.  Element k at words [13 k, +13), raw 29-bit limbs.  The host pads the array to whole waves with
+// all-zero cases: every lane runs and no DPP partner is ever inactive.  The even lane stores.
+//   7: xyzz_add_dual<G1DualOps>(a[4], b[4]) -> 4, then canonical (the fold's form)            in 8, out 8
+//   8: xyzz_madd_dual<G1DualOps>(acc[4], q[2]) -> 4, then canonical (k_accum_group<DUAL>)      in 6, out 8
+template <int OP>
+__global__ void __launch_bounds__(64) k_diag_g1_dual(const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    using F = G1Field;
+    constexpr int NIN = OP == 7 ? 8 : 6, L = FqParams::L;
+    const uint32_t c = (blockIdx.x * blockDim.x + threadIdx.x) / 2;
+    const uint32_t* w = in + (size_t)c * NIN * L;
+    uint32_t* o = out + (size_t)c * 8 * L;
+    auto ld = [&](int k) { Fq a; for (int i = 0; i < L; i++) a.l[i] = w[k * L + i]; return a; };
+    XYZZ<F> r;
+    if constexpr (OP == 7) r = xyzz_add_dual<G1DualOps, XYZZ<F>>(XYZZ<F>{ld(0), ld(1), ld(2), ld(3)}, XYZZ<F>{ld(4), ld(5), ld(6), ld(7)});
+    else r = xyzz_madd_dual<G1DualOps, XYZZ<F>, Affine<F>>(XYZZ<F>{ld(0), ld(1), ld(2), ld(3)}, Affine<F>{ld(4), ld(5)});
+    if (G1DualOps::hi()) return;
+    const Fq v[8] = {r.x, r.y, r.zz, r.zzz, F::canon(r.x), F::canon(r.y), F::canon1(r.zz), F::canon1(r.zzz)};
+    for (int k = 0; k < 8; k++)
+        for (int i = 0; i < L; i++) o[k * L + i] = v[k].l[i];
+}
+
 }  // namespace
 
 // ---- phase timer ----
@@ -1892,4 +1915,9 @@ extern "C" int zk_msm_g2_dev(zk_ctx* ctx, const zk_bases* bases, size_t off, con
     if (!ctx || !bases || !out || bases->group != 2 || (n && !scalars)) return ZK_ERR_ARG;
     return msm_run_t<G2Field>(ctx, bases, off, scalars, n, out);
     ZK_API_END
+}
+
+void zk_diag_launch_g1_dual(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes) {
+    if (op == 7) hipLaunchKernelGGL(k_diag_g1_dual<7>, lanes / 64, 64, 0, st, in, out);
+    if (op == 8) hipLaunchKernelGGL(k_diag_g1_dual<8>, lanes / 64, 64, 0, st, in, out);
 }

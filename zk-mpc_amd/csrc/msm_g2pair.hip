@@ -71,8 +71,11 @@ __device__ __forceinline__ Fq mulp(const Left& A, const Fq& b, bool odd) {
     return fp_mul2<FqParams, true>(A.p, b, A.q, xchg(b));
 }
 
+// lazy domain: no final subtraction, result < (p b + q b') / RI + p -- below p + eps for the products of madd_p_lazy except the odd
+// lane of P^2 (four operands up to 7p + eps: below p + 1.09 eps); every product is below p + 2 eps, the range the column bounds of
+// tests/test_abi.py::test_lazy_domain_column_bounds assume for a product operand
 template <bool TOPSPLIT = false>
-__device__ __forceinline__ Fq mulp_l(const Left& A, const Fq& b) {     // lazy domain: no final subtraction, result < p + eps
+__device__ __forceinline__ Fq mulp_l(const Left& A, const Fq& b) {
     return fp_mul2_lazy<FqParams, TOPSPLIT, true>(A.p, b, A.q, xchg(b));
 }
 
@@ -456,6 +459,44 @@ struct RedG2Quad {
 };
 constexpr size_t RED_QUAD_MAX_BUCKETS = (size_t)1 << 14;      // (measured: 2^13 buckets 0.41 -> 0.31 ms of chain, 2^15 nothing)
 
+
+// ---- test hook (diag.hip: zk_diag_fq2_pair_dev): the functions above on a case array, one case per lane pair (ops 0 - 4) or
+// lane quad (5, 6).  Element k of a case is an Fq2 value: component c at words [(2k + c) 13, +13), raw 29-bit limbs (the top one
+// may be wide).  The host pads the array to whole waves with all-zero cases, so every lane runs and no DPP partner is ever inactive.
+//   0: mulp(a, b)   1: mulp_l<false>(a, b)   2: mulp_l<true>(a, b)                                               in 2, out 1
+//   3: madd_p_lazy(acc[4], q[2]) -> 4, then its canonical form as k_accum_g2pair stores it                     in 6, out 8
+//   4: dbl_affine_p(q[2])                                                                                        in 2, out 4
+//   5: xyzz_add_dual<G2QuadOps>(a[4], b[4]) -> 4, then canonical (the fold's form)                             in 8, out 8
+//   6: xyzz_madd_dual<G2QuadBase>(acc[4], q[2]) -> 4, then canonical (k_accum_g2pair<4>)                       in 6, out 8
+template <int OP>
+__global__ void __launch_bounds__(64) k_diag_fq2_pair(const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    constexpr int G = OP >= 5 ? 4 : 2;
+    constexpr int NIN = OP == 3 || OP == 6 ? 6 : OP == 5 ? 8 : 2;
+    constexpr int NOUT = OP <= 2 ? 1 : OP == 4 ? 4 : 8;
+    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, c = lane / G, oddw = lane & 1u;
+    const bool odd = oddw != 0;
+    const uint32_t* w = in + (size_t)c * NIN * 2 * L;
+    uint32_t* o = out + (size_t)c * NOUT * 2 * L;
+    auto ld = [&](int k) { Fq a; for (int i = 0; i < L; i++) a.l[i] = w[(2 * k + oddw) * L + i]; return a; };
+    auto st = [&](int k, const Fq& a) { for (int i = 0; i < L; i++) o[(2 * k + oddw) * L + i] = a.l[i]; };
+    auto st8 = [&](const XyzzP& r) {
+        st(0, r.x); st(1, r.y); st(2, r.zz); st(3, r.zzz);
+        st(4, B::canon(r.x)); st(5, B::canon(r.y)); st(6, B::canon1(r.zz)); st(7, B::canon1(r.zzz));
+    };
+    if constexpr (OP == 0) st(0, mulp(prep(ld(0), odd), ld(1), odd));
+    if constexpr (OP == 1) st(0, mulp_l<false>(prep(ld(0), odd), ld(1)));
+    if constexpr (OP == 2) st(0, mulp_l<true>(prep(ld(0), odd), ld(1)));
+    if constexpr (OP == 3) st8(madd_p_lazy(XyzzP{ld(0), ld(1), ld(2), ld(3)}, AffP{ld(4), ld(5)}, odd));
+    if constexpr (OP == 4) { const XyzzP r = dbl_affine_p(AffP{ld(0), ld(1)}, odd); st(0, r.x); st(1, r.y); st(2, r.zz); st(3, r.zzz); }
+    if constexpr (OP == 5) {
+        const XP r = xyzz_add_dual<G2QuadOps, XP>(XP{ld(0), ld(1), ld(2), ld(3)}, XP{ld(4), ld(5), ld(6), ld(7)});
+        if (!G2QuadOps::hi()) st8(XyzzP{r.x, r.y, r.zz, r.zzz});
+    }
+    if constexpr (OP == 6) {
+        const XyzzP r = xyzz_madd_dual<G2QuadBase, XyzzP, AffP>(XyzzP{ld(0), ld(1), ld(2), ld(3)}, AffP{ld(4), ld(5)});
+        if (!G2QuadBase::hi()) st8(r);
+    }
+}
 }  // namespace
 
 // One pair of lanes per segment: `segments` logical threads.
@@ -494,4 +535,18 @@ int zk_launch_reduce_g2pair(zk_ctx* ctx, hipStream_t st, const ZkG2PairReduce& a
                        a.bits, gg);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
+}
+
+void zk_diag_launch_fq2_pair(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes) {
+    const unsigned blocks = lanes / 64;
+    switch (op) {
+        case 0: hipLaunchKernelGGL(k_diag_fq2_pair<0>, blocks, 64, 0, st, in, out); break;
+        case 1: hipLaunchKernelGGL(k_diag_fq2_pair<1>, blocks, 64, 0, st, in, out); break;
+        case 2: hipLaunchKernelGGL(k_diag_fq2_pair<2>, blocks, 64, 0, st, in, out); break;
+        case 3: hipLaunchKernelGGL(k_diag_fq2_pair<3>, blocks, 64, 0, st, in, out); break;
+        case 4: hipLaunchKernelGGL(k_diag_fq2_pair<4>, blocks, 64, 0, st, in, out); break;
+        case 5: hipLaunchKernelGGL(k_diag_fq2_pair<5>, blocks, 64, 0, st, in, out); break;
+        case 6: hipLaunchKernelGGL(k_diag_fq2_pair<6>, blocks, 64, 0, st, in, out); break;
+        default: break;
+    }
 }

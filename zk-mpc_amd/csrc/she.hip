@@ -106,6 +106,8 @@ __device__ __forceinline__ F7 f7l_canon(const F7& a) {
     const F7 t = fp_reduce_once<Fq753Params>(a.l);
     return fp_reduce_once<Fq753Params>(t.l);
 }
+// -v of the pointwise products (k_she_inv_tile): v < 2.01 q -> 3 q - v reduced, < 2.01 q
+__device__ __forceinline__ F7 f7l_negate(const F7& v) { return f7l_red(f7l_sub<3>(fp_zero<Fq753Params>(), v)); }
 
 // limb-major table of n elements (internal form)
 __device__ __forceinline__ F7 tab_load(const uint32_t* tab, uint32_t n, uint32_t i) {
@@ -257,7 +259,7 @@ __global__ void __launch_bounds__(TILE_THREADS) k_she_inv_tile(InvArgs a, const 
             if (a.x1.base)
                 v = f7l_add(v, f7l_mul(f7_load(a.x1.base, row_elem(a.x1, n, row, j)), f7_load(a.y1.base, row_elem(a.y1, n, row, j))));
             v = f7l_red(v);
-            if (a.negate) v = f7l_red(f7l_sub<3>(fp_zero<Fq753Params>(), v));
+            if (a.negate) v = f7l_negate(v);
             lds_put(lds, l, v);
         }
     }
@@ -549,6 +551,30 @@ int she_schoolbook(zk_ctx* ctx, RowMap x0, RowMap y0, RowMap x1, RowMap y1, RowM
     return ZK_OK;
 }
 
+// ---- test hook (diag.hip: zk_diag_f7l_dev): the lazy-domain functions above on a case array, one case per lane; element k of a
+// case at words [26 k, +26), raw 29-bit limbs (any u32).  The host pads the array to whole waves with all-zero cases.
+//   0: f7l_red(a)  1: f7l_add(a, b)  2: f7l_sub<2>(a, b)  3: f7l_sub<3>(a, b)  4: f7l_mul(a, b)  5: f7l_canon(a)
+//   6: the forward butterfly of k_she_fwd_* on U and V = x[j+t] S -> lo, hi   7: the inverse butterfly of k_she_inv_* -> lo, hi
+//   8: f7l_negate(v)
+template <int OP>
+__global__ void __launch_bounds__(64) k_diag_f7l(const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    constexpr int NIN = OP == 0 || OP == 5 || OP == 8 ? 1 : OP == 7 ? 3 : 2, NOUT = OP >= 6 && OP <= 7 ? 2 : 1;
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t* w = in + (size_t)c * NIN * L7;
+    uint32_t* o = out + (size_t)c * NOUT * L7;
+    auto ld = [&](int k) { F7 a; for (int i = 0; i < L7; i++) a.l[i] = w[k * L7 + i]; return a; };
+    auto st = [&](int k, const F7& a) { for (int i = 0; i < L7; i++) o[k * L7 + i] = a.l[i]; };
+    if constexpr (OP == 0) st(0, f7l_red(ld(0)));
+    if constexpr (OP == 1) st(0, f7l_add(ld(0), ld(1)));
+    if constexpr (OP == 2) st(0, f7l_sub<2>(ld(0), ld(1)));
+    if constexpr (OP == 3) st(0, f7l_sub<3>(ld(0), ld(1)));
+    if constexpr (OP == 4) st(0, f7l_mul(ld(0), ld(1)));
+    if constexpr (OP == 5) st(0, f7l_canon(ld(0)));
+    if constexpr (OP == 6) { const F7 U = ld(0), V = ld(1); st(0, f7l_red(f7l_add(U, V))); st(1, f7l_red(f7l_sub<2>(U, V))); }
+    if constexpr (OP == 7) { const F7 U = ld(0), V = ld(1); st(0, f7l_red(f7l_add(U, V))); st(1, f7l_mul(f7l_red(f7l_sub<3>(U, V)), ld(2))); }
+    if constexpr (OP == 8) st(0, f7l_negate(ld(0)));
+}
+
 int check_n(zk_ctx* ctx, size_t n, const char* who) {
     if (n == 0 || n > ((size_t)1 << SHE_MAX_LOG)) {
         ctx->last_error = std::string(who) + ": degree must be in 1..2^14 (2N <= 2^15, the 2-adicity of the MNT4-753 base field)";
@@ -763,4 +789,20 @@ extern "C" int zk_she_decode_dev(zk_ctx* ctx, const void* enc, void* out_fr, siz
     for (size_t b = 0; b < batch && log_n; b++) ZK_TRY(zk_ntt_launch(ctx, (char*)out_fr + b * n * 32, log_n, 0, 0));
     return ZK_OK;
     ZK_API_END
+}
+
+void zk_diag_launch_f7l(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes) {
+    const unsigned blocks = lanes / 64;
+    switch (op) {
+        case 0: hipLaunchKernelGGL(k_diag_f7l<0>, blocks, 64, 0, st, in, out); break;
+        case 1: hipLaunchKernelGGL(k_diag_f7l<1>, blocks, 64, 0, st, in, out); break;
+        case 2: hipLaunchKernelGGL(k_diag_f7l<2>, blocks, 64, 0, st, in, out); break;
+        case 3: hipLaunchKernelGGL(k_diag_f7l<3>, blocks, 64, 0, st, in, out); break;
+        case 4: hipLaunchKernelGGL(k_diag_f7l<4>, blocks, 64, 0, st, in, out); break;
+        case 5: hipLaunchKernelGGL(k_diag_f7l<5>, blocks, 64, 0, st, in, out); break;
+        case 6: hipLaunchKernelGGL(k_diag_f7l<6>, blocks, 64, 0, st, in, out); break;
+        case 7: hipLaunchKernelGGL(k_diag_f7l<7>, blocks, 64, 0, st, in, out); break;
+        case 8: hipLaunchKernelGGL(k_diag_f7l<8>, blocks, 64, 0, st, in, out); break;
+        default: break;
+    }
 }
