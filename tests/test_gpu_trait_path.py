@@ -565,3 +565,61 @@ def test_the_h_msm_started_at_the_end_of_the_transform(ctx, log_n):
     assert _spec_stats(ctx)["taken"] > s2["taken"]
     ctx._ck(ctx.lib.zk_bases_cache_drop(ctx.h))
     ctx._ck(ctx.lib.zk_bases_cache_config(ctx.h, 64 << 30, 1))
+
+
+def test_builder_slices_beside_captures_of_the_side_stream(ctx):
+    """The table cache's builder thread launches its slices on the context's side stream, on which the calling thread captures the
+    sorts of the MSMs started ahead (core.hip: zk_graph_run).  A 2^17-point table earns its window multiples (built by the thread,
+    not inline); then ~2 s of small MSMs with no gap of 0.3 ms, two tables taking turns over one scalar vector (jobs started ahead on
+    the side stream) and the vector length moving every few rounds (new sort keys captured there), so that the builder only works
+    through its 50 ms starvation path, in the middle of calls.  Every call succeeds with the right sum, and the big table then has
+    its multiples and the right sum from them.  A guard against regressions; what rules the overlap out is the side stream's lock
+    (ctx.hpp)."""
+    import time
+    rng = O.Prng(9090)
+    ctx._ck(ctx.lib.zk_bases_cache_drop(ctx.h))
+    ctx._ck(ctx.lib.zk_bases_cache_config(ctx.h, 64 << 30, 1))
+    ctx._ck(ctx.lib.zk_bases_cache_trust(ctx.h, 0))
+    ctx._ck(ctx.lib.zk_msm_speculate(ctx.h, 1))
+
+    def table(n):
+        ks = [rng.fr() for _ in range(n)]
+        dk = ctx.upload(cv.fr_to_mont(ks))
+        tb = ctx.fixed_base(dk.ptr, n, 1, cv.fr_to_mont([1])[0])
+        pts = np.ascontiguousarray(tb.download())
+        tb.free(); dk.free()
+        return ks, pts
+
+    big_ks, big = table(1 << 17)
+    tabs = [table(8192), table(8192)]          # with multiples (c = 15, W = 17): sorts of > 2^16 / 17 scalars take the graph path
+    # four scalar patterns: 4096 random scalars, then zeros up to whatever length the round uses (one expected sum per pattern)
+    M, N0 = 4096, 4608
+    pats = [[rng.fr() for _ in range(M)] for _ in range(4)]
+    vecs = [cv.fr_to_mont(p + [0] * 8192) for p in pats]
+    want = [[O.g1_mul(O.G1_GEN, sum(s * k for s, k in zip(p, ks[:M])) % O.R_MOD) for ks, _ in tabs] for p in pats]
+    sc = [rng.fr() for _ in range(1 << 17)]
+    big_scal = cv.fr_to_mont(sc)
+    big_want = O.g1_mul(O.G1_GEN, sum(s * k for s, k in zip(sc, big_ks)) % O.R_MOD)
+    for _ in range(2):                                             # upload, then the hit that starts the build on the thread
+        assert cv.g1_projective_to_affine(ctx.multi_scalar_mul_g1(big, big_scal)) == big_want
+    assert _stats2(ctx)["building"] == 1
+    b0, s0 = _stats2(ctx), _spec_stats(ctx)
+    got = []
+    t0 = time.monotonic()
+    rnd = 0
+    while time.monotonic() - t0 < 2.0:
+        n = N0 + (rnd // 3 * 97) % (8192 - N0 + 1)
+        p = rnd % len(vecs)
+        for k in (0, 1):
+            got.append((p, k, n, ctx.multi_scalar_mul_g1(tabs[k][1], vecs[p][:n])))
+        rnd += 1
+    for p, k, n, g in got:
+        assert cv.g1_projective_to_affine(g) == want[p][k], "round pattern %d, table %d, %d scalars" % (p, k, n)
+    s1 = _spec_stats(ctx)
+    assert s1["started"] > s0["started"] and s1["taken"] > s0["taken"], (s0, s1)
+    ctx._ck(ctx.lib.zk_bases_cache_sync(ctx.h))
+    b1, st = _stats2(ctx), _stats(ctx)
+    assert b1["building"] == 0 and b1["builds"] > b0["builds"] and st["pre"] == 3 and st["entries"] == 3, (b0, b1, st)
+    assert cv.g1_projective_to_affine(ctx.multi_scalar_mul_g1(big, big_scal)) == big_want
+    ctx._ck(ctx.lib.zk_bases_cache_drop(ctx.h))
+    ctx._ck(ctx.lib.zk_bases_cache_config(ctx.h, 64 << 30, 1))

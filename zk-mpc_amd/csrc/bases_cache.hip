@@ -52,6 +52,81 @@ struct CacheEntry {
     size_t bytes;
 };
 
+// The builder: a thread that hands one build's slices to the context's side stream one at a time, each while no library call is in
+// flight on the device (the caller's own time between two calls), and waits for it before it looks again.  Its operations are
+// called from the caller's thread only; the slices are launched and waited for under ctx->side_mu (the side stream's rule: ctx.hpp).
+class Builder {
+    std::thread th;
+    std::mutex m;
+    std::condition_variable cv;
+    ZkPrecompJob* job = nullptr;          // the build in progress (written by the caller's thread only)
+    size_t need = 0;                      // the bytes it was budgeted
+    bool done = true, stop = false;       // (under m)
+    std::atomic<bool> cancelled{false}, rush{false};
+
+    void run(zk_ctx* ctx, hipStream_t st) {
+        (void)hipSetDevice(ctx->device);
+        std::unique_lock<std::mutex> lk(m);
+        for (;;) {
+            cv.wait(lk, [&] { return stop || !done; });
+            if (stop) return;
+            ZkPrecompJob* j = job;
+            lk.unlock();
+            bool more = true;
+            while (more && !cancelled.load()) {
+                // a gap: no entry point executing on this context, and none for the last 0.3 ms (the calls of a burst are microseconds
+                // apart; a slice handed out between two of them would run under the second).  A caller that never leaves the library
+                // still gets its tables -- one slice (~1 ms of kernels) per 50 ms of waiting -- and zk_bases_cache_sync (rush) takes
+                // them at full speed.
+                // (Tables of up to 2^16 points never come here: advance_builds builds them in the call that earns them.)
+                const auto t0 = std::chrono::steady_clock::now();
+                while (!ctx->activity->quiet_for(300000) && !rush.load() && !cancelled.load() &&
+                       std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(50))
+                    std::this_thread::sleep_for(std::chrono::microseconds(50));
+                // one slice at a time, waited for: the next look at the context's activity comes after it
+                std::lock_guard<std::mutex> side(ctx->side_mu);
+                hipError_t e = zk_bases_precompute_step(j, st, &more);
+                if (e == hipSuccess) e = hipStreamSynchronize(st);
+                if (e != hipSuccess) { j->err = e; (void)hipGetLastError(); break; }
+            }
+            lk.lock();
+            done = true;
+            cv.notify_all();
+        }
+    }
+
+   public:
+    ~Builder() {
+        if (job) zk_bases_precompute_finish(collect(true), false);
+        { std::lock_guard<std::mutex> lk(m); stop = true; }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+    }
+    const zk_bases* table() const { return job ? job->b : nullptr; }
+    size_t bytes() const { return job ? need : 0; }
+    // `j` goes to the thread (started on first use) to be built on `side`.  false: no thread to be had, the job stays the caller's
+    bool start(zk_ctx* c, hipStream_t side, ZkPrecompJob* j, size_t bytes) {
+        std::lock_guard<std::mutex> lk(m);
+        if (!th.joinable()) try { th = std::thread([this, c, side] { run(c, side); }); } catch (const std::system_error&) { return false; }
+        job = j; need = bytes; done = false;
+        cv.notify_all();
+        return true;
+    }
+    bool finished() { std::lock_guard<std::mutex> lk(m); return done; }
+    // the build in progress comes to an end (finished, or cancelled) and the builder is idle again; the job is the caller's
+    ZkPrecompJob* collect(bool cancel) {
+        if (!job) return nullptr;
+        if (cancel) cancelled.store(true);
+        rush.store(true);
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return done; });
+        rush.store(false); cancelled.store(false);
+        ZkPrecompJob* j = job;
+        job = nullptr;
+        return j;
+    }
+};
+
 struct ZkBasesCache {
     std::vector<CacheEntry> e;
     size_t budget = 0;            // 0 until the first use: then a quarter of the device memory
@@ -61,16 +136,7 @@ struct ZkBasesCache {
     uint64_t tick = 0;
     uint64_t hits = 0, misses = 0, evictions = 0, uploaded = 0, replaced = 0, uncached = 0;
     uint64_t verified = 0, verified_bytes = 0, builds = 0;
-    ZkPrecompJob* building = nullptr;     // at most one table's multiples under construction
-    size_t building_bytes = 0;
-    hipStream_t pre_stream = nullptr;
-    // the builder: a thread that hands the build's slices to pre_stream one at a time, each while no library call is in flight on
-    // the device (the caller's own time between two calls), and waits for it before it looks again
-    std::thread builder;
-    std::mutex bm;
-    std::condition_variable bcv, bcv_done;
-    bool bstop = false;
-    std::atomic<bool> build_done{true}, bcancel{false}, rush{false};
+    Builder builder;                      // at most one table's multiples under construction
     uint32_t* flag_dev = nullptr;         // verification: set by k_words_differ
     uint32_t* flag_host = nullptr;        // page-locked
     const zk_bases* leased = nullptr;     // the table the call in progress runs on: never evicted under it
@@ -177,64 +243,15 @@ ZkBasesCache* cache_of(zk_ctx* ctx) {
 }
 
 size_t resident(const ZkBasesCache* c) {
-    size_t s = c->building_bytes;
+    size_t s = c->builder.bytes();
     for (auto& x : c->e) s += x.bytes;
     return s;
-}
-
-void builder_main(zk_ctx* ctx, ZkBasesCache* c) {
-    (void)hipSetDevice(ctx->device);
-    std::unique_lock<std::mutex> lk(c->bm);
-    for (;;) {
-        c->bcv.wait(lk, [&] { return c->bstop || (c->building && !c->build_done.load()); });
-        if (c->bstop) return;
-        ZkPrecompJob* j = c->building;
-        lk.unlock();
-        bool more = true;
-        while (more && !c->bcancel.load()) {
-            // a gap: no entry point executing on this context, and none for the last 0.3 ms (the calls of a burst are microseconds
-            // apart; a slice handed out between two of them would run under the second).  A caller that never leaves the library
-            // still gets its tables -- one slice (~1 ms of kernels) per 50 ms of waiting -- and zk_bases_cache_sync (rush) takes
-            // them at full speed.
-            // (Tables of up to 2^16 points never come here: advance_builds builds them in the call that earns them.)
-            const auto t0 = std::chrono::steady_clock::now();
-            while (!ctx->activity->quiet_for(300000) && !c->rush.load() && !c->bcancel.load() &&
-                   std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(50))
-                std::this_thread::sleep_for(std::chrono::microseconds(50));
-            // one slice at a time, waited for: the next look at the context's activity comes after it
-            hipError_t e = zk_bases_precompute_step(j, c->pre_stream, &more);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->pre_stream);
-            if (e != hipSuccess) { j->err = e; (void)hipGetLastError(); break; }
-        }
-        lk.lock();
-        c->build_done.store(true);
-        c->bcv_done.notify_all();
-    }
-}
-
-// the build in progress comes to an end (finished, or cancelled) and the builder is idle again; the job is the caller's
-ZkPrecompJob* builder_collect(ZkBasesCache* c, bool cancel) {
-    if (!c->building) return nullptr;
-    if (cancel) c->bcancel.store(true);
-    c->rush.store(true);
-    {
-        std::unique_lock<std::mutex> lk(c->bm);
-        c->bcv_done.wait(lk, [&] { return c->build_done.load(); });
-    }
-    c->rush.store(false);
-    c->bcancel.store(false);
-    std::lock_guard<std::mutex> lk(c->bm);                  // (the builder reads `building` in its wait predicate)
-    ZkPrecompJob* j = c->building;
-    c->building = nullptr;
-    c->building_bytes = 0;
-    return j;
 }
 
 // a table of the cache (or one made for a single call) goes: nothing of a proving key's presort points into it, and every MSM
 // over it has been collected (the entry points are synchronous) -- no presort to drop, no stream to wait for
 void free_table(zk_ctx* ctx, ZkBasesCache* c, zk_bases* b, uint32_t* raw) {
-    if (c && c->building && c->building->b == b)            // its multiples are being built: stop, throw them away
-        (void)zk_bases_precompute_finish(ctx, builder_collect(c, true), false);
+    if (c && b && c->builder.table() == b) zk_bases_precompute_finish(c->builder.collect(true), false);   // its multiples: stop, throw them away
     if (b) zk_msm_spec_forget(ctx, b);                      // (a job started ahead over this table, a learned succession through it)
     if (raw) (void)hipFree(raw);
     if (b) {
@@ -264,13 +281,12 @@ void make_room(zk_ctx* ctx, ZkBasesCache* c, size_t need, const zk_bases* keep, 
 // a finished build is published; then the next table that has earned its multiples starts (one at a time: two builds side by
 // side would only take the chip from each other, and freeing one's scratch would wait for the other)
 int advance_builds(zk_ctx* ctx, ZkBasesCache* c, bool wait) {
+    auto built = [c](const zk_bases* b) { c->builds += b->pre ? 1 : 0; for (auto& y : c->e) if (y.b == b) y.bytes = table_bytes(b); };
     for (;;) {
-        if (c->building) {
-            if (!wait && !c->build_done.load()) return ZK_OK;
-            zk_bases* b = c->building->b;
-            ZK_TRY(zk_bases_precompute_finish(ctx, builder_collect(c, false), true));
-            if (b->pre) c->builds++;
-            for (auto& y : c->e) if (y.b == b) y.bytes = table_bytes(b);
+        if (const zk_bases* b = c->builder.table()) {
+            if (!wait && !c->builder.finished()) return ZK_OK;
+            zk_bases_precompute_finish(c->builder.collect(false), true);    // (a failed build: the table stays plain, its note says why)
+            built(b);
         }
         if (c->precompute_after <= 0) return ZK_OK;
         size_t pick = SIZE_MAX;
@@ -293,32 +309,19 @@ int advance_builds(zk_ctx* ctx, ZkBasesCache* c, bool wait) {
             // to the builder, and a proof over it has no gap of 0.3 ms for the builder to work in -- waiting for one, the builder
             // starved and the MSMs of small circuits ran on plain tables: 2^10 0.36 -> 0.51 ms per G1 call, measured)
             ZK_TRY(zk_bases_precompute(ctx, xb));
-            for (auto& y : c->e) if (y.b == xb) y.bytes = table_bytes(xb);
-            if (xb->pre) c->builds++;
+            built(xb);
             continue;
         }
-        if (!c->pre_stream) ZK_TRY(zk_side_stream(ctx, &c->pre_stream));      // (the context's: shared with the MSMs started ahead)
+        hipStream_t side;
+        ZK_TRY(zk_side_stream(ctx, &side));                  // (the context's: shared with the MSMs started ahead)
         ZkPrecompJob* j = nullptr;
         ZK_TRY(zk_bases_precompute_begin(ctx, xb, c->budget - resident(c), &j));
         if (!j) continue;                                    // skipped (the note says why)
-        bool have_thread = true;
-        {
-            std::lock_guard<std::mutex> lk(c->bm);
-            if (!c->builder.joinable()) {
-                try { c->builder = std::thread(builder_main, ctx, c); } catch (const std::system_error&) { have_thread = false; }
-            }
-            if (have_thread) {
-                c->building = j;
-                c->building_bytes = need;
-                c->build_done.store(false);
-            }
-        }
-        if (!have_thread) {                                  // no thread to be had: the table stays plain (never a failed call)
-            (void)zk_bases_precompute_finish(ctx, j, false);
+        if (!c->builder.start(ctx, side, j, need)) {         // no thread to be had: the table stays plain (never a failed call)
+            zk_bases_precompute_finish(j, false);
             xb->pre_note = "window multiples skipped: the builder thread could not be started";
             continue;
         }
-        c->bcv.notify_all();
         if (!wait) return ZK_OK;
     }
 }
@@ -407,36 +410,27 @@ void zk_bases_cache_free(zk_ctx* ctx) {
     ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
     if (!c) return;
     while (!c->e.empty()) drop_entry(ctx, c, c->e.size() - 1);
-    if (c->building) (void)zk_bases_precompute_finish(ctx, builder_collect(c, true), false);
-    if (c->builder.joinable()) {
-        { std::lock_guard<std::mutex> lk(c->bm); c->bstop = true; }
-        c->bcv.notify_all();
-        c->builder.join();
-    }
-    if (c->pre_stream) (void)hipStreamSynchronize(c->pre_stream);      // (the context's side stream: it goes with the context)
     if (c->flag_dev) (void)hipFree(c->flag_dev);
     if (c->flag_host) (void)hipHostFree(c->flag_host);
-    delete c;
+    delete c;                                                // (the builder's thread is joined here, a build left is dropped)
     ctx->bases_cache = nullptr;
 }
 
-void zk_bases_lease_release(zk_ctx* ctx, ZkBasesLease* l) {
-    if (l->temporary && l->b) free_table(ctx, nullptr, const_cast<zk_bases*>(l->b), l->raw_tmp);
-    l->b = nullptr;
-    l->raw_tmp = nullptr;
-    if (ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache) c->leased = nullptr;
+ZkBasesLease::~ZkBasesLease() {
+    if (temporary && b) free_table(ctx, nullptr, const_cast<zk_bases*>(b), raw_tmp);
+    if (ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache) if (c->leased == entry) c->leased = nullptr;
 }
 
 int zk_bases_cache_poll(zk_ctx* ctx) {
     ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
-    if (!c || (!c->building && c->e.empty())) return ZK_OK;
+    if (!c || (!c->builder.table() && c->e.empty())) return ZK_OK;
     return advance_builds(ctx, c, false);
 }
 
 int zk_bases_cache_get(zk_ctx* ctx, const ZkHostTable& t, size_t n, ZkBasesLease* out) {
     ZkBasesCache* c = cache_of(ctx);
     ZK_TRY(check_layout(ctx, t));
-    *out = ZkBasesLease();
+    auto lease = [&](zk_bases* b) { out->b = b; out->entry = b; c->leased = b; };     // (from here on the lease's destructor ends it)
     const size_t plain = n * point_bytes(t.group);
     if (c->budget == 0 || n < MIN_CACHED || 2 * plain > c->budget) {          // cache off, or not worth / not able to keep
         ZK_TRY(upload_table(ctx, t, n, &out->raw_tmp, const_cast<zk_bases**>(&out->b), nullptr));
@@ -455,9 +449,7 @@ int zk_bases_cache_get(zk_ctx* ctx, const ZkHostTable& t, size_t n, ZkBasesLease
         x.hits++;
         x.last = ++c->tick;
         c->hits++;
-        out->b = x.b;
-        out->entry = x.b;
-        c->leased = x.b;
+        lease(x.b);
         out->verify = !c->trust;
         if (out->verify && x.host) {
             c->fresh.resize(plain);                          // (host comparison: the caller's table is packed into this)
@@ -478,9 +470,7 @@ int zk_bases_cache_get(zk_ctx* ctx, const ZkHostTable& t, size_t n, ZkBasesLease
     c->uploaded += plain;
     x.group = t.group; x.n = n; x.fp = fp; x.last = ++c->tick; x.hits = 0; x.pre_tried = false; x.bytes = table_bytes(x.b);
     c->e.push_back(x);
-    out->b = x.b;
-    out->entry = x.b;
-    c->leased = x.b;
+    lease(x.b);
     return ZK_OK;
 }
 
@@ -522,8 +512,7 @@ int zk_bases_cache_verify(zk_ctx* ctx, ZkBasesLease* l, const ZkHostTable& t, si
     if (bad.load()) ZK_FAIL(ctx, ZK_ERR_ARG, "multi_scalar_mul: a base is not Public (the reference asserts !b.is_shared(): wire/pairing.rs:716)");
     c->verified++;
     c->verified_bytes += bytes;
-    if (*c->flag_host == 0) return ZK_OK;
-    *same = false;
+    *same = *c->flag_host == 0;
     return ZK_OK;
 }
 
@@ -533,7 +522,7 @@ int zk_bases_cache_replace(zk_ctx* ctx, ZkBasesLease* l) {
     CacheEntry* x = nullptr;
     for (auto& y : c->e) if (y.b == l->entry) x = &y;
     if (!x) ZK_FAIL(ctx, ZK_ERR_STATE, "bases cache: the leased entry is gone");
-    if (c->building && c->building->b == x->b) (void)zk_bases_precompute_finish(ctx, builder_collect(c, true), false);
+    if (c->builder.table() == x->b) zk_bases_precompute_finish(c->builder.collect(true), false);
     zk_bases* b = x->b;
     zk_msm_spec_drop(ctx);                                   // (whatever was started ahead may read this table)
     if (b->pre) { ZK_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(b->pre); b->pre = nullptr; b->c_pre = b->W_pre = b->pre_stride = 0; b->pre_note.clear(); }
@@ -607,7 +596,7 @@ extern "C" int zk_bases_cache_stats2(zk_ctx* ctx, uint64_t out[4]) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !out) return ZK_ERR_ARG;
     ZkBasesCache* c = cache_of(ctx);
-    out[0] = c->verified; out[1] = c->verified_bytes; out[2] = c->builds; out[3] = c->building ? 1 : 0;
+    out[0] = c->verified; out[1] = c->verified_bytes; out[2] = c->builds; out[3] = c->builder.table() ? 1 : 0;
     return ZK_OK;
     ZK_API_END
 }

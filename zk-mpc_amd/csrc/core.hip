@@ -196,6 +196,22 @@ int zk_scratch(zk_ctx* ctx, const char* name, size_t bytes, void** out) {
     return ZK_OK;
 }
 
+// ONE side stream per context for everything that runs beside the caller's own calls on the trait-shaped path -- the slices of the
+// table cache's builder (bases_cache.hip) and the MSMs started ahead (msm.hip) -- and no accumulate stream with it: with the default
+// four hardware queues every stream beyond {null, context, transfer ring, this one} shares a queue with one of them, and the
+// host-slice transforms and products then run 8 - 30 % longer even while the extra streams sit idle (measured, round 6: seven
+// transforms at 2^20 12.9-13.4 -> 13.8-15.5 ms, the batch product 2.4 -> 3.1-3.3 ms with one to four idle streams more;
+// GPU_MAX_HW_QUEUES=8 takes the effect away, but that is the host application's setting, and the one-call provers lose with it).
+int zk_side_stream(zk_ctx* ctx, hipStream_t* out) {
+    if (ctx->aux.empty()) {
+        hipStream_t st;
+        ZK_HIP(ctx, zk_stream_create(&st, true));
+        ctx->aux.push_back(st);
+    }
+    *out = ctx->aux[0];
+    return ZK_OK;
+}
+
 // Run `enqueue` -- kernel launches and memsets on `st` ONLY: no allocation, no host wait, no other stream -- and from the third use
 // with the same key on replay it as ONE graph launch.  First use: plain (scratch slots and function attributes come into being);
 // second use: captured while it is enqueued; a key must cover every argument of every launch (ctx->scratch_gen covers the scratch
@@ -231,10 +247,13 @@ int zk_graph_run(zk_ctx* ctx, const std::string& key, hipStream_t st, const std:
     }
     if (e.seen++ == 0) return enqueue();
     const uint64_t gen = ctx->scratch_gen;
+    std::unique_lock<std::mutex> side(ctx->side_mu, std::defer_lock);     // (a capture of the side stream: its rule, ctx.hpp)
+    if (!ctx->aux.empty() && st == ctx->aux[0]) side.lock();
     if (hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); return enqueue(); }
     const int rc = enqueue();
     hipGraph_t g = nullptr;
     const hipError_t ce = hipStreamEndCapture(st, &g);
+    if (side) side.unlock();
     if (rc != ZK_OK || ce != hipSuccess || !g || gen != ctx->scratch_gen) {
         // nothing ran (a capture only records): not capturable as it stands -- enqueue it for real and stop trying for this key
         if (g) (void)hipGraphDestroy(g);

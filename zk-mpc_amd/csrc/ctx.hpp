@@ -116,6 +116,11 @@ struct zk_ctx {
     int n_cu = 256;                 // compute units of the device
     hipStream_t stream = nullptr;
     std::vector<hipStream_t> aux;   // high-priority helper streams for concurrent MSMs (created on first use)
+    // aux[0] is the side stream (core.hip: zk_side_stream).  A thread other than the caller's inside an entry point (the table cache's
+    // builder) enqueues on it or waits on it only while holding side_mu, and zk_graph_run holds side_mu while it captures that
+    // stream: capture is per stream, so an outside launch would be recorded instead of run.  Lock order: side_mu is never held while
+    // the builder's own mutex is taken or while anything waits on the builder (no enqueue of zk_graph_run collects a build).
+    std::mutex side_mu;
     hipStream_t acc_stream = nullptr;  // stream carrying the accumulate kernels back to back
     std::string last_error;
     // grow-only scratch arena: named slots, each re-used across calls (no hipMalloc on the hot path)

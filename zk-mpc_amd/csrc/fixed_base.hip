@@ -494,8 +494,10 @@ hipError_t zk_bases_precompute_step(ZkPrecompJob* j, hipStream_t st, bool* more)
     if (j->b->group == 1) return precompute_step_t<G1Field>(j, st, more);
     return precompute_step_t<G2Field>(j, st, more);
 }
-// the stream the slices ran on has been waited for.  keep = false (or a slice failed): throw the table away
-int zk_bases_precompute_finish(zk_ctx* ctx, ZkPrecompJob* j, bool keep) {
+// the stream the slices ran on has been waited for.  keep = false (or a slice failed): throw the table away.  A failed build is not
+// an error of the call that happens to collect the job: the table stays plain and its note says why (a sticky device error reaches
+// the caller through its own next HIP call)
+void zk_bases_precompute_finish(ZkPrecompJob* j, bool keep) {
     zk_bases* b = j->b;
     if (j->xy) (void)hipFree(j->xy);
     if (j->scr) (void)hipFree(j->scr);
@@ -515,15 +517,10 @@ int zk_bases_precompute_finish(zk_ctx* ctx, ZkPrecompJob* j, bool keep) {
     } else {
         if (j->packed) (void)hipFree(j->packed);
         if (j->wide) (void)hipFree(j->wide);
-        if (e == hipErrorOutOfMemory) {                     // not an error of the call that happens to collect the job: the table stays plain
-            b->pre_note = "window multiples skipped: more than a third of the free device memory, or hipMalloc failed";
-            delete j;
-            return ZK_OK;
-        }
+        if (e == hipErrorOutOfMemory) b->pre_note = "window multiples skipped: more than a third of the free device memory, or hipMalloc failed";
+        else if (e != hipSuccess) b->pre_note = std::string("window multiples skipped: the build failed: ") + hipGetErrorString(e);
     }
     delete j;
-    ZK_HIP(ctx, e);
-    return ZK_OK;
 }
 
 // "" when nothing was attempted; the layout that was built; or why the table was skipped

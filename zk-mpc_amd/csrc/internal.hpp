@@ -75,18 +75,22 @@ struct ZkHostTable {
     size_t stride = 0, off_x = 0, off_y = 0, off_inf = SIZE_MAX, off_tag = SIZE_MAX;
     uint8_t tag_public = 0;
 };
-struct ZkBasesLease {
+struct ZkBasesLease {               // a table handed out by zk_bases_cache_get for one call: released by scope, on every exit of the call
+    zk_ctx* const ctx;              // the context it was taken on
     const zk_bases* b = nullptr;    // the table to run on
-    bool temporary = false;         // made for this call only (cache off / tiny / over budget): zk_bases_lease_release frees it
+    bool temporary = false;         // made for this call only (cache off / tiny / over budget): freed with the lease
     bool verify = false;            // a hit by fingerprint: zk_bases_cache_verify must confirm it before the result leaves the library
     uint32_t* raw_tmp = nullptr;
     void* stage = nullptr;          // device buffer the caller's slice is compared in
     const void* entry = nullptr;
+    explicit ZkBasesLease(zk_ctx* c) : ctx(c) {}
+    ~ZkBasesLease();                // bases_cache.hip
+    ZkBasesLease(const ZkBasesLease&) = delete;
+    ZkBasesLease& operator=(const ZkBasesLease&) = delete;
 };
 int zk_bases_cache_get(zk_ctx* ctx, const ZkHostTable& t, size_t n, ZkBasesLease* out);
 int zk_bases_cache_verify(zk_ctx* ctx, ZkBasesLease* l, const ZkHostTable& t, size_t n, bool* same);
 int zk_bases_cache_replace(zk_ctx* ctx, ZkBasesLease* l);
-void zk_bases_lease_release(zk_ctx* ctx, ZkBasesLease* l);
 // msm.hip: n_lanes MSMs (device scalar vectors of n elements) over ONE host table, through the cache -- verified hit and all
 // scalars_fp: a fingerprint of the scalar vector taken from the caller's HOST memory (64 sampled elements and the length; 0 = none):
 // what the speculation below recognises a repeated vector by -- a candidate, confirmed word for word on the device before any
@@ -97,7 +101,7 @@ int zk_msm_table_run(zk_ctx* ctx, const ZkHostTable& t, size_t n_table, int n_la
 // in G2 over one `assignment`: src/groth16.rs:137-160).  drop: abandon what is in flight (waits for its kernels); forget: a table is
 // leaving the cache or changing content; free: with the context.
 void zk_msm_spec_drop(zk_ctx* ctx);
-int zk_side_stream(zk_ctx* ctx, hipStream_t* out);                       // groth16_pipeline.hip: the context's one side stream (= aux[0])
+int zk_side_stream(zk_ctx* ctx, hipStream_t* out);                       // core.hip: the context's one side stream (= aux[0])
 void zk_msm_spec_forget(zk_ctx* ctx, const zk_bases* b);
 void zk_msm_spec_fft_begin(zk_ctx* ctx, const void* dev, size_t N, int kind);            // msm.hip: a host-slice transform's output as the next MSM's scalars
 void zk_msm_spec_fft_end(zk_ctx* ctx, size_t N, int kind, const std::function<uint64_t(size_t)>& fp_of);
@@ -124,7 +128,7 @@ struct ZkPrecompJob {
 };
 int zk_bases_precompute_begin(zk_ctx* ctx, zk_bases* b, size_t budget_bytes, ZkPrecompJob** out);   // *out = NULL: skipped (b->pre_note says why)
 hipError_t zk_bases_precompute_step(ZkPrecompJob* j, hipStream_t st, bool* more);
-int zk_bases_precompute_finish(zk_ctx* ctx, ZkPrecompJob* j, bool keep);
+void zk_bases_precompute_finish(ZkPrecompJob* j, bool keep);
 int zk_msm_run(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n,
                void* out_host_projective);
 

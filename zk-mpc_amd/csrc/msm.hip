@@ -1450,7 +1450,7 @@ static int spec_same_scalars(zk_ctx* ctx, ZkMsmSpec* sp, const void* scalars, si
     return ZK_OK;
 }
 // the tables that followed `b` last time, over a private copy of the scalars: every phase of every job on the context's ONE side
-// stream, one job behind the other (groth16_pipeline.hip::zk_side_stream says why there is only one)
+// stream, one job behind the other (core.hip::zk_side_stream says why there is only one)
 static int spec_start_tables(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* const* next, int cnt, const void* scalars, size_t n, uint64_t fp);
 static int spec_start(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* b, const void* scalars, size_t n, uint64_t fp) {
     const zk_bases* next[2] = {nullptr, nullptr};
@@ -1501,7 +1501,7 @@ static int spec_start_tables(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* const* 
 // n_lanes MSMs over the same table (the two lanes of a SPDZ multi_scale_pub_group: share/spdz.rs:482-488): scalars_dev[l] -> outs[l].
 template <class F>
 int msm_table_run_t(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, const void* const* scalars_dev, size_t n, void* const* outs, uint64_t sfp) {
-    ZkBasesLease lease;
+    ZkBasesLease lease(ctx);
     ZK_TRY(zk_bases_cache_get(ctx, t, nu, &lease));
     const bool spec_ok = spec_enabled() && n_lanes == 1 && !lease.temporary && sfp != 0 && !ctx->profiling &&
                          !(ctx->msm_spec && ((ZkMsmSpec*)ctx->msm_spec)->off);
@@ -1586,7 +1586,6 @@ int msm_table_run_t(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, c
         rc = zk_bases_cache_replace(ctx, &lease);            // the table at the caller's address is not the cached one any more: again, on the right one
     }
     if (rc != ZK_OK && sp) spec_drop(ctx, sp);
-    zk_bases_lease_release(ctx, &lease);
     return rc;
 }
 
