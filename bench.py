@@ -18,9 +18,14 @@ N > 1: N-party collaborative prove (additive shares, honest backend; --spdz: the
 A step = one proof.  Timing: W untimed proofs, then exactly K proofs bracketed by barrier +
 device synchronisation; max over ranks.  One JSON line on rank 0.
 
-Outside the timed region the run checks itself: the bytes of the timed proofs are compared with the oracle's known-trapdoor
-prediction (Fr arithmetic on the CPU + three scalar multiplications; `proof_matches_prediction`), for N > 1 the revealed
-proof against the prediction on the summed shares, identical on every rank.
+N = 1 without --full (a plain run): set-up, priming, the W warm-up and K timed proofs, --dump-outputs, the line -- nothing else.
+--full adds everything beside the headline figure, outside the timed region: the timed proofs' bytes against the oracle's
+known-trapdoor prediction (Fr arithmetic on the CPU + three scalar multiplications; `proof_matches_prediction`), a profiled
+loop for the per-kernel `roofline` and `phases_ms_per_proof`, isolated and device-resident proofs, standalone MSMs, Marlin /
+SHE, the micro sweeps, the boolean-heavy and natural-domain legs, the composed trait paths and the CPU baseline (--no-extras,
+--no-micro, --no-predict and --no-cpu-baseline leave parts of it out).  The other modes (N > 1, --force-mpc, --one-prover,
+--marlin) always check themselves: for N > 1 the revealed proof against the prediction on the summed shares, identical on
+every rank.
 """
 from __future__ import annotations
 
@@ -769,6 +774,36 @@ def dump_outputs(dirname, proof: bytes) -> dict:
     return {"dir": dirname, "arrays": {name: list(a.shape) for name, a in arrays.items()}, "dtype": "float64"}
 
 
+def groth16_headline(args, n, r1cs, world, Q, dist, dt, step_s, t_setup, proof) -> dict:
+    """The Groth16 line's own fields, from the timed steps alone: `value` = constraints of one proof x K / T over the
+    barrier-bracketed region (max over ranks), its configuration and the per-step spread.  A plain run's line is this."""
+    import hashlib
+    K = args.steps
+    per_proof = n * K / dt
+    share_kind = "SPDZ (share + MAC lanes, MAC-checked opens)" if args.spdz else "additive-share"
+    return {
+        "metric": "R1CS constraints/sec (prove), Groth16 BLS12-377",
+        "value": round(per_proof, 1),
+        "unit": "constraints/s",
+        "n_gpus": world, "steps": K, "warmup": args.warmup,
+        "ms_per_step": round(dt / K * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u32x13 (29-bit limbs, int64 accumulate)", "data": "synthetic",
+        "config": {"workload": "mul-chain R1CS, n=2^%d%s constraints, QAP domain 2^%d, %s" % (
+            args.log_constraints, "" if args.natural_domain else "-2", r1cs.domain_log,
+            "local prove" if dist is None else "%d-party %s collaborative prove" % (world, share_kind)),
+            "constraints": n, "parties": world,
+            "queue": ("isolated proofs" if (dist is not None or args.no_hint) else
+                      "host witness -> host proof bytes (zk_groth16_prove_queued), proofs back to back over a queue of %d DIFFERENT "
+                      "assignments in page-locked host memory, the next one announced: its upload runs under the current proof and "
+                      "each timed proof also runs the front of its successor; phase timers off" % Q)},
+        "proof_constraints_per_s": round(per_proof, 1),
+        "ms_per_step_median": round(float(np.median(step_s)) * 1e3, 3), "ms_per_step_max": round(max(step_s) * 1e3, 3),
+        "setup_s": round(t_setup, 2),
+        "proof_sha": hashlib.sha256(proof).hexdigest()[:16],
+    }
+
+
 def hbm_in_use_gb():
     """Device memory held by this process when the line is written.  Scratch arenas and key tables are grow-only, so this is the
     high-water mark of the run up to freed temporaries."""
@@ -1004,8 +1039,8 @@ def main():
     ap.add_argument("--force-mpc", action="store_true", help="run the collaborative code path even with one rank (1-party: exercises transport + share plumbing)")
     ap.add_argument("--cpu-sample-log", type=int, default=None,
                     help="log2 of the CPU baseline's constraint count (default: the benched configuration itself; 16 = bounded sample)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the Marlin / SHE side measurements")
-    ap.add_argument("--no-micro", action="store_true", help="skip the SURVEY 8(d) MSM / NTT sweeps and the natural-domain proof (~60 s)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the Marlin / SHE side measurements")
+    ap.add_argument("--no-micro", action="store_true", help="with --full: skip the SURVEY 8(d) MSM / NTT sweeps and the natural-domain proof (~60 s)")
     ap.add_argument("--no-predict", action="store_true", help="skip the known-trapdoor check of the timed proofs (CPU, ~10 s per proof at 2^20)")
     ap.add_argument("--queue", type=int, default=4, help="number of DIFFERENT assignments the timed proofs cycle through")
     ap.add_argument("--natural-domain", action="store_true",
@@ -1021,6 +1056,9 @@ def main():
                          "of N parties; total work fixed (strong scaling); add --one-gpu for a functional run on one device")
     ap.add_argument("--marlin", action="store_true",
                     help="prove with Marlin/KZG instead of Groth16 (BASELINE configs 4 and 5: --gpus 1, or --gpus 8 --spdz --log-constraints 22)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also run the self-checks and every side measurement (prediction check, roofline, "
+                         "isolated and device-resident proofs, MSMs, Marlin / SHE, micro sweeps, trait paths, CPU baseline; ~80 s at 2^20)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64; e.g. DIR = bench_outputs, which git ignores)")
     args = ap.parse_args()
@@ -1161,7 +1199,7 @@ def main():
     for _ in range(args.warmup):
         proof = step(it); it += 1
     # the timed region runs the PRODUCTION path: phase timers off (they also switch the captured sort graphs off: core.hip); the
-    # per-kernel averages of `roofline` come from a separate short profiled loop of the same step right after it (N = 1)
+    # per-kernel averages of `roofline` come from a separate short profiled loop of the same step right after it (N = 1, --full)
     if dist is not None:
         ctx.set_profiling(True)               # (N > 1: the per-open wall times are part of the line)
         party.be.open_stats()                 # reset the per-open wall-time counters
@@ -1174,6 +1212,16 @@ def main():
         step_s.append(time.perf_counter() - ts)          # (a proof call returns with the proof's bytes: no extra synchronisation)
     barrier()
     dt = time.perf_counter() - t0
+    if dist is None and not args.full:
+        # a plain run ends here: the headline line and --dump-outputs, nothing else on the device or the CPU
+        for pb in pinned:
+            pb.free()
+        out = groth16_headline(args, n, r1cs, world, Q, dist, dt, step_s, t_setup, proof)
+        out["hbm_in_use_gb"] = hbm_in_use_gb()
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, proof)
+        os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        return
     profiled_steps = args.steps
     profiled_ms = None
     if dist is None:
@@ -1408,27 +1456,10 @@ def main():
                                     "avg_launch_ms": round(g2_s * 1e3, 3), "launches": g2_cnt,
                                     "int_alu": {"achieved": round(madds * MADS_PER_MADD_G2 / g2_s / 1e12, 3), "peak": round(peak / 1e12, 3),
                                                 "unit": "T v_mad_u64_u32 lane-ops/s", "frac": round(madds * MADS_PER_MADD_G2 / g2_s / peak, 4)}}
-        share_kind = "SPDZ (share + MAC lanes, MAC-checked opens)" if args.spdz else "additive-share"
-        out = {
-            "metric": "R1CS constraints/sec (prove), Groth16 BLS12-377",
-            "value": round(per_proof, 1),
-            "unit": "constraints/s",
-            "n_gpus": world, "steps": K, "warmup": args.warmup,
-            "ms_per_step": round(dt / K * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u32x13 (29-bit limbs, int64 accumulate)", "data": "synthetic",
-            "config": {"workload": "mul-chain R1CS, n=2^%d%s constraints, QAP domain 2^%d, %s" % (
-                args.log_constraints, "" if args.natural_domain else "-2", r1cs.domain_log,
-                "local prove" if dist is None else "%d-party %s collaborative prove" % (world, share_kind)),
-                "constraints": n, "parties": world,
-                "queue": ("isolated proofs" if (dist is not None or args.no_hint) else
-                          "host witness -> host proof bytes (zk_groth16_prove_queued), proofs back to back over a queue of %d DIFFERENT "
-                          "assignments in page-locked host memory, the next one announced: its upload runs under the current proof and "
-                          "each timed proof also runs the front of its successor; phase timers off" % Q)},
-            "proof_constraints_per_s": round(per_proof, 1),
+        out = groth16_headline(args, n, r1cs, world, Q, dist, dt, step_s, t_setup, proof)
+        out.update({
             "proof_matches_prediction": pred.get("ok"),
             "prediction_check": pred,
-            "ms_per_step_median": round(float(np.median(step_s)) * 1e3, 3), "ms_per_step_max": round(max(step_s) * 1e3, 3),
             "isolated_proof_ms": None if isolated_ms is None else round(isolated_ms, 3),
             "isolated_proof_ms_all": isolated_all,
             "host_witness_leg": host_leg,
@@ -1436,11 +1467,9 @@ def main():
             "phases_ms_per_proof": {k: round(v[0] / profiled_steps, 3) for k, v in sorted(timers.items())},
             "phases_from": ("the timed steps" if dist is not None else
                             "a separate loop of %d steps of the same call with the phase timers on, right after the timed region" % profiled_steps),
-            "setup_s": round(t_setup, 2),
-            "proof_sha": hashlib.sha256(proof).hexdigest()[:16],
             "roofline": roof,
             "hbm_in_use_gb": hbm_in_use_gb(),
-        }
+        })
         if args.dump_outputs:
             out["dump_outputs"] = dump_outputs(args.dump_outputs, proof)
         try:      # which tables carry window multiples, in which layout -- or why not (a skipped table costs 16 digits per scalar instead of 13)

@@ -1,6 +1,7 @@
-"""bench.py's one-line contract on the GPU box, at small sizes: the N = 1 line carries `roofline` and the self-checks, and the
-N-party path (one process per party, launched as the driver launches it) runs end to end -- here over gloo with every party on
-cuda:0, because RCCL refuses two ranks on one device; with one GPU per rank the same code runs over RCCL."""
+"""bench.py's one-line contract on the GPU box, at small sizes: a plain N = 1 line is the headline alone, with --full it carries
+`roofline` and the self-checks, and the N-party path (one process per party, launched as the driver launches it) runs end to
+end -- here over gloo with every party on cuda:0, because RCCL refuses two ranks on one device; with one GPU per rank the same
+code runs over RCCL."""
 import json
 import os
 import socket
@@ -23,8 +24,8 @@ def _line(cmd):
 
 
 def test_single_gpu_line_small():
-    d = _line([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-constraints", "14", "--no-extras", "--no-micro",
-               "--cpu-sample-log", "12"])
+    d = _line([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-constraints", "14", "--full", "--no-extras",
+               "--no-micro", "--cpu-sample-log", "12"])
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["unit"] == "constraints/s" and d["value"] > 0
     assert d["proof_matches_prediction"] is True
     # the top-level roofline is the roof that binds (an MSM kernel is judged on the integer-ALU roof), its peak measured
@@ -34,6 +35,37 @@ def test_single_gpu_line_small():
     assert roof["hbm"]["frac"] < roof["frac"] and roof["int_alu"]["frac"] == roof["frac"]
     assert len(d["msm_mscalar_per_s"]["g2_ms"]["all"]) >= 7 and d["msm_mscalar_per_s"]["g2_ms"]["max"] < 4 * d["msm_mscalar_per_s"]["g2_ms"]["median"]
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] in ("port", "reference")
+
+
+SIDE_LEGS = ("prediction_check", "proof_matches_prediction", "roofline", "phases_ms_per_proof", "host_witness_leg",
+             "device_resident_leg", "isolated_proof_ms", "window_multiples", "msm_mscalar_per_s", "other_workloads", "micro",
+             "boolean_heavy", "natural_domain", "trait_path", "trait_path_collab", "cpu_baseline")
+
+
+def test_plain_line_is_the_headline_alone():
+    """Without --full the N = 1 line is the headline and the timed steps' own figures, nothing measured or checked beside them;
+    the same arguments with --full time the same proofs (same bytes) and hold them to the known-trapdoor prediction."""
+    args = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-constraints", "12"]
+    plain = _line(args)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["unit"] == "constraints/s" and plain["higher_is_better"] is True and plain["steps"] == 3
+    assert plain["value"] == pytest.approx(((1 << 12) - 2) / (plain["ms_per_step"] * 1e-3), rel=5e-3)
+    assert not [k for k in SIDE_LEGS if k in plain]
+    full = _line(args + ["--full", "--no-extras", "--no-micro", "--no-cpu-baseline"])
+    assert full["proof_sha"] == plain["proof_sha"] and full["proof_matches_prediction"] is True
+    assert full["roofline"]["bound"] == "int_alu"
+
+
+def test_plain_run_at_the_headline_size_spends_little_outside_its_steps():
+    """The benchmark's own command at its default size: the whole process, start to exit, less (K + W) x ms_per_step, stays
+    within 30 s -- set-up, priming and import included."""
+    import time
+    t0 = time.perf_counter()
+    d = _line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    outside = time.perf_counter() - t0 - (3 + 1) * d["ms_per_step"] * 1e-3
+    assert d["config"]["constraints"] == (1 << 20) - 2
+    assert outside < 30.0, outside
 
 
 @pytest.mark.parametrize("extra", [[], ["--marlin"]])
@@ -174,11 +206,11 @@ def test_one_prover_line_over_three_contexts():
 
 
 def test_single_gpu_line_carries_the_composed_trait_paths():
-    """The default command's side legs at a small size: `trait_path` (examples/host_trait_groth16 = create_proof over the trait-shaped
+    """The --full command's side legs at a small size: `trait_path` (examples/host_trait_groth16 = create_proof over the trait-shaped
     entry points, plain element types) and `trait_path_collab` (the same over MpcField / MpcG1Affine, P parties) run, every proof of a
     run has the same bytes, and the steady state says how it compares with the resident API."""
-    d = _line([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-constraints", "12", "--no-micro", "--no-cpu-baseline",
-               "--no-predict"])
+    d = _line([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-constraints", "12", "--full", "--no-micro",
+               "--no-cpu-baseline", "--no-predict"])
     tp = d["trait_path"]
     assert "error" not in tp, tp
     for mode in ("cache_packed", "cache_strided", "cache_strided_trust", "nocache_packed"):

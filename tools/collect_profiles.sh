@@ -3,7 +3,7 @@
 # trait paths (plain and collaborative) call by call
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r6prof; rm -rf $O; mkdir -p $O
-B="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-micro --no-predict"
+B="python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras --no-micro --no-predict"
 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- $B > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o f --output-format csv -- $B > $O/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o w --output-format csv -- $B > $O/write.log 2>&1
