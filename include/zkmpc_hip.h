@@ -186,6 +186,15 @@ int zk_msm_g1_dev(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const 
                   size_t n, zk_g1_projective* out_host);
 int zk_msm_g2_dev(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev,
                   size_t n, zk_g2_projective* out_host);
+/* count MSMs over ONE resident table in one call: outs[k] = sum_{i<n} scalars[k*stride + i] * bases[base_offset + i], k < count;
+ * stride >= n in elements (scalars as zk_msm_g1_dev takes them).  Every outs[k] is the point zk_msm_g1_dev / zk_msm_g2_dev gives
+ * for vector k.  The launches do not grow with count: the vectors are one job over count bucket spaces.  A job takes at most
+ * 2^22 buckets and 2^28 digits; larger counts are cut into jobs of that many vectors.  count = 0, n = 0, stride < n or a range
+ * past the table: ZK_ERR_ARG. */
+int zk_msm_g1_multi_dev(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev,
+                        size_t n, size_t stride, size_t count, zk_g1_projective* outs_host);
+int zk_msm_g2_multi_dev(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev,
+                        size_t n, size_t stride, size_t count, zk_g2_projective* outs_host);
 /* Fixed-base batch: out[i] = scalars[i] * G (G1/G2 generator scaled by gen_k), affine results on
  * device as a zk_bases table.  FixedBaseMSM::multi_scalar_mul + batch_normalization_into_affine
  * (ec/src/msm/fixed_base.rs:11-95, arkworks/groth16/src/generator.rs:130-215). */
@@ -345,6 +354,19 @@ int zk_groth16_msms_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, const
  * (non-shared) assignment resident on the device; proof = a||b||c compressed, 192 bytes. */
 int zk_groth16_prove_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, const void* z_dev,
                          const zk_fr* r, const zk_fr* s, uint8_t proof_out[192]);
+/* count plain proofs of one key and one constraint system in one call.  z_dev: count assignments of m = ni + nw elements, back
+ * to back (each as zk_groth16_prove_dev takes it); r[count], s[count]; proofs_out: count x 192 bytes, proof k the bytes
+ * zk_groth16_prove_dev gives for (z_k, r[k], s[k]).  The five MSMs of all proofs run as five multi-vector jobs (zk_msm_g1_multi_dev);
+ * the witness maps of all proofs are one batched witness map; the host tails run on at most 16 helper threads.  Launches do not
+ * grow with count.  Device memory: count * (m + 6D) * 32 bytes (D = the domain size) plus, per MSM job of up to 2^22 buckets,
+ * ~16 bytes per scalar digit and two bucket sets per proof; a batch that does not fit 90 % of the free memory fails with
+ * ZK_ERR_NOMEM before any device work (the host form: before its upload) and leaves the context usable.  An announced next assignment
+ * (zk_groth16_hint_next_dev, zk_groth16_prove_queued) is drained and dropped.  count = 0, a null pointer or a key that does not
+ * match the system: ZK_ERR_ARG.  zk_groth16_prove_batch: the assignments in host memory, through the context's staging ring. */
+int zk_groth16_prove_batch_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, size_t count, const void* z_dev,
+                               const zk_fr* r, const zk_fr* s, uint8_t* proofs_out);
+int zk_groth16_prove_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, size_t count, const zk_fr* z_host,
+                           const zk_fr* r, const zk_fr* s, uint8_t* proofs_out);
 /* The same proof with the five MSMs of src/groth16.rs:106,110,137,148,160 spread over n_ctx contexts -- one per GPU of a node; for a
  * functional run several on one GPU -- each with ITS OWN copy of the proving key and the constraint system (pks[i], r1css[i]
  * belong to ctxs[i]).  The work is cut by cost into base ranges (a G2 term weighs 2.7 G1 terms), a context holding a piece of H runs

@@ -133,6 +133,8 @@ PROTOTYPES = {
     "zk_bases_window_bits": (_U32, [_P]),
     "zk_msm_g1_dev": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
     "zk_msm_g2_dev": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
+    "zk_msm_g1_multi_dev": (_I, [_P, _P, _SZ, _P, _SZ, _SZ, _SZ, _P]),
+    "zk_msm_g2_multi_dev": (_I, [_P, _P, _SZ, _P, _SZ, _SZ, _SZ, _P]),
     "zk_fixed_base_g1_dev": (_I, [_P, _P, _P, _SZ, C.POINTER(_P)]),
     "zk_fixed_base_g2_dev": (_I, [_P, _P, _P, _SZ, C.POINTER(_P)]),
     "zk_bases_download_g1": (_I, [_P, _P, _SZ, _SZ, _P]),
@@ -182,6 +184,8 @@ PROTOTYPES = {
     "zk_groth16_hint_next_dev": (_I, [_P, _P]),
     "zk_groth16_chain_fronts": (_I, [_P, _I]),
     "zk_groth16_prove_dev": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "zk_groth16_prove_batch_dev": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P]),
+    "zk_groth16_prove_batch": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P]),
     "zk_groth16_prove_multi": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "zk_groth16_multi_plan": (_I, [_P, _P, _I, C.c_char_p, _SZ, C.POINTER(_SZ)]),
     "zk_groth16_prove": (_I, [_P, _P, _P, _P, _P, _P, _P]),

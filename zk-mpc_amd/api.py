@@ -422,6 +422,13 @@ class Context:
         self._ck(fn(self.h, bases.h, base_offset, C.c_void_p(int(scalars_dev)), n, _ptr(out)))
         return out
 
+    def msm_multi_dev(self, bases: "Bases", base_offset: int, scalars_dev, n: int, stride: int, count: int) -> np.ndarray:
+        """count MSMs over one table in one call: row k = sum_i scalars[k*stride + i] * bases[base_offset + i] (18 or 36 u64 each)."""
+        out = np.zeros((count, 18 if bases.group == 1 else 36), dtype=np.uint64)
+        fn = self.lib.zk_msm_g1_multi_dev if bases.group == 1 else self.lib.zk_msm_g2_multi_dev
+        self._ck(fn(self.h, bases.h, base_offset, C.c_void_p(int(scalars_dev)), n, stride, count, _ptr(out) if count else None))
+        return out
+
     # ---- dense polynomials / KZG10 (names follow DensePolynomial / KZG10 in the reference) ----
     def msm_batch_dev(self, jobs):
         """jobs: list of (Bases, base_offset, scalars_dev, n).  Returns one projective array per job (18 or 36 u64)."""
@@ -793,6 +800,26 @@ class Context:
         out = np.zeros(192, dtype=np.uint8)
         self._ck(self.lib.zk_groth16_prove_dev(self.h, pk.h, r1cs.h, C.c_void_p(int(z_dev)), C.byref(r), C.byref(s), _ptr(out)))
         return out.tobytes()
+
+    def create_proofs_batch_dev(self, pk: "ProvingKey", r1cs: "R1cs", z_dev, count: int, r_list, s_list) -> list:
+        """count proofs of one key in one call: z_dev holds count assignments back to back; proof k as create_proof_dev(z_k, r_k, s_k)."""
+        assert len(r_list) == count and len(s_list) == count
+        r = (_lib.Fr * max(count, 1))(*[_fr_struct(x) for x in r_list])
+        s = (_lib.Fr * max(count, 1))(*[_fr_struct(x) for x in s_list])
+        out = np.zeros((max(count, 1), 192), dtype=np.uint8)
+        self._ck(self.lib.zk_groth16_prove_batch_dev(self.h, pk.h, r1cs.h, count, C.c_void_p(int(z_dev)), r, s, _ptr(out)))
+        return [out[k].tobytes() for k in range(count)]
+
+    def create_proofs_batch(self, pk: "ProvingKey", r1cs: "R1cs", z_mont, r_list, s_list) -> list:
+        """The same with the assignments in host memory: z_mont = count x m Montgomery elements (count x m x 4 u64)."""
+        z = np.ascontiguousarray(z_mont, dtype=np.uint64).reshape(len(r_list), -1, 4)
+        assert z.shape[1] == r1cs.num_instance + r1cs.num_witness and len(s_list) == len(r_list)
+        count = len(r_list)
+        r = (_lib.Fr * max(count, 1))(*[_fr_struct(x) for x in r_list])
+        s = (_lib.Fr * max(count, 1))(*[_fr_struct(x) for x in s_list])
+        out = np.zeros((max(count, 1), 192), dtype=np.uint8)
+        self._ck(self.lib.zk_groth16_prove_batch(self.h, pk.h, r1cs.h, count, _ptr(z), r, s, _ptr(out)))
+        return [out[k].tobytes() for k in range(count)]
 
     def create_proof_multi(self, others, pks, r1css, z_dev, r_mont4, s_mont4) -> bytes:
         """zk_groth16_prove_multi: this context plus `others` (one per further device), each with its own key and constraint

@@ -1,0 +1,206 @@
+// groth16_batch.hip -- count proofs of ONE key and ONE constraint system in one call (create_proof, src/groth16.rs:68-183, for
+// count assignments).  Every proof is the bytes zk_groth16_prove_dev returns for the same (z, r, s).
+//
+// A small proof leaves the device idle: its MSMs are chains of launch and dependency latencies.  Here the five MSMs of all the
+// proofs are five multi-vector jobs (msm.hip: zk_msm_prepare_multi): one sort, one accumulate launch and one reduce chain each, over
+// count bucket spaces of one table -- the launches of one proof, whatever count is.  The z jobs (A, B in G1, L over l_pad, B in G2)
+// share one sort of the count z vectors where their window widths agree, as zk_groth16_run_msms shares it for one proof.
+// The witness maps of all proofs are one batched witness map (r1cs.hip: zk_groth16_witness_map_batch: mat-vec, strided transforms
+// and vector operations over count D elements), on the context stream beside the z sort.  So the call's launches do not grow with
+// count until a job reaches the multi-job limits (zk_msm_multi_chunk): then the MSMs run in chunks of proofs.
+// Host tails (ZkProofTail would start six pool tasks per proof): the terms that need no MSM result (delta r, delta s, delta_2 s)
+// as at most 8 tasks while the device works -- beside the at most 8 threads of a multi job's Horner chains -- and the rest as at
+// most 16 tasks over contiguous ranges of proofs once the sums are in.
+#include "../../include/zkmpc_hip.h"
+#include "groth16_int.hpp"
+#include <algorithm>
+
+using namespace zk;
+
+namespace {
+
+constexpr size_t TAIL_TASKS = 16, PRE_TASKS = 8;
+
+// f(lo, hi) over [0, count) in at most `tasks` contiguous ranges on the context's pool (the first range on this thread)
+template <class Fn>
+void over_ranges(zk_ctx* ctx, size_t count, size_t tasks, const Fn& f) {
+    const size_t nt = std::min(count, tasks), per = (count + nt - 1) / nt;
+    std::vector<ZkTask<void>> ts;
+    for (size_t t = 1; t < nt; t++) {
+        const size_t lo = t * per, hi = std::min(count, lo + per);
+        if (lo < hi) ts.push_back(zk_async(ctx, [&f, lo, hi] { f(lo, hi); }));
+    }
+    f(0, std::min(count, per));
+    for (auto& t : ts) t.get();
+}
+
+// cnt proofs: z = their assignments (m elements each), h = their cnt quotients of D elements once front() has run on the context
+// stream (the first chunk enqueues the batched witness map there, beside its z sort); pre_ready() returns once pre[0..cnt) is complete
+int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, const char* z, const char* h, const std::function<int()>& front,
+                const std::function<void()>& pre_ready, const ZkTailPre* pre, uint8_t* proofs) {
+    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, nvars = m - 1;
+    hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;
+    struct Event {
+        hipEvent_t e = nullptr;
+        ~Event() { if (e) (void)hipEventDestroy(e); }
+    } e0;
+    ZK_HIP(ctx, hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
+    ZK_HIP(ctx, hipEventRecord(e0.e, ctx->stream));                  // z was produced on the context stream
+    ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0.e, 0));
+    ZkMsmJob J[5];                                                   // 0: B in G2, 1: A, 2: B in G1, 3: L, 4: H
+    struct Streams {                       // declared after the jobs: every exit drains the streams before the jobs and their events go
+        zk_ctx* ctx;
+        ~Streams() {
+            (void)hipStreamSynchronize(ctx->aux[0]);
+            (void)hipStreamSynchronize(ctx->acc_stream);
+            (void)hipStreamSynchronize(ctx->stream);
+        }
+    } drain{ctx};
+    const bool l_shared = pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
+                          pk->l_pad->c_pre == pk->a->c_pre;
+    ZK_TRY(zk_msm_prepare_multi(ctx, &J[0], pk->b_g2, 1, z + 32, nvars, m, cnt, 8));
+    ZK_TRY(zk_msm_prepare_multi(ctx, &J[1], pk->a, 1, z + 32, nvars, m, cnt, 9));
+    ZK_TRY(zk_msm_prepare_multi(ctx, &J[2], pk->b_g1, 1, z + 32, nvars, m, cnt, 10));
+    if (l_shared) ZK_TRY(zk_msm_prepare_multi(ctx, &J[3], pk->l_pad, 1, z + 32, nvars, m, cnt, 11));
+    else ZK_TRY(zk_msm_prepare_multi(ctx, &J[3], pk->l, 0, z + r->ni * 32, r->nw, m, cnt, 11));
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[0], s_sort, nullptr));
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[1], s_sort, &J[0]));
+    const ZkMsmJob* lender = J[0].c == J[1].c ? &J[0] : &J[1];
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[2], s_sort, lender));
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[3], s_sort, l_shared ? lender : nullptr));
+    ZK_TRY(front());                                                 // the witness map on the context stream, beside the z sort
+    ZK_TRY(zk_msm_prepare_multi(ctx, &J[4], pk->h, 0, h, std::min(pk->h->n, D), D, cnt, 12));   // :106, min(len) rule
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[4], ctx->stream, nullptr));
+    // B in G2 (the long reduce chain) on the accumulate stream, the z jobs of G1 on the sort stream, H on the context stream
+    ZK_TRY(zk_msm_enqueue_accum(ctx, &J[0], s_acc));
+    ZK_TRY(zk_msm_enqueue_reduce(ctx, &J[0], s_acc));
+    for (int j = 1; j <= 3; j++) {
+        ZK_TRY(zk_msm_enqueue_accum(ctx, &J[j], s_sort));
+        ZK_TRY(zk_msm_enqueue_reduce(ctx, &J[j], s_sort));
+    }
+    ZK_TRY(zk_msm_enqueue_accum(ctx, &J[4], ctx->stream));
+    ZK_TRY(zk_msm_enqueue_reduce(ctx, &J[4], ctx->stream));
+    std::vector<zk_g1_projective> a(cnt), b1(cnt), l(cnt), hs(cnt);
+    std::vector<zk_g2_projective> b2(cnt);
+    ZK_TRY(zk_msm_finish_multi(ctx, &J[0], b2.data()));
+    ZK_TRY(zk_msm_finish_multi(ctx, &J[1], a.data()));
+    ZK_TRY(zk_msm_finish_multi(ctx, &J[2], b1.data()));
+    ZK_TRY(zk_msm_finish_multi(ctx, &J[3], l.data()));
+    ZK_TRY(zk_msm_finish_multi(ctx, &J[4], hs.data()));
+    pre_ready();
+    over_ranges(ctx, cnt, TAIL_TASKS, [&](size_t lo, size_t hi) {
+        for (size_t k = lo; k < hi; k++) zk_proof_tail_rest(pk, pre[k], a[k], b1[k], b2[k], hs[k], l[k], proofs + k * 192);
+    });
+    return ZK_OK;
+}
+
+// device bytes the MSM jobs of a chunk of cnt proofs need: per job its sort (sorted entries, keys, values and the segment tables:
+// ~16 bytes per digit) and its bucket sums (with room for split buckets)
+size_t chunk_bytes(const zk_pk* pk, const zk_r1cs* r, size_t cnt) {
+    const size_t D = (size_t)1 << r->log_d, nvars = r->ni + r->nw - 1;
+    size_t bytes = 0;
+    const zk_bases* tabs[5] = {pk->b_g2, pk->a, pk->b_g1, pk->l_pad ? pk->l_pad : pk->l, pk->h};
+    const size_t lens[5] = {nvars, nvars, nvars, pk->l_pad ? nvars : r->nw, std::min(pk->h->n, D)};
+    for (int j = 0; j < 5; j++) {
+        const size_t W = tabs[j]->pre ? (255 + tabs[j]->c_pre - 1) / tabs[j]->c_pre : 32;
+        const size_t XW = tabs[j]->group == 1 ? 48 : 96;
+        const size_t buckets = tabs[j]->pre ? ((size_t)1 << (tabs[j]->c_pre - 1)) : W * std::max<size_t>(lens[j], 16);
+        bytes += cnt * (lens[j] * W * 16 + buckets * XW * 4 * 2);
+    }
+    return bytes;
+}
+
+// The key against the system, the proofs per MSM chunk, and the device memory: the assignments (count m elements: the caller's,
+// or the host form's upload) and the witness map's 6 count D elements (a | b | c and the transforms' scratch), plus one chunk's
+// MSM scratch, against 90 % of the free memory.
+int batch_plan(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size_t* chunk_out) {
+    const size_t m = r->ni + r->nw, nvars = m - 1, D = (size_t)1 << r->log_d;
+    if (!pk->a || !pk->b_g1 || !pk->b_g2 || !pk->l || !pk->h || pk->a->n != nvars + 1 || pk->b_g1->n != nvars + 1 ||
+        pk->b_g2->n != nvars + 1 || pk->l->n != r->nw || r->ni < 1)
+        ZK_FAIL(ctx, ZK_ERR_ARG, "groth16 batch: proving key does not match the constraint system");
+    // proofs per chunk: every job's bucket spaces within what one multi job takes (zk_msm_multi_chunk)
+    size_t chunk = count;
+    chunk = std::min(chunk, zk_msm_multi_chunk(pk->b_g2, nvars));
+    chunk = std::min(chunk, zk_msm_multi_chunk(pk->a, nvars));
+    chunk = std::min(chunk, zk_msm_multi_chunk(pk->b_g1, nvars));
+    chunk = std::min(chunk, zk_msm_multi_chunk(pk->l, r->nw));
+    if (pk->l_pad) chunk = std::min(chunk, zk_msm_multi_chunk(pk->l_pad, nvars));
+    chunk = std::min(chunk, zk_msm_multi_chunk(pk->h, std::min(pk->h->n, D)));
+    size_t free_b = 0, total_b = 0;
+    ZK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    const double need = (double)count * (double)(m + 6 * D) * 32.0 + (double)chunk_bytes(pk, r, chunk);
+    if (need > (double)(free_b / 10 * 9))
+        ZK_FAIL(ctx, ZK_ERR_NOMEM, "groth16 batch: the working set of " + std::to_string(count) + " proofs (" +
+                                       std::to_string((unsigned long long)(need / 1048576.0)) + " MiB) does not fit the free device memory (" +
+                                       std::to_string(free_b >> 20) + " MiB)");
+    *chunk_out = chunk;
+    return ZK_OK;
+}
+
+// a device allocation of this call only (the batch's buffers grow with count: not kept in the context's grow-only scratch arena)
+struct CallMem {
+    zk_ctx* ctx;
+    void* p = nullptr;
+    ~CallMem() {
+        if (!p) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+    }
+};
+
+int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size_t chunk, const void* z_dev, const zk_fr* r_,
+              const zk_fr* s_, uint8_t* proofs_out) {
+    const size_t m = r->ni + r->nw, D = (size_t)1 << r->log_d;
+    // an announced next assignment (zk_groth16_hint_next_dev, zk_groth16_prove_queued) is drained and dropped: its front reads
+    // scratch this call does not own, and the next single proof is not the one it was announced for
+    zk_presort_free(ctx);
+    if (ctx->copy_stream) ZK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    ctx->next_z = nullptr;
+    ctx->next_z_host = nullptr;
+    ctx->next_z_dev = nullptr;
+    ctx->next_z_pk = ctx->next_z_r = nullptr;
+    ctx->next_z_m = 0;
+    if (count == 1) return zk_groth16_prove_dev(ctx, pk, r, z_dev, r_, s_, proofs_out);
+    ZK_TRY(zk_prover_streams(ctx, 1));
+    CallMem wm{ctx};
+    ZK_HIP(ctx, hipMalloc(&wm.p, count * 6 * D * 32));
+    std::vector<ZkTailPre> pre(count);
+    // the terms of the tails that need no MSM result, beside the device work (prove_chunk waits for them before its tails)
+    ZkTask<void> pre_task = zk_async(ctx, [&] {
+        over_ranges(ctx, count, PRE_TASKS, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) zk_proof_tail_pre(pk, &r_[k], &s_[k], &pre[k]); });
+    });
+    const std::function<void()> pre_ready = [&] { if (pre_task.valid()) pre_task.get(); };
+    const std::function<int()> wmap = [&] { return zk_groth16_witness_map_batch(ctx, r, count, z_dev, wm.p); };
+    const std::function<int()> none = [] { return ZK_OK; };
+    int rc = ZK_OK;
+    for (size_t k0 = 0; k0 < count && rc == ZK_OK; k0 += chunk)
+        rc = prove_chunk(ctx, pk, r, std::min(chunk, count - k0), (const char*)z_dev + k0 * m * 32, (const char*)wm.p + k0 * D * 32,
+                         k0 == 0 ? wmap : none, pre_ready, pre.data() + k0, proofs_out + k0 * 192);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int zk_groth16_prove_batch_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, const void* z_dev, const zk_fr* r_,
+                                          const zk_fr* s_, uint8_t* proofs_out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !pk || !r || !count || !z_dev || !r_ || !s_ || !proofs_out) return ZK_ERR_ARG;
+    size_t chunk;
+    ZK_TRY(batch_plan(ctx, pk, r, count, &chunk));
+    return run_batch(ctx, pk, r, count, chunk, z_dev, r_, s_, proofs_out);
+    ZK_API_END
+}
+
+extern "C" int zk_groth16_prove_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, const zk_fr* z_host, const zk_fr* r_,
+                                      const zk_fr* s_, uint8_t* proofs_out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !pk || !r || !count || !z_host || !r_ || !s_ || !proofs_out) return ZK_ERR_ARG;
+    size_t chunk;
+    ZK_TRY(batch_plan(ctx, pk, r, count, &chunk));                 // before the upload: the assignments are part of the working set
+    const size_t m = r->ni + r->nw;
+    CallMem z{ctx};
+    ZK_HIP(ctx, hipMalloc(&z.p, count * m * 32));
+    ZK_TRY(zk_xfer_h2d(ctx, z.p, z_host, count * m * 32, zk_host_is_pinned(z_host)));
+    return run_batch(ctx, pk, r, count, chunk, z.p, r_, s_, proofs_out);
+    ZK_API_END
+}

@@ -83,7 +83,10 @@ int zk_prover_streams(zk_ctx* ctx, size_t k);
 // after_abc runs on the calling thread as soon as A, B-in-G1 and B-in-G2 have delivered.
 int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h_in, void* h_scratch,
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc = nullptr);
-int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: see zk_pk::l_pad
+int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);
+// r1cs.hip: the witness map of count assignments (count x m elements back to back) with launches that do not grow with count;
+// abc = room for 6 count D elements, the count quotients in its first count D on return
+int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);     // groth16_key.hip: see zk_pk::l_pad
 
 // The O(1) host tail of a proof (groth16_prove.hip).  The chains run on the context's helper threads and reference this object:
 // declare it after the MSM sums it reads; the destructor joins.
@@ -113,6 +116,17 @@ class ZkProofTail {
     void join();
     void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
 };
+
+// The same tail for the proofs of a batch (groth16_batch.hip), on the calling thread: the terms that need no MSM result first (they
+// run while the device works), then the rest.  The operations of ZkProofTail, in the same order: the same bytes.
+struct ZkTailPre {
+    uint32_t rw[8], sw[8];
+    zk::XYZZ<zk::Fq64Field> r_g1, r_s_delta, s_g1;
+    zk::XYZZ<zk::Fq264Field> s_g2;
+};
+void zk_proof_tail_pre(const zk_pk* pk, const zk_fr* r, const zk_fr* s, ZkTailPre* t);
+void zk_proof_tail_rest(const zk_pk* pk, const ZkTailPre& t, const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum,
+                        const zk_g2_projective& b2_sum, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
 
 namespace zk {
 template <class F>

@@ -71,6 +71,46 @@ void ZkProofTail::finish(const zk_g1_projective& h_sum, const zk_g1_projective& 
     g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
 }
 
+void zk_proof_tail_pre(const zk_pk* pk, const zk_fr* r, const zk_fr* s, ZkTailPre* t) {
+    using H1 = Fq64Field;
+    using H2 = Fq264Field;
+    const bool glv = pk->points_in_subgroup;
+    auto mul1 = [glv](const XYZZ<H1>& p, const uint32_t* k) { return glv ? host64_scalar_mul_glv(p, k) : host64_scalar_mul<H1>(p, k); };
+    fr_abi_to_canon_words(r->l, t->rw);
+    fr_abi_to_canon_words(s->l, t->sw);
+    const XYZZ<H1> delta1 = xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk->delta_g1));
+    t->r_g1 = mul1(delta1, t->rw);
+    t->r_s_delta = mul1(t->r_g1, t->sw);
+    t->s_g1 = mul1(delta1, t->sw);
+    t->s_g2 = host64_scalar_mul<H2>(xyzz_from_affine<H2>(aff_to_host64<G2Field>(pk->delta_g2)), t->sw);
+}
+
+void zk_proof_tail_rest(const zk_pk* pk, const ZkTailPre& t, const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum,
+                        const zk_g2_projective& b2_sum, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
+    using H1 = Fq64Field;
+    using H2 = Fq264Field;
+    const bool glv = pk->points_in_subgroup;
+    auto mul1 = [glv](const XYZZ<H1>& p, const uint32_t* k) { return glv ? host64_scalar_mul_glv(p, k) : host64_scalar_mul<H1>(p, k); };
+    const XYZZ<H1> a_acc = host64_proj_from_abi<H1>((const uint64_t*)&a_sum);
+    const XYZZ<H1> b1_acc = host64_proj_from_abi<H1>((const uint64_t*)&b1_sum);
+    const XYZZ<H2> b2_acc = host64_proj_from_abi<H2>((const uint64_t*)&b2_sum);
+    const XYZZ<H1> g_a = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(t.r_g1, aff_to_host64<G1Field>(pk->a0)), a_acc),
+                                       aff_to_host64<G1Field>(pk->alpha_g1));
+    const XYZZ<H1> s_g_a = mul1(g_a, t.sw);
+    const XYZZ<H1> g1_b = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(t.s_g1, aff_to_host64<G1Field>(pk->b0_g1)), b1_acc),
+                                        aff_to_host64<G1Field>(pk->beta_g1));
+    const XYZZ<H1> r_g1_b = mul1(g1_b, t.rw);
+    const XYZZ<H2> g2_b = xyzz_madd<H2>(xyzz_add<H2>(xyzz_madd<H2>(t.s_g2, aff_to_host64<G2Field>(pk->b0_g2)), b2_acc),
+                                        aff_to_host64<G2Field>(pk->beta_g2));
+    XYZZ<H1> g_c = xyzz_add<H1>(s_g_a, r_g1_b);
+    g_c = xyzz_add<H1>(g_c, xyzz_neg<H1>(t.r_s_delta));
+    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&l_sum));
+    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&h_sum));
+    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_a)), proof);
+    g2_serialize(aff_from_host64<G2Field>(xyzz_to_affine<H2>(g2_b)), proof + 48);
+    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
+}
+
 extern "C" int zk_groth16_prove_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const zk_fr* r_, const zk_fr* s_,
                                     uint8_t proof[192]) {
     ZK_API_BEGIN(ctx)

@@ -14,6 +14,10 @@ extern "C" int zk_comm_destroy(zk_ctx* ctx);
 extern "C" int zk_fr_sum_parties_dev(zk_ctx* ctx, const void* gathered_dev, size_t n_parties, size_t n, void* out_dev);
 int zk_ntt_launch(zk_ctx* ctx, void* buf_dev, uint32_t log_n, int inverse, int coset);
 int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs_dev, int count, uint32_t log_n, int inverse, int coset);   // count <= 4, same size and kind, one launch per pass
+// count transforms of one size and kind in place at base + k * stride elements (stride >= 2^log_n): one launch per pass whatever
+// count is (up to 65535 transforms per launch).  tmp: room for min(count, 65535) 2^log_n elements for transforms of more than one pass
+// (2^log_n > 2^10), or NULL for the context's grow-only "ntt_tmp" slot
+int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp = nullptr);
 int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
 
 // vec_ops.hip
@@ -170,6 +174,9 @@ struct ZkMsmJob {
     void *desc = nullptr, *heavy = nullptr, *heavy2 = nullptr;
     size_t max_heavy2 = 0, max_heavy_segs = 0, max_groups = 0;
     std::vector<ZkPhaseTimer*> timers;
+    // several scalar vectors over one table (zk_msm_prepare_multi): n = mcount * mn scalars, vector k at scalars + k * mstride
+    // elements; Wb = mcount bucket sets of the vector's geometry back to back
+    size_t mcount = 0, mn = 0, mstride = 0;
     ~ZkMsmJob();
 };
 int zk_msm_prepare(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n, int slot);
@@ -177,6 +184,12 @@ int zk_msm_enqueue_sort(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJ
 int zk_msm_enqueue_accum(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st);
 int zk_msm_enqueue_reduce(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st);
 int zk_msm_finish(zk_ctx* ctx, ZkMsmJob* job, void* out_host_projective);
+// count vectors of n scalars (stride elements apart) over one table as ONE job: the same launches as one MSM whatever count is.
+// Callers keep count * buckets per vector within zk_msm_multi_chunk.  finish_multi writes count projective points.
+int zk_msm_prepare_multi(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n,
+                         size_t stride, size_t count, int slot);
+size_t zk_msm_multi_chunk(const zk_bases* bases, size_t n);      // vectors of n scalars one multi job takes at most
+int zk_msm_finish_multi(zk_ctx* ctx, ZkMsmJob* job, void* outs_host_projective);
 // Several SMALL G1 jobs (sorted already, tables of window multiples with the same bucket count) as one accumulate launch and one
 // launch per level of the reduce chain; zk_msm_group_ok says whether a set qualifies (else: the per-job calls above)
 int zk_msm_finish_many(zk_ctx* ctx, ZkMsmJob* const* jobs, void* const* outs, int count);      // the host halves side by side

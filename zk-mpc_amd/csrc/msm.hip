@@ -827,7 +827,8 @@ int msm_bufs_t(zk_ctx* ctx, ZkMsmJob* job, MsmBufs<F>& b, bool need_sort) {
     char nm[64];
     auto slotname = [&](const char* base) { snprintf(nm, sizeof nm, "%s.%d", base, job->slot); return nm; };
     if (need_sort) {
-        ZK_TRY(zk_scratch(ctx, slotname("msm_dig"), W * n * 4, (void**)&b.dig));
+        b.dig = nullptr;                                      // (a multi job always takes the bucket sort: no digit array)
+        if (!job->mcount) ZK_TRY(zk_scratch(ctx, slotname("msm_dig"), W * n * 4, (void**)&b.dig));
         ZK_TRY(zk_scratch(ctx, slotname("msm_sorted"), W * n * 4, (void**)&b.sorted));
         ZK_TRY(zk_scratch(ctx, slotname("msm_counts"), nbuck * 4, (void**)&b.counts));
         ZK_TRY(zk_scratch(ctx, slotname("msm_offs"), Wb * (NB + 1) * 4, (void**)&b.offs));
@@ -855,6 +856,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     const size_t n = job->n;
     const bool share_merged = share && share->Wb == 1 && share->W > 1;       // entries are table indices w * n_tab + tab_off + i
     if (share && share->n == n && share->scalars == job->scalars && share->sorted && share->Wb == job->Wb &&
+        share->mcount == job->mcount && share->mstride == job->mstride &&
         share->n_tab == job->n_tab && (share->tab_off == job->tab_off || share_merged) && share->c == job->c) {
         // same scalar vector as an earlier job (A, B-in-G1 and B-in-G2 all use z[1..]): reuse its sort.  A different offset into a
         // table of window multiples (a polynomial's commitment over the shifted powers: marlin_pc/mod.rs:172-243) folds into
@@ -872,9 +874,10 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     MsmBufs<F> b;
     ZK_TRY(msm_bufs_t<F>(ctx, job, b, true));
     const uint32_t W = job->W, NB = job->NB, seg = job->seg, Wb = job->Wb;
-    const int merged = Wb == 1 && W > 1;
+    const uint32_t Wbv = job->mcount ? Wb / (uint32_t)job->mcount : Wb;    // bucket sets of one vector
+    const int merged = Wbv == 1 && W > 1;
     const size_t nbuck = (size_t)Wb * NB;
-    const MsmPlan p = make_plan(n, merged ? job->c : 0);
+    const MsmPlan p = make_plan(job->mcount ? job->mn : n, merged ? job->c : 0);
     Bias bias;
     WinOff wo;
     for (int i = 0; i < 65; i++) wo.off[i] = job->off[i];
@@ -888,7 +891,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
     job->timers.push_back(tm);
     tm->begin(g1 ? "msm_g1.sort" : "msm_g2.sort");
-    const bool one_block = merged && (size_t)W * n <= SS_MAX_ENTRIES && NB <= SS_MAX_NB && seg <= SS_MAX_SEG;      // k_sort_small: writes all of ctr itself
+    const bool one_block = !job->mcount && merged && (size_t)W * n <= SS_MAX_ENTRIES && NB <= SS_MAX_NB && seg <= SS_MAX_SEG;      // k_sort_small: writes all of ctr itself
     const uint32_t grp_base = (uint32_t)(nbuck + job->max_heavy_segs);       // where the group sums of two-level buckets live in `sums`
     auto scans = [&](uint32_t Wx, uint32_t NBx) -> int {      // counting-sort path only: one block per window
         if (NBx > 65536) ZK_FAIL(ctx, ZK_ERR_ARG, "msm: a bucket set of more than 2^16 buckets needs the bucket sort (>= 2^16 digits)");
@@ -903,6 +906,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     ga.n_tab = job->n_tab; ga.tab_off = job->tab_off; ga.NBt = (uint32_t)nbuck;
     ga.lanes = (uint32_t)ctx->n_cu * 4 * 64 * 2; ga.seg_max = seg;
     ga.sorted = b.sorted; ga.offs = b.offs; ga.ctr = ctr;
+    if (job->mcount) { ga.vec_n = (uint32_t)job->mn; ga.vec_nb = Wbv * NB; ga.vec_stride = job->mstride; }
     // ... and for every bucket set the counting sort's one-block-per-window scan cannot take (a short MSM over a table of
     // window multiples with c = 20: 2^19 buckets whatever n is -- the bucket sort is correct for any total)
     if (one_block) {
@@ -930,14 +934,15 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     {
         auto put = [&](const void* p, size_t nbytes) { gkey.append((const char*)p, nbytes); };
         const uint64_t words[] = {ctx->scratch_gen, (uint64_t)(uintptr_t)job->scalars, (uint64_t)n, W, NB, Wb, job->c, seg, (uint64_t)job->slot,
-                                  (uint64_t)merged, job->n_tab, job->tab_off, (uint64_t)job->max_segs, (uint64_t)job->max_heavy_segs, (uint64_t)g1};
+                                  (uint64_t)merged, job->n_tab, job->tab_off, (uint64_t)job->max_segs, (uint64_t)job->max_heavy_segs, (uint64_t)g1,
+                                  (uint64_t)job->mcount, (uint64_t)job->mstride};
         put(words, sizeof words);
         put(job->off, sizeof job->off);
     }
     ZK_TRY(zk_graph_run(ctx, gkey, st, [&]() -> int {
         uint32_t flat_buckets = 0;
         if (!one_block) ZK_HIP(ctx, hipMemsetAsync(b.small, 0, (64 + 8 + 3 * (size_t)(seg + 1)) * 4, st));
-        if (((size_t)W * n >= 65536 || NB > 65536) && zk_msm_group_supported(ga)) {
+        if (job->mcount || (((size_t)W * n >= 65536 || NB > 65536) && zk_msm_group_supported(ga))) {
             const uint32_t NBt = (uint32_t)nbuck;
             ZK_TRY(zk_msm_group(ctx, st, job->slot, ga));
             hipLaunchKernelGGL(k_build_segs, zk_grid(nbuck, 256, 512), 256, (seg + 1) * 4, st, b.offs, (const uint32_t*)nullptr, win_segs,
@@ -1226,9 +1231,30 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     return ZK_OK;
 }
 
+// window sum = 2^cl * sum_j 2^j rowbit_j + sum_j 2^j colbit_j + (plain sum): ONE Horner chain over the row bits followed by
+// the column bits (msm_reduce.cuh), then Horner over the windows, most significant first (variable_base.rs:94-105).  All
+// in the 64-bit host field.  w counts bucket sets in job->hw.
+template <class F>
+XYZZ<typename Host64Of<F>::type> msm_window_sum(const ZkMsmJob* job, size_t w) {
+    constexpr size_t XW = 4 * F::WORDS;
+    using H = typename Host64Of<F>::type;
+    const uint32_t nout = job->nout;
+    const uint32_t* base = job->hw + w * nout * XW;
+    XYZZ<H> ws = xyzz_inf<H>();
+    const uint32_t cl = job->log_nb / 2, rl = job->log_nb - cl;
+    for (int j = (int)rl - 1; j >= 0; j--) {
+        ws = xyzz_dbl<H>(ws);
+        ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)j * XW)));
+    }
+    for (int j = (int)cl - 1; j >= 0; j--) {
+        ws = xyzz_dbl<H>(ws);
+        ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(rl + j) * XW)));
+    }
+    return xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(nout - 1) * XW)));
+}
+
 template <class F>
 int msm_finish_t(zk_ctx* ctx, ZkMsmJob* job, void* out_host) {
-    constexpr size_t XW = 4 * F::WORDS;
     if (job->n == 0) {
         host_write_projective<F>(aff_inf<F>(), (uint64_t*)out_host);
         return ZK_OK;
@@ -1236,25 +1262,8 @@ int msm_finish_t(zk_ctx* ctx, ZkMsmJob* job, void* out_host) {
     if (job->reduce_done) ZK_HIP(ctx, hipEventSynchronize(job->reduce_done));
     else ZK_HIP(ctx, hipStreamSynchronize(job->stream));
     for (auto* t : job->timers) t->resolve();
-    // window sum = 2^cl * sum_j 2^j rowbit_j + sum_j 2^j colbit_j + (plain sum): ONE Horner chain over the row bits followed by
-    // the column bits (msm_reduce.cuh), then Horner over the windows, most significant first (variable_base.rs:94-105).  All
-    // in the 64-bit host field.
     using H = typename Host64Of<F>::type;
-    const uint32_t nout = job->nout;
-    auto window_sum = [&](uint32_t w) {
-        const uint32_t* base = job->hw + (size_t)w * nout * XW;
-        XYZZ<H> ws = xyzz_inf<H>();
-        const uint32_t cl = job->log_nb / 2, rl = job->log_nb - cl;
-        for (int j = (int)rl - 1; j >= 0; j--) {
-            ws = xyzz_dbl<H>(ws);
-            ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)j * XW)));
-        }
-        for (int j = (int)cl - 1; j >= 0; j--) {
-            ws = xyzz_dbl<H>(ws);
-            ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(rl + j) * XW)));
-        }
-        return xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(nout - 1) * XW)));
-    };
+    auto window_sum = [&](uint32_t w) { return msm_window_sum<F>(job, w); };
     XYZZ<H> total = xyzz_inf<H>();
     // the per-window Horner chains (~15 doublings + 16 additions each for 16 windows) are independent: four host threads take
     // them, because the last job's finish sits on the proof's critical path.  A merged bucket set is one window: one chain.
@@ -1287,6 +1296,75 @@ int msm_run_t(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void
     if (rc == ZK_OK) rc = msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream);
     if (rc == ZK_OK) rc = msm_finish_t<F>(ctx, &job, out_host);
     return rc;
+}
+
+// ---- several scalar vectors over one table as ONE job ----
+// The vectors' digits go to count bucket spaces of the one-vector geometry (msm_sort.hip: VecMap), so the sort, the accumulate kernel
+// and the reduce chain see one job of count * n scalars and count * Wb bucket sets: the same launches as one MSM.  The accumulate
+// kernel is unchanged -- it only ever sees bucket ranges and table entries, and every vector's entries are those of the one table.
+// The bucket sort takes at most 2^22 buckets (G_MAXNC bins of 2^10), and a job keeps to 2^28 digits (uint32 counters, ~2.5 GiB of
+// sort scratch): zk_msm_multi_chunk says how many vectors that is; callers cut larger counts into jobs of that many.
+constexpr size_t MULTI_MAX_BUCKETS = (size_t)1 << 22, MULTI_MAX_DIGITS = (size_t)1 << 28;
+
+template <class F>
+int msm_prepare_multi_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars, size_t n, size_t stride,
+                        size_t count, int slot) {
+    if (n == 0 || count == 0 || stride < n) ZK_FAIL(ctx, ZK_ERR_ARG, "msm multi: n, count >= 1 and stride >= n");
+    ZK_TRY(msm_prepare_t<F>(ctx, job, bases, base_offset, scalars, n, slot));       // the geometry of ONE vector
+    if (count > zk_msm_multi_chunk(bases, n)) ZK_FAIL(ctx, ZK_ERR_ARG, "msm multi: too many vectors for one job");
+    job->mcount = count; job->mn = n; job->mstride = stride;
+    job->n = n * count;
+    job->Wb *= (uint32_t)count;
+    const size_t lanes = (size_t)ctx->n_cu * 4 * 64 * 2, digits = job->n * job->W;   // the segment length of msm_prepare_t, for all digits
+    const size_t per_lane = (digits + lanes - 1) / lanes;
+    uint32_t seg = digits <= ((size_t)1 << 19) ? 8 : 32;
+    while (seg < per_lane && seg < 4096) seg <<= 1;
+    job->seg = seg;
+    return ZK_OK;
+}
+
+template <class F>
+int msm_finish_multi_t(zk_ctx* ctx, ZkMsmJob* job, void* outs) {
+    using H = typename Host64Of<F>::type;
+    using P = typename std::conditional<F::WORDS == 12, zk_g1_projective, zk_g2_projective>::type;
+    if (job->reduce_done) ZK_HIP(ctx, hipEventSynchronize(job->reduce_done));
+    else ZK_HIP(ctx, hipStreamSynchronize(job->stream));
+    for (auto* t : job->timers) t->resolve();
+    const size_t count = job->mcount, nwin = job->Wb / count;
+    auto one = [&](size_t k) {
+        XYZZ<H> total = xyzz_inf<H>();
+        for (int w = (int)nwin - 1; w >= 0; w--) {
+            const uint32_t cw = nwin == 1 ? 0u : (uint32_t)(job->off[w + 1] - job->off[w]);
+            for (uint32_t b = 0; b < cw; b++) total = xyzz_dbl<H>(total);
+            total = xyzz_add<H>(total, msm_window_sum<F>(job, k * nwin + (size_t)w));
+        }
+        host64_write_projective<H>(xyzz_to_affine<H>(total), (uint64_t*)((P*)outs + k));
+    };
+    // contiguous ranges of vectors on at most eight threads (a vector of a merged table is one window: ~30 us; of a plain one ~0.5 ms)
+    const size_t nt = std::min<size_t>(count, 8), per = (count + nt - 1) / nt;
+    std::vector<ZkTask<void>> tasks;
+    for (size_t t = 1; t < nt; t++)
+        tasks.push_back(zk_async(ctx, [&, t] { for (size_t k = t * per; k < std::min(count, (t + 1) * per); k++) one(k); }));
+    for (size_t k = 0; k < std::min(count, per); k++) one(k);
+    for (auto& f : tasks) f.get();
+    return ZK_OK;
+}
+
+template <class F>
+int msm_multi_run_t(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const char* scalars, size_t n, size_t stride, size_t count,
+                    void* outs) {
+    using P = typename std::conditional<F::WORDS == 12, zk_g1_projective, zk_g2_projective>::type;
+    const size_t chunk = zk_msm_multi_chunk(bases, n);
+    for (size_t k0 = 0; k0 < count; k0 += chunk) {
+        ZkMsmJob job;
+        const size_t cnt = std::min(chunk, count - k0);
+        ZK_TRY(msm_prepare_multi_t<F>(ctx, &job, bases, base_offset, scalars + k0 * stride * 32, n, stride, cnt, 8));
+        ZK_TRY(msm_enqueue_sort_t<F>(ctx, &job, ctx->stream, nullptr));
+        ZK_TRY(msm_enqueue_accum_t<F>(ctx, &job, ctx->stream));
+        ZK_TRY(msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream));
+        ZK_TRY(msm_finish_multi_t<F>(ctx, &job, (P*)outs + k0));
+    }
+    return ZK_OK;
 }
 
 // A host table -> a resident one.  layout == NULL: the ABI's packed form (zk_g1_affine / zk_g2_affine, all-zero = infinity);
@@ -1735,6 +1813,21 @@ int zk_msm_finish(zk_ctx* ctx, ZkMsmJob* job, void* out) {
     if (job->group == 1) return msm_finish_t<G1Field>(ctx, job, out);
     return msm_finish_t<G2Field>(ctx, job, out);
 }
+size_t zk_msm_multi_chunk(const zk_bases* bases, size_t n) {
+    const bool merged = bases->pre != nullptr && (n >= 4096 || n * 8 >= bases->n);     // msm_prepare_t's choice
+    const MsmPlan p = make_plan(n, merged ? bases->c_pre : 0);
+    const size_t buckets = (size_t)(merged ? 1 : p.W) * p.NB, digits = (size_t)p.W * n;
+    return std::max<size_t>(1, std::min(MULTI_MAX_BUCKETS / buckets, MULTI_MAX_DIGITS / digits));
+}
+int zk_msm_prepare_multi(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n,
+                         size_t stride, size_t count, int slot) {
+    if (bases->group == 1) return msm_prepare_multi_t<G1Field>(ctx, job, bases, base_offset, scalars_dev, n, stride, count, slot);
+    return msm_prepare_multi_t<G2Field>(ctx, job, bases, base_offset, scalars_dev, n, stride, count, slot);
+}
+int zk_msm_finish_multi(zk_ctx* ctx, ZkMsmJob* job, void* outs) {
+    if (job->group == 1) return msm_finish_multi_t<G1Field>(ctx, job, outs);
+    return msm_finish_multi_t<G2Field>(ctx, job, outs);
+}
 
 int zk_msm_run(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n, void* out) {
     if (bases->group == 1) return msm_run_t<G1Field>(ctx, bases, base_offset, scalars_dev, n, out);
@@ -1913,6 +2006,27 @@ extern "C" int zk_msm_g2_dev(zk_ctx* ctx, const zk_bases* bases, size_t off, con
     ZK_API_BEGIN(ctx)
     if (!ctx || !bases || !out || bases->group != 2 || (n && !scalars)) return ZK_ERR_ARG;
     return msm_run_t<G2Field>(ctx, bases, off, scalars, n, out);
+    ZK_API_END
+}
+
+// count vectors at once (zk_msm_g1_multi_dev): n >= 1, stride >= n, base_offset + n <= the table
+static bool multi_args_ok(const zk_bases* bases, int group, size_t off, const void* scalars, size_t n, size_t stride, size_t count,
+                          const void* outs) {
+    return bases && outs && scalars && bases->group == group && n >= 1 && count >= 1 && stride >= n && off <= bases->n &&
+           n <= bases->n - off && count <= ((size_t)1 << 32) / stride;
+}
+extern "C" int zk_msm_g1_multi_dev(zk_ctx* ctx, const zk_bases* bases, size_t off, const void* scalars, size_t n, size_t stride,
+                                   size_t count, zk_g1_projective* outs) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !multi_args_ok(bases, 1, off, scalars, n, stride, count, outs)) return ZK_ERR_ARG;
+    return msm_multi_run_t<G1Field>(ctx, bases, off, (const char*)scalars, n, stride, count, outs);
+    ZK_API_END
+}
+extern "C" int zk_msm_g2_multi_dev(zk_ctx* ctx, const zk_bases* bases, size_t off, const void* scalars, size_t n, size_t stride,
+                                   size_t count, zk_g2_projective* outs) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !multi_args_ok(bases, 2, off, scalars, n, stride, count, outs)) return ZK_ERR_ARG;
+    return msm_multi_run_t<G2Field>(ctx, bases, off, (const char*)scalars, n, stride, count, outs);
     ZK_API_END
 }
 

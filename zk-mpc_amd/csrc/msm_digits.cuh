@@ -50,6 +50,11 @@ struct ZkGroupArgs {
     uint32_t* sorted;         // out: the entries grouped by bucket (room for W * n)
     uint32_t* offs;           // out: NBt + 1 bucket starts (offs[NBt] = the number of non-zero digits)
     uint32_t* ctr;            // out: ctr[3] = the segment length for this input, ctr[4] = the number of non-zero digits
+    // several vectors over one table (zk_msm_g1_multi_dev): scalar j of the n is element i = j % vec_n of vector k = j / vec_n, read
+    // at k * vec_stride + i; its digits go to the k-th of n / vec_n bucket spaces of vec_nb buckets, its entries are those of i.
+    // vec_n = 0: one vector.
+    uint32_t vec_n = 0, vec_nb = 0;
+    size_t vec_stride = 0;
 };
 bool zk_msm_group_supported(const ZkGroupArgs& a);
 int zk_msm_group(zk_ctx* ctx, hipStream_t st, int slot, const ZkGroupArgs& a);

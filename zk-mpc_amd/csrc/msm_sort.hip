@@ -35,6 +35,23 @@ constexpr uint32_t G_MAXNC = 4096;       // bins (k_scan: 4 per lane of one bloc
 constexpr uint32_t G_NONE = 0xffffffffu;
 
 struct GroupGeom { uint32_t W, NB, merged, n_tab, tab_off, NBt, F, NC; };
+// several vectors (ZkGroupArgs::vec_n): scalar j is element j % n of vector j / n, read at (j / n) * stride + j % n; its buckets are
+// offset by (j / n) * nb
+struct VecMap { uint32_t n, nb; size_t stride; };
+// scalar j of the kernels' flat range -> its place in memory, its index inside its vector and the bucket offset of its vector
+template <bool MULTI>
+__device__ __forceinline__ size_t vec_place(size_t j, const VecMap& vm, uint32_t& idx, uint32_t& bofs) {
+    if constexpr (!MULTI) {
+        idx = (uint32_t)j;
+        bofs = 0;
+        return j;
+    } else {
+        const uint32_t k = (uint32_t)j / vm.n;
+        idx = (uint32_t)j - k * vm.n;
+        bofs = k * vm.nb;
+        return (size_t)k * vm.stride + idx;
+    }
+}
 
 // words of (canonical scalar + bias) of scalar i into column `col` of kw (9 x TW words)
 template <uint32_t TW>
@@ -47,20 +64,21 @@ __device__ __forceinline__ void load_scalar_words(const void* scalars, size_t i,
 // digit w of the scalar in column col: false for a zero digit; bucket = its id among all NBt buckets, neg = the sign bit of the entry
 template <uint32_t TW>
 __device__ __forceinline__ bool tile_digit(const uint32_t (*kw)[TW], uint32_t col, const WinOff& wo, uint32_t w, const GroupGeom& g,
-                                           uint32_t& bucket, uint32_t& neg) {
+                                           uint32_t& bucket, uint32_t& neg, uint32_t bofs = 0) {
     const uint32_t bit = wo.off[w], wi = bit >> 5;
     uint64_t two = kw[wi][col];
     if (wi + 1 < 9) two |= (uint64_t)kw[wi + 1][col] << 32;
     const int32_t d = signed_digit(two, bit, wo.off[w + 1] - bit);
     if (d == 0) return false;
     const uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
-    bucket = (g.merged ? 0u : w * g.NB) + mag - 1;
+    bucket = bofs + (g.merged ? 0u : w * g.NB) + mag - 1;
     neg = d < 0 ? 0x80000000u : 0u;
     return true;
 }
 
+template <bool MULTI>
 __global__ void __launch_bounds__(G_NT)
-k_hist(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g, uint32_t* bin_count) {
+k_hist(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g, uint32_t* bin_count, VecMap vm) {
     extern __shared__ uint32_t g_lds[];
     uint32_t (*kw)[G_TILE] = reinterpret_cast<uint32_t (*)[G_TILE]>(g_lds);
     uint32_t* cnt = g_lds + 9 * G_TILE;
@@ -72,10 +90,11 @@ k_hist(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g, uint32_
             const uint32_t col = tid + k * G_NT;
             const size_t i = t0 + col;
             if (i >= n) continue;
-            load_scalar_words<G_TILE>(scalars, i, bias, kw, col);
+            uint32_t idx, bofs;
+            load_scalar_words<G_TILE>(scalars, vec_place<MULTI>(i, vm, idx, bofs), bias, kw, col);
             for (uint32_t w = 0; w < g.W; w++) {
                 uint32_t bucket, neg;
-                if (tile_digit<G_TILE>(kw, col, wo, w, g, bucket, neg)) atomicAdd(&cnt[bucket >> g.F], 1u);
+                if (tile_digit<G_TILE>(kw, col, wo, w, g, bucket, neg, bofs)) atomicAdd(&cnt[bucket >> g.F], 1u);
             }
         }
     }
@@ -168,8 +187,9 @@ constexpr uint32_t S_CAP = S_TILE * S_WG;
 // LDS words: kw[9][S_TILE] | cursor[NC] | delta[NC] | wsum[16] | stage_val[S_CAP] | stage_key+bin[S_CAP] (two 16-bit halves)
 static size_t scatter_lds_bytes(uint32_t NC) { return (size_t)(9 * S_TILE + 2 * NC + 16 + 2 * S_CAP) * 4; }
 
+template <bool MULTI>
 __global__ void __launch_bounds__(G_NT)
-k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g, uint32_t* cursor, uint16_t* key_lo, uint32_t* val) {
+k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g, uint32_t* cursor, uint16_t* key_lo, uint32_t* val, VecMap vm) {
     extern __shared__ uint32_t g_lds[];
     uint32_t (*kw)[S_TILE] = reinterpret_cast<uint32_t (*)[S_TILE]>(g_lds);
     uint32_t* cur = g_lds + 9 * S_TILE;            // per bin: count, then the bin's cursor inside the stage
@@ -182,8 +202,9 @@ k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g,
     for (size_t t0 = (size_t)blockIdx.x * S_TILE; t0 < n; t0 += (size_t)gridDim.x * S_TILE) {
         const size_t i = t0 + tid;
         const bool have = i < n;
+        uint32_t idx = 0, bofs = 0;                // i inside its vector, the bucket offset of its vector
         __syncthreads();                           // the previous tile's last pass is through with kw
-        if (have) load_scalar_words<S_TILE>(scalars, i, bias, kw, tid);
+        if (have) load_scalar_words<S_TILE>(scalars, vec_place<MULTI>(i, vm, idx, bofs), bias, kw, tid);
         for (uint32_t w0 = 0; w0 < g.W; w0 += S_WG) {
             const uint32_t w1 = min(w0 + S_WG, g.W);
             for (uint32_t b = tid; b < g.NC; b += G_NT) cur[b] = 0;
@@ -191,7 +212,7 @@ k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g,
             if (have)
                 for (uint32_t w = w0; w < w1; w++) {
                     uint32_t bucket, neg;
-                    if (tile_digit<S_TILE>(kw, tid, wo, w, g, bucket, neg)) atomicAdd(&cur[bucket >> g.F], 1u);
+                    if (tile_digit<S_TILE>(kw, tid, wo, w, g, bucket, neg, bofs)) atomicAdd(&cur[bucket >> g.F], 1u);
                 }
             __syncthreads();
             // exclusive scan of the counts over the bins (lane t owns bins t*per .. t*per+per-1), one global reservation per bin
@@ -215,10 +236,10 @@ k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g,
             if (have)
                 for (uint32_t w = w0; w < w1; w++) {
                     uint32_t bucket, neg;
-                    if (!tile_digit<S_TILE>(kw, tid, wo, w, g, bucket, neg)) continue;
+                    if (!tile_digit<S_TILE>(kw, tid, wo, w, g, bucket, neg, bofs)) continue;
                     const uint32_t bin = bucket >> g.F;
                     const uint32_t p = atomicAdd(&cur[bin], 1u);
-                    st_val[p] = (g.merged ? (uint32_t)(w * g.n_tab + g.tab_off + i) : (uint32_t)i) | neg;
+                    st_val[p] = (g.merged ? (uint32_t)(w * g.n_tab + g.tab_off + idx) : idx) | neg;
                     st_kb[p] = (bucket & fmask) | (bin << 16);
                 }
             __syncthreads();
@@ -397,8 +418,10 @@ int zk_msm_group(zk_ctx* ctx, hipStream_t st, int slot, const ZkGroupArgs& a) {
     uint32_t *bin_count = bins, *bin_start = bins + (g.NC + 1), *cursor = bins + 2 * (g.NC + 1), *bin_long = bins + 3 * (g.NC + 1),
              *hdr = bins + 4 * (g.NC + 1);
     if (!ctx->flags["group_lds"]) {
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (9 * G_TILE + G_MAXNC) * 4));
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_scatter_bins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds_bytes(G_MAXNC)));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (9 * G_TILE + G_MAXNC) * 4));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (9 * G_TILE + G_MAXNC) * 4));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_scatter_bins<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds_bytes(G_MAXNC)));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_scatter_bins<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds_bytes(G_MAXNC)));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_bins, hipFuncAttributeMaxDynamicSharedMemorySize, BINS_LDS_WORDS * 4));
         ctx->flags["group_lds"] = 1;
     }
@@ -406,10 +429,13 @@ int zk_msm_group(zk_ctx* ctx, hipStream_t st, int slot, const ZkGroupArgs& a) {
     ZK_HIP(ctx, hipMemsetAsync(ghist, 0, max_long * 2048 * 4, st));
     const unsigned tiles = (unsigned)((a.n + G_TILE - 1) / G_TILE);
     const unsigned pg = tiles < 512 ? tiles : 512;
-    hipLaunchKernelGGL(k_hist, pg, G_NT, (9 * G_TILE + g.NC) * 4, st, a.scalars, a.n, a.wo, a.bias, g, bin_count);
+    const VecMap vm{a.vec_n, a.vec_nb, a.vec_stride};
+    if (a.vec_n) hipLaunchKernelGGL(k_hist<true>, pg, G_NT, (9 * G_TILE + g.NC) * 4, st, a.scalars, a.n, a.wo, a.bias, g, bin_count, vm);
+    else hipLaunchKernelGGL(k_hist<false>, pg, G_NT, (9 * G_TILE + g.NC) * 4, st, a.scalars, a.n, a.wo, a.bias, g, bin_count, vm);
     hipLaunchKernelGGL(k_scan_bins, 1, G_NT, 0, st, (const uint32_t*)bin_count, g, a.lanes, a.seg_max, bin_start, cursor, items, bin_long, hdr,
                        a.ctr);
-    hipLaunchKernelGGL(k_scatter_bins, pg, G_NT, scatter_lds_bytes(g.NC), st, a.scalars, a.n, a.wo, a.bias, g, cursor, key_lo, val);
+    if (a.vec_n) hipLaunchKernelGGL(k_scatter_bins<true>, pg, G_NT, scatter_lds_bytes(g.NC), st, a.scalars, a.n, a.wo, a.bias, g, cursor, key_lo, val, vm);
+    else hipLaunchKernelGGL(k_scatter_bins<false>, pg, G_NT, scatter_lds_bytes(g.NC), st, a.scalars, a.n, a.wo, a.bias, g, cursor, key_lo, val, vm);
     hipLaunchKernelGGL(k_bins_pre, (unsigned)max_items, G_NT, 0, st, (const uint16_t*)key_lo, (const uint32_t*)bin_start, (const uint2*)items,
                        (const uint32_t*)bin_long, (const uint32_t*)hdr, ghist);
     hipLaunchKernelGGL(k_bins, (unsigned)max_items, G_NT, BINS_LDS_WORDS * 4, st, (const uint16_t*)key_lo, (const uint32_t*)val,

@@ -22,6 +22,7 @@
 #include "devutil.cuh"
 #include "frlazy.cuh"
 #include "internal.hpp"
+#include <algorithm>
 
 using namespace zk;
 
@@ -214,15 +215,26 @@ constexpr int NTT_BATCH = 4;
 struct NttBatch {
     const uint32_t* src[NTT_BATCH];
     uint32_t* dst[NTT_BATCH];
+    __device__ const uint32_t* src_of(uint32_t y) const { return src[y]; }
+    __device__ uint32_t* dst_of(uint32_t y) const { return dst[y]; }
 };
-template <int POST>
+// ... or many transforms of one size and kind at a fixed stride (the batched witness map, groth16_batch.hip): transform y reads
+// src + y * src_stride and writes dst + y * dst_stride (32-bit words)
+struct NttStrided {
+    const uint32_t* src;
+    uint32_t* dst;
+    size_t src_stride, dst_stride;
+    __device__ const uint32_t* src_of(uint32_t y) const { return src + y * src_stride; }
+    __device__ uint32_t* dst_of(uint32_t y) const { return dst + y * dst_stride; }
+};
+template <int POST, class B>
 __global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_pass(NttBatch nb, const uint32_t* __restrict__ tw,
+k_ntt_pass(B nb, const uint32_t* __restrict__ tw,
            const uint32_t* __restrict__ pre, uint32_t log_n, uint32_t logS, uint32_t logM, uint32_t logC, int inverse,
            int final_rev, FrK post_k, const uint32_t* __restrict__ post) {
     extern __shared__ uint32_t lds[];
-    const uint32_t* data = nb.src[blockIdx.y];
-    uint32_t* out = nb.dst[blockIdx.y];
+    const uint32_t* data = nb.src_of(blockIdx.y);
+    uint32_t* out = nb.dst_of(blockIdx.y);
     const uint32_t C = 1u << logC, E = C << logM;
     const uint32_t N1 = (1u << log_n) - 1;
     const uint32_t tid = threadIdx.x, NT = blockDim.x;
@@ -274,9 +286,20 @@ k_ntt_pass(NttBatch nb, const uint32_t* __restrict__ tw,
     }
 }
 
-// In-place bit reversal fused with the post-scale: MODE 0 none, 1 constant k, 2 table post[i].
-template <int MODE>
-__global__ void __launch_bounds__(256) k_bitrev_scale(uint32_t* data, uint32_t log_n, FrK k, const uint32_t* post) {
+// In-place bit reversal fused with the post-scale: MODE 0 none, 1 constant k, 2 table post[i].  P: one buffer (OneBuf) or transform
+// blockIdx.y of a strided run (StridedBuf)
+struct OneBuf {
+    uint32_t* p;
+    __device__ uint32_t* at(uint32_t) const { return p; }
+};
+struct StridedBuf {
+    uint32_t* p;
+    size_t stride;
+    __device__ uint32_t* at(uint32_t y) const { return p + y * stride; }
+};
+template <int MODE, class P>
+__global__ void __launch_bounds__(256) k_bitrev_scale(P buf, uint32_t log_n, FrK k, const uint32_t* post) {
+    uint32_t* data = buf.at(blockIdx.y);
     const size_t n = (size_t)1 << log_n;
     const Fr kk = frk(k);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -357,24 +380,36 @@ void zk_domains_free(zk_ctx* ctx) {
     ctx->domains.clear();
 }
 
-// `count` (<= NTT_BATCH) transforms of the same size and kind, in place on bufs[k], as one launch per pass.
-int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs, int count, uint32_t log_n, int inverse, int coset) {
-    if (count < 1 || count > NTT_BATCH) ZK_FAIL(ctx, ZK_ERR_ARG, "ntt: batch of 1..4 transforms");
+// `count` transforms of the same size and kind, in place, as one launch per pass: on bufs[k] (count <= NTT_BATCH), or -- bufs =
+// NULL -- on sbase + k * stride_words (count <= NTT_STRIDED_MAX, the grid's y extent).
+constexpr int NTT_STRIDED_MAX = 65535;
+static int ntt_run(zk_ctx* ctx, void* const* bufs, uint32_t* sbase, size_t stride_words, int count, uint32_t log_n, int inverse, int coset,
+                   uint32_t* tmp_given = nullptr) {
+    const bool strided = bufs == nullptr;
     zk_domain* d;
     ZK_TRY(get_domain(ctx, log_n, coset != 0, &d));
     FrK zero{};
     const int post_mode = !inverse ? 0 : (!coset ? 1 : 2);
     const FrK post_k = post_mode == 1 ? to_frk(d->size_inv) : zero;
     const uint32_t* post_tab = post_mode == 2 ? d->icos : nullptr;
-    auto launch = [&](const NttBatch& nb, uint32_t tiles, uint32_t nt, uint32_t E, const uint32_t* pre, uint32_t logS,
+    auto launch = [&](const NttBatch& nb, const NttStrided& ns, uint32_t tiles, uint32_t nt, uint32_t E, const uint32_t* pre, uint32_t logS,
                       uint32_t logM, uint32_t logC, int final_rev) {
         const dim3 grid(tiles, (unsigned)count);
+        if (strided) {
+            if (post_mode == 0)
+                hipLaunchKernelGGL((k_ntt_pass<0, NttStrided>), grid, nt, E * 36, ctx->stream, ns, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            else if (post_mode == 1)
+                hipLaunchKernelGGL((k_ntt_pass<1, NttStrided>), grid, nt, E * 36, ctx->stream, ns, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            else
+                hipLaunchKernelGGL((k_ntt_pass<2, NttStrided>), grid, nt, E * 36, ctx->stream, ns, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            return;
+        }
         if (post_mode == 0)
-            hipLaunchKernelGGL(k_ntt_pass<0>, grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            hipLaunchKernelGGL((k_ntt_pass<0, NttBatch>), grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
         else if (post_mode == 1)
-            hipLaunchKernelGGL(k_ntt_pass<1>, grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            hipLaunchKernelGGL((k_ntt_pass<1, NttBatch>), grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
         else
-            hipLaunchKernelGGL(k_ntt_pass<2>, grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
+            hipLaunchKernelGGL((k_ntt_pass<2, NttBatch>), grid, nt, E * 36, ctx->stream, nb, d->tw, pre, log_n, logS, logM, logC, inverse, final_rev, post_k, post_tab);
     };
     bool permuted = false;      // the last pass already wrote the natural order (and the post-scale)
     if (log_n > 0) {
@@ -382,16 +417,22 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs, int count, uint32_t log_
         uint32_t base = log_n / passes, extra = log_n % passes;
         uint32_t remaining = log_n;
         if (!ctx->flags["ntt_lds"]) {
-            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<0>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
-            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
-            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<2>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<0, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<1, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<2, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<0, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<1, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
+            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<2, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ctx->flags["ntt_lds"] = 1;
         }
         // with two or more passes the first one writes a scratch buffer and the last one scatters from it back into the
         // caller's buffer in natural order; a single-pass transform (N <= 2^LOGM_MAX) keeps the separate permutation
         uint32_t* tmp = nullptr;
         const size_t words = ((size_t)1 << log_n) * 8;
-        if (passes >= 2) ZK_TRY(zk_scratch(ctx, "ntt_tmp", (size_t)count * words * 4, (void**)&tmp));
+        if (passes >= 2) {
+            if (tmp_given) tmp = tmp_given;
+            else ZK_TRY(zk_scratch(ctx, "ntt_tmp", (size_t)count * words * 4, (void**)&tmp));
+        }
         for (uint32_t p = 0; p < passes; p++) {
             uint32_t logM = base + (p < extra ? 1 : 0);
             uint32_t logS = remaining - logM;
@@ -413,28 +454,46 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs, int count, uint32_t log_
             const uint32_t* pre = (p == 0 && coset && !inverse) ? d->cos : nullptr;
             const bool last = p + 1 == passes;
             NttBatch nb{};
-            for (int k = 0; k < count; k++) {
-                uint32_t* data = (uint32_t*)bufs[k];
-                uint32_t* t = tmp ? tmp + (size_t)k * words : nullptr;
-                nb.src[k] = (t && p > 0) ? t : data;
-                nb.dst[k] = t ? (last ? data : t) : data;
+            NttStrided ns{};
+            if (strided) {       // the scratch holds transform k at k * words, the caller's buffer at k * stride_words
+                ns.src = (tmp && p > 0) ? tmp : sbase;
+                ns.src_stride = (tmp && p > 0) ? words : stride_words;
+                ns.dst = (tmp && !last) ? tmp : sbase;
+                ns.dst_stride = (tmp && !last) ? words : stride_words;
+            } else {
+                for (int k = 0; k < count; k++) {
+                    uint32_t* data = (uint32_t*)bufs[k];
+                    uint32_t* t = tmp ? tmp + (size_t)k * words : nullptr;
+                    nb.src[k] = (t && p > 0) ? t : data;
+                    nb.dst[k] = t ? (last ? data : t) : data;
+                }
             }
-            launch(nb, tiles, nt, E, pre, logS, logM, logC, (tmp && last) ? 1 : 0);
+            launch(nb, ns, tiles, nt, E, pre, logS, logM, logC, (tmp && last) ? 1 : 0);
             ZK_HIP(ctx, hipGetLastError());
             remaining = logS;
         }
         permuted = tmp != nullptr;
     }
-    if (!permuted) {
+    if (!permuted && strided) {
+        const dim3 g(zk_grid((size_t)1 << log_n, 256), (unsigned)count);
+        if (!inverse) {
+            if (log_n > 1) hipLaunchKernelGGL((k_bitrev_scale<0, StridedBuf>), g, 256, 0, ctx->stream, StridedBuf{sbase, stride_words}, log_n, zero, nullptr);
+        } else if (!coset) {
+            hipLaunchKernelGGL((k_bitrev_scale<1, StridedBuf>), g, 256, 0, ctx->stream, StridedBuf{sbase, stride_words}, log_n, to_frk(d->size_inv), nullptr);
+        } else {
+            hipLaunchKernelGGL((k_bitrev_scale<2, StridedBuf>), g, 256, 0, ctx->stream, StridedBuf{sbase, stride_words}, log_n, zero, d->icos);
+        }
+        ZK_HIP(ctx, hipGetLastError());
+    } else if (!permuted) {
         unsigned g = zk_grid((size_t)1 << log_n, 256);
         for (int k = 0; k < count; k++) {
             uint32_t* data = (uint32_t*)bufs[k];
             if (!inverse) {
-                if (log_n > 1) hipLaunchKernelGGL(k_bitrev_scale<0>, g, 256, 0, ctx->stream, data, log_n, zero, nullptr);
+                if (log_n > 1) hipLaunchKernelGGL((k_bitrev_scale<0, OneBuf>), g, 256, 0, ctx->stream, OneBuf{data}, log_n, zero, nullptr);
             } else if (!coset) {
-                hipLaunchKernelGGL(k_bitrev_scale<1>, g, 256, 0, ctx->stream, data, log_n, to_frk(d->size_inv), nullptr);
+                hipLaunchKernelGGL((k_bitrev_scale<1, OneBuf>), g, 256, 0, ctx->stream, OneBuf{data}, log_n, to_frk(d->size_inv), nullptr);
             } else {
-                hipLaunchKernelGGL(k_bitrev_scale<2>, g, 256, 0, ctx->stream, data, log_n, zero, d->icos);
+                hipLaunchKernelGGL((k_bitrev_scale<2, OneBuf>), g, 256, 0, ctx->stream, OneBuf{data}, log_n, zero, d->icos);
             }
         }
         ZK_HIP(ctx, hipGetLastError());
@@ -442,6 +501,18 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs, int count, uint32_t log_
     return ZK_OK;
 }
 
+int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs, int count, uint32_t log_n, int inverse, int coset) {
+    if (count < 1 || count > NTT_BATCH || !bufs) ZK_FAIL(ctx, ZK_ERR_ARG, "ntt: batch of 1..4 transforms");
+    return ntt_run(ctx, bufs, nullptr, 0, count, log_n, inverse, coset);
+}
+int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp) {
+    if (!base || stride < ((size_t)1 << log_n)) ZK_FAIL(ctx, ZK_ERR_ARG, "ntt: strided transforms need stride >= 2^log_n");
+    for (size_t k0 = 0; k0 < count; k0 += NTT_STRIDED_MAX) {
+        const int cnt = (int)std::min<size_t>(NTT_STRIDED_MAX, count - k0);
+        ZK_TRY(ntt_run(ctx, nullptr, (uint32_t*)base + k0 * stride * 8, stride * 8, cnt, log_n, inverse, coset, (uint32_t*)tmp));
+    }
+    return ZK_OK;
+}
 int zk_ntt_launch(zk_ctx* ctx, void* buf, uint32_t log_n, int inverse, int coset) { return zk_ntt_launch_batch(ctx, &buf, 1, log_n, inverse, coset); }
 
 extern "C" int zk_fr_ntt_dev(zk_ctx* ctx, void* buf, uint32_t log_n, int inverse, int coset) {

@@ -41,6 +41,30 @@ k_spmv(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff, int 
     }
 }
 
+// The same for count assignments at once (the batched witness map): element t of out is row t % D of assignment t / D, whose
+// elements start at z + (t / D) * m; out holds count vectors of D elements back to back.
+__global__ void __launch_bounds__(256)
+k_spmv_multi(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff, int all_one, const void* z, size_t m, size_t nc,
+             size_t n_copy, uint32_t log_d, size_t total, void* out) {
+    const size_t dmask = ((size_t)1 << log_d) - 1;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = t & dmask;
+        const char* zk = (const char*)z + (t >> log_d) * m * 32;
+        Fr acc = fp_zero<FrParams>();
+        if (r < nc) {
+            uint32_t lo = row_ptr[r], hi = row_ptr[r + 1];
+            for (uint32_t k = lo; k < hi; k++) {
+                Fr v = fr_load(zk, col[k]);
+                if (!all_one) v = fr_mul(v, fr_load(coeff, k));
+                acc = fr_add(acc, v);
+            }
+        } else if (r < nc + n_copy) {
+            acc = fr_load(zk, r - nc);
+        }
+        fr_store(out, t, acc);
+    }
+}
+
 int upload_mat(zk_ctx* ctx, zk_r1cs::Mat& m, size_t nc, const uint32_t* rp, const uint32_t* col, const zk_fr* coeff) {
     m.nnz = rp[nc];
     m.h_row_ptr.assign(rp, rp + nc + 1);
@@ -192,6 +216,30 @@ extern "C" int zk_groth16_witness_map_post_dev(zk_ctx* ctx, const zk_r1cs* r, vo
     ZK_TRY(zk_ntt_launch(ctx, ab, r->log_d, 1, 1));                                  // coset_ifft of ab  (:303)
     return zk_vec_sub_scale_launch(ctx, ab, c, zinv, ab, (size_t)1 << r->log_d);    // (. - c) / Z(g), c in coefficient form (:298-302)
     ZK_API_END
+}
+
+// zk_groth16_witness_map_dev for count assignments (z: count x m elements back to back) in one go: abc = room for 6 count D elements,
+// h = its first count D on return (quotient k at k D); the last 3 count D are the transforms' scratch.  The same operations in the same order, each over all count vectors: three
+// mat-vec launches, strided transforms (one launch per pass whatever count is), one product and one (. - c) / Z(g) launch over
+// count D elements.
+int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc) {
+    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, total = count * D;
+    char* a = (char*)abc;
+    char *b = a + total * 32, *c = b + total * 32, *tmp = c + total * 32;
+    const unsigned g = zk_grid(total, 256);
+    for (int which = 0; which < 3; which++) {
+        const auto& mt = r->m[which];
+        hipLaunchKernelGGL(k_spmv_multi, g, 256, 0, ctx->stream, mt.row_ptr, mt.col, mt.coeff, mt.all_one ? 1 : 0, z, m, r->nc,
+                           which == 0 ? r->ni : (size_t)0, r->log_d, total, (void*)(which == 0 ? a : which == 1 ? b : c));
+    }
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_TRY(zk_ntt_launch_strided(ctx, a, 3 * count, D, r->log_d, 1, 0, tmp));    // ifft of every a, b, c (a | b | c are one strided run)
+    ZK_TRY(zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 0, 1, tmp));    // coset_fft of every a and b
+    ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, a, b, a, total));
+    uint32_t zinv[9];
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zinv));
+    ZK_TRY(zk_ntt_launch_strided(ctx, a, count, D, r->log_d, 1, 1, tmp));        // coset_ifft of every product
+    return zk_vec_sub_scale_launch(ctx, a, c, zinv, a, total);
 }
 
 extern "C" int zk_groth16_witness_map_dev(zk_ctx* ctx, const zk_r1cs* r, const void* z, void* h) {
