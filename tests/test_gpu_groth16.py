@@ -539,3 +539,45 @@ def test_one_prover_deal_with_a_boundary_crumb_on_wide_window_tables(ctx):
     finally:
         for c in others:
             c.close()
+
+
+def test_every_prover_refuses_a_key_of_another_system(ctx):
+    """One check of the key against the constraint system (zk_groth16_key_matches) in front of every prover: with a key set up for
+    a mul-chain of another size zk_groth16_prove_dev, _prove_batch_dev (count 2), _msms_presort_dev, _msms_begin_dev and
+    _prove_multi (one context) each return ZK_ERR_ARG.  None of them leaves a presort pending: the refusals happen with a good
+    presort of the right key in flight (the presort / begin forms drop it before they look at the key), and the proof of the right
+    key directly after each refusal equals the known-trapdoor prediction."""
+    import zkref_c as OC
+    from zk_mpc_amd._lib import ZkError
+    n, n_other = 1000, 1500
+    rng = O.Prng(20261)
+    mont = lambda v: cv.fr_to_mont([v])[0]
+    td = [mont(rng.fr()) for _ in range(7)]
+    dr, dr_other = ctx.r1cs_mul_chain(n), ctx.r1cs_mul_chain(n_other)
+    pk, pk_other = ctx.groth16_setup(dr, *td), ctx.groth16_setup(dr_other, *td)
+    z = ctx.mul_chain_assignment_dev(n, mont(rng.fr()), mont(rng.fr()))
+    z2 = ctx.upload(np.concatenate([ctx.download(z, (n + 3, 4))] * 2))
+    r, s = mont(rng.fr()), mont(rng.fr())
+    cr = OC.R1cs(2, n + 1, *OC.mul_chain_csr(n))
+    zarr = ctx.download(z, (n + 3, 4))
+    want = OC.groth16_predict(cr, np.stack(td), zarr, OC.witness_map(cr, zarr, OC.num_threads()), r, s)
+    assert ctx.create_proof_dev(pk, dr, z.ptr, r, s) == want
+    refused = [
+        ("prove_dev", lambda: ctx.create_proof_dev(pk_other, dr, z.ptr, r, s)),
+        ("prove_batch_dev", lambda: ctx.create_proofs_batch_dev(pk_other, dr, z2.ptr, 2, [r, r], [s, s])),
+        ("msms_presort_dev", lambda: ctx.groth16_msms_presort_dev(pk_other, dr, z.ptr)),
+        ("msms_begin_dev", lambda: ctx.groth16_msms_begin_dev(pk_other, dr, z.ptr)),
+        ("prove_multi", lambda: ctx.create_proof_multi([], [pk_other], [dr], z.ptr, r, s)),
+    ]
+    for name, call in refused:
+        ctx.groth16_msms_presort_dev(pk, dr, z.ptr)          # a good presort in flight while the call is refused
+        with pytest.raises(ZkError, match="error -2"):       # ZK_ERR_ARG
+            call()
+        assert ctx.create_proof_dev(pk, dr, z.ptr, r, s) == want, name
+    for call in (refused[2][1], refused[3][1]):              # refused, and the key they were refused for goes right after
+        with pytest.raises(ZkError, match="error -2"):
+            call()
+    pk_other.free()
+    assert ctx.create_proof_dev(pk, dr, z.ptr, r, s) == want
+    assert ctx.create_proofs_batch_dev(pk, dr, z2.ptr, 2, [r, r], [s, s]) == [want, want]
+    pk.free()

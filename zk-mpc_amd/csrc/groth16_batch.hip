@@ -35,10 +35,10 @@ void over_ranges(zk_ctx* ctx, size_t count, size_t tasks, const Fn& f) {
 }
 
 // cnt proofs: z = their assignments (m elements each), h = their cnt quotients of D elements once front() has run on the context
-// stream (the first chunk enqueues the batched witness map there, beside its z sort); pre_ready() returns once pre[0..cnt) is complete
+// stream (the first chunk enqueues the batched witness map there, beside its z sort); pre_ready() returns once the pre terms of tails[0..cnt) are complete
 int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, const char* z, const char* h, const std::function<int()>& front,
-                const std::function<void()>& pre_ready, const ZkTailPre* pre, uint8_t* proofs) {
-    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, nvars = m - 1;
+                const std::function<void()>& pre_ready, ZkTail* tails, uint8_t* proofs) {
+    const ZkG16Jobs T(pk, r, z, h);
     hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;
     struct Event {
         hipEvent_t e = nullptr;
@@ -56,20 +56,11 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
             (void)hipStreamSynchronize(ctx->stream);
         }
     } drain{ctx};
-    const bool l_shared = pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
-                          pk->l_pad->c_pre == pk->a->c_pre;
-    ZK_TRY(zk_msm_prepare_multi(ctx, &J[0], pk->b_g2, 1, z + 32, nvars, m, cnt, 8));
-    ZK_TRY(zk_msm_prepare_multi(ctx, &J[1], pk->a, 1, z + 32, nvars, m, cnt, 9));
-    ZK_TRY(zk_msm_prepare_multi(ctx, &J[2], pk->b_g1, 1, z + 32, nvars, m, cnt, 10));
-    if (l_shared) ZK_TRY(zk_msm_prepare_multi(ctx, &J[3], pk->l_pad, 1, z + 32, nvars, m, cnt, 11));
-    else ZK_TRY(zk_msm_prepare_multi(ctx, &J[3], pk->l, 0, z + r->ni * 32, r->nw, m, cnt, 11));
-    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[0], s_sort, nullptr));
-    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[1], s_sort, &J[0]));
-    const ZkMsmJob* lender = J[0].c == J[1].c ? &J[0] : &J[1];
-    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[2], s_sort, lender));
-    ZK_TRY(zk_msm_enqueue_sort(ctx, &J[3], s_sort, l_shared ? lender : nullptr));
+    ZkMsmJob* const zj[4] = {&J[0], &J[1], &J[2], &J[3]};
+    ZK_TRY(T.sort_z(ctx, zj, s_sort, 8, cnt));                       // slots 8..11
+    if (!T.l_shared) ZK_TRY(zk_msm_enqueue_sort(ctx, &J[3], s_sort, nullptr));
     ZK_TRY(front());                                                 // the witness map on the context stream, beside the z sort
-    ZK_TRY(zk_msm_prepare_multi(ctx, &J[4], pk->h, 0, h, std::min(pk->h->n, D), D, cnt, 12));   // :106, min(len) rule
+    ZK_TRY(T.prepare(ctx, 4, &J[4], 12, cnt));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &J[4], ctx->stream, nullptr));
     // B in G2 (the long reduce chain) on the accumulate stream, the z jobs of G1 on the sort stream, H on the context stream
     ZK_TRY(zk_msm_enqueue_accum(ctx, &J[0], s_acc));
@@ -89,7 +80,12 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
     ZK_TRY(zk_msm_finish_multi(ctx, &J[4], hs.data()));
     pre_ready();
     over_ranges(ctx, cnt, TAIL_TASKS, [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; k++) zk_proof_tail_rest(pk, pre[k], a[k], b1[k], b2[k], hs[k], l[k], proofs + k * 192);
+        for (size_t k = lo; k < hi; k++) {
+            zk_tail_chain_a(pk, &tails[k], a[k]);
+            zk_tail_chain_b(pk, &tails[k], b1[k]);
+            zk_tail_chain_2(pk, &tails[k], b2[k]);
+            zk_tail_finish(tails[k], hs[k], l[k], proofs + k * 192);
+        }
     });
     return ZK_OK;
 }
@@ -97,15 +93,12 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
 // device bytes the MSM jobs of a chunk of cnt proofs need: per job its sort (sorted entries, keys, values and the segment tables:
 // ~16 bytes per digit) and its bucket sums (with room for split buckets)
 size_t chunk_bytes(const zk_pk* pk, const zk_r1cs* r, size_t cnt) {
-    const size_t D = (size_t)1 << r->log_d, nvars = r->ni + r->nw - 1;
     size_t bytes = 0;
-    const zk_bases* tabs[5] = {pk->b_g2, pk->a, pk->b_g1, pk->l_pad ? pk->l_pad : pk->l, pk->h};
-    const size_t lens[5] = {nvars, nvars, nvars, pk->l_pad ? nvars : r->nw, std::min(pk->h->n, D)};
-    for (int j = 0; j < 5; j++) {
-        const size_t W = tabs[j]->pre ? (255 + tabs[j]->c_pre - 1) / tabs[j]->c_pre : 32;
-        const size_t XW = tabs[j]->group == 1 ? 48 : 96;
-        const size_t buckets = tabs[j]->pre ? ((size_t)1 << (tabs[j]->c_pre - 1)) : W * std::max<size_t>(lens[j], 16);
-        bytes += cnt * (lens[j] * W * 16 + buckets * XW * 4 * 2);
+    for (const ZkG16Jobs::Job& j : ZkG16Jobs(pk, r, nullptr, nullptr).j) {
+        const size_t W = j.tab->pre ? (255 + j.tab->c_pre - 1) / j.tab->c_pre : 32;
+        const size_t XW = j.tab->group == 1 ? 48 : 96;
+        const size_t buckets = j.tab->pre ? ((size_t)1 << (j.tab->c_pre - 1)) : W * std::max<size_t>(j.n, 16);
+        bytes += cnt * (j.n * W * 16 + buckets * XW * 4 * 2);
     }
     return bytes;
 }
@@ -114,18 +107,11 @@ size_t chunk_bytes(const zk_pk* pk, const zk_r1cs* r, size_t cnt) {
 // or the host form's upload) and the witness map's 6 count D elements (a | b | c and the transforms' scratch), plus one chunk's
 // MSM scratch, against 90 % of the free memory.
 int batch_plan(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size_t* chunk_out) {
-    const size_t m = r->ni + r->nw, nvars = m - 1, D = (size_t)1 << r->log_d;
-    if (!pk->a || !pk->b_g1 || !pk->b_g2 || !pk->l || !pk->h || pk->a->n != nvars + 1 || pk->b_g1->n != nvars + 1 ||
-        pk->b_g2->n != nvars + 1 || pk->l->n != r->nw || r->ni < 1)
-        ZK_FAIL(ctx, ZK_ERR_ARG, "groth16 batch: proving key does not match the constraint system");
+    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
+    const size_t m = r->ni + r->nw, D = (size_t)1 << r->log_d;
     // proofs per chunk: every job's bucket spaces within what one multi job takes (zk_msm_multi_chunk)
     size_t chunk = count;
-    chunk = std::min(chunk, zk_msm_multi_chunk(pk->b_g2, nvars));
-    chunk = std::min(chunk, zk_msm_multi_chunk(pk->a, nvars));
-    chunk = std::min(chunk, zk_msm_multi_chunk(pk->b_g1, nvars));
-    chunk = std::min(chunk, zk_msm_multi_chunk(pk->l, r->nw));
-    if (pk->l_pad) chunk = std::min(chunk, zk_msm_multi_chunk(pk->l_pad, nvars));
-    chunk = std::min(chunk, zk_msm_multi_chunk(pk->h, std::min(pk->h->n, D)));
+    for (const ZkG16Jobs::Job& j : ZkG16Jobs(pk, r, nullptr, nullptr).j) chunk = std::min(chunk, zk_msm_multi_chunk(j.tab, j.n));
     size_t free_b = 0, total_b = 0;
     ZK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
     const double need = (double)count * (double)(m + 6 * D) * 32.0 + (double)chunk_bytes(pk, r, chunk);
@@ -153,21 +139,22 @@ int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size
     const size_t m = r->ni + r->nw, D = (size_t)1 << r->log_d;
     // an announced next assignment (zk_groth16_hint_next_dev, zk_groth16_prove_queued) is drained and dropped: its front reads
     // scratch this call does not own, and the next single proof is not the one it was announced for
-    zk_presort_free(ctx);
-    if (ctx->copy_stream) ZK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    ctx->next_z = nullptr;
-    ctx->next_z_host = nullptr;
-    ctx->next_z_dev = nullptr;
-    ctx->next_z_pk = ctx->next_z_r = nullptr;
-    ctx->next_z_m = 0;
+    ZK_TRY(zk_next_z_drop(ctx, true));
     if (count == 1) return zk_groth16_prove_dev(ctx, pk, r, z_dev, r_, s_, proofs_out);
     ZK_TRY(zk_prover_streams(ctx, 1));
     CallMem wm{ctx};
     ZK_HIP(ctx, hipMalloc(&wm.p, count * 6 * D * 32));
-    std::vector<ZkTailPre> pre(count);
+    std::vector<ZkTail> tails(count);
     // the terms of the tails that need no MSM result, beside the device work (prove_chunk waits for them before its tails)
     ZkTask<void> pre_task = zk_async(ctx, [&] {
-        over_ranges(ctx, count, PRE_TASKS, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) zk_proof_tail_pre(pk, &r_[k], &s_[k], &pre[k]); });
+        over_ranges(ctx, count, PRE_TASKS, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                zk_tail_begin(&r_[k], &s_[k], &tails[k]);
+                zk_tail_pre_a(pk, &tails[k]);
+                zk_tail_pre_b(pk, &tails[k]);
+                zk_tail_pre_2(pk, &tails[k]);
+            }
+        });
     });
     const std::function<void()> pre_ready = [&] { if (pre_task.valid()) pre_task.get(); };
     const std::function<int()> wmap = [&] { return zk_groth16_witness_map_batch(ctx, r, count, z_dev, wm.p); };
@@ -175,7 +162,7 @@ int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size
     int rc = ZK_OK;
     for (size_t k0 = 0; k0 < count && rc == ZK_OK; k0 += chunk)
         rc = prove_chunk(ctx, pk, r, std::min(chunk, count - k0), (const char*)z_dev + k0 * m * 32, (const char*)wm.p + k0 * D * 32,
-                         k0 == 0 ? wmap : none, pre_ready, pre.data() + k0, proofs_out + k0 * 192);
+                         k0 == 0 ? wmap : none, pre_ready, tails.data() + k0, proofs_out + k0 * 192);
     return rc;
 }
 

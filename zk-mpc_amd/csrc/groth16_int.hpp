@@ -6,6 +6,7 @@
 //   groth16_pipeline.hip the five MSMs of create_proof as a stream pipeline, fronts, presorts       (src/groth16.rs:106-160)
 //   msm_batch.hip        several independent MSMs enqueued in one go (Marlin's commitment rounds)
 //   groth16_prove.hip    create_proof for a local prover                                           (src/groth16.rs:68-183)
+//   groth16_batch.hip    create_proof for many assignments of one key in one call
 //   groth16_multi.hip    one prover's MSMs spread over several devices
 //   groth16_shared.hip   create_proof over additive / SPDZ shares as one call
 #pragma once
@@ -14,6 +15,7 @@
 #include "hostfield64.hpp"
 #include "internal.hpp"
 #include "../../include/zkmpc_hip.h"
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <functional>
@@ -83,30 +85,82 @@ int zk_prover_streams(zk_ctx* ctx, size_t k);
 // after_abc runs on the calling thread as soon as A, B-in-G1 and B-in-G2 have delivered.
 int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h_in, void* h_scratch,
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc = nullptr);
-int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);
+int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: see zk_pk::l_pad
 // r1cs.hip: the witness map of count assignments (count x m elements back to back) with launches that do not grow with count;
 // abc = room for 6 count D elements, the count quotients in its first count D on return
-int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);     // groth16_key.hip: see zk_pk::l_pad
+int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);
+// every prover's check of the key against the system (groth16_pipeline.hip): the tables there, an instance, the four lengths
+int zk_groth16_key_matches(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r);
+int zk_next_z_drop(zk_ctx* ctx, bool drain);      // groth16_pipeline.hip: forget an announced next assignment (drain: its front and upload first)
 
-// The O(1) host tail of a proof (groth16_prove.hip).  The chains run on the context's helper threads and reference this object:
-// declare it after the MSM sums it reads; the destructor joins.
-class ZkProofTail {
-    using H1 = zk::Fq64Field;
-    using H2 = zk::Fq264Field;
-    using X1 = zk::XYZZ<H1>;
-    using X2 = zk::XYZZ<H2>;
-    zk_ctx* ctx;
-    bool glv;                                        // the key's points are in the prime-order subgroup: G1 scalar multiplications through the endomorphism
+// The one statement of the five MSMs of create_proof (src/groth16.rs:160, :137, :148, :110, :106), in the fixed order 0 = B in G2, 1 = A,
+// 2 = B in G1, 3 = L, 4 = H: every prover reads its tables, offsets, scalars and lengths here.  z, h may be NULL where only the
+// lengths are wanted.  pad_l = false keeps L on l_query (the several-device prover cuts it by terms of the witness part).
+struct ZkG16Jobs {
+    struct Job {
+        const zk_bases* tab;
+        size_t off;             // first base
+        const char* scal;
+        size_t n;
+    } j[5];
+    size_t m, D;                // elements between two assignments / two quotients of a batch
+    bool l_shared;              // L over l_pad reads z[1..] like jobs 0..2 (the instance meets infinity) and borrows their sort
+    ZkG16Jobs(const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h, bool pad_l = true) : m(r->ni + r->nw), D((size_t)1 << r->log_d) {
+        const size_t nvars = m - 1;
+        const char *z1 = z ? (const char*)z + 32 : nullptr, *zw = z ? (const char*)z + r->ni * 32 : nullptr;
+        l_shared = pad_l && pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
+                   pk->l_pad->c_pre == pk->a->c_pre;
+        j[0] = {pk->b_g2, 1, z1, nvars};        // query[1..] x z[1..]
+        j[1] = {pk->a, 1, z1, nvars};
+        j[2] = {pk->b_g1, 1, z1, nvars};
+        j[3] = l_shared ? Job{pk->l_pad, 1, z1, nvars} : Job{pk->l, 0, zw, r->nw};        // aux_assignment against l_query
+        j[4] = {pk->h, 0, (const char*)h, std::min(pk->h->n, D)};        // min(len) rule (variable_base.rs:15-17): h_query has D-1 entries, h has D
+    }
+    // job k into scratch slot `slot`: of one proof (multi = 0), or as a multi-vector job of `multi` >= 1 proofs (assignments m,
+    // quotients D elements apart; a batch's last chunk may be one proof and is collected as a multi job all the same)
+    int prepare(zk_ctx* ctx, int k, ZkMsmJob* job, int slot, size_t multi = 0) const {
+        if (!multi) return zk_msm_prepare(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, slot);
+        return zk_msm_prepare_multi(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, k == 4 ? D : m, multi, slot);
+    }
+    // The z jobs J[0..3] prepared (slots slot0..slot0+3) and their sorts enqueued on st: job 0 sorts, A borrows its sort, B in G1 and a
+    // shared L borrow from the lender.  have0: J[0] is prepared and sorted already.  An L of its own is sorted by the caller.
+    int sort_z(zk_ctx* ctx, ZkMsmJob* const* J, hipStream_t st, int slot0, size_t multi = 0, bool have0 = false) const {
+        for (int k = have0 ? 1 : 0; k < 4; k++) ZK_TRY(prepare(ctx, k, J[k], slot0 + k, multi));
+        if (!have0) ZK_TRY(zk_msm_enqueue_sort(ctx, J[0], st, nullptr));
+        ZK_TRY(zk_msm_enqueue_sort(ctx, J[1], st, J[0]));
+        // (the G2 table may carry windows of another width than the G1 tables: then A sorts for itself and the other G1 jobs borrow A's)
+        const ZkMsmJob* lender = J[0]->c == J[1]->c ? J[0] : J[1];
+        ZK_TRY(zk_msm_enqueue_sort(ctx, J[2], st, lender));
+        return l_shared ? zk_msm_enqueue_sort(ctx, J[3], st, lender) : ZK_OK;
+    }
+};
+
+// The O(1) host tail of a proof (groth16_prove.hip), cut where it can be scheduled: three terms that need only the key and r, s;
+// three chains that need the A, B-in-G1 and B-in-G2 sums; the finish.  Every proof of the library is these functions.
+struct ZkTail {
+    using X1 = zk::XYZZ<zk::Fq64Field>;
     uint32_t rw[8], sw[8];
-    X1 mul1(const X1& p, const uint32_t* k) const { return glv ? zk::host64_scalar_mul_glv(p, k) : zk::host64_scalar_mul<H1>(p, k); }
-    X1 delta1;
-    X2 delta2;
-    zk::Affine<H1> a0, alpha, b0, beta1;
-    zk::Affine<H2> b02, beta2;
-    X1 g_a, s_g_a, r_s_delta, r_g1_b;
-    X1 r_g1, s_g1;                                   // delta r, delta s, delta_2 s: they depend on the key and on r, s only, and start
-    X2 s_g2;                                         // with the proof (pre_*), under the device's work, not behind it
-    zk::Affine<H2> b_aff;
+    X1 r_g1, r_s_delta, s_g1;                        // delta r, delta r s, delta s
+    zk::XYZZ<zk::Fq264Field> s_g2;                   // delta_2 s
+    X1 g_a, s_g_a, r_g1_b;
+    zk::Affine<zk::Fq264Field> b_aff;
+};
+void zk_tail_begin(const zk_fr* r, const zk_fr* s, ZkTail* t);
+void zk_tail_pre_a(const zk_pk* pk, ZkTail* t);      // independent of each other
+void zk_tail_pre_b(const zk_pk* pk, ZkTail* t);
+void zk_tail_pre_2(const zk_pk* pk, ZkTail* t);
+void zk_tail_chain_a(const zk_pk* pk, ZkTail* t, const zk_g1_projective& a_sum);       // after pre_a
+void zk_tail_chain_b(const zk_pk* pk, ZkTail* t, const zk_g1_projective& b1_sum);      // after pre_b
+void zk_tail_chain_2(const zk_pk* pk, ZkTail* t, const zk_g2_projective& b2_sum);      // after pre_2
+void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
+
+// The tail of a single proof: the pre terms start with the proof on the context's helper threads, under the device's work; the chains
+// as soon as A, B-in-G1 and B-in-G2 have delivered (abc_ready), while the devices still work on L and H.  The tasks reference this
+// object: declare it after the MSM sums it reads; the destructor joins.  (A batch runs the same functions over ranges of proofs.)
+class ZkProofTail {
+    zk_ctx* ctx;
+    const zk_pk* pk;
+    ZkTail t;
     ZkTask<void> pre_a, pre_b, pre_2;                // (the chains wait for them; declared first = joined last)
     ZkTask<void> chain_a, chain_b, chain_g2;         // (last members: joined before the fields the chains write go)
 
@@ -116,17 +170,6 @@ class ZkProofTail {
     void join();
     void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
 };
-
-// The same tail for the proofs of a batch (groth16_batch.hip), on the calling thread: the terms that need no MSM result first (they
-// run while the device works), then the rest.  The operations of ZkProofTail, in the same order: the same bytes.
-struct ZkTailPre {
-    uint32_t rw[8], sw[8];
-    zk::XYZZ<zk::Fq64Field> r_g1, r_s_delta, s_g1;
-    zk::XYZZ<zk::Fq264Field> s_g2;
-};
-void zk_proof_tail_pre(const zk_pk* pk, const zk_fr* r, const zk_fr* s, ZkTailPre* t);
-void zk_proof_tail_rest(const zk_pk* pk, const ZkTailPre& t, const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum,
-                        const zk_g2_projective& b2_sum, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
 
 namespace zk {
 template <class F>

@@ -24,8 +24,10 @@ constexpr double G2_WEIGHT = 2.7;               // cost of a G2 term in G1 terms
 constexpr size_t MIN_PIECE = 4096;              // no piece smaller than this (unless it is all that is left of its job)
 
 // the stretch [share * d, share * (d + 1)) of the cost line, as pieces
-std::vector<std::vector<Piece>> deal(const size_t len[5], int n_ctx) {
+std::vector<std::vector<Piece>> deal(const ZkG16Jobs& T, int n_ctx) {
     const double w[5] = {G2_WEIGHT, 1, 1, 1, 1};
+    size_t len[5];
+    for (int j = 0; j < 5; j++) len[j] = T.j[j].n;
     double total = 0;
     for (int j = 0; j < 5; j++) total += w[j] * (double)len[j];
     std::vector<std::vector<Piece>> out(n_ctx);
@@ -66,12 +68,11 @@ static int prove_multi(zk_ctx* ctx0, zk_ctx* const* ctxs, const zk_pk* const* pk
             pks[d]->h->n != pks[0]->h->n || pks[d]->l->n != pks[0]->l->n)
             ZK_FAIL(ctx0, ZK_ERR_ARG, "zk_groth16_prove_multi: the contexts' keys / constraint systems differ in shape");
     }
-    const zk_r1cs* r0 = rs[0];
-    const size_t D = (size_t)1 << r0->log_d, ni = r0->ni, nw = r0->nw, nvars = (ni - 1) + nw, m = ni + nw;
-    if (pks[0]->a->n != nvars + 1 || pks[0]->b_g1->n != nvars + 1 || pks[0]->b_g2->n != nvars + 1 || pks[0]->l->n != nw)
-        ZK_FAIL(ctx0, ZK_ERR_ARG, "groth16: proving key does not match the constraint system");
-    const size_t len[5] = {nvars, nvars, nvars, nw, std::min(pks[0]->h->n, D)};
-    const std::vector<std::vector<Piece>> plan = deal(len, n_ctx);
+    ZK_TRY(zk_groth16_key_matches(ctx0, pks[0], rs[0]));
+    // (L stays on l_query: cut by terms of the witness part)
+    const ZkG16Jobs T0(pks[0], rs[0], nullptr, nullptr, false);
+    const size_t D = T0.D, m = T0.m;
+    const std::vector<std::vector<Piece>> plan = deal(T0, n_ctx);
 
     // the assignment was produced on context 0's stream
     ZK_HIP(ctx0, hipStreamSynchronize(ctx0->stream));
@@ -115,14 +116,13 @@ static int prove_multi(zk_ctx* ctx0, zk_ctx* const* ctxs, const zk_pk* const* pk
             }
             z = zc;
         }
-        const char* zb = (const char*)z;
         void* h = nullptr;
         for (const Piece& p : pc)
             if (p.job == 4 && !h) {
                 ZK_TRY(zk_scratch(c, "prove_h", D * 32, &h));
                 ZK_TRY(zk_groth16_witness_map_dev(c, rs[d], z, h));
             }
-        const zk_pk* pk = pks[d];
+        const ZkG16Jobs T(pks[d], rs[d], z, h, false);
         std::vector<const zk_bases*> bases;
         std::vector<size_t> offs, lens;
         std::vector<const void*> scal;
@@ -133,14 +133,8 @@ static int prove_multi(zk_ctx* ctx0, zk_ctx* const* ctxs, const zk_pk* const* pk
         part2[d].resize(n2);
         size_t k1 = 0, k2 = 0;
         for (const Piece& p : pc) {
-            switch (p.job) {
-                case 0: bases.push_back(pk->b_g2); offs.push_back(1 + p.lo); scal.push_back(zb + 32 + p.lo * 32); break;     // query[1..] x z[1..]
-                case 1: bases.push_back(pk->a); offs.push_back(1 + p.lo); scal.push_back(zb + 32 + p.lo * 32); break;
-                case 2: bases.push_back(pk->b_g1); offs.push_back(1 + p.lo); scal.push_back(zb + 32 + p.lo * 32); break;
-                case 3: bases.push_back(pk->l); offs.push_back(p.lo); scal.push_back(zb + (ni + p.lo) * 32); break;          // l_query x the witness part
-                default: bases.push_back(pk->h); offs.push_back(p.lo); scal.push_back((const char*)h + p.lo * 32); break;
-            }
-            lens.push_back(p.n);
+            const ZkG16Jobs::Job& j = T.j[p.job];                      // a piece is the job's entry shifted by lo
+            bases.push_back(j.tab); offs.push_back(j.off + p.lo); scal.push_back(j.scal + p.lo * 32); lens.push_back(p.n);
             outs.push_back(p.job == 0 ? (void*)&part2[d][k2++] : (void*)&part1[d][k1++]);
         }
         return zk_msm_batch_dev(c, bases.size(), bases.data(), offs.data(), scal.data(), lens.data(), outs.data());
@@ -207,10 +201,8 @@ extern "C" int zk_groth16_prove_multi(zk_ctx* const* ctxs, const zk_pk* const* p
 extern "C" int zk_groth16_multi_plan(const zk_pk* pk, const zk_r1cs* r, int n_ctx, char* out, size_t cap, size_t* written) {
     ZK_API_BEGIN_NOCTX
     if (!pk || !r || n_ctx < 1 || n_ctx > 64 || !out || !cap || !written) return ZK_ERR_ARG;
-    const size_t D = (size_t)1 << r->log_d, nvars = (r->ni - 1) + r->nw;
-    const size_t len[5] = {nvars, nvars, nvars, r->nw, std::min(pk->h->n, D)};
     std::string s;
-    const auto plan = deal(len, n_ctx);
+    const auto plan = deal(ZkG16Jobs(pk, r, nullptr, nullptr, false), n_ctx);
     for (int d = 0; d < n_ctx; d++)
         for (const Piece& p : plan[d]) s += std::to_string(d) + " " + std::to_string(p.job) + " " + std::to_string(p.lo) + " " + std::to_string(p.n) + "\n";
     if (s.size() + 1 > cap) return ZK_ERR_ARG;

@@ -18,6 +18,27 @@ void zk_presort_free(zk_ctx* ctx) {
     delete p;
 }
 
+int zk_next_z_drop(zk_ctx* ctx, bool drain) {
+    if (drain) {                    // its front reads the slot it was uploaded to; the upload may still run
+        zk_presort_free(ctx);
+        if (ctx->copy_stream) ZK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    }
+    ctx->next_z = nullptr;
+    ctx->next_z_host = nullptr;
+    ctx->next_z_dev = nullptr;
+    ctx->next_z_pk = ctx->next_z_r = nullptr;
+    ctx->next_z_m = 0;
+    return ZK_OK;
+}
+
+int zk_groth16_key_matches(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r) {
+    const size_t n = r->ni + r->nw;
+    if (!pk->a || !pk->b_g1 || !pk->b_g2 || !pk->l || !pk->h || r->ni < 1 || pk->a->n != n || pk->b_g1->n != n || pk->b_g2->n != n ||
+        pk->l->n != r->nw)
+        ZK_FAIL(ctx, ZK_ERR_ARG, "groth16: proving key does not match the constraint system");
+    return ZK_OK;
+}
+
 int zk_prover_streams(zk_ctx* ctx, size_t k) {
     while (ctx->aux.size() < k) {
         hipStream_t st;
@@ -40,13 +61,12 @@ int zk_prover_streams(zk_ctx* ctx, size_t k) {
 int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h_in, void* h_scratch,
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc) {
     const auto t_enter = std::chrono::steady_clock::now();
-    const size_t D = (size_t)1 << r->log_d;
-    const size_t nvars = (r->ni - 1) + r->nw;
-    const char* zb = (const char*)z;
-    if (pk->a->n != nvars + 1 || pk->b_g1->n != nvars + 1 || pk->b_g2->n != nvars + 1 || pk->l->n != r->nw)
-        ZK_FAIL(ctx, ZK_ERR_ARG, "groth16: proving key does not match the constraint system");
+    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
+    const ZkG16Jobs T(pk, r, z, h_in ? h_in : h_scratch);
+    const size_t D = T.D, nvars = T.j[0].n;
+    const bool l_shared = T.l_shared;
     ZK_TRY(zk_prover_streams(ctx, 1));
-    hipStream_t s_sort = ctx->aux[0], s_red = ctx->aux[0], s_acc = ctx->acc_stream;
+    hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;      // (the sort stream carries reduce chains as well)
     struct Events {                               // destroyed on every exit path (the error returns below used to leak them)
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
@@ -80,38 +100,21 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     // z was produced on the context stream.  (With a front that stream already carries this proof's witness map and H-sort:
     // waiting for it here would hold the sort stream -- and the G2 reduce chain on it -- until the H-sort is through.)
     if (!fronted) ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0, 0));
-    int rc = presorted ? ZK_OK : zk_msm_prepare(ctx, J[0], pk->b_g2, 1, zb + 32, nvars, 1);                 // src/groth16.rs:160 (query[1..])
     const bool have_z_jobs = begun || chained;
-    if (rc == ZK_OK && !have_z_jobs) rc = zk_msm_prepare(ctx, J[1], pk->a, 1, zb + 32, nvars, 2);              // :137
-    if (rc == ZK_OK && !have_z_jobs) rc = zk_msm_prepare(ctx, J[2], pk->b_g1, 1, zb + 32, nvars, 3);           // :148
-    // :110: aux_assignment against l_query; over the padded table the same sum reads z[1..] (the instance meets infinity)
-    const bool l_shared = pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
-                          pk->l_pad->c_pre == pk->a->c_pre;
-    if (rc == ZK_OK && !have_z_jobs) rc = l_shared ? zk_msm_prepare(ctx, J[3], pk->l_pad, 1, zb + 32, nvars, 4)
-                                                   : zk_msm_prepare(ctx, J[3], pk->l, 0, zb + r->ni * 32, r->nw, 4);
-    if (rc == ZK_OK && !presorted) rc = zk_msm_enqueue_sort(ctx, J[0], s_sort, nullptr);
-    if (rc == ZK_OK && !have_z_jobs) rc = zk_msm_enqueue_sort(ctx, J[1], s_sort, J[0]);
-    // (the G2 table may carry windows of another width than the G1 tables: then A sorts for itself and the other G1 jobs borrow A's)
-    const ZkMsmJob* lender = J[0]->c == J[1]->c ? J[0] : J[1];
-    if (rc == ZK_OK && !have_z_jobs) rc = zk_msm_enqueue_sort(ctx, J[2], s_sort, lender);
-    if (rc == ZK_OK && !have_z_jobs && l_shared) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, lender);
-    const void* h = h_in;
+    int rc = have_z_jobs ? ZK_OK : T.sort_z(ctx, J, s_sort, 1, 0, presorted);       // the z jobs: slots 1..4, one sort of z[1..]
     ZkPhaseTimer tm(ctx);
     // the first accumulate kernel is gated on the witness map, which would otherwise be starved beside it (un-gating it: within
     // the noise of consecutive runs, round 3)
     if (fronted) {
         // witness map and H's sort were enqueued with the previous proof (enqueue_front below)
-        h = h_scratch;
         ZK_HIP(ctx, hipStreamWaitEvent(s_acc, pre->wm_done, 0));
     } else {
         if (rc == ZK_OK && !h_in) {
             tm.begin("witness_map");
             rc = zk_groth16_witness_map_dev(ctx, r, z, h_scratch);
             tm.end();
-            h = h_scratch;
         }
-        // h_acc: min(len) rule (variable_base.rs:15-17): h_query has D-1 entries, h has D
-        if (rc == ZK_OK) rc = zk_msm_prepare(ctx, J[4], pk->h, 0, h, std::min(pk->h->n, D), 5);   // :106
+        if (rc == ZK_OK) rc = T.prepare(ctx, 4, J[4], 5);
         if (rc == ZK_OK) {
             ZK_HIP(ctx, hipEventRecord(e1, ctx->stream));
             ZK_HIP(ctx, hipStreamWaitEvent(s_acc, e1, 0));
@@ -123,8 +126,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e1, 0));
         rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);
     }
-    // accumulate order (job numbers: 0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H; H's scalars arrive last)
-    const int ord[5] = {0, 1, 2, 3, 4};
+    // accumulate order = job order (0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H; H's scalars arrive last)
     // A job of up to 2^16 terms occupies a tenth of the chip for the length of its longest bucket (~0.3 ms): five of them one
     // behind the other on the accumulate stream are most of a small proof.  There every job's accumulate kernel goes on the stream
     // of its own reduce chain instead (G2 alone on the accumulate stream, the G1 jobs alternating between the sort stream and the
@@ -138,8 +140,8 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     ZkMsmJob* g1jobs[4] = {J[1], J[2], J[3], J[4]};
     const bool grouped = chained || (small_jobs && rc == ZK_OK && zk_msm_group_ok(g1jobs, 4));
     for (int k = 0; k < 5 && rc == ZK_OK && !chained; k++) {
-        if (grouped && ord[k] != 0) continue;
-        if (!begun || ord[k] == 4) rc = zk_msm_enqueue_accum(ctx, J[ord[k]], small_jobs ? job_stream(ord[k]) : s_acc);
+        if (grouped && k != 0) continue;
+        if (!begun || k == 4) rc = zk_msm_enqueue_accum(ctx, J[k], small_jobs ? job_stream(k) : s_acc);
     }
     if (grouped && !chained && rc == ZK_OK) rc = zk_msm_enqueue_accum_group(ctx, g1jobs, 4, s_sort);
     // B-in-G2's reduce chain (the long one) stays on the sort stream; the four G1 reduces go to the main stream, idle by
@@ -149,10 +151,10 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     // through): on one stream the last job's chain queued behind its predecessor's, which was still waiting for slots
     // beside the last accumulate kernel, and ~0.6 ms of it ran after the GPU had otherwise gone idle.
     for (int k = 0; k < 5 && rc == ZK_OK && !chained; k++) {
-        hipStream_t rs = small_jobs ? job_stream(ord[k]) : ((ord[k] == 0 || (k & 1) == 0) ? s_red : ctx->stream);
-        if (begun && ord[k] == 0) continue;                 // B in G2's chain went out with zk_groth16_msms_begin_dev
-        if (grouped && ord[k] != 0) continue;
-        rc = zk_msm_enqueue_reduce(ctx, J[ord[k]], rs);
+        hipStream_t rs = small_jobs ? job_stream(k) : ((k & 1) == 0 ? s_sort : ctx->stream);
+        if (begun && k == 0) continue;                      // B in G2's chain went out with zk_groth16_msms_begin_dev
+        if (grouped && k != 0) continue;
+        rc = zk_msm_enqueue_reduce(ctx, J[k], rs);
     }
     if (grouped && !chained && rc == ZK_OK) rc = zk_msm_enqueue_reduce_group(ctx, g1jobs, 4, s_sort);
     // The caller announced the next assignment (zk_groth16_hint_next_dev): enqueue that proof's front now, behind this
@@ -177,7 +179,8 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         // H job's chain below.
         for (int k = 0; k < 4; k++)
             if (J[k]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(s_acc, J[k]->reduce_done, 0));
-        rc = zk_msm_prepare(ctx, &nf->job, pk->b_g2, 1, (const char*)zn + 32, nvars, 1);
+        const ZkG16Jobs N(pk, r, zn, h_scratch);
+        rc = N.prepare(ctx, 0, &nf->job, 1);
         if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->job, s_acc, nullptr);
         if (rc == ZK_OK) rc = zk_groth16_witness_map_dev(ctx, r, zn, h_scratch);
         if (rc == ZK_OK) {
@@ -186,7 +189,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
             if (J[4]->accum_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->accum_done, 0));
             // H's own chain (slot 5: k_fold reads ctr / heavy there) may be on the other stream
             if (J[4]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->reduce_done, 0));
-            rc = zk_msm_prepare(ctx, &nf->jobh, pk->h, 0, h_scratch, std::min(pk->h->n, D), 5);
+            rc = N.prepare(ctx, 4, &nf->jobh, 5);
             if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->jobh, ctx->stream, nullptr);
         }
         // A SMALL proof (its four G1 jobs one group): the next proof's whole device chain goes out as well -- accumulate launches and
@@ -197,14 +200,9 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         if (rc == ZK_OK && grouped && ctx->chain_fronts) {
             const int par = (ctx->front_parity ^= 1);
             nf->job.pin_key = 48 + par;
-            rc = zk_msm_prepare(ctx, &nf->j1, pk->a, 1, (const char*)zn + 32, nvars, 2);
-            if (rc == ZK_OK) rc = zk_msm_prepare(ctx, &nf->j2, pk->b_g1, 1, (const char*)zn + 32, nvars, 3);
-            if (rc == ZK_OK) rc = zk_msm_prepare(ctx, &nf->j3, pk->l_pad, 1, (const char*)zn + 32, nvars, 4);
             nf->j1.pin_key = 50 + par;                               // (the group's results travel in its first job's buffer)
-            if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->j1, s_acc, &nf->job);
-            const ZkMsmJob* nl = nf->job.c == nf->j1.c ? &nf->job : &nf->j1;
-            if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->j2, s_acc, nl);
-            if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->j3, s_acc, nl);
+            ZkMsmJob* nz[4] = {&nf->job, &nf->j1, &nf->j2, &nf->j3};
+            rc = N.sort_z(ctx, nz, s_acc, 1, 0, true);               // (l_shared here: the z-sort above serves all four)
             ZkMsmJob* ng[4] = {&nf->j1, &nf->j2, &nf->j3, &nf->jobh};
             if (rc == ZK_OK && zk_msm_group_ok(ng, 4)) {
                 rc = zk_msm_enqueue_accum(ctx, &nf->job, s_acc);
@@ -228,7 +226,6 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     }
     // finish in completion order: the host-side Horner of an early job overlaps the GPU work of the later ones
     void* outs[5] = {out_g2, &out_g1[2], &out_g1[3], &out_g1[1], &out_g1[0]};
-    int abc_left = 3;
     if (grouped && rc == ZK_OK) {
         // the four G1 jobs of a group become ready together: their host halves side by side, B in G2's on this thread
         void* gouts[4] = {outs[1], outs[2], outs[3], outs[4]};
@@ -239,14 +236,13 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         if (rc == ZK_OK && after_abc) after_abc();
     } else {
         for (int k = 0; k < 5 && rc == ZK_OK; k++) {
-            rc = zk_msm_finish(ctx, J[ord[k]], outs[ord[k]]);
-            if (ord[k] <= 2 && --abc_left == 0 && rc == ZK_OK && after_abc) after_abc();   // A, B1, B2 are in: the caller's host work overlaps the rest
+            rc = zk_msm_finish(ctx, J[k], outs[k]);
+            if (k == 2 && rc == ZK_OK && after_abc) after_abc();   // A, B1, B2 are in: the caller's host work overlaps the rest
         }
     }
     if (!front_enqueued) {                         // (with a front in flight the streams carry the next proof's kernels)
         (void)hipStreamSynchronize(s_sort);
         (void)hipStreamSynchronize(s_acc);
-        (void)hipStreamSynchronize(s_red);
         (void)hipStreamSynchronize(ctx->stream);
     }
     tm.resolve();
@@ -280,8 +276,7 @@ extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const z
     ZK_API_BEGIN(ctx)
     if (!ctx || !pk || !r || !z) return ZK_ERR_ARG;
     zk_presort_free(ctx);
-    const size_t nvars = (r->ni - 1) + r->nw;
-    if (pk->b_g2->n != nvars + 1) ZK_FAIL(ctx, ZK_ERR_ARG, "groth16: proving key does not match the constraint system");
+    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
     ZK_TRY(zk_prover_streams(ctx, 1));
     hipEvent_t e0;
     ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
@@ -291,7 +286,7 @@ extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const z
     std::unique_ptr<ZkPresort> p(new ZkPresort());
     p->pk = pk;
     p->z = z;
-    ZK_TRY(zk_msm_prepare(ctx, &p->job, pk->b_g2, 1, (const char*)z + 32, nvars, 1));
+    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr).prepare(ctx, 0, &p->job, 1));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &p->job, ctx->aux[0], nullptr));
     ctx->presort = p.release();
     return ZK_OK;
@@ -307,9 +302,7 @@ extern "C" int zk_groth16_msms_begin_dev(zk_ctx* ctx, const zk_pk* pk, const zk_
     ZK_API_BEGIN(ctx)
     if (!ctx || !pk || !r || !z) return ZK_ERR_ARG;
     zk_presort_free(ctx);
-    const size_t nvars = (r->ni - 1) + r->nw;
-    if (pk->a->n != nvars + 1 || pk->b_g1->n != nvars + 1 || pk->b_g2->n != nvars + 1 || pk->l->n != r->nw)
-        ZK_FAIL(ctx, ZK_ERR_ARG, "groth16: proving key does not match the constraint system");
+    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
     ZK_TRY(zk_prover_streams(ctx, 1));
     hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;
     hipEvent_t e0;
@@ -320,19 +313,10 @@ extern "C" int zk_groth16_msms_begin_dev(zk_ctx* ctx, const zk_pk* pk, const zk_
     (void)hipEventDestroy(e0);
     std::unique_ptr<ZkPresort> p(new ZkPresort());
     p->pk = pk; p->z = z; p->r = r; p->begun = true;
-    const char* zb = (const char*)z;
-    const bool l_shared = pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
-                          pk->l_pad->c_pre == pk->a->c_pre;
+    const ZkG16Jobs T(pk, r, z, nullptr);
     ZkMsmJob* J[4] = {&p->job, &p->j1, &p->j2, &p->j3};
-    int rc = zk_msm_prepare(ctx, J[0], pk->b_g2, 1, zb + 32, nvars, 1);
-    if (rc == ZK_OK) rc = zk_msm_prepare(ctx, J[1], pk->a, 1, zb + 32, nvars, 2);
-    if (rc == ZK_OK) rc = zk_msm_prepare(ctx, J[2], pk->b_g1, 1, zb + 32, nvars, 3);
-    if (rc == ZK_OK) rc = l_shared ? zk_msm_prepare(ctx, J[3], pk->l_pad, 1, zb + 32, nvars, 4)
-                                   : zk_msm_prepare(ctx, J[3], pk->l, 0, zb + r->ni * 32, r->nw, 4);
-    if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, J[0], s_sort, nullptr);
-    if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, J[1], s_sort, J[0]);
-    if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, J[2], s_sort, J[0]);
-    if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, l_shared ? J[0] : nullptr);
+    int rc = T.sort_z(ctx, J, s_sort, 1);
+    if (rc == ZK_OK && !T.l_shared) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);
     for (int k = 0; k < 4 && rc == ZK_OK; k++) rc = zk_msm_enqueue_accum(ctx, J[k], s_acc);
     // only the G2 job's reduce chain here (sort stream); the G1 chains are enqueued by zk_groth16_msms_dev, which spreads them over
     // the context stream (the caller's own kernels are through by then) and the sort stream as the one-call form does

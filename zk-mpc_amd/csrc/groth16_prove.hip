@@ -8,44 +8,61 @@ using namespace zk;
 
 // The O(1) tail of create_proof on the host, 64-bit limbs (hostfield64.hpp): calculate_coeff (src/groth16.rs:185-201: initial +
 // query[0] + acc + vk_param) for A, B-in-G1 and B-in-G2, the r / s terms (:115, :140, :161), C (:169-174) and the 192 bytes.
-// Everything that depends only on the A, B-in-G1 and B-in-G2 sums (and on r, s, the key) starts -- on the context's helper
-// threads -- as soon as those three MSMs have delivered (abc_ready), while the devices still work on L and H.
-ZkProofTail::ZkProofTail(zk_ctx* c, const zk_pk* pk, const zk_fr* r_, const zk_fr* s_) : ctx(c), glv(pk->points_in_subgroup) {
-    fr_abi_to_canon_words(r_->l, rw);
-    fr_abi_to_canon_words(s_->l, sw);
-    delta1 = xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk->delta_g1));
-    delta2 = xyzz_from_affine<H2>(aff_to_host64<G2Field>(pk->delta_g2));
-    a0 = aff_to_host64<G1Field>(pk->a0); alpha = aff_to_host64<G1Field>(pk->alpha_g1);
-    b0 = aff_to_host64<G1Field>(pk->b0_g1); beta1 = aff_to_host64<G1Field>(pk->beta_g1);
-    b02 = aff_to_host64<G2Field>(pk->b0_g2); beta2 = aff_to_host64<G2Field>(pk->beta_g2);
-    // the scalar multiplications that need no MSM result: four of the seven of a proof (0.2 - 0.7 ms each on one host thread)
-    pre_a = zk_async(ctx, [this] {
-        r_g1 = mul1(delta1, rw);
-        r_s_delta = mul1(r_g1, sw);                                                     // :115
-    });
-    pre_b = zk_async(ctx, [this] { s_g1 = mul1(delta1, sw); });
-    pre_2 = zk_async(ctx, [this] { s_g2 = host64_scalar_mul<H2>(delta2, sw); });
+namespace {
+using H1 = Fq64Field;
+using H2 = Fq264Field;
+using X1 = XYZZ<H1>;
+// G1 scalar multiplications through the endomorphism where the key's points are in the prime-order subgroup
+X1 mul1(const zk_pk* pk, const X1& p, const uint32_t* k) { return pk->points_in_subgroup ? host64_scalar_mul_glv(p, k) : host64_scalar_mul<H1>(p, k); }
+template <class H, class G>
+XYZZ<H> coeff(const XYZZ<H>& initial, const Affine<G>& q0, const void* acc, const Affine<G>& vk_param) {
+    return xyzz_madd<H>(xyzz_add<H>(xyzz_madd<H>(initial, aff_to_host64<G>(q0)), host64_proj_from_abi<H>((const uint64_t*)acc)), aff_to_host64<G>(vk_param));
+}
+}  // namespace
+
+void zk_tail_begin(const zk_fr* r, const zk_fr* s, ZkTail* t) {
+    fr_abi_to_canon_words(r->l, t->rw);
+    fr_abi_to_canon_words(s->l, t->sw);
+}
+// the scalar multiplications that need no MSM result: four of the seven of a proof (0.2 - 0.7 ms each on one host thread)
+void zk_tail_pre_a(const zk_pk* pk, ZkTail* t) {
+    t->r_g1 = mul1(pk, xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk->delta_g1)), t->rw);
+    t->r_s_delta = mul1(pk, t->r_g1, t->sw);                                                               // :115
+}
+void zk_tail_pre_b(const zk_pk* pk, ZkTail* t) { t->s_g1 = mul1(pk, xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk->delta_g1)), t->sw); }
+void zk_tail_pre_2(const zk_pk* pk, ZkTail* t) { t->s_g2 = host64_scalar_mul<H2>(xyzz_from_affine<H2>(aff_to_host64<G2Field>(pk->delta_g2)), t->sw); }
+void zk_tail_chain_a(const zk_pk* pk, ZkTail* t, const zk_g1_projective& a_sum) {
+    t->g_a = coeff<H1>(t->r_g1, pk->a0, &a_sum, pk->alpha_g1);
+    t->s_g_a = mul1(pk, t->g_a, t->sw);                                                                    // :140
+}
+void zk_tail_chain_b(const zk_pk* pk, ZkTail* t, const zk_g1_projective& b1_sum) {
+    t->r_g1_b = mul1(pk, coeff<H1>(t->s_g1, pk->b0_g1, &b1_sum, pk->beta_g1), t->rw);                      // :161
+}
+void zk_tail_chain_2(const zk_pk* pk, ZkTail* t, const zk_g2_projective& b2_sum) {
+    t->b_aff = xyzz_to_affine<H2>(coeff<H2>(t->s_g2, pk->b0_g2, &b2_sum, pk->beta_g2));
+}
+void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
+    X1 g_c = xyzz_add<H1>(t.s_g_a, t.r_g1_b);                                                              // :169-174
+    g_c = xyzz_add<H1>(g_c, xyzz_neg<H1>(t.r_s_delta));
+    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&l_sum));
+    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&h_sum));
+    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(t.g_a)), proof);
+    g2_serialize(aff_from_host64<G2Field>(t.b_aff), proof + 48);
+    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
 }
 
+ZkProofTail::ZkProofTail(zk_ctx* c, const zk_pk* pk_, const zk_fr* r_, const zk_fr* s_) : ctx(c), pk(pk_) {
+    zk_tail_begin(r_, s_, &t);
+    pre_a = zk_async(ctx, [this] { zk_tail_pre_a(pk, &t); });
+    pre_b = zk_async(ctx, [this] { zk_tail_pre_b(pk, &t); });
+    pre_2 = zk_async(ctx, [this] { zk_tail_pre_2(pk, &t); });
+}
+
+// (the sums are copied: the caller's may be overwritten while the chains run)
 void ZkProofTail::abc_ready(const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum, const zk_g2_projective& b2_sum) {
-    const X1 a_acc = host64_proj_from_abi<H1>((const uint64_t*)&a_sum);
-    const X1 b1_acc = host64_proj_from_abi<H1>((const uint64_t*)&b1_sum);
-    const X2 b2_acc = host64_proj_from_abi<H2>((const uint64_t*)&b2_sum);
-    chain_a = zk_async(ctx, [this, a_acc] {
-        pre_a.wait();
-        g_a = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(r_g1, a0), a_acc), alpha);
-        s_g_a = mul1(g_a, sw);                                                           // :140
-    });
-    chain_b = zk_async(ctx, [this, b1_acc] {
-        pre_b.wait();
-        const X1 g1_b = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(s_g1, b0), b1_acc), beta1);
-        r_g1_b = mul1(g1_b, rw);                                                         // :161
-    });
-    chain_g2 = zk_async(ctx, [this, b2_acc] {
-        pre_2.wait();
-        const X2 g2_b = xyzz_madd<H2>(xyzz_add<H2>(xyzz_madd<H2>(s_g2, b02), b2_acc), beta2);
-        b_aff = xyzz_to_affine<H2>(g2_b);
-    });
+    chain_a = zk_async(ctx, [this, a_sum] { pre_a.wait(); zk_tail_chain_a(pk, &t, a_sum); });
+    chain_b = zk_async(ctx, [this, b1_sum] { pre_b.wait(); zk_tail_chain_b(pk, &t, b1_sum); });
+    chain_g2 = zk_async(ctx, [this, b2_sum] { pre_2.wait(); zk_tail_chain_2(pk, &t, b2_sum); });
 }
 
 void ZkProofTail::join() {
@@ -60,55 +77,7 @@ void ZkProofTail::join() {
 
 void ZkProofTail::finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
     join();
-    const X1 h_acc = host64_proj_from_abi<H1>((const uint64_t*)&h_sum);
-    const X1 l_acc = host64_proj_from_abi<H1>((const uint64_t*)&l_sum);
-    X1 g_c = xyzz_add<H1>(s_g_a, r_g1_b);                                                                 // :169-174
-    g_c = xyzz_add<H1>(g_c, xyzz_neg<H1>(r_s_delta));
-    g_c = xyzz_add<H1>(g_c, l_acc);
-    g_c = xyzz_add<H1>(g_c, h_acc);
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_a)), proof);
-    g2_serialize(aff_from_host64<G2Field>(b_aff), proof + 48);
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
-}
-
-void zk_proof_tail_pre(const zk_pk* pk, const zk_fr* r, const zk_fr* s, ZkTailPre* t) {
-    using H1 = Fq64Field;
-    using H2 = Fq264Field;
-    const bool glv = pk->points_in_subgroup;
-    auto mul1 = [glv](const XYZZ<H1>& p, const uint32_t* k) { return glv ? host64_scalar_mul_glv(p, k) : host64_scalar_mul<H1>(p, k); };
-    fr_abi_to_canon_words(r->l, t->rw);
-    fr_abi_to_canon_words(s->l, t->sw);
-    const XYZZ<H1> delta1 = xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk->delta_g1));
-    t->r_g1 = mul1(delta1, t->rw);
-    t->r_s_delta = mul1(t->r_g1, t->sw);
-    t->s_g1 = mul1(delta1, t->sw);
-    t->s_g2 = host64_scalar_mul<H2>(xyzz_from_affine<H2>(aff_to_host64<G2Field>(pk->delta_g2)), t->sw);
-}
-
-void zk_proof_tail_rest(const zk_pk* pk, const ZkTailPre& t, const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum,
-                        const zk_g2_projective& b2_sum, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
-    using H1 = Fq64Field;
-    using H2 = Fq264Field;
-    const bool glv = pk->points_in_subgroup;
-    auto mul1 = [glv](const XYZZ<H1>& p, const uint32_t* k) { return glv ? host64_scalar_mul_glv(p, k) : host64_scalar_mul<H1>(p, k); };
-    const XYZZ<H1> a_acc = host64_proj_from_abi<H1>((const uint64_t*)&a_sum);
-    const XYZZ<H1> b1_acc = host64_proj_from_abi<H1>((const uint64_t*)&b1_sum);
-    const XYZZ<H2> b2_acc = host64_proj_from_abi<H2>((const uint64_t*)&b2_sum);
-    const XYZZ<H1> g_a = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(t.r_g1, aff_to_host64<G1Field>(pk->a0)), a_acc),
-                                       aff_to_host64<G1Field>(pk->alpha_g1));
-    const XYZZ<H1> s_g_a = mul1(g_a, t.sw);
-    const XYZZ<H1> g1_b = xyzz_madd<H1>(xyzz_add<H1>(xyzz_madd<H1>(t.s_g1, aff_to_host64<G1Field>(pk->b0_g1)), b1_acc),
-                                        aff_to_host64<G1Field>(pk->beta_g1));
-    const XYZZ<H1> r_g1_b = mul1(g1_b, t.rw);
-    const XYZZ<H2> g2_b = xyzz_madd<H2>(xyzz_add<H2>(xyzz_madd<H2>(t.s_g2, aff_to_host64<G2Field>(pk->b0_g2)), b2_acc),
-                                        aff_to_host64<G2Field>(pk->beta_g2));
-    XYZZ<H1> g_c = xyzz_add<H1>(s_g_a, r_g1_b);
-    g_c = xyzz_add<H1>(g_c, xyzz_neg<H1>(t.r_s_delta));
-    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&l_sum));
-    g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&h_sum));
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_a)), proof);
-    g2_serialize(aff_from_host64<G2Field>(xyzz_to_affine<H2>(g2_b)), proof + 48);
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
+    zk_tail_finish(t, h_sum, l_sum, proof);
 }
 
 extern "C" int zk_groth16_prove_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const zk_fr* r_, const zk_fr* s_,
@@ -152,22 +121,17 @@ extern "C" int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1
         z = ctx->next_z_dev;
         ctx->z_slot ^= 1;
         ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next_z_ready, 0));
+        ZK_TRY(zk_next_z_drop(ctx, false));
     } else {
         // Not the announced assignment (or announced for another key / system / length: the upload may be shorter than m).  A
         // front enqueued for the announced one still reads the other slot, and its z-sort / witness map may run for as long as
         // this proof takes: let it drain before either slot is written (run_msms would only drop it later).
-        zk_presort_free(ctx);
-        if (ctx->copy_stream) ZK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+        ZK_TRY(zk_next_z_drop(ctx, true));
         ZK_TRY(zk_scratch(ctx, ctx->z_slot ? "prove_z1" : "prove_z0", m * 32, &z));
         // page-locked memory (zk_host_alloc) goes to the DMA engine as it is; anything else through the context's ring, so that
         // the runtime never pins memory the caller is about to free (hostxfer.hip)
         ZK_TRY(zk_xfer_h2d(ctx, z, z_host, m * 32, zk_host_is_pinned(z_host)));
     }
-    ctx->next_z_host = nullptr;
-    ctx->next_z_dev = nullptr;
-    ctx->next_z = nullptr;
-    ctx->next_z_pk = ctx->next_z_r = nullptr;
-    ctx->next_z_m = 0;
     if (z_next_host) {
         if (!ctx->copy_stream) ZK_HIP(ctx, zk_stream_create(&ctx->copy_stream, false));
         if (!ctx->next_z_ready) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->next_z_ready, hipEventDisableTiming));
