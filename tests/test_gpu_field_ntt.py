@@ -2,7 +2,9 @@
 import numpy as np
 import pytest
 
+import ntt_cases as NC
 import zkref as O
+import zk_mpc_amd as Z
 import zk_mpc_amd.convert as cv
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +38,63 @@ def test_batch_product_in_place_host(ctx):
     ctx.batch_product_in_place(am, bm)
     assert cv.fr_from_mont(am) == [x * y % O.R_MOD for x, y in zip(a, b)]
     ctx.batch_product_in_place(am[:0], bm[:0])  # empty input
+
+
+SHARE_SIZES = [1, 255, 256, 257, 70000]       # below, on and above one 256-thread block; several blocks
+
+
+def share_inputs(kind, n, count, seed):
+    """`count` residue vectors: uniform random, every element r - 1, or every element 0."""
+    if kind == "random":
+        rs = np.random.RandomState(seed)
+        return [NC.uniform(rs, n) for _ in range(count)]
+    return [np.tile(NC.limbs([O.R_MOD - 1 if kind == "top" else 0])[0], (n, 1)) for _ in range(count)]
+
+
+@pytest.mark.parametrize("leader", [True, False])
+@pytest.mark.parametrize("n", SHARE_SIZES)
+def test_beaver_combine_direct(ctx, n, leader):
+    """zk_beaver_combine_dev called directly (k_beaver: the 2^5 of the device's internal form goes in once per opened value,
+    fr_mul32): tz - sx ty - oy tx (+ sx oy on the leader) with a real triple, and 1 - a - b + ab (leader) / 0 (others) with the
+    dummy triple source, in python integers; random, all r - 1 and all 0 inputs; leader and non-leader contexts."""
+    R, rinv = O.R_MOD, pow(NC.MONT, -1, O.R_MOD)
+    c = ctx if leader else Z.Context(0, 1, 2)
+    try:
+        for kind in ("random", "top", "zero"):
+            vecs = share_inputs(kind, n, 5, 50 + n)
+            sx, oy, tx, ty, tz = (NC.ints(v) for v in vecs)
+            dev = [c.upload(v) for v in vecs]
+            out = c.alloc(n * 32)
+            c.beaver_combine_dev(dev[0].ptr, dev[1].ptr, out.ptr, n, triple=(dev[2].ptr, dev[3].ptr, dev[4].ptr))
+            lead = (lambda a, b: a * b * rinv) if leader else (lambda a, b: 0)
+            want = NC.limbs((z - a * y * rinv - b * x * rinv + lead(a, b)) % R for a, b, x, y, z in zip(sx, oy, tx, ty, tz))
+            bad = NC.mismatch(c.download(out, (n, 4)), want)
+            assert bad is None, "real triple, %s: %s" % (kind, bad)
+            c.beaver_combine_dev(dev[0].ptr, dev[1].ptr, out.ptr, n)
+            want = NC.limbs((NC.MONT - a - b + a * b * rinv) % R if leader else 0 for a, b in zip(sx, oy))
+            bad = NC.mismatch(c.download(out, (n, 4)), want)
+            assert bad is None, "dummy triple, %s: %s" % (kind, bad)
+            for buf in dev + [out]:
+                buf.free()
+    finally:
+        if not leader:
+            c.close()
+
+
+@pytest.mark.parametrize("parties", [1, 2, 3, 8])
+@pytest.mark.parametrize("n", SHARE_SIZES)
+def test_sum_parties_direct(ctx, n, parties):
+    """zk_fr_sum_parties_dev: out[i] = sum_p gathered[p n + i] mod r, for random shares and for all r - 1 (with eight parties:
+    a sum of eight maximal residues)."""
+    for kind in ("random", "top"):
+        g = np.concatenate(share_inputs(kind, n, parties, 60 + n + parties))
+        cols = [NC.ints(g[p * n:(p + 1) * n]) for p in range(parties)]
+        dg, out = ctx.upload(g), ctx.alloc(n * 32)
+        ctx.fr_sum_parties_dev(dg.ptr, parties, n, out.ptr)
+        bad = NC.mismatch(ctx.download(out, (n, 4)), NC.limbs(sum(t) % O.R_MOD for t in zip(*cols)))
+        dg.free()
+        out.free()
+        assert bad is None, "%s: %s" % (kind, bad)
 
 
 @pytest.mark.parametrize("log_n", [0, 1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 13, 14, 15, 17])

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import marlin_ref as M
+import ntt_cases as NC
 import zkref as O
 import zk_mpc_amd.convert as cv
 from helpers import mont1
@@ -121,6 +122,140 @@ def test_poly_mul(ctx, na, nb):
     da, db, out = up(ctx, a), up(ctx, b), ctx.alloc((na + nb) * 32)
     ctx.poly_mul_dev(da.ptr, na, db.ptr, nb, out.ptr)
     assert cv.fr_from_mont(ctx.download(out, (na + nb - 1, 4))) == O.poly_mul(a, b)
+
+
+R = O.R_MOD
+R2 = NC.MONT * NC.MONT % R          # a residue x R inverts to x^-1 R = (x R)^-1 R^2
+
+
+def inv_chunk(n):
+    """Elements per lane of zk_fr_batch_inverse_dev: 8 / 16 / 32 while <= 2048 chunk totals go to the host, 32 in k_batch_inverse."""
+    ch = 8
+    while ch < 32 and (n + ch - 1) // ch > 2048:
+        ch *= 2
+    return ch
+
+
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 16384, 16385, 32768, 32769, 65536, 65537, (1 << 20) + 3])
+def test_batch_inversion_dispatch_seams(ctx, n):
+    """zk_fr_batch_inverse_dev on both sides of each of its four paths (host-inverted chunk totals with 8, 16, 32 elements per
+    lane up to 16 384 / 32 768 / 65 536 elements, the one-kernel form above), with zeros where the chunk walk could trip: none,
+    all, one whole chunk, the whole (partial) last chunk, the first and last slot of a chunk, index 0 and n - 1.  The values 1,
+    -1 and the residue r - 1 are in every vector.  Reference: pow(x, -1, r), zeros left zero (from 2^20 on Montgomery's trick in
+    python, held to x * inv == 1 on every element)."""
+    ch = inv_chunk(n)
+    v = NC.uniform(np.random.RandomState(4000 + n % 1000), n)
+    special = NC.limbs([NC.MONT, R - NC.MONT, R - 1])
+    for k in range(min(3, n - 1)):
+        v[n // 3 + k] = special[k]
+    xs = NC.ints(v)
+    assert all(xs)
+    if n <= 1 << 17:
+        inv = [pow(x, -1, R) * R2 % R for x in xs]
+    else:
+        pre, run = [], 1
+        for x in xs:
+            pre.append(run)
+            run = run * x % R
+        acc, inv = pow(run, -1, R), [0] * n
+        for i in range(n - 1, -1, -1):
+            inv[i] = acc * pre[i] % R * R2 % R
+            acc = acc * xs[i] % R
+    assert all(x * y % R == R2 for x, y in zip(xs, inv))
+    want = NC.limbs(inv)
+    mid = (((n + ch - 1) // ch) // 2) * ch
+    mid_end = min(n, mid + ch)
+    last = ((n - 1) // ch) * ch
+    patterns = {"none": [], "all": range(n), "chunk": range(mid, mid_end), "last_chunk": range(last, n),
+                "chunk_edges": [mid, mid_end - 1], "ends": [0, n - 1]}
+    for name, zeros in patterns.items():
+        zeros = np.array(list(zeros), dtype=np.int64)
+        a, w = v.copy(), want.copy()
+        a[zeros] = 0
+        w[zeros] = 0
+        d = ctx.upload(a)
+        ctx.batch_inversion_dev(d.ptr, n)
+        bad = NC.mismatch(ctx.download(d, (n, 4)), w)
+        d.free()
+        assert bad is None, "zeros '%s', %d elements per lane: %s" % (name, ch, bad)
+
+
+@pytest.mark.parametrize("n", [1, 8, 9, 65536, 65537, (1 << 20) + 5])
+def test_powers_dispatch_seam(ctx, n):
+    """zk_fr_powers_dev on both sides of its switch from 8 to 32 powers per lane (n = 2^16) and at lane ends, for the bases
+    0, 1, -1, a 2^10-th root of unity (the sequence has to cycle exactly) and random, from the starts 0, 1 and random."""
+    rng = O.Prng(4100 + n % 1000)
+    root = O.Domain(1 << 10).group_gen
+    out = ctx.alloc(n * 32)
+    for base in (0, 1, R - 1, root, rng.fr()):
+        for start in (0, 1, rng.fr()):
+            ctx.fr_powers_dev(mont1(base), mont1(start), n, out.ptr)
+            got = ctx.download(out, (n, 4))
+            bad = NC.mismatch(got, NC.geometric(NC.mont(start), base, n))
+            assert bad is None, "base %x start %x: %s" % (base, start, bad)
+            if base == root and n > 1024:
+                assert np.array_equal(got[1024:], got[:-1024])
+    out.free()
+
+
+def horner(c, z):
+    acc = 0
+    for x in reversed(c):
+        acc = (acc * z + x) % R
+    return acc
+
+
+@pytest.mark.parametrize("na,nb", [(600, 425), (600, 426), (2500, 1597), (2500, 1598), ((1 << 19) + 7, (1 << 19) - 6),
+                                   ((1 << 19) + 7, (1 << 19) - 5)])
+def test_poly_mul_pass_seams(ctx, na, nb):
+    """zk_poly_mul_dev with na + nb - 1 on both sides of 2^10 (one-pass -> two-pass transforms), 2^12 and 2^20 (two -> three
+    passes).  Operands, all as residues x R:
+      random x random -- against the schoolbook product O.poly_mul up to 2^12; above, a(z) b(z) == out(z) at two random z by
+        Horner in python (a wrong product passes one point with probability at most degree / r < 2^-230);
+      sparse x dense -- a has five non-zero terms (both ends among them), so the product is five shifted multiples of b;
+      all r - 1 x all r - 1 -- maximal residues: out[k] = c^2 * #{(i, j): i + j = k}."""
+    nout = na + nb - 1
+    rs = np.random.RandomState(na + nb)
+    rinv = pow(NC.MONT, -1, R)
+
+    def product(a, b):
+        da, db, out = ctx.upload(a), ctx.upload(b), ctx.alloc((nout + 1) * 32)
+        ctx.poly_mul_dev(da.ptr, na, db.ptr, nb, out.ptr)
+        got = ctx.download(out, (nout, 4))
+        for buf in (da, db, out):
+            buf.free()
+        assert NC.below_r(got).all()
+        return got
+
+    # random x random
+    a, b = NC.uniform(rs, na), NC.uniform(rs, nb)
+    ai, bi = NC.ints(a), NC.ints(b)
+    got = product(a, b)
+    if nout <= 1 << 13:
+        assert NC.mismatch(got, NC.limbs(x * rinv % R for x in O.poly_mul(ai, bi))) is None
+    else:
+        gi = NC.ints(got)
+        for z in (O.Prng(na).fr(), O.Prng(nb).fr()):
+            assert horner(ai, z) * horner(bi, z) % R == horner(gi, z) * NC.MONT % R
+    # sparse x dense
+    terms = {0: ai[0], 1: R - 1, na // 2: NC.MONT, na - 2: ai[na - 2], na - 1: R - NC.MONT}
+    sp = np.zeros((na, 4), dtype=np.uint64)
+    want = [0] * nout
+    for pos, c in terms.items():
+        sp[pos] = NC.limbs([c])[0]
+        cr = c * rinv % R
+        for j, y in enumerate(bi):
+            want[pos + j] += cr * y
+    bad = NC.mismatch(product(sp, b), NC.limbs(x % R for x in want))
+    assert bad is None, "sparse x dense: %s" % bad
+    # all r - 1
+    top = NC.limbs([R - 1])[0]
+    k = np.arange(nout, dtype=np.int64)
+    count = np.minimum(np.minimum(k + 1, nout - k), min(na, nb))
+    c2 = (R - 1) * (R - 1) * rinv % R
+    want = NC.limbs(c2 * m % R for m in count.tolist())
+    bad = NC.mismatch(product(np.tile(top, (na, 1)), np.tile(top, (nb, 1))), want)
+    assert bad is None, "all r - 1: %s" % bad
 
 
 def test_kzg10_commit_open_check(ctx):
