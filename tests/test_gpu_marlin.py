@@ -261,3 +261,49 @@ def test_native_marlin_prove_equals_the_python_sequence(ctx, n):
     bad = list(zz); bad[dix.num_instance + 1] = (bad[dix.num_instance + 1] + 1) % O.R_MOD
     with pytest.raises(Exception, match="sum over H|divisible"):
         DM.prove_native(keys, ctx.upload(cv.fr_to_mont(bad)), Rng.from_seed(seed, 20))
+
+
+# ---- |H| = 2^18: the smallest size at which the one-call prover starts MSMs ahead of their round's batch -------------------------
+
+@pytest.fixture(scope="module")
+def early_case(ctx):
+    """The mul-chain with n = 2^18 - 3 (|H| = |K| = 2^18), its index and SRS, and the proof bytes of the Python sequence -- which
+    never starts an MSM early -- computed once for the tests below."""
+    import os
+    import types
+    from zk_mpc_amd.api import Rng
+    assert os.environ.get("ZK_MARLIN_EARLY", "1") != "0", "ZK_MARLIN_EARLY=0 keeps every MSM in its round's batch: nothing starts early"
+    m = DM.HostField.m
+    n = (1 << 18) - 3
+    ni, nw, a, b, c = DM.mul_chain_system(ctx, n)
+    index = DM.Index(ctx, ni, nw, a, b, c)
+    assert index.dom_h.size == 1 << 18
+    keys = DM.IndexKeys(index, DM.UniversalSrs(ctx, DM.ahp_max_degree(index) + 5, 0x1234567, 3, 7))
+    z = ctx.mul_chain_assignment_dev(n, m(3), m(5))
+    seed = bytes((5 * i + 2) & 0xff for i in range(32))
+    want = DM.prove(keys, z, Rng.from_seed(seed, 20), mask_on_device=True).serialize(ctx)
+    return types.SimpleNamespace(n=n, ni=ni, keys=keys, z=z, seed=seed, want=want)
+
+
+def test_native_equals_python_sequence_with_early_msms(ctx, early_case):
+    """From |H| = 2^18 zk_marlin_prove starts the MSMs of the mask polynomial, t and g_2 before their round's batch: the same
+    bytes as the Python sequence, and the same again from the scratch the first call left."""
+    from zk_mpc_amd.api import Rng
+    e = early_case
+    assert DM.prove_native(e.keys, e.z, Rng.from_seed(e.seed, 20), mask_on_device=True) == e.want
+    assert DM.prove_native(e.keys, e.z, Rng.from_seed(e.seed, 20), mask_on_device=True) == e.want
+
+
+def test_failed_proof_with_early_job_in_flight_leaves_context_usable(ctx, early_case):
+    """Over shares (one party: its transport object is never called) the outer sum-check's zero test is a synchronous open behind the start of t's MSMs:
+    an unsatisfied system is refused while that early job is in flight.  The job is drained, and the context proves as before."""
+    from zk_mpc_amd import mpc
+    from zk_mpc_amd.api import Rng
+    e = early_case
+    bad = ctx.download(e.z, (e.n + 3, 4))
+    k = e.ni + 1                                                  # one witness element
+    bad[k] = cv.fr_to_mont([(cv.fr_from_mont(bad[k].reshape(1, 4))[0] + 1) % O.R_MOD])[0]
+    party = mpc.Party(ctx, net=mpc.LocalNet.create(1)[0])
+    with pytest.raises(Exception, match="sum over H"):
+        party.marlin_prove_shared_native(e.keys, ctx.upload(bad), Rng.from_seed(e.seed, 20), mask_on_device=True)
+    assert DM.prove_native(e.keys, e.z, Rng.from_seed(e.seed, 20), mask_on_device=True) == e.want

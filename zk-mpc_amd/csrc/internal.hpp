@@ -20,6 +20,9 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs_dev, int count, uint32_t 
 int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp = nullptr);
 int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
 
+// rng.hip: four little-endian 64-bit words are a canonical field element (< r): what Fr::rand keeps and what a prover accepts from a peer
+bool zk_fr_words_valid(const uint64_t l[4]);
+
 // vec_ops.hip
 // core.hip: a launch-bound sequence on ONE stream as a captured graph from its third use with the same key (see there)
 int zk_graph_run(zk_ctx* ctx, const std::string& key, hipStream_t st, const std::function<int()>& enqueue);

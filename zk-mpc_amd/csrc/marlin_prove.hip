@@ -10,6 +10,9 @@
 // The same sequence exists as zk-mpc_amd/marlin.py::prove (kept: it is what the collaborative provers build on, and the two are
 // tested against each other and against the oracle's independent prover byte for byte).  The index (Marlin::index: matrix
 // arithmetisation, index commitments) is a one-off set-up and stays with the caller, who hands over device-resident tables.
+//
+// Layout: ORACLES states once what each oracle is; MsmJobs is the argument list of one zk_msm_batch_dev call; Marlin<LANES> is one proof in
+// progress: its members are what crosses the rounds, its methods are the steps that marlin_impl runs in order.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "hostgroup.hpp"
@@ -20,7 +23,6 @@
 #include <chrono>
 #include <future>
 #include <array>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -79,18 +81,47 @@ struct Dom {
 struct Poly { char* p = nullptr; size_t n = 0; };        // n coefficients on the device
 struct Comm { Affine<G1Field> c, s; bool has_shift = false; };
 
+
+// ---- the oracles: the nine the prover sends, in the order their rounds commit (and serialise) them, then the index's twelve ----
+enum Oracle : int {
+    O_W, O_Z_A, O_Z_B, O_MASK_POLY, O_T, O_G_1, O_H_1, O_G_2, O_H_2,
+    O_A_ROW, O_A_COL, O_A_VAL, O_A_ROW_COL, O_B_ROW, O_B_COL, O_B_VAL, O_B_ROW_COL, O_C_ROW, O_C_COL, O_C_VAL, O_C_ROW_COL,
+    N_ORACLES, N_PROVER = O_A_ROW, O_NONE = -1
+};
+enum IndexPart : int { ROW, COL, VAL, ROW_COL };                        // the index oracles of matrix m = 0 (A), 1 (B), 2 (C)
+constexpr Oracle index_of(int m, IndexPart part) { return Oracle(O_A_ROW + 4 * m + part); }
+static_assert(index_of(0, ROW_COL) == O_A_ROW_COL && index_of(1, VAL) == O_B_VAL && index_of(2, COL) == O_C_COL, "Oracle lists row, col, val, row_col per matrix");
+enum class Bound { None, H, K };            // degree bound: none, |H| - 2, |K| - 2
+enum class EarlyMsm { No, Plain, Always };  // may its MSM start before the round's batch: never / not over shares / in every mode
+// label: error texts | round that commits it, 1 - 3 (0: an index oracle) | hiding: committed with a blinding polynomial (bound 1) | shared:
+// witness-dependent (mpc.py: Party.SHARED_POLYS; t, g_2, h_2 and the index are public) | early: see Marlin::start_early
+struct OracleInfo { const char* label; int round; bool hiding; Bound bound; bool shared; EarlyMsm early; };
+constexpr OracleInfo index_oracle(const char* label) { return {label, 0, false, Bound::None, false, EarlyMsm::No}; }
+constexpr OracleInfo ORACLES[N_ORACLES] = {
+    {"w", 1, true, Bound::None, true, EarlyMsm::No},
+    {"z_a", 1, true, Bound::None, true, EarlyMsm::No},
+    {"z_b", 1, true, Bound::None, true, EarlyMsm::No},
+    {"mask_poly", 1, false, Bound::None, true, EarlyMsm::Plain},     // (over shares every lane's job stays in the batch)
+    {"t", 2, false, Bound::None, false, EarlyMsm::Always},
+    {"g_1", 2, true, Bound::H, true, EarlyMsm::No},
+    {"h_1", 2, false, Bound::None, true, EarlyMsm::No},
+    {"g_2", 3, false, Bound::K, false, EarlyMsm::Always},
+    {"h_2", 3, false, Bound::None, false, EarlyMsm::No},
+    index_oracle("a_row"), index_oracle("a_col"), index_oracle("a_val"), index_oracle("a_row_col"), index_oracle("b_row"), index_oracle("b_col"),
+    index_oracle("b_val"), index_oracle("b_row_col"), index_oracle("c_row"), index_oracle("c_col"), index_oracle("c_val"), index_oracle("c_row_col"),
+};
+std::vector<Oracle> round_oracles(int round) {
+    std::vector<Oracle> v;
+    for (int o = 0; o < N_PROVER; o++) if (ORACLES[o].round == round) v.push_back((Oracle)o);
+    return v;
+}
+
+// One lane -- 0: the share lane (or the plain prover), 1: the MAC lane of a SPDZ prover, own scratch names: its polynomials, the device calls on them
 struct Prover {
     zk_ctx* ctx;
-    const zk_marlin_index* ix;
-    const zk_bases *pg, *pgg;
-    size_t max_degree;
-    zk_rng* rng;
-    int lane = 0;                      // 0: the share lane (or the plain prover); 1: the MAC lane of a SPDZ prover -- own scratch names
+    int lane = 0;
     int rc = ZK_OK;
-    std::map<std::string, Poly> polys;
-    std::map<std::string, std::pair<std::vector<HF>, std::vector<HF>>> rands;   // label -> (blind, shifted blind)
-    std::map<std::string, Comm> comms;
-    std::map<std::string, size_t> bounds;
+    Poly polys[N_ORACLES];
 
     char* dev(const std::string& name, size_t elems) {
         void* p = nullptr;
@@ -121,7 +152,6 @@ struct Prover {
         return out;
     }
     bool is_zero(const void* v, size_t n) { int z = 0; ck(zk_fr_vec_is_zero_dev(ctx, v, n, &z)); return z != 0; }
-    HF eval(const Poly& p, const HF& x) { zk_fr xx = x.abi(), o; ck(zk_poly_evaluate_dev(ctx, p.p, p.n, &xx, &o)); return HF::from_abi(o); }
     HF next_fr(zk_rng* r) { zk_fr o; ck(zk_rng_next_fr(r, &o)); return HF::from_abi(o); }
     // p + r (X^n - 1) for deg p < n: one more coefficient
     Poly blind(const char* poly, size_t n, const char* r_dev, const std::string& name) {
@@ -150,9 +180,8 @@ void comm_tobytes(const Comm& c, std::vector<uint8_t>& out) {              // ma
     out.push_back(c.has_shift ? 1 : 0);
     g1_tobytes(c.has_shift ? c.s : aff_inf<G1Field>(), out);
 }
-Affine<G1Field> proj_to_aff(const zk_g1_projective& p) { return xyzz_to_affine<G1Field>(host_proj_from_abi<G1Field>((const uint64_t*)&p)); }
-// ... of several points with ONE field inversion (the commitments of a round: 2 - 6 points, an inversion is ~400 products) in
-// the 64-bit host field
+// projective -> affine for several points with ONE field inversion (the commitments of a round: 2 - 6 points, an inversion is ~400
+// products) in the 64-bit host field
 std::vector<Affine<G1Field>> batch_to_aff(const std::vector<zk_g1_projective>& pts) {
     using H = Fq64Field;
     const size_t n = pts.size();
@@ -194,22 +223,11 @@ void acc_scaled(std::vector<HF>& dst, const std::vector<HF>& src, const HF& k) {
 }
 
 // sum_i c_i G_i for the three powers_of_gamma_g a hiding bound of 1 uses: on the host (a three-term MSM through the device
-// pipeline costs a full sort / accumulate / reduce round trip, ~0.5 ms; this is three scalar multiplications in 64-bit limbs)
-zk_g1_projective small_msm(const zk_g1_projective* pts, const std::vector<HF>& c) {
-    zk_g1_projective acc{};
-    bool first = true;
-    for (size_t i = 0; i < c.size(); i++) {
-        zk_fr k = c[i].abi();
-        zk_g1_projective t, u;
-        zk_g1_mul(&pts[i], &k, &t);
-        if (first) { acc = t; first = false; } else { zk_g1_add(&acc, &t, &u); acc = u; }
-    }
-    return acc;
-}
-// ... with the scalar multiplications side by side on the context's helper threads (0.2 ms each: three in a row were longer than
-// the device batch of a small proof's round they are meant to hide under)
+// pipeline costs a full sort / accumulate / reduce round trip, ~0.5 ms; this is three scalar multiplications in 64-bit limbs), side
+// by side on the context's helper threads (0.2 ms each: three in a row were longer than the device batch of a small proof's round
+// they are meant to hide under)
 zk_g1_projective small_msm_par(zk_ctx* ctx, const zk_g1_projective* pts, const std::vector<HF>& c) {
-    if (c.size() < 2) return small_msm(pts, c);
+    if (c.empty()) return zk_g1_projective{};
     std::vector<zk_g1_projective> t(c.size());
     {
         std::vector<ZkTask<void>> tasks;
@@ -223,27 +241,46 @@ zk_g1_projective small_msm_par(zk_ctx* ctx, const zk_g1_projective* pts, const s
     return acc;
 }
 
-const char* const INDEX_LABELS[12] = {"a_row", "a_col", "a_val", "a_row_col", "b_row", "b_col", "b_val", "b_row_col",
-                                      "c_row", "c_col", "c_val", "c_row_col"};
-struct Term { HF c; const char* label; };      // label = nullptr: the constant term (LCTerm::One)
-
-}  // namespace
-
-extern "C" size_t zk_marlin_proof_max_size(void) { return 8 + 3 * 8 + 9 * 49 + 2 * 48 + 8 + 7 * 32 + 8 + 3 + 8 + 2 * (49 + 32) + 1; }
-
-namespace {
-
-bool fr_words_valid_abi(const uint64_t l[4]) {       // < r (is_valid, ff/src/fields/macros.rs:255-260): what arrives from a peer
-    Fr m;
-    for (int i = 0; i < 9; i++) m.l[i] = FrParams::P[i];
-    uint64_t pm[4];
-    host_store_ext<FrParams>(pm, m);
-    for (int i = 3; i >= 0; i--) {
-        if (l[i] < pm[i]) return true;
-        if (l[i] > pm[i]) return false;
+// The argument list of ONE zk_msm_batch_dev call: jobs in the order they were added, points back in that order.
+struct MsmJobs {
+    std::vector<const zk_bases*> tables;
+    std::vector<size_t> offs, lens; std::vector<const void*> scalars;
+    size_t size() const { return tables.size(); }
+    size_t add(const zk_bases* table, size_t off, const void* sc, size_t len) {
+        tables.push_back(table); offs.push_back(off); scalars.push_back(sc); lens.push_back(len);
+        return tables.size() - 1;
     }
-    return false;
-}
+    // a polynomial and, next to it, its copy shifted up to the degree bound (the same scalars from base `shift` on: they share a sort)
+    size_t add_with_shift(const zk_bases* table, size_t shift, const void* sc, size_t len) {
+        add(table, 0, sc, len);
+        return add(table, shift, sc, len) - 1;
+    }
+    std::vector<zk_g1_projective> run(zk_ctx* ctx, int* rc) {
+        std::vector<zk_g1_projective> outs(size());
+        std::vector<void*> outp(size());
+        for (size_t i = 0; i < size(); i++) outp[i] = &outs[i];
+        *rc = zk_msm_batch_dev(ctx, size(), tables.data(), offs.data(), scalars.data(), lens.data(), outp.data());
+        return outs;
+    }
+};
+
+// with zk_set_profiling(ctx, 1): host wall-clock laps of the phases land in the context's timers as "marlin.<phase>" (a lap
+// includes whatever device work the host waited for)
+struct Laps {
+    zk_ctx* ctx; bool on;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    explicit Laps(zk_ctx* c) : ctx(c), on(c->profiling) {}
+    void lap(const char* what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        auto& tm = ctx->timers[std::string("marlin.") + what];
+        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
+        tm.count += 1; t = now;
+    }
+};
+
+struct Term { HF c; Oracle o; };                // o = O_NONE: the constant term (LCTerm::One)
+using LinComb = std::vector<Term>;
 
 // Opens of O(1) values on the caller's transport, batched into ONE exchange: scalars and G1 points of this party's share lane
 // (AdditiveFieldShare / AdditiveGroupShare::open: the sum over parties).  LANES = 2 (SPDZ): frs[1] / g1s[1] are the MAC shares;
@@ -269,8 +306,8 @@ int open_small(ZkSharedNet& nt, const std::vector<HF> frs[2], const std::vector<
         std::vector<uint64_t> w(words);
         for (int p = 0; p < nt.parties(); p++) {
             memcpy(w.data(), all.data() + (size_t)p * words * 8, words * 8);
-            for (size_t i = 0; i < nf; i++) {
-                if (!fr_words_valid_abi(&w[4 * i])) ZK_FAIL(ctx, ZK_ERR_STATE, "collaborative prover: a party sent a non-canonical field element");
+            for (size_t i = 0; i < nf; i++) {      // what arrives from a peer: < r
+                if (!zk_fr_words_valid(&w[4 * i])) ZK_FAIL(ctx, ZK_ERR_STATE, "collaborative prover: a party sent a non-canonical field element");
                 zk_fr a;
                 memcpy(a.l, &w[4 * i], 32);
                 f[i] = f[i] + HF::from_abi(a);
@@ -305,551 +342,499 @@ int open_small(ZkSharedNet& nt, const std::vector<HF> frs[2], const std::vector<
     return ZK_OK;
 }
 
-bool label_shared(const char* l) {           // the witness-dependent oracles (mpc.py: Party.SHARED_POLYS); t, g_2, h_2 and the index are public
-    return !strcmp(l, "w") || !strcmp(l, "z_a") || !strcmp(l, "z_b") || !strcmp(l, "mask_poly") || !strcmp(l, "g_1") || !strcmp(l, "h_1");
-}
+// What the caller of a prover entry point hands over (lanes [0] = share / plain, [1] = MAC share under SPDZ)
+struct MarlinArgs {
+    const zk_marlin_index* ix;
+    const zk_bases *powers_g, *powers_gamma_g;
+    const void* const* z;
+    zk_rng* rng; int mask_on_device; bool shared;
+    const void *const *tx, *const *ty, *const *tz;
+    const zk_net_vtable* net;
+};
 
-// Marlin::prove, plain (shared = false, LANES = 1: zk_marlin_prove) or over this party's shares (zk_marlin_prove_shared[_spdz]):
-// MpcMarlin::prove, src/marlin.rs:56 / arkworks/marlin/src/lib.rs:152-319 with F = MpcField.  Every step of the rounds is linear
-// in the witness except z_A * z_B in round 2 (FieldShare::batch_mul over the 4|H| multiplication domain) and the zero test of the
-// outer sum-check (an open); commitments / evaluations / opening witnesses of witness-dependent oracles are computed on the
-// shares and opened (`publicize()`, lib.rs:171-228,296); public oracles enter a shared combination on the leader only (shift()).
-// LANES = 2: everything linear runs on the share lane and on the MAC lane, every open is MAC-checked; the MAC lane of this
-// party's fresh randomness is the share itself (from_add_shared with key 1).
+// One Marlin::prove in progress, plain (shared = false, LANES = 1: zk_marlin_prove) or over this party's shares
+// (zk_marlin_prove_shared[_spdz]): MpcMarlin::prove, src/marlin.rs:56 / arkworks/marlin/src/lib.rs:152-319 with F = MpcField.  Every
+// step of the rounds is linear in the witness except z_A * z_B in round 2 (FieldShare::batch_mul over the 4|H| multiplication
+// domain) and the zero test of the outer sum-check (an open); commitments / evaluations / opening witnesses of witness-dependent
+// oracles are computed on the shares and opened (`publicize()`, lib.rs:171-228,296); public oracles enter a shared combination on
+// the leader only (shift()).  LANES = 2: everything linear runs on the share lane and on the MAC lane, every open is MAC-checked;
+// the MAC lane of this party's fresh randomness is the share itself (from_add_shared with key 1).
 template <int LANES>
-int marlin_impl(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g, const zk_bases* powers_gamma_g, const void* const z_lanes[2],
-                zk_rng* zk_rng_, int mask_on_device, bool shared, const void* const tx[2], const void* const ty[2], const void* const tz[2],
-                const zk_net_vtable* net, uint8_t* proof_out, size_t cap, size_t* proof_len, uint64_t* bytes_sent) {
-    if (powers_g->group != 1 || powers_gamma_g->group != 1 || powers_gamma_g->n < 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: SRS tables");
-    if (cap < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer smaller than zk_marlin_proof_max_size()");
-    if (ix->num_constraints != ix->num_variables) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: NonSquareMatrix");
-    if (ix->num_instance == 0 || (ix->num_instance & (ix->num_instance - 1))) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: InvalidPublicInputLength");
-    // with zk_set_profiling(ctx, 1): host wall-clock laps of the phases land in the context's timers as "marlin.<phase>" (a lap
-    // includes whatever device work the host waited for)
-    struct Laps {
-        zk_ctx* ctx;
-        bool on;
-        std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-        explicit Laps(zk_ctx* c) : ctx(c), on(c->profiling) {}
-        void lap(const char* what) {
-            if (!on) return;
-            const auto now = std::chrono::steady_clock::now();
-            auto& tm = ctx->timers[std::string("marlin.") + what];
-            tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
-            tm.count += 1;
-            t = now;
-        }
-    } laps(ctx);
-    ZkSharedNet nt{ctx, net};
-    // divisibility / zero-sum checks whose verdict nothing waits for: the test is enqueued, the round's commitments go out behind
-    // it, and the verdict is read once the batch has synchronised the streams (a wait here left the device idle for the whole of
-    // the host's preparation of the batch: 0.1 - 0.15 ms per round of a small proof)
+struct Marlin : MarlinArgs {
+    zk_ctx* const ctx;
+    const size_t max_degree; const char* zb[2];   // of the SRS; the (shares of the) padded assignment
+    Laps laps; ZkSharedNet nt; const bool leader;
+    Prover PL[2]; Prover& P = PL[0];              // lane 0 also computes everything public
+    const Dom H, K, X, B;
+    const size_t n, ni, md, nwq;                  // |H|, |X|, the mask polynomial's degree (zk_bound = 1), coefficients of w
+    const Dom MUL;                                // the multiplication domain of round 2
+    // divisibility / zero-sum checks whose verdict nothing waits for: the test is enqueued, the round's commitments go out behind it, the verdict
+    // is read once the batch has synchronised the streams (a wait here left the device idle while the host prepared the batch: 0.1 - 0.15 ms per round)
     struct Pending { const uint32_t* verdict; const char* msg; };
     std::vector<Pending> pending;
-    auto check_later = [&](const void* v, size_t n, const char* msg) -> int {
-        const uint32_t* h = nullptr;
-        ZK_TRY(zk_fr_vec_is_zero_launch(ctx, v, n, (int)pending.size(), &h));
-        pending.push_back({h, msg});
-        return ZK_OK;
-    };
-    auto settle = [&]() -> int {
+    ZkEarlyMsm* early[N_PROVER] = {};             // MSMs started ahead of their round's batch (start_early), until commit_round collects them
+    zk_rng* fs = nullptr;                         // the transcript
+    zk_g1_projective gamma_pts[3];                // powers_of_gamma_g: what a hiding bound of 1 uses
+    // ---- what the steps hand on ----
+    std::vector<HF> pub;                          // seed_transcript: the public input, its leading 1 included
+    struct Blinds { std::vector<HF> plain, shifted; } rands[N_ORACLES];   // commit_round: the blinding polynomials (index oracles: none)
+    Comm comms[N_PROVER];                         // commit_round
+    char *xb[2], *wq[2], *mask[2], *tmp[2];       // round 1 -> 2: x and w as coefficients, the mask polynomial, |H| elements of scratch
+    HF alpha, eta[3], v_h_alpha;                  // round 1 / 2: challenges (eta: a, b, c), v_H(alpha)
+    HF beta, vv, gamma, xi;                       // round 2: challenge; round 3: v_H(alpha) v_H(beta), challenge; evaluate: challenge
+    std::vector<HF> evaluations;                  // evaluate: in the proof's (alphabetic) order
+    std::vector<LinComb> queries[2];              // evaluate: the combinations opened at beta / at gamma, in query-set order
+    Affine<G1Field> wit[2];                       // open_combinations: per query point the witness, and random_v if hiding
+    bool has_rv[2] = {false, false}; HF rvs[2];
+    Marlin(zk_ctx* c, const MarlinArgs& args)
+        : MarlinArgs(args), ctx(c), max_degree(powers_g->n - 1), zb{(const char*)z[0], LANES == 2 ? (const char*)z[1] : nullptr}, laps(c), nt{c, net},
+          leader(nt.leader()), PL{Prover{c, 0}, Prover{c, 1}}, H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * K.size - 3),
+          n(H.size), ni(ix->num_instance), md(3 * n + 2 - 3), nwq(n + 1 - X.size), MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1)) {
+        for (int l = 0; l < LANES; l++)
+            for (int i = 0; i < 12; i++) PL[l].polys[O_A_ROW + i] = Poly{(char*)ix->index_polys[i].ptr, ix->index_polys[i].n};
+    }
+    ~Marlin() {
+        for (ZkEarlyMsm* em : early) if (em) (void)zk_msm_early_finish(ctx, em, nullptr);     // an error path: let them drain
+        zk_rng_free(fs);
+    }
+    bool bounded(Oracle o) const { return ORACLES[o].bound != Bound::None; }
+    size_t bound(Oracle o) const { return (ORACLES[o].bound == Bound::H ? n : K.size) - 2; }
+    int lanes_rc() const { for (int l = 0; l < LANES; l++) if (PL[l].rc != ZK_OK) return PL[l].rc; return (int)ZK_OK; }
+    HF sample_outside(const Dom& d) { HF t = P.next_fr(fs); while (d.vanishing(t).is_zero()) t = P.next_fr(fs); return t; }
+    // sum_i c_i powers_of_gamma_g[i] on the context's helper threads (the blinding terms: ~1.2 ms of host scalar multiplications each,
+    // under the device batch); the caller joins them before it returns
+    ZkTask<zk_g1_projective> small_async(const std::vector<HF>& c) {
+        return zk_async(ctx, [ctx = ctx, pts = gamma_pts, c] { return small_msm_par(ctx, pts, c); });
+    }
+    int check_later(const void* v, size_t count, const char* msg) {
+        pending.push_back({nullptr, msg});                                       // (a failed launch ends the proof: nothing settles it)
+        return zk_fr_vec_is_zero_launch(ctx, v, count, (int)pending.size() - 1, &pending.back().verdict);
+    }
+    int settle() {
         const char* failed = nullptr;
-        for (auto& c : pending)
-            if (!failed && *c.verdict != 0) failed = c.msg;
+        for (auto& c : pending) if (!failed && *c.verdict != 0) failed = c.msg;
         pending.clear();
         if (failed) ZK_FAIL(ctx, ZK_ERR_STATE, failed);
         return ZK_OK;
-    };
-    const bool leader = nt.leader();
-    Prover PL[2] = {Prover{ctx, ix, powers_g, powers_gamma_g, powers_g->n - 1, zk_rng_}, Prover{ctx, ix, powers_g, powers_gamma_g, powers_g->n - 1, zk_rng_}};
-    PL[1].lane = 1;
-    Prover& P = PL[0];                            // lane 0 also carries everything public: blinds, commitments, bounds, public oracles
-    auto lanes_rc = [&]() { for (int l = 0; l < LANES; l++) if (PL[l].rc != ZK_OK) return PL[l].rc; return (int)ZK_OK; };
-    const Dom H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * Dom(ix->num_non_zero).size - 3);
-    const size_t n = H.size, ni = ix->num_instance;
-    {   // AHPForR1CS::max_degree (ahp/mod.rs:75-97)
-        const size_t need = std::max(std::max(2 * n - 1, 3 * n - 1), std::max(n, 3 * K.size - 3));
-        if (P.max_degree < need) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: IndexTooLarge for this SRS");
     }
-    if (B.size < 4 * K.size - 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: |K| < 4 is not supported by this entry point");
-    P.bounds["g_1"] = n - 2;
-    P.bounds["g_2"] = K.size - 2;
-    const char* zb[2] = {(const char*)z_lanes[0], LANES == 2 ? (const char*)z_lanes[1] : nullptr};
-    for (int l = 0; l < LANES; l++)
-        for (int i = 0; i < 12; i++) PL[l].polys[INDEX_LABELS[i]] = Poly{(char*)ix->index_polys[i].ptr, ix->index_polys[i].n};
-    for (int i = 0; i < 12; i++) P.rands[INDEX_LABELS[i]] = {};
-
-    zk_g1_projective gamma_pts[3];
-    {
-        zk_g1_affine a[3];
-        ZK_TRY(zk_bases_download_g1(ctx, powers_gamma_g, 0, 3, a));
-        for (int i = 0; i < 3; i++) zk_g1_from_affine(&a[i], &gamma_pts[i]);
+    // The sum over the parties of a device vector of shares (LANES = 2: MAC-checked), into scratch of its own
+    int open_dev(const char* const v[2], size_t count, const std::string& name, char** out) {
+        char* o = P.dev(name + "_open", count); char* dx = P.dev(name + "_dx", count);
+        ZK_TRY(P.rc);
+        if (LANES == 2) ZK_TRY(zk_shared_spdz_open_vec(nt, v[0], v[1], count, o, dx));
+        else ZK_TRY(nt.open_vec(v[0], count, o));
+        *out = o;
+        return ZK_OK;
     }
-
-    // ---- transcript seed: PROTOCOL_NAME | index_vk | public_input (lib.rs:161-164).  Over shares the instance part of the
-    // assignment is shared like the rest (from_public: the leader holds it) and opened here ----
-    std::vector<HF> pub(ni - 1);
-    {
-        std::vector<zk_fr> tmp(ni);
-        if (shared && ni == 1) {
-            // no public input beside the constant 1: nothing to open
-        } else if (shared) {
-            char* po = P.dev("pub_open", ni); char* pd = P.dev("pub_dx", ni);
-            ZK_TRY(P.rc);
-            if (LANES == 2) ZK_TRY(zk_shared_spdz_open_vec(nt, zb[0], zb[1], ni, po, pd));
-            else ZK_TRY(nt.open_vec(zb[0], ni, po));
-            ZK_TRY(zk_memcpy_d2h(ctx, tmp.data(), po, ni * 32));
-        } else {
-            ZK_TRY(zk_memcpy_d2h(ctx, tmp.data(), zb[0], ni * 32));
-        }
-        for (size_t i = 1; i < ni; i++) pub[i - 1] = HF::from_abi(tmp[i]);
-    }
-    std::vector<uint8_t> seed;
-    const char* name = "MARLIN-2019";
-    seed.insert(seed.end(), name, name + 11);
-    seed.insert(seed.end(), ix->ivk_bytes, ix->ivk_bytes + ix->ivk_len);
-    for (auto& v : pub) v.bytes(seed);
-    zk_rng* fs = nullptr;
-    ZK_TRY(zk_fsrng_new(seed.data(), seed.size(), &fs));
-    struct FsGuard { zk_rng* r; ~FsGuard() { zk_rng_free(r); } } guard{fs};
-    auto sample_outside = [&](const Dom& d) { HF t = P.next_fr(fs); while (d.vanishing(t).is_zero()) t = P.next_fr(fs); return t; };
-
-    // Oracles of a round that exist before the round's last polynomial does -- the mask polynomial (round 1), t (round 2), g_2
-    // (round 3); none of them hiding, so no draw of the prover's rng depends on where their commitment is computed -- have their MSMs
-    // started as soon as their coefficients are on the device (msm_batch.hip: zk_msm_early_begin); the context stream goes on with
-    // the round's polynomial arithmetic, commit_round collects them.  ZK_MARLIN_EARLY=0 keeps every job in the round's batch (A/B).
-    struct Early {
-        zk_ctx* ctx;
-        std::map<std::string, ZkEarlyMsm*> jobs;
-        ~Early() { for (auto& kv : jobs) if (kv.second) (void)zk_msm_early_finish(ctx, kv.second, nullptr); }     // an error path: let them drain
-    } early{ctx, {}};
-    static const bool early_on = !(getenv("ZK_MARLIN_EARLY") && atoi(getenv("ZK_MARLIN_EARLY")) == 0);
-    auto start_early = [&](const char* l) -> int {
+    // Oracles of a round that exist before the round's last polynomial does (ORACLES: the mask polynomial, t, g_2; none of them
+    // hiding, so no draw of the prover's rng depends on where their commitment is computed) have their MSMs started as soon as their
+    // coefficients are on the device (msm_batch.hip: zk_msm_early_begin); the context stream goes on with the round's polynomial
+    // arithmetic, commit_round collects them.  ZK_MARLIN_EARLY=0 keeps every job in the round's batch (A/B).
+    int start_early(Oracle o) {
+        static const bool early_on = !(getenv("ZK_MARLIN_EARLY") && atoi(getenv("ZK_MARLIN_EARLY")) == 0);
         // from |H| = 2^18 up only: measured on one box, alternating (profiles/r6_marlin_early_ab.jsonl) -- 2^20 65.0 / 64.7 -> 63.9 / 64.0 ms,
         // 2^18 21.8 -> 21.6; below that a round is a chain of latencies and the early job, which runs alone instead of in the round's
         // group launches (its own one-block sort, accumulate launch, reduce chain and host half), makes the proof LONGER:
         // 2^10 3.5 -> 4.2 ms, 2^12 4.3 -> 5.4, 2^14 6.1 -> 7.0, 2^16 9.5 -> 10.2
         if (!early_on || H.size < ((size_t)1 << 18)) return ZK_OK;
-        const Poly& p = P.polys[l];
-        const bool bounded = P.bounds.count(l) != 0;
+        if (ORACLES[o].early == EarlyMsm::No || (ORACLES[o].early == EarlyMsm::Plain && shared)) return ZK_OK;
+        const Poly& p = P.polys[o];
         if (!p.n) return ZK_OK;
-        if (bounded && p.n - 1 > P.bounds[l]) return ZK_OK;                      // (commit_round reports it)
-        const size_t offs[2] = {0, bounded ? P.max_degree - P.bounds[l] : 0};
-        ZkEarlyMsm* em = nullptr;
-        ZK_TRY(zk_msm_early_begin(ctx, bounded ? 2 : 1, P.pg, offs, p.p, p.n, &em));
-        early.jobs[l] = em;
-        return ZK_OK;
-    };
-
+        if (bounded(o) && p.n - 1 > bound(o)) return ZK_OK;                      // (commit_round reports it)
+        const size_t offs[2] = {0, bounded(o) ? max_degree - bound(o) : 0};
+        return zk_msm_early_begin(ctx, bounded(o) ? 2 : 1, powers_g, offs, p.p, p.n, &early[o]);
+    }
     // MarlinKZG10::commit for one round (marlin_pc/mod.rs:172-243): blinding polynomials in the reference's rng order, all MSMs
-    // of the round (every lane) as one pipelined batch; shared oracles' commitments opened; then the round's bytes into the transcript
-    auto commit_round = [&](std::initializer_list<const char*> labels) -> int {
-        std::vector<const zk_bases*> jb; std::vector<size_t> joff, jlen; std::vector<const void*> jsc;
-        struct Slot { std::string label; int which, lane; };
-        std::vector<Slot> slot;                                                  // which: 0 = comm / 1 = shifted
-        std::map<std::string, zk_g1_projective> acc[2][2];                       // [lane][which]
-        // the blinding terms (three host scalar multiplications each, ~1.2 ms) run on host threads under the device batch
-        std::vector<std::pair<std::pair<int, std::string>, ZkTask<zk_g1_projective>>> blinds;
-        auto blind_async = [&](int which, const char* l, const std::vector<HF>& c) {
-            blinds.push_back({{which, l}, zk_async(ctx, [ctx, &gamma_pts, c] { return small_msm_par(ctx, gamma_pts, c); })});
-        };
-        for (const char* l : labels) {
-            const bool hiding = !strcmp(l, "w") || !strcmp(l, "z_a") || !strcmp(l, "z_b") || !strcmp(l, "g_1");
-            const bool bounded = P.bounds.count(l) != 0;
-            std::vector<HF> blind, sblind;
-            if (hiding) for (int i = 0; i < 3; i++) blind.push_back(P.next_fr(P.rng));
-            if (hiding && bounded) for (int i = 0; i < 3; i++) sblind.push_back(P.next_fr(P.rng));
-            P.rands[l] = {blind, sblind};
+    // of the round (every lane) as one pipelined batch; shared oracles' commitments opened; the round's bytes into the transcript;
+    // then the verdicts of the round's pending checks
+    int commit_round(int round) {
+        const std::vector<Oracle> os = round_oracles(round);
+        MsmJobs jobs;
+        struct Acc { zk_g1_projective pt; bool has = false; } acc[2][2][N_PROVER];   // [lane][0 = comm / 1 = shifted]
+        std::vector<Acc*> dest;                                                  // where the batch's points go, in job order
+        ZkTask<zk_g1_projective> blind[2][N_PROVER];                             // [comm / shifted]: the blinding terms, under the device batch
+        for (Oracle o : os) {
+            const OracleInfo& oi = ORACLES[o];
+            Blinds& r = rands[o];
+            if (oi.hiding) for (int i = 0; i < 3; i++) r.plain.push_back(P.next_fr(rng));
+            if (oi.hiding && bounded(o)) for (int i = 0; i < 3; i++) r.shifted.push_back(P.next_fr(rng));
             for (int lane = 0; lane < LANES; lane++) {
-                if (lane == 1 && !label_shared(l)) continue;                     // public oracles are the same on every lane: committed once
-                if (lane == 0 && early.jobs.count(l)) continue;                  // started early: collected below
-                const Poly& p = PL[lane].polys[l];
-                jb.push_back(P.pg); joff.push_back(0); jsc.push_back(p.p); jlen.push_back(p.n); slot.push_back({l, 0, lane});
-                if (bounded) {
-                    if (p.n - 1 > P.bounds[l]) { ctx->last_error = std::string("zk_marlin_prove: ") + l + " exceeds its degree bound"; return ZK_ERR_STATE; }
-                    jb.push_back(P.pg); joff.push_back(P.max_degree - P.bounds[l]); jsc.push_back(p.p); jlen.push_back(p.n); slot.push_back({l, 1, lane});
-                }
+                if (lane == 1 && !oi.shared) continue;                           // public oracles are the same on every lane: committed once
+                if (lane == 0 && early[o]) continue;                             // started early: collected below
+                const Poly& p = PL[lane].polys[o];
+                dest.push_back(&acc[lane][0][o]);
+                if (!bounded(o)) { jobs.add(powers_g, 0, p.p, p.n); continue; }
+                if (p.n - 1 > bound(o)) { ctx->last_error = std::string("zk_marlin_prove: ") + oi.label + " exceeds its degree bound"; return ZK_ERR_STATE; }
+                jobs.add_with_shift(powers_g, max_degree - bound(o), p.p, p.n);
+                dest.push_back(&acc[lane][1][o]);
             }
-            if (hiding) blind_async(0, l, blind);
-            if (hiding && bounded) blind_async(1, l, sblind);
+            if (oi.hiding) blind[0][o] = small_async(r.plain);
+            if (oi.hiding && bounded(o)) blind[1][o] = small_async(r.shifted);
         }
         ZK_TRY(lanes_rc());
-        std::vector<zk_g1_projective> outs(jb.size());
-        std::vector<void*> outp(jb.size());
-        for (size_t i = 0; i < jb.size(); i++) outp[i] = &outs[i];
         laps.lap("commit.prep");
-        int brc = zk_msm_batch_dev(ctx, jb.size(), jb.data(), joff.data(), jsc.data(), jlen.data(), outp.data());
-        for (const char* l : labels) {                                           // the jobs that were started early
-            auto it = early.jobs.find(l);
-            if (it == early.jobs.end()) continue;
-            zk_g1_projective eo[2];
-            void* eop[2] = {&eo[0], &eo[1]};
-            ZkEarlyMsm* em = it->second;
-            early.jobs.erase(it);
+        int brc = ZK_OK;
+        const std::vector<zk_g1_projective> outs = jobs.run(ctx, &brc);
+        for (Oracle o : os) {                                                    // the jobs that were started early
+            if (!early[o]) continue;
+            zk_g1_projective eo[2]; void* eop[2] = {&eo[0], &eo[1]};
+            ZkEarlyMsm* em = early[o]; early[o] = nullptr;                      // (finish deletes the handle)
             const int erc = zk_msm_early_finish(ctx, em, eop);
             if (brc == ZK_OK) brc = erc;
-            acc[0][0][l] = eo[0];
-            if (P.bounds.count(l)) acc[0][1][l] = eo[1];
+            acc[0][0][o] = {eo[0], true};
+            if (bounded(o)) acc[0][1][o] = {eo[1], true};
         }
         laps.lap("commit.msm");
-        std::vector<std::pair<std::pair<int, std::string>, zk_g1_projective>> bl;
-        for (auto& b : blinds) bl.push_back({b.first, b.second.get()});          // joined before any return
+        zk_g1_projective bl[2][N_PROVER]; bool blinded[2][N_PROVER] = {};
+        for (Oracle o : os)                                                      // joined before any return
+            for (int w = 0; w < 2; w++) if ((blinded[w][o] = blind[w][o].valid())) bl[w][o] = blind[w][o].get();
         laps.lap("commit.blinds");
         ZK_TRY(brc);
-        for (size_t i = 0; i < jb.size(); i++) acc[slot[i].lane][slot[i].which][slot[i].label] = outs[i];
-        for (auto& b : bl)                                                       // the MAC lane of this party's fresh blinds is the share itself
-            for (int lane = 0; lane < LANES; lane++) {
-                auto it = acc[lane][b.first.first].find(b.first.second);
-                if (it == acc[lane][b.first.first].end()) continue;
-                zk_g1_projective t;
-                zk_g1_add(&it->second, &b.second, &t);
-                it->second = t;
-            }
+        for (size_t i = 0; i < outs.size(); i++) *dest[i] = {outs[i], true};
+        for (Oracle o : os)                                                      // the MAC lane of this party's fresh blinds is the share itself
+            for (int w = 0; w < 2; w++)
+                for (int lane = 0; lane < LANES && blinded[w][o]; lane++) {
+                    Acc& c = acc[lane][w][o];
+                    if (!c.has) continue;
+                    zk_g1_projective t;
+                    zk_g1_add(&c.pt, &bl[w][o], &t);
+                    c.pt = t;
+                }
         if (shared) {                                                            // first_comms.publicize() (lib.rs:180,205,228)
             std::vector<HF> nofr[2], ofr;
             std::vector<zk_g1_projective> pts[2], opened;
-            std::vector<std::pair<std::string, int>> what;
-            for (const char* l : labels) {
-                if (!label_shared(l)) continue;
+            std::vector<Acc*> what;
+            for (Oracle o : os) {
+                if (!ORACLES[o].shared) continue;
                 for (int which = 0; which < 2; which++) {
-                    if (!acc[0][which].count(l)) continue;
-                    for (int lane = 0; lane < LANES; lane++) pts[lane].push_back(acc[lane][which][l]);
-                    what.push_back({l, which});
+                    if (!acc[0][which][o].has) continue;
+                    for (int lane = 0; lane < LANES; lane++) pts[lane].push_back(acc[lane][which][o].pt);
+                    what.push_back(&acc[0][which][o]);
                 }
             }
             ZK_TRY(open_small<LANES>(nt, nofr, pts, ofr, opened));
-            for (size_t i = 0; i < what.size(); i++) acc[0][what[i].second][what[i].first] = opened[i];
+            for (size_t i = 0; i < what.size(); i++) what[i]->pt = opened[i];
         }
         std::vector<uint8_t> bytes;
         std::vector<zk_g1_projective> all;
-        for (const char* l : labels) {
-            all.push_back(acc[0][0][l]);
-            if (acc[0][1].count(l)) all.push_back(acc[0][1][l]);
+        for (Oracle o : os) {
+            all.push_back(acc[0][0][o].pt);
+            if (acc[0][1][o].has) all.push_back(acc[0][1][o].pt);
         }
         const std::vector<Affine<G1Field>> aff = batch_to_aff(all);
         size_t ai = 0;
-        for (const char* l : labels) {
-            Comm c;
+        for (Oracle o : os) {
+            Comm& c = comms[o];
             c.c = aff[ai++];
-            c.has_shift = acc[0][1].count(l) != 0;
+            c.has_shift = acc[0][1][o].has;
             c.s = c.has_shift ? aff[ai++] : aff_inf<G1Field>();
-            P.comms[l] = c;
             comm_tobytes(c, bytes);
         }
-        return zk_fsrng_absorb(fs, bytes.data(), bytes.size());                  // to_bytes![comms, EmptyMessage]
-    };
+        ZK_TRY(zk_fsrng_absorb(fs, bytes.data(), bytes.size()));                 // to_bytes![comms, EmptyMessage]
+        return settle();
+    }
 
-    laps.lap("setup");
-    // =========================== round 1 (prover.rs:216-404), every lane ===========================
-    const size_t md = 3 * n + 2 - 3;                                             // mask polynomial degree, zk_bound = 1
-    char* rnd = P.dev("rnd", 3 + md + 1);                                        // this party's (share of the) prover randomness: both lanes read it
-    ZK_TRY(P.rc);
-    {
+    // The transcript seed: PROTOCOL_NAME | index_vk | public_input (lib.rs:161-164).  Over shares the instance part of the
+    // assignment is shared like the rest (from_public: the leader holds it) and opened here.  Out: gamma_pts, pub, fs
+    int seed_transcript() {
+        zk_g1_affine g[3];
+        ZK_TRY(zk_bases_download_g1(ctx, powers_gamma_g, 0, 3, g));
+        for (int i = 0; i < 3; i++) zk_g1_from_affine(&g[i], &gamma_pts[i]);
+        std::vector<zk_fr> x(ni);
+        const char* from = zb[0];
+        if (shared && ni > 1) ZK_TRY(open_dev(zb, ni, "pub", (char**)&from));   // (ni = 1: no public input beside the constant 1, nothing to open)
+        if (!shared || ni > 1) ZK_TRY(zk_memcpy_d2h(ctx, x.data(), from, ni * 32));
+        pub.assign(ni, HF::one());
+        for (size_t i = 1; i < ni; i++) pub[i] = HF::from_abi(x[i]);
+        std::vector<uint8_t> seed;
+        const char* name = "MARLIN-2019";
+        seed.insert(seed.end(), name, name + 11);
+        seed.insert(seed.end(), ix->ivk_bytes, ix->ivk_bytes + ix->ivk_len);
+        for (size_t i = 1; i < ni; i++) pub[i].bytes(seed);
+        ZK_TRY(zk_fsrng_new(seed.data(), seed.size(), &fs));
+        laps.lap("setup");
+        return ZK_OK;
+    }
+
+    // Round 1 (prover.rs:216-404), every lane.  In: the assignment, the prover's rng.  Out: w, z_a, z_b, mask_poly committed; xb, wq, mask, tmp; alpha, eta
+    int round1() {
+        char* rnd = P.dev("rnd", 3 + md + 1);                                    // this party's (share of the) prover randomness: both lanes read it
+        ZK_TRY(P.rc);
         const size_t host_n = mask_on_device ? 3 : 3 + md + 1;
         std::vector<zk_fr> h(host_n);
-        ZK_TRY(zk_rng_fill_fr(P.rng, h.data(), host_n));
+        ZK_TRY(zk_rng_fill_fr(rng, h.data(), host_n));
         ZK_TRY(zk_memcpy_h2d(ctx, rnd, h.data(), host_n * 32));
         if (mask_on_device) {
             uint8_t key[32];
-            ZK_TRY(zk_rng_fill_bytes(P.rng, key, 32));
+            ZK_TRY(zk_rng_fill_bytes(rng, key, 32));
             ZK_TRY(zk_fr_random_dev(ctx, key, 0, rnd + 96, md + 1));
         }
-    }
-    const size_t nwq = n + 1 - X.size;
-    char *z_a[2], *z_b[2], *xb[2], *wq[2], *mask[2], *tmp[2];
-    for (int l = 0; l < LANES; l++) {                                            // the mask polynomial first: its commitment (the round's longest job) starts now
-        Prover& Q = PL[l];
-        mask[l] = Q.dev("mask", md + 1);
-        char* mq = Q.dev("mask_q", md + 1); char* mr = Q.dev("mask_r", n);
-        Q.d2d(mask[l], rnd + 96, md + 1);
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, mask[l], md + 1, H.log, mq, mr));
-        Q.op(ZK_OP_SUB, mask[l], mr, mask[l], 1);                                // the sum over H becomes zero
-        Q.polys["mask_poly"] = Poly{mask[l], md + 1};
-        ZK_TRY(Q.rc);
-    }
-    if (!shared) ZK_TRY(start_early("mask_poly"));                               // (over shares it is a shared oracle: every lane's job stays in the batch)
-    for (int l = 0; l < LANES; l++) {
-        Prover& Q = PL[l];
-        z_a[l] = Q.dev("z_a", n); z_b[l] = Q.dev("z_b", n);
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs, 0, zb[l], z_a[l], n));
-        ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs, 1, zb[l], z_b[l], n));
-        xb[l] = Q.dev("x_poly", X.size);
-        Q.d2d(xb[l], zb[l], X.size);
-        Q.ntt(xb[l], X, 1);
-        const Poly x_poly{xb[l], X.size};
-        char* x_evals = Q.fft(H, x_poly, "x_evals");
-        char* w_evals = Q.dev("w_evals", n);
-        tmp[l] = Q.dev("tmp_h", n);
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_fr_gather_dev(ctx, zb[l], ix->w_idx, n, w_evals));
-        ZK_TRY(zk_fr_gather_dev(ctx, x_evals, ix->x_idx, n, tmp[l]));
-        Q.op(ZK_OP_SUB, w_evals, tmp[l], w_evals, n);
-        char* za = Q.dev("za_c", n); char* zbb = Q.dev("zb_c", n);
-        Q.d2d(za, z_a[l], n); Q.d2d(zbb, z_b[l], n);
-        Q.ntt_batch({w_evals, za, zbb}, H, 1);                                   // the three interpolations of the round: one launch per pass
-        const Poly w_h = Q.blind(w_evals, n, rnd, "w_h");
-        wq[l] = Q.dev("w_poly", nwq);
-        char* wr = Q.dev("w_rem", X.size);
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, w_h.p, n + 1, X.log, wq[l], wr));
-        // (over shares the remainder is a share of zero: the reference's assert!(remainder.is_zero()) cannot be evaluated locally)
-        if (!shared) ZK_TRY(check_later(wr, X.size, "zk_marlin_prove: w polynomial is not divisible by v_X"));
-        Q.polys["w"] = Poly{wq[l], nwq};
-        Q.polys["z_a"] = Q.blind(za, n, rnd + 32, "z_a_poly");
-        Q.polys["z_b"] = Q.blind(zbb, n, rnd + 64, "z_b_poly");
-        ZK_TRY(Q.rc);
-    }
-    laps.lap("polys");
-    ZK_TRY(commit_round({"w", "z_a", "z_b", "mask_poly"}));
-    ZK_TRY(settle());
-    laps.lap("commit");
-    const HF alpha = sample_outside(H), eta_a = P.next_fr(fs), eta_b = P.next_fr(fs), eta_c = P.next_fr(fs);
-
-    laps.lap("round1");
-    // =========================== round 2 (prover.rs:438-565) ===========================
-    // public: r(alpha, X) on H, t = sum_M eta_M M^T r, their evaluations over the multiplication domain (computed once)
-    const HF v_h_alpha = H.vanishing(alpha), one = HF::one();
-    char* elems = P.dev("h_elems", n);
-    char* ra = P.dev("r_alpha", n);
-    ZK_TRY(P.rc);
-    { zk_fr g = H.gen.abi(), o = one.abi(), a = alpha.abi();
-      ZK_TRY(zk_fr_powers_dev(ctx, &g, &o, n, elems));
-      ZK_TRY(zk_fr_powers_dev(ctx, &o, &a, n, ra)); }                            // the constant vector alpha
-    P.op(ZK_OP_SUB, ra, elems, ra, n);
-    ZK_TRY(P.rc);
-    ZK_TRY(zk_fr_batch_inverse_dev(ctx, ra, n));
-    P.scale(ra, v_h_alpha, ra, n);                                               // r(alpha, X) on H (ahp/mod.rs:352-360)
-    char* t_ev = P.dev("t_ev", n);
-    const HF etas[3] = {eta_a, eta_b, eta_c};
-    for (int which = 0; which < 3; which++) {                                    // calculate_t on the transposed matrices
-        ZK_TRY(P.rc);
-        ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs_t, which, ra, which == 0 ? t_ev : tmp[0], n));
-        if (which == 0) P.scale(t_ev, etas[0], t_ev, n);
-        else { P.scale(tmp[0], etas[which], tmp[0], n); P.op(ZK_OP_ADD, t_ev, tmp[0], t_ev, n); }
-    }
-    P.ntt_batch({t_ev, ra}, H, 1);
-    for (int l = 0; l < LANES; l++) PL[l].polys["t"] = Poly{t_ev, n};
-    ZK_TRY(P.rc);
-    ZK_TRY(start_early("t"));                                                    // public: the product of the two witness vectors and h_1 are still to come
-    const Poly r_alpha_poly{ra, n};
-    const Dom MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1));
-    char* e_rp = P.padded(MUL, r_alpha_poly, "e_r"); char* e_tp = P.padded(MUL, P.polys["t"], "e_t");
-    P.ntt_batch({e_rp, e_tp}, MUL, 0);
-    char *e_a[2], *e_b[2], *e_s[2], *e_z[2];
-    for (int l = 0; l < LANES; l++) {
-        Prover& Q = PL[l];
-        char* zp = Q.dev("z_poly", n + 1);                                       // z = w v_X + x
-        Q.zero(zp, n + 1);
-        Q.d2d(zp + 32 * X.size, wq[l], nwq);
-        Q.op(ZK_OP_SUB, zp, wq[l], zp, nwq);
-        Q.op(ZK_OP_ADD, zp, xb[l], zp, X.size);
-        const Poly z_poly{zp, n + 1};
-        e_a[l] = Q.padded(MUL, Q.polys["z_a"], "e_a"); e_b[l] = Q.padded(MUL, Q.polys["z_b"], "e_b");
-        e_s[l] = Q.dev("e_s", MUL.size);
-        e_z[l] = Q.padded(MUL, z_poly, "e_z");
-        Q.ntt_batch({e_a[l], e_b[l], e_z[l]}, MUL, 0);
-        ZK_TRY(Q.rc);
-    }
-    // z_a z_b: the one product of two witness vectors (`DensePolynomial::mul` on MpcField = FieldShare::batch_mul)
-    if (!shared) P.op(ZK_OP_MUL, e_a[0], e_b[0], e_s[0], MUL.size);
-    else ZK_TRY(zk_shared_beaver_mul(nt, LANES, (const void* const*)e_a, (const void* const*)e_b, (void* const*)e_s, MUL.size, tx, ty, tz, "mp_bv"));
-    char *hq[2], *hr[2];
-    for (int l = 0; l < LANES; l++) {
-        Prover& Q = PL[l];
-        // r(alpha, X) (eta_c z_a z_b + eta_a z_a + eta_b z_b) - z t on the multiplication domain (public * own value: local): one pass
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_fr_outer_q1_launch(ctx, e_s[l], e_a[l], e_b[l], e_z[l], e_rp, e_tp, eta_a.v.l, eta_b.v.l, eta_c.v.l, e_s[l], MUL.size));
-        Q.ntt(e_s[l], MUL, 1);                                                   // q_1 (prover.rs:517-541)
-        Q.op(ZK_OP_ADD, e_s[l], mask[l], e_s[l], md + 1);
-        hq[l] = Q.dev("h1_q", MUL.size - n); hr[l] = Q.dev("h1_r", n);
-        ZK_TRY(Q.rc);
-        ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, e_s[l], MUL.size, H.log, hq[l], hr[l]));
-    }
-    {   // the outer sum-check's zero test (prover.rs:547-550): over shares the constant term is opened
-        bool zero_sum = true;
-        if (!shared) ZK_TRY(check_later(hr[0], 1, "zk_marlin_prove: outer sum-check: the sum over H is not zero (unsatisfied constraint system)"));
-        else {
-            char* zo = P.dev("zero_open", 1); char* zd = P.dev("zero_dx", 1);
-            ZK_TRY(P.rc);
-            if (LANES == 2) ZK_TRY(zk_shared_spdz_open_vec(nt, hr[0], hr[1], 1, zo, zd));
-            else ZK_TRY(nt.open_vec(hr[0], 1, zo));
-            zero_sum = P.is_zero(zo, 1);
+        for (int l = 0; l < LANES; l++) {                                        // the mask polynomial first: its commitment (the round's longest job) starts now
+            Prover& Q = PL[l];
+            mask[l] = Q.dev("mask", md + 1);
+            char* mq = Q.dev("mask_q", md + 1); char* mr = Q.dev("mask_r", n);
+            Q.d2d(mask[l], rnd + 96, md + 1);
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, mask[l], md + 1, H.log, mq, mr));
+            Q.op(ZK_OP_SUB, mask[l], mr, mask[l], 1);                            // the sum over H becomes zero
+            Q.polys[O_MASK_POLY] = Poly{mask[l], md + 1};
+            ZK_TRY(Q.rc);
         }
+        ZK_TRY(start_early(O_MASK_POLY));
+        for (int l = 0; l < LANES; l++) {
+            Prover& Q = PL[l];
+            char* z_a = Q.dev("z_a", n); char* z_b = Q.dev("z_b", n);
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs, 0, zb[l], z_a, n));
+            ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs, 1, zb[l], z_b, n));
+            xb[l] = Q.dev("x_poly", X.size);
+            Q.d2d(xb[l], zb[l], X.size);
+            Q.ntt(xb[l], X, 1);
+            char* x_evals = Q.fft(H, Poly{xb[l], X.size}, "x_evals");
+            char* w_evals = Q.dev("w_evals", n);
+            tmp[l] = Q.dev("tmp_h", n);
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_fr_gather_dev(ctx, zb[l], ix->w_idx, n, w_evals));
+            ZK_TRY(zk_fr_gather_dev(ctx, x_evals, ix->x_idx, n, tmp[l]));
+            Q.op(ZK_OP_SUB, w_evals, tmp[l], w_evals, n);
+            char* za = Q.dev("za_c", n); char* zbb = Q.dev("zb_c", n);
+            Q.d2d(za, z_a, n); Q.d2d(zbb, z_b, n);
+            Q.ntt_batch({w_evals, za, zbb}, H, 1);                               // the three interpolations of the round: one launch per pass
+            const Poly w_h = Q.blind(w_evals, n, rnd, "w_h");
+            wq[l] = Q.dev("w_poly", nwq);
+            char* wr = Q.dev("w_rem", X.size);
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, w_h.p, n + 1, X.log, wq[l], wr));
+            // (over shares the remainder is a share of zero: the reference's assert!(remainder.is_zero()) cannot be evaluated locally)
+            if (!shared) ZK_TRY(check_later(wr, X.size, "zk_marlin_prove: w polynomial is not divisible by v_X"));
+            Q.polys[O_W] = Poly{wq[l], nwq};
+            Q.polys[O_Z_A] = Q.blind(za, n, rnd + 32, "z_a_poly");
+            Q.polys[O_Z_B] = Q.blind(zbb, n, rnd + 64, "z_b_poly");
+            ZK_TRY(Q.rc);
+        }
+        laps.lap("polys");
+        ZK_TRY(commit_round(1));
+        laps.lap("commit");
+        alpha = sample_outside(H);
+        for (HF& e : eta) e = P.next_fr(fs);
+        laps.lap("round1");
+        return ZK_OK;
+    }
+
+    // Round 2 (prover.rs:438-565).  In: alpha, eta; z_a, z_b, w (wq), x (xb), mask; tmp.  Out: t, g_1, h_1 committed; v_h_alpha; beta
+    int round2() {
+        // public: r(alpha, X) on H, t = sum_M eta_M M^T r, their evaluations over the multiplication domain (computed once)
+        const HF one = HF::one();
+        v_h_alpha = H.vanishing(alpha);
+        char* elems = P.dev("h_elems", n);
+        char* ra = P.dev("r_alpha", n);
         ZK_TRY(P.rc);
-        if (!zero_sum) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_prove: outer sum-check: the sum over H is not zero (unsatisfied constraint system)");
+        { zk_fr g = H.gen.abi(), o = one.abi(), al = alpha.abi();
+          ZK_TRY(zk_fr_powers_dev(ctx, &g, &o, n, elems));
+          ZK_TRY(zk_fr_powers_dev(ctx, &o, &al, n, ra)); }                       // the constant vector alpha
+        P.op(ZK_OP_SUB, ra, elems, ra, n);
+        ZK_TRY(P.rc);
+        ZK_TRY(zk_fr_batch_inverse_dev(ctx, ra, n));
+        P.scale(ra, v_h_alpha, ra, n);                                           // r(alpha, X) on H (ahp/mod.rs:352-360)
+        char* t_ev = P.dev("t_ev", n);
+        for (int which = 0; which < 3; which++) {                                // calculate_t on the transposed matrices
+            ZK_TRY(P.rc);
+            ZK_TRY(zk_r1cs_matvec_dev(ctx, ix->r1cs_t, which, ra, which == 0 ? t_ev : tmp[0], n));
+            if (which == 0) P.scale(t_ev, eta[0], t_ev, n);
+            else { P.scale(tmp[0], eta[which], tmp[0], n); P.op(ZK_OP_ADD, t_ev, tmp[0], t_ev, n); }
+        }
+        P.ntt_batch({t_ev, ra}, H, 1);
+        for (int l = 0; l < LANES; l++) PL[l].polys[O_T] = Poly{t_ev, n};
+        ZK_TRY(P.rc);
+        ZK_TRY(start_early(O_T));                                                // public: the product of the two witness vectors and h_1 are still to come
+        char* e_rp = P.padded(MUL, Poly{ra, n}, "e_r"); char* e_tp = P.padded(MUL, P.polys[O_T], "e_t");
+        P.ntt_batch({e_rp, e_tp}, MUL, 0);
+        char *e_a[2], *e_b[2], *e_s[2], *e_z[2];
+        for (int l = 0; l < LANES; l++) {
+            Prover& Q = PL[l];
+            char* zp = Q.dev("z_poly", n + 1);                                   // z = w v_X + x
+            Q.zero(zp, n + 1);
+            Q.d2d(zp + 32 * X.size, wq[l], nwq);
+            Q.op(ZK_OP_SUB, zp, wq[l], zp, nwq);
+            Q.op(ZK_OP_ADD, zp, xb[l], zp, X.size);
+            e_a[l] = Q.padded(MUL, Q.polys[O_Z_A], "e_a"); e_b[l] = Q.padded(MUL, Q.polys[O_Z_B], "e_b");
+            e_s[l] = Q.dev("e_s", MUL.size);
+            e_z[l] = Q.padded(MUL, Poly{zp, n + 1}, "e_z");
+            Q.ntt_batch({e_a[l], e_b[l], e_z[l]}, MUL, 0);
+            ZK_TRY(Q.rc);
+        }
+        // z_a z_b: the one product of two witness vectors (`DensePolynomial::mul` on MpcField = FieldShare::batch_mul)
+        if (!shared) P.op(ZK_OP_MUL, e_a[0], e_b[0], e_s[0], MUL.size);
+        else ZK_TRY(zk_shared_beaver_mul(nt, LANES, (const void* const*)e_a, (const void* const*)e_b, (void* const*)e_s, MUL.size, tx, ty, tz, "mp_bv"));
+        char *hq[2], *hr[2];
+        for (int l = 0; l < LANES; l++) {
+            Prover& Q = PL[l];
+            // r(alpha, X) (eta_c z_a z_b + eta_a z_a + eta_b z_b) - z t on the multiplication domain (public * own value: local): one pass
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_fr_outer_q1_launch(ctx, e_s[l], e_a[l], e_b[l], e_z[l], e_rp, e_tp, eta[0].v.l, eta[1].v.l, eta[2].v.l, e_s[l], MUL.size));
+            Q.ntt(e_s[l], MUL, 1);                                               // q_1 (prover.rs:517-541)
+            Q.op(ZK_OP_ADD, e_s[l], mask[l], e_s[l], md + 1);
+            hq[l] = Q.dev("h1_q", MUL.size - n); hr[l] = Q.dev("h1_r", n);
+            ZK_TRY(Q.rc);
+            ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, e_s[l], MUL.size, H.log, hq[l], hr[l]));
+        }
+        // the outer sum-check's zero test (prover.rs:547-550): over shares the constant term is opened
+        const char* const not_zero = "zk_marlin_prove: outer sum-check: the sum over H is not zero (unsatisfied constraint system)";
+        char* zo = nullptr;
+        if (!shared) ZK_TRY(check_later(hr[0], 1, not_zero));
+        else ZK_TRY(open_dev(hr, 1, "zero", &zo));
+        const bool zero_sum = !shared || P.is_zero(zo, 1);
+        ZK_TRY(P.rc);
+        if (!zero_sum) ZK_FAIL(ctx, ZK_ERR_STATE, not_zero);
+        for (int l = 0; l < LANES; l++) {
+            PL[l].polys[O_G_1] = Poly{hr[l] + 32, n - 1};
+            PL[l].polys[O_H_1] = Poly{hq[l], std::min(MUL.size - n, 2 * n + 2 - 1)};
+        }
+        laps.lap("polys");
+        ZK_TRY(commit_round(2));
+        laps.lap("commit");
+        beta = sample_outside(H);
+        laps.lap("round2");
+        return ZK_OK;
     }
-    for (int l = 0; l < LANES; l++) {
-        PL[l].polys["g_1"] = Poly{hr[l] + 32, n - 1};
-        PL[l].polys["h_1"] = Poly{hq[l], std::min(MUL.size - n, 2 * n + 2 - 1)};
-    }
-    laps.lap("polys");
-    ZK_TRY(commit_round({"t", "g_1", "h_1"}));
-    ZK_TRY(settle());
-    laps.lap("commit");
-    const HF beta = sample_outside(H);
 
-    laps.lap("round2");
-    // =========================== round 3 (prover.rs:583-716): public values only ===========================
-    const HF vv = v_h_alpha * H.vanishing(beta);
-    char* f_ev = P.dev("f_ev", K.size);
-    char* a_ev = P.dev("a_ev", B.size); char* b_ev = P.dev("b_ev", B.size);
-    ZK_TRY(P.rc);
-    { zk_fr al = alpha.abi(), be = beta.abi(), v = vv.abi(), et[3] = {eta_a.abi(), eta_b.abi(), eta_c.abi()};
-      ZK_TRY(zk_marlin_round3_f_evals_dev(ctx, ix->on_k, K.size, &al, &be, et, &v, f_ev));
-      ZK_TRY(zk_marlin_round3_ab_evals_dev(ctx, ix->on_b, B.size, &al, &be, et, &v, a_ev, b_ev)); }
-    P.ntt(f_ev, K, 1);
-    const Poly f{f_ev, K.size};
-    for (int l = 0; l < LANES; l++) PL[l].polys["g_2"] = Poly{f_ev + 32, K.size - 1};
-    ZK_TRY(P.rc);
-    ZK_TRY(start_early("g_2"));                                                  // both of its commitments (degree bound |K| - 2), under the division that yields h_2
-    char* f_on_b = P.fft(B, f, "f_on_b");                                       // a - b f on B itself (degree <= 4|K| - 4 < |B|)
-    P.op(ZK_OP_MUL, b_ev, f_on_b, b_ev, B.size);
-    P.op(ZK_OP_SUB, a_ev, b_ev, a_ev, B.size);
-    P.ntt(a_ev, B, 1);
-    char* h2q = P.dev("h2_q", B.size - K.size); char* h2r = P.dev("h2_r", K.size);
-    ZK_TRY(P.rc);
-    ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, a_ev, B.size, K.log, h2q, h2r));
-    ZK_TRY(check_later(h2r, K.size, "zk_marlin_prove: inner sum-check: a - b f is not divisible by v_K"));
-    for (int l = 0; l < LANES; l++) {
-        PL[l].polys["g_2"] = Poly{f_ev + 32, K.size - 1};
-        PL[l].polys["h_2"] = Poly{h2q, B.size - K.size};
+    // Round 3 (prover.rs:583-716): public values only.  In: alpha, eta, beta, v_h_alpha.  Out: g_2, h_2 committed; vv; gamma
+    int round3() {
+        vv = v_h_alpha * H.vanishing(beta);
+        char* f_ev = P.dev("f_ev", K.size);
+        char* a_ev = P.dev("a_ev", B.size); char* b_ev = P.dev("b_ev", B.size);
+        ZK_TRY(P.rc);
+        { zk_fr al = alpha.abi(), be = beta.abi(), v = vv.abi(), et[3] = {eta[0].abi(), eta[1].abi(), eta[2].abi()};
+          ZK_TRY(zk_marlin_round3_f_evals_dev(ctx, ix->on_k, K.size, &al, &be, et, &v, f_ev));
+          ZK_TRY(zk_marlin_round3_ab_evals_dev(ctx, ix->on_b, B.size, &al, &be, et, &v, a_ev, b_ev)); }
+        P.ntt(f_ev, K, 1);
+        for (int l = 0; l < LANES; l++) PL[l].polys[O_G_2] = Poly{f_ev + 32, K.size - 1};
+        ZK_TRY(P.rc);
+        ZK_TRY(start_early(O_G_2));                                              // both of its commitments (degree bound |K| - 2), under the division that yields h_2
+        char* f_on_b = P.fft(B, Poly{f_ev, K.size}, "f_on_b");                  // a - b f on B itself (degree <= 4|K| - 4 < |B|)
+        P.op(ZK_OP_MUL, b_ev, f_on_b, b_ev, B.size);
+        P.op(ZK_OP_SUB, a_ev, b_ev, a_ev, B.size);
+        P.ntt(a_ev, B, 1);
+        char* h2q = P.dev("h2_q", B.size - K.size); char* h2r = P.dev("h2_r", K.size);
+        ZK_TRY(P.rc);
+        ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, a_ev, B.size, K.log, h2q, h2r));
+        ZK_TRY(check_later(h2r, K.size, "zk_marlin_prove: inner sum-check: a - b f is not divisible by v_K"));
+        for (int l = 0; l < LANES; l++) PL[l].polys[O_H_2] = Poly{h2q, B.size - K.size};
+        laps.lap("polys");
+        ZK_TRY(commit_round(3));
+        laps.lap("commit");
+        gamma = P.next_fr(fs);
+        laps.lap("round3");
+        return ZK_OK;
     }
-    laps.lap("polys");
-    ZK_TRY(commit_round({"g_2", "h_2"}));
-    ZK_TRY(settle());
-    laps.lap("commit");
-    const HF gamma = P.next_fr(fs);
 
-    laps.lap("round3");
-    // =========================== evaluations and linear combinations ===========================
-    std::map<std::string, HF> single;
-    {   // the evaluations of the query set in one batch (two launches, one copy back); z_b and g_1 are shared: every lane's
-        // evaluation, opened (`evaluations.publicize()`, lib.rs:296)
-        std::vector<std::pair<std::string, HF>> want = {{"z_b", beta}, {"g_1", beta}, {"t", beta}, {"g_2", gamma}};
-        for (const char* m : {"a", "b", "c"})
-            for (const char* part : {"_row", "_col", "_row_col"}) want.push_back({std::string(m) + part, gamma});
+    // The evaluations of the query set, absorbed, and the linear combinations over them.  In: oracles, challenges, pub.  Out: evaluations, queries, xi
+    int evaluate() {
+        // one batch (two launches, one copy back); z_b and g_1 are shared: every lane's evaluation, opened (`evaluations.publicize()`, lib.rs:296)
+        HF z_b_beta, g_1_beta, t_beta, g_2_gamma, row[3], col[3], row_col[3];    // row, col, row_col: of A, B, C at gamma
+        struct Want { Oracle o; const HF* point; HF* value; };
+        std::vector<Want> want = {{O_Z_B, &beta, &z_b_beta}, {O_G_1, &beta, &g_1_beta}, {O_T, &beta, &t_beta}, {O_G_2, &gamma, &g_2_gamma}};
+        for (int m = 0; m < 3; m++) {
+            want.push_back({index_of(m, ROW), &gamma, &row[m]});
+            want.push_back({index_of(m, COL), &gamma, &col[m]});
+            want.push_back({index_of(m, ROW_COL), &gamma, &row_col[m]});
+        }
         std::vector<zk_poly_ref> refs;
         std::vector<zk_fr> pts;
-        for (size_t i = 0; i < want.size(); i++) {
-            const Poly& p = P.polys[want[i].first];
-            refs.push_back(zk_poly_ref{p.p, p.n});
-            pts.push_back(want[i].second.abi());
-        }
-        if (LANES == 2)
-            for (const char* l : {"z_b", "g_1"}) { const Poly& p = PL[1].polys[l]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(beta.abi()); }
+        for (const Want& w : want) { const Poly& p = P.polys[w.o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(w.point->abi()); }
+        if (LANES == 2)                                                          // behind them: the MAC lane of the two shared ones
+            for (Oracle o : {O_Z_B, O_G_1}) { const Poly& p = PL[1].polys[o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(beta.abi()); }
         std::vector<zk_fr> vals(refs.size());
         ZK_TRY(zk_poly_evaluate_batch_dev(ctx, refs.data(), pts.data(), refs.size(), vals.data()));
-        std::map<std::string, HF> at;
-        for (size_t i = 0; i < want.size(); i++) at[want[i].first] = HF::from_abi(vals[i]);
+        for (size_t i = 0; i < want.size(); i++) *want[i].value = HF::from_abi(vals[i]);
         if (shared) {
-            std::vector<HF> frs[2] = {{at["z_b"], at["g_1"]}, {}}, ofr;
+            std::vector<HF> frs[2] = {{z_b_beta, g_1_beta}, {}}, ofr;
             if (LANES == 2) frs[1] = {HF::from_abi(vals[want.size()]), HF::from_abi(vals[want.size() + 1])};
             std::vector<zk_g1_projective> nog[2], og;
             ZK_TRY(open_small<LANES>(nt, frs, nog, ofr, og));
-            at["z_b"] = ofr[0];
-            at["g_1"] = ofr[1];
+            z_b_beta = ofr[0]; g_1_beta = ofr[1];
         }
-        for (const char* l : {"z_b", "g_1", "t", "g_2"}) single[l] = at[l];
-        const HF ba0 = beta * alpha;
-        for (const char* m : {"a", "b", "c"}) {
-            const std::string s(m);
-            single[s + "_denom"] = ba0 - alpha * at[s + "_row"] - beta * at[s + "_col"] + at[s + "_row_col"];
-        }
-    }
-    const HF ba = beta * alpha;
-    ZK_TRY(P.rc);
-    // construct_linear_combinations (ahp/mod.rs:112-290)
-    const HF v_h_beta = H.vanishing(beta), v_x_beta = beta.pow(ni) - one;
-    const HF r_alpha_at_beta = (alpha == beta) ? HF::from_u64(n) * alpha.pow(n - 1) : (v_h_alpha - v_h_beta) * (alpha - beta).inv();
-    HF x_beta = HF::zero();
-    {
-        std::vector<HF> x{one};
-        x.insert(x.end(), pub.begin(), pub.end());
+        const HF ba = beta * alpha, one = HF::one();
+        HF d[3];                                                                  // a_denom, b_denom, c_denom
+        for (int m = 0; m < 3; m++) d[m] = ba - alpha * row[m] - beta * col[m] + row_col[m];
+        ZK_TRY(P.rc);
+        // construct_linear_combinations (ahp/mod.rs:112-290)
+        const HF v_h_beta = H.vanishing(beta), v_x_beta = beta.pow(ni) - one;
+        const HF r_alpha_at_beta = (alpha == beta) ? HF::from_u64(n) * alpha.pow(n - 1) : (v_h_alpha - v_h_beta) * (alpha - beta).inv();
+        HF x_beta = HF::zero(), g = one;                                           // the public input's polynomial at beta
         if (v_x_beta.is_zero()) {
-            HF g = one;
-            for (size_t k = 0; k < ni; k++, g = g * X.gen) if (g == beta) x_beta = x[k];
+            for (size_t k = 0; k < ni; k++, g = g * X.gen) if (g == beta) x_beta = pub[k];
         } else {
             const HF l0 = v_x_beta * HF::from_u64(ni).inv();
-            HF g = one;
-            for (size_t k = 0; k < ni; k++, g = g * X.gen) x_beta = x_beta + x[k] * (l0 * g * (beta - g).inv());
+            for (size_t k = 0; k < ni; k++, g = g * X.gen) x_beta = x_beta + pub[k] * (l0 * g * (beta - g).inv());
         }
-    }
-    const HF z_b_beta = single["z_b"], t_beta = single["t"], g_1_beta = single["g_1"], g_2_gamma = single["g_2"];
-    const HF da = single["a_denom"], db = single["b_denom"], dc = single["c_denom"];
-    std::map<std::string, std::vector<Term>> lcs;
-    lcs["z_b"] = {{one, "z_b"}}; lcs["g_1"] = {{one, "g_1"}}; lcs["t"] = {{one, "t"}}; lcs["g_2"] = {{one, "g_2"}};
-    lcs["outer_sumcheck"] = {{one, "mask_poly"}, {r_alpha_at_beta * (eta_a + eta_c * z_b_beta), "z_a"}, {r_alpha_at_beta * eta_b * z_b_beta, nullptr},
-                             {(t_beta * v_x_beta).neg(), "w"}, {(t_beta * x_beta).neg(), nullptr}, {v_h_beta.neg(), "h_1"},
-                             {(beta * g_1_beta).neg(), nullptr}};
-    lcs["a_denom"] = {{ba, nullptr}, {alpha.neg(), "a_row"}, {beta.neg(), "a_col"}, {one, "a_row_col"}};
-    lcs["b_denom"] = {{ba, nullptr}, {alpha.neg(), "b_row"}, {beta.neg(), "b_col"}, {one, "b_row_col"}};
-    lcs["c_denom"] = {{ba, nullptr}, {alpha.neg(), "c_row"}, {beta.neg(), "c_col"}, {one, "c_row_col"}};
-    const HF b_expr = da * db * dc * (gamma * g_2_gamma + t_beta * HF::from_u64(K.size).inv());
-    lcs["inner_sumcheck"] = {{eta_a * db * dc * vv, "a_val"}, {eta_b * da * dc * vv, "b_val"}, {eta_c * db * da * vv, "c_val"},
-                             {b_expr.neg(), nullptr}, {K.vanishing(gamma).neg(), "h_2"}};
-    const char* const EVAL_LABELS[7] = {"a_denom", "b_denom", "c_denom", "g_1", "g_2", "t", "z_b"};
-    std::vector<HF> evaluations;
-    std::vector<uint8_t> ev_bytes;
-    for (const char* l : EVAL_LABELS) { evaluations.push_back(single[l]); single[l].bytes(ev_bytes); }
-    ZK_TRY(zk_fsrng_absorb(fs, ev_bytes.data(), ev_bytes.size()));
-    HF xi;
-    {   // u128::rand(&mut fs_rng).into()  (lib.rs:300)
-        uint64_t w[2];
+        const LinComb outer = {{one, O_MASK_POLY}, {r_alpha_at_beta * (eta[0] + eta[2] * z_b_beta), O_Z_A}, {r_alpha_at_beta * eta[1] * z_b_beta, O_NONE},
+                               {(t_beta * v_x_beta).neg(), O_W}, {(t_beta * x_beta).neg(), O_NONE}, {v_h_beta.neg(), O_H_1},
+                               {(beta * g_1_beta).neg(), O_NONE}};
+        const HF da = d[0], db = d[1], dc = d[2], b_expr = da * db * dc * (gamma * g_2_gamma + t_beta * HF::from_u64(K.size).inv());
+        const LinComb inner = {{eta[0] * db * dc * vv, O_A_VAL}, {eta[1] * da * dc * vv, O_B_VAL}, {eta[2] * db * da * vv, O_C_VAL},
+                               {b_expr.neg(), O_NONE}, {K.vanishing(gamma).neg(), O_H_2}};
+        auto denom_lc = [&](int m) {
+            return LinComb{{ba, O_NONE}, {alpha.neg(), index_of(m, ROW)}, {beta.neg(), index_of(m, COL)}, {one, index_of(m, ROW_COL)}};
+        };
+        // the query set, labels in alphabetic order: {g_1, outer_sumcheck, t, z_b} at beta, {a_denom, b_denom, c_denom, g_2, inner_sumcheck} at gamma
+        queries[0] = {{{one, O_G_1}}, outer, {{one, O_T}}, {{one, O_Z_B}}};
+        queries[1] = {denom_lc(0), denom_lc(1), denom_lc(2), {{one, O_G_2}}, inner};
+        evaluations = {da, db, dc, g_1_beta, g_2_gamma, t_beta, z_b_beta};      // a_denom, b_denom, c_denom, g_1, g_2, t, z_b
+        std::vector<uint8_t> ev_bytes;
+        for (const HF& e : evaluations) e.bytes(ev_bytes);
+        ZK_TRY(zk_fsrng_absorb(fs, ev_bytes.data(), ev_bytes.size()));
+        uint64_t w[2];                                                            // u128::rand(&mut fs_rng).into()  (lib.rs:300)
         ZK_TRY(zk_rng_next_u128(fs, w));
         xi = HF::from_u64(w[0]) + HF::from_u64(w[1]) * HF::from_u64((uint64_t)1 << 32) * HF::from_u64((uint64_t)1 << 32);
+        laps.lap("evals+lc");
+        return ZK_OK;
     }
 
-    laps.lap("evals+lc");
-    // =========================== open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340) ===========================
+    // open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340).  In: queries, xi, beta, gamma, rands.  Out: wit, has_rv, rvs.
     // Over shares: the witness of a share combination is a share of the witness.  A combination with a shared oracle in it runs on
     // every lane, public oracles entering it on the leader only (shift(): in both lanes, mac_share = 1 there), and its witness
     // (and random_v) is opened; a combination of public oracles only (the query point gamma) is computed alike by every party.
-    const std::vector<std::string> QUERY[2] = {{"g_1", "outer_sumcheck", "t", "z_b"}, {"a_denom", "b_denom", "c_denom", "g_2", "inner_sumcheck"}};
-    const HF points[2] = {beta, gamma};
-    std::vector<const zk_bases*> jb; std::vector<size_t> joff, jlen; std::vector<const void*> jsc;
-    size_t counts[2][2] = {{0, 0}, {0, 0}};                                      // [query point][lane]
-    std::vector<ZkTask<zk_g1_projective>> extra[2];                         // the blinding witnesses: host threads, joined after the batch
-    auto small_async = [&](const std::vector<HF>& c) { return zk_async(ctx, [ctx, &gamma_pts, c] { return small_msm_par(ctx, gamma_pts, c); }); };
-    bool has_rv[2] = {false, false}, q_shared[2] = {false, false};
-    HF rvs[2];
-    for (int q = 0; q < 2; q++) {
-        const HF z = points[q];
-        std::vector<std::pair<std::string, HF>> terms;                            // polynomial label -> accumulated coefficient (first-use order)
-        std::vector<HF> r_comb, sr, srw;
-        std::vector<std::pair<std::string, HF>> shifted;
-        HF cj = one;                                                              // xi^j
-        for (const std::string& label : QUERY[q]) {
-            const auto& lc = lcs[label];
-            std::vector<Term> ps;
-            for (const Term& t : lc) if (t.label) ps.push_back(t);
-            const HF c0 = cj;
-            cj = cj * xi;
-            for (const Term& t : ps) {
-                auto it = std::find_if(terms.begin(), terms.end(), [&](const std::pair<std::string, HF>& e) { return e.first == t.label; });
-                if (it == terms.end()) terms.push_back({t.label, t.c * c0}); else it->second = it->second + t.c * c0;
-                acc_scaled(r_comb, P.rands[t.label].first, t.c * c0);
-            }
-            if (lc.size() == 1 && P.bounds.count(ps[0].label)) {
-                const HF c1 = cj;
+    int open_combinations() {
+        const HF points[2] = {beta, gamma}, one = HF::one();
+        MsmJobs jobs;
+        size_t counts[2][2] = {{0, 0}, {0, 0}};                                  // [query point][lane]
+        std::vector<ZkTask<zk_g1_projective>> extra[2];                          // the blinding witnesses: host threads, joined after the batch
+        bool q_shared[2] = {false, false};
+        for (int q = 0; q < 2; q++) {
+            const HF z = points[q];
+            std::vector<std::pair<Oracle, HF>> terms;                            // polynomial -> accumulated coefficient (first-use order)
+            std::vector<HF> r_comb, sr, srw;
+            std::vector<std::pair<Oracle, HF>> shifted;
+            HF cj = one;                                                         // xi^j
+            for (const LinComb& lc : queries[q]) {
+                const HF c0 = cj;
                 cj = cj * xi;
-                shifted.push_back({ps[0].label, c1});
-                acc_scaled(sr, P.rands[ps[0].label].second, c1);
+                for (const Term& t : lc) {
+                    if (t.o == O_NONE) continue;
+                    auto it = std::find_if(terms.begin(), terms.end(), [&](const std::pair<Oracle, HF>& e) { return e.first == t.o; });
+                    if (it == terms.end()) terms.push_back({t.o, t.c * c0}); else it->second = it->second + t.c * c0;
+                    acc_scaled(r_comb, rands[t.o].plain, t.c * c0);
+                }
+                if (lc.size() == 1 && bounded(lc[0].o)) {                        // a degree-bounded oracle queried by itself
+                    const HF c1 = cj;
+                    cj = cj * xi;
+                    shifted.push_back({lc[0].o, c1});
+                    acc_scaled(sr, rands[lc[0].o].shifted, c1);
+                }
             }
-        }
-        bool any_shared = false;
-        for (auto& t : terms) any_shared = any_shared || (shared && label_shared(t.first.c_str()));
-        q_shared[q] = any_shared;
-        size_t cn = 0;
-        for (auto& t : terms) cn = std::max(cn, P.polys[t.first].n);
-        for (int l = 0; l < (any_shared ? LANES : 1); l++) {
-            Prover& Q = PL[l];
-            char* comb = Q.dev("comb" + std::to_string(q), cn);
-            {   // one launch for the whole combination (vec_ops.hip::k_lincomb)
+            bool any_shared = false;
+            for (auto& t : terms) any_shared = any_shared || (shared && ORACLES[t.first].shared);
+            q_shared[q] = any_shared;
+            size_t cn = 0;
+            for (auto& t : terms) cn = std::max(cn, P.polys[t.first].n);
+            for (int l = 0; l < (any_shared ? LANES : 1); l++) {
+                Prover& Q = PL[l];
+                char* comb = Q.dev("comb" + std::to_string(q), cn);
+                // one launch for the whole combination (vec_ops.hip::k_lincomb)
                 std::vector<const void*> tp; std::vector<size_t> tn; std::vector<std::array<uint32_t, 9>> tk;
                 for (auto& t : terms) {
-                    if (any_shared && !label_shared(t.first.c_str()) && !leader) continue;   // a public oracle in a shared combination: the leader's
+                    if (any_shared && !ORACLES[t.first].shared && !leader) continue;   // a public oracle in a shared combination: the leader's
                     const Poly& p = Q.polys[t.first];
                     tp.push_back(p.p); tn.push_back(p.n);
                     std::array<uint32_t, 9> k;
@@ -858,48 +843,42 @@ int marlin_impl(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g
                 }
                 ZK_TRY(Q.rc);
                 ZK_TRY(zk_fr_lincomb_launch(ctx, (int)tp.size(), tp.data(), tn.data(), (const uint32_t (*)[9])tk.data(), comb, cn));
-            }
-            char* quo = Q.dev("quo" + std::to_string(q), cn);
-            ZK_TRY(Q.rc);
-            { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, comb, cn, &zz, quo, nullptr)); }
-            const size_t first_job = jb.size();
-            jb.push_back(P.pg); joff.push_back(0); jsc.push_back(quo); jlen.push_back(cn - 1);
-            int si = 0;
-            for (auto& sh : shifted) {
-                if (any_shared && !label_shared(sh.first.c_str()) && !leader) continue;
-                const Poly& p = Q.polys[sh.first];
-                char* wq2 = Q.dev("swit" + std::to_string(q) + "_" + std::to_string(si++), p.n);
+                char* quo = Q.dev("quo" + std::to_string(q), cn);
                 ZK_TRY(Q.rc);
-                { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, p.p, p.n, &zz, wq2, nullptr)); }
-                Q.scale(wq2, sh.second, wq2, p.n - 1);
-                jb.push_back(P.pg); joff.push_back(P.max_degree - P.bounds[sh.first]); jsc.push_back(wq2); jlen.push_back(p.n - 1);
+                { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, comb, cn, &zz, quo, nullptr)); }
+                const size_t first_job = jobs.add(powers_g, 0, quo, cn - 1);
+                int si = 0;
+                for (auto& sh : shifted) {
+                    if (any_shared && !ORACLES[sh.first].shared && !leader) continue;
+                    const Poly& p = Q.polys[sh.first];
+                    char* wq2 = Q.dev("swit" + std::to_string(q) + "_" + std::to_string(si++), p.n);
+                    ZK_TRY(Q.rc);
+                    { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, p.p, p.n, &zz, wq2, nullptr)); }
+                    Q.scale(wq2, sh.second, wq2, p.n - 1);
+                    jobs.add(powers_g, max_degree - bound(sh.first), wq2, p.n - 1);
+                }
+                counts[q][l] = jobs.size() - first_job;
             }
-            counts[q][l] = jb.size() - first_job;
+            bool hiding = false;
+            for (auto& v : r_comb) hiding = hiding || !v.is_zero();
+            if (hiding) {
+                extra[q].push_back(small_async(host_div_linear(r_comb, z)));
+                has_rv[q] = true;
+                rvs[q] = host_eval(r_comb, z);
+            }
+            for (auto& sh : shifted) {
+                const std::vector<HF>& sb = rands[sh.first].shifted;
+                if (!sb.empty()) acc_scaled(srw, host_div_linear(sb, z), sh.second);
+            }
+            if (!srw.empty()) extra[q].push_back(small_async(srw));
+            if (!shifted.empty() && has_rv[q]) rvs[q] = rvs[q] + host_eval(sr, z);
         }
-        bool hiding = false;
-        for (auto& v : r_comb) hiding = hiding || !v.is_zero();
-        if (hiding) {
-            extra[q].push_back(small_async(host_div_linear(r_comb, z)));
-            has_rv[q] = true;
-            rvs[q] = host_eval(r_comb, z);
-        }
-        for (auto& sh : shifted) {
-            const std::vector<HF>& sb = P.rands[sh.first].second;
-            if (!sb.empty()) acc_scaled(srw, host_div_linear(sb, z), sh.second);
-        }
-        if (!srw.empty()) extra[q].push_back(small_async(srw));
-        if (!shifted.empty() && has_rv[q]) rvs[q] = rvs[q] + host_eval(sr, z);
-    }
-    ZK_TRY(lanes_rc());
-    std::vector<zk_g1_projective> outs(jb.size());
-    std::vector<void*> outp(jb.size());
-    for (size_t i = 0; i < jb.size(); i++) outp[i] = &outs[i];
-    const int orc = zk_msm_batch_dev(ctx, jb.size(), jb.data(), joff.data(), jsc.data(), jlen.data(), outp.data());
-    std::vector<zk_g1_projective> extra_pts[2];
-    for (int q = 0; q < 2; q++) for (auto& f : extra[q]) extra_pts[q].push_back(f.get());
-    ZK_TRY(orc);
-    Affine<G1Field> wit[2];
-    {
+        ZK_TRY(lanes_rc());
+        int orc = ZK_OK;
+        const std::vector<zk_g1_projective> outs = jobs.run(ctx, &orc);
+        std::vector<zk_g1_projective> extra_pts[2];
+        for (int q = 0; q < 2; q++) for (auto& f : extra[q]) extra_pts[q].push_back(f.get());
+        ZK_TRY(orc);
         size_t k = 0;
         std::vector<zk_g1_projective> wits;
         for (int q = 0; q < 2; q++) {
@@ -912,7 +891,7 @@ int marlin_impl(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g
                 k += counts[q][l];
                 wl[l] = w;
             }
-            if (q_shared[q]) {                                                  // the witness (and random_v) of a shared combination: opened
+            if (q_shared[q]) {                                                   // the witness (and random_v) of a shared combination: opened
                 std::vector<HF> frs[2], ofr;
                 std::vector<zk_g1_projective> pts[2], og;
                 for (int l = 0; l < LANES; l++) { pts[l].push_back(wl[l]); if (has_rv[q]) frs[l].push_back(rvs[q]); }
@@ -923,52 +902,76 @@ int marlin_impl(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g
             wits.push_back(wl[0]);
         }
         const std::vector<Affine<G1Field>> wa = batch_to_aff(wits);
-        wit[0] = wa[0];
-        wit[1] = wa[1];
+        wit[0] = wa[0]; wit[1] = wa[1];
+        laps.lap("open");
+        return ZK_OK;
     }
 
-    laps.lap("open");
-    // =========================== Proof::serialize (data_structures.rs:99-110, derive order) ===========================
-    std::vector<uint8_t> out;
-    auto u64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i))); };
-    auto g1c = [&](const Affine<G1Field>& a) { uint8_t b[48]; g1_serialize(a, b); out.insert(out.end(), b, b + 48); };
-    const std::vector<std::vector<const char*>> ROUNDS = {{"w", "z_a", "z_b", "mask_poly"}, {"t", "g_1", "h_1"}, {"g_2", "h_2"}};
-    u64(3);
-    for (auto& rnd_labels : ROUNDS) {
-        u64(rnd_labels.size());
-        for (const char* l : rnd_labels) {
-            const Comm& c = P.comms[l];
-            g1c(c.c);
-            out.push_back(c.has_shift ? 1 : 0);
-            if (c.has_shift) g1c(c.s);
+    // Proof::serialize (data_structures.rs:99-110, derive order).  In: comms, evaluations, wit, has_rv, rvs
+    int serialize(uint8_t* proof_out, size_t cap, size_t* proof_len) {
+        std::vector<uint8_t> out;
+        auto u64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i))); };
+        auto g1c = [&](const Affine<G1Field>& p) { uint8_t b[48]; g1_serialize(p, b); out.insert(out.end(), b, b + 48); };
+        u64(3);
+        for (int round = 1; round <= 3; round++) {
+            const std::vector<Oracle> os = round_oracles(round);
+            u64(os.size());
+            for (Oracle o : os) {
+                const Comm& c = comms[o];
+                g1c(c.c);
+                out.push_back(c.has_shift ? 1 : 0);
+                if (c.has_shift) g1c(c.s);
+            }
         }
+        u64(evaluations.size());
+        for (auto& e : evaluations) e.bytes(out);
+        u64(3); out.push_back(0); out.push_back(0); out.push_back(0);           // three EmptyMessage
+        u64(2);
+        for (int q = 0; q < 2; q++) {
+            g1c(wit[q]);
+            out.push_back(has_rv[q] ? 1 : 0);
+            if (has_rv[q]) rvs[q].bytes(out);
+        }
+        out.push_back(0);                                                        // BatchLCProof.evals = None
+        if (out.size() > cap) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer too small");
+        memcpy(proof_out, out.data(), out.size());
+        *proof_len = out.size();
+        return ZK_OK;
     }
-    u64(evaluations.size());
-    for (auto& e : evaluations) e.bytes(out);
-    u64(3); out.push_back(0); out.push_back(0); out.push_back(0);               // three EmptyMessage
-    u64(2);
-    for (int q = 0; q < 2; q++) {
-        g1c(wit[q]);
-        out.push_back(has_rv[q] ? 1 : 0);
-        if (has_rv[q]) rvs[q].bytes(out);
-    }
-    out.push_back(0);                                                            // BatchLCProof.evals = None
-    if (out.size() > cap) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer too small");
-    memcpy(proof_out, out.data(), out.size());
-    *proof_len = out.size();
-    if (bytes_sent) *bytes_sent = nt.bytes;
+};
+
+template <int LANES>
+int marlin_impl(zk_ctx* ctx, const MarlinArgs& a, uint8_t* proof_out, size_t cap, size_t* proof_len, uint64_t* bytes_sent) {
+    const zk_marlin_index* ix = a.ix;
+    if (!ctx || !ix || !a.powers_g || !a.powers_gamma_g || !a.z[0] || (LANES == 2 && !a.z[1]) || !a.rng || !proof_out || !proof_len) return ZK_ERR_ARG;
+    if (a.powers_g->group != 1 || a.powers_gamma_g->group != 1 || a.powers_gamma_g->n < 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: SRS tables");
+    if (cap < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer smaller than zk_marlin_proof_max_size()");
+    if (ix->num_constraints != ix->num_variables) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: NonSquareMatrix");
+    if (ix->num_instance == 0 || (ix->num_instance & (ix->num_instance - 1))) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: InvalidPublicInputLength");
+    Marlin<LANES> m(ctx, a);
+    const size_t need = std::max(std::max(2 * m.n - 1, 3 * m.n - 1), std::max(m.n, 3 * m.K.size - 3));   // AHPForR1CS::max_degree (ahp/mod.rs:75-97)
+    if (m.max_degree < need) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: IndexTooLarge for this SRS");
+    if (m.B.size < 4 * m.K.size - 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: |K| < 4 is not supported by this entry point");
+    ZK_TRY(m.seed_transcript());
+    ZK_TRY(m.round1());
+    ZK_TRY(m.round2());
+    ZK_TRY(m.round3());
+    ZK_TRY(m.evaluate());
+    ZK_TRY(m.open_combinations());
+    ZK_TRY(m.serialize(proof_out, cap, proof_len));
+    if (bytes_sent) *bytes_sent = m.nt.bytes;
     return ZK_OK;
 }
 
 }  // namespace
 
+extern "C" size_t zk_marlin_proof_max_size(void) { return 8 + 3 * 8 + 9 * 49 + 2 * 48 + 8 + 7 * 32 + 8 + 3 + 8 + 2 * (49 + 32) + 1; }
+
 extern "C" int zk_marlin_prove(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
                                const void* z_dev, zk_rng* zk_rng_, int mask_on_device, uint8_t* proof_out, size_t cap, size_t* proof_len) {
     ZK_API_BEGIN(ctx)
-    if (!ctx || !ix || !powers_g || !powers_gamma_g || !z_dev || !zk_rng_ || !proof_out || !proof_len) return ZK_ERR_ARG;
-    const void* z[2] = {z_dev, nullptr};
-    const void* none[2] = {nullptr, nullptr};
-    return marlin_impl<1>(ctx, ix, powers_g, powers_gamma_g, z, zk_rng_, mask_on_device, false, none, none, none, nullptr, proof_out, cap,
+    const void *z[2] = {z_dev, nullptr}, *none[2] = {nullptr, nullptr};
+    return marlin_impl<1>(ctx, MarlinArgs{ix, powers_g, powers_gamma_g, z, zk_rng_, mask_on_device, false, none, none, none, nullptr}, proof_out, cap,
                           proof_len, nullptr);
     ZK_API_END
 }
@@ -981,10 +984,9 @@ extern "C" int zk_marlin_prove_shared(zk_ctx* ctx, const zk_marlin_index* ix, co
                                       const void* tz, const zk_net_vtable* net, uint8_t* proof_out, size_t cap, size_t* proof_len,
                                       uint64_t* bytes_sent) {
     ZK_API_BEGIN(ctx)
-    if (!ctx || !ix || !powers_g || !powers_gamma_g || !z_share_dev || !zk_rng_ || !proof_out || !proof_len) return ZK_ERR_ARG;
     const void* z[2] = {z_share_dev, nullptr};
     const void *txs[2] = {tx, nullptr}, *tys[2] = {ty, nullptr}, *tzs[2] = {tz, nullptr};
-    return marlin_impl<1>(ctx, ix, powers_g, powers_gamma_g, z, zk_rng_, mask_on_device, true, txs, tys, tzs, net, proof_out, cap, proof_len,
+    return marlin_impl<1>(ctx, MarlinArgs{ix, powers_g, powers_gamma_g, z, zk_rng_, mask_on_device, true, txs, tys, tzs, net}, proof_out, cap, proof_len,
                           bytes_sent);
     ZK_API_END
 }
@@ -995,10 +997,8 @@ extern "C" int zk_marlin_prove_shared_spdz(zk_ctx* ctx, const zk_marlin_index* i
                                            const void* const tx_lanes[2], const void* const ty_lanes[2], const void* const tz_lanes[2],
                                            const zk_net_vtable* net, uint8_t* proof_out, size_t cap, size_t* proof_len, uint64_t* bytes_sent) {
     ZK_API_BEGIN(ctx)
-    if (!ctx || !ix || !powers_g || !powers_gamma_g || !z_lanes_dev || !z_lanes_dev[0] || !z_lanes_dev[1] || !zk_rng_ || !proof_out || !proof_len)
-        return ZK_ERR_ARG;
     const void* none[2] = {nullptr, nullptr};
-    return marlin_impl<2>(ctx, ix, powers_g, powers_gamma_g, z_lanes_dev, zk_rng_, mask_on_device, true, tx_lanes ? tx_lanes : none,
-                          ty_lanes ? ty_lanes : none, tz_lanes ? tz_lanes : none, net, proof_out, cap, proof_len, bytes_sent);
+    return marlin_impl<2>(ctx, MarlinArgs{ix, powers_g, powers_gamma_g, z_lanes_dev ? z_lanes_dev : none, zk_rng_, mask_on_device, true, tx_lanes ? tx_lanes : none,
+                                          ty_lanes ? ty_lanes : none, tz_lanes ? tz_lanes : none, net}, proof_out, cap, proof_len, bytes_sent);
     ZK_API_END
 }

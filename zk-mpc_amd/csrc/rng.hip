@@ -38,7 +38,9 @@ __global__ void __launch_bounds__(256) k_fr_random(ChaKey key, uint64_t stream_i
     }
 }
 
-bool fr_words_valid(const uint64_t l[4]) {   // < r  (is_valid, ff/src/fields/macros.rs:255-260)
+}  // namespace
+
+bool zk_fr_words_valid(const uint64_t l[4]) {   // < r  (is_valid, ff/src/fields/macros.rs:255-260)
     static const uint64_t R[4] = {0x0a11800000000001ull, 0x59aa76fed0000001ull, 0x60b44d1e5c37b001ull, 0x12ab655e9a2ca556ull};
     for (int i = 3; i >= 0; i--) {
         if (l[i] < R[i]) return true;
@@ -46,8 +48,6 @@ bool fr_words_valid(const uint64_t l[4]) {   // < r  (is_valid, ff/src/fields/ma
     }
     return false;
 }
-
-}  // namespace
 
 // out[i] = a uniformly random element of Fr, i < n (device vector in the reference's layout).  key32 = NULL: a fresh key
 // from the operating system's CSPRNG; otherwise the 32-byte ChaCha20 key (deterministic: tests only).  Vectors drawn under
@@ -167,7 +167,7 @@ extern "C" int zk_rng_next_fr(zk_rng* r, zk_fr* out) {
         uint64_t l[4];
         for (int i = 0; i < 4; i++) l[i] = r->fs.r.next_u64();
         l[3] &= 0xffffffffffffffffull >> 3;
-        if (fr_words_valid(l)) { memcpy(out->l, l, 32); return ZK_OK; }
+        if (zk_fr_words_valid(l)) { memcpy(out->l, l, 32); return ZK_OK; }
     }
     ZK_API_END
 }
