@@ -388,6 +388,48 @@ int zk_groth16_prove(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, const zk
 int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, const zk_fr* z_host,
                             const zk_fr* r, const zk_fr* s, const zk_fr* z_next_host, uint8_t proof_out[192]);
 
+/* ---- the pairing and Groth16 verification ------------------------------------------------------------- */
+/* An element of GT as Fp12<Fq12Parameters> lays it out: the tower Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - u), twelve Fq in the
+ * order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1 (ff/src/fields/models/fp12_2over3over2.rs, fp6_3over2.rs), each in the ABI's Fq form.
+ * The value is miller_loop^(ZK_GT_EXPONENT_MULTIPLE (q^12 - 1) / r): the final exponentiation's hard part is the chain of Hayashida,
+ * Hayasaka, Teruya (eprint 2020/875), which yields the cube of the reference's value.  3 is coprime to r: products, equality and
+ * "is one" -- every verdict -- are those of the reference; a caller that needs the reference's very words takes the cube there. */
+#define ZK_GT_EXPONENT_MULTIPLE 3
+int zk_gt_exponent_multiple(void);                       /* = ZK_GT_EXPONENT_MULTIPLE, for bindings that cannot read macros */
+typedef struct { zk_fq c[12]; } zk_gt;
+/* PairingEngine::product_of_pairings (ec/src/lib.rs:96-103) for count products of `pairs` pairs each:
+ * outs[k] = final_exponentiation(prod_{j < pairs} miller_loop(p[k * pairs + j], q[k * pairs + j])), k < count; host slices in and
+ * out, device kernels (one Miller loop per lane, one final exponentiation per product).  A pair with either point at infinity
+ * contributes the factor 1.  Points are taken as they come: on the curve and in the prime-order subgroups is the caller's business
+ * (GroupAffine::deserialize checks both; zk_bases_deserialize_compressed checks the first).  pairs = 0, count = 0, a null
+ * pointer or more than 2^22 pairs in all: ZK_ERR_ARG. */
+int zk_pairing_products(zk_ctx* ctx, const zk_g1_affine* p, const zk_g2_affine* q, size_t pairs, size_t count, zk_gt* outs);
+/* The same arithmetic compiled for the host (64-bit limbs; no device, no context): for O(1) checks and for tests.  Also
+ * ZK_ERR_ARG for a coordinate word that is not below q. */
+int zk_pairing_products_host(const zk_g1_affine* p, const zk_g2_affine* q, size_t pairs, size_t count, zk_gt* outs);
+int zk_gt_is_one(const zk_gt* a);                        /* 1 / 0 */
+int zk_gt_eq(const zk_gt* a, const zk_gt* b);            /* 1 / 0 */
+int zk_gt_mul(const zk_gt* a, const zk_gt* b, zk_gt* out);
+/* Groth16::verify (arkworks/groth16/src/verifier.rs:13-61) for count proofs of one resident key.  inputs_host: count x
+ * inputs_per_proof public inputs (the instance without its leading 1; inputs_per_proof must be num_instance - 1 = the key's
+ * gamma_abc_g1 length - 1); proofs_host: count x 192 bytes as the provers write them; ok[k] = 1 / 0.  A, B, C are decompressed on
+ * the device; a proof whose bytes are not points of the curves gets ok = 0 (it is not an error of the call).  The prepared inputs
+ * gamma_abc[0] + sum x_i gamma_abc[i] are one scalar-multiplication lane per proof, then 3 count Miller loops -- (A, B), (prepared,
+ * -gamma), (C, -delta) -- and count final exponentiations, each compared with e(alpha, beta), which is computed once per key and kept
+ * on it.  No subgroup check on A, B, C (Proof::deserialize does one).  ZK_ERR_ARG: a key without verifying-key parts (zk_pk_upload:
+ * its host view has no gamma), inputs_per_proof that does not match, an input that is not below r, a null pointer, count = 0. */
+int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                            const uint8_t* proofs_host, int* ok);
+/* One proof through the host arithmetic (no device, no context), on a host view of the VerifyingKey
+ * (arkworks/groth16/src/data_structures.rs:43-58; a resident key gives it through zk_pk_vk_g1 / zk_pk_vk_g2 / zk_pk_download_g1
+ * with which = 5).  n_inputs must be gamma_abc_len - 1. */
+typedef struct {
+    zk_g1_affine alpha_g1;
+    zk_g2_affine beta_g2, gamma_g2, delta_g2;
+    const zk_g1_affine* gamma_abc_g1; size_t gamma_abc_len;
+} zk_vk_host;
+int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok);
+
 /* ---- dense polynomials over Fr and KZG10 (row a14: the data-parallel pieces of the Marlin / poly-commit path) ---- */
 /* out[i] = start * base^i, i < n (device vector). */
 int zk_fr_powers_dev(zk_ctx* ctx, const zk_fr* base, const zk_fr* start, size_t n, void* out_dev);
@@ -685,6 +727,13 @@ int zk_diag_fq_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in13s, uint32_t* ou
 int zk_diag_fr_lazy_dev(zk_ctx* ctx, int op, const uint32_t* in9s, uint32_t* out9s, size_t n_cases);
 int zk_diag_fq2_pair_dev(zk_ctx* ctx, int op, const uint32_t* in13s, uint32_t* out13s, size_t n_cases);
 int zk_diag_f7l_dev(zk_ctx* ctx, int op, const uint32_t* in26s, uint32_t* out26s, size_t n_cases);
+/* Test hooks: the Fq12 tower of csrc/pairing.cuh as the device code object runs it (zk_diag_fq12_dev, one case per lane) and as the
+ * host instantiation runs it (zk_diag_fq12_host).  A case is two zk_gt (a, b), the result one: op 0 a b; 1 a^2; 2 a times the sparse
+ * line (b.c[0], b.c[1]) + (b.c[6], b.c[7]) w + (b.c[8], b.c[9]) w^3; 3 1 / a (0 for 0); 4, 5, 6 a^q, a^(q^2), a^(q^3); 7 the
+ * cyclotomic squaring (a^2 for a in the cyclotomic subgroup).  ZK_ERR_ARG for an unknown op, a null pointer, a word not below q or
+ * n_cases outside 1 .. 2^20. */
+int zk_diag_fq12_dev(zk_ctx* ctx, int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases);
+int zk_diag_fq12_host(int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases);
 /* Diagnostic: k * a in G1 through the curve's endomorphism (hostfield64.hpp: host64_scalar_mul_glv: k split at lambda = z^2 - 1, one
  * joint chain) -- what the host tail of a Groth16 proof runs for keys made by zk_groth16_setup.  Equal to zk_g1_mul for every point of
  * the prime-order subgroup; kept apart from it because ProjectiveCurve::mul (zk_g1_mul) is defined on the whole curve. */

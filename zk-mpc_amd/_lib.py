@@ -62,6 +62,15 @@ class G2Projective(C.Structure):
     _fields_ = [("x", Fq * 2), ("y", Fq * 2), ("z", Fq * 2)]
 
 
+class Gt(C.Structure):
+    _fields_ = [("c", Fq * 12)]
+
+
+class VkHost(C.Structure):
+    _fields_ = [("alpha_g1", G1Affine), ("beta_g2", G2Affine), ("gamma_g2", G2Affine), ("delta_g2", G2Affine),
+                ("gamma_abc_g1", C.c_void_p), ("gamma_abc_len", C.c_size_t)]
+
+
 class R1csHost(C.Structure):
     _fields_ = [("num_constraints", C.c_size_t), ("num_instance", C.c_size_t), ("num_witness", C.c_size_t),
                 ("a_row_ptr", C.c_void_p), ("a_col", C.c_void_p), ("a_coeff", C.c_void_p),
@@ -265,6 +274,16 @@ PROTOTYPES = {
     "zk_diag_fq2_pair_dev": (_I, [_P, _I, _P, _P, _SZ]),
     "zk_diag_f7l_dev": (_I, [_P, _I, _P, _P, _SZ]),
     "zk_diag_g1_mul_glv": (_I, [_P, _P, _P]),
+    "zk_gt_exponent_multiple": (_I, []),
+    "zk_pairing_products": (_I, [_P, _P, _P, _SZ, _SZ, _P]),
+    "zk_pairing_products_host": (_I, [_P, _P, _SZ, _SZ, _P]),
+    "zk_gt_is_one": (_I, [_P]),
+    "zk_gt_eq": (_I, [_P, _P]),
+    "zk_gt_mul": (_I, [_P, _P, _P]),
+    "zk_groth16_verify_batch": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
+    "zk_groth16_verify_host": (_I, [_P, _P, _SZ, _P, _P]),
+    "zk_diag_fq12_dev": (_I, [_P, _I, _P, _P, _SZ]),
+    "zk_diag_fq12_host": (_I, [_I, _P, _P, _SZ]),
 }
 
 _lib = None

@@ -850,6 +850,38 @@ class Context:
         self._ck(self.lib.zk_groth16_prove(self.h, pk.h, r1cs.h, _ptr(z), C.byref(r), C.byref(s), _ptr(out)))
         return out.tobytes()
 
+    # ---- the pairing and Groth16 verification (csrc/pairing.hip) ----
+    def pairing_products(self, p: np.ndarray, q: np.ndarray, pairs: int = 1) -> np.ndarray:
+        """PairingEngine::product_of_pairings for count = len(p) / pairs products: p (n, 12), q (n, 24) uint64 -> (count, 72) GT values."""
+        p, q, count = _pairing_args(p, q, pairs)
+        out = np.zeros((count, 72), dtype=np.uint64)
+        self._ck(self.lib.zk_pairing_products(self.h, _ptr(p), _ptr(q), pairs, count, _ptr(out)))
+        return out
+
+    def groth16_verify_batch(self, pk: "ProvingKey", inputs_mont: np.ndarray, proofs) -> np.ndarray:
+        """Groth16::verify for many proofs of one key: inputs_mont (count, num_instance - 1, 4) Montgomery, proofs = count x 192
+        bytes (a list of proofs or one bytes object); returns count verdicts (1 / 0)."""
+        data = b"".join(proofs) if isinstance(proofs, (list, tuple)) else bytes(proofs)
+        if len(data) % 192:
+            raise ValueError("proofs must be a whole number of 192-byte proofs")
+        count = len(data) // 192
+        inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(count, -1, 4) if count else np.zeros((0, 0, 4), np.uint64)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        ok = np.zeros(count, dtype=np.int32)
+        self._ck(self.lib.zk_groth16_verify_batch(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(ok)))
+        return ok
+
+    def groth16_verify(self, pk: "ProvingKey", inputs_mont: np.ndarray, proof: bytes) -> bool:
+        """Groth16::verify of one proof as create_proof returns it (device path)."""
+        return bool(self.groth16_verify_batch(pk, np.asarray(inputs_mont, dtype=np.uint64).reshape(1, -1, 4), proof)[0])
+
+    def diag_fq12(self, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+        """Test hook: the Fq12 tower on the device, one case (a[i], b[i]) per lane; a, b (n, 72) uint64."""
+        cases = np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.uint64)
+        out = np.zeros((cases.shape[0], 72), dtype=np.uint64)
+        self._ck(self.lib.zk_diag_fq12_dev(self.h, op, _ptr(cases), _ptr(out), cases.shape[0]))
+        return out
+
 
 class Bases:
     def __init__(self, ctx: Context, h, group: int, owned: bool = True):
@@ -942,7 +974,102 @@ class ProvingKey:
         self.ctx._ck(self.ctx.lib.zk_pk_vk_g2(self.h, which, _ptr(out)))
         return out
 
+    def verify_host(self, inputs_mont, proof: bytes) -> bool:
+        """Groth16::verify of one proof through the host arithmetic, on this key's verifying-key parts."""
+        return groth16_verify_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont, proof)
+
     def free(self):
         if self.h:
             self.ctx.lib.zk_pk_free(self.ctx.h, self.h)
             self.h = None
+
+
+# ---- the pairing's host forms: the same arithmetic compiled for the host, no device and no Context ----
+def _pairing_args(p, q, pairs):
+    p = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 12)
+    q = np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 24)
+    if pairs < 1 or p.shape[0] != q.shape[0] or p.shape[0] == 0 or p.shape[0] % pairs:
+        raise ValueError("pairing_products: need as many G1 as G2 points, a positive multiple of `pairs`")
+    return p, q, p.shape[0] // pairs
+
+
+def _ck_host(rc: int, what: str):
+    if rc != _lib.ZK_OK:
+        raise ZkError("%s failed (%d)" % (what, rc))
+
+
+def gt_exponent_multiple() -> int:
+    """c of the GT value miller_loop^(c (q^12 - 1) / r) (ZK_GT_EXPONENT_MULTIPLE)."""
+    return _lib.load().zk_gt_exponent_multiple()
+
+
+def pairing_products_host(p: np.ndarray, q: np.ndarray, pairs: int = 1) -> np.ndarray:
+    p, q, count = _pairing_args(p, q, pairs)
+    out = np.zeros((count, 72), dtype=np.uint64)
+    _ck_host(_lib.load().zk_pairing_products_host(_ptr(p), _ptr(q), pairs, count, _ptr(out)), "zk_pairing_products_host")
+    return out
+
+
+def gt_is_one(a: np.ndarray) -> bool:
+    return bool(_lib.load().zk_gt_is_one(_ptr(np.ascontiguousarray(a, dtype=np.uint64))))
+
+
+def gt_eq(a: np.ndarray, b: np.ndarray) -> bool:
+    return bool(_lib.load().zk_gt_eq(_ptr(np.ascontiguousarray(a, dtype=np.uint64)), _ptr(np.ascontiguousarray(b, dtype=np.uint64))))
+
+
+def gt_mul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    out = np.zeros(72, dtype=np.uint64)
+    _ck_host(_lib.load().zk_gt_mul(_ptr(np.ascontiguousarray(a, dtype=np.uint64)), _ptr(np.ascontiguousarray(b, dtype=np.uint64)), _ptr(out)), "zk_gt_mul")
+    return out
+
+
+def gt_to_w_basis(gt: np.ndarray) -> list:
+    """A GT value (72 uint64: tower order) as the 12 canonical coefficients of 1, w, ... w^11 over Fq (w^12 = -5): the Fq component
+    h of c[i].c[j] is the coefficient of w^(2 j + i + 6 h)."""
+    from . import convert as cv
+    row = np.asarray(gt, dtype=np.uint64).reshape(72)
+    out = [0] * 12
+    for i in range(2):
+        for j in range(3):
+            for h in range(2):
+                out[2 * j + i + 6 * h] = cv._fq_at(row, 2 * (3 * i + j) + h)
+    return out
+
+
+def gt_from_w_basis(coeffs) -> np.ndarray:
+    from . import convert as cv
+    out = np.zeros(72, dtype=np.uint64)
+    for i in range(2):
+        for j in range(3):
+            for h in range(2):
+                m = cv.fq_to_mont_int(coeffs[2 * j + i + 6 * h])
+                for k in range(6):
+                    out[6 * (2 * (3 * i + j) + h) + k] = (m >> (64 * k)) & ((1 << 64) - 1)
+    return out
+
+
+def diag_fq12_host(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    cases = np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.uint64)
+    out = np.zeros((cases.shape[0], 72), dtype=np.uint64)
+    _ck_host(_lib.load().zk_diag_fq12_host(op, _ptr(cases), _ptr(out), cases.shape[0]), "zk_diag_fq12_host")
+    return out
+
+
+def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes) -> bool:
+    """Groth16::verify of one proof through the host arithmetic, on a host view of the VerifyingKey (points as uint64 arrays in the
+    ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery."""
+    vk = _lib.VkHost()
+    abc = np.ascontiguousarray(gamma_abc_g1, dtype=np.uint64).reshape(-1, 12)
+    for field, arr, n in (("alpha_g1", alpha_g1, 12), ("beta_g2", beta_g2, 24), ("gamma_g2", gamma_g2, 24), ("delta_g2", delta_g2, 24)):
+        arr = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1)
+        assert arr.size == n
+        C.memmove(C.addressof(getattr(vk, field)), arr.ctypes.data, n * 8)
+    vk.gamma_abc_g1, vk.gamma_abc_len = abc.ctypes.data, abc.shape[0]
+    inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(-1, 4)
+    if len(proof) != 192:
+        raise ValueError("a proof is 192 bytes")
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    ok = C.c_int(0)
+    _ck_host(_lib.load().zk_groth16_verify_host(C.byref(vk), _ptr(inp), inp.shape[0], _ptr(buf), C.byref(ok)), "zk_groth16_verify_host")
+    return bool(ok.value)

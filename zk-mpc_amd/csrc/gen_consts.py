@@ -32,6 +32,11 @@ FQ_QNR = 15                  # a quadratic non-residue of Fq (checked below); an
 assert pow(FQ_QNR, (Q_MOD - 1) // 2, Q_MOD) == Q_MOD - 1 and (Q_MOD - 1) % (1 << FQ_TWO_ADICITY) == 0 and ((Q_MOD - 1) >> FQ_TWO_ADICITY) % 2 == 1
 FR_GENERATOR = 22
 FR_TWO_ADICITY = 47
+BLS_X = 0x8508C00000000001   # the curve's seed x (curves/mod.rs:16-19); r = x^4 - x^2 + 1, q = (x - 1)^2 r / 3 + x
+assert R_MOD == BLS_X ** 4 - BLS_X ** 2 + 1 and 3 * Q_MOD == (BLS_X - 1) ** 2 * R_MOD + 3 * BLS_X
+# the hard part of the final exponentiation (pairing.cuh) runs the chain of Hayashida, Hayasaka, Teruya, "Efficient final
+# exponentiation via cyclotomic structure for pairings over families of elliptic curves" (eprint 2020/875), which yields the CUBE
+assert 3 * ((Q_MOD ** 4 - Q_MOD ** 2 + 1) // R_MOD) == (BLS_X - 1) ** 2 * (BLS_X + Q_MOD) * (BLS_X ** 2 + Q_MOD ** 2 - 1) + 3
 B = 29
 
 
@@ -127,6 +132,23 @@ def fq753_lazy():
     return "\n".join(out)
 
 
+def fq12_frobenius():
+    """Fq12 = Fq2[w]/(w^6 - u), u^2 = -5 (pairing.cuh): the q^j-power map sends a_k w^k to conj^j(a_k) u^(k (q^j - 1) / 6) w^k, and
+    u^(k (q^j - 1) / 6) = (-5)^(k (q^j - 1) / 12) lies in Fq because 12 divides q - 1.  FQ12_FROB[j - 1][k], internal form."""
+    assert (Q_MOD - 1) % 12 == 0
+    RI = 1 << (B * 14)
+    out = ["static constexpr uint32_t FQ12_FROB[3][6][13] = {   // (-5)^(k (q^j - 1) / 12), j = 1..3, k = 0..5; internal form"]
+    for j in (1, 2, 3):
+        rows = []
+        for k in range(6):
+            g = pow(Q_MOD - 5, k * (Q_MOD ** j - 1) // 12, Q_MOD)
+            rows.append("        {%s}," % ", ".join("0x%08xu" % l for l in limbs((g * RI) % Q_MOD, 13)))
+        out += ["    {"] + rows + ["    },"]
+    out.append("};")
+    out.append("static constexpr uint64_t BLS12_X = 0x%016xull;   // the curve's seed (curves/mod.rs:16-19)" % BLS_X)
+    return "\n".join(out)
+
+
 def main():
     two_adic_root = pow(FR_GENERATOR, (R_MOD - 1) >> FR_TWO_ADICITY, R_MOD)
     print("// GENERATED by gen_consts.py -- do not edit.  29-bit little-endian limbs.")
@@ -158,6 +180,7 @@ def main():
         ("TS_T_MINUS1_DIV2", (((Q_MOD - 1) >> FQ_TWO_ADICITY) - 1) // 2),   # Tonelli-Shanks exponent (plain bits)
     ]))
     print("static constexpr int FQ_TWO_ADICITY = %d;" % FQ_TWO_ADICITY)
+    print(fq12_frobenius())
     root753 = pow(Q753_GENERATOR, (Q753_MOD - 1) >> Q753_TWO_ADICITY, Q753_MOD)
     assert pow(root753, 1 << (Q753_TWO_ADICITY - 1), Q753_MOD) == Q753_MOD - 1
     print(field("Fq753Params", Q753_MOD, 26, 24, internal=[

@@ -21,6 +21,7 @@
 #include <functional>
 #include <future>
 #include <memory>
+#include <mutex>
 #include <vector>
 
 struct zk_r1cs {
@@ -48,6 +49,11 @@ struct zk_pk {
     bool points_in_subgroup = false;
     zk::Affine<zk::G1Field> alpha_g1, beta_g1, delta_g1, a0, b0_g1;
     zk::Affine<zk::G2Field> beta_g2, delta_g2, gamma_g2, b0_g2;
+    // the verifier's constant e(alpha, beta) (pairing.hip), computed by the first verification of this key: the GT value as the
+    // finish kernel compares it (12 Fq, internal form, packed)
+    mutable std::mutex e_alpha_beta_mu;
+    mutable bool have_e_alpha_beta = false;
+    mutable uint32_t e_alpha_beta[144];
 };
 
 // A sort of z[1..] (shared by the B-in-G2 / A / B-in-G1 / L jobs) enqueued ahead of the MSMs: the collaborative prover

@@ -1,6 +1,7 @@
 // internal.hpp -- declarations shared between the translation units of libzkmpc_hip.
 #pragma once
 #include "ctx.hpp"
+#include "ec.cuh"
 #include <stddef.h>
 #include <stdint.h>
 #include <atomic>
@@ -207,6 +208,12 @@ int zk_msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count, h
 struct ZkEarlyMsm;
 int zk_msm_early_begin(zk_ctx* ctx, int count, const zk_bases* bases, const size_t* base_offsets, const void* scalars_dev, size_t len, ZkEarlyMsm** out);
 int zk_msm_early_finish(zk_ctx* ctx, ZkEarlyMsm* em, void* const* outs);      // outs = NULL: abandon (waits for its kernels); deletes the handle
+
+// serialize.hip: GroupAffine::deserialize of n compressed points that are on the device already (no subgroup check), table form out;
+// bad_dev: one word, set if any x is off the curve; bad_each_dev (or NULL): one word per point.  And one point on the host.
+int zk_decompress_launch(zk_ctx* ctx, int group, const uint32_t* in_dev, size_t n, uint32_t* out_dev, uint32_t* bad_dev, uint32_t* bad_each_dev);
+bool zk_host_decompress_g1(const uint8_t in[48], zk::Affine<zk::G1Field>* out);
+bool zk_host_decompress_g2(const uint8_t in[96], zk::Affine<zk::G2Field>* out);
 
 // msm_sort.hip: the bucket sort (msm_digits.cuh declares its interface)
 

@@ -10,20 +10,21 @@
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "internal.hpp"
+#include <string.h>
 
 using namespace zk;
 
 namespace {
 
 // canonical limbs > (p - 1) / 2, i.e. y > -y for y != 0
-__device__ __forceinline__ bool fq_gt_half(const Fq& c) {
+__host__ __device__ __forceinline__ bool fq_gt_half(const Fq& c) {
     int32_t borrow = 0;
 #pragma unroll
     for (int k = 0; k < FqParams::L; k++) borrow = ((int32_t)FqParams::HALF[k] - (int32_t)c.l[k] + borrow) >> 29;
     return borrow < 0;
 }
 
-__device__ __forceinline__ void fq_words(const Fq& internal, uint32_t w[12], Fq* canon_out = nullptr) {
+__host__ __device__ __forceinline__ void fq_words(const Fq& internal, uint32_t w[12], Fq* canon_out = nullptr) {
     Fq c = fp_int_to_canon<FqParams>(internal);
     fp_pack<FqParams>(w, c);
     if (canon_out) *canon_out = c;
@@ -32,28 +33,28 @@ __device__ __forceinline__ void fq_words(const Fq& internal, uint32_t w[12], Fq*
 template <class F> struct Ser;
 template <> struct Ser<G1Field> {
     static constexpr int FW = 12;   // words per base-field element
-    __device__ static void words(const Fq& a, uint32_t* w) { fq_words(a, w); }
-    __device__ static bool gt_neg(const Fq& y) { return fq_gt_half(fp_int_to_canon<FqParams>(y)); }
-    __device__ static void one(uint32_t* w) { for (int i = 0; i < 12; i++) w[i] = 0; w[0] = 1; }
-    __device__ static Fq from_words(const uint32_t* w) { return fp_canon_to_int<FqParams>(fp_unpack<FqParams>(w)); }
+    __host__ __device__ static void words(const Fq& a, uint32_t* w) { fq_words(a, w); }
+    __host__ __device__ static bool gt_neg(const Fq& y) { return fq_gt_half(fp_int_to_canon<FqParams>(y)); }
+    __host__ __device__ static void one(uint32_t* w) { for (int i = 0; i < 12; i++) w[i] = 0; w[0] = 1; }
+    __host__ __device__ static Fq from_words(const uint32_t* w) { return fp_canon_to_int<FqParams>(fp_unpack<FqParams>(w)); }
 };
 template <> struct Ser<G2Field> {
     static constexpr int FW = 24;
-    __device__ static void words(const Fq2& a, uint32_t* w) { fq_words(a.c0, w); fq_words(a.c1, w + 12); }
-    __device__ static bool gt_neg(const Fq2& y) {
+    __host__ __device__ static void words(const Fq2& a, uint32_t* w) { fq_words(a.c0, w); fq_words(a.c1, w + 12); }
+    __host__ __device__ static bool gt_neg(const Fq2& y) {
         if (!fp_is_zero<FqParams>(y.c1)) return fq_gt_half(fp_int_to_canon<FqParams>(y.c1));
         return fq_gt_half(fp_int_to_canon<FqParams>(y.c0));
     }
-    __device__ static void one(uint32_t* w) { for (int i = 0; i < 24; i++) w[i] = 0; w[0] = 1; }
-    __device__ static Fq2 from_words(const uint32_t* w) {
+    __host__ __device__ static void one(uint32_t* w) { for (int i = 0; i < 24; i++) w[i] = 0; w[0] = 1; }
+    __host__ __device__ static Fq2 from_words(const uint32_t* w) {
         return Fq2{fp_canon_to_int<FqParams>(fp_unpack<FqParams>(w)), fp_canon_to_int<FqParams>(fp_unpack<FqParams>(w + 12))};
     }
 };
 
 // curve coefficient b of y^2 = x^3 + b: 1 on G1 (curves/g1.rs:22-26), 1/u = (0, -1/5) on the twist (curves/g2.rs:28-35)
-template <class F> __device__ typename F::T curve_b();
-template <> __device__ Fq curve_b<G1Field>() { return fp_one<FqParams>(); }
-template <> __device__ Fq2 curve_b<G2Field>() { return Fq2{fp_zero<FqParams>(), fp_const<FqParams>(FqParams::G2_B_C1)}; }
+template <class F> __host__ __device__ typename F::T curve_b();
+template <> __host__ __device__ Fq curve_b<G1Field>() { return fp_one<FqParams>(); }
+template <> __host__ __device__ Fq2 curve_b<G2Field>() { return Fq2{fp_zero<FqParams>(), fp_const<FqParams>(FqParams::G2_B_C1)}; }
 
 constexpr uint32_t FLAG_POSITIVE = 1u << 31, FLAG_INFINITY = 1u << 30;   // bits 7 / 6 of the last byte
 
@@ -110,7 +111,7 @@ __global__ void __launch_bounds__(256) k_deserialize_uncompressed(const uint32_t
 // ---- square roots, for the compressed form (GroupAffine::get_point_from_x, short_weierstrass_jacobian.rs:110-125) ----
 // Which root comes out does not matter: the sign flag of the encoding selects between y and -y afterwards.
 // Fq: Tonelli-Shanks with q - 1 = 2^46 t (ff/src/fields/macros.rs sqrt_impl, eprint 2012/685 alg. 5); false = non-residue.
-__device__ bool fq_sqrt(const Fq& a, Fq* out) {
+__host__ __device__ bool fq_sqrt(const Fq& a, Fq* out) {
     if (fp_is_zero<FqParams>(a)) { *out = a; return true; }
     const Fq one = fp_one<FqParams>();
     uint32_t e[FqParams::L];
@@ -139,7 +140,7 @@ __device__ bool fq_sqrt(const Fq& a, Fq* out) {
     return fp_eq<FqParams>(fp_sqr<FqParams>(x), a);
 }
 // Fq2 = Fq[u]/(u^2 + 5): through the norm (ff/src/fields/models/quadratic_extension.rs sqrt).
-__device__ bool fq2_sqrt(const Fq2& a, Fq2* out) {
+__host__ __device__ bool fq2_sqrt(const Fq2& a, Fq2* out) {
     using B = FqField;
     Fq r;
     if (B::is_zero(a.c1)) {
@@ -162,33 +163,46 @@ __device__ bool fq2_sqrt(const Fq2& a, Fq2* out) {
     *out = y;
     return Fq2Field::eq(Fq2Field::sqr(y), a);
 }
-__device__ __forceinline__ bool field_sqrt(const Fq& a, Fq* out) { return fq_sqrt(a, out); }
-__device__ __forceinline__ bool field_sqrt(const Fq2& a, Fq2* out) { return fq2_sqrt(a, out); }
+__host__ __device__ __forceinline__ bool field_sqrt(const Fq& a, Fq* out) { return fq_sqrt(a, out); }
+__host__ __device__ __forceinline__ bool field_sqrt(const Fq2& a, Fq2* out) { return fq2_sqrt(a, out); }
 
 // Compressed points (GroupAffine::deserialize, :888-905 without the subgroup check): x with the flags in its last byte.
+// One point from its FW words; false (and the point at infinity) if x is not the abscissa of a curve point.
 template <class F>
-__global__ void __launch_bounds__(64) k_deserialize_compressed(const uint32_t* in, size_t n, uint32_t* bases, uint32_t* bad) {
+__host__ __device__ bool decompress_point(const uint32_t* in, Affine<F>* out) {
+    constexpr int FW = Ser<F>::FW;
+    uint32_t w[FW];
+#pragma unroll
+    for (int k = 0; k < FW; k++) w[k] = in[k];
+    const uint32_t flags = w[FW - 1] & (FLAG_POSITIVE | FLAG_INFINITY);
+    w[FW - 1] &= ~(FLAG_POSITIVE | FLAG_INFINITY);
+    Affine<F> p;
+    p.x = F::zero();
+    p.y = F::zero();
+    bool good = true;
+    if (!(flags & FLAG_INFINITY)) {
+        p.x = Ser<F>::from_words(w);
+        typename F::T y, rhs = F::add(F::mul(F::sqr(p.x), p.x), curve_b<F>());
+        if (!field_sqrt(rhs, &y)) {
+            good = false;
+            p.x = F::zero();
+        } else {
+            const bool positive = (flags & FLAG_POSITIVE) != 0;
+            p.y = (Ser<F>::gt_neg(y) != positive) ? F::neg(y) : y;
+        }
+    }
+    *out = p;
+    return good;
+}
+// bad: one word for the whole table; bad_each (optional): one word per point, for callers that answer per point
+template <class F>
+__global__ void __launch_bounds__(64) k_deserialize_compressed(const uint32_t* in, size_t n, uint32_t* bases, uint32_t* bad, uint32_t* bad_each) {
     constexpr int FW = Ser<F>::FW;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        uint32_t w[FW];
-#pragma unroll
-        for (int k = 0; k < FW; k++) w[k] = in[i * FW + k];
-        const uint32_t flags = w[FW - 1] & (FLAG_POSITIVE | FLAG_INFINITY);
-        w[FW - 1] &= ~(FLAG_POSITIVE | FLAG_INFINITY);
         Affine<F> p;
-        p.x = F::zero();
-        p.y = F::zero();
-        if (!(flags & FLAG_INFINITY)) {
-            p.x = Ser<F>::from_words(w);
-            typename F::T y, rhs = F::add(F::mul(F::sqr(p.x), p.x), curve_b<F>());
-            if (!field_sqrt(rhs, &y)) {
-                atomicOr(bad, 1u);                       // x is not the abscissa of a curve point
-                p.x = F::zero();
-            } else {
-                const bool positive = (flags & FLAG_POSITIVE) != 0;
-                p.y = (Ser<F>::gt_neg(y) != positive) ? F::neg(y) : y;
-            }
-        }
+        const bool good = decompress_point<F>(in + i * FW, &p);
+        if (!good) atomicOr(bad, 1u);
+        if (bad_each) bad_each[i] = good ? 0u : 1u;
         aff_store16<F>(bases, i, p);
     }
 }
@@ -224,7 +238,7 @@ int deserialize_t(zk_ctx* ctx, int group, const uint8_t* bytes, size_t n, int co
         ZK_HIP(ctx, hipMemcpyAsync(stage, bytes, in_bytes, hipMemcpyHostToDevice, ctx->stream));
         ZK_HIP(ctx, hipMemsetAsync(bad, 0, 4, ctx->stream));
         if (compressed)
-            hipLaunchKernelGGL(k_deserialize_compressed<F>, zk_grid(n, 64, 1 << 16), 64, 0, ctx->stream, (const uint32_t*)stage, n, b->dev, bad);
+            hipLaunchKernelGGL(k_deserialize_compressed<F>, zk_grid(n, 64, 1 << 16), 64, 0, ctx->stream, (const uint32_t*)stage, n, b->dev, bad, (uint32_t*)nullptr);
         else
             hipLaunchKernelGGL(k_deserialize_uncompressed<F>, zk_grid(n, 256), 256, 0, ctx->stream, (const uint32_t*)stage, n, b->dev, bad);
         ZK_HIP(ctx, hipGetLastError());
@@ -243,6 +257,26 @@ int deserialize_t(zk_ctx* ctx, int group, const uint8_t* bytes, size_t n, int co
 }
 
 }  // namespace
+
+// the decompression alone, for callers that hold the bytes on the device and answer per point (pairing.hip)
+int zk_decompress_launch(zk_ctx* ctx, int group, const uint32_t* in_dev, size_t n, uint32_t* out_dev, uint32_t* bad_dev, uint32_t* bad_each_dev) {
+    if (!n) return ZK_OK;
+    if (group == 2) hipLaunchKernelGGL(k_deserialize_compressed<G2Field>, zk_grid(n, 64, 1 << 16), 64, 0, ctx->stream, in_dev, n, out_dev, bad_dev, bad_each_dev);
+    else hipLaunchKernelGGL(k_deserialize_compressed<G1Field>, zk_grid(n, 64, 1 << 16), 64, 0, ctx->stream, in_dev, n, out_dev, bad_dev, bad_each_dev);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+// ... and one point on the host, through the same code
+bool zk_host_decompress_g1(const uint8_t in[48], Affine<G1Field>* out) {
+    uint32_t w[12];
+    memcpy(w, in, 48);
+    return decompress_point<G1Field>(w, out);
+}
+bool zk_host_decompress_g2(const uint8_t in[96], Affine<G2Field>* out) {
+    uint32_t w[24];
+    memcpy(w, in, 96);
+    return decompress_point<G2Field>(w, out);
+}
 
 extern "C" size_t zk_point_serialized_size(int group, int compressed) {
     return (size_t)(group == 2 ? 96 : 48) * (compressed ? 1 : 2);
