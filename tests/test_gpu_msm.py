@@ -1,4 +1,6 @@
 """GPU parity: variable-base MSM on G1 / G2 against the oracle (Pippenger restatement == naive)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -333,6 +335,48 @@ def test_msm_batch_pipeline(ctx):
         want = ctx.msm_dev(b, off, s, m)
         to_aff = cv.g1_projective_to_affine if b.group == 1 else cv.g2_projective_to_affine
         assert to_aff(got) == to_aff(want)
+
+
+def test_msm_batch_more_jobs_than_any_numbered_range(ctx):
+    """zk_msm_batch_dev with 26 jobs of 8 scalars over one 64-point G1 table, distinct scalar vectors: every job has a pinned result
+    buffer of its own whatever its position (26 is past both places, 16 and 24, where hand-numbered buffer keys used to meet those
+    of other uses); every sum equals the single MSM's."""
+    rng = O.Prng(2626)
+    sc = ctx.upload(cv.fr_to_mont([rng.fr() for _ in range(64)]))
+    b = ctx.fixed_base(sc.ptr, 64, 1, mont1(1))
+    vecs = [ctx.upload(cv.fr_to_mont([rng.fr() for _ in range(8)])) for _ in range(26)]
+    outs = ctx.msm_batch_dev([(b, 0, v.ptr, 8) for v in vecs])
+    for v, got in zip(vecs, outs):
+        assert cv.g1_projective_to_affine(got) == cv.g1_projective_to_affine(ctx.msm_dev(b, 0, v.ptr, 8))
+    for v in vecs:
+        v.free()
+    b.free(); sc.free()
+
+
+def test_msm_strided_grows_and_reuses_the_pinned_buffers(ctx):
+    """zk_msm_g1_strided on a padded {x, y, infinity} table of 64, then 4096, then 64 points on one context: a pinned buffer's first
+    allocation, its growth, and a smaller request served by the larger buffer.  Each sum equals zk_msm_g1 over the packed points."""
+    rs = np.random.RandomState(64)
+
+    def rand_mont(m):
+        a = rs.randint(0, 1 << 62, size=(m, 4), dtype=np.uint64)
+        a[:, 3] &= np.uint64((1 << 60) - 1)
+        return a
+    dk = ctx.upload(rand_mont(4096))
+    tab = ctx.fixed_base(dk.ptr, 4096, 1, mont1(1))
+    pts = np.ascontiguousarray(tab.download())
+    raw = np.zeros((4096, 104), dtype=np.uint8)                            # 96 bytes of coordinates, the flag, padding
+    raw[:, :96] = pts.view(np.uint8).reshape(4096, 96)
+    lay = (C.c_size_t * 4)(104, 0, 48, 96)
+    for n in (64, 4096, 64):
+        scal = rand_mont(n)
+        packed, padded = np.ascontiguousarray(pts[:n]), np.ascontiguousarray(raw[:n])
+        out = np.zeros(18, dtype=np.uint64)
+        ctx._ck(ctx.lib.zk_msm_g1_strided(ctx.h, padded.ctypes.data_as(C.c_void_p), n, lay, scal.ctypes.data_as(C.c_void_p), n,
+                                          out.ctypes.data_as(C.c_void_p)))
+        assert cv.g1_projective_to_affine(out) == cv.g1_projective_to_affine(ctx.multi_scalar_mul_g1(packed, scal))
+    tab.free(); dk.free()
+    ctx._ck(ctx.lib.zk_bases_cache_drop(ctx.h))
 
 
 def test_msm_batch_over_window_multiples_with_offsets(ctx):

@@ -127,6 +127,7 @@ class Builder {
     }
 };
 
+}  // namespace
 struct ZkBasesCache {
     std::vector<CacheEntry> e;
     size_t budget = 0;            // 0 until the first use: then a quarter of the device memory
@@ -142,6 +143,7 @@ struct ZkBasesCache {
     const zk_bases* leased = nullptr;     // the table the call in progress runs on: never evicted under it
     std::vector<char> fresh;              // host verification: the caller's table as it was packed for the comparison
 };
+namespace {
 
 constexpr size_t SAMPLE = 64;
 constexpr size_t MIN_CACHED = 256;        // smaller tables are cheaper to upload than to look up
@@ -234,7 +236,7 @@ size_t table_bytes(const zk_bases* b) {
 
 ZkBasesCache* cache_of(zk_ctx* ctx) {
     if (!ctx->bases_cache) ctx->bases_cache = new ZkBasesCache();
-    ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
+    ZkBasesCache* c = ctx->bases_cache;
     if (!c->configured && c->budget == 0) {
         size_t fr = 0, total = 0;
         c->budget = hipMemGetInfo(&fr, &total) == hipSuccess ? total / 4 : (size_t)16 << 30;
@@ -407,7 +409,7 @@ int upload_table(zk_ctx* ctx, const ZkHostTable& t, size_t n, uint32_t** raw_out
 }  // namespace
 
 void zk_bases_cache_free(zk_ctx* ctx) {
-    ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
+    ZkBasesCache* c = ctx->bases_cache;
     if (!c) return;
     while (!c->e.empty()) drop_entry(ctx, c, c->e.size() - 1);
     if (c->flag_dev) (void)hipFree(c->flag_dev);
@@ -418,11 +420,11 @@ void zk_bases_cache_free(zk_ctx* ctx) {
 
 ZkBasesLease::~ZkBasesLease() {
     if (temporary && b) free_table(ctx, nullptr, const_cast<zk_bases*>(b), raw_tmp);
-    if (ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache) if (c->leased == entry) c->leased = nullptr;
+    if (ZkBasesCache* c = ctx->bases_cache) if (c->leased == entry) c->leased = nullptr;
 }
 
 int zk_bases_cache_poll(zk_ctx* ctx) {
-    ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
+    ZkBasesCache* c = ctx->bases_cache;
     if (!c || (!c->builder.table() && c->e.empty())) return ZK_OK;
     return advance_builds(ctx, c, false);
 }
@@ -565,7 +567,7 @@ extern "C" int zk_bases_cache_trust(zk_ctx* ctx, int fingerprint_only) {
 extern "C" int zk_bases_cache_drop(zk_ctx* ctx) {
     ZK_API_BEGIN(ctx)
     if (!ctx) return ZK_ERR_ARG;
-    ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
+    ZkBasesCache* c = ctx->bases_cache;
     if (c) while (!c->e.empty()) drop_entry(ctx, c, c->e.size() - 1);
     return ZK_OK;
     ZK_API_END
@@ -574,7 +576,7 @@ extern "C" int zk_bases_cache_drop(zk_ctx* ctx) {
 extern "C" int zk_bases_cache_sync(zk_ctx* ctx) {
     ZK_API_BEGIN(ctx)
     if (!ctx) return ZK_ERR_ARG;
-    ZkBasesCache* c = (ZkBasesCache*)ctx->bases_cache;
+    ZkBasesCache* c = ctx->bases_cache;
     if (!c) return ZK_OK;
     return advance_builds(ctx, c, true);
     ZK_API_END

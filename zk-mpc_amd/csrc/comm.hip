@@ -72,8 +72,6 @@ const Rccl* rccl(std::string* err) {
     return &r;
 }
 
-struct Comm { ncclComm_t comm = nullptr; int rank = 0, n = 1; int pattern = 0; };   // pattern: zk_comm_set_open_pattern
-
 #define ZK_NCCL(ctx, R, expr)                                                                   \
     do {                                                                                          \
         ncclResult_t _e = (expr);                                                                 \
@@ -84,6 +82,8 @@ struct Comm { ncclComm_t comm = nullptr; int rank = 0, n = 1; int pattern = 0; }
     } while (0)
 
 }  // namespace
+
+struct ZkComm { ncclComm_t comm = nullptr; int rank = 0, n = 1; int pattern = 0; };   // pattern: zk_comm_set_open_pattern
 
 extern "C" int zk_comm_unique_id(uint8_t out[128]) {
     ZK_API_BEGIN_NOCTX
@@ -107,7 +107,7 @@ extern "C" int zk_comm_init(zk_ctx* ctx, const uint8_t id_bytes[128], int rank, 
     ZK_HIP(ctx, hipSetDevice(ctx->device));
     ncclUniqueId id;
     memcpy(&id, id_bytes, 128);
-    Comm* c = new Comm();
+    ZkComm* c = new ZkComm();
     c->rank = rank;
     c->n = n_parties;
     ncclResult_t e = R->CommInitRank(&c->comm, n_parties, id, rank);
@@ -125,7 +125,7 @@ extern "C" int zk_comm_destroy(zk_ctx* ctx) {
     ZK_API_BEGIN(ctx)
     if (!ctx) return ZK_ERR_ARG;
     if (!ctx->comm) return ZK_OK;
-    Comm* c = (Comm*)ctx->comm;
+    ZkComm* c = ctx->comm;
     const Rccl* R = rccl(nullptr);
     (void)hipStreamSynchronize(ctx->stream);
     if (R && R->CommDestroy && c->comm) (void)R->CommDestroy(c->comm);
@@ -154,7 +154,7 @@ extern "C" int zk_comm_info(zk_ctx* ctx, int* n_ranks, int* rank, int* device, i
         if (dladdr((void*)R->GetUniqueId, &di) && di.dli_fname) { strncpy(lib_path, di.dli_fname, lib_path_cap - 1); lib_path[lib_path_cap - 1] = 0; }
     }
     if (ctx->comm) {
-        Comm* c = (Comm*)ctx->comm;
+        ZkComm* c = ctx->comm;
         int v = c->n;
         if (n_ranks) { if (R->CommCount) ZK_NCCL(ctx, R, R->CommCount(c->comm, &v)); *n_ranks = v; }
         v = c->rank;
@@ -170,7 +170,7 @@ extern "C" int zk_comm_set_open_pattern(zk_ctx* ctx, int pattern) {
     ZK_API_BEGIN(ctx)
     if (!ctx || pattern < 0 || pattern > 2) return ZK_ERR_ARG;
     if (!ctx->comm) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_comm_set_open_pattern: no communicator (zk_comm_init)");
-    ((Comm*)ctx->comm)->pattern = pattern;
+    ctx->comm->pattern = pattern;
     return ZK_OK;
     ZK_API_END
 }
@@ -181,7 +181,7 @@ extern "C" int zk_open_sum_fr_dev(zk_ctx* ctx, const void* v_dev, size_t n, void
     if (!ctx || (n && (!v_dev || !out_dev))) return ZK_ERR_ARG;
     if (!ctx->comm) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_open_sum_fr_dev: no communicator (zk_comm_init)");
     if (n == 0) return ZK_OK;
-    Comm* c = (Comm*)ctx->comm;
+    ZkComm* c = ctx->comm;
     const Rccl* R = rccl(&ctx->last_error);
     if (!R) return ZK_ERR_STATE;
     const int P = c->n;

@@ -196,6 +196,19 @@ int zk_scratch(zk_ctx* ctx, const char* name, size_t bytes, void** out) {
     return ZK_OK;
 }
 
+int zk_pinned(zk_ctx* ctx, ZkPin key, size_t bytes, void** out, unsigned flags) {
+    auto& s = ctx->pinned[key];
+    if (s.bytes < bytes) {
+        if (s.p) (void)hipHostFree(s.p);
+        s.p = nullptr;                                     // (empty before the allocation: a failed one leaves nothing to free twice)
+        s.bytes = 0;
+        ZK_HIP(ctx, hipHostMalloc(&s.p, bytes, flags));
+        s.bytes = bytes;
+    }
+    *out = s.p;
+    return ZK_OK;
+}
+
 // ONE side stream per context for everything that runs beside the caller's own calls on the trait-shaped path -- the slices of the
 // table cache's builder (bases_cache.hip) and the MSMs started ahead (msm.hip) -- and no accumulate stream with it: with the default
 // four hardware queues every stream beyond {null, context, transfer ring, this one} shares a queue with one of them, and the

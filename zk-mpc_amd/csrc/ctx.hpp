@@ -29,7 +29,21 @@
 #define ZK_ERR_STATE -4
 #define ZK_ERR_MAC -5
 
-struct zk_domain;  // ntt.hip
+struct zk_domain;      // ntt.hip
+struct ZkComm;         // comm.hip
+struct ZkXfer;         // hostxfer.hip
+struct ZkXferSmall;    // hostxfer.hip
+struct ZkBasesCache;   // bases_cache.hip
+struct ZkMsmSpec;      // msm.hip
+struct ZkPresort;      // groth16_int.hpp
+
+// The name of one of a context's pinned host buffers (core.hip: zk_pinned): what it is for (a ZkPinKind of internal.hpp) and which
+// one of that kind.  Two uses cannot meet in one buffer whatever their indices are.
+struct ZkPin {
+    uint8_t kind;
+    uint32_t idx;
+    bool operator<(const ZkPin& o) const { return kind != o.kind ? kind < o.kind : idx < o.idx; }
+};
 
 // The context's host helper threads (window Horner chains, the O(1) scalar multiplications of a proof, Marlin's blinding
 // terms: ~20 short tasks per proof).  Workers are created on demand and then kept: a task is queued only when an idle worker
@@ -126,9 +140,9 @@ struct zk_ctx {
     // grow-only scratch arena: named slots, each re-used across calls (no hipMalloc on the hot path)
     struct Slot { void* p = nullptr; size_t bytes = 0; };
     std::map<std::string, Slot> slots;
-    std::map<int, Slot> pinned;     // pinned host staging per MSM slot
+    std::map<ZkPin, Slot> pinned;   // pinned host staging: grown by zk_pinned alone, freed by zk_ctx_destroy alone
     std::map<uint32_t, zk_domain*> domains;  // keyed by log2(size)
-    std::map<std::string, int> flags;         // one-time per-context setup markers
+    bool lds_attr_done[8] = {};               // one-time per-context kernel attributes, by ZkLdsAttr (internal.hpp)
     // core.hip: zk_graph_run -- a launch-bound sequence (the ~13 launches of a bucket sort) replayed as one captured graph.  Key = a
     // digest of everything the launches depend on, `scratch_gen` included (it moves whenever a scratch slot is allocated anew: every
     // graph that baked the old addresses in stops matching).
@@ -136,12 +150,13 @@ struct zk_ctx {
     std::map<std::string, GraphEntry> graphs;
     uint64_t scratch_gen = 0;
     uint64_t graphs_gen = 0;                  // the generation the entries of `graphs` were swept for
-    void* comm = nullptr;                     // RCCL communicator of this party (comm.hip), created by zk_comm_init
-    void* xfer = nullptr;                     // hostxfer.hip: the page-locked ring host slices travel through (ZkXfer)
-    void* xfer_small = nullptr;               // hostxfer.hip: rotating page-locked slots for transfers below 128 KiB
-    void* bases_cache = nullptr;              // bases_cache.hip: resident copies of host base slices seen by zk_msm_g1 / _g2 (ZkBasesCache)
-    void* msm_spec = nullptr;                 // msm.hip: MSMs over the tables a caller asks for next with the same scalars, started ahead (ZkMsmSpec)
-    void* presort = nullptr;                  // groth16_pipeline.hip: a sort of z[1..] enqueued ahead of zk_groth16_msms_dev (ZkPresort)
+    // each owned by the file that defines its type and released by that file's zk_*_free (zk_ctx_destroy calls them, in its order)
+    ZkComm* comm = nullptr;                   // RCCL communicator of this party (comm.hip), created by zk_comm_init
+    ZkXfer* xfer = nullptr;                   // hostxfer.hip: the page-locked ring host slices travel through
+    ZkXferSmall* xfer_small = nullptr;        // hostxfer.hip: rotating page-locked slots for transfers below 128 KiB
+    ZkBasesCache* bases_cache = nullptr;      // bases_cache.hip: resident copies of host base slices seen by zk_msm_g1 / _g2
+    ZkMsmSpec* msm_spec = nullptr;            // msm.hip: MSMs over the tables a caller asks for next with the same scalars, started ahead
+    ZkPresort* presort = nullptr;             // groth16_pipeline.hip: a sort of z[1..] enqueued ahead of zk_groth16_msms_dev
     const void* next_z = nullptr;             // groth16_pipeline.hip: zk_groth16_hint_next_dev
     // groth16_prove.hip: zk_groth16_hint_next (host-slice form): the announced assignment is uploaded on its own stream into the
     // idle one of two device slots while the current proof runs; next_z_ready is recorded behind that copy
@@ -291,6 +306,9 @@ static inline auto zk_async(zk_ctx* ctx, Fn&& fn) -> ZkTask<decltype(fn())> {
 #define ZK_API_BEGIN_NOCTX return zk_api_guarded((zk_ctx*)nullptr, [&]() -> int {
 #define ZK_API_END });
 
+// The context's pinned host buffer `key`, grown to at least `bytes` (grow-only; contents are unspecified after a growth).  The only
+// place that allocates one; a failed allocation leaves the slot empty.
+int zk_pinned(zk_ctx* ctx, ZkPin key, size_t bytes, void** out, unsigned flags = hipHostMallocDefault);
 // Returns a device buffer of at least `bytes` bound to `name`; contents are unspecified.
 int zk_scratch(zk_ctx* ctx, const char* name, size_t bytes, void** out);
 // The same for a buffer whose users leave it all-zero behind them: it is zeroed when it is (re)allocated, never afterwards.

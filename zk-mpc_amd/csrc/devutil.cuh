@@ -24,6 +24,21 @@ __device__ __forceinline__ Fr fr_mul(const Fr& a, const Fr& b) { return fp_mul<F
 __device__ __forceinline__ Fr fr_add(const Fr& a, const Fr& b) { return fp_add<FrParams>(a, b); }
 __device__ __forceinline__ Fr fr_sub(const Fr& a, const Fr& b) { return fp_sub<FrParams>(a, b); }
 
+// ---- a field constant passed to a kernel by value (internal form: nine limbs) ----
+struct FrK { uint32_t l[9]; };
+__device__ __forceinline__ Fr frk(const FrK& k) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
+    return r;
+}
+inline FrK to_frk(const uint32_t* l) {
+    FrK k;
+    for (int i = 0; i < 9; i++) k.l[i] = l[i];
+    return k;
+}
+inline FrK to_frk(const Fr& a) { return to_frk(a.l); }
+
 // ---- packed points (internal form) via 16-byte loads; F::WORDS is a multiple of 4 ----
 template <class F>
 __device__ __forceinline__ typename F::T felt_load16(const uint32_t* w) {

@@ -57,10 +57,10 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
         }
     } drain{ctx};
     ZkMsmJob* const zj[4] = {&J[0], &J[1], &J[2], &J[3]};
-    ZK_TRY(T.sort_z(ctx, zj, s_sort, 8, cnt));                       // slots 8..11
+    ZK_TRY(T.sort_z(ctx, zj, s_sort, ZK_SLOT_G16_BATCH, cnt));
     if (!T.l_shared) ZK_TRY(zk_msm_enqueue_sort(ctx, &J[3], s_sort, nullptr));
     ZK_TRY(front());                                                 // the witness map on the context stream, beside the z sort
-    ZK_TRY(T.prepare(ctx, 4, &J[4], 12, cnt));
+    ZK_TRY(T.prepare(ctx, 4, &J[4], ZK_SLOT_G16_BATCH, cnt));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &J[4], ctx->stream, nullptr));
     // B in G2 (the long reduce chain) on the accumulate stream, the z jobs of G1 on the sort stream, H on the context stream
     ZK_TRY(zk_msm_enqueue_accum(ctx, &J[0], s_acc));

@@ -122,16 +122,16 @@ struct ZkG16Jobs {
         j[3] = l_shared ? Job{pk->l_pad, 1, z1, nvars} : Job{pk->l, 0, zw, r->nw};        // aux_assignment against l_query
         j[4] = {pk->h, 0, (const char*)h, std::min(pk->h->n, D)};        // min(len) rule (variable_base.rs:15-17): h_query has D-1 entries, h has D
     }
-    // job k into scratch slot `slot`: of one proof (multi = 0), or as a multi-vector job of `multi` >= 1 proofs (assignments m,
+    // job k into scratch slot slot0 + k: of one proof (multi = 0), or as a multi-vector job of `multi` >= 1 proofs (assignments m,
     // quotients D elements apart; a batch's last chunk may be one proof and is collected as a multi job all the same)
-    int prepare(zk_ctx* ctx, int k, ZkMsmJob* job, int slot, size_t multi = 0) const {
-        if (!multi) return zk_msm_prepare(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, slot);
-        return zk_msm_prepare_multi(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, k == 4 ? D : m, multi, slot);
+    int prepare(zk_ctx* ctx, int k, ZkMsmJob* job, ZkMsmSlot slot0, size_t multi = 0) const {
+        if (!multi) return zk_msm_prepare(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, slot0 + k);
+        return zk_msm_prepare_multi(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, k == 4 ? D : m, multi, slot0 + k);
     }
-    // The z jobs J[0..3] prepared (slots slot0..slot0+3) and their sorts enqueued on st: job 0 sorts, A borrows its sort, B in G1 and a
+    // The z jobs J[0..3] prepared and their sorts enqueued on st: job 0 sorts, A borrows its sort, B in G1 and a
     // shared L borrow from the lender.  have0: J[0] is prepared and sorted already.  An L of its own is sorted by the caller.
-    int sort_z(zk_ctx* ctx, ZkMsmJob* const* J, hipStream_t st, int slot0, size_t multi = 0, bool have0 = false) const {
-        for (int k = have0 ? 1 : 0; k < 4; k++) ZK_TRY(prepare(ctx, k, J[k], slot0 + k, multi));
+    int sort_z(zk_ctx* ctx, ZkMsmJob* const* J, hipStream_t st, ZkMsmSlot slot0, size_t multi = 0, bool have0 = false) const {
+        for (int k = have0 ? 1 : 0; k < 4; k++) ZK_TRY(prepare(ctx, k, J[k], slot0, multi));
         if (!have0) ZK_TRY(zk_msm_enqueue_sort(ctx, J[0], st, nullptr));
         ZK_TRY(zk_msm_enqueue_sort(ctx, J[1], st, J[0]));
         // (the G2 table may carry windows of another width than the G1 tables: then A sorts for itself and the other G1 jobs borrow A's)

@@ -81,14 +81,7 @@ static int prove_multi(zk_ctx* ctx0, zk_ctx* const* ctxs, const zk_pk* const* pk
     for (int d = 1; d < n_ctx && !z_stage; d++) {
         int peer = 1;
         if (ctxs[d]->device != ctx0->device && (hipDeviceCanAccessPeer(&peer, ctxs[d]->device, ctx0->device) != hipSuccess || !peer)) {
-            auto& pin = ctx0->pinned[-2];
-            if (pin.bytes < m * 32) {
-                if (pin.p) (void)hipHostFree(pin.p);
-                pin.p = nullptr; pin.bytes = 0;
-                ZK_HIP(ctx0, hipHostMalloc(&pin.p, m * 32, hipHostMallocPortable));
-                pin.bytes = m * 32;
-            }
-            z_stage = pin.p;
+            ZK_TRY(zk_pinned(ctx0, {ZK_PIN_MULTI_Z, 0}, m * 32, &z_stage, hipHostMallocPortable));
             ZK_HIP(ctx0, hipMemcpyAsync(z_stage, z_dev0, m * 32, hipMemcpyDeviceToHost, ctx0->stream));
             ZK_HIP(ctx0, hipStreamSynchronize(ctx0->stream));
         }

@@ -8,7 +8,7 @@ using namespace zk;
 
 void zk_presort_free(zk_ctx* ctx) {
     if (!ctx || !ctx->presort) return;
-    ZkPresort* p = (ZkPresort*)ctx->presort;
+    ZkPresort* p = ctx->presort;
     ctx->presort = nullptr;
     if (ctx->aux.size()) (void)hipStreamSynchronize(ctx->aux[0]);   // its kernels write the job's scratch slot
     if (p->front || p->begun) {                                     // these run on the accumulate and context streams as well
@@ -79,7 +79,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     ZkMsmJob* J[5] = {&own[0], &own[1], &own[2], &own[3], &own[4]};
     // the sort of z[1..] may already be running (zk_groth16_msms_presort_dev, enqueued by the collaborative prover before
     // its Beaver open): take it over as job 0's
-    ZkPresort* pre = (ZkPresort*)ctx->presort;
+    ZkPresort* pre = ctx->presort;
     ctx->presort = nullptr;
     std::unique_ptr<ZkPresort> pre_owner(pre);
     // (a begun set can only be taken over whole, by the call that brings h: anything else drains and drops it below -- its jobs
@@ -101,7 +101,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     // waiting for it here would hold the sort stream -- and the G2 reduce chain on it -- until the H-sort is through.)
     if (!fronted) ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0, 0));
     const bool have_z_jobs = begun || chained;
-    int rc = have_z_jobs ? ZK_OK : T.sort_z(ctx, J, s_sort, 1, 0, presorted);       // the z jobs: slots 1..4, one sort of z[1..]
+    int rc = have_z_jobs ? ZK_OK : T.sort_z(ctx, J, s_sort, ZK_SLOT_G16, 0, presorted);       // the z jobs: one sort of z[1..]
     ZkPhaseTimer tm(ctx);
     // the first accumulate kernel is gated on the witness map, which would otherwise be starved beside it (un-gating it: within
     // the noise of consecutive runs, round 3)
@@ -114,7 +114,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
             rc = zk_groth16_witness_map_dev(ctx, r, z, h_scratch);
             tm.end();
         }
-        if (rc == ZK_OK) rc = T.prepare(ctx, 4, J[4], 5);
+        if (rc == ZK_OK) rc = T.prepare(ctx, 4, J[4], ZK_SLOT_G16);
         if (rc == ZK_OK) {
             ZK_HIP(ctx, hipEventRecord(e1, ctx->stream));
             ZK_HIP(ctx, hipStreamWaitEvent(s_acc, e1, 0));
@@ -180,7 +180,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         for (int k = 0; k < 4; k++)
             if (J[k]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(s_acc, J[k]->reduce_done, 0));
         const ZkG16Jobs N(pk, r, zn, h_scratch);
-        rc = N.prepare(ctx, 0, &nf->job, 1);
+        rc = N.prepare(ctx, 0, &nf->job, ZK_SLOT_G16);
         if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->job, s_acc, nullptr);
         if (rc == ZK_OK) rc = zk_groth16_witness_map_dev(ctx, r, zn, h_scratch);
         if (rc == ZK_OK) {
@@ -189,7 +189,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
             if (J[4]->accum_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->accum_done, 0));
             // H's own chain (slot 5: k_fold reads ctr / heavy there) may be on the other stream
             if (J[4]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->reduce_done, 0));
-            rc = N.prepare(ctx, 4, &nf->jobh, 5);
+            rc = N.prepare(ctx, 4, &nf->jobh, ZK_SLOT_G16);
             if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->jobh, ctx->stream, nullptr);
         }
         // A SMALL proof (its four G1 jobs one group): the next proof's whole device chain goes out as well -- accumulate launches and
@@ -199,10 +199,10 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         // chip used to wait).  The results land in the other pair of pinned buffers: this proof's are read below.
         if (rc == ZK_OK && grouped && ctx->chain_fronts) {
             const int par = (ctx->front_parity ^= 1);
-            nf->job.pin_key = 48 + par;
-            nf->j1.pin_key = 50 + par;                               // (the group's results travel in its first job's buffer)
+            nf->job.pin = {ZK_PIN_FRONT, (uint32_t)par};
+            nf->j1.pin = {ZK_PIN_FRONT_GROUP, (uint32_t)par};                         // (the group's results travel in its first job's buffer)
             ZkMsmJob* nz[4] = {&nf->job, &nf->j1, &nf->j2, &nf->j3};
-            rc = N.sort_z(ctx, nz, s_acc, 1, 0, true);               // (l_shared here: the z-sort above serves all four)
+            rc = N.sort_z(ctx, nz, s_acc, ZK_SLOT_G16, 0, true);             // (l_shared here: the z-sort above serves all four)
             ZkMsmJob* ng[4] = {&nf->j1, &nf->j2, &nf->j3, &nf->jobh};
             if (rc == ZK_OK && zk_msm_group_ok(ng, 4)) {
                 rc = zk_msm_enqueue_accum(ctx, &nf->job, s_acc);
@@ -286,7 +286,7 @@ extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const z
     std::unique_ptr<ZkPresort> p(new ZkPresort());
     p->pk = pk;
     p->z = z;
-    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr).prepare(ctx, 0, &p->job, 1));
+    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr).prepare(ctx, 0, &p->job, ZK_SLOT_G16));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &p->job, ctx->aux[0], nullptr));
     ctx->presort = p.release();
     return ZK_OK;
@@ -315,7 +315,7 @@ extern "C" int zk_groth16_msms_begin_dev(zk_ctx* ctx, const zk_pk* pk, const zk_
     p->pk = pk; p->z = z; p->r = r; p->begun = true;
     const ZkG16Jobs T(pk, r, z, nullptr);
     ZkMsmJob* J[4] = {&p->job, &p->j1, &p->j2, &p->j3};
-    int rc = T.sort_z(ctx, J, s_sort, 1);
+    int rc = T.sort_z(ctx, J, s_sort, ZK_SLOT_G16);
     if (rc == ZK_OK && !T.l_shared) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);
     for (int k = 0; k < 4 && rc == ZK_OK; k++) rc = zk_msm_enqueue_accum(ctx, J[k], s_acc);
     // only the G2 job's reduce chain here (sort stream); the G1 chains are enqueued by zk_groth16_msms_dev, which spreads them over

@@ -15,40 +15,11 @@ using namespace zk;
 // opened value is the reference's, and so are the 192 bytes.
 namespace {
 
-struct FrK { uint32_t l[9]; };
-__device__ __forceinline__ Fr frk(const FrK& k) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
-    return r;
-}
-FrK to_frk(const Fr& a) {
-    FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = a.l[i];
-    return k;
-}
-// the 256-bit word of a field element is below the modulus (is_valid, ff/src/fields/macros.rs:255-260): what arrives from a peer
-bool fr_abi_valid(const uint64_t l[4]) {
-    Fr m;
-    for (int i = 0; i < 9; i++) m.l[i] = FrParams::P[i];
-    uint64_t pm[4];
-    host_store_ext<FrParams>(pm, m);
-    for (int i = 3; i >= 0; i--) {
-        if (l[i] < pm[i]) return true;
-        if (l[i] > pm[i]) return false;
-    }
-    return false;
-}
-
 __global__ void __launch_bounds__(256) k_vec_add_const(const void* a, FrK k, void* out, size_t n) {
     const Fr kk = frk(k);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         fr_store(out, i, fr_add(fr_load(a, i), kk));
 }
-
-}  // namespace
-
-namespace {
 
 __global__ void __launch_bounds__(256) k_vec_neg(const void* a, void* out, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -200,7 +171,7 @@ int prove_shared_impl(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void
             uint64_t w[MW];
             memcpy(w, all.data() + (size_t)p * sizeof w, sizeof w);
             for (int k = 0; k < 2; k++) {
-                if (!fr_abi_valid(w + 4 * k)) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a non-canonical field element");
+                if (!zk_fr_words_valid(w + 4 * k)) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a non-canonical field element");
                 o.f[k] = fp_add<FrParams>(o.f[k], host_load_ext<FrParams>(w + 4 * k));
             }
             // points from a peer: canonical coordinates, on the curve; the malicious-security prover also checks the subgroup

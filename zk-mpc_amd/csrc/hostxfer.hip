@@ -134,6 +134,7 @@ class XferTeam {
     }
 };
 
+}  // namespace
 struct ZkXfer {
     char* ring = nullptr;
     hipStream_t st = nullptr;                     // the DMA stream (never the context stream: copies overlap nothing on it)
@@ -143,6 +144,7 @@ struct ZkXfer {
     std::atomic<uint32_t> filled[XF_NPIECE];      // upload: piece p of the round is in the ring
     std::atomic<int> err{(int)hipSuccess};
 };
+namespace {
 
 int xfer_get(zk_ctx* ctx, ZkXfer** out) {
     if (!ctx->xfer) {
@@ -159,7 +161,7 @@ int xfer_get(zk_ctx* ctx, ZkXfer** out) {
         ZK_HIP(ctx, hipEventCreateWithFlags(&x->fence, hipEventDisableTiming));
         x->team.reset(new XferTeam(threads, ctx->device));
     }
-    *out = (ZkXfer*)ctx->xfer;
+    *out = ctx->xfer;
     if (!(*out)->ring || !(*out)->fence || !(*out)->team) ZK_FAIL(ctx, ZK_ERR_STATE, "host transfer ring: not initialised (an earlier allocation failed)");
     return ZK_OK;
 }
@@ -184,12 +186,14 @@ int fence_out(zk_ctx* ctx, ZkXfer* x) {
 // 0.06 ms per 32 KB transform call, but on some boxes / allocator states 0.26 ms -- the runtime's own staging decisions; a copy into
 // our own slot and a DMA from it is the same every time.)
 constexpr unsigned XS_SLOTS = 16;
+}  // namespace
 struct ZkXferSmall {
     char* buf = nullptr;
     hipEvent_t ev[XS_SLOTS] = {};
     bool used[XS_SLOTS] = {};
     unsigned next = 0;
 };
+namespace {
 int small_get(zk_ctx* ctx, ZkXferSmall** out) {
     if (!ctx->xfer_small) {
         ZkXferSmall* x = new ZkXferSmall();
@@ -200,7 +204,7 @@ int small_get(zk_ctx* ctx, ZkXferSmall** out) {
         }
         for (unsigned i = 0; i < XS_SLOTS; i++) ZK_HIP(ctx, hipEventCreateWithFlags(&x->ev[i], hipEventDisableTiming));
     }
-    *out = (ZkXferSmall*)ctx->xfer_small;
+    *out = ctx->xfer_small;
     if (!(*out)->buf || !(*out)->ev[XS_SLOTS - 1]) ZK_FAIL(ctx, ZK_ERR_STATE, "host transfer slots: not initialised (an earlier allocation failed)");
     return ZK_OK;
 }
@@ -222,13 +226,13 @@ bool zk_host_is_pinned(const void* host) {
 }
 
 void zk_xfer_free(zk_ctx* ctx) {
-    if (ZkXferSmall* xs = (ZkXferSmall*)ctx->xfer_small) {
+    if (ZkXferSmall* xs = ctx->xfer_small) {
         for (auto& e : xs->ev) if (e) (void)hipEventDestroy(e);
         if (xs->buf) (void)hipHostFree(xs->buf);
         delete xs;
         ctx->xfer_small = nullptr;
     }
-    ZkXfer* x = (ZkXfer*)ctx->xfer;
+    ZkXfer* x = ctx->xfer;
     if (!x) return;
     x->team.reset();
     if (x->st) { (void)hipStreamSynchronize(x->st); (void)hipStreamDestroy(x->st); }

@@ -21,6 +21,10 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs_dev, int count, uint32_t 
 int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp = nullptr);
 int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
 
+// The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
+enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_COUNT };
+static_assert(ZK_LDS_COUNT <= sizeof(zk_ctx::lds_attr_done), "zk_ctx::lds_attr_done is too short");
+
 // rng.hip: four little-endian 64-bit words are a canonical field element (< r): what Fr::rand keeps and what a prover accepts from a peer
 bool zk_fr_words_valid(const uint64_t l[4]);
 
@@ -154,10 +158,47 @@ struct ZkPhaseTimer {
     void resolve();  // waits for the recorded end events (not for the stream) and accumulates into ctx->timers
 };
 
+// What a context's pinned host buffers are for (the kind of a ZkPin; ctx.hpp: zk_pinned).  idx says which one of the kind.
+enum ZkPinKind : uint8_t {
+    ZK_PIN_OF_SLOT = 0,       // (a ZkMsmJob's default, never a buffer: the job's results go to MSM_SLOT / MSM_GROUP of its scratch slot)
+    ZK_PIN_MSM_SLOT,          // idx = scratch slot: a job's reduce results
+    ZK_PIN_MSM_GROUP,         // idx = scratch slot of the group's first job: a group's results
+    ZK_PIN_BATCH_JOB,         // idx = position in a zk_msm_batch_dev call: the host reads them all at the end
+    ZK_PIN_AHEAD,             // idx = k of a speculative (msm.hip) or started-ahead (msm_batch.hip) MSM: see ZK_SLOT_AHEAD
+    ZK_PIN_FRONT,             // idx = parity: B in G2 of a chained front (groth16_pipeline.hip)
+    ZK_PIN_FRONT_GROUP,       // idx = parity: the G1 group of a chained front
+    ZK_PIN_MULTI_Z,           // groth16_multi.hip: the assignment staged for the other devices
+    ZK_PIN_STRIDED_UPLOAD,    // msm.hip: a strided host table gathered into the packed form
+    ZK_PIN_INV_TOTALS,        // poly.hip: the block totals of a batch inversion
+    ZK_PIN_ZERO_VERDICTS,     // vec_ops.hip: the verdicts of zk_fr_vec_is_zero_launch
+};
+
+// The MSM scratch slots: the `slot` of zk_msm_prepare names the "msm_*.<slot>" scratch buffers, and two jobs on one slot share every
+// sort and reduce buffer.  A range's users leave nothing in flight when they return unless it says so here.
+enum ZkMsmSlot : int {
+    ZK_SLOT_RUN = 0,          // (1) zk_msm_run and the host-slice calls' own job: synchronous, one at a time
+    // (5) the Groth16 pipeline: the z jobs and H (ZkG16Jobs: slot0 + k).  A presort / begun set / front may be in flight between two calls
+    // (ctx->presort).  zk_msm_batch_dev rotates its jobs over the first four of these and therefore drops a pending presort first.
+    ZK_SLOT_G16 = 1,
+    // (2) MSMs that run beside the caller's own calls: the speculation of the host-slice path (msm.hip) and the started-ahead MSMs of
+    // zk_marlin_prove (msm_batch.hip), in flight beside jobs of ZK_SLOT_RUN and of zk_msm_batch_dev.  The two share the slots and
+    // ZK_PIN_AHEAD because they never coexist: zk_msm_early_begin drops the speculation, nothing starts one until the prover has
+    // collected or abandoned its early jobs (only the host-slice entry points speculate; the prover calls none), and the
+    // speculation drops itself before its next start.
+    ZK_SLOT_AHEAD = 6,
+    // (5) the batch prover's five multi-vector jobs (groth16_batch.hip); zk_msm_multi_dev's one job takes the first: both synchronous
+    ZK_SLOT_G16_BATCH = 8,
+    ZK_SLOT_END = 13,
+};
+constexpr int ZK_SLOT_G16_COUNT = 5, ZK_SLOT_AHEAD_COUNT = 2;
+static_assert(ZK_SLOT_RUN + 1 <= ZK_SLOT_G16 && ZK_SLOT_G16 + ZK_SLOT_G16_COUNT <= ZK_SLOT_AHEAD &&
+              ZK_SLOT_AHEAD + ZK_SLOT_AHEAD_COUNT <= ZK_SLOT_G16_BATCH && ZK_SLOT_G16_BATCH + ZK_SLOT_G16_COUNT <= ZK_SLOT_END,
+              "the MSM scratch slot ranges overlap");
+
 // An MSM in flight (msm.hip): prepare -> enqueue_sort -> enqueue_accum -> enqueue_reduce -> finish.
 struct ZkMsmJob {
     int group = 1, slot = 0;
-    int pin_key = -1;                 // pinned result buffer (ctx->pinned key); -1: the slot's.  Jobs enqueued without a host wait in between need their own
+    ZkPin pin = {ZK_PIN_OF_SLOT, 0};  // pinned result buffer; OF_SLOT: the slot's.  Jobs enqueued without a host wait in between need their own
     size_t n = 0, max_segs = 0, max_heavy = 0;
     uint32_t c = 0, W = 0, NB = 0, seg = 0;
     uint16_t off[65] = {0};           // window w covers scalar bits [off[w], off[w+1])

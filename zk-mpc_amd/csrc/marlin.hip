@@ -16,18 +16,6 @@ using namespace zk;
 
 namespace {
 
-struct FrK { uint32_t l[9]; };
-__device__ __forceinline__ Fr frk(const FrK& k) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
-    return r;
-}
-FrK to_frk(const Fr& a) {
-    FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = a.l[i];
-    return k;
-}
 Fr host_int(const zk_fr* a) { return fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a->l)); }
 
 // out[i] = idx[i] == 0xFFFFFFFF ? 0 : src[idx[i]]

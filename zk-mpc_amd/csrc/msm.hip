@@ -912,9 +912,9 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     if (one_block) {
         // a small MSM over window multiples: the whole sort in one block (k_sort_small)
         const size_t lds = ((size_t)NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4;
-        if (!ctx->flags["sort_small_lds"]) {
+        if (!ctx->lds_attr_done[ZK_LDS_SORT_SMALL]) {
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_sort_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)SS_MAX_NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4)));
-            ctx->flags["sort_small_lds"] = 1;
+            ctx->lds_attr_done[ZK_LDS_SORT_SMALL] = true;
         }
         hipLaunchKernelGGL(k_sort_small, 1, SS_NT, lds, st, SortSmallArgs{job->scalars, (uint32_t)n, wo, W, NB, bias, seg, job->n_tab, job->tab_off, grp_base,
                            b.dig, b.sorted, b.desc, b.heavy, b.heavy2, b.order, ctr});
@@ -1045,14 +1045,8 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
     // pinned destination: a pageable one would make the "async" copy block the host until this job is done
-    auto& pin = ctx->pinned[job->pin_key >= 0 ? job->pin_key : job->slot];
-    const size_t bytes = std::max<size_t>((size_t)64 * 17, (size_t)job->Wb * job->nout) * XW * 4;
-    if (pin.bytes < bytes) {
-        if (pin.p) (void)hipHostFree(pin.p);
-        ZK_HIP(ctx, hipHostMalloc(&pin.p, bytes, hipHostMallocDefault));
-        pin.bytes = bytes;
-    }
-    job->hw = (uint32_t*)pin.p;
+    const ZkPin key = job->pin.kind != ZK_PIN_OF_SLOT ? job->pin : ZkPin{ZK_PIN_MSM_SLOT, (uint32_t)job->slot};
+    ZK_TRY(zk_pinned(ctx, key, std::max<size_t>((size_t)64 * 17, (size_t)job->Wb * job->nout) * XW * 4, (void**)&job->hw));
     ZK_HIP(ctx, hipMemcpyAsync(job->hw, b.bits, (size_t)job->Wb * job->nout * XW * 4, hipMemcpyDeviceToHost, st));
     // finish() waits for this event, not for the stream: later jobs' reduce phases may be queued behind on the same stream
     ZK_HIP(ctx, hipEventCreateWithFlags(&job->reduce_done, hipEventDisableTiming));
@@ -1100,9 +1094,9 @@ static int msm_enqueue_sort_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count,
     ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
     jobs[0]->timers.push_back(tm);
     tm->begin("msm_g1.sort");
-    if (!ctx->flags["sort_small_group_lds"]) {
+    if (!ctx->lds_attr_done[ZK_LDS_SORT_SMALL_GROUP]) {
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_sort_small_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)SS_MAX_NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4)));
-        ctx->flags["sort_small_group_lds"] = 1;
+        ctx->lds_attr_done[ZK_LDS_SORT_SMALL_GROUP] = true;
     }
     const size_t lds = ((size_t)nb_max + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4;
     hipLaunchKernelGGL(k_sort_small_group, count, SS_NT, lds, st, g);
@@ -1214,17 +1208,12 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     }
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
-    auto& pin = ctx->pinned[jobs[0]->pin_key >= 0 ? jobs[0]->pin_key : 32 + jobs[0]->slot];
-    const size_t bytes = (size_t)MSM_GROUP_MAX * 32 * XW * 4;
-    if (pin.bytes < bytes) {
-        if (pin.p) (void)hipHostFree(pin.p);
-        pin.p = nullptr; pin.bytes = 0;
-        ZK_HIP(ctx, hipHostMalloc(&pin.p, bytes, hipHostMallocDefault));
-        pin.bytes = bytes;
-    }
-    ZK_HIP(ctx, hipMemcpyAsync(pin.p, bits, (size_t)count * nout * XW * 4, hipMemcpyDeviceToHost, st));
+    const ZkPin key = jobs[0]->pin.kind != ZK_PIN_OF_SLOT ? jobs[0]->pin : ZkPin{ZK_PIN_MSM_GROUP, (uint32_t)jobs[0]->slot};
+    uint32_t* hw;
+    ZK_TRY(zk_pinned(ctx, key, (size_t)MSM_GROUP_MAX * 32 * XW * 4, (void**)&hw));
+    ZK_HIP(ctx, hipMemcpyAsync(hw, bits, (size_t)count * nout * XW * 4, hipMemcpyDeviceToHost, st));
     for (int k = 0; k < count; k++) {
-        jobs[k]->hw = (uint32_t*)pin.p + (size_t)k * nout * XW;
+        jobs[k]->hw = hw + (size_t)k * nout * XW;
         ZK_HIP(ctx, hipEventCreateWithFlags(&jobs[k]->reduce_done, hipEventDisableTiming));
         ZK_HIP(ctx, hipEventRecord(jobs[k]->reduce_done, st));
     }
@@ -1290,7 +1279,7 @@ int msm_finish_t(zk_ctx* ctx, ZkMsmJob* job, void* out_host) {
 template <class F>
 int msm_run_t(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars, size_t n, void* out_host) {
     ZkMsmJob job;
-    int rc = msm_prepare_t<F>(ctx, &job, bases, base_offset, scalars, n, 0);
+    int rc = msm_prepare_t<F>(ctx, &job, bases, base_offset, scalars, n, ZK_SLOT_RUN);
     if (rc == ZK_OK) rc = msm_enqueue_sort_t<F>(ctx, &job, ctx->stream, nullptr);
     if (rc == ZK_OK) rc = msm_enqueue_accum_t<F>(ctx, &job, ctx->stream);
     if (rc == ZK_OK) rc = msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream);
@@ -1358,7 +1347,7 @@ int msm_multi_run_t(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, cons
     for (size_t k0 = 0; k0 < count; k0 += chunk) {
         ZkMsmJob job;
         const size_t cnt = std::min(chunk, count - k0);
-        ZK_TRY(msm_prepare_multi_t<F>(ctx, &job, bases, base_offset, scalars + k0 * stride * 32, n, stride, cnt, 8));
+        ZK_TRY(msm_prepare_multi_t<F>(ctx, &job, bases, base_offset, scalars + k0 * stride * 32, n, stride, cnt, ZK_SLOT_G16_BATCH));
         ZK_TRY(msm_enqueue_sort_t<F>(ctx, &job, ctx->stream, nullptr));
         ZK_TRY(msm_enqueue_accum_t<F>(ctx, &job, ctx->stream));
         ZK_TRY(msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream));
@@ -1386,14 +1375,8 @@ int bases_upload_t(zk_ctx* ctx, const void* host, size_t n, int group, const ZkA
             if (layout->stride < 2 * FE || layout->off_x + FE > layout->stride || layout->off_y + FE > layout->stride ||
                 (layout->off_inf != SIZE_MAX && layout->off_inf >= layout->stride))
                 ZK_FAIL(ctx, ZK_ERR_ARG, "strided base table: the field offsets do not fit the stride");
-            auto& pin = ctx->pinned[-3];
-            if (pin.bytes < bytes) {
-                if (pin.p) (void)hipHostFree(pin.p);
-                pin.p = nullptr; pin.bytes = 0;
-                ZK_HIP(ctx, hipHostMalloc(&pin.p, bytes, hipHostMallocDefault));
-                pin.bytes = bytes;
-            }
-            char* dst = (char*)pin.p;
+            char* dst;
+            ZK_TRY(zk_pinned(ctx, {ZK_PIN_STRIDED_UPLOAD, 0}, bytes, (void**)&dst));
             const ZkAffineLayout lay = *layout;
             auto pack = [=](size_t lo, size_t hi) {
                 for (size_t i = lo; i < hi; i++) {
@@ -1454,11 +1437,12 @@ int bases_download_t(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n, vo
 // call's kernels, as they do in the resident prover.  What CAN be known: which table followed which with the same scalars last time.
 // So a context learns "after table T (scalars S) came table T' with the same S" (candidates by a fingerprint of 64 sampled scalars
 // taken from host memory), and when T is asked for again it also starts the MSMs over T' and T'' -- on a private copy of the scalars,
-// on the context's side stream, own scratch slots (6, 7) -- before it collects T's result.  The next call, if it names T' and
+// on the context's side stream, own scratch slots (ZK_SLOT_AHEAD) -- before it collects T's result.  The next call, if it names T' and
 // its scalars are WORD FOR WORD the ones the speculative job ran on (compared on the device), takes that result; anything else
 // drops the speculation (and after two wrong guesses for a table the pattern is forgotten).  Table hits are verified as always.
 // Nothing speculative is ever returned unverified; ZK_MSM_SPEC=0 switches the whole thing off (A/B).
 struct SpecJob { const zk_bases* table; ZkMsmJob job; };
+}  // namespace
 struct ZkMsmSpec {
     const zk_bases* last_table = nullptr;
     uint64_t last_fp = 0;
@@ -1486,13 +1470,14 @@ struct ZkMsmSpec {
     const zk_bases* late_table = nullptr;
     size_t late_n = 0;
 };
+namespace {
 static bool spec_enabled() {
     static const bool on = !(getenv("ZK_MSM_SPEC") && atoi(getenv("ZK_MSM_SPEC")) == 0);
     return on;
 }
 static ZkMsmSpec* spec_of(zk_ctx* ctx) {
     if (!ctx->msm_spec) ctx->msm_spec = new ZkMsmSpec();
-    return (ZkMsmSpec*)ctx->msm_spec;
+    return ctx->msm_spec;
 }
 __global__ void __launch_bounds__(256) k_scalars_differ(const uint4* a, const uint4* b, size_t n16, uint32_t* flag) {
     bool diff = false;
@@ -1558,8 +1543,8 @@ static int spec_start_tables(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* const* 
     for (int k = 0; k < cnt && rc == ZK_OK; k++) {
         std::unique_ptr<SpecJob> j(new SpecJob());
         j->table = next[k];
-        j->job.pin_key = 40 + k;
-        rc = zk_msm_prepare(ctx, &j->job, next[k], 0, copy, n, 6 + k);
+        j->job.pin = {ZK_PIN_AHEAD, (uint32_t)k};
+        rc = zk_msm_prepare(ctx, &j->job, next[k], 0, copy, n, ZK_SLOT_AHEAD + k);
         if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &j->job, s_sort, nullptr);
         if (rc == ZK_OK) rc = zk_msm_enqueue_accum(ctx, &j->job, s_sort);
         if (rc == ZK_OK) rc = zk_msm_enqueue_reduce(ctx, &j->job, s_sort);
@@ -1582,7 +1567,7 @@ int msm_table_run_t(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, c
     ZkBasesLease lease(ctx);
     ZK_TRY(zk_bases_cache_get(ctx, t, nu, &lease));
     const bool spec_ok = spec_enabled() && n_lanes == 1 && !lease.temporary && sfp != 0 && !ctx->profiling &&
-                         !(ctx->msm_spec && ((ZkMsmSpec*)ctx->msm_spec)->off);
+                         !(ctx->msm_spec && ctx->msm_spec->off);
     ZkMsmSpec* sp = spec_ok || ctx->msm_spec ? spec_of(ctx) : nullptr;
     int rc = ZK_OK;
     SpecJob* take = nullptr;
@@ -1646,7 +1631,7 @@ int msm_table_run_t(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, c
                 const bool small_call = lease.b->pre ? n * ((255 + lease.b->c_pre - 1) / lease.b->c_pre) <= ((size_t)1 << 22) : n <= ((size_t)1 << 17);
                 if (want_spec && small_call) (void)spec_start(ctx, sp, lease.b, scalars_dev[0], n, sfp);
                 ZkMsmJob job;
-                rc = msm_prepare_t<F>(ctx, &job, lease.b, 0, scalars_dev[0], n, 0);
+                rc = msm_prepare_t<F>(ctx, &job, lease.b, 0, scalars_dev[0], n, ZK_SLOT_RUN);
                 if (rc == ZK_OK) rc = msm_enqueue_sort_t<F>(ctx, &job, ctx->stream, nullptr);
                 if (rc == ZK_OK) rc = msm_enqueue_accum_t<F>(ctx, &job, ctx->stream);
                 if (rc == ZK_OK) rc = msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream);
@@ -1863,14 +1848,14 @@ int zk_msm_table_run(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, 
 }
 uint64_t zk_scalars_fingerprint(const void* fr, size_t n) { return scalars_fingerprint((const zk_fr*)fr, n); }
 void zk_msm_spec_drop(zk_ctx* ctx) {
-    if (ctx->msm_spec) spec_drop(ctx, (ZkMsmSpec*)ctx->msm_spec);
+    if (ctx->msm_spec) spec_drop(ctx, ctx->msm_spec);
 }
 // A transform of 2^log_n elements on a caller's host vector has been enqueued (its result is in `dev`, final on the context stream,
 // not yet on its way back): if the MSM that followed such a transform last time took the output as its scalars, that MSM starts
 // now -- under the download of the result and the upload of the scalars the call will bring (which are compared with `dev`'s copy
 // before the result is released, like every job started ahead).
 void zk_msm_spec_fft_begin(zk_ctx* ctx, const void* dev, size_t N, int kind) {
-    ZkMsmSpec* sp = (ZkMsmSpec*)ctx->msm_spec;
+    ZkMsmSpec* sp = ctx->msm_spec;
     if (sp) sp->late_dev = nullptr;                          // (a transform that failed between begin and end leaves nothing behind)
     if (!sp || sp->off || !spec_enabled() || ctx->profiling || !sp->jobs.empty()) return;
     auto it = sp->fft_succ.find(N * 4 + (size_t)kind);        // (of the seven transforms of a witness map only the last -- the one coset
@@ -1913,13 +1898,13 @@ extern "C" int zk_msm_speculate(zk_ctx* ctx, int on) {
 extern "C" int zk_msm_speculate_stats(zk_ctx* ctx, uint64_t out[3]) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !out) return ZK_ERR_ARG;
-    ZkMsmSpec* sp = (ZkMsmSpec*)ctx->msm_spec;
+    ZkMsmSpec* sp = ctx->msm_spec;
     out[0] = sp ? sp->started : 0; out[1] = sp ? sp->taken : 0; out[2] = sp ? sp->dropped : 0;
     return ZK_OK;
     ZK_API_END
 }
 void zk_msm_spec_forget(zk_ctx* ctx, const zk_bases* b) {
-    ZkMsmSpec* sp = (ZkMsmSpec*)ctx->msm_spec;
+    ZkMsmSpec* sp = ctx->msm_spec;
     if (!sp) return;
     for (auto& j : sp->jobs) if (j->table == b) { spec_drop(ctx, sp); break; }
     if (sp->last_table == b) sp->last_table = nullptr;
@@ -1930,7 +1915,7 @@ void zk_msm_spec_forget(zk_ctx* ctx, const zk_bases* b) {
     for (auto it = sp->succ.begin(); it != sp->succ.end();) it = it->second == b ? sp->succ.erase(it) : std::next(it);
 }
 void zk_msm_spec_free(zk_ctx* ctx) {
-    ZkMsmSpec* sp = (ZkMsmSpec*)ctx->msm_spec;
+    ZkMsmSpec* sp = ctx->msm_spec;
     if (!sp) return;
     spec_drop(ctx, sp);
     if (sp->flag_dev) (void)hipFree(sp->flag_dev);

@@ -23,7 +23,7 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
         if (off + lens[k] > bases[k]->n) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_msm_batch_dev: a job reads past its base table");
     }
     if (n_jobs == 0) return ZK_OK;
-    zk_presort_free(ctx);            // the batch rotates over the same scratch slots
+    zk_presort_free(ctx);            // the batch rotates over the pipeline's scratch slots (ZK_SLOT_G16)
     ZK_TRY(zk_prover_streams(ctx, 2));
     constexpr size_t SLOTS = 3;
     hipStream_t s_acc = ctx->acc_stream, s_sort = ctx->aux[0], s_sort2 = ctx->aux[1];
@@ -39,7 +39,7 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
     std::vector<ZkMsmJob> jobs(n_jobs);
     // G1 jobs of up to 2^23 digits over tables of window multiples (the commitments of a Marlin round up to |H| = 2^18: 4 - 7 jobs) go
     // in GROUPS of up to four: sorts one behind the other, then one accumulate launch and one launch per level
-    // of the reduce chain for the group (msm.hip: zk_msm_enqueue_*_group).  Group position p uses scratch slot 1 + p; a slot's
+    // of the reduce chain for the group (msm.hip: zk_msm_enqueue_*_group).  Group position p uses scratch slot ZK_SLOT_G16 + p; a slot's
     // next user waits for its previous user's chain.
     {
         bool small = n_jobs >= 2;
@@ -57,8 +57,8 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
                 for (size_t p = 0; p < cnt && rc == ZK_OK; p++) {
                     const size_t k = g0 + p, j = perm[k];
                     grp[p] = &jobs[k];
-                    jobs[k].pin_key = 16 + (int)k;
-                    rc = zk_msm_prepare(ctx, &jobs[k], bases[j], base_offsets ? base_offsets[j] : 0, scalars_dev[j], lens[j], 1 + (int)p);
+                    jobs[k].pin = {ZK_PIN_BATCH_JOB, (uint32_t)k};
+                    rc = zk_msm_prepare(ctx, &jobs[k], bases[j], base_offsets ? base_offsets[j] : 0, scalars_dev[j], lens[j], ZK_SLOT_G16 + (int)p);
                 }
                 if (rc != ZK_OK) break;
                 {   // a group that leaves most of the chip idle (<= 2^21 digits in all) lasts as long as its longest segment: the one job
@@ -119,8 +119,8 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
     int rc = ZK_OK;
     for (size_t k = 0; k < n_jobs && rc == ZK_OK; k++) {
         const size_t j = perm[k];
-        jobs[k].pin_key = 16 + (int)k;                   // its own pinned result buffer: the host reads them all at the end
-        rc = zk_msm_prepare(ctx, &jobs[k], bases[j], base_offsets ? base_offsets[j] : 0, scalars_dev[j], lens[j], 1 + (int)(k % SLOTS));
+        jobs[k].pin = {ZK_PIN_BATCH_JOB, (uint32_t)k};   // its own pinned result buffer: the host reads them all at the end
+        rc = zk_msm_prepare(ctx, &jobs[k], bases[j], base_offsets ? base_offsets[j] : 0, scalars_dev[j], lens[j], ZK_SLOT_G16 + (int)(k % SLOTS));
         // the slot's previous user must be through its reduce chain (k_fold reads the sort scratch, the chain the sums) before
         // this job's sort rewrites the slot; that job's accumulate kernel is then done as well
         if (rc == ZK_OK && k >= SLOTS && jobs[k - SLOTS].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(s_sort, jobs[k - SLOTS].reduce_done, 0));
@@ -161,7 +161,7 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
 // and accumulate streams, as soon as the coefficients are on the device; the context stream goes on with the round's polynomial
 // arithmetic (launch-bound for small proofs: the device is otherwise idle under it); the round's batch (zk_msm_batch_dev) then
 // carries fewer jobs -- without its longest one in round 1 -- and zk_msm_early_finish collects the result.  Own scratch slots
-// (6, 7) and pinned result buffers: nothing the batch rotates over.
+// (ZK_SLOT_AHEAD) and pinned result buffers: nothing the batch rotates over.
 struct ZkEarlyMsm {
     ZkMsmJob jobs[2];
     int count = 0;
@@ -171,7 +171,7 @@ int zk_msm_early_begin(zk_ctx* ctx, int count, const zk_bases* bases, const size
     if (count < 1 || count > 2 || !bases || !scalars_dev || !len) return ZK_ERR_ARG;
     for (int k = 0; k < count; k++)
         if (base_offsets[k] + len > bases->n) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_msm_early_begin: a job reads past its base table");
-    zk_msm_spec_drop(ctx);                                   // (msm.hip's speculative jobs use the same scratch slots)
+    zk_msm_spec_drop(ctx);                                   // (msm.hip's speculative jobs use the same scratch slots and pinned buffers)
     ZK_TRY(zk_prover_streams(ctx, 1));
     hipStream_t s_acc = ctx->acc_stream, s_sort = ctx->aux[0];
     hipEvent_t e0;
@@ -186,8 +186,8 @@ int zk_msm_early_begin(zk_ctx* ctx, int count, const zk_bases* bases, const size
     int rc = ZK_OK;
     for (int k = 0; k < count && rc == ZK_OK; k++) {
         ZkMsmJob& j = em->jobs[k];
-        j.pin_key = 40 + k;
-        rc = zk_msm_prepare(ctx, &j, bases, base_offsets[k], scalars_dev, len, 6 + k);
+        j.pin = {ZK_PIN_AHEAD, (uint32_t)k};
+        rc = zk_msm_prepare(ctx, &j, bases, base_offsets[k], scalars_dev, len, ZK_SLOT_AHEAD + k);
         if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &j, s_sort, k ? &em->jobs[0] : nullptr);
         if (rc == ZK_OK) rc = zk_msm_enqueue_accum(ctx, &j, s_acc);
         // the reduce chain: a LARGE job's behind its accumulate kernel on the sort stream (the batch's sorts queue behind it; the

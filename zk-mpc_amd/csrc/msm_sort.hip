@@ -417,13 +417,13 @@ int zk_msm_group(zk_ctx* ctx, hipStream_t st, int slot, const ZkGroupArgs& a) {
     ZK_TRY(zk_scratch(ctx, name("msm_ghist"), max_long * 2048 * 4, (void**)&ghist));       // per long bin: histogram[1024] | cursors[1024]
     uint32_t *bin_count = bins, *bin_start = bins + (g.NC + 1), *cursor = bins + 2 * (g.NC + 1), *bin_long = bins + 3 * (g.NC + 1),
              *hdr = bins + 4 * (g.NC + 1);
-    if (!ctx->flags["group_lds"]) {
+    if (!ctx->lds_attr_done[ZK_LDS_SORT_GROUP]) {
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (9 * G_TILE + G_MAXNC) * 4));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (9 * G_TILE + G_MAXNC) * 4));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_scatter_bins<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds_bytes(G_MAXNC)));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_scatter_bins<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds_bytes(G_MAXNC)));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_bins, hipFuncAttributeMaxDynamicSharedMemorySize, BINS_LDS_WORDS * 4));
-        ctx->flags["group_lds"] = 1;
+        ctx->lds_attr_done[ZK_LDS_SORT_GROUP] = true;
     }
     ZK_HIP(ctx, hipMemsetAsync(bin_count, 0, (size_t)(g.NC + 1) * 4, st));
     ZK_HIP(ctx, hipMemsetAsync(ghist, 0, max_long * 2048 * 4, st));

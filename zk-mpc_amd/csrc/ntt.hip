@@ -41,18 +41,6 @@ constexpr int LOGM_MAX = 10;
 constexpr int NTT_THREADS = 1024;   // (512 / 256 threads per tile, two / four butterflies per lane and stage: 2^20 in 131 / 144 us against 126: round 5)
 constexpr int TILE_ELEMS = 4096;  // x 36 B = 144 KiB of LDS
 
-struct FrK { uint32_t l[9]; };
-__device__ __forceinline__ Fr frk(const FrK& k) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
-    return r;
-}
-FrK to_frk(const Fr& a) {
-    FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = a.l[i];
-    return k;
-}
 
 // Table entries (twiddles, coset scales) are kept as their nine 29-bit limbs, 36 B each: a product takes them as they are
 // (re-slicing eight packed words into nine limbs was ~25 instructions in front of every twiddle product).
@@ -416,14 +404,14 @@ static int ntt_run(zk_ctx* ctx, void* const* bufs, uint32_t* sbase, size_t strid
         uint32_t passes = (log_n + LOGM_MAX - 1) / LOGM_MAX;
         uint32_t base = log_n / passes, extra = log_n % passes;
         uint32_t remaining = log_n;
-        if (!ctx->flags["ntt_lds"]) {
+        if (!ctx->lds_attr_done[ZK_LDS_NTT]) {
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<0, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<1, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<2, NttBatch>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<0, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<1, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass<2, NttStrided>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELEMS * 36));
-            ctx->flags["ntt_lds"] = 1;
+            ctx->lds_attr_done[ZK_LDS_NTT] = true;
         }
         // with two or more passes the first one writes a scratch buffer and the last one scatters from it back into the
         // caller's buffer in natural order; a single-pass transform (N <= 2^LOGM_MAX) keeps the separate permutation

@@ -30,18 +30,6 @@ namespace {
 
 constexpr int INV_CH = 32;   // batch-inversion chunk per thread
 
-struct FrK { uint32_t l[9]; };
-__device__ __forceinline__ Fr frk(const FrK& k) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
-    return r;
-}
-FrK to_frk(const Fr& a) {
-    FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = a.l[i];
-    return k;
-}
 Fr host_int(const zk_fr* x) { return fp_ext_to_int<FrParams>(host_load_ext<FrParams>(x->l)); }
 Fr host_pow(const Fr& a, uint64_t e) {
     Fr r = fp_one<FrParams>();
@@ -331,14 +319,8 @@ extern "C" int zk_fr_batch_inverse_dev(zk_ctx* ctx, void* v_dev, size_t n) {
         // short vector: the one inversion on the host (see k_inv_fwd)
         uint32_t* tot;
         ZK_TRY(zk_scratch(ctx, "poly_inv_tot", chunks * 36 * 2, (void**)&tot));
-        auto& pin = ctx->pinned[-4];
-        if (pin.bytes < 2048 * 36 * 2) {
-            if (pin.p) (void)hipHostFree(pin.p);
-            pin.p = nullptr; pin.bytes = 0;
-            ZK_HIP(ctx, hipHostMalloc(&pin.p, 2048 * 36 * 2, hipHostMallocDefault));
-            pin.bytes = 2048 * 36 * 2;
-        }
-        uint32_t* h = (uint32_t*)pin.p;
+        uint32_t* h;
+        ZK_TRY(zk_pinned(ctx, {ZK_PIN_INV_TOTALS, 0}, 2048 * 36 * 2, (void**)&h));
         hipLaunchKernelGGL(k_inv_fwd, zk_grid(chunks, 64, 8192), 64, 0, ctx->stream, (const void*)v_dev, n, ch, scr, tot);
         ZK_HIP(ctx, hipGetLastError());
         ZK_HIP(ctx, hipMemcpyAsync(h, tot, chunks * 36, hipMemcpyDeviceToHost, ctx->stream));

@@ -484,12 +484,12 @@ uint32_t ilog2(size_t n) { uint32_t l = 0; while (((size_t)1 << l) < n) l++; ret
 constexpr size_t LDS_BYTES = (size_t)L7 * TILE * 4;
 
 int she_lds_attr(zk_ctx* ctx) {
-    if (ctx->flags["she_lds"]) return ZK_OK;
+    if (ctx->lds_attr_done[ZK_LDS_SHE]) return ZK_OK;
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_she_fwd_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_she_fwd_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_she_inv_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_she_inv_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-    ctx->flags["she_lds"] = 1;
+    ctx->lds_attr_done[ZK_LDS_SHE] = true;
     return ZK_OK;
 }
 

@@ -15,15 +15,6 @@ using namespace zk;
 
 namespace {
 
-struct FrK { uint32_t l[9]; };  // a field constant passed by value (internal form)
-
-__device__ __forceinline__ Fr frk(const FrK& k) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
-    return r;
-}
-
 template <int OP>
 __global__ void __launch_bounds__(256) k_vec_op(const void* a, const void* b, void* out, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -122,12 +113,6 @@ __global__ void __launch_bounds__(256) k_any_nonzero(const void* v, size_t n, ui
         acc |= w.x | w.y | w.z | w.w;
     }
     if (acc) atomicOr(flag, 1u);
-}
-
-FrK to_frk(const uint32_t* l) {
-    FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = l[i];
-    return k;
 }
 
 }  // namespace
@@ -247,14 +232,9 @@ int zk_fr_vec_is_zero_launch(zk_ctx* ctx, const void* v, size_t n, int slot, con
     if (slot < 0 || slot >= 8) return ZK_ERR_ARG;
     uint32_t* flag;
     ZK_TRY(zk_scratch(ctx, "vec_flag_async", 8 * 16, (void**)&flag));
-    auto& pin = ctx->pinned[-5];
-    if (pin.bytes < 8 * 16) {
-        if (pin.p) (void)hipHostFree(pin.p);
-        pin.p = nullptr; pin.bytes = 0;
-        ZK_HIP(ctx, hipHostMalloc(&pin.p, 8 * 16, hipHostMallocDefault));
-        pin.bytes = 8 * 16;
-    }
-    uint32_t* h = (uint32_t*)pin.p + 4 * slot;
+    uint32_t* h;
+    ZK_TRY(zk_pinned(ctx, {ZK_PIN_ZERO_VERDICTS, 0}, 8 * 16, (void**)&h));
+    h += 4 * slot;
     ZK_HIP(ctx, hipMemsetAsync(flag + 4 * slot, 0, 4, ctx->stream));
     if (n) hipLaunchKernelGGL(k_any_nonzero, zk_grid(2 * n, 256), 256, 0, ctx->stream, v, n, flag + 4 * slot);
     ZK_HIP(ctx, hipMemcpyAsync(h, flag + 4 * slot, 4, hipMemcpyDeviceToHost, ctx->stream));
