@@ -308,6 +308,15 @@ int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r1cs, const zk_fr* alpha, const
 size_t zk_pk_query_len(const zk_pk* pk, int which);
 /* Borrowed handle to one query table (same `which`); owned by the key, valid until zk_pk_free. */
 const zk_bases* zk_pk_query_bases(const zk_pk* pk, int which);
+/* Shifted window multiples.  A proving key's tables hold the window multiples 2^(c j) P of every query point; with `levels` = M
+ * they also hold 2^(c j + m) P for m = 1 .. M, and a digit with v trailing zero bits takes level min(v, M) and the bucket of the
+ * digit shifted down by as much: an MSM over the key reduces 2^(c-2) + 2^(c-2-M) buckets instead of 2^(c-1), at M + 1 times the
+ * table memory.  Same sums, same proof bytes.  zk_msm_mul_levels sets M (0 .. 3) for the keys this context makes resident from
+ * now on (setup, upload, deserialize); -1 returns to the default, which the environment's ZK_MSM_MUL_LEVELS overrides.  M is
+ * lowered for small tables (a reduce window keeps at least 64 buckets).  zk_pk_mul_levels: what a resident key got. */
+int zk_msm_mul_levels(zk_ctx* ctx, int levels);
+uint32_t zk_pk_mul_levels(const zk_pk* pk);
+uint32_t zk_msm_mul_levels_clamp(uint32_t window_bits, uint32_t levels);   /* the M a table with windows of that width gets for `levels` */
 int zk_pk_download_g1(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g1_affine* out);
 int zk_pk_download_g2(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g2_affine* out);
 /* vk elements: 0=alpha_g1 1=beta_g1 2=delta_g1 (G1);  0=beta_g2 1=delta_g2 2=gamma_g2 (G2) */

@@ -763,6 +763,10 @@ class Context:
         """zk_groth16_chain_fronts: whether an announced small proof's front carries its whole device chain (default on)."""
         self._ck(self.lib.zk_groth16_chain_fronts(self.h, int(on)))
 
+    def msm_mul_levels(self, levels: int):
+        """zk_msm_mul_levels: shifted copies (0 .. 3) the tables of the keys made resident from now on carry; -1: the default."""
+        self._ck(self.lib.zk_msm_mul_levels(self.h, int(levels)))
+
     def host_alloc(self, nbytes: int) -> "HostBuf":
         """Page-locked host memory (zk_host_alloc) viewed as a numpy uint64 array."""
         return HostBuf(self, nbytes)
@@ -943,6 +947,10 @@ class ProvingKey:
 
     def __init__(self, ctx: Context, h):
         self.ctx, self.h = ctx, h
+
+    def mul_levels(self) -> int:
+        """zk_pk_mul_levels: the shifted copies this key's tables carry."""
+        return self.ctx.lib.zk_pk_mul_levels(self.h)
 
     def query_len(self, name: str) -> int:
         return self.ctx.lib.zk_pk_query_len(self.h, self.QUERIES[name])

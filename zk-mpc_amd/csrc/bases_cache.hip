@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(256) k_words_differ(const uint4* a, const uint
 size_t table_bytes(const zk_bases* b) {
     const size_t pw = b->group == 1 ? 24 : 48;
     size_t bytes = 2 * b->n * pw * 4;                       // device form + the packed copy
-    if (b->pre) bytes += (size_t)b->W_pre * b->n * (b->pre_stride ? b->pre_stride : pw) * 4;
+    if (b->pre) bytes += (size_t)b->W_pre * (b->pre_levels + 1) * b->n * (b->pre_stride ? b->pre_stride : pw) * 4;
     return bytes;
 }
 

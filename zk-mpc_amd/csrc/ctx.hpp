@@ -162,6 +162,7 @@ struct zk_ctx {
     // idle one of two device slots while the current proof runs; next_z_ready is recorded behind that copy
     hipStream_t copy_stream = nullptr;
     hipEvent_t next_z_ready = nullptr;
+    int mul_levels = -1;                      // zk_msm_mul_levels: shifted copies the next proving key's tables get (-1: the default)
     bool chain_fronts = true;                 // zk_groth16_chain_fronts: a small proof's front carries the next proof's whole device chain
     int front_parity = 0;                     // groth16_pipeline.hip: which pair of pinned result buffers the next chained front writes
     const void* next_z_host = nullptr;        // the host buffer that was announced (matched by address by zk_groth16_prove)

@@ -190,17 +190,21 @@ __global__ void __launch_bounds__(256) k_repack_limbs(const uint32_t* in, uint32
 // table AND the re-laid copy that briefly lives beside it -- may take at most a third of what is free when the call starts (a
 // 2^24-point G2 query would ask for 40 GB).  When the table is skipped the MSM falls back to per-window bucket sets; the reason
 // is kept in zk_bases::pre_note (zk_bases_precompute_note) and in zk_last_error, although the call succeeds.
+// levels: shifted copies (zk_bases::pre_levels) -- level m = 2^m times level m - 1, all W windows of it, behind it: ONE doubling per
+// point and level (a small table: one launch pair per level; a large one: per window, in the scratch the build has anyway).
 template <class F>
-int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout) {
+int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout, uint32_t levels = 0) {
     const size_t n = b->n, PW = 2 * F::WORDS;
+    const size_t Wt = (size_t)W * (levels + 1);                // window tables in all
     // levels per launch pair (k_dbl_levels); a forced packed layout keeps the level-by-level build: tests compare the two
     const uint32_t G = layout == 1 || W < 2 ? 1u : (n <= 4096 ? W - 1 : (n <= 16384 ? 4u : (n <= 65536 ? 2u : 1u)));
-    const size_t lv = G > 1 ? W - 1 : 1;                       // levels the scratch holds at once (G > 1: every level above the table itself)
+    const bool whole_levels = levels && n <= 65536;            // a shifted copy in one go
+    const size_t lv = whole_levels ? W : (G > 1 ? W - 1 : 1);  // levels the scratch holds at once (G > 1: every level above the table itself)
     uint32_t *xy, *scr;
     ZK_TRY(zk_scratch(ctx, "fb_xyzz", lv * n * 4 * F::WORDS * 4, (void**)&xy));
     ZK_TRY(zk_scratch(ctx, "fb_scr", lv * n * F::WORDS * 4, (void**)&scr));
     size_t mem_free = 0, mem_total = 0;
-    const size_t packed_bytes = (size_t)W * n * PW * 4;
+    const size_t packed_bytes = Wt * n * PW * 4;
     auto skip = [&](const char* why) {
         char msg[256];
         snprintf(msg, sizeof msg, "window multiples skipped for a %zu-point G%d table (c = %u, W = %u: %.2f GB packed): %s; %.2f GB free",
@@ -224,7 +228,7 @@ int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout) {
         if (extra) (void)hipFree(extra);
         (void)hipFree(b->pre);
         b->pre = nullptr;
-        b->c_pre = b->W_pre = b->pre_stride = 0;
+        b->c_pre = b->W_pre = b->pre_stride = b->pre_levels = 0;
     };
     hipError_t e = hipMemcpyAsync(b->pre, b->dev, n * PW * 4, hipMemcpyDeviceToDevice, ctx->stream);
     const size_t chunks = (n + NORM_CHUNK - 1) / NORM_CHUNK;
@@ -246,10 +250,19 @@ int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout) {
         hipLaunchKernelGGL(k_batch_affine<F>, (unsigned)((chunks + 63) / 64), 64, 0, ctx->stream, xy, b->pre + (size_t)w * n * PW, scr, n);
         e = hipGetLastError();
     }
+    for (uint32_t m = 1; m <= levels && e == hipSuccess; m++) {
+        const size_t per = whole_levels ? (size_t)W * n : n, pchunks = (per + NORM_CHUNK - 1) / NORM_CHUNK;
+        for (size_t o = 0; o < (size_t)W * n && e == hipSuccess; o += per) {
+            hipLaunchKernelGGL(k_dbl_c<F>, zk_grid(per, 256), 256, 0, ctx->stream, b->pre + ((size_t)(m - 1) * W * n + o) * PW, xy, per, 1u);
+            hipLaunchKernelGGL(k_batch_affine<F>, (unsigned)((pchunks + 63) / 64), 64, 0, ctx->stream, xy, b->pre + ((size_t)m * W * n + o) * PW, scr, per);
+            e = hipGetLastError();
+        }
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { fail_free(nullptr); ZK_HIP(ctx, e); }
     b->c_pre = c;
     b->W_pre = W;
+    b->pre_levels = levels;
     b->pre_stride = 0;
     b->pre_note = "packed";
     // G1: a 96-byte point in a packed table straddles two 128-byte lines half of the time and the accumulate kernel's gather
@@ -261,7 +274,7 @@ int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout) {
         for (int form : {3, 2}) {
             if (layout && layout != form) continue;
             if (!layout && b->pre_stride) break;
-            const size_t words = form == 3 ? 64 : 32, bytes = (size_t)W * n * words * 4;
+            const size_t words = form == 3 ? 64 : 32, bytes = Wt * n * words * 4;
             if (packed_bytes + bytes > budget) {         // (the packed table is still alive while the copy is made)
                 if (layout) { fail_free(nullptr); return skip("the forced layout does not fit a third of the free device memory"); }
                 continue;
@@ -273,9 +286,9 @@ int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout) {
                 continue;
             }
             if (form == 3)
-                hipLaunchKernelGGL(k_repack_limbs<F>, zk_grid((size_t)W * n, 256), 256, 0, ctx->stream, (const uint32_t*)b->pre, wide, (size_t)W * n);
+                hipLaunchKernelGGL(k_repack_limbs<F>, zk_grid(Wt * n, 256), 256, 0, ctx->stream, (const uint32_t*)b->pre, wide, Wt * n);
             else
-                hipLaunchKernelGGL(k_repack<F>, zk_grid((size_t)W * n, 256), 256, 0, ctx->stream, (const uint32_t*)b->pre, wide, (size_t)W * n, 32u);
+                hipLaunchKernelGGL(k_repack<F>, zk_grid(Wt * n, 256), 256, 0, ctx->stream, (const uint32_t*)b->pre, wide, Wt * n, 32u);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
             if (e != hipSuccess) { fail_free(wide); ZK_HIP(ctx, e); }
@@ -357,13 +370,48 @@ extern "C" uint32_t zk_bases_window_bits(const zk_bases* b) { return b ? b->c_pr
 // how many copies (windows) the multiples of an n-point table have: what bases_cache.hip budgets for
 uint32_t zk_precompute_windows(size_t n) { const uint32_t c = precompute_window_bits(n); return (255 + c - 1) / c; }
 
-static int precompute_run(zk_ctx* ctx, zk_bases* b, int layout) {
+static int precompute_run(zk_ctx* ctx, zk_bases* b, int layout, uint32_t levels = 0) {
     if (!ctx || layout < 0 || layout > 3) return ZK_ERR_ARG;
     if (!b || b->pre || b->n < ZK_PRECOMP_MIN_POINTS) return ZK_OK;
     const uint32_t c = precompute_window_bits(b->n);
     const uint32_t W = (255 + c - 1) / c;
-    if (b->group == 1) return precompute_t<G1Field>(ctx, b, c, W, layout);
-    return precompute_t<G2Field>(ctx, b, c, W, layout);
+    levels = zk_msm_mul_levels_clamp(c, levels);
+    if (b->group == 1) return precompute_t<G1Field>(ctx, b, c, W, layout, levels);
+    return precompute_t<G2Field>(ctx, b, c, W, layout, levels);
+}
+
+// A reduce window of a table with M shifted copies has 2^(c - 2 - M) buckets: M is lowered until that is at least 2^ZK_MSM_MIN_LOG_NB
+// (the smallest window the grid reduce is run at: c = 8 without copies)
+extern "C" uint32_t zk_msm_mul_levels_clamp(uint32_t c, uint32_t levels) {
+    uint32_t M = levels < ZK_MSM_MAX_LEVELS ? levels : ZK_MSM_MAX_LEVELS;
+    while (M && c < 2 + M + ZK_MSM_MIN_LOG_NB) M--;
+    return M;
+}
+// How many shifted copies the tables of a proving key get whose z queries have n points.  Forced: zk_msm_mul_levels, else the
+// environment's ZK_MSM_MUL_LEVELS (0 .. 3; tests, A/B runs).  Otherwise the measured default for the 20-bit windows of
+// 2^19 points and more, lowered until the whole key -- four G1 tables in the 256-byte form, the packed one that lives beside the
+// last while it is re-laid, one G2 table -- fits a third of the free device memory, the headroom every table build keeps.
+constexpr uint32_t MUL_LEVELS_DEFAULT = 3;   // 2^20: 14.78 ms per proof against 15.05 (M = 2: 14.86, M = 1: no gain), profiles/mul_levels_ab.jsonl
+uint32_t zk_mul_levels_for_key(zk_ctx* ctx, size_t n) {
+    if (n < ZK_PRECOMP_MIN_POINTS || !precompute_enabled_by_default()) return 0;
+    const uint32_t c = precompute_window_bits(n), W = (255 + c - 1) / c;
+    const char* e = getenv("ZK_MSM_MUL_LEVELS");
+    const int forced = ctx->mul_levels >= 0 ? ctx->mul_levels : (e && *e ? atoi(e) : -1);
+    if (forced >= 0) return zk_msm_mul_levels_clamp(c, (uint32_t)forced);
+    uint32_t M = zk_msm_mul_levels_clamp(c, c >= 20 ? MUL_LEVELS_DEFAULT : 0u);
+    if (!M) return 0;
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    while (M && (size_t)(M + 1) * W * n * (4 * 256 + 96 + 192) > mem_free / 3) M--;
+    return M;
+}
+int zk_bases_precompute_levels(zk_ctx* ctx, zk_bases* b, uint32_t levels) {
+    if (!precompute_enabled_by_default() || !b || b->n < ZK_PRECOMP_MIN_POINTS) return ZK_OK;
+    // (a table that does not fit with its copies is tried with fewer: its MSMs then sort for themselves, the sums are the same)
+    for (uint32_t lv = levels;; lv--) {
+        ZK_TRY(precompute_run(ctx, b, 0, lv));
+        if (b->pre || lv == 0) return ZK_OK;
+    }
 }
 
 extern "C" int zk_bases_precompute(zk_ctx* ctx, zk_bases* b) {

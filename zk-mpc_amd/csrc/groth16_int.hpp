@@ -47,6 +47,8 @@ struct zk_pk {
     // every point is a multiple of the generators (zk_groth16_setup): the proof tail may use the endomorphism (hostfield64.hpp:
     // host64_scalar_mul_glv); a deserialised key is not checked for subgroup membership and keeps the plain scalar multiplication
     bool points_in_subgroup = false;
+    // shifted copies of the window multiples its tables were asked to carry (zk_mul_levels_for_key; zk_bases::pre_levels is what each got)
+    uint32_t mul_levels = 0;
     zk::Affine<zk::G1Field> alpha_g1, beta_g1, delta_g1, a0, b0_g1;
     zk::Affine<zk::G2Field> beta_g2, delta_g2, gamma_g2, b0_g2;
     // the verifier's constant e(alpha, beta) (pairing.hip), computed by the first verification of this key: the GT value as the
@@ -92,6 +94,7 @@ int zk_prover_streams(zk_ctx* ctx, size_t k);
 int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h_in, void* h_scratch,
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc = nullptr);
 int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: see zk_pk::l_pad
+int zk_pk_precompute(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: window multiples of every query, then l_pad
 // r1cs.hip: the witness map of count assignments (count x m elements back to back) with launches that do not grow with count;
 // abc = room for 6 count D elements, the count quotients in its first count D on return
 int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);
@@ -115,7 +118,7 @@ struct ZkG16Jobs {
         const size_t nvars = m - 1;
         const char *z1 = z ? (const char*)z + 32 : nullptr, *zw = z ? (const char*)z + r->ni * 32 : nullptr;
         l_shared = pad_l && pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
-                   pk->l_pad->c_pre == pk->a->c_pre;
+                   pk->l_pad->c_pre == pk->a->c_pre && pk->l_pad->pre_levels == pk->a->pre_levels;
         j[0] = {pk->b_g2, 1, z1, nvars};        // query[1..] x z[1..]
         j[1] = {pk->a, 1, z1, nvars};
         j[2] = {pk->b_g1, 1, z1, nvars};

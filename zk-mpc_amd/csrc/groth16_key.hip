@@ -83,7 +83,23 @@ int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk) {
     ZK_HIP(ctx, hipMemsetAsync(b->dev, 0, front * PW, ctx->stream));
     ZK_HIP(ctx, hipMemcpyAsync((char*)b->dev + front * PW, pk->l->dev, pk->l->n * PW, hipMemcpyDeviceToDevice, ctx->stream));
     ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return zk_bases_precompute_auto(ctx, b);
+    return zk_bases_precompute_levels(ctx, b, pk->mul_levels);
+}
+
+// The window multiples of the five queries and the padded l_query, with the key's shifted copies (zk_pk::mul_levels): every way a key
+// becomes resident (upload, setup, deserialize) ends here
+int zk_pk_precompute(zk_ctx* ctx, zk_pk* pk) {
+    pk->mul_levels = pk->a ? zk_mul_levels_for_key(ctx, pk->a->n) : 0;
+    for (zk_bases* q : {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l}) ZK_TRY(zk_bases_precompute_levels(ctx, q, pk->mul_levels));
+    return zk_pk_make_l_pad(ctx, pk);
+}
+extern "C" uint32_t zk_pk_mul_levels(const zk_pk* pk) { return pk && pk->a ? pk->a->pre_levels : 0u; }
+extern "C" int zk_msm_mul_levels(zk_ctx* ctx, int levels) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || levels < -1 || levels > (int)ZK_MSM_MAX_LEVELS) return ZK_ERR_ARG;
+    ctx->mul_levels = levels;
+    return ZK_OK;
+    ZK_API_END
 }
 
 extern "C" int zk_pk_free(zk_ctx* ctx, zk_pk* pk) {
@@ -108,9 +124,7 @@ extern "C" int zk_pk_upload(zk_ctx* ctx, const zk_pk_host* h, zk_pk** out) {
     if (rc == ZK_OK) rc = zk_bases_upload_g2(ctx, h->b_g2_query, h->b_g2_len, &pk->b_g2);
     if (rc == ZK_OK) rc = zk_bases_upload_g1(ctx, h->h_query, h->h_len, &pk->h);
     if (rc == ZK_OK) rc = zk_bases_upload_g1(ctx, h->l_query, h->l_len, &pk->l);
-    for (zk_bases* q : {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l})
-        if (rc == ZK_OK) rc = zk_bases_precompute_auto(ctx, q);
-    if (rc == ZK_OK) rc = zk_pk_make_l_pad(ctx, pk);
+    if (rc == ZK_OK) rc = zk_pk_precompute(ctx, pk);
     if (rc != ZK_OK) { zk_pk_free(ctx, pk); return rc; }
     pk->alpha_g1 = host_aff_from_abi<G1Field>((const uint64_t*)&h->alpha_g1);
     pk->beta_g1 = host_aff_from_abi<G1Field>((const uint64_t*)&h->beta_g1);
@@ -241,9 +255,7 @@ extern "C" int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r, const zk_fr* alph
     if (rc == ZK_OK) rc = zk_fixed_base_g1_dev(ctx, g1_k, dev, l.size(), &pk->l);
     if (rc == ZK_OK) rc = upload_fr(ctx, gamma_abc, "setup_scalars", &dev);
     if (rc == ZK_OK) rc = zk_fixed_base_g1_dev(ctx, g1_k, dev, gamma_abc.size(), &pk->gamma_abc);
-    for (zk_bases* q : {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l})
-        if (rc == ZK_OK) rc = zk_bases_precompute_auto(ctx, q);
-    if (rc == ZK_OK) rc = zk_pk_make_l_pad(ctx, pk);
+    if (rc == ZK_OK) rc = zk_pk_precompute(ctx, pk);
     if (rc != ZK_OK) { zk_pk_free(ctx, pk); return rc; }
     pk->points_in_subgroup = true;            // every point of this key is a scalar multiple of a generator
 

@@ -55,6 +55,9 @@ struct zk_bases {
     uint32_t c_pre = 0, W_pre = 0;
     uint32_t pre_stride = 0;   // 32-bit words per point in `pre` (0: packed, 2 * WORDS).  G1: 32 = one 128-byte line per 96-byte point;
                                // 64 = limb form, line 0 the point, line 1 its negative (fixed_base.hip::k_repack_limbs)
+    // shifted multiples (Groth16 proving keys): `pre` holds pre_levels + 1 such tables back to back, level m = 2^m times level 0
+    // (entry index m * W_pre * n + w * n + i); an MSM over it reduces 2^(c-2) + 2^(c-2-M) buckets instead of 2^(c-1) (msm_digits.cuh)
+    uint32_t pre_levels = 0;
     std::string pre_note;      // which layout `pre` has, or why the window multiples were skipped (zk_bases_precompute_note)
 };
 // hostxfer.hip: caller-owned (pageable) host memory <-> device through the context's page-locked ring; h2d returns once the host
@@ -125,6 +128,11 @@ void zk_bases_cache_free(zk_ctx* ctx);
 extern "C" int zk_bases_free(zk_ctx* ctx, zk_bases* b);
 constexpr size_t ZK_PRECOMP_MIN_POINTS = 256;                    // tables below this keep the plain form (zk_bases_precompute is a no-op)
 extern "C" int zk_bases_precompute(zk_ctx* ctx, zk_bases* b);
+// ... with `levels` shifted copies (zk_bases::pre_levels), clamped so that a reduce window keeps 2^ZK_MSM_MIN_LOG_NB buckets
+constexpr uint32_t ZK_MSM_MAX_LEVELS = 3, ZK_MSM_MIN_LOG_NB = 6;
+extern "C" uint32_t zk_msm_mul_levels_clamp(uint32_t c, uint32_t levels);   // fixed_base.hip
+uint32_t zk_mul_levels_for_key(zk_ctx* ctx, size_t n);              // fixed_base.hip: what a proving key whose z tables have n points gets
+int zk_bases_precompute_levels(zk_ctx* ctx, zk_bases* b, uint32_t levels);
 uint32_t zk_precompute_windows(size_t n);                            // fixed_base.hip: copies a table of n points would get
 int zk_bases_precompute_auto(zk_ctx* ctx, zk_bases* b);             // only when ZK_PRECOMP=1 (off by default: see fixed_base.hip)
 // fixed_base.hip: the window multiples of a resident table built in slices on a side stream, published by a later call
@@ -203,7 +211,10 @@ struct ZkMsmJob {
     uint32_t c = 0, W = 0, NB = 0, seg = 0;
     uint16_t off[65] = {0};           // window w covers scalar bits [off[w], off[w+1])
     uint32_t Wb = 0;                  // bucket sets: W, or 1 when the bases carry precomputed window multiples
-    uint32_t log_nb = 0, nout = 0;    // reduce phase (msm_reduce.cuh): a bucket set of 2^log_nb buckets leaves nout = log_nb + 1 points for the host
+    uint32_t log_nb = 0, nout = 0;    // reduce phase (msm_reduce.cuh): a window of 2^log_nb buckets leaves nout = log_nb + 1 points for the host
+    // shifted multiples (zk_bases::pre_levels): M levels above the table, NB = (2^M + 1) 2^log_nb compact buckets that the reduce
+    // takes as red_win = 2^M + 1 windows per bucket set; lvl_stride = table entries between two levels
+    uint32_t M = 0, red_win = 1, lvl_stride = 0;
     uint32_t n_tab = 0, tab_off = 0;  // merged mode: table stride and offset of this MSM's first base
     uint32_t stride = 0;              // 32-bit words between consecutive points of bases_dev (the packed 2 * WORDS, or zk_bases::pre_stride)
     const uint32_t* bases_dev = nullptr;

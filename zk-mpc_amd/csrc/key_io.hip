@@ -124,9 +124,7 @@ extern "C" int zk_pk_deserialize(zk_ctx* ctx, const uint8_t* bytes, size_t len, 
         pk->beta_g2 = g2s[0]; pk->gamma_g2 = g2s[1]; pk->delta_g2 = g2s[2];
         pk->beta_g1 = g1s[0]; pk->delta_g1 = g1s[1];
     }
-    for (zk_bases* q : {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l})
-        if (rc == ZK_OK) rc = zk_bases_precompute_auto(ctx, q);
-    if (rc == ZK_OK) rc = zk_pk_make_l_pad(ctx, pk);
+    if (rc == ZK_OK) rc = zk_pk_precompute(ctx, pk);
     if (rc == ZK_OK) rc = first_point<G1Field>(ctx, pk->a, &pk->a0);
     if (rc == ZK_OK) rc = first_point<G1Field>(ctx, pk->b_g1, &pk->b0_g1);
     if (rc == ZK_OK) rc = first_point<G2Field>(ctx, pk->b_g2, &pk->b0_g2);

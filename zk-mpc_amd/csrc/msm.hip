@@ -90,7 +90,7 @@ MsmPlan make_plan(size_t n, uint32_t forced_c = 0) {
 
 // dig[w*n + i] = |d| | (d<0 ? 1<<31 : 0), and counts[w*NB + |d| - 1]++ for |d| > 0.
 __global__ void __launch_bounds__(256)
-k_digits(const void* scalars, size_t n, WinOff wo, uint32_t W, uint32_t NB, Bias bias, uint32_t* dig, uint32_t* counts, int merged) {
+k_digits(const void* scalars, size_t n, WinOff wo, uint32_t W, uint32_t NB, Bias bias, uint32_t* dig, uint32_t* counts, int merged, LevelMap lm) {
     __shared__ uint32_t kw[9][256];
     const uint32_t tid = threadIdx.x;
     for (size_t i0 = blockIdx.x * (size_t)256; i0 < n; i0 += (size_t)gridDim.x * 256) {
@@ -107,7 +107,8 @@ k_digits(const void* scalars, size_t n, WinOff wo, uint32_t W, uint32_t NB, Bias
                 const int32_t d = signed_digit(two, bit, wo.off[w + 1] - bit);
                 uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
                 dig[(size_t)w * n + i] = mag | (d < 0 ? 0x80000000u : 0u);
-                if (mag) atomicAdd(&counts[(merged ? 0 : (size_t)w * NB) + mag - 1], 1u);
+                uint32_t eoff;
+                if (mag) atomicAdd(&counts[merged ? level_bucket(mag, lm, eoff) : (size_t)w * NB + mag - 1], 1u);
             }
         }
     }
@@ -117,7 +118,7 @@ k_digits(const void* scalars, size_t n, WinOff wo, uint32_t W, uint32_t NB, Bias
 // merged (precomputed window multiples): one bucket set; the entry is the TABLE index w*n_tab + tab_off + i.
 __global__ void __launch_bounds__(256)
 k_scatter(const uint32_t* dig, size_t n, uint32_t W, uint32_t NB, const uint32_t* offs, uint32_t* counts, uint32_t* sorted,
-          int merged, uint32_t n_tab, uint32_t tab_off) {
+          int merged, uint32_t n_tab, uint32_t tab_off, LevelMap lm) {
     const size_t total = (size_t)W * n;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         uint32_t d = dig[t];
@@ -125,8 +126,10 @@ k_scatter(const uint32_t* dig, size_t n, uint32_t W, uint32_t NB, const uint32_t
         if (!mag) continue;
         size_t w = t / n, i = t - w * n;
         if (merged) {
-            uint32_t slot = atomicSub(&counts[mag - 1], 1u) - 1;
-            sorted[offs[mag - 1] + slot] = (uint32_t)(w * n_tab + tab_off + i) | (d & 0x80000000u);
+            uint32_t eoff;
+            const uint32_t b = level_bucket(mag, lm, eoff);
+            uint32_t slot = atomicSub(&counts[b], 1u) - 1;
+            sorted[offs[b] + slot] = (uint32_t)(w * n_tab + tab_off + i + eoff) | (d & 0x80000000u);
         } else {
             uint32_t slot = atomicSub(&counts[w * NB + mag - 1], 1u) - 1;
             sorted[w * n + offs[w * (NB + 1) + mag - 1] + slot] = (uint32_t)i | (d & 0x80000000u);
@@ -312,7 +315,7 @@ k_order(const SegDesc* desc, const uint32_t* ctr, uint32_t* bin_cursor, uint32_t
 constexpr uint32_t SS_NT = 1024;
 constexpr uint32_t SS_MAX_ENTRIES = 1u << 16, SS_MAX_NB = 1u << 15, SS_MAX_SEG = 64;   // (70 k entries in one block: 157 us against ~105 for the six launches)
 struct SortSmallArgs {
-    const void* scalars; uint32_t n; WinOff wo; uint32_t W, NB; Bias bias; uint32_t seg, n_tab, tab_off, grp_base;
+    const void* scalars; uint32_t n; WinOff wo; uint32_t W, NB; Bias bias; uint32_t seg, n_tab, tab_off, grp_base; LevelMap lm;
     uint32_t* dig; uint32_t* sorted; SegDesc* desc; HeavyDesc* heavy; HeavyDesc* heavy2; uint32_t* order; uint32_t* ctr;
 };
 __device__ __forceinline__ void sort_small_body(const SortSmallArgs& a) {
@@ -320,6 +323,7 @@ __device__ __forceinline__ void sort_small_body(const SortSmallArgs& a) {
     const uint32_t n = a.n, W = a.W, NB = a.NB, seg = a.seg, n_tab = a.n_tab, tab_off = a.tab_off, grp_base = a.grp_base;
     const WinOff& wo = a.wo;
     const Bias& bias = a.bias;
+    const LevelMap lm = a.lm;
     uint32_t* dig = a.dig; uint32_t* sorted = a.sorted; SegDesc* desc = a.desc; HeavyDesc* heavy = a.heavy; HeavyDesc* heavy2 = a.heavy2;
     uint32_t* order = a.order; uint32_t* ctr = a.ctr;
     extern __shared__ uint32_t ss_lds[];
@@ -348,7 +352,8 @@ __device__ __forceinline__ void sort_small_body(const SortSmallArgs& a) {
             const int32_t d = signed_digit(two, bit, wo.off[w + 1] - bit);
             const uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
             dig[(size_t)w * n + i] = mag | (d < 0 ? 0x80000000u : 0u);
-            if (mag) atomicAdd(&cnt[mag - 1], 1u);
+            uint32_t eoff;
+            if (mag) atomicAdd(&cnt[level_bucket(mag, lm, eoff)], 1u);
         }
     }
     __syncthreads();
@@ -411,7 +416,9 @@ __device__ __forceinline__ void sort_small_body(const SortSmallArgs& a) {
             const uint32_t mag = d[u] & 0x7fffffffu;
             if (!mag) continue;
             const uint32_t t = t0 + u * SS_NT, w = t / n, i = t - w * n;
-            sorted[atomicAdd(&cnt[mag - 1], 1u)] = (w * n_tab + tab_off + i) | (d[u] & 0x80000000u);
+            uint32_t eoff;
+            const uint32_t b = level_bucket(mag, lm, eoff);
+            sorted[atomicAdd(&cnt[b], 1u)] = (w * n_tab + tab_off + i + eoff) | (d[u] & 0x80000000u);
         }
     }
     // segments by length, longest first: lh[len] becomes the first position of that length
@@ -787,6 +794,12 @@ int msm_prepare_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base
         job->n_tab = (uint32_t)bases->n;
         job->tab_off = (uint32_t)base_offset;
         job->stride = bases->pre_stride ? bases->pre_stride : 2 * F::WORDS;
+        if (bases->pre_levels) {                                // shifted multiples (msm_digits.cuh): fewer, compactly numbered buckets
+            job->M = bases->pre_levels;
+            job->red_win = (1u << job->M) + 1;
+            job->lvl_stride = (uint32_t)(bases->W_pre * bases->n);
+            job->NB = (p.NB >> 1) + (p.NB >> (1 + job->M));
+        }
     } else {
         job->Wb = p.W;
         job->bases_dev = bases->dev + base_offset * (2 * F::WORDS);
@@ -805,6 +818,7 @@ int msm_prepare_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base
     // Reduce phase geometry (msm_reduce.cuh): every bucket set is a grid of 2^rl x 2^cl buckets, rl + cl = log2(NB)
     uint32_t lg = 0;
     while ((1u << lg) < p.NB) lg++;
+    if (job->M) lg = p.c - 2 - job->M;                         // the compact buckets are 2^M + 1 windows of this size
     job->log_nb = lg;
     job->nout = lg + 1;
     return ZK_OK;
@@ -842,10 +856,10 @@ int msm_bufs_t(zk_ctx* ctx, ZkMsmJob* job, MsmBufs<F>& b, bool need_sort) {
     }
     ZK_TRY(zk_scratch(ctx, slotname("msm_sums"), (nbuck + job->max_heavy_segs + job->max_groups) * XW * 4, (void**)&b.sums));
     ZK_TRY(zk_scratch_zeroed(ctx, slotname("msm_fold_done"), job->max_heavy2 * 4, (void**)&b.fold_done));
-    const GridGeom gg = make_grid_geom(job->log_nb, (uint32_t)Wb, 256);     // the partial counts do not depend on the block size
+    const GridGeom gg = make_grid_geom(job->log_nb, (uint32_t)Wb * job->red_win, 256);     // the partial counts do not depend on the block size
     ZK_TRY(zk_scratch(ctx, slotname("msm_rowP"), grid_row_points(gg) * XW * 4, (void**)&b.rowP));
     ZK_TRY(zk_scratch(ctx, slotname("msm_colP"), grid_col_points(gg) * XW * 4, (void**)&b.colP));
-    ZK_TRY(zk_scratch(ctx, slotname("msm_bits"), (size_t)Wb * job->nout * XW * 4, (void**)&b.bits));
+    ZK_TRY(zk_scratch(ctx, slotname("msm_bits"), (size_t)Wb * job->red_win * job->nout * XW * 4, (void**)&b.bits));
     return ZK_OK;
 }
 
@@ -857,7 +871,8 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     const bool share_merged = share && share->Wb == 1 && share->W > 1;       // entries are table indices w * n_tab + tab_off + i
     if (share && share->n == n && share->scalars == job->scalars && share->sorted && share->Wb == job->Wb &&
         share->mcount == job->mcount && share->mstride == job->mstride &&
-        share->n_tab == job->n_tab && (share->tab_off == job->tab_off || share_merged) && share->c == job->c) {
+        share->n_tab == job->n_tab && (share->tab_off == job->tab_off || share_merged) && share->c == job->c &&
+        share->M == job->M && share->lvl_stride == job->lvl_stride) {
         // same scalar vector as an earlier job (A, B-in-G1 and B-in-G2 all use z[1..]): reuse its sort.  A different offset into a
         // table of window multiples (a polynomial's commitment over the shifted powers: marlin_pc/mod.rs:172-243) folds into
         // the base pointer -- the entries index the table linearly
@@ -904,6 +919,8 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     ZkGroupArgs ga;
     ga.scalars = job->scalars; ga.n = n; ga.wo = wo; ga.bias = bias; ga.W = W; ga.NB = NB; ga.merged = merged != 0;
     ga.n_tab = job->n_tab; ga.tab_off = job->tab_off; ga.NBt = (uint32_t)nbuck;
+    const LevelMap lm{job->M, job->M ? 1u << (job->c - 1 - job->M) : 0u, job->lvl_stride};
+    ga.lm = lm;
     ga.lanes = (uint32_t)ctx->n_cu * 4 * 64 * 2; ga.seg_max = seg;
     ga.sorted = b.sorted; ga.offs = b.offs; ga.ctr = ctr;
     if (job->mcount) { ga.vec_n = (uint32_t)job->mn; ga.vec_nb = Wbv * NB; ga.vec_stride = job->mstride; }
@@ -916,7 +933,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_sort_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)SS_MAX_NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4)));
             ctx->lds_attr_done[ZK_LDS_SORT_SMALL] = true;
         }
-        hipLaunchKernelGGL(k_sort_small, 1, SS_NT, lds, st, SortSmallArgs{job->scalars, (uint32_t)n, wo, W, NB, bias, seg, job->n_tab, job->tab_off, grp_base,
+        hipLaunchKernelGGL(k_sort_small, 1, SS_NT, lds, st, SortSmallArgs{job->scalars, (uint32_t)n, wo, W, NB, bias, seg, job->n_tab, job->tab_off, grp_base, lm,
                            b.dig, b.sorted, b.desc, b.heavy, b.heavy2, b.order, ctr});
         ZK_HIP(ctx, hipGetLastError());
         tm->end();
@@ -935,7 +952,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         auto put = [&](const void* p, size_t nbytes) { gkey.append((const char*)p, nbytes); };
         const uint64_t words[] = {ctx->scratch_gen, (uint64_t)(uintptr_t)job->scalars, (uint64_t)n, W, NB, Wb, job->c, seg, (uint64_t)job->slot,
                                   (uint64_t)merged, job->n_tab, job->tab_off, (uint64_t)job->max_segs, (uint64_t)job->max_heavy_segs, (uint64_t)g1,
-                                  (uint64_t)job->mcount, (uint64_t)job->mstride};
+                                  (uint64_t)job->mcount, (uint64_t)job->mstride, job->M, job->lvl_stride};
         put(words, sizeof words);
         put(job->off, sizeof job->off);
     }
@@ -951,10 +968,10 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         } else {
             ZK_HIP(ctx, hipMemsetAsync(b.counts, 0, nbuck * 4, st));
             ZK_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctr + 3), (int)seg, 1, st));             // the host's plan is the segment length
-            hipLaunchKernelGGL(k_digits, zk_grid(n, 256), 256, 0, st, job->scalars, n, wo, W, NB, bias, b.dig, b.counts, merged);
+            hipLaunchKernelGGL(k_digits, zk_grid(n, 256), 256, 0, st, job->scalars, n, wo, W, NB, bias, b.dig, b.counts, merged, lm);
             ZK_TRY(scans(Wb, NB));
             hipLaunchKernelGGL(k_scatter, zk_grid((size_t)W * n, 256), 256, 0, st, b.dig, n, W, NB, b.offs, b.counts, b.sorted, merged,
-                               job->n_tab, job->tab_off);
+                               job->n_tab, job->tab_off, lm);
             hipLaunchKernelGGL(k_build_segs, zk_grid(nbuck, 256, 512), 256, (seg + 1) * 4, st, b.offs, b.seg_local, win_segs,
                                merged ? (size_t)0 : n, Wb, NB, b.desc, b.heavy, b.heavy2, ctr, hist, grp_base);
         }
@@ -1023,20 +1040,21 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     const unsigned heavy_blocks = (unsigned)std::min<size_t>(job->max_heavy, 256);
     if constexpr (F::WORDS != 12) {
         // G2: the same chain on lane pairs (msm_g2pair.hip)
-        ZkG2PairReduce a{job->heavy, job->heavy2, job->ctr, b.fold_done, b.sums, b.rowP, b.colP, b.bits, job->log_nb, job->Wb, 2 * light_blocks, heavy_blocks};
+        ZkG2PairReduce a{job->heavy, job->heavy2, job->ctr, b.fold_done, b.sums, b.rowP, b.colP, b.bits, job->log_nb, job->Wb * job->red_win, 2 * light_blocks, heavy_blocks};
         a.quads = msm_latency_bound(job);
         ZK_TRY(zk_launch_reduce_g2pair(ctx, st, a));
     } else {
         hipLaunchKernelGGL(k_fold<F>, light_blocks + heavy_blocks, 64, 64 * XW * 4, st, (const HeavyDesc*)job->heavy, (const HeavyDesc*)job->heavy2,
                            (const uint32_t*)job->ctr, b.fold_done, b.sums, light_blocks);
         const GridSrc src{{(const uint32_t*)b.sums, nullptr, nullptr, nullptr}, 0u};
-        if (((size_t)job->Wb << job->log_nb) <= RED_DUAL_MAX_BUCKETS) {
-            const GridGeom gg = make_grid_geom(job->log_nb, job->Wb, RedG1Dual::PTS);
+        const uint32_t n_win = job->Wb * job->red_win;
+        if (((size_t)n_win << job->log_nb) <= RED_DUAL_MAX_BUCKETS) {
+            const GridGeom gg = make_grid_geom(job->log_nb, n_win, RedG1Dual::PTS);
             hipLaunchKernelGGL(k_grid_l1<RedG1Dual>, gg.row_blocks + gg.col_blocks, RedG1Dual::NT, RedG1Dual::PTS * XW * 4, st, src, b.rowP, b.colP, gg);
             hipLaunchKernelGGL(k_grid_bits<RedG1Dual>, gg.n_win * job->nout, RedG1Dual::NT, RedG1Dual::PTS * XW * 4, st, (const uint32_t*)b.rowP,
                                (const uint32_t*)b.colP, b.bits, gg);
         } else {
-            const GridGeom gg = make_grid_geom(job->log_nb, job->Wb, RedG1::PTS);
+            const GridGeom gg = make_grid_geom(job->log_nb, n_win, RedG1::PTS);
             hipLaunchKernelGGL(k_grid_l1<RedG1>, gg.row_blocks + gg.col_blocks, RedG1::NT, RedG1::PTS * XW * 4, st, src, b.rowP, b.colP, gg);
             hipLaunchKernelGGL(k_grid_bits<RedG1>, gg.n_win * job->nout, RedG1::NT, RedG1::PTS * XW * 4, st, (const uint32_t*)b.rowP,
                                (const uint32_t*)b.colP, b.bits, gg);                                                  // 48 KiB of LDS each
@@ -1046,8 +1064,9 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     tm->end();
     // pinned destination: a pageable one would make the "async" copy block the host until this job is done
     const ZkPin key = job->pin.kind != ZK_PIN_OF_SLOT ? job->pin : ZkPin{ZK_PIN_MSM_SLOT, (uint32_t)job->slot};
-    ZK_TRY(zk_pinned(ctx, key, std::max<size_t>((size_t)64 * 17, (size_t)job->Wb * job->nout) * XW * 4, (void**)&job->hw));
-    ZK_HIP(ctx, hipMemcpyAsync(job->hw, b.bits, (size_t)job->Wb * job->nout * XW * 4, hipMemcpyDeviceToHost, st));
+    const size_t nbits = (size_t)job->Wb * job->red_win * job->nout;
+    ZK_TRY(zk_pinned(ctx, key, std::max<size_t>((size_t)64 * 17, nbits) * XW * 4, (void**)&job->hw));
+    ZK_HIP(ctx, hipMemcpyAsync(job->hw, b.bits, nbits * XW * 4, hipMemcpyDeviceToHost, st));
     // finish() waits for this event, not for the stream: later jobs' reduce phases may be queued behind on the same stream
     ZK_HIP(ctx, hipEventCreateWithFlags(&job->reduce_done, hipEventDisableTiming));
     ZK_HIP(ctx, hipEventRecord(job->reduce_done, st));
@@ -1063,7 +1082,7 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
 constexpr uint32_t SS_GROUP_MAX_ENTRIES = 3u << 15;
 static bool sort_small_fits(const ZkMsmJob* j) {
     const bool merged = j->Wb == 1 && j->W > 1;
-    return j->n > 0 && merged && (size_t)j->W * j->n <= SS_GROUP_MAX_ENTRIES && j->NB <= SS_MAX_NB && j->seg <= SS_MAX_SEG;
+    return j->n > 0 && merged && !j->M && (size_t)j->W * j->n <= SS_GROUP_MAX_ENTRIES && j->NB <= SS_MAX_NB && j->seg <= SS_MAX_SEG;
 }
 static bool msm_sort_group_ok(ZkMsmJob* const* jobs, int count) {
     if (count < 1 || count > MSM_GROUP_MAX) return false;
@@ -1085,7 +1104,7 @@ static int msm_enqueue_sort_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count,
         for (int i = 0; i < 65; i++) a.wo.off[i] = job->off[i];
         a.wo.off[65] = 0;
         for (int i = 0; i < 9; i++) a.bias.w[i] = p.bias[i];
-        a.n_tab = job->n_tab; a.tab_off = job->tab_off;
+        a.n_tab = job->n_tab; a.tab_off = job->tab_off; a.lm = LevelMap{0, 0, 0};
         a.grp_base = (uint32_t)((size_t)job->Wb * job->NB + job->max_heavy_segs);
         a.dig = b.dig; a.sorted = b.sorted; a.desc = b.desc; a.heavy = b.heavy; a.heavy2 = b.heavy2; a.order = b.order; a.ctr = b.small + 64;
         job->sorted = b.sorted; job->desc = b.desc; job->order = b.order; job->ctr = b.small + 64; job->heavy = b.heavy; job->heavy2 = b.heavy2;
@@ -1117,7 +1136,7 @@ static bool msm_group_ok(ZkMsmJob* const* jobs, int count) {
     if (count < 2 || count > MSM_GROUP_MAX) return false;
     for (int k = 0; k < count; k++) {
         const ZkMsmJob* j = jobs[k];
-        if (j->group != 1 || j->n == 0 || j->Wb != 1 || j->log_nb != jobs[0]->log_nb || (j->stride == 64) != (jobs[0]->stride == 64) || !j->sort_done) return false;
+        if (j->group != 1 || j->n == 0 || j->Wb != 1 || j->M || j->log_nb != jobs[0]->log_nb || (j->stride == 64) != (jobs[0]->stride == 64) || !j->sort_done) return false;
         // (a job that fills the chip by itself gains nothing from company: Marlin rounds, same box, limit 2^21 / 2^23 / 2^24 digits --
         // |H| = 2^16 11.4 / 10.6 / -, 2^17 16.2 / 14.8 / -, 2^18 22.0 / 21.7 / 21.0, 2^19 34.8 / 35.0 / 34.9, 2^20 62.9 / - / 64.1 ms)
         if ((size_t)j->n * j->W > ((size_t)1 << 23)) return false;
@@ -1223,23 +1242,45 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
 // window sum = 2^cl * sum_j 2^j rowbit_j + sum_j 2^j colbit_j + (plain sum): ONE Horner chain over the row bits followed by
 // the column bits (msm_reduce.cuh), then Horner over the windows, most significant first (variable_base.rs:94-105).  All
 // in the 64-bit host field.  w counts bucket sets in job->hw.
+// set counts bucket sets in job->hw.  A set over shifted multiples (job->M > 0) is R = 2^M + 1 reduce windows of Nw = 2^log_nb compact
+// buckets; window w leaves T_w = sum_i S_i and, by the chain above, U_w = sum_i (i + 1) S_i.  Bucket i of window w carries the label
+//     w Nw + (i + 1)                      w = 0, 1     (the labels 1 .. D, D = 2 Nw)
+//     D + 2 (w - 2) Nw - 1 + 2 (i + 1)    w >= 2       (the odd labels above D)
+// so the set's sum is  U_0 + U_1 + 2 sum_{w>=2} U_w  +  Nw (T_1 + 2 sum_{w>=2} (w - 1) T_w)  -  sum_{w>=2} T_w.
+// The chain is linear in its nout points: the U terms are combined point by point and take ONE chain.
 template <class F>
-XYZZ<typename Host64Of<F>::type> msm_window_sum(const ZkMsmJob* job, size_t w) {
+XYZZ<typename Host64Of<F>::type> msm_set_sum(const ZkMsmJob* job, size_t set) {
     constexpr size_t XW = 4 * F::WORDS;
     using H = typename Host64Of<F>::type;
-    const uint32_t nout = job->nout;
-    const uint32_t* base = job->hw + w * nout * XW;
+    const uint32_t nout = job->nout, R = job->red_win;
+    const uint32_t* base = job->hw + set * R * nout * XW;
+    auto raw = [&](uint32_t w, uint32_t j) { return xyzz_to_host64<F>(xyzz_load<F>(base + ((size_t)w * nout + j) * XW)); };
+    auto pt = [&](uint32_t j) {                      // point j of the chain: of the one window, or U's combination over the windows
+        if (R == 1) return raw(0, j);
+        XYZZ<H> odd = raw(2, j);
+        for (uint32_t w = 3; w < R; w++) odd = xyzz_add<H>(odd, raw(w, j));
+        return xyzz_add<H>(xyzz_dbl<H>(odd), xyzz_add<H>(raw(0, j), raw(1, j)));
+    };
     XYZZ<H> ws = xyzz_inf<H>();
     const uint32_t cl = job->log_nb / 2, rl = job->log_nb - cl;
     for (int j = (int)rl - 1; j >= 0; j--) {
         ws = xyzz_dbl<H>(ws);
-        ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)j * XW)));
+        ws = xyzz_add<H>(ws, pt((uint32_t)j));
     }
     for (int j = (int)cl - 1; j >= 0; j--) {
         ws = xyzz_dbl<H>(ws);
-        ws = xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(rl + j) * XW)));
+        ws = xyzz_add<H>(ws, pt(rl + (uint32_t)j));
     }
-    return xyzz_add<H>(ws, xyzz_to_host64<F>(xyzz_load<F>(base + (size_t)(nout - 1) * XW)));
+    ws = xyzz_add<H>(ws, pt(nout - 1));
+    if (R == 1) return ws;
+    XYZZ<H> run = xyzz_inf<H>(), tot = xyzz_inf<H>();            // run = sum_{w' >= w} T_w', tot = sum_{w >= 2} (w - 1) T_w
+    for (uint32_t w = R - 1; w >= 2; w--) {
+        run = xyzz_add<H>(run, raw(w, nout - 1));
+        tot = xyzz_add<H>(tot, run);
+    }
+    XYZZ<H> lin = xyzz_add<H>(raw(1, nout - 1), xyzz_dbl<H>(tot));
+    for (uint32_t k = 0; k < job->log_nb; k++) lin = xyzz_dbl<H>(lin);
+    return xyzz_add<H>(xyzz_add<H>(ws, lin), xyzz_neg<H>(run));
 }
 
 template <class F>
@@ -1252,7 +1293,7 @@ int msm_finish_t(zk_ctx* ctx, ZkMsmJob* job, void* out_host) {
     else ZK_HIP(ctx, hipStreamSynchronize(job->stream));
     for (auto* t : job->timers) t->resolve();
     using H = typename Host64Of<F>::type;
-    auto window_sum = [&](uint32_t w) { return msm_window_sum<F>(job, w); };
+    auto window_sum = [&](uint32_t w) { return msm_set_sum<F>(job, w); };
     XYZZ<H> total = xyzz_inf<H>();
     // the per-window Horner chains (~15 doublings + 16 additions each for 16 windows) are independent: four host threads take
     // them, because the last job's finish sits on the proof's critical path.  A merged bucket set is one window: one chain.
@@ -1325,7 +1366,7 @@ int msm_finish_multi_t(zk_ctx* ctx, ZkMsmJob* job, void* outs) {
         for (int w = (int)nwin - 1; w >= 0; w--) {
             const uint32_t cw = nwin == 1 ? 0u : (uint32_t)(job->off[w + 1] - job->off[w]);
             for (uint32_t b = 0; b < cw; b++) total = xyzz_dbl<H>(total);
-            total = xyzz_add<H>(total, msm_window_sum<F>(job, k * nwin + (size_t)w));
+            total = xyzz_add<H>(total, msm_set_sum<F>(job, k * nwin + (size_t)w));
         }
         host64_write_projective<H>(xyzz_to_affine<H>(total), (uint64_t*)((P*)outs + k));
     };
@@ -1801,7 +1842,8 @@ int zk_msm_finish(zk_ctx* ctx, ZkMsmJob* job, void* out) {
 size_t zk_msm_multi_chunk(const zk_bases* bases, size_t n) {
     const bool merged = bases->pre != nullptr && (n >= 4096 || n * 8 >= bases->n);     // msm_prepare_t's choice
     const MsmPlan p = make_plan(n, merged ? bases->c_pre : 0);
-    const size_t buckets = (size_t)(merged ? 1 : p.W) * p.NB, digits = (size_t)p.W * n;
+    const size_t nb = merged && bases->pre_levels ? (p.NB >> 1) + (p.NB >> (1 + bases->pre_levels)) : p.NB;
+    const size_t buckets = (size_t)(merged ? 1 : p.W) * nb, digits = (size_t)p.W * n;
     return std::max<size_t>(1, std::min(MULTI_MAX_BUCKETS / buckets, MULTI_MAX_DIGITS / digits));
 }
 int zk_msm_prepare_multi(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n,

@@ -33,6 +33,23 @@ __device__ __forceinline__ int32_t signed_digit(uint64_t two, uint32_t bit, uint
     return (int32_t)((uint32_t)(two >> (bit & 31)) & mask) - (int32_t)half;
 }
 
+// Shifted window multiples (fixed_base.hip: a key's tables also hold 2^(c w + m) * P for m = 1 .. M).  A digit of magnitude d with
+// v trailing zero bits takes its point from level m = min(v, M) and goes to the bucket labelled d >> m: the labels that occur are
+// [1, D] and the odd ones in (D, 2^(c-1)], D = 2^(c-1-M) -- 2^(c-2) + 2^(c-2-M) buckets instead of 2^(c-1).  Compact bucket index:
+// label - 1 up to D, then D + (label - D - 1) / 2.  The reduce sees 2^M + 1 windows of D / 2 buckets (msm.hip: msm_set_sum has the
+// weights).  M = 0: the plain bucket mag - 1, level 0.
+struct LevelMap { uint32_t M, D, stride; };   // stride: table entries between two levels
+// mag >= 1.  Returns the bucket; eoff = what the level adds to the table index of the entry
+ZK_HD uint32_t level_bucket(uint32_t mag, const LevelMap& lm, uint32_t& eoff) {
+    eoff = 0;
+    if (!lm.M) return mag - 1;
+    uint32_t v = 0;
+    while (v < lm.M && !((mag >> v) & 1u)) v++;
+    eoff = v * lm.stride;
+    const uint32_t label = mag >> v;
+    return label <= lm.D ? label - 1 : lm.D + ((label - lm.D - 1) >> 1);
+}
+
 }  // namespace zk
 
 // What msm_sort.hip::zk_msm_group needs to know about one MSM: the scalars, the window plan, how a digit becomes a bucket id and a
@@ -46,6 +63,7 @@ struct ZkGroupArgs {
     bool merged;              // one bucket set for all windows (a table with window multiples): entry = w * n_tab + tab_off + i
     uint32_t n_tab, tab_off;
     uint32_t NBt;             // buckets in all (NB, or W * NB)
+    zk::LevelMap lm = {0, 0, 0};   // merged only: the table's shifted multiples (NB is then the compact bucket count)
     uint32_t lanes, seg_max;  // resident lanes of the accumulate kernel, and the segment length of a full-density input
     uint32_t* sorted;         // out: the entries grouped by bucket (room for W * n)
     uint32_t* offs;           // out: NBt + 1 bucket starts (offs[NBt] = the number of non-zero digits)

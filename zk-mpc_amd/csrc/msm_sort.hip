@@ -34,7 +34,7 @@ constexpr uint32_t G_CH = 32768;         // entries a bin block stages in LDS (1
 constexpr uint32_t G_MAXNC = 4096;       // bins (k_scan: 4 per lane of one block)
 constexpr uint32_t G_NONE = 0xffffffffu;
 
-struct GroupGeom { uint32_t W, NB, merged, n_tab, tab_off, NBt, F, NC; };
+struct GroupGeom { uint32_t W, NB, merged, n_tab, tab_off, NBt, F, NC; LevelMap lm; };
 // several vectors (ZkGroupArgs::vec_n): scalar j is element j % n of vector j / n, read at (j / n) * stride + j % n; its buckets are
 // offset by (j / n) * nb
 struct VecMap { uint32_t n, nb; size_t stride; };
@@ -62,6 +62,7 @@ __device__ __forceinline__ void load_scalar_words(const void* scalars, size_t i,
     for (int k = 0; k < 9; k++) kw[k][col] = w9[k];
 }
 // digit w of the scalar in column col: false for a zero digit; bucket = its id among all NBt buckets, neg = the sign bit of the entry
+// plus, for a table with shifted multiples, the offset of the digit's level (msm_digits.cuh: level_bucket)
 template <uint32_t TW>
 __device__ __forceinline__ bool tile_digit(const uint32_t (*kw)[TW], uint32_t col, const WinOff& wo, uint32_t w, const GroupGeom& g,
                                            uint32_t& bucket, uint32_t& neg, uint32_t bofs = 0) {
@@ -71,8 +72,9 @@ __device__ __forceinline__ bool tile_digit(const uint32_t (*kw)[TW], uint32_t co
     const int32_t d = signed_digit(two, bit, wo.off[w + 1] - bit);
     if (d == 0) return false;
     const uint32_t mag = d < 0 ? (uint32_t)(-d) : (uint32_t)d;
-    bucket = bofs + (g.merged ? 0u : w * g.NB) + mag - 1;
-    neg = d < 0 ? 0x80000000u : 0u;
+    uint32_t eoff;
+    bucket = bofs + (g.merged ? 0u : w * g.NB) + level_bucket(mag, g.lm, eoff);
+    neg = (d < 0 ? 0x80000000u : 0u) | eoff;
     return true;
 }
 
@@ -239,7 +241,7 @@ k_scatter_bins(const void* scalars, size_t n, WinOff wo, Bias bias, GroupGeom g,
                     if (!tile_digit<S_TILE>(kw, tid, wo, w, g, bucket, neg, bofs)) continue;
                     const uint32_t bin = bucket >> g.F;
                     const uint32_t p = atomicAdd(&cur[bin], 1u);
-                    st_val[p] = (g.merged ? (uint32_t)(w * g.n_tab + g.tab_off + idx) : idx) | neg;
+                    st_val[p] = (g.merged ? (uint32_t)(w * g.n_tab + g.tab_off + idx) : idx) + neg;     // (neg: bit 31 and the level's offset)
                     st_kb[p] = (bucket & fmask) | (bin << 16);
                 }
             __syncthreads();
@@ -378,7 +380,7 @@ k_bins(const uint16_t* __restrict__ key_lo, const uint32_t* __restrict__ val, co
 // of ~0.85 G_CH entries at full density so that an ordinary bin fits the LDS stage.
 static GroupGeom group_geom(const ZkGroupArgs& a) {
     GroupGeom g;
-    g.W = a.W; g.NB = a.NB; g.merged = a.merged ? 1u : 0u; g.n_tab = a.n_tab; g.tab_off = a.tab_off; g.NBt = a.NBt;
+    g.W = a.W; g.NB = a.NB; g.merged = a.merged ? 1u : 0u; g.n_tab = a.n_tab; g.tab_off = a.tab_off; g.NBt = a.NBt; g.lm = a.lm;
     uint32_t lg_nbt = 0;
     while (((uint64_t)1 << lg_nbt) < (uint64_t)a.NBt) lg_nbt++;
     const uint64_t total = (uint64_t)a.W * a.n;
