@@ -439,6 +439,43 @@ typedef struct {
 } zk_vk_host;
 int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok);
 
+/* ---- Marlin verification ------------------------------------------------------------------------------------------------------ */
+/* Marlin::verify (arkworks/marlin/src/lib.rs:324-442) with MarlinKZG10::check_combinations, for proofs as zk_marlin_prove writes them
+ * (CanonicalSerialize of marlin::Proof).  The key is a host view: the IndexVerifierKey's bytes as the transcript absorbs them and
+ * the parts of kzg10::VerifierKey the check needs.
+ *   ivk_bytes        IndexVerifierKey::write: index_info (3 x u64) | 12 index commitments, exactly zk_marlin_index.ivk_bytes.  A
+ *                    commitment is written as marlin_pc::Commitment::write does -- comm (x | y | infinity, 97 bytes) | shifted_exists
+ *                    | shifted_comm (97 bytes) -- so ivk_len = 24 + 12 x 195
+ *   g, gamma_g, h, beta_h    kzg10::VerifierKey
+ *   shift_h, shift_k         degree_bounds_and_shift_powers: powers_of_g[max_degree - (|H| - 2)], powers_of_g[max_degree - (|K| - 2)]
+ * The public input is padded with zeros to its domain's size (lib.rs:335-345).  The transcript is re-derived from ivk_bytes, the
+ * padded input and the proof's commitments; there is one pairing equation per query point, e(L_q, h) e(W_q, -beta_h) = 1, and the
+ * two are not folded together by a random coefficient (the verdict is a function of the inputs alone).
+ * ok = 0 with ZK_OK -- what is wrong with a PROOF: truncated or trailing bytes, an Option flag other than 0 or 1, a vector length
+ * other than the protocol's, a shifted commitment present or absent against the key's degree bounds (g_1, g_2), an evaluation or
+ * random_v not below r, an abscissa not below q or stray flag bits, bytes that are no curve point, a point outside the prime-order
+ * subgroup.  UNLIKE the library's other deserialisers (zk_bases_deserialize_compressed, zk_groth16_verify_batch), these two test
+ * subgroup membership of the proof's 13 points (r P = O): the reference's Proof::deserialize does, and the pairing's value on a point
+ * outside G1 is nothing the reference defines.
+ * ZK_ERR_ARG -- what is wrong with the CALL: a null pointer, ivk_len other than 24 + 12 x 195 or index commitments not written as
+ * above, a key point that is not a canonical curve point or is at infinity, an input not below r; for the batch also count = 0,
+ * count above 2^20 (four Miller lanes per proof) and decreasing offsets. */
+typedef struct {
+    const uint8_t* ivk_bytes; size_t ivk_len;
+    zk_g1_affine g, gamma_g;
+    zk_g2_affine h, beta_h;
+    zk_g1_affine shift_h, shift_k;
+} zk_marlin_vk_host;
+/* One proof through the host arithmetic: no device, no context. */
+int zk_marlin_verify_host(const zk_marlin_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t* proof, size_t proof_len, int* ok);
+/* count proofs of one key on the device: proof k is proofs_host[offsets[k] .. offsets[k + 1]) with the inputs
+ * inputs_host[k * inputs_per_proof ..]; ok[k] = 1 / 0, and a bad proof does not disturb its neighbours.  The 13 count points are
+ * decompressed on the device, the host derives each proof's transcript and term lists, one launch computes the 2 count combined
+ * commitments and the 13 count subgroup tests (one term per lane), then 4 count Miller loops and 2 count final exponentiations.
+ * The number of launches does not depend on count. */
+int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                           const uint8_t* proofs_host, const size_t* offsets, int* ok);
+
 /* ---- dense polynomials over Fr and KZG10 (row a14: the data-parallel pieces of the Marlin / poly-commit path) ---- */
 /* out[i] = start * base^i, i < n (device vector). */
 int zk_fr_powers_dev(zk_ctx* ctx, const zk_fr* base, const zk_fr* start, size_t n, void* out_dev);
@@ -743,6 +780,16 @@ int zk_diag_f7l_dev(zk_ctx* ctx, int op, const uint32_t* in26s, uint32_t* out26s
  * n_cases outside 1 .. 2^20. */
 int zk_diag_fq12_dev(zk_ctx* ctx, int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases);
 int zk_diag_fq12_host(int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases);
+/* Test hooks: n_segments short linear combinations of G1 points, out[s] = sum over t in [seg_offsets[s], seg_offsets[s + 1]) of
+ * scalars[t] * points[point_index[t]] -- as the device kernel of csrc/g1_lincomb.hip computes them (one term per lane, signed 4-bit
+ * windows, a segmented tree over the wave; the hook packs the segments into waves) and as the same per-term source computes them on
+ * the host (the sum there is a plain loop).  A scalar is 8 raw 32-bit words, little endian, all 256 bits used and never reduced; a
+ * point with all-zero words is infinity, and so is a result.  ZK_ERR_ARG: a null pointer, no segment or point, a segment of more
+ * than 64 terms, decreasing offsets or seg_offsets[0] != 0, an index >= n_points, a coordinate word not below q. */
+int zk_diag_g1_lincomb_dev(zk_ctx* ctx, const zk_g1_affine* points, size_t n_points, const uint32_t* point_index, const uint32_t* scalars,
+                           const uint32_t* seg_offsets, size_t n_segments, zk_g1_affine* out);
+int zk_diag_g1_lincomb_host(const zk_g1_affine* points, size_t n_points, const uint32_t* point_index, const uint32_t* scalars,
+                            const uint32_t* seg_offsets, size_t n_segments, zk_g1_affine* out);
 /* Diagnostic: k * a in G1 through the curve's endomorphism (hostfield64.hpp: host64_scalar_mul_glv: k split at lambda = z^2 - 1, one
  * joint chain) -- what the host tail of a Groth16 proof runs for keys made by zk_groth16_setup.  Equal to zk_g1_mul for every point of
  * the prime-order subgroup; kept apart from it because ProjectiveCurve::mul (zk_g1_mul) is defined on the whole curve. */

@@ -71,6 +71,11 @@ class VkHost(C.Structure):
                 ("gamma_abc_g1", C.c_void_p), ("gamma_abc_len", C.c_size_t)]
 
 
+class MarlinVkHost(C.Structure):
+    _fields_ = [("ivk_bytes", C.c_char_p), ("ivk_len", C.c_size_t), ("g", G1Affine), ("gamma_g", G1Affine),
+                ("h", G2Affine), ("beta_h", G2Affine), ("shift_h", G1Affine), ("shift_k", G1Affine)]
+
+
 class R1csHost(C.Structure):
     _fields_ = [("num_constraints", C.c_size_t), ("num_instance", C.c_size_t), ("num_witness", C.c_size_t),
                 ("a_row_ptr", C.c_void_p), ("a_col", C.c_void_p), ("a_coeff", C.c_void_p),
@@ -287,6 +292,10 @@ PROTOTYPES = {
     "zk_groth16_verify_host": (_I, [_P, _P, _SZ, _P, _P]),
     "zk_diag_fq12_dev": (_I, [_P, _I, _P, _P, _SZ]),
     "zk_diag_fq12_host": (_I, [_I, _P, _P, _SZ]),
+    "zk_marlin_verify_host": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
+    "zk_marlin_verify_batch": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P]),
+    "zk_diag_g1_lincomb_dev": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "zk_diag_g1_lincomb_host": (_I, [_P, _SZ, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

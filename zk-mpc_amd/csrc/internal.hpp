@@ -7,6 +7,7 @@
 #include <atomic>
 #include <functional>
 #include <string>
+#include <vector>
 
 // ntt.hip
 void zk_domains_free(zk_ctx* ctx);
@@ -22,7 +23,7 @@ int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, 
 int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
 
 // The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
-enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_COUNT };
+enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_COUNT };
 static_assert(ZK_LDS_COUNT <= sizeof(zk_ctx::lds_attr_done), "zk_ctx::lds_attr_done is too short");
 
 // rng.hip: four little-endian 64-bit words are a canonical field element (< r): what Fr::rand keeps and what a prover accepts from a peer
@@ -266,6 +267,25 @@ int zk_msm_early_finish(zk_ctx* ctx, ZkEarlyMsm* em, void* const* outs);      //
 int zk_decompress_launch(zk_ctx* ctx, int group, const uint32_t* in_dev, size_t n, uint32_t* out_dev, uint32_t* bad_dev, uint32_t* bad_each_dev);
 bool zk_host_decompress_g1(const uint8_t in[48], zk::Affine<zk::G1Field>* out);
 bool zk_host_decompress_g2(const uint8_t in[96], zk::Affine<zk::G2Field>* out);
+
+// pairing.hip: its Miller-loop and finish kernels for pairs that are on the device already (table form); lanes in one launch at most
+constexpr size_t ZK_PAIRING_MAX_LANES = (size_t)1 << 22;
+int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev);
+int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, const uint32_t* want_dev, const uint32_t* bad_dev, int* ok_dev);
+// g1_lincomb.hip: n_segments short linear combinations of G1 points in one launch, one term per lane.  Lane g holds point
+// point_index[g] of points_dev (table form; n_points of them) and the raw 256-bit scalar scalars_dev[8 g ..]; segment s is the lanes
+// seg_offsets[s] .. seg_offsets[s + 1] - 1, which must lie in one wave of 64 (ZkLincombPack lays the lanes out so); seg_offsets[0] = 0,
+// seg_offsets[n_segments] = n_lanes.  Out: segment s as an affine point (table form) and its infinity flag.  On ctx->stream, no wait.
+int zk_g1_lincomb_launch(zk_ctx* ctx, const uint32_t* points_dev, size_t n_points, const uint32_t* point_index_dev, const uint32_t* scalars_dev,
+                         const uint32_t* seg_offsets_dev, size_t n_segments, size_t n_lanes, uint32_t* out_affine_dev, uint32_t* out_is_inf_dev);
+// The lane layout of such a launch, built on the host segment by segment: a segment that would straddle a wave starts the next one, and
+// the lanes left over join the segment before them with a zero scalar.  add() refuses more than 64 terms.
+struct ZkLincombPack {
+    std::vector<uint32_t> point_index, scalars, seg_off;      // per lane; 8 words per lane; per segment (finish() appends the end)
+    size_t lanes() const { return point_index.size(); }
+    bool add(const uint32_t* idx, const uint32_t* k8, size_t len);
+    void finish() { seg_off.push_back((uint32_t)lanes()); }
+};
 
 // msm_sort.hip: the bucket sort (msm_digits.cuh declares its interface)
 

@@ -17,6 +17,7 @@
 #include "devutil.cuh"
 #include "hostgroup.hpp"
 #include "internal.hpp"
+#include "marlin_lc.hpp"
 #include "sharednet.hpp"
 #include "hostfield64.hpp"
 #include <algorithm>
@@ -29,54 +30,6 @@
 using namespace zk;
 
 namespace {
-
-// ---- Fr on the host (internal Montgomery form of the device arithmetic) ----
-struct HF {
-    Fr v;
-    static HF zero() { return HF{fp_zero<FrParams>()}; }
-    static HF one() { return HF{fp_one<FrParams>()}; }
-    static HF from_u64(uint64_t x) {
-        Fr t = fp_zero<FrParams>();
-        t.l[0] = (uint32_t)(x & MASK29); t.l[1] = (uint32_t)((x >> 29) & MASK29); t.l[2] = (uint32_t)(x >> 58);
-        return HF{fp_canon_to_int<FrParams>(t)};
-    }
-    static HF from_abi(const zk_fr& a) { return HF{fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a.l))}; }
-    zk_fr abi() const { zk_fr o; host_store_ext<FrParams>(o.l, fp_int_to_ext<FrParams>(v)); return o; }
-    HF operator+(const HF& b) const { return HF{fp_add<FrParams>(v, b.v)}; }
-    HF operator-(const HF& b) const { return HF{fp_sub<FrParams>(v, b.v)}; }
-    HF operator*(const HF& b) const { return HF{fp_mul<FrParams>(v, b.v)}; }
-    HF neg() const { return HF{fp_neg<FrParams>(v)}; }
-    HF inv() const { return HF{fp_inv<FrParams>(v)}; }
-    bool is_zero() const { return fp_is_zero<FrParams>(v); }
-    bool operator==(const HF& b) const { return fp_eq<FrParams>(v, b.v); }
-    HF pow(uint64_t e) const {
-        HF r = one();
-        bool started = false;
-        for (int b = 63; b >= 0; b--) {
-            if (started) r = r * r;
-            if ((e >> b) & 1) { r = started ? r * *this : *this; started = true; }
-        }
-        return r;
-    }
-    void bytes(std::vector<uint8_t>& out) const {          // Fp::write: into_repr(), little endian
-        uint32_t w[8];
-        fp_pack<FrParams>(w, fp_int_to_canon<FrParams>(v));
-        for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) out.push_back((uint8_t)(w[i] >> (8 * b)));
-    }
-};
-
-struct Dom {
-    size_t size; uint32_t log; HF gen;
-    explicit Dom(size_t num_coeffs) {
-        log = 0;
-        while (((size_t)1 << log) < num_coeffs) log++;
-        size = (size_t)1 << log;
-        Fr w = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-        for (uint32_t i = 0; i < (uint32_t)FR_TWO_ADICITY - log; i++) w = fp_sqr<FrParams>(w);
-        gen = HF{w};
-    }
-    HF vanishing(const HF& t) const { return t.pow(size) - HF::one(); }
-};
 
 struct Poly { char* p = nullptr; size_t n = 0; };        // n coefficients on the device
 struct Comm { Affine<G1Field> c, s; bool has_shift = false; };
@@ -758,22 +711,13 @@ struct Marlin : MarlinArgs {
         HF d[3];                                                                  // a_denom, b_denom, c_denom
         for (int m = 0; m < 3; m++) d[m] = ba - alpha * row[m] - beta * col[m] + row_col[m];
         ZK_TRY(P.rc);
-        // construct_linear_combinations (ahp/mod.rs:112-290)
-        const HF v_h_beta = H.vanishing(beta), v_x_beta = beta.pow(ni) - one;
-        const HF r_alpha_at_beta = (alpha == beta) ? HF::from_u64(n) * alpha.pow(n - 1) : (v_h_alpha - v_h_beta) * (alpha - beta).inv();
-        HF x_beta = HF::zero(), g = one;                                           // the public input's polynomial at beta
-        if (v_x_beta.is_zero()) {
-            for (size_t k = 0; k < ni; k++, g = g * X.gen) if (g == beta) x_beta = pub[k];
-        } else {
-            const HF l0 = v_x_beta * HF::from_u64(ni).inv();
-            for (size_t k = 0; k < ni; k++, g = g * X.gen) x_beta = x_beta + pub[k] * (l0 * g * (beta - g).inv());
-        }
-        const LinComb outer = {{one, O_MASK_POLY}, {r_alpha_at_beta * (eta[0] + eta[2] * z_b_beta), O_Z_A}, {r_alpha_at_beta * eta[1] * z_b_beta, O_NONE},
-                               {(t_beta * v_x_beta).neg(), O_W}, {(t_beta * x_beta).neg(), O_NONE}, {v_h_beta.neg(), O_H_1},
-                               {(beta * g_1_beta).neg(), O_NONE}};
-        const HF da = d[0], db = d[1], dc = d[2], b_expr = da * db * dc * (gamma * g_2_gamma + t_beta * HF::from_u64(K.size).inv());
-        const LinComb inner = {{eta[0] * db * dc * vv, O_A_VAL}, {eta[1] * da * dc * vv, O_B_VAL}, {eta[2] * db * da * vv, O_C_VAL},
-                               {b_expr.neg(), O_NONE}, {K.vanishing(gamma).neg(), O_H_2}};
+        // construct_linear_combinations (ahp/mod.rs:112-290): the coefficients are marlin_lc.hpp's, shared with the verifier
+        MarlinLcIn in{alpha, {eta[0], eta[1], eta[2]}, beta, gamma, z_b_beta, t_beta, g_1_beta, g_2_gamma, {d[0], d[1], d[2]}, pub.data()};
+        const MarlinLc c = marlin_lc(H, K, X, in);
+        const HF da = d[0], db = d[1], dc = d[2];
+        const LinComb outer = {{one, O_MASK_POLY}, {c.z_a, O_Z_A}, {c.outer_c_zb, O_NONE}, {c.w, O_W}, {c.outer_c_x, O_NONE}, {c.h_1, O_H_1},
+                               {c.outer_c_g1, O_NONE}};
+        const LinComb inner = {{c.val[0], O_A_VAL}, {c.val[1], O_B_VAL}, {c.val[2], O_C_VAL}, {c.inner_c, O_NONE}, {c.h_2, O_H_2}};
         auto denom_lc = [&](int m) {
             return LinComb{{ba, O_NONE}, {alpha.neg(), index_of(m, ROW)}, {beta.neg(), index_of(m, COL)}, {one, index_of(m, ROW_COL)}};
         };

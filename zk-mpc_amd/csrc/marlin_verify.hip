@@ -1,0 +1,519 @@
+// marlin_verify.hip -- Marlin::verify: one proof on the host (zk_marlin_verify_host), a batch on the device (zk_marlin_verify_batch).
+//
+// Replaces (reference):
+//   Marlin::verify                                   arkworks/marlin/src/lib.rs:324-442
+//   Proof::deserialize                               marlin/src/data_structures.rs:99-110 (points through GroupAffine::deserialize:
+//                                                    canonical, on the curve, in the prime-order subgroup)
+//   AHPForR1CS::verifier_*_round, verifier_query_set, construct_linear_combinations   ahp/verifier.rs:42-170, ahp/mod.rs:112-290
+//   MarlinKZG10::check_combinations, accumulate_commitments_and_values, KZG10::check  poly-commit/src/marlin/mod.rs:309-420,
+//                                                    marlin_pc/mod.rs:342-400, kzg10/mod.rs:320-343
+// One equation builder, two back ends.  parse_proof reads the bytes (structure, canonical scalars and abscissae); build_equations
+// re-derives the transcript and turns (key, input, proof) into two lists of terms (point reference, Fr scalar), one per query point:
+//   L_q = sum_j xi^j (combination j of the commitments)  -  val_q g  -  random_v_q gamma_g  +  z_q W_q        (z = beta, gamma)
+// and the proof holds iff e(L_q, h) e(W_q, -beta_h) = 1 for both -- KZG10::check with the witness term moved to the left, so that G2
+// only ever sees the key's two points.  The two query points are NOT folded by a random coefficient (kzg10::batch_check takes an rng).
+// The host back end evaluates the terms with host64_scalar_mul and pairing.cuh over Fq264Field; the device back end is
+// g1_lincomb.hip (one wave per proof) followed by pairing.hip's kernels as they are.
+#include "../../include/zkmpc_hip.h"
+#include "devutil.cuh"
+#include "fsrng.hpp"
+#include "hostfield64.hpp"
+#include "hostgroup.hpp"
+#include "internal.hpp"
+#include "marlin_lc.hpp"
+#include "pairing.cuh"
+#include <chrono>
+#include <string.h>
+#include <vector>
+
+using namespace zk;
+
+namespace {
+
+using H2 = Fq264Field;
+constexpr int GTW = 144;
+constexpr size_t IVK_COMM = 2 * 97 + 1, IVK_LEN = 24 + 12 * IVK_COMM;      // marlin_pc::Commitment::write: comm | bool | shifted_comm
+
+// the points an equation refers to: the key's sixteen, then the proof's thirteen
+enum KeyPoint : uint32_t { KP_INDEX = 0 /* 12: a_row, a_col, a_val, a_row_col, b_.., c_.. */, KP_G = 12, KP_GAMMA_G, KP_SHIFT_H, KP_SHIFT_K, N_KEY_POINTS };
+enum ProofPoint : uint32_t { PP_W, PP_Z_A, PP_Z_B, PP_MASK, PP_T, PP_G_1, PP_H_1, PP_G_2, PP_H_2, PP_G_1_SHIFTED, PP_G_2_SHIFTED, PP_WIT_BETA, PP_WIT_GAMMA, N_PROOF_POINTS };
+enum Eval : int { E_A_DENOM, E_B_DENOM, E_C_DENOM, E_G_1, E_G_2, E_T, E_Z_B, N_EVALS };      // the proof's order (sorted labels)
+constexpr int ROUND_LEN[3] = {4, 3, 2};
+constexpr size_t MAX_INPUTS = (size_t)1 << 24;
+
+struct Key {
+    const uint8_t* ivk;
+    size_t num_constraints, num_non_zero;
+    Affine<G1Field> pts[N_KEY_POINTS];
+    Affine<G2Field> h, neg_beta_h;
+};
+
+bool bytes_below_q(const uint8_t b[48], uint8_t top_mask) {           // little-endian, the flag bits of the last byte masked away
+    uint64_t l[6];
+    uint8_t t[48];
+    memcpy(t, b, 48);
+    t[47] &= top_mask;
+    memcpy(l, t, 48);
+    return host64::cmp(l, host64::P) < 0;
+}
+Fq fq_from_canonical_bytes(const uint8_t b[48]) {
+    uint32_t w[12];
+    memcpy(w, b, 48);
+    return fp_canon_to_int<FqParams>(fp_unpack<FqParams>(w));
+}
+bool on_curve_g1(const Affine<G1Field>& p) {
+    using F = G1Field;
+    return F::eq(F::sqr(p.y), F::add(F::mul(F::sqr(p.x), p.x), F::one()));
+}
+bool on_curve_g2(const Affine<G2Field>& p) {
+    const Affine<H2> a = aff_to_host64<G2Field>(p);
+    return H2::eq(H2::sqr(a.y), H2::add(H2::mul(H2::sqr(a.x), a.x), Host64Curve<H2>::b()));
+}
+bool abi_words_below_q(const void* p, int n_fq) {
+    for (int i = 0; i < n_fq; i++)
+        if (host64::cmp((const uint64_t*)p + 6 * i, host64::P) >= 0) return false;
+    return true;
+}
+
+// what is wrong with the CALL (ZK_ERR_ARG): the key as the struct gives it
+bool load_key(const zk_marlin_vk_host* vk, Key* k) {
+    if (!vk || !vk->ivk_bytes || vk->ivk_len != IVK_LEN) return false;
+    k->ivk = vk->ivk_bytes;
+    uint64_t info[3];
+    memcpy(info, vk->ivk_bytes, 24);
+    k->num_constraints = info[1];
+    k->num_non_zero = info[2];
+    if (!info[1] || !info[2] || info[1] > ((uint64_t)1 << 40) || info[2] > ((uint64_t)1 << 40)) return false;
+    for (int i = 0; i < 12; i++) {
+        const uint8_t* c = vk->ivk_bytes + 24 + i * IVK_COMM;
+        // comm (x | y | infinity = 0), no shifted commitment: false, then GroupAffine::zero() = (0, 1, infinity = 1)
+        if (c[96] != 0 || c[97] != 0 || c[97 + 1 + 96] != 1 || c[98 + 48] != 1) return false;
+        for (int j = 0; j < 96; j++)
+            if (c[98 + j] != 0 && j != 48) return false;
+        if (!bytes_below_q(c, 0xff) || !bytes_below_q(c + 48, 0xff)) return false;
+        k->pts[KP_INDEX + i] = Affine<G1Field>{fq_from_canonical_bytes(c), fq_from_canonical_bytes(c + 48)};
+    }
+    const zk_g1_affine* g1s[4] = {&vk->g, &vk->gamma_g, &vk->shift_h, &vk->shift_k};
+    for (int i = 0; i < 4; i++) {
+        if (!abi_words_below_q(g1s[i], 2)) return false;
+        k->pts[KP_G + i] = host_aff_from_abi<G1Field>((const uint64_t*)g1s[i]);
+    }
+    for (int i = 0; i < (int)N_KEY_POINTS; i++)
+        if (aff_is_inf<G1Field>(k->pts[i]) || !on_curve_g1(k->pts[i])) return false;
+    if (!abi_words_below_q(&vk->h, 4) || !abi_words_below_q(&vk->beta_h, 4)) return false;
+    k->h = host_aff_from_abi<G2Field>((const uint64_t*)&vk->h);
+    const Affine<G2Field> bh = host_aff_from_abi<G2Field>((const uint64_t*)&vk->beta_h);
+    if (aff_is_inf<G2Field>(k->h) || aff_is_inf<G2Field>(bh) || !on_curve_g2(k->h) || !on_curve_g2(bh)) return false;
+    k->neg_beta_h = aff_neg<G2Field>(bh);
+    return true;
+}
+
+// the formatted public input 1 | inputs | zeros up to the domain's size (lib.rs:335-345); false: an input not below r
+bool load_input(const zk_fr* inputs, size_t n_inputs, std::vector<HF>* x) {
+    const Dom X(n_inputs + 1);
+    x->assign(X.size, HF::zero());
+    (*x)[0] = HF::one();
+    for (size_t i = 0; i < n_inputs; i++) {
+        if (!zk_fr_words_valid(inputs[i].l)) return false;
+        (*x)[i + 1] = HF::from_abi(inputs[i]);
+    }
+    return true;
+}
+
+// ---- the proof's bytes --------------------------------------------------------------------------------------------------------
+struct Parsed {
+    bool ok = false;                                // the structure, canonical scalars, canonical abscissae and flag bits
+    const uint8_t* pt[N_PROOF_POINTS] = {};         // 48 compressed bytes each
+    const uint8_t* ev_bytes = nullptr;              // 7 x 32, as absorbed
+    HF ev[N_EVALS];
+    bool has_rv[2] = {false, false};
+    HF rv[2];
+};
+bool fr_from_canonical_bytes(const uint8_t* b, HF* out) {
+    uint64_t l[4];
+    memcpy(l, b, 32);
+    if (!zk_fr_words_valid(l)) return false;
+    uint32_t w[8];
+    memcpy(w, b, 32);
+    *out = HF{fp_canon_to_int<FrParams>(fp_unpack<FrParams>(w))};
+    return true;
+}
+// GroupAffine::deserialize up to the curve: the infinity flag stands alone over an all-zero x, else x is below q
+bool point_bytes_canonical(const uint8_t b[48]) {
+    if (b[47] & 0x40) {
+        if (b[47] != 0x40) return false;
+        for (int i = 0; i < 47; i++) if (b[i]) return false;
+        return true;
+    }
+    return bytes_below_q(b, 0x3f);
+}
+Parsed parse_proof(const uint8_t* p, size_t len) {
+    Parsed r;
+    size_t pos = 0;
+    auto take = [&](size_t n) -> const uint8_t* {
+        if (len - pos < n) return nullptr;
+        const uint8_t* o = p + pos;
+        pos += n;
+        return o;
+    };
+    auto u64_is = [&](uint64_t want) {
+        const uint8_t* b = take(8);
+        uint64_t v;
+        if (!b) return false;
+        memcpy(&v, b, 8);
+        return v == want;
+    };
+    auto point = [&](uint32_t which) {
+        const uint8_t* b = take(48);
+        if (!b || !point_bytes_canonical(b)) return false;
+        r.pt[which] = b;
+        return true;
+    };
+    if (!u64_is(3)) return r;
+    uint32_t o = 0;
+    for (int rnd = 0; rnd < 3; rnd++) {
+        if (!u64_is((uint64_t)ROUND_LEN[rnd])) return r;
+        for (int i = 0; i < ROUND_LEN[rnd]; i++, o++) {
+            if (!point(o)) return r;
+            const uint8_t* has = take(1);
+            // a shifted commitment exactly where the key has a degree bound: g_1, g_2
+            if (!has || *has > 1 || (*has == 1) != (o == PP_G_1 || o == PP_G_2)) return r;
+            if (*has && !point(o == PP_G_1 ? PP_G_1_SHIFTED : PP_G_2_SHIFTED)) return r;
+        }
+    }
+    if (!u64_is(N_EVALS)) return r;
+    if (!(r.ev_bytes = take(32 * N_EVALS))) return r;
+    for (int i = 0; i < N_EVALS; i++)
+        if (!fr_from_canonical_bytes(r.ev_bytes + 32 * i, &r.ev[i])) return r;
+    if (!u64_is(3)) return r;
+    const uint8_t* msgs = take(3);                                     // three EmptyMessage: Option::None each
+    if (!msgs || msgs[0] || msgs[1] || msgs[2]) return r;
+    if (!u64_is(2)) return r;
+    for (int q = 0; q < 2; q++) {
+        if (!point(PP_WIT_BETA + q)) return r;
+        const uint8_t* has = take(1);
+        if (!has || *has > 1) return r;
+        r.has_rv[q] = *has == 1;
+        if (r.has_rv[q]) {
+            const uint8_t* b = take(32);
+            if (!b || !fr_from_canonical_bytes(b, &r.rv[q])) return r;
+        }
+    }
+    const uint8_t* evals = take(1);                                    // BatchLCProof.evals = None, then the end
+    if (!evals || *evals || pos != len) return r;
+    r.ok = true;
+    return r;
+}
+
+// ---- the equations ------------------------------------------------------------------------------------------------------------
+struct Term { uint32_t point; uint32_t k[8]; };     // point: a KeyPoint, or N_KEY_POINTS + a ProofPoint; k: the plain integer below r
+struct Equations { std::vector<Term> q[2]; };       // at beta, at gamma
+
+HF next_fr(zkfs::FiatShamirRng& fs) {               // Fr::rand (zk_rng_next_fr)
+    for (;;) {
+        zk_fr o;
+        for (int i = 0; i < 4; i++) o.l[i] = fs.r.next_u64();
+        o.l[3] &= 0xffffffffffffffffull >> 3;
+        if (zk_fr_words_valid(o.l)) return HF::from_abi(o);
+    }
+}
+HF sample_outside(const Dom& d, zkfs::FiatShamirRng& fs) {
+    HF t = next_fr(fs);
+    while (d.vanishing(t).is_zero()) t = next_fr(fs);
+    return t;
+}
+void g1_to_bytes(const Affine<G1Field>& p, std::vector<uint8_t>& out) {       // GroupAffine::write: x | y | infinity; zero() = (0, 1, true)
+    const size_t at = out.size();
+    out.resize(at + 97, 0);
+    if (aff_is_inf<G1Field>(p)) { out[at + 48] = 1; out[at + 96] = 1; return; }
+    fq_canonical_bytes(p.x, &out[at]);
+    fq_canonical_bytes(p.y, &out[at + 48]);
+}
+
+// pts: the proof's thirteen points, decompressed (by either back end).  x: load_input's.
+Equations build_equations(const Key& key, const std::vector<HF>& x, const Parsed& pr, const Affine<G1Field>* pts) {
+    const Dom H(key.num_constraints), K(key.num_non_zero), X(x.size());
+    std::vector<uint8_t> buf(11 + IVK_LEN);
+    memcpy(buf.data(), "MARLIN-2019", 11);
+    memcpy(buf.data() + 11, key.ivk, IVK_LEN);
+    for (size_t i = 1; i < x.size(); i++) x[i].bytes(buf);
+    zkfs::FiatShamirRng fs = zkfs::FiatShamirRng::from_seed(buf.data(), buf.size());
+    auto absorb_round = [&](int rnd, uint32_t first) {
+        buf.clear();
+        for (uint32_t o = first; o < first + (uint32_t)ROUND_LEN[rnd]; o++) {
+            const bool has = o == PP_G_1 || o == PP_G_2;
+            g1_to_bytes(pts[o], buf);
+            buf.push_back(has ? 1 : 0);
+            g1_to_bytes(has ? pts[o == PP_G_1 ? PP_G_1_SHIFTED : PP_G_2_SHIFTED] : aff_inf<G1Field>(), buf);
+        }
+        fs.absorb(buf);
+    };
+    MarlinLcIn in;
+    absorb_round(0, PP_W);
+    in.alpha = sample_outside(H, fs);
+    for (HF& e : in.eta) e = next_fr(fs);
+    absorb_round(1, PP_T);
+    in.beta = sample_outside(H, fs);
+    absorb_round(2, PP_G_2);
+    in.gamma = next_fr(fs);
+    fs.absorb(pr.ev_bytes, 32 * N_EVALS);
+    const uint64_t lo = fs.r.next_u64(), hi = fs.r.next_u64();        // u128::rand: the opening challenge
+    const HF two32 = HF::from_u64((uint64_t)1 << 32), xi = HF::from_u64(lo) + HF::from_u64(hi) * two32 * two32;
+    in.z_b_beta = pr.ev[E_Z_B]; in.t_beta = pr.ev[E_T]; in.g_1_beta = pr.ev[E_G_1]; in.g_2_gamma = pr.ev[E_G_2];
+    for (int m = 0; m < 3; m++) in.d[m] = pr.ev[E_A_DENOM + m];
+    in.x = x.data();
+    const MarlinLc c = marlin_lc(H, K, X, in);
+
+    Equations eq;
+    const HF one = HF::one();
+    auto term = [](std::vector<Term>& v, uint32_t point, const HF& k) {
+        Term t;
+        t.point = point;
+        k.canon_words(t.k);
+        v.push_back(t);
+    };
+    auto pp = [](uint32_t o) { return (uint32_t)N_KEY_POINTS + o; };
+    // a combination's constant terms move into its value (marlin/mod.rs:343-350); a degree-bounded oracle queried alone takes a
+    // second power of xi with shifted - v shift_power (marlin_pc/mod.rs:359-383)
+    {   // beta: g_1, outer_sumcheck, t, z_b
+        std::vector<Term>& v = eq.q[0];
+        HF cj = one, val = HF::zero();
+        term(v, pp(PP_G_1), cj); val = val + pr.ev[E_G_1] * cj; cj = cj * xi;
+        term(v, pp(PP_G_1_SHIFTED), cj); term(v, KP_SHIFT_H, (pr.ev[E_G_1] * cj).neg()); cj = cj * xi;
+        term(v, pp(PP_MASK), cj); term(v, pp(PP_Z_A), c.z_a * cj); term(v, pp(PP_W), c.w * cj); term(v, pp(PP_H_1), c.h_1 * cj);
+        val = val + (c.outer_c_zb + c.outer_c_x + c.outer_c_g1).neg() * cj; cj = cj * xi;
+        term(v, pp(PP_T), cj); val = val + pr.ev[E_T] * cj; cj = cj * xi;
+        term(v, pp(PP_Z_B), cj); val = val + pr.ev[E_Z_B] * cj;
+        term(v, KP_G, val.neg());
+        if (pr.has_rv[0]) term(v, KP_GAMMA_G, pr.rv[0].neg());
+        term(v, pp(PP_WIT_BETA), in.beta);
+    }
+    {   // gamma: a_denom, b_denom, c_denom, g_2, inner_sumcheck
+        std::vector<Term>& v = eq.q[1];
+        HF cj = one, val = HF::zero();
+        for (uint32_t m = 0; m < 3; m++) {
+            term(v, KP_INDEX + 4 * m + 0, (in.alpha * cj).neg()); term(v, KP_INDEX + 4 * m + 1, (in.beta * cj).neg()); term(v, KP_INDEX + 4 * m + 3, cj);
+            val = val + (in.d[m] - c.ba) * cj; cj = cj * xi;
+        }
+        term(v, pp(PP_G_2), cj); val = val + pr.ev[E_G_2] * cj; cj = cj * xi;
+        term(v, pp(PP_G_2_SHIFTED), cj); term(v, KP_SHIFT_K, (pr.ev[E_G_2] * cj).neg()); cj = cj * xi;
+        for (uint32_t m = 0; m < 3; m++) term(v, KP_INDEX + 4 * m + 2, c.val[m] * cj);
+        term(v, pp(PP_H_2), c.h_2 * cj);
+        val = val + c.inner_c.neg() * cj;
+        term(v, KP_G, val.neg());
+        if (pr.has_rv[1]) term(v, KP_GAMMA_G, pr.rv[1].neg());
+        term(v, pp(PP_WIT_GAMMA), in.gamma);
+    }
+    return eq;
+}
+
+void r_words(uint32_t w[8]) { fp_pack<FrParams>(w, fp_const<FrParams>(FrParams::P)); }      // r itself, for the subgroup test
+
+// pairs = 2 products against this: the Fq12 one, packed internal words (k_pairing_finish's `want`)
+void packed_one(uint32_t w[GTW]) {
+    memset(w, 0, GTW * 4);
+    Fq2Field::store(w, Fq2Field::one());
+}
+
+// proof k of a batch: its Miller pairs (L_beta, h), (W_beta, -beta_h), (L_gamma, h), (W_gamma, -beta_h), and per PRODUCT the flag
+// that voids it: the host's structural verdict, a point off the curve, a point outside the subgroup (r P != O)
+__global__ void __launch_bounds__(64) k_marlin_pairs(size_t count, const uint32_t* __restrict__ lc_out, const uint32_t* __restrict__ lc_inf,
+                                                     const uint32_t* __restrict__ pts, const uint32_t* __restrict__ g2, const uint32_t* __restrict__ host_bad,
+                                                     const uint32_t* __restrict__ bad_pt, uint32_t* __restrict__ P, uint32_t* __restrict__ Q,
+                                                     uint32_t* __restrict__ bad) {
+    const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    constexpr size_t SEGS = 2 + N_PROOF_POINTS;
+    const Affine<G2Field> h = aff_load16<G2Field>(g2, 0), nbh = aff_load16<G2Field>(g2, 1);
+    for (int q = 0; q < 2; q++) {
+        aff_store16<G1Field>(P, 4 * k + 2 * q, aff_load16<G1Field>(lc_out, SEGS * k + q));
+        aff_store16<G1Field>(P, 4 * k + 2 * q + 1, aff_load16<G1Field>(pts, N_KEY_POINTS + N_PROOF_POINTS * k + PP_WIT_BETA + q));
+        aff_store16<G2Field>(Q, 4 * k + 2 * q, h);
+        aff_store16<G2Field>(Q, 4 * k + 2 * q + 1, nbh);
+    }
+    uint32_t b = host_bad[k];
+    for (size_t i = 0; i < N_PROOF_POINTS; i++) b |= bad_pt[N_PROOF_POINTS * k + i] | (lc_inf[SEGS * k + 2 + i] ? 0u : 1u);
+    bad[2 * k] = bad[2 * k + 1] = b ? 1u : 0u;
+}
+
+struct Lap {
+    zk_ctx* ctx;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char* what) {                    // with zk_set_profiling: host wall-clock of a phase into "marlin_verify.<phase>"
+        if (!ctx->profiling) return;
+        const auto now = std::chrono::steady_clock::now();
+        auto& tm = ctx->timers[std::string("marlin_verify.") + what];
+        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
+        tm.count += 1;
+        t = now;
+    }
+};
+
+}  // namespace
+
+extern "C" int zk_marlin_verify_host(const zk_marlin_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t* proof, size_t proof_len, int* ok) {
+    ZK_API_BEGIN_NOCTX
+    if (!vk || !proof || !ok) return ZK_ERR_ARG;
+    Key key;
+    std::vector<HF> x;
+    if (!load_key(vk, &key) || (n_inputs && !inputs) || n_inputs > MAX_INPUTS || !load_input(inputs, n_inputs, &x)) return ZK_ERR_ARG;
+    *ok = 0;
+    const Parsed pr = parse_proof(proof, proof_len);
+    if (!pr.ok) return ZK_OK;
+    using H1 = Fq64Field;
+    Affine<G1Field> pts[N_PROOF_POINTS];
+    uint32_t rw[8];
+    r_words(rw);
+    for (uint32_t i = 0; i < N_PROOF_POINTS; i++) {
+        if (!zk_host_decompress_g1(pr.pt[i], &pts[i])) return ZK_OK;
+        // the plain chain, not the endomorphism's: the point is not known to be in the subgroup yet
+        if (!xyzz_is_inf<H1>(host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(pts[i])), rw))) return ZK_OK;
+    }
+    const Equations eq = build_equations(key, x, pr, pts);
+    const Affine<H2> q2[2] = {aff_to_host64<G2Field>(key.h), aff_to_host64<G2Field>(key.neg_beta_h)};
+    for (int q = 0; q < 2; q++) {
+        XYZZ<H1> L = xyzz_inf<H1>();
+        for (const Term& t : eq.q[q]) {
+            const Affine<G1Field>& p = t.point < N_KEY_POINTS ? key.pts[t.point] : pts[t.point - N_KEY_POINTS];
+            L = xyzz_add<H1>(L, host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(p)), t.k));
+        }
+        const Affine<H1> p2[2] = {xyzz_to_affine<H1>(L), aff_to_host64<G1Field>(pts[PP_WIT_BETA + q])};
+        Fq12<H2> e;
+        pairing_product<H2>(e, p2, q2, 2);
+        if (!fq12_eq<H2>(e, fq12_one<H2>())) return ZK_OK;
+    }
+    *ok = 1;
+    return ZK_OK;
+    ZK_API_END
+}
+
+extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                      const uint8_t* proofs_host, const size_t* offsets, int* ok) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !vk || !count || !proofs_host || !offsets || !ok || count > ZK_PAIRING_MAX_LANES / 4) return ZK_ERR_ARG;
+    for (size_t k = 0; k < count; k++)
+        if (offsets[k + 1] < offsets[k]) return ZK_ERR_ARG;
+    Key key;
+    if (!load_key(vk, &key) || (inputs_per_proof && !inputs_host) || inputs_per_proof > MAX_INPUTS) return ZK_ERR_ARG;
+    std::vector<std::vector<HF>> xs(count);
+    for (size_t k = 0; k < count; k++)
+        if (!load_input(inputs_host + k * inputs_per_proof, inputs_per_proof, &xs[k])) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_verify_batch: a public input is not below r");
+    Lap lap{ctx};
+
+    // 1. the bytes: structure on the host, the 13 count compressed points to the device (a proof without them: infinity)
+    constexpr size_t NP = N_PROOF_POINTS, SEGS = 2 + NP;
+    std::vector<Parsed> prs(count);
+    std::vector<uint8_t> comp(count * NP * 48, 0);
+    std::vector<uint32_t> host_bad(count);
+    for (size_t k = 0; k < count; k++) {
+        prs[k] = parse_proof(proofs_host + offsets[k], offsets[k + 1] - offsets[k]);
+        host_bad[k] = prs[k].ok ? 0u : 1u;
+        for (size_t i = 0; i < NP; i++) {
+            uint8_t* dst = &comp[(k * NP + i) * 48];
+            if (prs[k].ok) memcpy(dst, prs[k].pt[i], 48); else dst[47] = 0x40;
+        }
+    }
+    lap.lap("parse");
+    const size_t n_pts = N_KEY_POINTS + NP * count, n_pairs = 4 * count;
+    uint8_t* d_comp;
+    uint32_t *d_pts, *d_flags, *d_g2, *d_idx, *d_k, *d_off, *d_lc, *d_lcinf, *P, *Q, *ml;
+    ZK_TRY(zk_scratch(ctx, "mvfy_comp", comp.size(), (void**)&d_comp));
+    ZK_TRY(zk_scratch(ctx, "mvfy_pts", n_pts * 96, (void**)&d_pts));
+    // any | bad_pt (13 count) | host_bad (count) | bad (2 count) | ok (2 count)
+    ZK_TRY(zk_scratch(ctx, "mvfy_flags", (1 + NP * count + count + 2 * count + 2 * count) * 4, (void**)&d_flags));
+    ZK_TRY(zk_scratch(ctx, "mvfy_g2", 2 * 192 + GTW * 4, (void**)&d_g2));
+    uint32_t *bad_any = d_flags, *bad_pt = d_flags + 1, *d_host_bad = bad_pt + NP * count, *bad = d_host_bad + count;
+    int* d_ok = (int*)(bad + 2 * count);
+    hipStream_t st = ctx->stream;
+    ZkPhaseTimer tm(ctx);
+    ZK_HIP(ctx, hipMemcpyAsync(d_comp, comp.data(), comp.size(), hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemsetAsync(bad_any, 0, 4, st));
+    tm.begin("marlin_verify.k_decompress");
+    ZK_TRY(zk_decompress_launch(ctx, 1, (const uint32_t*)d_comp, NP * count, d_pts + N_KEY_POINTS * 24, bad_any, bad_pt));
+    tm.end();
+    // 2. the equations need the ordinates (the transcript absorbs x | y): back they come, with the curve flags
+    std::vector<uint32_t> pts_w(NP * count * 24), bad_pt_h(NP * count);
+    ZK_HIP(ctx, hipMemcpyAsync(pts_w.data(), d_pts + N_KEY_POINTS * 24, pts_w.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipMemcpyAsync(bad_pt_h.data(), bad_pt, bad_pt_h.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    lap.lap("decompress");
+    // the builders: ~90 us per proof on one thread -- at count 1 024 that was 91 ms of a 160 ms call, in eight ranges over the
+    // context's helper threads it is 12 ms of 60 - 80 (DESIGN 6 "Marlin verification", profiles/marlin_verify_batch*.jsonl); below 64
+    // proofs they are under a millisecond beside 33 ms of kernels and stay on the calling thread.  The packing stays in order.
+    std::vector<Equations> eqs(count);
+    auto build_range = [&](size_t from, size_t to) {
+        for (size_t k = from; k < to; k++) {
+            bool good = prs[k].ok;
+            for (size_t i = 0; i < NP && good; i++) good = bad_pt_h[k * NP + i] == 0;
+            if (!good) continue;
+            Affine<G1Field> pts[NP];
+            for (size_t i = 0; i < NP; i++) pts[i] = aff_load<G1Field>(&pts_w[(k * NP + i) * 24]);
+            eqs[k] = build_equations(key, xs[k], prs[k], pts);
+        }
+    };
+    {
+        const size_t parts = count >= 64 ? 8 : 1;
+        std::vector<ZkTask<void>> tasks;
+        for (size_t p = 1; p < parts; p++) tasks.push_back(zk_async(ctx, [&, p] { build_range(count * p / parts, count * (p + 1) / parts); }));
+        build_range(0, count / parts);
+        for (auto& t : tasks) t.get();
+    }
+    ZkLincombPack pk;
+    uint32_t rw[8];
+    r_words(rw);
+    for (size_t k = 0; k < count; k++) {
+        const Equations& eq = eqs[k];
+        for (int q = 0; q < 2; q++) {
+            std::vector<uint32_t> idx, ks;
+            for (const Term& t : eq.q[q]) {
+                idx.push_back(t.point < N_KEY_POINTS ? t.point : (uint32_t)(N_KEY_POINTS + NP * k + (t.point - N_KEY_POINTS)));
+                ks.insert(ks.end(), t.k, t.k + 8);
+            }
+            if (!pk.add(idx.data(), ks.data(), idx.size())) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_verify_batch: an equation has more than 64 terms");
+        }
+        for (size_t i = 0; i < NP; i++) {                               // r P_i, to be infinity
+            const uint32_t idx = (uint32_t)(N_KEY_POINTS + NP * k + i);
+            pk.add(&idx, rw, 1);
+        }
+    }
+    pk.finish();
+    lap.lap("build");
+    // 3. the key's constants, the term lists; combinations; pairs; pairings
+    struct Consts { uint32_t g1[N_KEY_POINTS * 24]; uint32_t g2[2 * 48]; uint32_t one[GTW]; } cs;
+    for (int i = 0; i < (int)N_KEY_POINTS; i++) aff_store<G1Field>(cs.g1 + 24 * i, key.pts[i]);
+    aff_store<G2Field>(cs.g2, key.h);
+    aff_store<G2Field>(cs.g2 + 48, key.neg_beta_h);
+    packed_one(cs.one);
+    ZK_TRY(zk_scratch(ctx, "mvfy_idx", pk.point_index.size() * 4, (void**)&d_idx));
+    ZK_TRY(zk_scratch(ctx, "mvfy_k", pk.scalars.size() * 4, (void**)&d_k));
+    ZK_TRY(zk_scratch(ctx, "mvfy_off", pk.seg_off.size() * 4, (void**)&d_off));
+    ZK_TRY(zk_scratch(ctx, "mvfy_lc", SEGS * count * 96, (void**)&d_lc));
+    ZK_TRY(zk_scratch(ctx, "mvfy_lcinf", SEGS * count * 4, (void**)&d_lcinf));
+    ZK_TRY(zk_scratch(ctx, "pair_p", n_pairs * 96, (void**)&P));
+    ZK_TRY(zk_scratch(ctx, "pair_q", n_pairs * 192, (void**)&Q));
+    ZK_TRY(zk_scratch(ctx, "pair_ml", n_pairs * GTW * 4, (void**)&ml));
+    ZK_HIP(ctx, hipMemcpyAsync(d_pts, cs.g1, sizeof cs.g1, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_g2, cs.g2, sizeof cs.g2 + sizeof cs.one, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_host_bad, host_bad.data(), count * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_idx, pk.point_index.data(), pk.point_index.size() * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_k, pk.scalars.data(), pk.scalars.size() * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_off, pk.seg_off.data(), pk.seg_off.size() * 4, hipMemcpyHostToDevice, st));
+    tm.begin("marlin_verify.k_lincomb");
+    ZK_TRY(zk_g1_lincomb_launch(ctx, d_pts, n_pts, d_idx, d_k, d_off, SEGS * count, pk.lanes(), d_lc, d_lcinf));
+    tm.end();
+    tm.begin("marlin_verify.k_pairing");
+    hipLaunchKernelGGL(k_marlin_pairs, (unsigned)((count + 63) / 64), 64, 0, st, count, (const uint32_t*)d_lc, (const uint32_t*)d_lcinf, (const uint32_t*)d_pts,
+                       (const uint32_t*)d_g2, (const uint32_t*)d_host_bad, (const uint32_t*)bad_pt, P, Q, bad);
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_TRY(zk_miller_launch(ctx, P, Q, n_pairs, ml));
+    ZK_TRY(zk_pairing_finish_launch(ctx, ml, 2, 2 * count, d_g2 + 2 * 48, bad, d_ok));
+    tm.end();
+    std::vector<int> ok2(2 * count);
+    ZK_HIP(ctx, hipMemcpyAsync(ok2.data(), d_ok, 2 * count * sizeof(int), hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t k = 0; k < count; k++) ok[k] = (ok2[2 * k] && ok2[2 * k + 1]) ? 1 : 0;
+    lap.lap("device");
+    tm.resolve();
+    return ZK_OK;
+    ZK_API_END
+}

@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(64) k_diag_fq12(int op, const uint32_t* __rest
 }
 
 inline unsigned blocks64(size_t n) { return (unsigned)((n + 63) / 64); }
-constexpr size_t PAIRING_MAX_LANES = (size_t)1 << 22;
+constexpr size_t PAIRING_MAX_LANES = ZK_PAIRING_MAX_LANES;
 
 // ---- host forms ----------------------------------------------------------------------------------------------------------------------
 Affine<Fq64Field> host_g1(const zk_g1_affine* p) {
@@ -177,6 +177,19 @@ void pk_e_alpha_beta(const zk_pk* pk, uint32_t out[GTW]) {
 }
 
 }  // namespace
+
+// the two kernels for a caller that has laid out its pairs on the device already (marlin_verify.hip): table-form points, `want` and
+// `bad` as k_pairing_finish takes them, ok[k] on the device; on ctx->stream, no wait
+int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev) {
+    hipLaunchKernelGGL(k_miller<false>, blocks64(n), 64, 0, ctx->stream, p_dev, q_dev, n, ml_dev);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, const uint32_t* want_dev, const uint32_t* bad_dev, int* ok_dev) {
+    hipLaunchKernelGGL(k_pairing_finish, blocks64(count), 64, 0, ctx->stream, ml_dev, pairs, count, (uint32_t*)nullptr, want_dev, bad_dev, ok_dev);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
 
 extern "C" int zk_gt_exponent_multiple(void) {
     ZK_API_BEGIN_NOCTX

@@ -409,3 +409,69 @@ def prove_native(keys: IndexKeys, assignment_dev: DevBuf, zk_rng, mask_on_device
     ctx._ck(ctx.lib.zk_marlin_prove(ctx.h, C.byref(d), srs.powers_g.h, srs.powers_gamma_g.h, C.c_void_p(assignment_dev.ptr), zk_rng.h,
                                     int(mask_on_device), out, cap, C.byref(n)))
     return bytes(out[:n.value])
+
+
+# ---- Marlin::verify (csrc/marlin_verify.hip) --------------------------------------------------------------------------------------
+
+class VerifierKey:
+    """The host view of a Marlin verifier key (include/zkmpc_hip.h: zk_marlin_vk_host): the IndexVerifierKey's bytes and the parts of
+    kzg10::VerifierKey the check needs.  From an IndexKeys (g, gamma_g and the two shift powers come out of its resident SRS tables)
+    plus the G2 side h, beta_h as affine arrays in the ABI's form (24 uint64 each), or field by field through `from_parts`."""
+
+    def __init__(self, keys: IndexKeys, h, beta_h):
+        srs = keys.srs
+        g = srs.powers_g.download(0, 1)[0]
+        gamma_g = srs.powers_gamma_g.download(0, 1)[0]
+        shift_h = srs.powers_g.download(srs.max_degree - keys.bounds["g_1"], 1)[0]
+        shift_k = srs.powers_g.download(srs.max_degree - keys.bounds["g_2"], 1)[0]
+        self._set(keys.ivk_bytes(), g, gamma_g, h, beta_h, shift_h, shift_k)
+
+    @classmethod
+    def from_parts(cls, ivk_bytes: bytes, g, gamma_g, h, beta_h, shift_h, shift_k) -> "VerifierKey":
+        self = cls.__new__(cls)
+        self._set(ivk_bytes, g, gamma_g, h, beta_h, shift_h, shift_k)
+        return self
+
+    def _set(self, ivk_bytes, g, gamma_g, h, beta_h, shift_h, shift_k):
+        import ctypes as C
+        self.ivk = bytes(ivk_bytes)
+        self.struct = _lib.MarlinVkHost()
+        self.struct.ivk_bytes, self.struct.ivk_len = self.ivk, len(self.ivk)
+        for field, arr, n in (("g", g, 12), ("gamma_g", gamma_g, 12), ("h", h, 24), ("beta_h", beta_h, 24), ("shift_h", shift_h, 12), ("shift_k", shift_k, 12)):
+            arr = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1)
+            if arr.size != n:
+                raise ValueError("%s: expected %d uint64 words" % (field, n))
+            C.memmove(C.addressof(getattr(self.struct, field)), arr.ctypes.data, n * 8)
+
+
+def _verify_args(inputs, count):
+    inp = np.ascontiguousarray(inputs, dtype=np.uint64)
+    return inp.reshape(count, -1, 4) if inp.size else np.zeros((count, 0, 4), np.uint64)
+
+
+def verify_host(vk: VerifierKey, inputs, proof: bytes) -> bool:
+    """Marlin::verify of one proof through the host arithmetic (no device): inputs (n, 4) Montgomery, the instance without its 1."""
+    import ctypes as C
+    inp = _verify_args(inputs, 1)
+    buf = np.frombuffer(bytes(proof) or b"\0", dtype=np.uint8)
+    ok = C.c_int(0)
+    rc = _lib.load().zk_marlin_verify_host(C.byref(vk.struct), inp.ctypes.data_as(C.c_void_p), inp.shape[1], buf.ctypes.data_as(C.c_void_p),
+                                           len(proof), C.byref(ok))
+    if rc != _lib.ZK_OK:
+        raise _lib.ZkError("zk_marlin_verify_host failed (%d)" % rc)
+    return bool(ok.value)
+
+
+def verify_batch(ctx: Context, vk: VerifierKey, inputs, proofs) -> np.ndarray:
+    """Marlin::verify of many proofs of one key on the device: inputs (count, n, 4) Montgomery, proofs a list of byte strings (they
+    need not have one length: a truncated proof is rejected, not an error); returns count verdicts (1 / 0)."""
+    import ctypes as C
+    count = len(proofs)
+    inp = _verify_args(inputs, count)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(p) for p in proofs])
+    buf = np.frombuffer(b"".join(bytes(p) for p in proofs) or b"\0", dtype=np.uint8)
+    ok = np.zeros(count, dtype=np.int32)
+    ctx._ck(ctx.lib.zk_marlin_verify_batch(ctx.h, C.byref(vk.struct), count, inp.ctypes.data_as(C.c_void_p), inp.shape[1],
+                                           buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), ok.ctypes.data_as(C.c_void_p)))
+    return ok
