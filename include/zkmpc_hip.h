@@ -316,6 +316,14 @@ const zk_bases* zk_pk_query_bases(const zk_pk* pk, int which);
  * lowered for small tables (a reduce window keeps at least 64 buckets).  zk_pk_mul_levels: what a resident key got. */
 int zk_msm_mul_levels(zk_ctx* ctx, int levels);
 uint32_t zk_pk_mul_levels(const zk_pk* pk);
+/* H over coset values: a key made by zk_groth16_setup also carries h_eval (D points: h_query through the transposes of coset_ifft
+ * and of the division by Z(g)) and l_eval_pad (l_query minus h_query through the transposes of ifft and of C, one point per
+ * variable).  Its local proofs (prove_dev / prove_queued / prove_batch) then stop the witness map at a o b on the coset: four
+ * transforms instead of six, no C mat-vec.  Same group elements, same proof bytes.  ZK_G16_EVAL_H=0 in the environment turns it
+ * off (no tables, the old witness map); an uploaded or deserialised key has no such tables, nor one set up where the key with them
+ * would take more than half of the free device memory (two more G1 tables with their window multiples: 28 GB at 2^20 points).
+ * zk_pk_eval_h: 1 if proofs of this key for this system take that path. */
+int zk_pk_eval_h(const zk_pk* pk, const zk_r1cs* r1cs);
 uint32_t zk_msm_mul_levels_clamp(uint32_t window_bits, uint32_t levels);   /* the M a table with windows of that width gets for `levels` */
 int zk_pk_download_g1(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g1_affine* out);
 int zk_pk_download_g2(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g2_affine* out);

@@ -186,6 +186,7 @@ PROTOTYPES = {
     "zk_pk_query_bases": (_P, [_P, _I]),
     "zk_msm_mul_levels": (_I, [_P, _I]),
     "zk_pk_mul_levels": (_U32, [_P]),
+    "zk_pk_eval_h": (_I, [_P, _P]),
     "zk_msm_mul_levels_clamp": (_U32, [_U32, _U32]),
     "zk_pk_download_g1": (_I, [_P, _P, _I, _SZ, _SZ, _P]),
     "zk_pk_download_g2": (_I, [_P, _P, _I, _SZ, _SZ, _P]),

@@ -952,6 +952,10 @@ class ProvingKey:
         """zk_pk_mul_levels: the shifted copies this key's tables carry."""
         return self.ctx.lib.zk_pk_mul_levels(self.h)
 
+    def eval_h(self, r1cs: "R1cs") -> bool:
+        """zk_pk_eval_h: local proofs of this key for this system multiply h_eval with a o b on the coset (four transforms per proof)."""
+        return bool(self.ctx.lib.zk_pk_eval_h(self.h, r1cs.h))
+
     def query_len(self, name: str) -> int:
         return self.ctx.lib.zk_pk_query_len(self.h, self.QUERIES[name])
 

@@ -402,8 +402,15 @@ uint32_t zk_mul_levels_for_key(zk_ctx* ctx, size_t n) {
     if (!M) return 0;
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    while (M && (size_t)(M + 1) * W * n * (4 * 256 + 96 + 192) > mem_free / 3) M--;
+    while (M && zk_key_tables_bytes(n, M, 4) > mem_free / 3) M--;
     return M;
+}
+// the tables of a key whose queries have n points, with M shifted copies: g1_tables G1 tables in the 256-byte form, the packed one
+// that lives beside the last while it is re-laid, one G2 table
+size_t zk_key_tables_bytes(size_t n, uint32_t M, int g1_tables) {
+    if (n < ZK_PRECOMP_MIN_POINTS || !precompute_enabled_by_default()) return n * ((size_t)g1_tables * 96 + 192);
+    const uint32_t c = precompute_window_bits(n), W = (255 + c - 1) / c;
+    return (size_t)(M + 1) * W * n * ((size_t)g1_tables * 256 + 96 + 192);
 }
 int zk_bases_precompute_levels(zk_ctx* ctx, zk_bases* b, uint32_t levels) {
     if (!precompute_enabled_by_default() || !b || b->n < ZK_PRECOMP_MIN_POINTS) return ZK_OK;

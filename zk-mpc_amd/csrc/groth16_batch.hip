@@ -84,7 +84,7 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
             zk_tail_chain_a(pk, &tails[k], a[k]);
             zk_tail_chain_b(pk, &tails[k], b1[k]);
             zk_tail_chain_2(pk, &tails[k], b2[k]);
-            zk_tail_finish(tails[k], hs[k], l[k], proofs + k * 192);
+            zk_tail_finish(tails[k], hs[k], l[k], proofs + k * 192, T.l_const);
         }
     });
     return ZK_OK;
@@ -157,7 +157,7 @@ int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size
         });
     });
     const std::function<void()> pre_ready = [&] { if (pre_task.valid()) pre_task.get(); };
-    const std::function<int()> wmap = [&] { return zk_groth16_witness_map_batch(ctx, r, count, z_dev, wm.p); };
+    const std::function<int()> wmap = [&] { return ZkG16Jobs(pk, r, nullptr, nullptr).witness_map_batch(ctx, count, z_dev, wm.p); };
     const std::function<int()> none = [] { return ZK_OK; };
     int rc = ZK_OK;
     for (size_t k0 = 0; k0 < count && rc == ZK_OK; k0 += chunk)

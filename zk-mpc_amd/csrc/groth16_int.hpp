@@ -17,6 +17,7 @@
 #include "../../include/zkmpc_hip.h"
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <future>
@@ -44,6 +45,13 @@ struct zk_pk {
     // L job indexes its table by the position in z like A and B do and reuses their sort of z[1..]; the instance part adds
     // infinity, which the complete addition skips.  Only the prover's pipeline reads it.
     zk_bases* l_pad = nullptr;
+    // H over coset values: with e = a o b on the coset, sum_i h_i H_i = sum_j e_j H'_j - sum_k z_k K_k, where H' is the
+    // transpose of coset_ifft and of the division by Z(g) applied to h_query, and K is h_query through the transposes of ifft and
+    // of C.  h_eval = the D points H'_j; l_eval_pad = l_pad with L_k - K_k in the witness slots and -K_k in the instance slots
+    // (slot 0, the constant's, is read by the proof tail: l_eval_0).  Built by zk_groth16_setup, where the trapdoor gives their
+    // scalars; a key that was loaded has neither and its proofs take the quotient's coefficients over h_query as before.
+    zk_bases *h_eval = nullptr, *l_eval_pad = nullptr;
+    zk::Affine<zk::G1Field> l_eval_0;
     // every point is a multiple of the generators (zk_groth16_setup): the proof tail may use the endomorphism (hostfield64.hpp:
     // host64_scalar_mul_glv); a deserialised key is not checked for subgroup membership and keeps the plain scalar multiplication
     bool points_in_subgroup = false;
@@ -95,9 +103,19 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc = nullptr);
 int zk_pk_make_l_pad(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: see zk_pk::l_pad
 int zk_pk_precompute(zk_ctx* ctx, zk_pk* pk);     // groth16_key.hip: window multiples of every query, then l_pad
+// ZK_G16_EVAL_H=0 in the environment (read once): no key gets h_eval / l_eval_pad and no prover reads them
+inline bool zk_g16_eval_h_enabled() {
+    static const bool on = [] { const char* e = getenv("ZK_G16_EVAL_H"); return !(e && *e && atoi(e) == 0); }();
+    return on;
+}
 // r1cs.hip: the witness map of count assignments (count x m elements back to back) with launches that do not grow with count;
 // abc = room for 6 count D elements, the count quotients in its first count D on return
 int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);
+// r1cs.hip: the witness map that ends at e = a o b on the coset (two mat-vecs, ifft and coset_fft of a and b, the product): what the
+// H job of a key with h_eval multiplies (zk_pk::h_eval).  The batch form takes the same abc and leaves the count e vectors in its
+// first count D elements.
+int zk_groth16_witness_map_eval_dev(zk_ctx* ctx, const zk_r1cs* r, const void* z, void* e);
+int zk_groth16_witness_map_eval_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);
 // every prover's check of the key against the system (groth16_pipeline.hip): the tables there, an instance, the four lengths
 int zk_groth16_key_matches(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r);
 int zk_next_z_drop(zk_ctx* ctx, bool drain);      // groth16_pipeline.hip: forget an announced next assignment (drain: its front and upload first)
@@ -105,6 +123,9 @@ int zk_next_z_drop(zk_ctx* ctx, bool drain);      // groth16_pipeline.hip: forge
 // The one statement of the five MSMs of create_proof (src/groth16.rs:160, :137, :148, :110, :106), in the fixed order 0 = B in G2, 1 = A,
 // 2 = B in G1, 3 = L, 4 = H: every prover reads its tables, offsets, scalars and lengths here.  z, h may be NULL where only the
 // lengths are wanted.  pad_l = false keeps L on l_query (the several-device prover cuts it by terms of the witness part).
+// The table also says WHICH witness map feeds job 4: with eval_h (a key with h_eval / l_eval_pad, the environment not against it, L
+// padded, and the caller not bringing a quotient of its own: quotient_given) job 4 is h_eval over the coset values e, job 3 is
+// l_eval_pad and the tail adds l_const; witness_map / witness_map_batch run the map that goes with the jobs.
 struct ZkG16Jobs {
     struct Job {
         const zk_bases* tab;
@@ -114,16 +135,36 @@ struct ZkG16Jobs {
     } j[5];
     size_t m, D;                // elements between two assignments / two quotients of a batch
     bool l_shared;              // L over l_pad reads z[1..] like jobs 0..2 (the instance meets infinity) and borrows their sort
-    ZkG16Jobs(const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h, bool pad_l = true) : m(r->ni + r->nw), D((size_t)1 << r->log_d) {
+    bool eval_h;                // job 4 = h_eval x e, job 3 = l_eval_pad x z[1..] (sharing the sort as l_pad does)
+    const zk::Affine<zk::G1Field>* l_const = nullptr;      // eval_h: -K_0, the constant variable's term of L, for zk_tail_finish
+    const zk_r1cs* r;
+    ZkG16Jobs(const zk_pk* pk, const zk_r1cs* r_, const void* z, const void* h, bool pad_l = true, bool quotient_given = false)
+        : m(r_->ni + r_->nw), D((size_t)1 << r_->log_d), r(r_) {
         const size_t nvars = m - 1;
         const char *z1 = z ? (const char*)z + 32 : nullptr, *zw = z ? (const char*)z + r->ni * 32 : nullptr;
-        l_shared = pad_l && pk->l_pad && pk->l_pad->n == nvars + 1 && (pk->l_pad->pre != nullptr) == (pk->a->pre != nullptr) &&
-                   pk->l_pad->c_pre == pk->a->c_pre && pk->l_pad->pre_levels == pk->a->pre_levels;
+        auto like_a = [&](const zk_bases* t) {
+            return t && t->n == nvars + 1 && (t->pre != nullptr) == (pk->a->pre != nullptr) && t->c_pre == pk->a->c_pre && t->pre_levels == pk->a->pre_levels;
+        };
+        l_shared = pad_l && like_a(pk->l_pad);
+        eval_h = pad_l && !quotient_given && zk_g16_eval_h_enabled() && pk->h_eval && pk->h_eval->n == D && like_a(pk->l_eval_pad);
         j[0] = {pk->b_g2, 1, z1, nvars};        // query[1..] x z[1..]
         j[1] = {pk->a, 1, z1, nvars};
         j[2] = {pk->b_g1, 1, z1, nvars};
         j[3] = l_shared ? Job{pk->l_pad, 1, z1, nvars} : Job{pk->l, 0, zw, r->nw};        // aux_assignment against l_query
         j[4] = {pk->h, 0, (const char*)h, std::min(pk->h->n, D)};        // min(len) rule (variable_base.rs:15-17): h_query has D-1 entries, h has D
+        if (eval_h) {
+            l_shared = true;
+            j[3] = {pk->l_eval_pad, 1, z1, nvars};
+            j[4] = {pk->h_eval, 0, (const char*)h, D};
+            l_const = &pk->l_eval_0;
+        }
+    }
+    // the witness map whose output job 4 reads, into h (one proof) or into abc (count proofs: zk_groth16_witness_map_batch's layout)
+    int witness_map(zk_ctx* ctx, const void* z, void* h) const {
+        return eval_h ? zk_groth16_witness_map_eval_dev(ctx, r, z, h) : zk_groth16_witness_map_dev(ctx, r, z, h);
+    }
+    int witness_map_batch(zk_ctx* ctx, size_t count, const void* z, void* abc) const {
+        return eval_h ? zk_groth16_witness_map_eval_batch(ctx, r, count, z, abc) : zk_groth16_witness_map_batch(ctx, r, count, z, abc);
     }
     // job k into scratch slot slot0 + k: of one proof (multi = 0), or as a multi-vector job of `multi` >= 1 proofs (assignments m,
     // quotients D elements apart; a batch's last chunk may be one proof and is collected as a multi job all the same)
@@ -161,7 +202,9 @@ void zk_tail_pre_2(const zk_pk* pk, ZkTail* t);
 void zk_tail_chain_a(const zk_pk* pk, ZkTail* t, const zk_g1_projective& a_sum);       // after pre_a
 void zk_tail_chain_b(const zk_pk* pk, ZkTail* t, const zk_g1_projective& b1_sum);      // after pre_b
 void zk_tail_chain_2(const zk_pk* pk, ZkTail* t, const zk_g2_projective& b2_sum);      // after pre_2
-void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
+// (l_const: ZkG16Jobs::l_const of the table the sums came from, NULL without)
+void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192],
+                    const zk::Affine<zk::G1Field>* l_const = nullptr);
 
 // The tail of a single proof: the pre terms start with the proof on the context's helper threads, under the device's work; the chains
 // as soon as A, B-in-G1 and B-in-G2 have delivered (abc_ready), while the devices still work on L and H.  The tasks reference this
@@ -177,7 +220,7 @@ class ZkProofTail {
     ZkProofTail(zk_ctx* c, const zk_pk* pk, const zk_fr* r_, const zk_fr* s_);
     void abc_ready(const zk_g1_projective& a_sum, const zk_g1_projective& b1_sum, const zk_g2_projective& b2_sum);
     void join();
-    void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]);
+    void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192], const zk::Affine<zk::G1Field>* l_const = nullptr);
 };
 
 namespace zk {

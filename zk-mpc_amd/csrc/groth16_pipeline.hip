@@ -62,7 +62,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc) {
     const auto t_enter = std::chrono::steady_clock::now();
     ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
-    const ZkG16Jobs T(pk, r, z, h_in ? h_in : h_scratch);
+    const ZkG16Jobs T(pk, r, z, h_in ? h_in : h_scratch, true, h_in != nullptr);      // (a caller's h is the quotient: over h_query)
     const size_t D = T.D, nvars = T.j[0].n;
     const bool l_shared = T.l_shared;
     ZK_TRY(zk_prover_streams(ctx, 1));
@@ -111,7 +111,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
     } else {
         if (rc == ZK_OK && !h_in) {
             tm.begin("witness_map");
-            rc = zk_groth16_witness_map_dev(ctx, r, z, h_scratch);
+            rc = T.witness_map(ctx, z, h_scratch);
             tm.end();
         }
         if (rc == ZK_OK) rc = T.prepare(ctx, 4, J[4], ZK_SLOT_G16);
@@ -182,7 +182,7 @@ int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const vo
         const ZkG16Jobs N(pk, r, zn, h_scratch);
         rc = N.prepare(ctx, 0, &nf->job, ZK_SLOT_G16);
         if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->job, s_acc, nullptr);
-        if (rc == ZK_OK) rc = zk_groth16_witness_map_dev(ctx, r, zn, h_scratch);
+        if (rc == ZK_OK) rc = N.witness_map(ctx, zn, h_scratch);
         if (rc == ZK_OK) {
             ZK_HIP(ctx, hipEventCreateWithFlags(&nf->wm_done, hipEventDisableTiming));
             ZK_HIP(ctx, hipEventRecord(nf->wm_done, ctx->stream));
@@ -286,7 +286,7 @@ extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const z
     std::unique_ptr<ZkPresort> p(new ZkPresort());
     p->pk = pk;
     p->z = z;
-    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr).prepare(ctx, 0, &p->job, ZK_SLOT_G16));
+    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr, true, true).prepare(ctx, 0, &p->job, ZK_SLOT_G16));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &p->job, ctx->aux[0], nullptr));
     ctx->presort = p.release();
     return ZK_OK;
@@ -313,7 +313,7 @@ extern "C" int zk_groth16_msms_begin_dev(zk_ctx* ctx, const zk_pk* pk, const zk_
     (void)hipEventDestroy(e0);
     std::unique_ptr<ZkPresort> p(new ZkPresort());
     p->pk = pk; p->z = z; p->r = r; p->begun = true;
-    const ZkG16Jobs T(pk, r, z, nullptr);
+    const ZkG16Jobs T(pk, r, z, nullptr, true, true);      // (zk_groth16_msms_dev brings the quotient)
     ZkMsmJob* J[4] = {&p->job, &p->j1, &p->j2, &p->j3};
     int rc = T.sort_z(ctx, J, s_sort, ZK_SLOT_G16);
     if (rc == ZK_OK && !T.l_shared) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);

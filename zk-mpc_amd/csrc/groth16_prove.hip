@@ -41,11 +41,12 @@ void zk_tail_chain_b(const zk_pk* pk, ZkTail* t, const zk_g1_projective& b1_sum)
 void zk_tail_chain_2(const zk_pk* pk, ZkTail* t, const zk_g2_projective& b2_sum) {
     t->b_aff = xyzz_to_affine<H2>(coeff<H2>(t->s_g2, pk->b0_g2, &b2_sum, pk->beta_g2));
 }
-void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
+void zk_tail_finish(const ZkTail& t, const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192], const Affine<G1Field>* l_const) {
     X1 g_c = xyzz_add<H1>(t.s_g_a, t.r_g1_b);                                                              // :169-174
     g_c = xyzz_add<H1>(g_c, xyzz_neg<H1>(t.r_s_delta));
     g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&l_sum));
     g_c = xyzz_add<H1>(g_c, host64_proj_from_abi<H1>((const uint64_t*)&h_sum));
+    if (l_const) g_c = xyzz_madd<H1>(g_c, aff_to_host64<G1Field>(*l_const));                                  // z_0 = 1 times -K_0 (zk_pk::l_eval_pad)
     g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(t.g_a)), proof);
     g2_serialize(aff_from_host64<G2Field>(t.b_aff), proof + 48);
     g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<H1>(g_c)), proof + 144);
@@ -75,9 +76,9 @@ void ZkProofTail::join() {
     if (pre_2.valid()) pre_2.wait();
 }
 
-void ZkProofTail::finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192]) {
+void ZkProofTail::finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192], const Affine<G1Field>* l_const) {
     join();
-    zk_tail_finish(t, h_sum, l_sum, proof);
+    zk_tail_finish(t, h_sum, l_sum, proof, l_const);
 }
 
 extern "C" int zk_groth16_prove_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const zk_fr* r_, const zk_fr* s_,
@@ -94,7 +95,7 @@ extern "C" int zk_groth16_prove_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs*
     const auto t_tail = std::chrono::steady_clock::now();      // what is left of the host work once the GPU is done
     tail.join();
     ZK_TRY(rc_msm);
-    tail.finish(m1[0], m1[1], proof);
+    tail.finish(m1[0], m1[1], proof, ZkG16Jobs(pk, r, nullptr, nullptr).l_const);      // (the table run_msms read)
     if (ctx->profiling) {
         auto& t = ctx->timers["host.tail"];
         t.ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_tail).count();

@@ -133,6 +133,7 @@ extern "C" int zk_bases_precompute(zk_ctx* ctx, zk_bases* b);
 constexpr uint32_t ZK_MSM_MAX_LEVELS = 3, ZK_MSM_MIN_LOG_NB = 6;
 extern "C" uint32_t zk_msm_mul_levels_clamp(uint32_t c, uint32_t levels);   // fixed_base.hip
 uint32_t zk_mul_levels_for_key(zk_ctx* ctx, size_t n);              // fixed_base.hip: what a proving key whose z tables have n points gets
+size_t zk_key_tables_bytes(size_t n, uint32_t M, int g1_tables);     // fixed_base.hip: device bytes of such a key's tables with M shifted copies
 int zk_bases_precompute_levels(zk_ctx* ctx, zk_bases* b, uint32_t levels);
 uint32_t zk_precompute_windows(size_t n);                            // fixed_base.hip: copies a table of n points would get
 int zk_bases_precompute_auto(zk_ctx* ctx, zk_bases* b);             // only when ZK_PRECOMP=1 (off by default: see fixed_base.hip)

@@ -242,6 +242,39 @@ int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, co
     return zk_vec_sub_scale_launch(ctx, a, c, zinv, a, total);
 }
 
+// The witness map for a key that carries h_eval (zk_pk::h_eval): it ends at e = a o b on the coset.  The rest of the map above -- c,
+// coset_ifft, (. - c) / Z(g) -- is linear in (e, z) and sits in the key's tables: four transforms instead of six, no C mat-vec.
+int zk_groth16_witness_map_eval_dev(zk_ctx* ctx, const zk_r1cs* r, const void* z, void* e) {
+    if (!ctx || !r || !z || !e) return ZK_ERR_ARG;
+    const size_t D = (size_t)1 << r->log_d;
+    void* b;
+    ZK_TRY(zk_scratch(ctx, "wm_b", D * 32, &b));
+    ZK_TRY(spmv(ctx, r, 0, z, r->ni, e));
+    ZK_TRY(spmv(ctx, r, 1, z, 0, b));
+    void* v[2] = {e, b};
+    ZK_TRY(zk_ntt_launch_batch(ctx, v, 2, r->log_d, 1, 0));    // ifft of a, b
+    ZK_TRY(zk_ntt_launch_batch(ctx, v, 2, r->log_d, 0, 1));    // coset_fft of a, b
+    return zk_vec_op_launch(ctx, ZK_OP_MUL, e, b, e, D);
+}
+
+// ... for count assignments, in zk_groth16_witness_map_batch's buffer: a | b in the first 2 count D elements, the transforms' scratch
+// behind them; the count e vectors in the first count D on return
+int zk_groth16_witness_map_eval_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc) {
+    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, total = count * D;
+    char* a = (char*)abc;
+    char *b = a + total * 32, *tmp = b + total * 32;
+    const unsigned g = zk_grid(total, 256);
+    for (int which = 0; which < 2; which++) {
+        const auto& mt = r->m[which];
+        hipLaunchKernelGGL(k_spmv_multi, g, 256, 0, ctx->stream, mt.row_ptr, mt.col, mt.coeff, mt.all_one ? 1 : 0, z, m, r->nc,
+                           which == 0 ? r->ni : (size_t)0, r->log_d, total, (void*)(which == 0 ? a : b));
+    }
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_TRY(zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 1, 0, tmp));    // ifft of every a, b
+    ZK_TRY(zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 0, 1, tmp));    // coset_fft of every a, b
+    return zk_vec_op_launch(ctx, ZK_OP_MUL, a, b, a, total);
+}
+
 extern "C" int zk_groth16_witness_map_dev(zk_ctx* ctx, const zk_r1cs* r, const void* z, void* h) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !r || !z || !h) return ZK_ERR_ARG;
