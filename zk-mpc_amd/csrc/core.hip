@@ -89,7 +89,7 @@ extern "C" int zk_ctx_destroy(zk_ctx* ctx) {
     for (auto st : ctx->aux) (void)hipStreamDestroy(st);
     if (ctx->acc_stream) (void)hipStreamDestroy(ctx->acc_stream);
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-    if (ctx->next_z_ready) (void)hipEventDestroy(ctx->next_z_ready);
+    if (ctx->next.ready) (void)hipEventDestroy(ctx->next.ready);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return ZK_OK;

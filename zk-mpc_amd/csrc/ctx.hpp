@@ -35,7 +35,7 @@ struct ZkXfer;         // hostxfer.hip
 struct ZkXferSmall;    // hostxfer.hip
 struct ZkBasesCache;   // bases_cache.hip
 struct ZkMsmSpec;      // msm.hip
-struct ZkPresort;      // groth16_int.hpp
+struct ZkG16Flight;    // groth16_int.hpp
 
 // The name of one of a context's pinned host buffers (core.hip: zk_pinned): what it is for (a ZkPinKind of internal.hpp) and which
 // one of that kind.  Two uses cannot meet in one buffer whatever their indices are.
@@ -156,21 +156,28 @@ struct zk_ctx {
     ZkXferSmall* xfer_small = nullptr;        // hostxfer.hip: rotating page-locked slots for transfers below 128 KiB
     ZkBasesCache* bases_cache = nullptr;      // bases_cache.hip: resident copies of host base slices seen by zk_msm_g1 / _g2
     ZkMsmSpec* msm_spec = nullptr;            // msm.hip: MSMs over the tables a caller asks for next with the same scalars, started ahead
-    ZkPresort* presort = nullptr;             // groth16_pipeline.hip: a sort of z[1..] enqueued ahead of zk_groth16_msms_dev
-    const void* next_z = nullptr;             // groth16_pipeline.hip: zk_groth16_hint_next_dev
-    // groth16_prove.hip: zk_groth16_hint_next (host-slice form): the announced assignment is uploaded on its own stream into the
-    // idle one of two device slots while the current proof runs; next_z_ready is recorded behind that copy
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t next_z_ready = nullptr;
-    int mul_levels = -1;                      // zk_msm_mul_levels: shifted copies the next proving key's tables get (-1: the default)
+    // groth16_pipeline.hip: MSM jobs of a proof enqueued ahead of it (a presort, a begun set, the next proof's front), and how its fronts go out
+    ZkG16Flight* flight = nullptr;
     bool chain_fronts = true;                 // zk_groth16_chain_fronts: a small proof's front carries the next proof's whole device chain
-    int front_parity = 0;                     // groth16_pipeline.hip: which pair of pinned result buffers the next chained front writes
-    const void* next_z_host = nullptr;        // the host buffer that was announced (matched by address by zk_groth16_prove)
-    const void* next_z_pk = nullptr;          // ... together with the key, the constraint system and the length it was announced for
-    const void* next_z_r = nullptr;
-    size_t next_z_m = 0;
-    void* next_z_dev = nullptr;               // where its copy lives
-    int z_slot = 0;                           // which of the two "prove_z" slots the CURRENT proof reads
+    int front_parity = 0;                     // which pair of pinned result buffers the next chained front writes
+    // The assignment announced for the next proof.  z alone: zk_groth16_hint_next_dev.  The rest: zk_groth16_prove_queued (host-slice
+    // form) -- the announced assignment is uploaded on its own stream into the idle one of two device slots while the current proof
+    // runs; `ready` is recorded behind that copy (created once, kept across announcements)
+    struct NextZ {
+        const void* z = nullptr;              // what the proof in between enqueues the front of (it takes the pointer)
+        const void* host = nullptr;           // the host buffer that was announced (matched by address by zk_groth16_prove_queued)
+        const void *pk = nullptr, *r = nullptr;      // ... together with the key, the constraint system and the length it was announced for
+        size_t m = 0;
+        void* dev = nullptr;                  // where its copy lives
+        hipEvent_t ready = nullptr;
+        int slot = 0;                         // which of the two "prove_z" slots the CURRENT proof reads
+        bool matches(const void* z_host, const void* pk_, const void* r_, size_t m_) const {
+            return host == z_host && dev && pk == pk_ && r == r_ && m == m_;
+        }
+        void clear() { z = host = pk = r = nullptr; dev = nullptr; m = 0; }
+    } next;
+    hipStream_t copy_stream = nullptr;        // the upload's stream
+    int mul_levels = -1;                      // zk_msm_mul_levels: shifted copies the next proving key's tables get (-1: the default)
     std::mutex mu;
     // timing of the most recent instrumented call (ms), filled when ZK_PROFILE env or explicit request
     struct Timer { float ms = 0; int count = 0; };

@@ -40,13 +40,7 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
                 const std::function<void()>& pre_ready, ZkTail* tails, uint8_t* proofs) {
     const ZkG16Jobs T(pk, r, z, h);
     hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;
-    struct Event {
-        hipEvent_t e = nullptr;
-        ~Event() { if (e) (void)hipEventDestroy(e); }
-    } e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(e0.e, ctx->stream));                  // z was produced on the context stream
-    ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0.e, 0));
+    ZK_TRY(zk_behind_context_stream(ctx, &s_sort, 1));               // z was produced on the context stream
     ZkMsmJob J[5];                                                   // 0: B in G2, 1: A, 2: B in G1, 3: L, 4: H
     struct Streams {                       // declared after the jobs: every exit drains the streams before the jobs and their events go
         zk_ctx* ctx;
@@ -56,8 +50,7 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
             (void)hipStreamSynchronize(ctx->stream);
         }
     } drain{ctx};
-    ZkMsmJob* const zj[4] = {&J[0], &J[1], &J[2], &J[3]};
-    ZK_TRY(T.sort_z(ctx, zj, s_sort, ZK_SLOT_G16_BATCH, cnt));
+    ZK_TRY(T.sort_z(ctx, J, s_sort, ZK_SLOT_G16_BATCH, cnt));
     if (!T.l_shared) ZK_TRY(zk_msm_enqueue_sort(ctx, &J[3], s_sort, nullptr));
     ZK_TRY(front());                                                 // the witness map on the context stream, beside the z sort
     ZK_TRY(T.prepare(ctx, 4, &J[4], ZK_SLOT_G16_BATCH, cnt));

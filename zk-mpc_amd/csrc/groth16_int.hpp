@@ -1,5 +1,5 @@
 // groth16_int.hpp -- what the Groth16 translation units share: the device-side constraint system and proving key, the state of a
-// proof's front that was enqueued ahead of its proof, and the pipeline's internal entry points.
+// jobs of a proof that were enqueued ahead of it (ZkG16Flight), and the pipeline's internal entry points.
 //   r1cs.hip             constraint system upload, sparse mat-vec, R1CStoQAP::witness_map          (src/groth16.rs:205-306)
 //   groth16_key.hip      proving key upload / accessors, generate_parameters with known toxic waste (generator.rs:44-231)
 //   key_io.hip           CanonicalSerialize framing of keys and SRS                                (data_structures.rs:133-151)
@@ -66,32 +66,32 @@ struct zk_pk {
     mutable uint32_t e_alpha_beta[144];
 };
 
-// A sort of z[1..] (shared by the B-in-G2 / A / B-in-G1 / L jobs) enqueued ahead of the MSMs: the collaborative prover
-// calls zk_groth16_msms_presort_dev right after the local half of the witness map, so the sort runs under the Beaver open
-// (network time) instead of in front of the first accumulate kernel.  Owned by the context until run_msms takes it over.
-struct ZkPresort {
-    ZkMsmJob job;
-    const zk_pk* pk = nullptr;
-    const void* z = nullptr;
-    // the whole FRONT of the next local proof (zk_groth16_hint_next_dev): besides the sort of z also its witness map and
-    // the H job's sort, enqueued behind the current proof's last kernels so that they run under its reduce tail and the
-    // host time between two proofs
-    bool front = false;
-    const zk_r1cs* r = nullptr;
-    void* h = nullptr;                 // where the witness map put h
-    ZkMsmJob jobh;
-    hipEvent_t wm_done = nullptr;
-    // zk_groth16_msms_begin_dev: not only the sort of z but the four MSMs over z -- A, B in G1, B in G2, L: sorted, their
-    // accumulate kernels and reduce chains enqueued -- are under way; zk_groth16_msms_dev then adds the H job and collects all
-    // five.  The collaborative prover calls it before its Beaver open: the exchange and the second half of the witness map run
-    // under 12 ms of accumulate kernels that do not need h.
-    bool begun = false;
-    ZkMsmJob j1, j2, j3;
-    // a SMALL local proof's front carries its whole device chain (groth16_pipeline.hip: "chained"): besides the sorts and the witness
-    // map also the accumulate launches and reduce chains of all five jobs are enqueued behind the current proof's -- the device
-    // goes from one proof's chain into the next while the host still finishes the first
-    bool chained = false;
-    ~ZkPresort() { if (wm_done) (void)hipEventDestroy(wm_done); }
+// The five MSM jobs of ONE proof, in ZkG16Jobs order (0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H), and how far each has been
+// enqueued.  run_msms drives its own proof's flight through the stages; one that was started AHEAD of its proof is owned by the
+// context (zk_ctx::flight) until run_msms takes it over or zk_presort_free drains and drops it:
+//   at[0] == SORTED alone: a sort of z[1..] (shared by the B-in-G2 / A / B-in-G1 / L jobs).  The collaborative prover calls zk_groth16_
+//     msms_presort_dev right after the local half of the witness map: the sort runs under the Beaver open, not in front of the first accumulate.
+//   at[0] == REDUCED, at[1..3] == ACCUMULATED (zk_groth16_msms_begin_dev): not only the sort of z but the four MSMs over z are under
+//     way; zk_groth16_msms_dev then adds the H job and collects all five.  The collaborative prover calls it before its Beaver open:
+//     the exchange and the second half of the witness map run under 12 ms of accumulate kernels that do not need h.
+//   at[0] == SORTED, at[4] == SORTED, h and wm_done set: the whole FRONT of the next local proof (zk_groth16_hint_next_dev) --
+//     besides the sort of z also its witness map and the H job's sort, enqueued behind the current proof's last kernels so that
+//     they run under its reduce tail and the host time between two proofs.
+//   all five REDUCED: a SMALL local proof's front carries its whole device chain -- besides the sorts and the witness map also the
+//     accumulate launches and reduce chains of all five jobs are enqueued behind the current proof's; the device goes from one
+//     proof's chain into the next while the host still finishes the first.
+struct ZkG16Flight {
+    const zk_pk* pk; const zk_r1cs* r; const void* z;      // whose proof
+    void* h;                           // where its witness map wrote (NULL: none ran; the caller brings h)
+    ZkMsmJob J[5];
+    ZkMsmJob* const g1[4] = {&J[1], &J[2], &J[3], &J[4]};      // the four G1 jobs, as the group calls take them
+    enum Stage : uint8_t { NONE, SORTED, ACCUMULATED, REDUCED } at[5] = {NONE, NONE, NONE, NONE, NONE};
+    hipEvent_t wm_done = nullptr;      // recorded behind the witness map: gates the first accumulate kernel (and a late sort of L)
+    bool grouped = false;              // jobs 1..4 go / went out as one group launch
+    bool beyond_sort_z() const { return at[1] || at[2] || at[3] || at[4]; }      // (then zk_presort_free drains more than the sort stream)
+    ZkG16Flight(const zk_pk* pk_, const zk_r1cs* r_, const void* z_, void* h_) : pk(pk_), r(r_), z(z_), h(h_) {}
+    ZkG16Flight(const ZkG16Flight&) = delete; ZkG16Flight& operator=(const ZkG16Flight&) = delete;      // (g1 points into this object)
+    ~ZkG16Flight() { if (wm_done) (void)hipEventDestroy(wm_done); }
 };
 
 // the context's helper streams: aux[0..k) and the accumulate stream (created on first use)
@@ -119,6 +119,8 @@ int zk_groth16_witness_map_eval_batch(zk_ctx* ctx, const zk_r1cs* r, size_t coun
 // every prover's check of the key against the system (groth16_pipeline.hip): the tables there, an instance, the four lengths
 int zk_groth16_key_matches(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r);
 int zk_next_z_drop(zk_ctx* ctx, bool drain);      // groth16_pipeline.hip: forget an announced next assignment (drain: its front and upload first)
+// groth16_pipeline.hip: z was produced on the context stream -- the waiters go on behind what that stream carries now
+int zk_behind_context_stream(zk_ctx* ctx, const hipStream_t* waiters, int count);
 
 // The one statement of the five MSMs of create_proof (src/groth16.rs:160, :137, :148, :110, :106), in the fixed order 0 = B in G2, 1 = A,
 // 2 = B in G1, 3 = L, 4 = H: every prover reads its tables, offsets, scalars and lengths here.  z, h may be NULL where only the
@@ -173,15 +175,16 @@ struct ZkG16Jobs {
         return zk_msm_prepare_multi(ctx, job, j[k].tab, j[k].off, j[k].scal, j[k].n, k == 4 ? D : m, multi, slot0 + k);
     }
     // The z jobs J[0..3] prepared and their sorts enqueued on st: job 0 sorts, A borrows its sort, B in G1 and a
-    // shared L borrow from the lender.  have0: J[0] is prepared and sorted already.  An L of its own is sorted by the caller.
-    int sort_z(zk_ctx* ctx, ZkMsmJob* const* J, hipStream_t st, ZkMsmSlot slot0, size_t multi = 0, bool have0 = false) const {
-        for (int k = have0 ? 1 : 0; k < 4; k++) ZK_TRY(prepare(ctx, k, J[k], slot0, multi));
-        if (!have0) ZK_TRY(zk_msm_enqueue_sort(ctx, J[0], st, nullptr));
-        ZK_TRY(zk_msm_enqueue_sort(ctx, J[1], st, J[0]));
+    // shared L borrow from the lender.  have0: J[0] is prepared and sorted already; njobs = 1: job 0 alone.  An L of its own is sorted by the caller.
+    int sort_z(zk_ctx* ctx, ZkMsmJob* J, hipStream_t st, ZkMsmSlot slot0, size_t multi = 0, bool have0 = false, int njobs = 4) const {
+        for (int k = have0 ? 1 : 0; k < njobs; k++) ZK_TRY(prepare(ctx, k, &J[k], slot0, multi));
+        if (!have0) ZK_TRY(zk_msm_enqueue_sort(ctx, &J[0], st, nullptr));
+        if (njobs == 1) return ZK_OK;
+        ZK_TRY(zk_msm_enqueue_sort(ctx, &J[1], st, &J[0]));
         // (the G2 table may carry windows of another width than the G1 tables: then A sorts for itself and the other G1 jobs borrow A's)
-        const ZkMsmJob* lender = J[0]->c == J[1]->c ? J[0] : J[1];
-        ZK_TRY(zk_msm_enqueue_sort(ctx, J[2], st, lender));
-        return l_shared ? zk_msm_enqueue_sort(ctx, J[3], st, lender) : ZK_OK;
+        const ZkMsmJob* lender = J[0].c == J[1].c ? &J[0] : &J[1];
+        ZK_TRY(zk_msm_enqueue_sort(ctx, &J[2], st, lender));
+        return l_shared ? zk_msm_enqueue_sort(ctx, &J[3], st, lender) : ZK_OK;
     }
 };
 

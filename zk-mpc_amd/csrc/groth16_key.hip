@@ -110,7 +110,7 @@ extern "C" int zk_msm_mul_levels(zk_ctx* ctx, int levels) {
 extern "C" int zk_pk_free(zk_ctx* ctx, zk_pk* pk) {
     ZK_API_BEGIN(ctx)
     if (!pk) return ZK_OK;
-    // a pending presort / front (ZkPresort) is matched by address: it must not outlive the objects it points to, or a new
+    // a pending presort / front (ZkG16Flight) is matched by address: it must not outlive the objects it points to, or a new
     // key allocated at the same address would adopt a sort of the old key's tables
     zk_presort_free(ctx);
     zk_bases* all[9] = {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l, pk->gamma_abc, pk->l_pad, pk->h_eval, pk->l_eval_pad};

@@ -1,21 +1,23 @@
 // groth16_pipeline.hip -- the five MSMs of create_proof (src/groth16.rs:106,110,137,148,160) as a pipeline over three streams, with
-// the next proof's front and the collaborative prover's presorts enqueued ahead of their proofs.
+// the next proof's front and the collaborative prover's presorts enqueued ahead of their proofs (ZkG16Flight).
 #include "../../include/zkmpc_hip.h"
 #include "groth16_int.hpp"
 #include <chrono>
 
 using namespace zk;
+using Stage = ZkG16Flight::Stage;
+
+static void drain_streams(zk_ctx* ctx) {                  // the three streams of the pipeline (zk_prover_streams has run)
+    (void)hipStreamSynchronize(ctx->aux[0]);
+    (void)hipStreamSynchronize(ctx->acc_stream);
+    (void)hipStreamSynchronize(ctx->stream);
+}
 
 void zk_presort_free(zk_ctx* ctx) {
-    if (!ctx || !ctx->presort) return;
-    ZkPresort* p = ctx->presort;
-    ctx->presort = nullptr;
-    if (ctx->aux.size()) (void)hipStreamSynchronize(ctx->aux[0]);   // its kernels write the job's scratch slot
-    if (p->front || p->begun) {                                     // these run on the accumulate and context streams as well
-        if (ctx->acc_stream) (void)hipStreamSynchronize(ctx->acc_stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    delete p;
+    if (!ctx || !ctx->flight) return;
+    const std::unique_ptr<ZkG16Flight> f(std::exchange(ctx->flight, nullptr));
+    if (f->beyond_sort_z()) drain_streams(ctx);                     // its kernels run on the accumulate and context streams as well
+    else (void)hipStreamSynchronize(ctx->aux[0]);           // its kernels write the job's scratch slot
 }
 
 int zk_next_z_drop(zk_ctx* ctx, bool drain) {
@@ -23,11 +25,7 @@ int zk_next_z_drop(zk_ctx* ctx, bool drain) {
         zk_presort_free(ctx);
         if (ctx->copy_stream) ZK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
-    ctx->next_z = nullptr;
-    ctx->next_z_host = nullptr;
-    ctx->next_z_dev = nullptr;
-    ctx->next_z_pk = ctx->next_z_r = nullptr;
-    ctx->next_z_m = 0;
+    ctx->next.clear();
     return ZK_OK;
 }
 
@@ -51,6 +49,27 @@ int zk_prover_streams(zk_ctx* ctx, size_t k) {
     return ZK_OK;
 }
 
+int zk_behind_context_stream(zk_ctx* ctx, const hipStream_t* waiters, int count) {
+    if (count <= 0) return ZK_OK;
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } e0;      // destroyed on every exit path
+    ZK_HIP(ctx, hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
+    ZK_HIP(ctx, hipEventRecord(e0.e, ctx->stream));
+    for (int k = 0; k < count; k++) ZK_HIP(ctx, hipStreamWaitEvent(waiters[k], e0.e, 0));
+    return ZK_OK;
+}
+
+namespace {
+
+// What every entry point here does first: a pending flight that is not this call's goes, the key is checked, the helper streams are
+// there, and the first `waiters` of {sort stream, accumulate stream} wait for the context stream, where z was produced.
+int enter(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, bool keep_flight, int waiters) {
+    if (!keep_flight) zk_presort_free(ctx);
+    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
+    ZK_TRY(zk_prover_streams(ctx, 1));
+    const hipStream_t w[2] = {ctx->aux[0], ctx->acc_stream};
+    return zk_behind_context_stream(ctx, w, waiters);
+}
+
 // The five MSMs of create_proof as a pipeline over THREE streams (the runtime maps streams onto ~3
 // usable hardware queues; a fourth stream lands on an occupied queue and serialises behind it):
 //   main       : witness map, then the sort of the H job (its scalars come out of the witness map)
@@ -58,204 +77,205 @@ int zk_prover_streams(zk_ctx* ctx, size_t k) {
 //                z[1..]), then, as the accumulate kernels complete, each job's reduce phase in job order
 //   accum      : the five accumulate kernels back to back, B-in-G2 first (longest reduce), H last;
 //                the first one is gated on the witness map, which would otherwise be starved 15x beside it
+// The plan: the stream of the z jobs' sort and of each job's accumulate kernel and reduce chain (accumulate order = job order)
+struct StreamPlan { hipStream_t sort_z, accum[5], reduce[5]; };
+enum PlanRow { PLAN_LARGE, PLAN_SMALL, PLAN_GROUPED, PLAN_FRONT };
+StreamPlan stream_plan(zk_ctx* ctx, PlanRow row) {
+    const hipStream_t main = ctx->stream, sort = ctx->aux[0], acc = ctx->acc_stream;      // (the sort stream carries reduce chains as well)
+    switch (row) {
+    case PLAN_LARGE:
+        // B-in-G2's reduce chain (the long one) stays on the sort stream; the four G1 reduces go to the main stream, idle by
+        // then, so that each runs right behind its own accumulate kernel instead of queueing behind the G2 chain (that
+        // queueing left 4 x 0.7 ms of reduces after the last accumulate).
+        // The last two reduce chains alternate between the two streams (the sort stream is idle again once the G2 chain is
+        // through): on one stream the last job's chain queued behind its predecessor's, which was still waiting for slots
+        // beside the last accumulate kernel, and ~0.6 ms of it ran after the GPU had otherwise gone idle.
+        return {sort, {acc, acc, acc, acc, acc}, {sort, main, sort, main, sort}};
+    case PLAN_SMALL:
+        // A job of up to 2^16 terms occupies a tenth of the chip for the length of its longest bucket (~0.3 ms): five of them one
+        // behind the other on the accumulate stream are most of a small proof.  There every job's accumulate kernel goes on the stream
+        // of its own reduce chain instead (G2 alone on the accumulate stream, the G1 jobs alternating between the sort stream and the
+        // context stream): the kernels overlap, the chain follows its kernel without an event.  (Ordering against the next proof's
+        // front does not lean on the accumulate stream: that front waits for every job's reduce_done / accum_done event.)
+        return {sort, {acc, sort, main, sort, main}, {acc, sort, main, sort, main}};
+    case PLAN_GROUPED:
+        // ... and where the four G1 jobs qualify (tables of window multiples with the same bucket count: every key of >= 256 points)
+        // they are ONE accumulate launch and one launch per level of the reduce chain, on the sort stream (round 5: two jobs per stream,
+        // one behind the other, were 2 x (0.26 + 0.2) ms of a 1.2 ms proof at 2^10)
+        return {sort, {acc, sort, sort, sort, sort}, {acc, sort, sort, sort, sort}};
+    default:
+        // The front of the NEXT proof: its z-sort goes on the accumulate stream (in order behind the five accumulate kernels, the
+        // readers of this proof's sort products); a whole chain (a grouped proof's front) on the streams this proof's own chains are
+        // on, so stream order keeps every reader of a scratch buffer in front of its next writer.
+        return {acc, {acc, sort, sort, sort, sort}, {acc, sort, sort, sort, sort}};
+    }
+}
+
+// The stages: each advances at[] and passes over a job that is already there.  First the z jobs: one sort of z[1..], job 0's
+// (first_only: no more than that), which a presort or a front may have enqueued already; the others borrow it.
+int sort_z(zk_ctx* ctx, ZkG16Flight& F, const ZkG16Jobs& T, hipStream_t st, bool first_only = false) {
+    if (F.at[first_only ? 0 : 1] >= Stage::SORTED) return ZK_OK;
+    ZK_TRY(T.sort_z(ctx, F.J, st, ZK_SLOT_G16, 0, F.at[0] >= Stage::SORTED, first_only ? 1 : 4));
+    F.at[0] = Stage::SORTED;
+    if (!first_only) { F.at[1] = F.at[2] = Stage::SORTED; if (T.l_shared) F.at[3] = Stage::SORTED; }
+    return ZK_OK;
+}
+
+// The witness map into F.h (the caller brings h: none) and H's prepare and sort, on the context stream.  The first accumulate
+// kernel is gated on the witness map, which would otherwise be starved beside it (un-gating it: within the noise of consecutive
+// runs, round 3): wm_done, which the accumulate stream waits for.
+// `behind`: F is the front of the proof after `behind`.  Its witness map and H-sort queue behind that proof's H-sort and reduce
+// chains on the context stream; the H-sort rewrites slot 5 and also waits for the last accumulate kernel, the reader of the H
+// job's sort products, and for H's own chain (k_fold reads ctr / heavy there), which may be on the other stream.  The gate is left
+// to the call that takes the front over: it finds at[4] == SORTED.  (prepare only fills the job in on the host: it enqueues nothing.)
+int witness_map_and_h(zk_ctx* ctx, ZkG16Flight& F, const ZkG16Jobs& T, ZkPhaseTimer* tm, const ZkG16Flight* behind) {
+    if (F.at[4] == Stage::NONE) {
+        if (F.h) {
+            if (tm) tm->begin("witness_map");
+            const int rc = T.witness_map(ctx, F.z, F.h);
+            if (tm) tm->end();
+            ZK_TRY(rc);
+        }
+        ZK_TRY(T.prepare(ctx, 4, &F.J[4], ZK_SLOT_G16));
+        ZK_HIP(ctx, hipEventCreateWithFlags(&F.wm_done, hipEventDisableTiming));
+        ZK_HIP(ctx, hipEventRecord(F.wm_done, ctx->stream));
+        if (behind && behind->J[4].accum_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, behind->J[4].accum_done, 0));
+        if (behind && behind->J[4].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, behind->J[4].reduce_done, 0));
+        ZK_TRY(zk_msm_enqueue_sort(ctx, &F.J[4], ctx->stream, nullptr));
+        F.at[4] = Stage::SORTED;
+    }
+    if (!behind) ZK_HIP(ctx, hipStreamWaitEvent(ctx->acc_stream, F.wm_done, 0));
+    return ZK_OK;
+}
+
+// L's sort after the witness map where L does not share the z jobs' (it is not needed before the fourth accumulate kernel)
+int sort_l_late(zk_ctx* ctx, ZkG16Flight& F, hipStream_t st) {
+    if (F.at[3] >= Stage::SORTED) return ZK_OK;
+    if (F.wm_done) ZK_HIP(ctx, hipStreamWaitEvent(st, F.wm_done, 0));
+    ZK_TRY(zk_msm_enqueue_sort(ctx, &F.J[3], st, nullptr));
+    F.at[3] = Stage::SORTED;
+    return ZK_OK;
+}
+
+// The first `njobs` jobs that are at `from` go one stage on -- SORTED: the accumulate kernels, ACCUMULATED: the reduce chains --
+// each on its stream of the plan, the G1 jobs of a group as one launch (one per level of the chain).
+int advance(zk_ctx* ctx, ZkG16Flight& F, const StreamPlan& P, Stage from, int njobs = 5) {
+    const bool acc = from == Stage::SORTED;
+    const hipStream_t* st = acc ? P.accum : P.reduce;
+    for (int k = 0; k < njobs; k++) {
+        if (F.at[k] != from || (F.grouped && k != 0)) continue;
+        ZK_TRY(acc ? zk_msm_enqueue_accum(ctx, &F.J[k], st[k]) : zk_msm_enqueue_reduce(ctx, &F.J[k], st[k]));
+        F.at[k] = Stage(from + 1);
+    }
+    if (F.grouped && F.at[1] == from) {
+        ZK_TRY(acc ? zk_msm_enqueue_accum_group(ctx, F.g1, 4, st[1]) : zk_msm_enqueue_reduce_group(ctx, F.g1, 4, st[1]));
+        F.at[1] = F.at[2] = F.at[3] = F.at[4] = Stage(from + 1);
+    }
+    return ZK_OK;
+}
+int accumulate(zk_ctx* ctx, ZkG16Flight& F, const StreamPlan& P) { return advance(ctx, F, P, Stage::SORTED); }
+int reduce(zk_ctx* ctx, ZkG16Flight& F, const StreamPlan& P, int njobs = 5) { return advance(ctx, F, P, Stage::ACCUMULATED, njobs); }
+
+// finish in completion order: the host-side Horner of an early job overlaps the GPU work of the later ones
+int collect(zk_ctx* ctx, ZkG16Flight& F, zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc) {
+    void* outs[5] = {out_g2, &out_g1[2], &out_g1[3], &out_g1[1], &out_g1[0]};
+    if (F.grouped) {
+        // the four G1 jobs of a group become ready together: their host halves side by side, B in G2's on this thread
+        ZkTask<int> g1fin = zk_async(ctx, [&] { (void)hipSetDevice(ctx->device); return zk_msm_finish_many(ctx, F.g1, outs + 1, 4); });
+        const int rc0 = zk_msm_finish(ctx, &F.J[0], outs[0]), rc1 = g1fin.get();
+        if (rc0 == ZK_OK && rc1 == ZK_OK && after_abc) after_abc();
+        return rc0 != ZK_OK ? rc0 : rc1;
+    }
+    for (int k = 0; k < 5; k++) {
+        ZK_TRY(zk_msm_finish(ctx, &F.J[k], outs[k]));
+        if (k == 2 && after_abc) after_abc();      // A, B1, B2 are in: the caller's host work overlaps the rest
+    }
+    return ZK_OK;
+}
+
+// The caller announced the next assignment (zk_groth16_hint_next_dev): enqueue that proof's front N now, behind the kernels of this
+// proof C.  Its z-sort also waits for the reduce chains, whose fold kernels read the segment tables.  No buffer is doubled: stream
+// order and these events keep every reader in front of the next writer.
+int enqueue_front(zk_ctx* ctx, const ZkG16Flight& C, ZkG16Flight& N, const ZkG16Jobs& T) {
+    const StreamPlan P = stream_plan(ctx, PLAN_FRONT);
+    if (N.z == ctx->next.dev && ctx->next.ready) {      // announced from the host: its upload runs on the copy stream
+        ZK_HIP(ctx, hipStreamWaitEvent(P.sort_z, ctx->next.ready, 0));
+        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next.ready, 0));
+    }
+    // a reduce chain reads its job's segment tables (k_fold: ctr / heavy live in the sort scratch of the job's slot).  The
+    // next proof's z-sort rewrites slot 1, whose products the four z jobs share: it waits for THEIR chains (not for the H
+    // job's, the last one: the z-sort is meant to run under that tail); the next H-sort rewrites slot 5 and waits for the
+    // H job's chain.
+    for (int k = 0; k < 4; k++)
+        if (C.J[k].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(P.sort_z, C.J[k].reduce_done, 0));
+    ZK_TRY(sort_z(ctx, N, T, P.sort_z, true));
+    ZK_TRY(witness_map_and_h(ctx, N, T, nullptr, &C));
+    // A SMALL proof (its four G1 jobs one group): the next proof's whole device chain goes out as well -- accumulate launches and
+    // reduce chains of all five jobs.  The device then runs from one proof's chain into the next while the host
+    // finishes the first (Horner chains, the tail's scalar multiplications, the caller's next call: ~0.2 ms during which the
+    // chip used to wait).  The results land in the other pair of pinned buffers: this proof's are still to be read.
+    if (!C.grouped || !ctx->chain_fronts) return ZK_OK;
+    const uint32_t par = (uint32_t)(ctx->front_parity ^= 1);
+    N.J[0].pin = {ZK_PIN_FRONT, par};
+    N.J[1].pin = {ZK_PIN_FRONT_GROUP, par};                    // (the group's results travel in its first job's buffer)
+    ZK_TRY(sort_z(ctx, N, T, P.sort_z));                       // (l_shared here: the z-sort above serves all four)
+    if (!(N.grouped = zk_msm_group_ok(N.g1, 4))) return ZK_OK; // (not for one key: whether its G1 jobs group is the key's property)
+    ZK_TRY(accumulate(ctx, N, P));
+    return reduce(ctx, N, P);
+}
+
+}  // namespace
+
 int zk_groth16_run_msms(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z, const void* h_in, void* h_scratch,
                         zk_g1_projective out_g1[4], zk_g2_projective* out_g2, const std::function<void()>& after_abc) {
     const auto t_enter = std::chrono::steady_clock::now();
-    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
-    const ZkG16Jobs T(pk, r, z, h_in ? h_in : h_scratch, true, h_in != nullptr);      // (a caller's h is the quotient: over h_query)
-    const size_t D = T.D, nvars = T.j[0].n;
-    const bool l_shared = T.l_shared;
-    ZK_TRY(zk_prover_streams(ctx, 1));
-    hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;      // (the sort stream carries reduce chains as well)
-    struct Events {                               // destroyed on every exit path (the error returns below used to leak them)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } evs;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&evs.e0, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventCreateWithFlags(&evs.e1, hipEventDisableTiming));
-    const hipEvent_t e0 = evs.e0, e1 = evs.e1;
-    ZK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    ZkMsmJob own[5];  // 0: B in G2, 1: A, 2: B in G1, 3: L, 4: H
-    ZkMsmJob* J[5] = {&own[0], &own[1], &own[2], &own[3], &own[4]};
-    // the sort of z[1..] may already be running (zk_groth16_msms_presort_dev, enqueued by the collaborative prover before
-    // its Beaver open): take it over as job 0's
-    ZkPresort* pre = ctx->presort;
-    ctx->presort = nullptr;
-    std::unique_ptr<ZkPresort> pre_owner(pre);
-    // (a begun set can only be taken over whole, by the call that brings h: anything else drains and drops it below -- its jobs
-    // own the scratch slots this call is about to use)
-    const bool presorted = pre && pre->pk == pk && pre->z == z && pre->job.n == nvars && (!pre->begun || (h_in && pre->r == r));
-    const bool fronted = presorted && pre->front && !h_in && pre->r == r && pre->h == h_scratch;
-    if (pre && !presorted) {                       // a front / sort for other inputs: let it drain before its scratch is reused
-        pre_owner.release();
-        ctx->presort = pre;
-        zk_presort_free(ctx);
-        pre = nullptr;
-    }
-    const bool begun = presorted && pre->begun && h_in && pre->r == r;     // the four z jobs are already enqueued to the end
-    const bool chained = fronted && pre->chained;                          // ... all five are (a small proof's front: see below)
-    if (presorted) J[0] = &pre->job;
-    if (fronted) J[4] = &pre->jobh;
-    if (begun || chained) { J[1] = &pre->j1; J[2] = &pre->j2; J[3] = &pre->j3; }
+    // Part of this proof may already be under way (ZkG16Flight): take it over.  A front's witness map wrote h_scratch; a begun set
+    // can only be taken over whole, by the call that brings h; a sort of z[1..] alone serves any call.  Anything else is drained
+    // and dropped: its jobs own the scratch slots this call is about to use.
+    ZkG16Flight* const pend = ctx->flight;
+    const bool mine = pend && pend->pk == pk && pend->z == z && pend->J[0].n == r->ni + r->nw - 1 &&
+                      (pend->h ? !h_in && pend->r == r && pend->h == h_scratch : !pend->beyond_sort_z() || (h_in && pend->r == r));
     // z was produced on the context stream.  (With a front that stream already carries this proof's witness map and H-sort:
     // waiting for it here would hold the sort stream -- and the G2 reduce chain on it -- until the H-sort is through.)
-    if (!fronted) ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0, 0));
-    const bool have_z_jobs = begun || chained;
-    int rc = have_z_jobs ? ZK_OK : T.sort_z(ctx, J, s_sort, ZK_SLOT_G16, 0, presorted);       // the z jobs: one sort of z[1..]
+    ZK_TRY(enter(ctx, pk, r, mine, mine && pend->h ? 0 : 1));
+    const ZkG16Jobs T(pk, r, z, h_in ? h_in : h_scratch, true, h_in != nullptr);      // (a caller's h is the quotient: over h_query)
+    ZkG16Flight own(pk, r, z, nullptr);
+    const std::unique_ptr<ZkG16Flight> taken(mine ? std::exchange(ctx->flight, nullptr) : nullptr);
+    ZkG16Flight& F = mine ? *taken : own;
+    F.h = h_in ? nullptr : h_scratch;
+    const bool small = F.at[1] < Stage::ACCUMULATED && T.D <= ((size_t)1 << 16);      // (a begun set, a chained front: enqueued further already)
+    StreamPlan P = stream_plan(ctx, small ? PLAN_SMALL : PLAN_LARGE);
     ZkPhaseTimer tm(ctx);
-    // the first accumulate kernel is gated on the witness map, which would otherwise be starved beside it (un-gating it: within
-    // the noise of consecutive runs, round 3)
-    if (fronted) {
-        // witness map and H's sort were enqueued with the previous proof (enqueue_front below)
-        ZK_HIP(ctx, hipStreamWaitEvent(s_acc, pre->wm_done, 0));
-    } else {
-        if (rc == ZK_OK && !h_in) {
-            tm.begin("witness_map");
-            rc = T.witness_map(ctx, z, h_scratch);
-            tm.end();
-        }
-        if (rc == ZK_OK) rc = T.prepare(ctx, 4, J[4], ZK_SLOT_G16);
-        if (rc == ZK_OK) {
-            ZK_HIP(ctx, hipEventRecord(e1, ctx->stream));
-            ZK_HIP(ctx, hipStreamWaitEvent(s_acc, e1, 0));
-            rc = zk_msm_enqueue_sort(ctx, J[4], ctx->stream, nullptr);
-        }
+    int rc = sort_z(ctx, F, T, P.sort_z);
+    if (rc == ZK_OK) rc = witness_map_and_h(ctx, F, T, &tm, nullptr);
+    if (rc == ZK_OK) rc = sort_l_late(ctx, F, P.sort_z);
+    if (rc == ZK_OK && small && (F.grouped = zk_msm_group_ok(F.g1, 4))) P = stream_plan(ctx, PLAN_GROUPED);
+    if (rc == ZK_OK) rc = accumulate(ctx, F, P);
+    if (rc == ZK_OK) rc = reduce(ctx, F, P);
+    const void* const zn = std::exchange(ctx->next.z, nullptr);
+    if (rc == ZK_OK && zn && !h_in && T.l_shared) {
+        std::unique_ptr<ZkG16Flight> N(new ZkG16Flight(pk, r, zn, h_scratch));
+        rc = enqueue_front(ctx, F, *N, ZkG16Jobs(pk, r, zn, h_scratch));
+        if (rc == ZK_OK) ctx->flight = N.release();
+        else drain_streams(ctx);                           // part of it is in flight: let it drain before its jobs go
     }
-    // L's sort after the witness map (it is not needed before the fourth accumulate kernel)
-    if (rc == ZK_OK && !l_shared && !have_z_jobs) {
-        ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e1, 0));
-        rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);
-    }
-    // accumulate order = job order (0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H; H's scalars arrive last)
-    // A job of up to 2^16 terms occupies a tenth of the chip for the length of its longest bucket (~0.3 ms): five of them one
-    // behind the other on the accumulate stream are most of a small proof.  There every job's accumulate kernel goes on the stream
-    // of its own reduce chain instead (G2 alone on the accumulate stream, the G1 jobs alternating between the sort stream and the
-    // context stream): the kernels overlap, the chain follows its kernel without an event.  (Ordering against the next proof's
-    // front does not lean on the accumulate stream: that front waits for every job's reduce_done / accum_done event.)
-    const bool small_jobs = !begun && D <= ((size_t)1 << 16);
-    auto job_stream = [&](int k) -> hipStream_t { return k == 0 ? s_acc : ((k & 1) ? s_sort : ctx->stream); };
-    // ... and where the four G1 jobs qualify (tables of window multiples with the same bucket count: every key of >= 256 points)
-    // they are ONE accumulate launch and one launch per level of the reduce chain, on the sort stream (round 5: two jobs per stream,
-    // one behind the other, were 2 x (0.26 + 0.2) ms of a 1.2 ms proof at 2^10)
-    ZkMsmJob* g1jobs[4] = {J[1], J[2], J[3], J[4]};
-    const bool grouped = chained || (small_jobs && rc == ZK_OK && zk_msm_group_ok(g1jobs, 4));
-    for (int k = 0; k < 5 && rc == ZK_OK && !chained; k++) {
-        if (grouped && k != 0) continue;
-        if (!begun || k == 4) rc = zk_msm_enqueue_accum(ctx, J[k], small_jobs ? job_stream(k) : s_acc);
-    }
-    if (grouped && !chained && rc == ZK_OK) rc = zk_msm_enqueue_accum_group(ctx, g1jobs, 4, s_sort);
-    // B-in-G2's reduce chain (the long one) stays on the sort stream; the four G1 reduces go to the main stream, idle by
-    // then, so that each runs right behind its own accumulate kernel instead of queueing behind the G2 chain (that
-    // queueing left 4 x 0.7 ms of reduces after the last accumulate).
-    // The last two reduce chains alternate between the two streams (the sort stream is idle again once the G2 chain is
-    // through): on one stream the last job's chain queued behind its predecessor's, which was still waiting for slots
-    // beside the last accumulate kernel, and ~0.6 ms of it ran after the GPU had otherwise gone idle.
-    for (int k = 0; k < 5 && rc == ZK_OK && !chained; k++) {
-        hipStream_t rs = small_jobs ? job_stream(k) : ((k & 1) == 0 ? s_sort : ctx->stream);
-        if (begun && k == 0) continue;                      // B in G2's chain went out with zk_groth16_msms_begin_dev
-        if (grouped && k != 0) continue;
-        rc = zk_msm_enqueue_reduce(ctx, J[k], rs);
-    }
-    if (grouped && !chained && rc == ZK_OK) rc = zk_msm_enqueue_reduce_group(ctx, g1jobs, 4, s_sort);
-    // The caller announced the next assignment (zk_groth16_hint_next_dev): enqueue that proof's front now, behind this
-    // proof's kernels.  Its z-sort goes on the accumulate stream (in order behind the five accumulate kernels, the readers of
-    // this proof's sort products; it also waits for the reduce chains, whose fold kernels read the segment tables), its
-    // witness map and H-sort on the context stream (behind this proof's H-sort and reduce chains; the H-sort also waits for
-    // the last accumulate kernel, the reader of the H job's sort products).  No buffer is doubled: stream order and these
-    // events keep every reader in front of the next writer.
-    bool front_enqueued = false;
-    if (rc == ZK_OK && ctx->next_z && !h_in && l_shared) {
-        const void* zn = ctx->next_z;
-        ctx->next_z = nullptr;
-        std::unique_ptr<ZkPresort> nf(new ZkPresort());
-        nf->pk = pk; nf->z = zn; nf->r = r; nf->h = h_scratch; nf->front = true;
-        if (zn == ctx->next_z_dev && ctx->next_z_ready) {      // announced from the host: its upload runs on the copy stream
-            ZK_HIP(ctx, hipStreamWaitEvent(s_acc, ctx->next_z_ready, 0));
-            ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next_z_ready, 0));
-        }
-        // a reduce chain reads its job's segment tables (k_fold: ctr / heavy live in the sort scratch of the job's slot).  The
-        // next proof's z-sort rewrites slot 1, whose products the four z jobs share: it waits for THEIR chains (not for the H
-        // job's, the last one: the z-sort is meant to run under that tail); the next H-sort rewrites slot 5 and waits for the
-        // H job's chain below.
-        for (int k = 0; k < 4; k++)
-            if (J[k]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(s_acc, J[k]->reduce_done, 0));
-        const ZkG16Jobs N(pk, r, zn, h_scratch);
-        rc = N.prepare(ctx, 0, &nf->job, ZK_SLOT_G16);
-        if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->job, s_acc, nullptr);
-        if (rc == ZK_OK) rc = N.witness_map(ctx, zn, h_scratch);
-        if (rc == ZK_OK) {
-            ZK_HIP(ctx, hipEventCreateWithFlags(&nf->wm_done, hipEventDisableTiming));
-            ZK_HIP(ctx, hipEventRecord(nf->wm_done, ctx->stream));
-            if (J[4]->accum_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->accum_done, 0));
-            // H's own chain (slot 5: k_fold reads ctr / heavy there) may be on the other stream
-            if (J[4]->reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, J[4]->reduce_done, 0));
-            rc = N.prepare(ctx, 4, &nf->jobh, ZK_SLOT_G16);
-            if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &nf->jobh, ctx->stream, nullptr);
-        }
-        // A SMALL proof (its four G1 jobs one group): the next proof's whole device chain goes out as well -- accumulate launches and
-        // reduce chains of all five jobs, on the streams this proof's own chains are on, so stream order keeps every reader of a
-        // scratch buffer in front of its next writer.  The device then runs from one proof's chain into the next while the host
-        // finishes the first (Horner chains, the tail's scalar multiplications, the caller's next call: ~0.2 ms during which the
-        // chip used to wait).  The results land in the other pair of pinned buffers: this proof's are read below.
-        if (rc == ZK_OK && grouped && ctx->chain_fronts) {
-            const int par = (ctx->front_parity ^= 1);
-            nf->job.pin = {ZK_PIN_FRONT, (uint32_t)par};
-            nf->j1.pin = {ZK_PIN_FRONT_GROUP, (uint32_t)par};                         // (the group's results travel in its first job's buffer)
-            ZkMsmJob* nz[4] = {&nf->job, &nf->j1, &nf->j2, &nf->j3};
-            rc = N.sort_z(ctx, nz, s_acc, ZK_SLOT_G16, 0, true);             // (l_shared here: the z-sort above serves all four)
-            ZkMsmJob* ng[4] = {&nf->j1, &nf->j2, &nf->j3, &nf->jobh};
-            if (rc == ZK_OK && zk_msm_group_ok(ng, 4)) {
-                rc = zk_msm_enqueue_accum(ctx, &nf->job, s_acc);
-                if (rc == ZK_OK) rc = zk_msm_enqueue_accum_group(ctx, ng, 4, s_sort);
-                if (rc == ZK_OK) rc = zk_msm_enqueue_reduce(ctx, &nf->job, s_acc);
-                if (rc == ZK_OK) rc = zk_msm_enqueue_reduce_group(ctx, ng, 4, s_sort);
-                nf->chained = rc == ZK_OK;
-            }
-            if (rc != ZK_OK) {                                       // part of a chain is in flight: let it drain before its jobs go
-                ctx->presort = nf.release();
-                zk_presort_free(ctx);
-            }
-        }
-        if (rc == ZK_OK) { ctx->presort = nf.release(); front_enqueued = true; }
-    }
-    ctx->next_z = nullptr;
     if (ctx->profiling) {                          // host time from the call to the last enqueue (a small proof's device chain starts late by it)
         auto& t = ctx->timers["host.enqueue"];
         t.ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
         t.count += 1;
     }
-    // finish in completion order: the host-side Horner of an early job overlaps the GPU work of the later ones
-    void* outs[5] = {out_g2, &out_g1[2], &out_g1[3], &out_g1[1], &out_g1[0]};
-    if (grouped && rc == ZK_OK) {
-        // the four G1 jobs of a group become ready together: their host halves side by side, B in G2's on this thread
-        void* gouts[4] = {outs[1], outs[2], outs[3], outs[4]};
-        ZkTask<int> g1fin = zk_async(ctx, [&] { (void)hipSetDevice(ctx->device); return zk_msm_finish_many(ctx, g1jobs, gouts, 4); });
-        rc = zk_msm_finish(ctx, J[0], outs[0]);
-        const int rc1 = g1fin.get();
-        if (rc == ZK_OK) rc = rc1;
-        if (rc == ZK_OK && after_abc) after_abc();
-    } else {
-        for (int k = 0; k < 5 && rc == ZK_OK; k++) {
-            rc = zk_msm_finish(ctx, J[k], outs[k]);
-            if (k == 2 && rc == ZK_OK && after_abc) after_abc();   // A, B1, B2 are in: the caller's host work overlaps the rest
-        }
-    }
-    if (!front_enqueued) {                         // (with a front in flight the streams carry the next proof's kernels)
-        (void)hipStreamSynchronize(s_sort);
-        (void)hipStreamSynchronize(s_acc);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
+    if (rc == ZK_OK) rc = collect(ctx, F, out_g1, out_g2, after_abc);
+    if (!ctx->flight) drain_streams(ctx);                  // (with a front in flight the streams carry the next proof's kernels)
     tm.resolve();
     return rc;
 }
-
 
 // The next zk_groth16_prove_dev on this context will be for `z_next_dev` (same key, same constraint system): the proof
 // in between enqueues that proof's front (z-sort, witness map, H-sort) behind its own kernels.  Pass NULL to withdraw.
 extern "C" int zk_groth16_hint_next_dev(zk_ctx* ctx, const void* z_next_dev) {
     ZK_API_BEGIN(ctx)
     if (!ctx) return ZK_ERR_ARG;
-    ctx->next_z = z_next_dev;
+    ctx->next.z = z_next_dev;
     return ZK_OK;
     ZK_API_END
 }
@@ -275,20 +295,10 @@ extern "C" int zk_groth16_chain_fronts(zk_ctx* ctx, int on) {
 extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !pk || !r || !z) return ZK_ERR_ARG;
-    zk_presort_free(ctx);
-    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
-    ZK_TRY(zk_prover_streams(ctx, 1));
-    hipEvent_t e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(e0, ctx->stream));          // z was produced on the context stream
-    ZK_HIP(ctx, hipStreamWaitEvent(ctx->aux[0], e0, 0));
-    (void)hipEventDestroy(e0);
-    std::unique_ptr<ZkPresort> p(new ZkPresort());
-    p->pk = pk;
-    p->z = z;
-    ZK_TRY(ZkG16Jobs(pk, r, z, nullptr, true, true).prepare(ctx, 0, &p->job, ZK_SLOT_G16));
-    ZK_TRY(zk_msm_enqueue_sort(ctx, &p->job, ctx->aux[0], nullptr));
-    ctx->presort = p.release();
+    ZK_TRY(enter(ctx, pk, r, false, 1));
+    std::unique_ptr<ZkG16Flight> F(new ZkG16Flight(pk, r, z, nullptr));
+    ZK_TRY(sort_z(ctx, *F, ZkG16Jobs(pk, r, z, nullptr, true, true), ctx->aux[0], true));
+    ctx->flight = F.release();
     return ZK_OK;
     ZK_API_END
 }
@@ -301,33 +311,19 @@ extern "C" int zk_groth16_msms_presort_dev(zk_ctx* ctx, const zk_pk* pk, const z
 extern "C" int zk_groth16_msms_begin_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* z) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !pk || !r || !z) return ZK_ERR_ARG;
-    zk_presort_free(ctx);
-    ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
-    ZK_TRY(zk_prover_streams(ctx, 1));
-    hipStream_t s_sort = ctx->aux[0], s_acc = ctx->acc_stream;
-    hipEvent_t e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(e0, ctx->stream));          // z was produced on the context stream
-    ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0, 0));
-    ZK_HIP(ctx, hipStreamWaitEvent(s_acc, e0, 0));
-    (void)hipEventDestroy(e0);
-    std::unique_ptr<ZkPresort> p(new ZkPresort());
-    p->pk = pk; p->z = z; p->r = r; p->begun = true;
+    ZK_TRY(enter(ctx, pk, r, false, 2));
+    std::unique_ptr<ZkG16Flight> F(new ZkG16Flight(pk, r, z, nullptr));
     const ZkG16Jobs T(pk, r, z, nullptr, true, true);      // (zk_groth16_msms_dev brings the quotient)
-    ZkMsmJob* J[4] = {&p->job, &p->j1, &p->j2, &p->j3};
-    int rc = T.sort_z(ctx, J, s_sort, ZK_SLOT_G16);
-    if (rc == ZK_OK && !T.l_shared) rc = zk_msm_enqueue_sort(ctx, J[3], s_sort, nullptr);
-    for (int k = 0; k < 4 && rc == ZK_OK; k++) rc = zk_msm_enqueue_accum(ctx, J[k], s_acc);
+    const StreamPlan P = stream_plan(ctx, PLAN_LARGE);
+    int rc = sort_z(ctx, *F, T, P.sort_z);
+    if (rc == ZK_OK) rc = sort_l_late(ctx, *F, P.sort_z);
+    if (rc == ZK_OK) rc = accumulate(ctx, *F, P);          // (jobs 0..3: H is not sorted)
     // only the G2 job's reduce chain here (sort stream); the G1 chains are enqueued by zk_groth16_msms_dev, which spreads them over
     // the context stream (the caller's own kernels are through by then) and the sort stream as the one-call form does
-    if (rc == ZK_OK) rc = zk_msm_enqueue_reduce(ctx, J[0], s_sort);
-    if (rc != ZK_OK) {                                   // whatever was enqueued drains before the jobs (and their events) go
-        (void)hipStreamSynchronize(s_sort);
-        (void)hipStreamSynchronize(s_acc);
-        return rc;
-    }
-    ctx->presort = p.release();
-    return ZK_OK;
+    if (rc == ZK_OK) rc = reduce(ctx, *F, P, 1);
+    if (rc == ZK_OK) ctx->flight = F.release();
+    else drain_streams(ctx);                                     // whatever was enqueued drains before the jobs (and their events) go
+    return rc;
     ZK_API_END
 }
 

@@ -116,47 +116,47 @@ extern "C" int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1
     if (!ctx || !pk || !r || !z_host) return ZK_ERR_ARG;
     const size_t m = r->ni + r->nw;
     void* z;
-    if (ctx->next_z_host == z_host && ctx->next_z_dev && ctx->next_z_pk == pk && ctx->next_z_r == r && ctx->next_z_m == m) {
+    zk_ctx::NextZ& nx = ctx->next;
+    if (nx.matches(z_host, pk, r, m)) {
         // announced by the previous call for this key, this system and this length: already uploaded (the front that reads it
         // waited for the copy)
-        z = ctx->next_z_dev;
-        ctx->z_slot ^= 1;
-        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next_z_ready, 0));
+        z = nx.dev;
+        nx.slot ^= 1;
+        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, nx.ready, 0));
         ZK_TRY(zk_next_z_drop(ctx, false));
     } else {
         // Not the announced assignment (or announced for another key / system / length: the upload may be shorter than m).  A
         // front enqueued for the announced one still reads the other slot, and its z-sort / witness map may run for as long as
         // this proof takes: let it drain before either slot is written (run_msms would only drop it later).
         ZK_TRY(zk_next_z_drop(ctx, true));
-        ZK_TRY(zk_scratch(ctx, ctx->z_slot ? "prove_z1" : "prove_z0", m * 32, &z));
+        ZK_TRY(zk_scratch(ctx, nx.slot ? "prove_z1" : "prove_z0", m * 32, &z));
         // page-locked memory (zk_host_alloc) goes to the DMA engine as it is; anything else through the context's ring, so that
         // the runtime never pins memory the caller is about to free (hostxfer.hip)
         ZK_TRY(zk_xfer_h2d(ctx, z, z_host, m * 32, zk_host_is_pinned(z_host)));
     }
     if (z_next_host) {
         if (!ctx->copy_stream) ZK_HIP(ctx, zk_stream_create(&ctx->copy_stream, false));
-        if (!ctx->next_z_ready) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->next_z_ready, hipEventDisableTiming));
+        if (!nx.ready) ZK_HIP(ctx, hipEventCreateWithFlags(&nx.ready, hipEventDisableTiming));
         void* zn;
         // the other slot: its last reader was the previous proof, which has delivered its bytes
-        ZK_TRY(zk_scratch(ctx, ctx->z_slot ? "prove_z0" : "prove_z1", m * 32, &zn));
+        ZK_TRY(zk_scratch(ctx, nx.slot ? "prove_z0" : "prove_z1", m * 32, &zn));
         if (zk_host_is_pinned(z_next_host)) {
             ZK_HIP(ctx, hipMemcpyAsync(zn, z_next_host, m * 32, hipMemcpyHostToDevice, ctx->copy_stream));
-            ZK_HIP(ctx, hipEventRecord(ctx->next_z_ready, ctx->copy_stream));
+            ZK_HIP(ctx, hipEventRecord(nx.ready, ctx->copy_stream));
         } else {
             // pageable: staged through the ring now (the call returns behind the host copy) on the ring's DMA stream ALONE -- no
             // fence with the context stream in either direction (the slot's last reader has delivered its bytes; the consumer waits
-            // for next_z_ready), so the DMA runs beside this proof's witness map and sorts instead of inside their stream
+            // for `ready`), so the DMA runs beside this proof's witness map and sorts instead of inside their stream
             const char* src = (const char*)z_next_host;
             const ZkXferFill fill = [src](char* dst, size_t off, size_t len) { memcpy(dst, src + off, len); };
             ZK_TRY(zk_xfer_h2d_fn(ctx, zn, m * 32, fill, false, nullptr));
             hipStream_t xs;
             ZK_TRY(zk_xfer_stream(ctx, &xs));
-            ZK_HIP(ctx, hipEventRecord(ctx->next_z_ready, xs));
+            ZK_HIP(ctx, hipEventRecord(nx.ready, xs));
         }
-        ctx->next_z_host = z_next_host;
-        ctx->next_z_dev = zn;
-        ctx->next_z = zn;
-        ctx->next_z_pk = pk; ctx->next_z_r = r; ctx->next_z_m = m;
+        nx.host = z_next_host;
+        nx.z = nx.dev = zn;
+        nx.pk = pk; nx.r = r; nx.m = m;
     }
     return zk_groth16_prove_dev(ctx, pk, r, z, r_, s_, proof);
     ZK_API_END

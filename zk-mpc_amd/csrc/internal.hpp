@@ -11,7 +11,7 @@
 
 // ntt.hip
 void zk_domains_free(zk_ctx* ctx);
-void zk_presort_free(zk_ctx* ctx);   // groth16_pipeline.hip: drop a pending zk_groth16_msms_presort_dev
+void zk_presort_free(zk_ctx* ctx);   // groth16_pipeline.hip: drain and drop the MSM jobs enqueued ahead of a proof (ZkG16Flight)
 extern "C" int zk_comm_destroy(zk_ctx* ctx);
 extern "C" int zk_fr_sum_parties_dev(zk_ctx* ctx, const void* gathered_dev, size_t n_parties, size_t n, void* out_dev);
 int zk_ntt_launch(zk_ctx* ctx, void* buf_dev, uint32_t log_n, int inverse, int coset);
@@ -188,7 +188,7 @@ enum ZkPinKind : uint8_t {
 enum ZkMsmSlot : int {
     ZK_SLOT_RUN = 0,          // (1) zk_msm_run and the host-slice calls' own job: synchronous, one at a time
     // (5) the Groth16 pipeline: the z jobs and H (ZkG16Jobs: slot0 + k).  A presort / begun set / front may be in flight between two calls
-    // (ctx->presort).  zk_msm_batch_dev rotates its jobs over the first four of these and therefore drops a pending presort first.
+    // (ctx->flight).  zk_msm_batch_dev rotates its jobs over the first four of these and therefore drops a pending flight first.
     ZK_SLOT_G16 = 1,
     // (2) MSMs that run beside the caller's own calls: the speculation of the host-slice path (msm.hip) and the started-ahead MSMs of
     // zk_marlin_prove (msm_batch.hip), in flight beside jobs of ZK_SLOT_RUN and of zk_msm_batch_dev.  The two share the slots and
