@@ -210,7 +210,7 @@ int zk_pinned(zk_ctx* ctx, ZkPin key, size_t bytes, void** out, unsigned flags) 
 }
 
 // ONE side stream per context for everything that runs beside the caller's own calls on the trait-shaped path -- the slices of the
-// table cache's builder (bases_cache.hip) and the MSMs started ahead (msm.hip) -- and no accumulate stream with it: with the default
+// table cache's builder (bases_cache.hip) and the MSMs started ahead (msm_host.hip) -- and no accumulate stream with it: with the default
 // four hardware queues every stream beyond {null, context, transfer ring, this one} shares a queue with one of them, and the
 // host-slice transforms and products then run 8 - 30 % longer even while the extra streams sit idle (measured, round 6: seven
 // transforms at 2^20 12.9-13.4 -> 13.8-15.5 ms, the batch product 2.4 -> 3.1-3.3 ms with one to four idle streams more;

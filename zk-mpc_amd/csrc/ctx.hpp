@@ -34,7 +34,7 @@ struct ZkComm;         // comm.hip
 struct ZkXfer;         // hostxfer.hip
 struct ZkXferSmall;    // hostxfer.hip
 struct ZkBasesCache;   // bases_cache.hip
-struct ZkMsmSpec;      // msm.hip
+struct ZkMsmSpec;      // msm_host.hip
 struct ZkG16Flight;    // groth16_int.hpp
 
 // The name of one of a context's pinned host buffers (core.hip: zk_pinned): what it is for (a ZkPinKind of internal.hpp) and which
@@ -155,7 +155,7 @@ struct zk_ctx {
     ZkXfer* xfer = nullptr;                   // hostxfer.hip: the page-locked ring host slices travel through
     ZkXferSmall* xfer_small = nullptr;        // hostxfer.hip: rotating page-locked slots for transfers below 128 KiB
     ZkBasesCache* bases_cache = nullptr;      // bases_cache.hip: resident copies of host base slices seen by zk_msm_g1 / _g2
-    ZkMsmSpec* msm_spec = nullptr;            // msm.hip: MSMs over the tables a caller asks for next with the same scalars, started ahead
+    ZkMsmSpec* msm_spec = nullptr;            // msm_host.hip: MSMs over the tables a caller asks for next with the same scalars, started ahead
     // groth16_pipeline.hip: MSM jobs of a proof enqueued ahead of it (a presort, a begun set, the next proof's front), and how its fronts go out
     ZkG16Flight* flight = nullptr;
     bool chain_fronts = true;                 // zk_groth16_chain_fronts: a small proof's front carries the next proof's whole device chain

@@ -107,21 +107,21 @@ struct ZkBasesLease {               // a table handed out by zk_bases_cache_get 
 int zk_bases_cache_get(zk_ctx* ctx, const ZkHostTable& t, size_t n, ZkBasesLease* out);
 int zk_bases_cache_verify(zk_ctx* ctx, ZkBasesLease* l, const ZkHostTable& t, size_t n, bool* same);
 int zk_bases_cache_replace(zk_ctx* ctx, ZkBasesLease* l);
-// msm.hip: n_lanes MSMs (device scalar vectors of n elements) over ONE host table, through the cache -- verified hit and all
+// msm_host.hip: n_lanes MSMs (device scalar vectors of n elements) over ONE host table, through the cache -- verified hit and all
 // scalars_fp: a fingerprint of the scalar vector taken from the caller's HOST memory (64 sampled elements and the length; 0 = none):
 // what the speculation below recognises a repeated vector by -- a candidate, confirmed word for word on the device before any
 // speculative result is handed out
 int zk_msm_table_run(zk_ctx* ctx, const ZkHostTable& t, size_t n_table, int n_lanes, const void* const* scalars_dev, size_t n, void* const* outs,
                      uint64_t scalars_fp = 0);
-// msm.hip: MSMs started ahead for the tables a caller asks for next with the SAME scalar vector (create_proof: A, then B in G1, then B
+// msm_host.hip: MSMs started ahead for the tables a caller asks for next with the SAME scalar vector (create_proof: A, then B in G1, then B
 // in G2 over one `assignment`: src/groth16.rs:137-160).  drop: abandon what is in flight (waits for its kernels); forget: a table is
 // leaving the cache or changing content; free: with the context.
 void zk_msm_spec_drop(zk_ctx* ctx);
 int zk_side_stream(zk_ctx* ctx, hipStream_t* out);                       // core.hip: the context's one side stream (= aux[0])
 void zk_msm_spec_forget(zk_ctx* ctx, const zk_bases* b);
-void zk_msm_spec_fft_begin(zk_ctx* ctx, const void* dev, size_t N, int kind);            // msm.hip: a host-slice transform's output as the next MSM's scalars
+void zk_msm_spec_fft_begin(zk_ctx* ctx, const void* dev, size_t N, int kind);            // msm_host.hip: a host-slice transform's output as the next MSM's scalars
 void zk_msm_spec_fft_end(zk_ctx* ctx, size_t N, int kind, const std::function<uint64_t(size_t)>& fp_of);
-uint64_t zk_scalars_fingerprint(const void* fr, size_t n);                     // msm.hip: what zk_msm_g1/_g2 recognise a repeated scalar vector by
+uint64_t zk_scalars_fingerprint(const void* fr, size_t n);                     // msm_host.hip: what zk_msm_g1/_g2 recognise a repeated scalar vector by
 void zk_msm_spec_free(zk_ctx* ctx);
 int zk_prover_streams(zk_ctx* ctx, size_t k);      // groth16_pipeline.hip: the context's helper streams
 int zk_bases_cache_poll(zk_ctx* ctx);            // publish finished window multiples, start the next build (cheap: one event query)
@@ -174,7 +174,7 @@ enum ZkPinKind : uint8_t {
     ZK_PIN_MSM_SLOT,          // idx = scratch slot: a job's reduce results
     ZK_PIN_MSM_GROUP,         // idx = scratch slot of the group's first job: a group's results
     ZK_PIN_BATCH_JOB,         // idx = position in a zk_msm_batch_dev call: the host reads them all at the end
-    ZK_PIN_AHEAD,             // idx = k of a speculative (msm.hip) or started-ahead (msm_batch.hip) MSM: see ZK_SLOT_AHEAD
+    ZK_PIN_AHEAD,             // idx = k of a speculative (msm_host.hip) or started-ahead (msm_batch.hip) MSM: see ZK_SLOT_AHEAD
     ZK_PIN_FRONT,             // idx = parity: B in G2 of a chained front (groth16_pipeline.hip)
     ZK_PIN_FRONT_GROUP,       // idx = parity: the G1 group of a chained front
     ZK_PIN_MULTI_Z,           // groth16_multi.hip: the assignment staged for the other devices
@@ -190,7 +190,7 @@ enum ZkMsmSlot : int {
     // (5) the Groth16 pipeline: the z jobs and H (ZkG16Jobs: slot0 + k).  A presort / begun set / front may be in flight between two calls
     // (ctx->flight).  zk_msm_batch_dev rotates its jobs over the first four of these and therefore drops a pending flight first.
     ZK_SLOT_G16 = 1,
-    // (2) MSMs that run beside the caller's own calls: the speculation of the host-slice path (msm.hip) and the started-ahead MSMs of
+    // (2) MSMs that run beside the caller's own calls: the speculation of the host-slice path (msm_host.hip) and the started-ahead MSMs of
     // zk_marlin_prove (msm_batch.hip), in flight beside jobs of ZK_SLOT_RUN and of zk_msm_batch_dev.  The two share the slots and
     // ZK_PIN_AHEAD because they never coexist: zk_msm_early_begin drops the speculation, nothing starts one until the prover has
     // collected or abandoned its early jobs (only the host-slice entry points speculate; the prover calls none), and the

@@ -132,7 +132,7 @@ int gather_linear(zk_ctx* ctx, const FieldView& v, size_t n, void* const lane_de
     return ZK_OK;
 }
 
-// a fingerprint of a scalar vector from host memory (64 sampled elements: discriminant and first lane): what msm.hip's speculation
+// a fingerprint of a scalar vector from host memory (64 sampled elements: discriminant and first lane): what msm_host.hip's speculation
 // recognises the `assignment` of calculate_coeff's three calls -- and the `h` a transform has just written -- by (confirmed on the
 // device before anything is used)
 uint64_t mpc_scalars_fingerprint(const FieldView& v, size_t n) {
@@ -219,7 +219,7 @@ extern "C" int zk_mpc_fft_in_place(zk_ctx* ctx, void* vec, size_t n, const zk_mp
         if (N > n) ZK_HIP(ctx, hipMemsetAsync((char*)lane[l] + n * 32, 0, (N - n) * 32, ctx->stream));   // Vec::resize(size, zero): Public(0)
     if (run == 1) ZK_TRY(zk_ntt_launch(ctx, lane[0], log_n, inverse, coset));
     else ZK_TRY(zk_ntt_launch_batch(ctx, lane, 2, log_n, inverse, coset));
-    if (run == 1) zk_msm_spec_fft_begin(ctx, lane[0], N, (inverse ? 2 : 0) + (coset ? 1 : 0));    // (msm.hip: `h = witness_map(..)` is the H query's scalar vector next)
+    if (run == 1) zk_msm_spec_fft_begin(ctx, lane[0], N, (inverse ? 2 : 0) + (coset ? 1 : 0));    // (msm_host.hip: `h = witness_map(..)` is the H query's scalar vector next)
     for (int l = 0; l < run; l++) ZK_TRY(zk_xfer_d2h_fn(ctx, lane[l], N * 32, scatterer(v, l, pub ? Out::Public : Out::Shared)));
     if (run == 1) zk_msm_spec_fft_end(ctx, N, (inverse ? 2 : 0) + (coset ? 1 : 0), [&v](size_t m) { return mpc_scalars_fingerprint(v, m); });
     if (pub && N > n)                                       // the elements the caller appended are Public(0) already; say so for a caller that did not initialise them

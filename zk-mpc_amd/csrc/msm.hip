@@ -24,6 +24,8 @@
 //   6. host       : Horner over the <= 64 window sums, one inversion, output as Jacobian Z=1.
 // Arithmetic is exact, so zero scalars, repeated bases, P + P, P - P and infinity need no special
 // treatment beyond the complete formulas in ec.cuh.
+// The entry points on HOST slices (zk_msm_g1 / _g2 / _strided, the table run of the MPC entry points) and the MSMs they start
+// ahead are msm_host.hip, which drives the job stages below through internal.hpp.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "hostgroup.hpp"
@@ -34,7 +36,6 @@
 #include "ec_dual.cuh"
 #include <algorithm>
 #include <future>
-#include <map>
 #include <memory>
 #include <string.h>
 #include <vector>
@@ -1471,267 +1472,6 @@ int bases_download_t(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n, vo
     return ZK_OK;
 }
 
-// ---- MSMs started AHEAD for the tables a caller asks for next with the same scalars -----------------------------------------------
-// The unchanged create_proof runs its MSMs one call behind the other, and three of them over ONE scalar vector: calculate_coeff with
-// &pk.a_query, then &pk.b_g1_query, then &pk.b_g2_query over `assignment` (src/groth16.rs:137-160).  Every call is synchronous -- the
-// trait returns the point -- so the upload, the sort, the reduce chain and the host's Horner half of one call never overlap the next
-// call's kernels, as they do in the resident prover.  What CAN be known: which table followed which with the same scalars last time.
-// So a context learns "after table T (scalars S) came table T' with the same S" (candidates by a fingerprint of 64 sampled scalars
-// taken from host memory), and when T is asked for again it also starts the MSMs over T' and T'' -- on a private copy of the scalars,
-// on the context's side stream, own scratch slots (ZK_SLOT_AHEAD) -- before it collects T's result.  The next call, if it names T' and
-// its scalars are WORD FOR WORD the ones the speculative job ran on (compared on the device), takes that result; anything else
-// drops the speculation (and after two wrong guesses for a table the pattern is forgotten).  Table hits are verified as always.
-// Nothing speculative is ever returned unverified; ZK_MSM_SPEC=0 switches the whole thing off (A/B).
-struct SpecJob { const zk_bases* table; ZkMsmJob job; };
-}  // namespace
-struct ZkMsmSpec {
-    const zk_bases* last_table = nullptr;
-    uint64_t last_fp = 0;
-    size_t last_n = 0;
-    std::map<const zk_bases*, const zk_bases*> succ;
-    std::map<const zk_bases*, int> bad;
-    std::vector<std::unique_ptr<SpecJob>> jobs;          // in the order they will be asked for
-    size_t n = 0;
-    uint64_t fp = 0;
-    uint32_t* flag_dev = nullptr;
-    uint32_t* flag_host = nullptr;
-    uint64_t started = 0, taken = 0, dropped = 0;
-    bool off = false;                                     // zk_msm_speculate(ctx, 0)
-    // the transform a caller ran last on a host vector (zk_msm_spec_fft_begin / _end): its size, the fingerprints its output has as
-    // a scalar vector of N and of N - 1 elements (the min(len) rule against a query of D - 1 points), and -- learned -- which
-    // table was asked for with exactly that output as scalars: `h = witness_map(..)` and then multi_scalar_mul(&pk.h_query, &h)
-    // (src/groth16.rs:100-106)
-    size_t fft_N = 0;
-    int fft_kind = 0;                                     // inverse * 2 + coset
-    uint64_t fft_fp[2] = {0, 0};
-    struct AfterFft { const zk_bases* table; size_t n; };
-    std::map<size_t, AfterFft> fft_succ;
-    bool fp_pending = false;                              // a job started by fft_begin whose fingerprint fft_end still owes
-    const void* late_dev = nullptr;                       // a LARGE job fft_begin left to fft_end
-    const zk_bases* late_table = nullptr;
-    size_t late_n = 0;
-};
-namespace {
-static bool spec_enabled() {
-    static const bool on = !(getenv("ZK_MSM_SPEC") && atoi(getenv("ZK_MSM_SPEC")) == 0);
-    return on;
-}
-static ZkMsmSpec* spec_of(zk_ctx* ctx) {
-    if (!ctx->msm_spec) ctx->msm_spec = new ZkMsmSpec();
-    return ctx->msm_spec;
-}
-__global__ void __launch_bounds__(256) k_scalars_differ(const uint4* a, const uint4* b, size_t n16, uint32_t* flag) {
-    bool diff = false;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) {
-        const uint4 x = a[i], y = b[i];
-        diff = diff || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
-    }
-    if (diff) *flag = 1;
-}
-// what is in flight is abandoned: its kernels read the scratch slots and the scalar copy, so they are waited for
-static void spec_drop(zk_ctx* ctx, ZkMsmSpec* sp) {
-    if (sp->jobs.empty()) return;
-    if (!ctx->aux.empty()) (void)hipStreamSynchronize(ctx->aux[0]);
-    if (ctx->acc_stream) (void)hipStreamSynchronize(ctx->acc_stream);
-    sp->dropped += sp->jobs.size();
-    sp->jobs.clear();
-    sp->fp_pending = false;
-}
-// scalars (n elements on the device, final on the context stream) == the copy the speculative jobs run on?
-static int spec_same_scalars(zk_ctx* ctx, ZkMsmSpec* sp, const void* scalars, size_t n, bool* same) {
-    void* copy;
-    ZK_TRY(zk_scratch(ctx, "spec_scalars", n * 32, &copy));
-    if (!sp->flag_dev) {
-        ZK_HIP(ctx, hipMalloc((void**)&sp->flag_dev, 16));
-        ZK_HIP(ctx, hipHostMalloc((void**)&sp->flag_host, 16, hipHostMallocDefault));
-    }
-    ZK_HIP(ctx, hipMemsetAsync(sp->flag_dev, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(k_scalars_differ, zk_grid(n * 2, 256), 256, 0, ctx->stream, (const uint4*)scalars, (const uint4*)copy, n * 2, sp->flag_dev);
-    ZK_HIP(ctx, hipGetLastError());
-    ZK_HIP(ctx, hipMemcpyAsync(sp->flag_host, sp->flag_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *same = *sp->flag_host == 0;
-    return ZK_OK;
-}
-// the tables that followed `b` last time, over a private copy of the scalars: every phase of every job on the context's ONE side
-// stream, one job behind the other (core.hip::zk_side_stream says why there is only one)
-static int spec_start_tables(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* const* next, int cnt, const void* scalars, size_t n, uint64_t fp);
-static int spec_start(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* b, const void* scalars, size_t n, uint64_t fp) {
-    const zk_bases* next[2] = {nullptr, nullptr};
-    int cnt = 0;
-    auto it = sp->succ.find(b);
-    if (it != sp->succ.end() && it->second != b && sp->bad[it->second] < 2 && n <= it->second->n) {
-        next[cnt++] = it->second;
-        auto it2 = sp->succ.find(it->second);
-        if (it2 != sp->succ.end() && it2->second != b && it2->second != it->second && sp->bad[it2->second] < 2 && n <= it2->second->n) next[cnt++] = it2->second;
-    }
-    if (!cnt) return ZK_OK;
-    return spec_start_tables(ctx, sp, next, cnt, scalars, n, fp);
-}
-static int spec_start_tables(zk_ctx* ctx, ZkMsmSpec* sp, const zk_bases* const* next, int cnt, const void* scalars, size_t n, uint64_t fp) {
-    void* copy;
-    ZK_TRY(zk_scratch(ctx, "spec_scalars", n * 32, &copy));
-    hipStream_t s_sort;                                      // every phase of every job on the context's ONE side stream (zk_side_stream)
-    ZK_TRY(zk_side_stream(ctx, &s_sort));
-    ZK_HIP(ctx, hipMemcpyAsync(copy, scalars, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-    hipEvent_t e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s_sort, e0, 0);
-    (void)hipEventDestroy(e0);
-    ZK_HIP(ctx, e);
-    int rc = ZK_OK;
-    for (int k = 0; k < cnt && rc == ZK_OK; k++) {
-        std::unique_ptr<SpecJob> j(new SpecJob());
-        j->table = next[k];
-        j->job.pin = {ZK_PIN_AHEAD, (uint32_t)k};
-        rc = zk_msm_prepare(ctx, &j->job, next[k], 0, copy, n, ZK_SLOT_AHEAD + k);
-        if (rc == ZK_OK) rc = zk_msm_enqueue_sort(ctx, &j->job, s_sort, nullptr);
-        if (rc == ZK_OK) rc = zk_msm_enqueue_accum(ctx, &j->job, s_sort);
-        if (rc == ZK_OK) rc = zk_msm_enqueue_reduce(ctx, &j->job, s_sort);
-        sp->jobs.push_back(std::move(j));                    // (even a half-enqueued one: spec_drop waits for whatever it launched)
-        if (rc == ZK_OK) sp->started++;
-    }
-    sp->n = n;
-    sp->fp = fp;
-    if (rc != ZK_OK) spec_drop(ctx, sp);
-    return rc;
-}
-
-// AffineCurve::multi_scalar_mul on host slices.  The bases come through the context's table cache (bases_cache.hip): a table the
-// context has seen before -- the queries of a proving key, the powers of an SRS -- is resident already (window multiples are built
-// beside later calls), and only the scalars cross PCIe for the arithmetic; the caller's slice crosses once more, UNDER the MSM, to
-// be compared in full with what the cached table was made from (a hit is a candidate until that comparison is through).
-// n_lanes MSMs over the same table (the two lanes of a SPDZ multi_scale_pub_group: share/spdz.rs:482-488): scalars_dev[l] -> outs[l].
-template <class F>
-int msm_table_run_t(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, const void* const* scalars_dev, size_t n, void* const* outs, uint64_t sfp) {
-    ZkBasesLease lease(ctx);
-    ZK_TRY(zk_bases_cache_get(ctx, t, nu, &lease));
-    const bool spec_ok = spec_enabled() && n_lanes == 1 && !lease.temporary && sfp != 0 && !ctx->profiling &&
-                         !(ctx->msm_spec && ctx->msm_spec->off);
-    ZkMsmSpec* sp = spec_ok || ctx->msm_spec ? spec_of(ctx) : nullptr;
-    int rc = ZK_OK;
-    SpecJob* take = nullptr;
-    if (sp && !sp->jobs.empty()) {                           // is this the call the speculation was made for?
-        SpecJob* j = sp->jobs.front().get();
-        bool same = false;
-        if (spec_ok && j->table == lease.b && sp->n == n && sp->fp == sfp) rc = spec_same_scalars(ctx, sp, scalars_dev[0], n, &same);
-        if (rc == ZK_OK && same) take = j;
-        else {
-            if ((spec_ok || j->table != lease.b) && sp->bad[j->table] < 3) sp->bad[j->table]++;
-            spec_drop(ctx, sp);
-        }
-    }
-    if (sp && sp->fft_N) {                                   // the transform before this call: were its outputs this call's scalars?
-        const size_t N = sp->fft_N;
-        if (spec_ok && rc == ZK_OK && (n == N || n + 1 == N) && sfp == sp->fft_fp[n == N ? 0 : 1]) {
-            const size_t key = N * 4 + (size_t)sp->fft_kind;
-            auto it = sp->fft_succ.find(key);
-            if (it != sp->fft_succ.end() && it->second.table == lease.b && it->second.n == n) {
-                auto bd = sp->bad.find(lease.b);
-                if (bd != sp->bad.end() && bd->second > 0 && --bd->second == 0) sp->bad.erase(bd);
-            }
-            sp->fft_succ[key] = ZkMsmSpec::AfterFft{lease.b, n};
-        }
-        sp->fft_N = 0;
-    }
-    if (sp && spec_ok && rc == ZK_OK) {                      // learn: the same scalars as the call before, another table
-        if (sp->last_table && sp->last_table != lease.b && sp->last_n == n && sp->last_fp == sfp) {
-            auto it = sp->succ.find(sp->last_table);
-            if (it != sp->succ.end() && it->second == lease.b) {     // the succession held again: a table given up after two wrong
-                auto bd = sp->bad.find(lease.b);                     // guesses in a row earns its way back, one confirmation at a time
-                if (bd != sp->bad.end() && bd->second > 0 && --bd->second == 0) sp->bad.erase(bd);
-            }
-            sp->succ[sp->last_table] = lease.b;
-        }
-        sp->last_table = lease.b; sp->last_n = n; sp->last_fp = sfp;
-    } else if (sp) {
-        sp->last_table = nullptr;
-    }
-    for (int attempt = 0; attempt < 2 && rc == ZK_OK; attempt++) {
-        bool same = true;
-        int vrc = ZK_OK;
-        {
-            ZkTask<void> verifier;                           // (joins when this block is left, whatever the MSM did)
-            if (lease.verify)
-                verifier = zk_async(ctx, [&] { (void)hipSetDevice(ctx->device); vrc = zk_bases_cache_verify(ctx, &lease, t, nu, &same); });
-            if (take) {                                      // the result that was started during the previous call
-                rc = zk_msm_finish(ctx, &take->job, outs[0]);
-                sp->bad.erase(sp->jobs.front()->table);     // (two wrong guesses IN A ROW give a table up: spec_start)
-                sp->jobs.erase(sp->jobs.begin());
-                sp->taken++;
-                take = nullptr;
-            } else if (n_lanes == 1) {
-                // The MSMs this caller asked for next the last time it came with this table, on the side stream.  A SMALL call is a chain
-                // of latencies on a mostly idle chip: they start at once, behind nothing but the copy of the scalars, and run beside this
-                // call's own kernels (2^10 .. 2^16: -12 .. -20 % per proof).  A LARGE call fills the chip: started at once they only delay
-                // this call's result (2^20: the A call 4 -> 13.5 ms, the three calls 16.6 -> 21.6), so they queue behind this call's
-                // whole device chain (a reduce chain beside a running accumulate kernel is starved) and run under this call's host
-                // half and the caller's way back into the library.
-                const bool want_spec = spec_ok && attempt == 0 && sp->jobs.empty();
-                const bool small_call = lease.b->pre ? n * ((255 + lease.b->c_pre - 1) / lease.b->c_pre) <= ((size_t)1 << 22) : n <= ((size_t)1 << 17);
-                if (want_spec && small_call) (void)spec_start(ctx, sp, lease.b, scalars_dev[0], n, sfp);
-                ZkMsmJob job;
-                rc = msm_prepare_t<F>(ctx, &job, lease.b, 0, scalars_dev[0], n, ZK_SLOT_RUN);
-                if (rc == ZK_OK) rc = msm_enqueue_sort_t<F>(ctx, &job, ctx->stream, nullptr);
-                if (rc == ZK_OK) rc = msm_enqueue_accum_t<F>(ctx, &job, ctx->stream);
-                if (rc == ZK_OK) rc = msm_enqueue_reduce_t<F>(ctx, &job, ctx->stream);
-                if (rc == ZK_OK && want_spec && !small_call) (void)spec_start(ctx, sp, lease.b, scalars_dev[0], n, sfp);
-                if (rc == ZK_OK) rc = msm_finish_t<F>(ctx, &job, outs[0]);
-                else (void)hipStreamSynchronize(ctx->stream);
-            } else {
-                const zk_bases* bs[2] = {lease.b, lease.b};
-                const size_t lens[2] = {n, n};
-                rc = zk_msm_batch_dev(ctx, (size_t)n_lanes, bs, nullptr, scalars_dev, lens, outs);
-            }
-        }
-        if (rc == ZK_OK) rc = vrc;
-        if (rc != ZK_OK || same) break;
-        rc = zk_bases_cache_replace(ctx, &lease);            // the table at the caller's address is not the cached one any more: again, on the right one
-    }
-    if (rc != ZK_OK && sp) spec_drop(ctx, sp);
-    return rc;
-}
-
-// 64 sampled elements and the length: how a repeated scalar vector is recognised (a candidate: see spec_same_scalars)
-uint64_t scalars_fingerprint(const zk_fr* s, size_t n) {
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)n;
-    const size_t S = n < 64 ? n : 64;
-    for (size_t k = 0; k < S; k++) {
-        const size_t i = S > 1 ? k * (n - 1) / (S - 1) : 0;
-        for (int w = 0; w < 4; w++) { h ^= s[i].l[w]; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 32; }
-    }
-    return h ? h : 1;
-}
-
-ZkHostTable host_table(int group, const void* host, const ZkAffineLayout* layout) {
-    ZkHostTable t;
-    t.group = group;
-    t.host = host;
-    const size_t FE = group == 1 ? 48 : 96;
-    if (layout) { t.stride = layout->stride; t.off_x = layout->off_x; t.off_y = layout->off_y; t.off_inf = layout->off_inf; }
-    else { t.stride = 2 * FE; t.off_x = 0; t.off_y = FE; t.off_inf = SIZE_MAX; }
-    return t;
-}
-
-template <class F>
-int msm_host_t(zk_ctx* ctx, const void* bases_host, size_t nb, const ZkAffineLayout* layout, const zk_fr* scalars, size_t ns, int group, void* out) {
-    if (!ctx || !out) return ZK_ERR_ARG;
-    const size_t n = std::min(nb, ns);  // variable_base.rs:15-17
-    if (n && (!bases_host || !scalars)) return ZK_ERR_ARG;
-    if (n == 0) {
-        host_write_projective<F>(aff_inf<F>(), (uint64_t*)out);
-        return ZK_OK;
-    }
-    const size_t nu = nb <= 2 * n ? nb : n;                  // the whole slice (it is the cache's key) unless most of it is unused
-    void* sdev = nullptr;
-    ZK_TRY(zk_scratch(ctx, "msm_scalars_host", n * 32, &sdev));
-    ZK_TRY(zk_xfer_h2d(ctx, sdev, scalars, n * 32));
-    const void* sc[1] = {sdev};
-    void* outs[1] = {out};
-    return msm_table_run_t<F>(ctx, host_table(group, bases_host, layout), nu, 1, sc, n, outs, scalars_fingerprint(scalars, n));
-}
-
 
 // ---- test hook (diag.hip: zk_diag_fq2_pair_dev ops 7, 8): the G1 pair form of ec_dual.cuh on a case array, one case per lane pair,
 // both lanes reading the whole case.  Element k at words [13 k, +13), raw 29-bit limbs.  The host pads the array to whole waves with
@@ -1883,88 +1623,6 @@ int zk_bases_import_launch(zk_ctx* ctx, zk_bases* b, const void* raw, hipStream_
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
-// the MSM of the MPC entry points (mpc_host.hip): n_lanes scalar vectors on the device against one host table
-int zk_msm_table_run(zk_ctx* ctx, const ZkHostTable& t, size_t nu, int n_lanes, const void* const* scalars_dev, size_t n, void* const* outs, uint64_t sfp) {
-    if (t.group == 1) return msm_table_run_t<G1Field>(ctx, t, nu, n_lanes, scalars_dev, n, outs, sfp);
-    return msm_table_run_t<G2Field>(ctx, t, nu, n_lanes, scalars_dev, n, outs, sfp);
-}
-uint64_t zk_scalars_fingerprint(const void* fr, size_t n) { return scalars_fingerprint((const zk_fr*)fr, n); }
-void zk_msm_spec_drop(zk_ctx* ctx) {
-    if (ctx->msm_spec) spec_drop(ctx, ctx->msm_spec);
-}
-// A transform of 2^log_n elements on a caller's host vector has been enqueued (its result is in `dev`, final on the context stream,
-// not yet on its way back): if the MSM that followed such a transform last time took the output as its scalars, that MSM starts
-// now -- under the download of the result and the upload of the scalars the call will bring (which are compared with `dev`'s copy
-// before the result is released, like every job started ahead).
-void zk_msm_spec_fft_begin(zk_ctx* ctx, const void* dev, size_t N, int kind) {
-    ZkMsmSpec* sp = ctx->msm_spec;
-    if (sp) sp->late_dev = nullptr;                          // (a transform that failed between begin and end leaves nothing behind)
-    if (!sp || sp->off || !spec_enabled() || ctx->profiling || !sp->jobs.empty()) return;
-    auto it = sp->fft_succ.find(N * 4 + (size_t)kind);        // (of the seven transforms of a witness map only the last -- the one coset
-    if (it == sp->fft_succ.end()) return;                     // inverse -- writes the H query's scalars: the kind is part of what is learned)
-    const zk_bases* t = it->second.table;
-    const size_t n = it->second.n;
-    if (sp->bad[t] >= 2 || n > t->n || n > N) return;
-    const bool small_call = t->pre ? n * ((255 + t->c_pre - 1) / t->c_pre) <= ((size_t)1 << 22) : n <= ((size_t)1 << 17);
-    // A small job starts now, under the download of the transform's result.  A large one would share a hardware queue with that
-    // download (2^20: the last transform 1.7 -> 3.2 ms, measured): it starts when the result is through (zk_msm_spec_fft_end) and
-    // runs under the caller's way back into the library and the upload of the scalars.
-    if (!small_call) { sp->late_dev = dev; sp->late_table = t; sp->late_n = n; return; }
-    if (spec_start_tables(ctx, sp, &t, 1, dev, n, 0) == ZK_OK && !sp->jobs.empty()) sp->fp_pending = true;
-}
-// ... and the result has arrived in the caller's vector: fp_of(n) = the fingerprint an MSM entry point would compute over its first n
-// elements (plain: scalars_fingerprint; MpcField: mpc_host.hip's)
-void zk_msm_spec_fft_end(zk_ctx* ctx, size_t N, int kind, const std::function<uint64_t(size_t)>& fp_of) {
-    if (!spec_enabled() || ctx->profiling || N < 2) return;
-    ZkMsmSpec* sp = spec_of(ctx);
-    if (sp->off) return;
-    sp->fft_N = N;
-    sp->fft_kind = kind;
-    sp->fft_fp[0] = fp_of(N);
-    sp->fft_fp[1] = fp_of(N - 1);
-    if (sp->fp_pending && !sp->jobs.empty()) sp->fp = sp->n == N ? sp->fft_fp[0] : sp->fft_fp[1];
-    sp->fp_pending = false;
-    if (sp->late_dev && sp->jobs.empty() && (sp->late_n == N || sp->late_n + 1 == N))
-        (void)spec_start_tables(ctx, sp, &sp->late_table, 1, sp->late_dev, sp->late_n, sp->fft_fp[sp->late_n == N ? 0 : 1]);
-    sp->late_dev = nullptr;
-}
-extern "C" int zk_msm_speculate(zk_ctx* ctx, int on) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx) return ZK_ERR_ARG;
-    ZkMsmSpec* sp = spec_of(ctx);
-    sp->off = on == 0;
-    if (sp->off) { spec_drop(ctx, sp); sp->succ.clear(); sp->bad.clear(); sp->fft_succ.clear(); sp->fft_N = 0; sp->last_table = nullptr; }
-    return ZK_OK;
-    ZK_API_END
-}
-extern "C" int zk_msm_speculate_stats(zk_ctx* ctx, uint64_t out[3]) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !out) return ZK_ERR_ARG;
-    ZkMsmSpec* sp = ctx->msm_spec;
-    out[0] = sp ? sp->started : 0; out[1] = sp ? sp->taken : 0; out[2] = sp ? sp->dropped : 0;
-    return ZK_OK;
-    ZK_API_END
-}
-void zk_msm_spec_forget(zk_ctx* ctx, const zk_bases* b) {
-    ZkMsmSpec* sp = ctx->msm_spec;
-    if (!sp) return;
-    for (auto& j : sp->jobs) if (j->table == b) { spec_drop(ctx, sp); break; }
-    if (sp->last_table == b) sp->last_table = nullptr;
-    sp->succ.erase(b);
-    sp->bad.erase(b);
-    for (auto it = sp->fft_succ.begin(); it != sp->fft_succ.end();) it = it->second.table == b ? sp->fft_succ.erase(it) : std::next(it);
-    if (sp->late_table == b) sp->late_dev = nullptr;
-    for (auto it = sp->succ.begin(); it != sp->succ.end();) it = it->second == b ? sp->succ.erase(it) : std::next(it);
-}
-void zk_msm_spec_free(zk_ctx* ctx) {
-    ZkMsmSpec* sp = ctx->msm_spec;
-    if (!sp) return;
-    spec_drop(ctx, sp);
-    if (sp->flag_dev) (void)hipFree(sp->flag_dev);
-    if (sp->flag_host) (void)hipHostFree(sp->flag_host);
-    delete sp;
-    ctx->msm_spec = nullptr;
-}
 extern "C" int zk_bases_upload_g1(zk_ctx* ctx, const zk_g1_affine* h, size_t n, zk_bases** out) { ZK_API_BEGIN(ctx) return bases_upload_t<G1Field>(ctx, h, n, 1, nullptr, out); ZK_API_END }
 extern "C" int zk_bases_upload_g2(zk_ctx* ctx, const zk_g2_affine* h, size_t n, zk_bases** out) { ZK_API_BEGIN(ctx) return bases_upload_t<G2Field>(ctx, h, n, 2, nullptr, out); ZK_API_END }
 extern "C" int zk_bases_free(zk_ctx* ctx, zk_bases* b) {
@@ -1992,37 +1650,6 @@ extern "C" int zk_bases_download_g2(zk_ctx* ctx, const zk_bases* b, size_t off, 
     ZK_API_END
 }
 
-extern "C" int zk_msm_g1(zk_ctx* ctx, const zk_g1_affine* bases, size_t nb, const zk_fr* scalars, size_t ns, zk_g1_projective* out) {
-    ZK_API_BEGIN(ctx)
-    return msm_host_t<G1Field>(ctx, bases, nb, nullptr, scalars, ns, 1, out);
-    ZK_API_END
-}
-extern "C" int zk_msm_g2(zk_ctx* ctx, const zk_g2_affine* bases, size_t nb, const zk_fr* scalars, size_t ns, zk_g2_projective* out) {
-    ZK_API_BEGIN(ctx)
-    return msm_host_t<G2Field>(ctx, bases, nb, nullptr, scalars, ns, 2, out);
-    ZK_API_END
-}
-static bool layout_from_abi(const zk_affine_layout* l, ZkAffineLayout* o) {
-    if (!l) return false;
-    o->stride = l->stride; o->off_x = l->off_x; o->off_y = l->off_y; o->off_inf = l->off_infinity;
-    return true;
-}
-extern "C" int zk_msm_g1_strided(zk_ctx* ctx, const void* bases, size_t nb, const zk_affine_layout* layout, const zk_fr* scalars, size_t ns,
-                                 zk_g1_projective* out) {
-    ZK_API_BEGIN(ctx)
-    ZkAffineLayout lay;
-    if (!layout_from_abi(layout, &lay)) return ZK_ERR_ARG;
-    return msm_host_t<G1Field>(ctx, bases, nb, &lay, scalars, ns, 1, out);
-    ZK_API_END
-}
-extern "C" int zk_msm_g2_strided(zk_ctx* ctx, const void* bases, size_t nb, const zk_affine_layout* layout, const zk_fr* scalars, size_t ns,
-                                 zk_g2_projective* out) {
-    ZK_API_BEGIN(ctx)
-    ZkAffineLayout lay;
-    if (!layout_from_abi(layout, &lay)) return ZK_ERR_ARG;
-    return msm_host_t<G2Field>(ctx, bases, nb, &lay, scalars, ns, 2, out);
-    ZK_API_END
-}
 extern "C" int zk_msm_g1_dev(zk_ctx* ctx, const zk_bases* bases, size_t off, const void* scalars, size_t n, zk_g1_projective* out) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !bases || !out || bases->group != 1 || (n && !scalars)) return ZK_ERR_ARG;
