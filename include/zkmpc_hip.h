@@ -320,10 +320,26 @@ uint32_t zk_pk_mul_levels(const zk_pk* pk);
  * and of the division by Z(g)) and l_eval_pad (l_query minus h_query through the transposes of ifft and of C, one point per
  * variable).  Its local proofs (prove_dev / prove_queued / prove_batch) then stop the witness map at a o b on the coset: four
  * transforms instead of six, no C mat-vec.  Same group elements, same proof bytes.  ZK_G16_EVAL_H=0 in the environment turns it
- * off (no tables, the old witness map); an uploaded or deserialised key has no such tables, nor one set up where the key with them
- * would take more than half of the free device memory (two more G1 tables with their window multiples: 28 GB at 2^20 points).
+ * off (no tables, the old witness map); an uploaded or deserialised key has no such tables until zk_pk_derive_eval_h has made them,
+ * nor has one set up where the key with them would take more than half of the free device memory (two more G1 tables with their
+ * window multiples: 28 GB at 2^20 points).
  * zk_pk_eval_h: 1 if proofs of this key for this system take that path. */
 int zk_pk_eval_h(const zk_pk* pk, const zk_r1cs* r1cs);
+/* The same two tables for a key that was loaded (zk_pk_upload, zk_pk_deserialize), from the key's own points and the constraint
+ * system -- no trapdoor: h_query through a transform over G1 POINTS (csrc/g1_ntt.hip) and through the transposed sparse product with
+ * C.  They are the group elements zk_groth16_setup makes, so the proofs keep their bytes and take the four-transform witness map from
+ * then on; call it once per key after loading.  Before the tables are published the call checks the identity behind them on a random
+ * assignment of its own, over the key's own h_query / l_query: a key that fails it (points outside the prime-order subgroup) is left
+ * exactly as it was and the call returns ZK_ERR_ARG, with the reason in zk_last_error.  ZK_OK without doing anything: the key has
+ * the tables already, or ZK_G16_EVAL_H=0.  ZK_ERR_ARG: a null pointer, ni + nw != a_query's length, h_query not D - 1 points,
+ * l_query not nw points, D < 2, a key without its padded l_query.  ZK_ERR_NOMEM: the key with the two tables would not fit in half
+ * of the device memory (zk_groth16_setup's rule); the key is unchanged.  h_query, l_query and what serialises stay as they are; the
+ * collaborative, trait-shaped and several-device provers ignore the tables as they do for a key that was set up.  2 s at 2^20 points, half
+ * of what zk_pk_deserialize takes for that key. */
+int zk_pk_derive_eval_h(zk_ctx* ctx, zk_pk* pk, const zk_r1cs* r1cs);
+/* The tables of a key that carries them (tests): which 0 = h_eval (D points), 1 = l_eval_pad (ni + nw points), 2 = l_eval_0 (one
+ * point).  ZK_ERR_ARG for a key without them. */
+int zk_pk_download_eval_g1(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g1_affine* out);
 uint32_t zk_msm_mul_levels_clamp(uint32_t window_bits, uint32_t levels);   /* the M a table with windows of that width gets for `levels` */
 int zk_pk_download_g1(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g1_affine* out);
 int zk_pk_download_g2(zk_ctx* ctx, const zk_pk* pk, int which, size_t offset, size_t n, zk_g2_affine* out);
@@ -798,6 +814,13 @@ int zk_diag_g1_lincomb_dev(zk_ctx* ctx, const zk_g1_affine* points, size_t n_poi
                            const uint32_t* seg_offsets, size_t n_segments, zk_g1_affine* out);
 int zk_diag_g1_lincomb_host(const zk_g1_affine* points, size_t n_points, const uint32_t* point_index, const uint32_t* scalars,
                             const uint32_t* seg_offsets, size_t n_segments, zk_g1_affine* out);
+/* Test hooks: `count` transforms of 2^log_n G1 points each, out[v][j] = sum_i w^(ij) points[v][i] with w the domain generator of that
+ * size (inverse_root: 1 / w), natural order in and out, no scaling -- as the device kernels of csrc/g1_ntt.hip compute them (one
+ * butterfly per lane, one launch per level) and as the same per-butterfly source computes them on the host with a plain loop around
+ * it.  A point with all-zero words is infinity, and so is a result.  ZK_ERR_ARG: a null pointer, log_n > 12, count outside 1 .. 16, a
+ * coordinate word not below q. */
+int zk_diag_g1_ntt_dev(zk_ctx* ctx, const zk_g1_affine* points, uint32_t log_n, size_t count, int inverse_root, zk_g1_affine* out);
+int zk_diag_g1_ntt_host(const zk_g1_affine* points, uint32_t log_n, size_t count, int inverse_root, zk_g1_affine* out);
 /* Diagnostic: k * a in G1 through the curve's endomorphism (hostfield64.hpp: host64_scalar_mul_glv: k split at lambda = z^2 - 1, one
  * joint chain) -- what the host tail of a Groth16 proof runs for keys made by zk_groth16_setup.  Equal to zk_g1_mul for every point of
  * the prime-order subgroup; kept apart from it because ProjectiveCurve::mul (zk_g1_mul) is defined on the whole curve. */

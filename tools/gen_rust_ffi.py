@@ -428,6 +428,10 @@ pub fn create_proof_shared(pk: *const ZkPk, r1cs: *const ZkR1cs, z_share_dev: *c
         std::ptr::null(), std::ptr::null(), std::ptr::null() /* DummyFieldTripleSource */, &net, proof.as_mut_ptr(), &mut sent) }));
     proof
 }
+// After ProvingKey::deserialize (zk_pk_deserialize / zk_pk_upload) call this once per key: it builds the tables of "H over coset
+// values" from the key's own points, and create_proof_local then runs four transforms per proof instead of six, to the same bytes.
+// A key that has the tables is left alone; a key whose points fail the call's self-check keeps the old path (the error is returned).
+pub fn derive_eval_h(pk: *mut ZkPk, r1cs: *const ZkR1cs) -> i32 { CTX.with(|c| unsafe { zk_pk_derive_eval_h(*c, pk, r1cs) }) }
 pub fn create_proof_local(pk: *const ZkPk, r1cs: *const ZkR1cs, full_assignment: &[Fr], r: &Fr, s: &Fr) -> [u8; 192] {
     let mut proof = [0u8; 192];
     CTX.with(|c| check(unsafe { zk_groth16_prove(*c, pk, r1cs, full_assignment.as_ptr() as *const ZkFr, r as *const Fr as *const ZkFr,

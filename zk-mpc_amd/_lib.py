@@ -189,6 +189,8 @@ PROTOTYPES = {
     "zk_pk_eval_h": (_I, [_P, _P]),
     "zk_msm_mul_levels_clamp": (_U32, [_U32, _U32]),
     "zk_pk_download_g1": (_I, [_P, _P, _I, _SZ, _SZ, _P]),
+    "zk_pk_derive_eval_h": (_I, [_P, _P, _P]),
+    "zk_pk_download_eval_g1": (_I, [_P, _P, _I, _SZ, _SZ, _P]),
     "zk_pk_download_g2": (_I, [_P, _P, _I, _SZ, _SZ, _P]),
     "zk_pk_vk_g1": (_I, [_P, _I, _P]),
     "zk_pk_vk_g2": (_I, [_P, _I, _P]),
@@ -297,6 +299,8 @@ PROTOTYPES = {
     "zk_marlin_verify_batch": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P]),
     "zk_diag_g1_lincomb_dev": (_I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "zk_diag_g1_lincomb_host": (_I, [_P, _SZ, _P, _P, _P, _SZ, _P]),
+    "zk_diag_g1_ntt_dev": (_I, [_P, _P, _U32, _SZ, _I, _P]),
+    "zk_diag_g1_ntt_host": (_I, [_P, _U32, _SZ, _I, _P]),
 }
 
 _lib = None

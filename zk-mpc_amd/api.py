@@ -745,6 +745,16 @@ class Context:
         self._ck(self.lib.zk_pk_upload(self.h, C.byref(h), C.byref(out)))
         return ProvingKey(self, out)
 
+    def g1_ntt(self, points: np.ndarray, inverse_root: bool = False, host: bool = False) -> np.ndarray:
+        """Test hook (zk_diag_g1_ntt_dev / _host): the transform over G1 points of csrc/g1_ntt.hip, natural order, no scaling.
+        points: (n, 12) or (count, n, 12) uint64 with n a power of two up to 2^12; the result has the same shape."""
+        if host:
+            return g1_ntt_host(points, inverse_root)
+        pts, log_n, count = _g1_ntt_args(points)
+        out = np.zeros_like(pts)
+        self._ck(self.lib.zk_diag_g1_ntt_dev(self.h, _ptr(pts), log_n, count, int(inverse_root), _ptr(out)))
+        return out.reshape(np.shape(points))
+
     def witness_map_dev(self, r1cs: "R1cs", z_dev, h_dev):
         self._ck(self.lib.zk_groth16_witness_map_dev(self.h, r1cs.h, C.c_void_p(int(z_dev)), C.c_void_p(int(h_dev))))
 
@@ -956,6 +966,22 @@ class ProvingKey:
         """zk_pk_eval_h: local proofs of this key for this system multiply h_eval with a o b on the coset (four transforms per proof)."""
         return bool(self.ctx.lib.zk_pk_eval_h(self.h, r1cs.h))
 
+    def derive_eval_h(self, r1cs: "R1cs"):
+        """zk_pk_derive_eval_h: give a key that was loaded (pk_upload, proving_key_from_bytes) the tables of H over coset values, from
+        its own points and the constraint system.  Once per key; a key that has them is left alone.  Raises ZkError for a key that
+        fails the call's self-check (the key then proves as before)."""
+        self.ctx._ck(self.ctx.lib.zk_pk_derive_eval_h(self.ctx.h, self.h, r1cs.h))
+
+    EVAL_TABLES = {"h_eval": 0, "l_eval_pad": 1, "l_eval_0": 2}
+
+    def download_eval(self, name: str) -> np.ndarray:
+        """zk_pk_download_eval_g1: h_eval (D points), l_eval_pad (one per variable) or l_eval_0 (one point) as (n, 12) uint64."""
+        which = self.EVAL_TABLES[name]
+        n = 1 if which == 2 else (self.query_len("h_query") + 1 if which == 0 else self.query_len("a_query"))
+        out = np.zeros((n, 12), dtype=np.uint64)
+        self.ctx._ck(self.ctx.lib.zk_pk_download_eval_g1(self.ctx.h, self.h, which, 0, n, _ptr(out)))
+        return out
+
     def query_len(self, name: str) -> int:
         return self.ctx.lib.zk_pk_query_len(self.h, self.QUERIES[name])
 
@@ -1003,6 +1029,21 @@ def _pairing_args(p, q, pairs):
     if pairs < 1 or p.shape[0] != q.shape[0] or p.shape[0] == 0 or p.shape[0] % pairs:
         raise ValueError("pairing_products: need as many G1 as G2 points, a positive multiple of `pairs`")
     return p, q, p.shape[0] // pairs
+
+
+def _g1_ntt_args(points):
+    pts = np.ascontiguousarray(points, dtype=np.uint64)
+    if pts.ndim not in (2, 3) or pts.shape[-1] != 12 or pts.shape[-2] == 0 or pts.shape[-2] & (pts.shape[-2] - 1):
+        raise ValueError("g1_ntt: need (n, 12) or (count, n, 12) uint64 with n a power of two")
+    return pts, pts.shape[-2].bit_length() - 1, 1 if pts.ndim == 2 else pts.shape[0]
+
+
+def g1_ntt_host(points: np.ndarray, inverse_root: bool = False) -> np.ndarray:
+    """zk_diag_g1_ntt_host: the butterfly source of csrc/g1_ntt.cuh compiled for the host, no device and no Context."""
+    pts, log_n, count = _g1_ntt_args(points)
+    out = np.zeros_like(pts)
+    _ck_host(_lib.load().zk_diag_g1_ntt_host(_ptr(pts), log_n, count, int(inverse_root), _ptr(out)), "zk_diag_g1_ntt_host")
+    return out.reshape(np.shape(points))
 
 
 def _ck_host(rc: int, what: str):

@@ -306,6 +306,15 @@ int precompute_t(zk_ctx* ctx, zk_bases* b, uint32_t c, uint32_t W, int layout, u
 
 }  // namespace
 
+// k_batch_affine over n G1 points that are on the device already, on ctx->stream, no wait (scr: n Fq elements): how g1_ntt.hip ends a transform
+int zk_g1_batch_affine_launch(zk_ctx* ctx, const uint32_t* in_xyzz, uint32_t* out_aff, uint32_t* scr, size_t n) {
+    if (!n) return ZK_OK;
+    const size_t chunks = (n + NORM_CHUNK - 1) / NORM_CHUNK;
+    hipLaunchKernelGGL(k_batch_affine<G1Field>, (unsigned)((chunks + 63) / 64), 64, 0, ctx->stream, in_xyzz, out_aff, scr, n);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+
 extern "C" int zk_fixed_base_g1_dev(zk_ctx* ctx, const zk_fr* gen_k, const void* scalars, size_t n, zk_bases** out) {
     ZK_API_BEGIN(ctx)
     return fixed_base_run<G1Field>(ctx, g1_generator(), gen_k, scalars, n, 1, out);

@@ -7,6 +7,7 @@
 // The proving key's five queries are zk_bases tables (resident, with window multiples from 2^16 points on).
 #include "../../include/zkmpc_hip.h"
 #include "groth16_int.hpp"
+#include "g1_lincomb.cuh"
 
 using namespace zk;
 
@@ -326,3 +327,227 @@ extern "C" int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r, const zk_fr* alph
     ZK_API_END
 }
 
+// ---- H over coset values for a key that was LOADED: the two tables from the key's own points -----------------------------------
+
+namespace {
+
+struct DevBuf {                                                        // device memory of one call (the scratch slots are never given back)
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(zk_ctx* ctx, size_t bytes) {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { p = nullptr; (void)hipGetLastError(); ZK_FAIL(ctx, ZK_ERR_NOMEM, "zk_pk_derive_eval_h: hipMalloc failed"); }
+        return ZK_OK;
+    }
+    uint32_t* w() const { return (uint32_t*)p; }
+};
+int upload_words(zk_ctx* ctx, DevBuf* d, const std::vector<uint32_t>& v) {
+    ZK_TRY(d->alloc(ctx, v.size() * 4));
+    ZK_HIP(ctx, hipMemcpyAsync(d->p, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    return ZK_OK;
+}
+
+// K_k = sum_r C_rk W_r for every column k < m of C (W: D affine points, table form): one segment of zk_g1_lincomb_launch per chunk of
+// at most 64 terms of a column, then launches that add the partial sums of a column (scalar 1) until every column is one point.
+// K: m affine points.
+int transposed_c_product(zk_ctx* ctx, const zk_r1cs* r, const uint32_t* W, size_t D, DevBuf* K) {
+    const auto& mc = r->m[2];
+    const size_t m = r->ni + r->nw, nnz = mc.h_col.size();
+    std::vector<uint32_t> start(m + 1, 0), rows(nnz), scal(nnz * 8, 0);
+    for (size_t e = 0; e < nnz; e++) start[mc.h_col[e] + 1]++;
+    for (size_t k = 0; k < m; k++) start[k + 1] += start[k];
+    {
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < r->nc; i++)
+            for (uint32_t e = mc.h_row_ptr[i]; e < mc.h_row_ptr[i + 1]; e++) {
+                const uint32_t at = fill[mc.h_col[e]]++;
+                rows[at] = (uint32_t)i;
+                if (mc.all_one) scal[8 * (size_t)at] = 1;
+                else fp_pack<FrParams>(&scal[8 * (size_t)at], fp_int_to_canon<FrParams>(mc.h_coeff[e]));
+            }
+    }
+    std::vector<uint32_t> len(m);                                      // terms of column k at this level
+    for (size_t k = 0; k < m; k++) len[k] = start[k + 1] - start[k];
+    DevBuf pts_prev;                                                   // the level before's partial sums
+    const uint32_t* pts = W;
+    size_t n_pts = D;
+    for (bool first = true;; first = false) {
+        ZkLincombPack pack;
+        std::vector<uint32_t> idx, ones;
+        size_t at = 0, most = 0;
+        for (size_t k = 0; k < m; k++) {
+            for (size_t lo = 0; lo < len[k] || lo == 0; lo += LINCOMB_MAX_TERMS) {
+                const size_t n = std::min<size_t>(LINCOMB_MAX_TERMS, len[k] - lo);
+                bool ok;
+                if (first) ok = pack.add(rows.data() + at + lo, scal.data() + 8 * (at + lo), n);
+                else {
+                    idx.resize(n); ones.assign(8 * n, 0);
+                    for (size_t t = 0; t < n; t++) { idx[t] = (uint32_t)(at + lo + t); ones[8 * t] = 1; }
+                    ok = pack.add(idx.data(), ones.data(), n);
+                }
+                if (!ok) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_pk_derive_eval_h: a segment of more than 64 terms");
+            }
+            at += len[k];
+            len[k] = len[k] ? (uint32_t)((len[k] + LINCOMB_MAX_TERMS - 1) / LINCOMB_MAX_TERMS) : 1u;
+            most = std::max<size_t>(most, len[k]);
+        }
+        pack.finish();
+        const size_t n_seg = pack.seg_off.size() - 1;
+        DevBuf d_idx, d_k, d_off, d_inf, out;
+        ZK_TRY(upload_words(ctx, &d_idx, pack.point_index));
+        ZK_TRY(upload_words(ctx, &d_k, pack.scalars));
+        ZK_TRY(upload_words(ctx, &d_off, pack.seg_off));
+        ZK_TRY(d_inf.alloc(ctx, n_seg * 4));
+        ZK_TRY(out.alloc(ctx, n_seg * 96));
+        ZK_TRY(zk_g1_lincomb_launch(ctx, pts, n_pts, d_idx.w(), d_k.w(), d_off.w(), n_seg, pack.lanes(), out.w(), d_inf.w()));
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));                // (the pack is a local)
+        std::swap(pts_prev.p, out.p);                                  // (out now frees the level before's)
+        pts = pts_prev.w();
+        n_pts = n_seg;
+        if (most == 1) break;
+    }
+    std::swap(K->p, pts_prev.p);
+    return n_pts == m ? ZK_OK : ZK_ERR_STATE;
+}
+
+}  // namespace
+
+// The tables of "H over coset values" (zk_pk::h_eval, l_eval_pad, l_eval_0) for a key that came in through zk_pk_upload or
+// zk_pk_deserialize, from the key's own points -- nobody holds the trapdoor of such a key.  With H_i = h_query[i] (H_(D-1) = O),
+// zinv = 1 / Z(g), w the domain generator, g the coset generator:
+//   h_eval[j]     = sum_i w^(-ij) (zinv g^(-i) / D) H_i        a size-D transform over POINTS with root 1/w (g1_ntt.hip)
+//   W_r           = sum_i w^(-ir) (zinv / D) H_i               the same transform of the second vector of that batch
+//   l_eval_pad[k] = l_pad[k] - sum_r C_rk W_r                  the transposed sparse product, one short linear combination per column
+// -- the group elements zk_groth16_setup makes from the trapdoor, hence the same canonical words and the same proof bytes.  Before the
+// tables are published the call proves the identity on an assignment of its own (z_0 = 1, the rest random: the identity is linear,
+// the assignment need not satisfy anything): h_query x h + l_pad x z against h_eval x e + l_eval_pad x z + l_eval_0.  A key whose
+// h_query / l_query are not what a setup produces -- a point with a component outside the prime-order subgroup breaks the transform's
+// algebra -- fails it: the tables are dropped, the key stays exactly as it was, ZK_ERR_ARG.
+// ZK_OK and nothing done: the key has the tables already, or ZK_G16_EVAL_H=0.  ZK_ERR_ARG: a null pointer, a system of another size
+// (ni + nw != a_query's length, h_query not D - 1 points, l_query not nw points, D < 2), a key without l_pad.  ZK_ERR_NOMEM: the key
+// with six G1 tables at its mul_levels would not fit in half of the device memory that is free when the key's present tables are
+// counted as free (zk_groth16_setup's rule); the key is unchanged.  A pending presort / front is dropped.  With zk_set_profiling
+// the phases' wall times are left in the context's timers ("derive.transforms", ".product", ".tables", ".check").
+extern "C" int zk_pk_derive_eval_h(zk_ctx* ctx, zk_pk* pk, const zk_r1cs* r) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !pk || !r) return ZK_ERR_ARG;
+    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw;
+    if (!pk->a || !pk->h || !pk->l || m != pk->a->n || r->log_d < 1 || pk->h->n != D - 1 || pk->l->n != r->nw)
+        ZK_FAIL(ctx, ZK_ERR_ARG, "zk_pk_derive_eval_h: the key does not belong to this constraint system");
+    if (pk->h_eval && pk->l_eval_pad) return ZK_OK;
+    if (!zk_g16_eval_h_enabled()) return ZK_OK;
+    if (!pk->l_pad || pk->l_pad->n != m) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_pk_derive_eval_h: the key has no padded l_query");
+    {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 0; }
+        if (zk_key_tables_bytes(m, pk->mul_levels, 6) > (mem_free + zk_key_tables_bytes(m, pk->mul_levels, 4)) / 2)
+            ZK_FAIL(ctx, ZK_ERR_NOMEM, "zk_pk_derive_eval_h: the key with the two tables would take more than half of the device memory");
+    }
+    zk_presort_free(ctx);
+    using Clock = std::chrono::steady_clock;
+    auto t0 = Clock::now();
+    auto lap = [&](const char* name) {
+        if (!ctx->profiling) return;
+        auto& t = ctx->timers[name];
+        const auto now = Clock::now();
+        t.ms += std::chrono::duration<float, std::milli>(now - t0).count();
+        t.count += 1;
+        t0 = now;
+    };
+    struct Tables {                                                    // the two tables until they are published
+        zk_ctx* ctx;
+        zk_bases *he = nullptr, *le = nullptr;
+        ~Tables() { zk_bases_free(ctx, he); zk_bases_free(ctx, le); }
+    } tb{ctx};
+
+    // the pre-scales zinv g^(-i) / D (i < D) and zinv / D as raw scalars
+    uint32_t zw[9];
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zw));
+    Fr c;
+    for (int i = 0; i < 9; i++) c.l[i] = zw[i];
+    c = fp_mul<FrParams>(c, fp_inv<FrParams>(host_fr_from_u64(D)));
+    {
+        std::vector<uint32_t> sc((D + 1) * 8);
+        const Fr ginv = fp_const<FrParams>(FrParams::GENERATOR_INV);
+        Fr p = c;
+        for (size_t i = 0; i < D; i++) { fp_pack<FrParams>(&sc[8 * i], fp_int_to_canon<FrParams>(p)); p = fp_mul<FrParams>(p, ginv); }
+        fp_pack<FrParams>(&sc[8 * D], fp_int_to_canon<FrParams>(c));
+        DevBuf d_sc, work, scr, W, K;
+        const uint32_t* tw;
+        ZK_TRY(upload_words(ctx, &d_sc, sc));
+        ZK_TRY(zk_g1_ntt_twiddles(ctx, r->log_d, 1, &tw));           // (waits: sc has been read)
+        ZK_TRY(work.alloc(ctx, std::max(2 * D, m) * 192));
+        ZK_TRY(scr.alloc(ctx, std::max(D, m) * 48));
+        ZK_TRY(W.alloc(ctx, D * 96));
+        ZK_TRY(zk_bases_alloc_dev(ctx, 1, D, &tb.he));
+        const ZkG1NttScale scale{d_sc.w(), {0u, (uint32_t)D}, {1u, 0u}};
+        ZK_TRY(zk_g1_ntt_launch(ctx, pk->h->dev, D - 1, 0, &scale, r->log_d, 2, tw, work.w()));
+        ZK_TRY(zk_g1_batch_affine_launch(ctx, work.w(), tb.he->dev, scr.w(), D));
+        ZK_TRY(zk_g1_batch_affine_launch(ctx, work.w() + D * 48, W.w(), scr.w(), D));
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        lap("derive.transforms");
+        ZK_TRY(transposed_c_product(ctx, r, W.w(), D, &K));
+        ZK_TRY(zk_bases_alloc_dev(ctx, 1, m, &tb.le));
+        ZK_TRY(zk_g1_sub_launch(ctx, pk->l_pad->dev, K.w(), work.w(), m));
+        ZK_TRY(zk_g1_batch_affine_launch(ctx, work.w(), tb.le->dev, scr.w(), m));
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        lap("derive.product");
+    }
+    ZK_TRY(zk_bases_precompute_levels(ctx, tb.he, pk->mul_levels));
+    ZK_TRY(zk_bases_precompute_levels(ctx, tb.le, pk->mul_levels));
+    Affine<G1Field> le0;
+    ZK_TRY(first_point<G1Field>(ctx, tb.le, &le0));
+    lap("derive.tables");
+
+    // the identity on an assignment of the call's own, over the key's tables and over the new ones
+    {
+        DevBuf z, h;
+        ZK_TRY(z.alloc(ctx, m * 32));
+        ZK_TRY(h.alloc(ctx, D * 32));
+        ZK_TRY(zk_fr_random_dev(ctx, nullptr, 0, z.p, m));
+        uint32_t one[8];
+        fp_pack<FrParams>(one, fp_int_to_ext<FrParams>(fp_one<FrParams>()));
+        ZK_HIP(ctx, hipMemcpyAsync(z.p, one, 32, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        zk_g1_projective s_h, s_l, s_he, s_le;
+        ZK_TRY(zk_groth16_witness_map_dev(ctx, r, z.p, h.p));
+        ZK_TRY(zk_msm_run(ctx, pk->h, 0, h.p, D - 1, &s_h));
+        ZK_TRY(zk_msm_run(ctx, pk->l_pad, 1, (const char*)z.p + 32, m - 1, &s_l));
+        ZK_TRY(zk_groth16_witness_map_eval_dev(ctx, r, z.p, h.p));
+        ZK_TRY(zk_msm_run(ctx, tb.he, 0, h.p, D, &s_he));
+        ZK_TRY(zk_msm_run(ctx, tb.le, 1, (const char*)z.p + 32, m - 1, &s_le));
+        using H = Fq64Field;
+        const Affine<H> lhs = xyzz_to_affine<H>(xyzz_add<H>(host64_proj_from_abi<H>((const uint64_t*)&s_h), host64_proj_from_abi<H>((const uint64_t*)&s_l)));
+        const Affine<H> rhs = xyzz_to_affine<H>(xyzz_madd<H>(
+            xyzz_add<H>(host64_proj_from_abi<H>((const uint64_t*)&s_he), host64_proj_from_abi<H>((const uint64_t*)&s_le)), aff_to_host64<G1Field>(le0)));
+        lap("derive.check");
+        if (!H::eq(lhs.x, rhs.x) || !H::eq(lhs.y, rhs.y))
+            ZK_FAIL(ctx, ZK_ERR_ARG,
+                    "zk_pk_derive_eval_h: the key's h_query / l_query do not satisfy the identity of H over coset values (points outside the "
+                    "prime-order subgroup, or a key of another system); the key is unchanged");
+    }
+    zk_presort_free(ctx);
+    pk->h_eval = tb.he;
+    pk->l_eval_pad = tb.le;
+    pk->l_eval_0 = le0;
+    tb.he = tb.le = nullptr;
+    if (!ZkG16Jobs(pk, r, nullptr, nullptr).eval_h) {                  // (a table that got fewer shifted copies than the key's: no memory for them)
+        zk_bases_free(ctx, pk->h_eval); zk_bases_free(ctx, pk->l_eval_pad);
+        pk->h_eval = pk->l_eval_pad = nullptr;
+        ZK_FAIL(ctx, ZK_ERR_NOMEM, "zk_pk_derive_eval_h: no memory for the window multiples of the two tables; the key is unchanged");
+    }
+    return ZK_OK;
+    ZK_API_END
+}
+
+// h_eval (which = 0: D points), l_eval_pad (1: ni + nw points) or l_eval_0 (2: one point) of a key that carries them
+extern "C" int zk_pk_download_eval_g1(zk_ctx* ctx, const zk_pk* pk, int which, size_t off, size_t n, zk_g1_affine* out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !pk || !pk->h_eval || !pk->l_eval_pad || which < 0 || which > 2 || (n && !out)) return ZK_ERR_ARG;
+    if (which == 2) {
+        if (off + n > 1) return ZK_ERR_ARG;
+        if (n) host_aff_to_abi<G1Field>((uint64_t*)out, pk->l_eval_0);
+        return ZK_OK;
+    }
+    return zk_bases_download_g1(ctx, which == 0 ? pk->h_eval : pk->l_eval_pad, off, n, out);
+    ZK_API_END
+}

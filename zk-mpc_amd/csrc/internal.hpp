@@ -288,6 +288,19 @@ struct ZkLincombPack {
     void finish() { seg_off.push_back((uint32_t)lanes()); }
 };
 
+// fixed_base.hip: n G1 points XYZZ -> affine table form (Montgomery's trick; scr_dev: n Fq elements), on ctx->stream, no wait
+int zk_g1_batch_affine_launch(zk_ctx* ctx, const uint32_t* in_xyzz_dev, uint32_t* out_affine_dev, uint32_t* scr_dev, size_t n);
+// g1_ntt.hip: `count` radix-2 transforms of 2^log_n G1 points that share their twiddles, one butterfly per lane, log_n butterfly
+// launches and one load launch whatever count is.  The input is affine (table form): vector v reads points in_dev[v in_vstride + i]
+// for i < n_in and infinity beyond; with `scale` point i of vector v is first multiplied by the raw 256-bit scalar number
+// scale->base[v] + i scale->step[v] of scale->k (count <= 2 then).  The result is left in work_xyzz_dev (count 2^log_n XYZZ points,
+// vector after vector, natural order) for zk_g1_batch_affine_launch.  On ctx->stream, no wait.
+struct ZkG1NttScale { const uint32_t* k; uint32_t base[2], step[2]; };
+int zk_g1_ntt_twiddles(zk_ctx* ctx, uint32_t log_n, int inverse_root, const uint32_t** twiddles_dev);   // 2^(log_n - 1) raw scalars in the "g1ntt_tw" slot
+int zk_g1_ntt_launch(zk_ctx* ctx, const uint32_t* in_dev, size_t n_in, size_t in_vstride, const ZkG1NttScale* scale, uint32_t log_n, size_t count,
+                     const uint32_t* twiddles_dev, uint32_t* work_xyzz_dev);
+int zk_g1_sub_launch(zk_ctx* ctx, const uint32_t* a_affine_dev, const uint32_t* b_affine_dev, uint32_t* out_xyzz_dev, size_t n);   // a[i] - b[i]
+
 // msm_sort.hip: the bucket sort (msm_digits.cuh declares its interface)
 
 // msm_g2pair.hip: the G2 accumulate kernel with two lanes per point addition
