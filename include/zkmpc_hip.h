@@ -210,11 +210,30 @@ int zk_bases_download_g2(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n
 size_t zk_point_serialized_size(int group, int compressed);      /* 48 / 96 (G1), 96 / 192 (G2) */
 int zk_bases_serialize(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n, int compressed, uint8_t* out_host);
 /* GroupAffine::deserialize_unchecked (:930-942) on n uncompressed points, plus an on-curve check (error instead of
- * a silently wrong table); no subgroup check. */
+ * a silently wrong table); no subgroup check (zk_bases_deserialize_checked makes one). */
 int zk_bases_deserialize_uncompressed(zk_ctx* ctx, int group, const uint8_t* bytes_host, size_t n, zk_bases** out);
 /* GroupAffine::deserialize (:888-905) on n compressed points: y from x by a square root in Fq / Fq2 (get_point_from_x,
- * :110-125), sign from the flag; error if an x is not on the curve; no subgroup check. */
+ * :110-125), sign from the flag; error if an x is not on the curve; no subgroup check (zk_bases_deserialize_checked makes one). */
 int zk_bases_deserialize_compressed(zk_ctx* ctx, int group, const uint8_t* bytes_host, size_t n, zk_bases** out);
+
+/* ---- subgroup membership (is_in_correct_subgroup_assuming_on_curve, short_weierstrass_jacobian.rs:146-149: r P == O) ----
+ * The reference makes this test on every point it deserialises (GroupAffine::deserialize / deserialize_uncompressed, :888-940).  Here
+ * it is a kernel of its own, one point per lane, through the curves' endomorphisms instead of the 253-bit chain: [z]([z] P) ==
+ * (beta^2 x, -y) on G1 and [z] Q == psi(Q) on G2, z the curve's seed -- the same verdict as r P == O for EVERY point of the curve
+ * (DESIGN 5b'''' has the proofs).  Infinity is in the subgroup.  Points are taken to be on their curve.
+ * zk_bases_subgroup_check: points [offset, offset + n) of a resident table in one launch.  *n_outside = how many are outside,
+ * *first_outside = the first of them counted from offset ((size_t)-1: none), in_each_host (or NULL) = n bytes, 1 = inside.  n = 0
+ * is allowed.  ZK_ERR_ARG: a null pointer, offset + n past the table. */
+int zk_bases_subgroup_check(zk_ctx* ctx, const zk_bases* bases, size_t offset, size_t n, uint8_t* in_each_host, size_t* n_outside,
+                            size_t* first_outside);
+/* The same test compiled for the host (64-bit limbs; no device, no context): flags[i] = 1 / 0.  ZK_ERR_ARG for a null pointer or a
+ * coordinate word that is not below q. */
+int zk_g1_in_subgroup_host(const zk_g1_affine* points, size_t n, uint8_t* flags);
+int zk_g2_in_subgroup_host(const zk_g2_affine* points, size_t n, uint8_t* flags);
+/* GroupAffine::deserialize (compressed != 0) / deserialize_uncompressed (compressed = 0) in full: zk_bases_deserialize_compressed /
+ * _uncompressed, then the subgroup test.  A point outside the subgroup is ZK_ERR_ARG like a point off the curve
+ * (SerializationError::InvalidData), zk_last_error names the index of the first one, and nothing is left allocated. */
+int zk_bases_deserialize_checked(zk_ctx* ctx, int group, const uint8_t* bytes_host, size_t n, int compressed, zk_bases** out);
 
 /* CanonicalSerialize framing of the Groth16 keys (arkworks/groth16/src/data_structures.rs:43-58,133-151) and of a KZG10
  * UniversalParams (poly-commit/src/kzg10/data_structures.rs:40-80, the file save_srs_to_file writes: src/marlin.rs:371-376), in the
@@ -230,6 +249,23 @@ int zk_kzg_srs_serialize(zk_ctx* ctx, const zk_bases* powers_g, const zk_bases* 
                          const zk_g2_affine* beta_h, int compressed, uint8_t* out_host, size_t cap);
 int zk_kzg_srs_deserialize(zk_ctx* ctx, const uint8_t* bytes_host, size_t len, int compressed, zk_bases** powers_g,
                            zk_bases** powers_gamma_g, zk_g2_affine* h, zk_g2_affine* beta_h);
+/* The two loaders above are deserialize_unchecked plus the curve equation.  The reference's deserialize also tests subgroup
+ * membership of every point; these do: the unchecked loader, then the test over every table (one launch per table) and the single
+ * points.  A point outside the subgroup is ZK_ERR_ARG with the part and the index in zk_last_error; nothing is left allocated and the
+ * outputs are not written.  A key that passes proves exactly as one from zk_pk_deserialize does. */
+int zk_pk_deserialize_checked(zk_ctx* ctx, const uint8_t* bytes_host, size_t len, int compressed, zk_pk** out);
+int zk_kzg_srs_deserialize_checked(zk_ctx* ctx, const uint8_t* bytes_host, size_t len, int compressed, zk_bases** powers_g,
+                                   zk_bases** powers_gamma_g, zk_g2_affine* h, zk_g2_affine* beta_h);
+/* The subgroup test over a resident key: parts 0 = a_query, 1 = b_g1_query, 2 = b_g2_query, 3 = h_query, 4 = l_query, 5 =
+ * gamma_abc_g1 (one launch per table, whatever its length), 6 = the single points in the order alpha_g1, beta_g1, delta_g1, beta_g2,
+ * gamma_g2, delta_g2 (on the host).  outside[k] = how many points of part k are outside, first[k] = the index of the first
+ * ((size_t)-1: none).  A point outside is a finding about the KEY, not an error of the call: ZK_OK with the report filled and the
+ * key untouched.  The call only reports: whatever it finds, the key proves as before (the O(1) tail of a loaded key's proofs keeps the
+ * plain scalar multiplication; only keys from zk_groth16_setup take the G1 endomorphism there).  ZK_ERR_ARG: a null pointer. */
+#define ZK_PK_SUBGROUP_PARTS 7
+typedef struct { size_t outside[7]; size_t first[7]; } zk_pk_subgroup_report;
+int zk_pk_check_subgroups(zk_ctx* ctx, const zk_pk* pk, zk_pk_subgroup_report* report);
+int zk_pk_points_in_subgroup(const zk_pk* pk);           /* 1: the key came from zk_groth16_setup (its tail takes the endomorphism); else 0 */
 
 /* n_jobs independent MSMs pipelined over the library's sort / accumulate streams (one job sorts while the previous one
  * accumulates).  outs[k] receives a zk_g1_projective or zk_g2_projective according to bases[k]'s group; base_offsets may
@@ -434,7 +470,8 @@ typedef struct { zk_fq c[12]; } zk_gt;
  * outs[k] = final_exponentiation(prod_{j < pairs} miller_loop(p[k * pairs + j], q[k * pairs + j])), k < count; host slices in and
  * out, device kernels (one Miller loop per lane, one final exponentiation per product).  A pair with either point at infinity
  * contributes the factor 1.  Points are taken as they come: on the curve and in the prime-order subgroups is the caller's business
- * (GroupAffine::deserialize checks both; zk_bases_deserialize_compressed checks the first).  pairs = 0, count = 0, a null
+ * (GroupAffine::deserialize checks both; zk_bases_deserialize_compressed checks the first, zk_bases_deserialize_checked and
+ * zk_g1_in_subgroup_host / zk_g2_in_subgroup_host the second).  pairs = 0, count = 0, a null
  * pointer or more than 2^22 pairs in all: ZK_ERR_ARG. */
 int zk_pairing_products(zk_ctx* ctx, const zk_g1_affine* p, const zk_g2_affine* q, size_t pairs, size_t count, zk_gt* outs);
 /* The same arithmetic compiled for the host (64-bit limbs; no device, no context): for O(1) checks and for tests.  Also
@@ -449,10 +486,16 @@ int zk_gt_mul(const zk_gt* a, const zk_gt* b, zk_gt* out);
  * the device; a proof whose bytes are not points of the curves gets ok = 0 (it is not an error of the call).  The prepared inputs
  * gamma_abc[0] + sum x_i gamma_abc[i] are one scalar-multiplication lane per proof, then 3 count Miller loops -- (A, B), (prepared,
  * -gamma), (C, -delta) -- and count final exponentiations, each compared with e(alpha, beta), which is computed once per key and kept
- * on it.  No subgroup check on A, B, C (Proof::deserialize does one).  ZK_ERR_ARG: a key without verifying-key parts (zk_pk_upload:
+ * on it.  No subgroup check on A, B, C (Proof::deserialize does one; so does zk_groth16_verify_batch_checked).  ZK_ERR_ARG: a key without verifying-key parts (zk_pk_upload:
  * its host view has no gamma), inputs_per_proof that does not match, an input that is not below r, a null pointer, count = 0. */
 int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                             const uint8_t* proofs_host, int* ok);
+/* The same with Proof::deserialize's subgroup test: behind the decompression A and C of every proof (one launch over 2 count G1
+ * points) and B (one launch over count G2 points) go through the subgroup kernel, and a proof with a point outside gets ok = 0 --
+ * where the unchecked form answers 1 for a valid proof whose A or C was moved by a point of the cofactor torsion, which the pairing
+ * does not see.  Same arguments, same errors; the launches do not grow with count. */
+int zk_groth16_verify_batch_checked(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                    const uint8_t* proofs_host, int* ok);
 /* One proof through the host arithmetic (no device, no context), on a host view of the VerifyingKey
  * (arkworks/groth16/src/data_structures.rs:43-58; a resident key gives it through zk_pk_vk_g1 / zk_pk_vk_g2 / zk_pk_download_g1
  * with which = 5).  n_inputs must be gamma_abc_len - 1. */
@@ -462,6 +505,8 @@ typedef struct {
     const zk_g1_affine* gamma_abc_g1; size_t gamma_abc_len;
 } zk_vk_host;
 int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok);
+/* ... with the subgroup test on A, B, C (the host instantiation of the same code). */
+int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok);
 
 /* ---- Marlin verification ------------------------------------------------------------------------------------------------------ */
 /* Marlin::verify (arkworks/marlin/src/lib.rs:324-442) with MarlinKZG10::check_combinations, for proofs as zk_marlin_prove writes them

@@ -76,6 +76,10 @@ class MarlinVkHost(C.Structure):
                 ("h", G2Affine), ("beta_h", G2Affine), ("shift_h", G1Affine), ("shift_k", G1Affine)]
 
 
+class PkSubgroupReport(C.Structure):
+    _fields_ = [("outside", C.c_size_t * 7), ("first", C.c_size_t * 7)]
+
+
 class R1csHost(C.Structure):
     _fields_ = [("num_constraints", C.c_size_t), ("num_instance", C.c_size_t), ("num_witness", C.c_size_t),
                 ("a_row_ptr", C.c_void_p), ("a_col", C.c_void_p), ("a_coeff", C.c_void_p),
@@ -301,6 +305,16 @@ PROTOTYPES = {
     "zk_diag_g1_lincomb_host": (_I, [_P, _SZ, _P, _P, _P, _SZ, _P]),
     "zk_diag_g1_ntt_dev": (_I, [_P, _P, _U32, _SZ, _I, _P]),
     "zk_diag_g1_ntt_host": (_I, [_P, _U32, _SZ, _I, _P]),
+    "zk_bases_subgroup_check": (_I, [_P, _P, _SZ, _SZ, _P, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "zk_g1_in_subgroup_host": (_I, [_P, _SZ, _P]),
+    "zk_g2_in_subgroup_host": (_I, [_P, _SZ, _P]),
+    "zk_bases_deserialize_checked": (_I, [_P, _I, _P, _SZ, _I, C.POINTER(_P)]),
+    "zk_pk_deserialize_checked": (_I, [_P, _P, _SZ, _I, C.POINTER(_P)]),
+    "zk_kzg_srs_deserialize_checked": (_I, [_P, _P, _SZ, _I, C.POINTER(_P), C.POINTER(_P), _P, _P]),
+    "zk_pk_check_subgroups": (_I, [_P, _P, _P]),
+    "zk_pk_points_in_subgroup": (_I, [_P]),
+    "zk_groth16_verify_batch_checked": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
+    "zk_groth16_verify_host_checked": (_I, [_P, _P, _SZ, _P, _P]),
 }
 
 _lib = None

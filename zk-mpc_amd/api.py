@@ -395,16 +395,30 @@ class Context:
         self._ck(fn(self.h, _ptr(arr), arr.shape[0], C.byref(h)))
         return Bases(self, h, group)
 
-    def bases_deserialize_uncompressed(self, data: bytes, n: int, group: int) -> "Bases":
-        return self._bases_deserialize(data, n, group, 0)
+    def bases_deserialize_uncompressed(self, data: bytes, n: int, group: int, check_subgroup: bool = False) -> "Bases":
+        """GroupAffine::deserialize_unchecked plus the curve equation; check_subgroup: deserialize_uncompressed in full
+        (zk_bases_deserialize_checked: a point outside the prime-order subgroup raises ZkError naming its index)."""
+        return self._bases_deserialize(data, n, group, 0, check_subgroup)
 
-    def bases_deserialize_compressed(self, data: bytes, n: int, group: int) -> "Bases":
-        return self._bases_deserialize(data, n, group, 1)
+    def bases_deserialize_compressed(self, data: bytes, n: int, group: int, check_subgroup: bool = False) -> "Bases":
+        return self._bases_deserialize(data, n, group, 1, check_subgroup)
 
-    def _bases_deserialize(self, data: bytes, n: int, group: int, compressed: int) -> "Bases":
+    def bases_subgroup_check(self, bases: "Bases", offset: int = 0, n: int = None):
+        """zk_bases_subgroup_check: the subgroup test (r P == O, through the endomorphisms) over points [offset, offset + n) of a
+        resident table in one launch.  -> (in_each (n,) uint8 with 1 = inside, n_outside, first_outside or None)."""
+        n = len(bases) - offset if n is None else n
+        each = np.zeros(max(n, 1), dtype=np.uint8)
+        n_out, first = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.lib.zk_bases_subgroup_check(self.h, bases.h, offset, n, _ptr(each), C.byref(n_out), C.byref(first)))
+        return each[:n], n_out.value, (None if first.value == C.c_size_t(-1).value else first.value)
+
+    def _bases_deserialize(self, data: bytes, n: int, group: int, compressed: int, check_subgroup: bool = False) -> "Bases":
         buf = np.frombuffer(data, dtype=np.uint8)
         assert buf.size == n * self.lib.zk_point_serialized_size(group, compressed)
         out = C.c_void_p()
+        if check_subgroup:
+            self._ck(self.lib.zk_bases_deserialize_checked(self.h, group, _ptr(np.ascontiguousarray(buf)) if n else None, n, compressed, C.byref(out)))
+            return Bases(self, out, group)
         fn = self.lib.zk_bases_deserialize_compressed if compressed else self.lib.zk_bases_deserialize_uncompressed
         self._ck(fn(self.h, group, _ptr(np.ascontiguousarray(buf)) if n else None, n, C.byref(out)))
         return Bases(self, out, group)
@@ -872,9 +886,10 @@ class Context:
         self._ck(self.lib.zk_pairing_products(self.h, _ptr(p), _ptr(q), pairs, count, _ptr(out)))
         return out
 
-    def groth16_verify_batch(self, pk: "ProvingKey", inputs_mont: np.ndarray, proofs) -> np.ndarray:
+    def groth16_verify_batch(self, pk: "ProvingKey", inputs_mont: np.ndarray, proofs, check_subgroup: bool = False) -> np.ndarray:
         """Groth16::verify for many proofs of one key: inputs_mont (count, num_instance - 1, 4) Montgomery, proofs = count x 192
-        bytes (a list of proofs or one bytes object); returns count verdicts (1 / 0)."""
+        bytes (a list of proofs or one bytes object); returns count verdicts (1 / 0).  check_subgroup: A, B, C also pass the
+        subgroup test of Proof::deserialize (zk_groth16_verify_batch_checked)."""
         data = b"".join(proofs) if isinstance(proofs, (list, tuple)) else bytes(proofs)
         if len(data) % 192:
             raise ValueError("proofs must be a whole number of 192-byte proofs")
@@ -882,12 +897,13 @@ class Context:
         inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(count, -1, 4) if count else np.zeros((0, 0, 4), np.uint64)
         buf = np.frombuffer(data, dtype=np.uint8)
         ok = np.zeros(count, dtype=np.int32)
-        self._ck(self.lib.zk_groth16_verify_batch(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(ok)))
+        fn = self.lib.zk_groth16_verify_batch_checked if check_subgroup else self.lib.zk_groth16_verify_batch
+        self._ck(fn(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(ok)))
         return ok
 
-    def groth16_verify(self, pk: "ProvingKey", inputs_mont: np.ndarray, proof: bytes) -> bool:
+    def groth16_verify(self, pk: "ProvingKey", inputs_mont: np.ndarray, proof: bytes, check_subgroup: bool = False) -> bool:
         """Groth16::verify of one proof as create_proof returns it (device path)."""
-        return bool(self.groth16_verify_batch(pk, np.asarray(inputs_mont, dtype=np.uint64).reshape(1, -1, 4), proof)[0])
+        return bool(self.groth16_verify_batch(pk, np.asarray(inputs_mont, dtype=np.uint64).reshape(1, -1, 4), proof, check_subgroup)[0])
 
     def diag_fq12(self, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         """Test hook: the Fq12 tower on the device, one case (a[i], b[i]) per lane; a, b (n, 72) uint64."""
@@ -982,6 +998,21 @@ class ProvingKey:
         self.ctx._ck(self.ctx.lib.zk_pk_download_eval_g1(self.ctx.h, self.h, which, 0, n, _ptr(out)))
         return out
 
+    SUBGROUP_PARTS = ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query", "gamma_abc_g1", "single_points")
+
+    def check_subgroups(self) -> dict:
+        """zk_pk_check_subgroups: the subgroup test over every table and single point of the key.  -> {part: (n_outside,
+        first_outside or None)}.  A report only: the key proves as before whatever it says."""
+        rep = _lib.PkSubgroupReport()
+        self.ctx._ck(self.ctx.lib.zk_pk_check_subgroups(self.ctx.h, self.h, C.byref(rep)))
+        none = C.c_size_t(-1).value
+        return {name: (rep.outside[k], None if rep.first[k] == none else rep.first[k]) for k, name in enumerate(self.SUBGROUP_PARTS)}
+
+    @property
+    def points_in_subgroup(self) -> bool:
+        """zk_pk_points_in_subgroup: the key came from groth16_setup, and its proofs' tail takes the G1 endomorphism."""
+        return bool(self.ctx.lib.zk_pk_points_in_subgroup(self.h))
+
     def query_len(self, name: str) -> int:
         return self.ctx.lib.zk_pk_query_len(self.h, self.QUERIES[name])
 
@@ -1012,9 +1043,10 @@ class ProvingKey:
         self.ctx._ck(self.ctx.lib.zk_pk_vk_g2(self.h, which, _ptr(out)))
         return out
 
-    def verify_host(self, inputs_mont, proof: bytes) -> bool:
+    def verify_host(self, inputs_mont, proof: bytes, check_subgroup: bool = False) -> bool:
         """Groth16::verify of one proof through the host arithmetic, on this key's verifying-key parts."""
-        return groth16_verify_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont, proof)
+        return groth16_verify_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont, proof,
+                                   check_subgroup)
 
     def free(self):
         if self.h:
@@ -1109,9 +1141,21 @@ def diag_fq12_host(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return out
 
 
-def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes) -> bool:
+def in_subgroup_host(points, group: int) -> np.ndarray:
+    """zk_g1_in_subgroup_host / zk_g2_in_subgroup_host: the subgroup test on the host; points (n, 12) / (n, 24) uint64 in the ABI's
+    form -> (n,) uint8, 1 = inside."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12 if group == 1 else 24)
+    out = np.zeros(max(pts.shape[0], 1), dtype=np.uint8)
+    lib = _lib.load()
+    fn = lib.zk_g1_in_subgroup_host if group == 1 else lib.zk_g2_in_subgroup_host
+    _ck_host(fn(_ptr(pts), pts.shape[0], _ptr(out)), "zk_g%d_in_subgroup_host" % group)
+    return out[:pts.shape[0]]
+
+
+def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes, check_subgroup: bool = False) -> bool:
     """Groth16::verify of one proof through the host arithmetic, on a host view of the VerifyingKey (points as uint64 arrays in the
-    ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery."""
+    ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery.  check_subgroup: A, B, C also pass
+    Proof::deserialize's subgroup test (zk_groth16_verify_host_checked)."""
     vk = _lib.VkHost()
     abc = np.ascontiguousarray(gamma_abc_g1, dtype=np.uint64).reshape(-1, 12)
     for field, arr, n in (("alpha_g1", alpha_g1, 12), ("beta_g2", beta_g2, 24), ("gamma_g2", gamma_g2, 24), ("delta_g2", delta_g2, 24)):
@@ -1124,5 +1168,6 @@ def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inp
         raise ValueError("a proof is 192 bytes")
     buf = np.frombuffer(bytes(proof), dtype=np.uint8)
     ok = C.c_int(0)
-    _ck_host(_lib.load().zk_groth16_verify_host(C.byref(vk), _ptr(inp), inp.shape[0], _ptr(buf), C.byref(ok)), "zk_groth16_verify_host")
+    fn = _lib.load().zk_groth16_verify_host_checked if check_subgroup else _lib.load().zk_groth16_verify_host
+    _ck_host(fn(C.byref(vk), _ptr(inp), inp.shape[0], _ptr(buf), C.byref(ok)), "zk_groth16_verify_host")
     return bool(ok.value)

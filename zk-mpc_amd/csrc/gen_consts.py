@@ -149,6 +149,89 @@ def fq12_frobenius():
     return "\n".join(out)
 
 
+# ---- subgroup membership through the endomorphisms (subgroup.cuh) --------------------------------------------------------------------
+# A wrong constant below fails HERE (the build), not in a test: the identities are asserted on the generators with a textbook
+# chord-and-tangent law over Fq and Fq2 = Fq[u]/(u^2 + 5).
+def _f2mul(a, b):
+    return ((a[0] * b[0] - 5 * a[1] * b[1]) % Q_MOD, (a[0] * b[1] + a[1] * b[0]) % Q_MOD)
+
+
+def _f2inv(a):
+    ni = pow((a[0] * a[0] + 5 * a[1] * a[1]) % Q_MOD, -1, Q_MOD)
+    return (a[0] * ni % Q_MOD, -a[1] * ni % Q_MOD)
+
+
+class _Fq:
+    mul = staticmethod(lambda a, b: a * b % Q_MOD)
+    sub = staticmethod(lambda a, b: (a - b) % Q_MOD)
+    inv = staticmethod(lambda a: pow(a, -1, Q_MOD))
+    k = staticmethod(lambda a, k: a * k % Q_MOD)
+    zero = 0
+
+
+class _Fq2:
+    mul = staticmethod(_f2mul)
+    sub = staticmethod(lambda a, b: ((a[0] - b[0]) % Q_MOD, (a[1] - b[1]) % Q_MOD))
+    inv = staticmethod(_f2inv)
+    k = staticmethod(lambda a, k: (a[0] * k % Q_MOD, a[1] * k % Q_MOD))
+    zero = (0, 0)
+
+
+def _ec_add(P, Q, F):
+    if P is None or Q is None:
+        return Q if P is None else P
+    (x1, y1), (x2, y2) = P, Q
+    if x1 == x2:
+        if y1 != y2 or y1 == F.zero:
+            return None
+        lam = F.mul(F.k(F.mul(x1, x1), 3), F.inv(F.k(y1, 2)))
+    else:
+        lam = F.mul(F.sub(y2, y1), F.inv(F.sub(x2, x1)))
+    x3 = F.sub(F.sub(F.mul(lam, lam), x1), x2)
+    return (x3, F.sub(F.mul(lam, F.sub(x1, x3)), y1))
+
+
+def _ec_mul(P, k, F):
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = _ec_add(acc, acc, F)
+        if bit == "1":
+            acc = _ec_add(acc, P, F)
+    return acc
+
+
+def subgroup_consts():
+    """BETA2: phi(x, y) = (beta x, y) is lambda = x^2 - 1 on G1 (lambda^2 + lambda + 1 = r), so [x]([x] P) = P + phi(P) = -phi^2(P) =
+    (beta^2 x, -y) exactly on the subgroup.  PSI_CX, PSI_CY: psi(x, y) = (conj(x) u^((q-1)/3), conj(y) u^((q-1)/2)) is the twist's
+    untwist-Frobenius-twist map, [x] on G2; both coefficients lie in Fq (u^2 = -5 and 12 divides q - 1)."""
+    import math
+    lam = BLS_X * BLS_X - 1
+    assert lam * lam + lam + 1 == R_MOD
+    g1 = (G1X, G1Y)
+    w = next(pow(g, (Q_MOD - 1) // 3, Q_MOD) for g in range(2, 50) if pow(g, (Q_MOD - 1) // 3, Q_MOD) != 1)
+    lam_g1 = _ec_mul(g1, lam, _Fq)
+    beta = next(b for b in (w, w * w % Q_MOD) if (b * G1X % Q_MOD, G1Y) == lam_g1)      # the beta of hostfield64.hpp::GLV_BETA
+    beta2 = beta * beta % Q_MOD
+    assert (beta2 * beta) % Q_MOD == 1 and beta2 != 1
+    assert _ec_mul(_ec_mul(g1, BLS_X, _Fq), BLS_X, _Fq) == (beta2 * G1X % Q_MOD, Q_MOD - G1Y)
+    assert (Q_MOD - 1) % 12 == 0
+    cx, cy = pow(Q_MOD - 5, (Q_MOD - 1) // 6, Q_MOD), pow(Q_MOD - 5, (Q_MOD - 1) // 4, Q_MOD)
+    g2 = ((G2X0, G2X1), (G2Y0, G2Y1))
+    psi_g2 = ((G2X0 * cx % Q_MOD, -G2X1 * cx % Q_MOD), (G2Y0 * cy % Q_MOD, -G2Y1 * cy % Q_MOD))
+    assert _ec_mul(g2, BLS_X, _Fq2) == psi_g2
+    # psi^2 - t psi + q = 0 (t = x + 1): psi(Q) = x Q gives (q - x) Q = h1 r Q = O with h1 = (x - 1)^2 / 3, and the order of Q divides
+    # #E'(Fq2) = h2 r; gcd(h1, h2) = 1 leaves r Q = O.  #E'(Fq2): the sextic twist of E(Fq2) whose order r divides.
+    h1 = (BLS_X - 1) ** 2 // 3
+    assert Q_MOD - BLS_X == h1 * R_MOD
+    t2 = (BLS_X + 1) ** 2 - 2 * Q_MOD
+    f2 = math.isqrt((4 * Q_MOD * Q_MOD - t2 * t2) // 3)
+    assert 3 * f2 * f2 == 4 * Q_MOD * Q_MOD - t2 * t2
+    orders = [n for n in (Q_MOD * Q_MOD + 1 - (t2 + 3 * f2) // 2, Q_MOD * Q_MOD + 1 - (t2 - 3 * f2) // 2) if n % R_MOD == 0]
+    assert len(orders) == 1 and _ec_mul(g2, orders[0], _Fq2) is None
+    assert math.gcd(h1, orders[0] // R_MOD) == 1
+    return [("BETA2", beta2), ("PSI_CX", cx), ("PSI_CY", cy)]
+
+
 def main():
     two_adic_root = pow(FR_GENERATOR, (R_MOD - 1) >> FR_TWO_ADICITY, R_MOD)
     print("// GENERATED by gen_consts.py -- do not edit.  29-bit little-endian limbs.")
@@ -175,7 +258,7 @@ def main():
         ("G2_B_C1", (-pow(5, -1, Q_MOD)) % Q_MOD),        # curves/g2.rs:28-35 (b' = 1/u)
         ("TS_ROOT", pow(FQ_QNR, (Q_MOD - 1) >> FQ_TWO_ADICITY, Q_MOD)),   # a primitive 2^46-th root of unity (QNR^T)
         ("INV2", (Q_MOD + 1) // 2),
-    ], raw=[
+    ] + subgroup_consts(), raw=[
         ("HALF", (Q_MOD - 1) // 2),                       # y > -y  <=>  canonical(y) > (q - 1) / 2
         ("TS_T_MINUS1_DIV2", (((Q_MOD - 1) >> FQ_TWO_ADICITY) - 1) // 2),   # Tonelli-Shanks exponent (plain bits)
     ]))

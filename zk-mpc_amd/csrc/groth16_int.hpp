@@ -54,6 +54,7 @@ struct zk_pk {
     zk::Affine<zk::G1Field> l_eval_0;
     // every point is a multiple of the generators (zk_groth16_setup): the proof tail may use the endomorphism (hostfield64.hpp:
     // host64_scalar_mul_glv); a deserialised key is not checked for subgroup membership and keeps the plain scalar multiplication
+    // (zk_pk_check_subgroups reports on a loaded key; it does not switch the key's proofs to another path)
     bool points_in_subgroup = false;
     // shifted copies of the window multiples its tables were asked to carry (zk_mul_levels_for_key; zk_bases::pre_levels is what each got)
     uint32_t mul_levels = 0;
@@ -225,6 +226,23 @@ class ZkProofTail {
     void join();
     void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192], const zk::Affine<zk::G1Field>* l_const = nullptr);
 };
+
+// ---- the ABI's affine structs (x | y in the reference's Montgomery words) as host-field points; a coordinate word is valid below q ----
+inline zk::Affine<zk::Fq64Field> zk_host_g1(const zk_g1_affine* p) {
+    uint32_t w[24];
+    memcpy(w, p, 96);
+    return zk::Affine<zk::Fq64Field>{zk::Fq64Field::load(w), zk::Fq64Field::load(w + 12)};
+}
+inline zk::Affine<zk::Fq264Field> zk_host_g2(const zk_g2_affine* p) {
+    uint32_t w[48];
+    memcpy(w, p, 192);
+    return zk::Affine<zk::Fq264Field>{zk::Fq264Field::load(w), zk::Fq264Field::load(w + 24)};
+}
+inline bool zk_words_below_q(const uint64_t* l, int n_fq) {
+    for (int i = 0; i < n_fq; i++)
+        if (zk::host64::cmp(l + 6 * i, zk::host64::P) >= 0) return false;
+    return true;
+}
 
 namespace zk {
 template <class F>

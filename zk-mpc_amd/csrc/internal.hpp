@@ -263,11 +263,18 @@ struct ZkEarlyMsm;
 int zk_msm_early_begin(zk_ctx* ctx, int count, const zk_bases* bases, const size_t* base_offsets, const void* scalars_dev, size_t len, ZkEarlyMsm** out);
 int zk_msm_early_finish(zk_ctx* ctx, ZkEarlyMsm* em, void* const* outs);      // outs = NULL: abandon (waits for its kernels); deletes the handle
 
-// serialize.hip: GroupAffine::deserialize of n compressed points that are on the device already (no subgroup check), table form out;
+// serialize.hip: GroupAffine::deserialize of n compressed points that are on the device already (no subgroup check: zk_subgroup_launch), table form out;
 // bad_dev: one word, set if any x is off the curve; bad_each_dev (or NULL): one word per point.  And one point on the host.
 int zk_decompress_launch(zk_ctx* ctx, int group, const uint32_t* in_dev, size_t n, uint32_t* out_dev, uint32_t* bad_dev, uint32_t* bad_each_dev);
 bool zk_host_decompress_g1(const uint8_t in[48], zk::Affine<zk::G1Field>* out);
 bool zk_host_decompress_g2(const uint8_t in[96], zk::Affine<zk::G2Field>* out);
+
+// subgroup.hip: subgroup membership (subgroup.cuh: r P == O through the endomorphisms) of n points that are on the device already, table
+// form, one point per lane.  bad_dev: one word, ORed with 1 if any point is outside; bad_each_dev (or NULL): one word per point, 1 =
+// outside -- written, or with or_each ORed into what the word holds (the verifier's off-curve flags).  On ctx->stream, no wait.
+int zk_subgroup_launch(zk_ctx* ctx, int group, const uint32_t* table_dev, size_t n, uint32_t* bad_dev, uint32_t* bad_each_dev, bool or_each = false);
+bool zk_host_in_subgroup_g1(const zk::Affine<zk::G1Field>& p);      // ... and one point on the host (64-bit limbs)
+bool zk_host_in_subgroup_g2(const zk::Affine<zk::G2Field>& p);
 
 // pairing.hip: its Miller-loop and finish kernels for pairs that are on the device already (table form); lanes in one launch at most
 constexpr size_t ZK_PAIRING_MAX_LANES = (size_t)1 << 22;

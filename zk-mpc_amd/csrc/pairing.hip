@@ -127,16 +127,6 @@ inline unsigned blocks64(size_t n) { return (unsigned)((n + 63) / 64); }
 constexpr size_t PAIRING_MAX_LANES = ZK_PAIRING_MAX_LANES;
 
 // ---- host forms ----------------------------------------------------------------------------------------------------------------------
-Affine<Fq64Field> host_g1(const zk_g1_affine* p) {
-    uint32_t w[24];
-    memcpy(w, p, 96);
-    return Affine<Fq64Field>{Fq64Field::load(w), Fq64Field::load(w + 12)};
-}
-Affine<H2> host_g2(const zk_g2_affine* p) {
-    uint32_t w[48];
-    memcpy(w, p, 192);
-    return Affine<H2>{H2::load(w), H2::load(w + 24)};
-}
 Fq12<H2> host_gt(const zk_gt* g) {
     uint32_t w[GTW];
     memcpy(w, g, sizeof w);
@@ -146,11 +136,6 @@ void host_gt_out(zk_gt* g, const Fq12<H2>& f) {
     uint32_t w[GTW];
     fq12_to_ext<H2>(w, f);
     memcpy(g, w, sizeof w);
-}
-bool words_below_q(const uint64_t* l, int n_fq) {
-    for (int i = 0; i < n_fq; i++)
-        if (host64::cmp(l + 6 * i, host64::P) >= 0) return false;
-    return true;
 }
 
 // Groth16::verify on host values: e(A, B) e(prepared, -gamma) e(C, -delta) == e(alpha, beta)
@@ -204,9 +189,9 @@ extern "C" int zk_pairing_products_host(const zk_g1_affine* p, const zk_g2_affin
     std::vector<Affine<H2>> Q(pairs);
     for (size_t k = 0; k < count; k++) {
         for (size_t j = 0; j < pairs; j++) {
-            if (!words_below_q((const uint64_t*)&p[k * pairs + j], 2) || !words_below_q((const uint64_t*)&q[k * pairs + j], 4)) return ZK_ERR_ARG;
-            P[j] = host_g1(&p[k * pairs + j]);
-            Q[j] = host_g2(&q[k * pairs + j]);
+            if (!zk_words_below_q((const uint64_t*)&p[k * pairs + j], 2) || !zk_words_below_q((const uint64_t*)&q[k * pairs + j], 4)) return ZK_ERR_ARG;
+            P[j] = zk_host_g1(&p[k * pairs + j]);
+            Q[j] = zk_host_g2(&q[k * pairs + j]);
         }
         Fq12<H2> r;
         pairing_product<H2>(r, P.data(), Q.data(), pairs);
@@ -253,7 +238,7 @@ extern "C" int zk_gt_eq(const zk_gt* a, const zk_gt* b) {
 }
 extern "C" int zk_gt_mul(const zk_gt* a, const zk_gt* b, zk_gt* out) {
     ZK_API_BEGIN_NOCTX
-    if (!a || !b || !out || !words_below_q((const uint64_t*)a, 12) || !words_below_q((const uint64_t*)b, 12)) return ZK_ERR_ARG;
+    if (!a || !b || !out || !zk_words_below_q((const uint64_t*)a, 12) || !zk_words_below_q((const uint64_t*)b, 12)) return ZK_ERR_ARG;
     Fq12<H2> r;
     fq12_mul<H2>(r, host_gt(a), host_gt(b));
     host_gt_out(out, r);
@@ -261,42 +246,44 @@ extern "C" int zk_gt_mul(const zk_gt* a, const zk_gt* b, zk_gt* out) {
     ZK_API_END
 }
 
-extern "C" int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
-    ZK_API_BEGIN_NOCTX
+namespace {
+// check_subgroup: A, B, C also pass the subgroup test of Proof::deserialize (subgroup.cuh, host instantiation)
+int verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok, bool check_subgroup) {
     if (!vk || !proof || !ok || !vk->gamma_abc_g1 || vk->gamma_abc_len != n_inputs + 1 || (n_inputs && !inputs)) return ZK_ERR_ARG;
-    if (!words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
-        !words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !words_below_q((const uint64_t*)&vk->delta_g2, 4))
+    if (!zk_words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !zk_words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
+        !zk_words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !zk_words_below_q((const uint64_t*)&vk->delta_g2, 4))
         return ZK_ERR_ARG;
     for (size_t i = 0; i <= n_inputs; i++)
-        if (!words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return ZK_ERR_ARG;
+        if (!zk_words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return ZK_ERR_ARG;
     for (size_t i = 0; i < n_inputs; i++)
         if (!zk_fr_words_valid(inputs[i].l)) return ZK_ERR_ARG;
     *ok = 0;
     Affine<G1Field> a, c;
     Affine<G2Field> b;
     if (!zk_host_decompress_g1(proof, &a) || !zk_host_decompress_g2(proof + 48, &b) || !zk_host_decompress_g1(proof + 144, &c)) return ZK_OK;
+    if (check_subgroup && !(zk_host_in_subgroup_g1(a) && zk_host_in_subgroup_g2(b) && zk_host_in_subgroup_g1(c))) return ZK_OK;
     // prepare_inputs (verifier.rs:18-33)
-    XYZZ<Fq64Field> acc = xyzz_from_affine<Fq64Field>(host_g1(&vk->gamma_abc_g1[0]));
+    XYZZ<Fq64Field> acc = xyzz_from_affine<Fq64Field>(zk_host_g1(&vk->gamma_abc_g1[0]));
     for (size_t i = 0; i < n_inputs; i++) {
         uint32_t kw[8];
         fr_abi_to_canon_words(inputs[i].l, kw);
-        acc = xyzz_add<Fq64Field>(acc, host64_scalar_mul<Fq64Field>(xyzz_from_affine<Fq64Field>(host_g1(&vk->gamma_abc_g1[i + 1])), kw));
+        acc = xyzz_add<Fq64Field>(acc, host64_scalar_mul<Fq64Field>(xyzz_from_affine<Fq64Field>(zk_host_g1(&vk->gamma_abc_g1[i + 1])), kw));
     }
     const Affine<Fq64Field> P[3] = {aff_to_host64<G1Field>(a), xyzz_to_affine<Fq64Field>(acc), aff_to_host64<G1Field>(c)};
-    const Affine<H2> Q[3] = {aff_to_host64<G2Field>(b), aff_neg<H2>(host_g2(&vk->gamma_g2)), aff_neg<H2>(host_g2(&vk->delta_g2))};
+    const Affine<H2> Q[3] = {aff_to_host64<G2Field>(b), aff_neg<H2>(zk_host_g2(&vk->gamma_g2)), aff_neg<H2>(zk_host_g2(&vk->delta_g2))};
     Fq12<H2> lhs, rhs;
     pairing_product<H2>(lhs, P, Q, 3);
-    const Affine<Fq64Field> alpha = host_g1(&vk->alpha_g1);
-    const Affine<H2> beta = host_g2(&vk->beta_g2);
+    const Affine<Fq64Field> alpha = zk_host_g1(&vk->alpha_g1);
+    const Affine<H2> beta = zk_host_g2(&vk->beta_g2);
     pairing_product<H2>(rhs, &alpha, &beta, 1);
     *ok = fq12_eq<H2>(lhs, rhs) ? 1 : 0;
     return ZK_OK;
-    ZK_API_END
 }
 
-extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                       const uint8_t* proofs_host, int* ok) {
-    ZK_API_BEGIN(ctx)
+// check_subgroup: behind the decompression one launch over the 2 count G1 points and one over the count G2 points OR "outside the
+// subgroup" into the off-curve flags, which k_verify_prepare folds into the proof's verdict
+int verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof, const uint8_t* proofs_host, int* ok,
+                 bool check_subgroup) {
     if (!ctx || !pk || !count || !proofs_host || !ok || count > PAIRING_MAX_LANES / 3) return ZK_ERR_ARG;
     if (!pk->gamma_abc || pk->gamma_abc->n == 0 || aff_is_inf<G2Field>(pk->gamma_g2))
         ZK_FAIL(ctx, ZK_ERR_ARG, "zk_groth16_verify_batch: the key has no verifying-key parts (gamma_g2, gamma_abc_g1)");
@@ -344,6 +331,10 @@ extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t coun
     ZK_HIP(ctx, hipMemsetAsync(bad_any, 0, 4, st));
     ZK_TRY(zk_decompress_launch(ctx, 1, (const uint32_t*)d_g1c, 2 * count, ac, bad_any, bad_ac));
     ZK_TRY(zk_decompress_launch(ctx, 2, (const uint32_t*)d_g2c, count, b, bad_any, bad_b));
+    if (check_subgroup) {
+        ZK_TRY(zk_subgroup_launch(ctx, 1, ac, 2 * count, bad_any, bad_ac, true));
+        ZK_TRY(zk_subgroup_launch(ctx, 2, b, count, bad_any, bad_b, true));
+    }
     hipLaunchKernelGGL(k_verify_prepare, blocks64(count), 64, 0, st, count, ninp, (const uint32_t*)d_in, (const uint32_t*)pk->gamma_abc->dev,
                        (const uint32_t*)ac, (const uint32_t*)b, (const uint32_t*)d_cs, (const uint32_t*)bad_ac, (const uint32_t*)bad_b, P, Q, bad);
     ZK_HIP(ctx, hipGetLastError());
@@ -355,13 +346,36 @@ extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t coun
     ZK_HIP(ctx, hipMemcpyAsync(ok, d_ok, count * sizeof(int), hipMemcpyDeviceToHost, st));
     ZK_HIP(ctx, hipStreamSynchronize(st));
     return ZK_OK;
+}
+}  // namespace
+
+extern "C" int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
+    ZK_API_BEGIN_NOCTX
+    return verify_host(vk, inputs, n_inputs, proof, ok, false);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
+    ZK_API_BEGIN_NOCTX
+    return verify_host(vk, inputs, n_inputs, proof, ok, true);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                       const uint8_t* proofs_host, int* ok) {
+    ZK_API_BEGIN(ctx)
+    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, false);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_batch_checked(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                               const uint8_t* proofs_host, int* ok) {
+    ZK_API_BEGIN(ctx)
+    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, true);
     ZK_API_END
 }
 
 extern "C" int zk_diag_fq12_host(int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases) {
     ZK_API_BEGIN_NOCTX
     if (!in_pairs || !out || op < 0 || op > 7 || n_cases < 1 || n_cases > ((size_t)1 << 20)) return ZK_ERR_ARG;
-    if (!words_below_q((const uint64_t*)in_pairs, (int)(24 * n_cases))) return ZK_ERR_ARG;
+    if (!zk_words_below_q((const uint64_t*)in_pairs, (int)(24 * n_cases))) return ZK_ERR_ARG;
     for (size_t i = 0; i < n_cases; i++) {
         uint32_t in[2 * GTW], o[GTW];
         memcpy(in, &in_pairs[2 * i], sizeof in);
@@ -374,7 +388,7 @@ extern "C" int zk_diag_fq12_host(int op, const zk_gt* in_pairs, zk_gt* out, size
 extern "C" int zk_diag_fq12_dev(zk_ctx* ctx, int op, const zk_gt* in_pairs, zk_gt* out, size_t n_cases) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !in_pairs || !out || op < 0 || op > 7 || n_cases < 1 || n_cases > ((size_t)1 << 20)) return ZK_ERR_ARG;
-    if (!words_below_q((const uint64_t*)in_pairs, (int)(24 * n_cases))) return ZK_ERR_ARG;
+    if (!zk_words_below_q((const uint64_t*)in_pairs, (int)(24 * n_cases))) return ZK_ERR_ARG;
     uint32_t *din, *dout;
     ZK_TRY(zk_scratch(ctx, "diag_fq12_in", n_cases * 2 * GTW * 4, (void**)&din));
     ZK_TRY(zk_scratch(ctx, "diag_fq12_out", n_cases * GTW * 4, (void**)&dout));

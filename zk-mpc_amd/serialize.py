@@ -36,13 +36,16 @@ def proving_key_bytes(ctx: Context, pk: ProvingKey, compressed: bool = True) -> 
     return bytes(out)
 
 
-def proving_key_from_bytes(ctx: Context, data: bytes, compressed: bool = False):
+def proving_key_from_bytes(ctx: Context, data: bytes, compressed: bool = False, check_subgroup: bool = False):
     """ProvingKey::deserialize (compressed: one square root per point on the device) or deserialize_uncompressed through
     zk_pk_deserialize: the tables go straight to the device and the key is resident like one from zk_pk_upload.
-    Returns (ProvingKey, gamma_g2, gamma_abc_g1): the prover does not use the last two, the verifier does."""
+    Returns (ProvingKey, gamma_g2, gamma_abc_g1): the prover does not use the last two, the verifier does.
+    check_subgroup: the reference's deserialize in full (zk_pk_deserialize_checked) -- a key with a point outside the prime-order
+    subgroups raises ZkError; the default is deserialize_unchecked plus the curve equation."""
     import ctypes as C
     h = C.c_void_p()
-    ctx._ck(ctx.lib.zk_pk_deserialize(ctx.h, data, len(data), int(compressed), C.byref(h)))
+    fn = ctx.lib.zk_pk_deserialize_checked if check_subgroup else ctx.lib.zk_pk_deserialize
+    ctx._ck(fn(ctx.h, data, len(data), int(compressed), C.byref(h)))
     pk = ProvingKey(ctx, h)
     return pk, pk.vk_g2(2), pk.download("gamma_abc_g1")
 
@@ -58,10 +61,12 @@ def kzg_srs_bytes(ctx: Context, powers_g: Bases, powers_gamma_g: Bases, h24, bet
     return bytes(out)
 
 
-def kzg_srs_from_bytes(ctx: Context, data: bytes, compressed: bool = True):
-    """-> (powers_g Bases, powers_gamma_g Bases, h (24,) uint64, beta_h (24,) uint64)."""
+def kzg_srs_from_bytes(ctx: Context, data: bytes, compressed: bool = True, check_subgroup: bool = False):
+    """-> (powers_g Bases, powers_gamma_g Bases, h (24,) uint64, beta_h (24,) uint64).  check_subgroup: both tables, h and beta_h
+    also pass the subgroup test (zk_kzg_srs_deserialize_checked)."""
     import ctypes as C
     pg, pgg = C.c_void_p(), C.c_void_p()
     h, bh = np.zeros(24, dtype=np.uint64), np.zeros(24, dtype=np.uint64)
-    ctx._ck(ctx.lib.zk_kzg_srs_deserialize(ctx.h, data, len(data), int(compressed), C.byref(pg), C.byref(pgg), h.ctypes.data, bh.ctypes.data))
+    fn = ctx.lib.zk_kzg_srs_deserialize_checked if check_subgroup else ctx.lib.zk_kzg_srs_deserialize
+    ctx._ck(fn(ctx.h, data, len(data), int(compressed), C.byref(pg), C.byref(pgg), h.ctypes.data, bh.ctypes.data))
     return Bases(ctx, pg, 1), Bases(ctx, pgg, 1), h, bh
