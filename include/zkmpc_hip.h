@@ -623,9 +623,15 @@ int zk_marlin_prove(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* p
  * An Encodedtext of degree N is N consecutive elements; a Ciphertext is c0 | c1 | c2 (3N elements,
  * src/she/ciphertext.rs:10-14); batches are contiguous.  N may be any value in 1..2^14: powers of two >= 4 use the
  * negacyclic NTT, everything else an O(N^2) kernel; results are identical to the reference's
- * DensePolynomial::mul + poly_remainder2 by X^N + 1. */
+ * DensePolynomial::mul + poly_remainder2 by X^N + 1.
+ * Aliasing.  The two element-wise calls (zk_she_vec_op_dev, zk_she_vec_scale_dev) may work in place: out_dev may be a_dev or
+ * b_dev.  The four ring calls (zk_she_negacyclic_mul_dev, zk_she_ciphertext_mul_dev, zk_she_encrypt_dev, zk_she_decrypt_dev)
+ * may not: they read whole polynomials of their inputs while they write the output, so a call whose output range (all `batch`
+ * results) overlaps the range of any device input, wholly or in part, is refused with ZK_ERR_ARG and a zk_last_error that names
+ * the call and the input; nothing is written.  This holds for every N, whichever path N selects.  Inputs may overlap each other
+ * (x_dev == y_dev squares a ciphertext). */
 typedef struct { uint64_t l[12]; } zk_fq753;
-/* Texts<Fq> add / sub / neg (src/she/texts.rs:43-127); ZK_OP_MUL is the coefficient-wise product. */
+/* Texts<Fq> add / sub / neg (src/she/texts.rs:43-127); ZK_OP_MUL is the coefficient-wise product.  In place allowed. */
 int zk_she_vec_op_dev(zk_ctx* ctx, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n);
 /* Encodedtext * Fq, Encodedtext * BigUint (src/she/encodedtext.rs:93-113). */
 int zk_she_vec_scale_dev(zk_ctx* ctx, const void* a_dev, const zk_fq753* k, void* out_dev, size_t n);

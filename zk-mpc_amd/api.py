@@ -563,24 +563,30 @@ class Context:
         return f
 
     def she_vec_op_dev(self, op: int, a, b, out, n: int):
+        """Element-wise on n Fq753 elements; `out` may be `a` or `b` (in place)."""
         self._ck(self.lib.zk_she_vec_op_dev(self.h, op, C.c_void_p(int(a)), C.c_void_p(int(b)) if b else None, C.c_void_p(int(out)), n))
 
     def she_vec_scale_dev(self, a, k12, out, n: int):
+        """Element-wise; `out` may be `a` (in place)."""
         k = self._fq753_struct(k12)
         self._ck(self.lib.zk_she_vec_scale_dev(self.h, C.c_void_p(int(a)), C.byref(k), C.c_void_p(int(out)), n))
 
     def encodedtext_mul_dev(self, a, b, out, n: int, batch: int = 1):
+        """a * b in F_q[X] / (X^n + 1), `batch` rows.  Not in place: raises ZkError when the range of `out` overlaps `a` or `b`."""
         self._ck(self.lib.zk_she_negacyclic_mul_dev(self.h, C.c_void_p(int(a)), C.c_void_p(int(b)), C.c_void_p(int(out)), n, batch))
 
     def ciphertext_mul_dev(self, x, y, out, n: int, batch: int = 1):
+        """Ciphertext product (c0 | c1 | c2 per ciphertext).  Not in place: raises ZkError when the range of `out` overlaps `x` or `y`."""
         self._ck(self.lib.zk_she_ciphertext_mul_dev(self.h, C.c_void_p(int(x)), C.c_void_p(int(y)), C.c_void_p(int(out)), n, batch))
 
     def ciphertext_encrypt_from_dev(self, e, pk_a, pk_b, r, p12, out, n: int, batch: int = 1):
+        """Not in place: raises ZkError when the range of `out` overlaps `e`, `pk_a`, `pk_b` or `r`."""
         p = self._fq753_struct(p12)
         self._ck(self.lib.zk_she_encrypt_dev(self.h, C.c_void_p(int(e)), C.c_void_p(int(pk_a)), C.c_void_p(int(pk_b)),
                                              C.c_void_p(int(r)), C.byref(p), C.c_void_p(int(out)), n, batch))
 
     def ciphertext_decrypt_dev(self, ct, sk, out, n: int, batch: int = 1):
+        """c0 - s c1 - s s c2.  Not in place: raises ZkError when the range of `out` overlaps `ct` or `sk`."""
         self._ck(self.lib.zk_she_decrypt_dev(self.h, C.c_void_p(int(ct)), C.c_void_p(int(sk)), C.c_void_p(int(out)), n, batch))
 
     def plaintexts_encode_dev(self, plain_fr, out, n: int, batch: int = 1):

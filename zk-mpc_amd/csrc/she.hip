@@ -27,6 +27,8 @@
 #include "devutil.cuh"
 #include "internal.hpp"
 
+#include <initializer_list>
+
 using namespace zk;
 
 namespace {
@@ -583,6 +585,23 @@ int check_n(zk_ctx* ctx, size_t n, const char* who) {
     return ZK_OK;
 }
 
+// The ring entry points read whole polynomials of their inputs while they write their output (the schoolbook kernel, the
+// three launches of a ciphertext product, the 3N-strided reads of the tails), so an output range that overlaps an input range
+// is refused for every N, whichever path N selects.  Ranges in elements of 96 bytes.
+struct ElemRange { const void* p; size_t elems; const char* name; };
+
+int check_no_overlap(zk_ctx* ctx, const char* who, const void* out, size_t out_elems, std::initializer_list<ElemRange> inputs) {
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + out_elems * 96;
+    for (const ElemRange& in : inputs) {
+        const uintptr_t i0 = (uintptr_t)in.p, i1 = i0 + in.elems * 96;
+        if (o0 < i1 && i0 < o1) {
+            ctx->last_error = std::string(who) + ": the output range overlaps the input " + in.name + " (the ring operations do not work in place)";
+            return ZK_ERR_ARG;
+        }
+    }
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" int zk_she_vec_op_dev(zk_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n) {
@@ -613,6 +632,7 @@ extern "C" int zk_she_negacyclic_mul_dev(zk_ctx* ctx, const void* a, const void*
     if (!ctx || (batch && (!a || !b || !out))) return ZK_ERR_ARG;
     ZK_TRY(check_n(ctx, n, "zk_she_negacyclic_mul_dev"));
     if (batch == 0) return ZK_OK;
+    ZK_TRY(check_no_overlap(ctx, "zk_she_negacyclic_mul_dev", out, batch * n, {{a, batch * n, "a"}, {b, batch * n, "b"}}));
     if (!ntt_path(n))
         return she_schoolbook(ctx, rows_of(a, 1, n), rows_of(b, 1, n), NO_ROWS, NO_ROWS, rows_of(out, 1, n), 0, (uint32_t)n, batch);
     uint32_t log_n = ilog2(n);
@@ -633,6 +653,7 @@ extern "C" int zk_she_ciphertext_mul_dev(zk_ctx* ctx, const void* x, const void*
     if (!ctx || (batch && (!x || !y || !out))) return ZK_ERR_ARG;
     ZK_TRY(check_n(ctx, n, "zk_she_ciphertext_mul_dev"));
     if (batch == 0) return ZK_OK;
+    ZK_TRY(check_no_overlap(ctx, "zk_she_ciphertext_mul_dev", out, batch * 3 * n, {{x, batch * 3 * n, "x"}, {y, batch * 3 * n, "y"}}));
     const char* xb = (const char*)x;
     const char* yb = (const char*)y;
     char* ob = (char*)out;
@@ -668,6 +689,8 @@ extern "C" int zk_she_encrypt_dev(zk_ctx* ctx, const void* e, const void* pk_a, 
     if (!ctx || !p || (batch && (!e || !pk_a || !pk_b || !r || !out))) return ZK_ERR_ARG;
     ZK_TRY(check_n(ctx, n, "zk_she_encrypt_dev"));
     if (batch == 0) return ZK_OK;
+    ZK_TRY(check_no_overlap(ctx, "zk_she_encrypt_dev", out, batch * 3 * n,
+                            {{e, batch * n, "e"}, {pk_a, n, "pk_a"}, {pk_b, n, "pk_b"}, {r, batch * 3 * n, "r"}}));
     const char* rb = (const char*)r;
     char* ob = (char*)out;
     size_t poly = n * 96;
@@ -703,6 +726,7 @@ extern "C" int zk_she_decrypt_dev(zk_ctx* ctx, const void* ct, const void* sk, v
     if (!ctx || (batch && (!ct || !sk || !out))) return ZK_ERR_ARG;
     ZK_TRY(check_n(ctx, n, "zk_she_decrypt_dev"));
     if (batch == 0) return ZK_OK;
+    ZK_TRY(check_no_overlap(ctx, "zk_she_decrypt_dev", out, batch * n, {{ct, batch * 3 * n, "ct"}, {sk, n, "sk"}}));
     const char* cb = (const char*)ct;
     size_t poly = n * 96;
     char* t;   // s*c1 + s*s*c2, packed rows
