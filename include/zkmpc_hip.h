@@ -590,8 +590,8 @@ int zk_marlin_round3_ab_evals_dev(zk_ctx* ctx, const zk_marlin_matrix_evals on_b
 /* Marlin::prove (arkworks/marlin/src/lib.rs:152-319) as one call: the three AHP rounds, MarlinKZG10 commitments (hiding bound 1 on
  * w, z_a, z_b, g_1; degree bounds |H| - 2 on g_1 and |K| - 2 on g_2 through the shifted powers), the Fiat-Shamir transcript
  * (FiatShamirRng<Blake2s> over the bytes to_bytes! writes), the evaluations and open_combinations, on an index the caller built
- * once (Marlin::index is set-up: zk-mpc_amd/marlin.py::Index / IndexKeys do it with the calls above) and hands over as
- * device-resident tables:
+ * once (Marlin::index is set-up: zk_marlin_index_build below makes it and zk_marlin_ix_view hands it over; a caller may also fill
+ * the struct itself) as device-resident tables:
  *   index_polys     a_row a_col a_val a_row_col b_... c_... (ahp/mod.rs:33-40): coefficient vectors
  *   on_k / on_b     evaluations of row / col / val (/ row_col) of A*, B*, C* on K and on the domain B of size >= 3|K| - 3
  *   r1cs / r1cs_t   the balanced, padded matrices (z_A, z_B) and their transposes with rows re-indexed into H (calculate_t)
@@ -617,6 +617,46 @@ typedef struct {
 size_t zk_marlin_proof_max_size(void);
 int zk_marlin_prove(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
                     const void* z_dev, zk_rng* zk_rng, int mask_on_device, uint8_t* proof_out, size_t cap, size_t* proof_len);
+
+/* Marlin::index (arkworks/marlin/src/lib.rs:101-146 over AHPForR1CS::index, ahp/indexer.rs:121-208 and ahp/constraint_systems.rs:23-264)
+ * as one call, for matrices as to_matrices() gives them -- the zk_r1cs_host of zk_r1cs_upload, neither padded nor square:
+ *   shape       on the host: the instance padded with zeros to a power of two (witness columns move up), the system made square (empty
+ *               rows, or trailing witnesses of value one), balance_matrices, every row in ascending column order (stable), the three
+ *               transposes with rows re-indexed into H; num_non_zero = the largest of the three entry counts
+ *   arithmetise one launch over 3 |K| entries: row = w^reindex(col), col = w^row, val = coeff w^reindex(col) / |H|, row_col = row col
+ *               (an entry past a matrix's last: 1, 1, 0, 1), w^i from the transform's resident table of H
+ *   transforms  twelve inverse transforms on K and twelve forward ones on B (size >= 3 |K| - 3), batched
+ *   commit      the twelve commitments over powers_g as one job list; ivk_bytes = index_info | 12 commitments (24 + 12 x 195 bytes)
+ * The handle owns every device buffer, both zk_r1cs and the ivk bytes; zk_marlin_ix_view is the zk_marlin_index the provers take,
+ * valid until zk_marlin_ix_free.  ZK_ERR_ARG, with nothing left allocated: a null pointer, a row_ptr that decreases or does not start
+ * at 0, a column that is not below num_instance + num_witness, num_instance = 0, powers_g shorter than max_degree_needed + 1
+ * (AHPForR1CS::max_degree; the reference's IndexTooLarge), a balanced matrix with more than |K| entries (num_non_zero is taken
+ * before balancing, which may leave B with more than A had: the reference's arithmetisation has no room for that either). */
+typedef struct zk_marlin_ix zk_marlin_ix;
+typedef struct {
+    size_t num_instance_in, num_witness_in, num_constraints_in;  /* as given */
+    size_t num_instance, num_witness, num_constraints;           /* padded and square: num_instance a power of two */
+    size_t num_non_zero, h_size, k_size, b_size, x_size, max_degree_needed;
+} zk_marlin_ix_info;
+int zk_marlin_index_build(zk_ctx* ctx, const zk_r1cs_host* m, const zk_bases* powers_g, zk_marlin_ix** out);
+int zk_marlin_ix_free(zk_ctx* ctx, zk_marlin_ix* ix);
+const zk_marlin_index* zk_marlin_ix_view(const zk_marlin_ix* ix);
+int zk_marlin_ix_info_get(const zk_marlin_ix* ix, zk_marlin_ix_info* out);
+/* The prover's assignment in the index's layout: z_dev = num_instance_in + num_witness_in elements as the circuit gives them,
+ * z_padded_dev = num_instance + num_witness elements: instance | zeros up to the power of two | witness | ones up to square. */
+int zk_marlin_pad_assignment_dev(zk_ctx* ctx, const zk_marlin_ix* ix, const void* z_dev, void* z_padded_dev);
+/* kzg10::VerifierKey + IndexVerifierKey for zk_marlin_verify_*: g = powers_g[0], gamma_g = powers_gamma_g[0], the shift powers
+ * powers_g[max_degree - (|H| - 2)] and powers_g[max_degree - (|K| - 2)] with max_degree = the table's length - 1; out->ivk_bytes
+ * points into the index (valid until zk_marlin_ix_free).  h, beta_h: the G2 side of the SRS. */
+int zk_marlin_vk_from_index(zk_ctx* ctx, const zk_marlin_ix* ix, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
+                            const zk_g2_affine* h, const zk_g2_affine* beta_h, zk_marlin_vk_host* out);
+/* The shape step alone, on the host (no device, no context; tests): which = 0 .. 2: A, B, C as the index holds them, 3 .. 5: their
+ * transposes over H.  row_ptr: num_constraints + 1 (or |H| + 1) entries, col / coeff: up to cap entries; info (or NULL) is filled
+ * first; a call with row_ptr = NULL fills info alone, which is how a caller sizes row_ptr (balancing moves rows between A and B:
+ * cap = the entries of A and B together, or those of C, always suffices).  ZK_ERR_ARG: what zk_marlin_index_build refuses about
+ * m, which outside 0 .. 5, cap below the matrix's entry count. */
+int zk_diag_marlin_shape_host(const zk_r1cs_host* m, int which, uint32_t* row_ptr, uint32_t* col, zk_fr* coeff, size_t cap,
+                              zk_marlin_ix_info* info);
 
 /* ---- SHE ring arithmetic of the preprocessing phase (row a15) ----
  * Elements are ark_mnt4_753::Fq = Fp768 (12 x u64 little-endian, Montgomery R = 2^768), the `Fq` of src/she.rs:17.

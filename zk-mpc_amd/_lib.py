@@ -42,6 +42,11 @@ class MarlinIndex(C.Structure):
                 ("w_idx", C.c_void_p), ("x_idx", C.c_void_p), ("ivk_bytes", C.c_char_p), ("ivk_len", C.c_size_t)]
 
 
+class MarlinIxInfo(C.Structure):
+    _fields_ = [(n, C.c_size_t) for n in ("num_instance_in", "num_witness_in", "num_constraints_in", "num_instance", "num_witness",
+                                          "num_constraints", "num_non_zero", "h_size", "k_size", "b_size", "x_size", "max_degree_needed")]
+
+
 class Fq753(C.Structure):
     _fields_ = [("l", C.c_uint64 * 12)]
 
@@ -315,6 +320,13 @@ PROTOTYPES = {
     "zk_pk_points_in_subgroup": (_I, [_P]),
     "zk_groth16_verify_batch_checked": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "zk_groth16_verify_host_checked": (_I, [_P, _P, _SZ, _P, _P]),
+    "zk_marlin_index_build": (_I, [_P, _P, _P, C.POINTER(_P)]),
+    "zk_marlin_ix_free": (_I, [_P, _P]),
+    "zk_marlin_ix_view": (_P, [_P]),
+    "zk_marlin_ix_info_get": (_I, [_P, _P]),
+    "zk_marlin_pad_assignment_dev": (_I, [_P, _P, _P, _P]),
+    "zk_marlin_vk_from_index": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "zk_diag_marlin_shape_host": (_I, [_P, _I, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

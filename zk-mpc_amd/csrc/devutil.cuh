@@ -39,6 +39,24 @@ inline FrK to_frk(const uint32_t* l) {
 }
 inline FrK to_frk(const Fr& a) { return to_frk(a.l); }
 
+// ---- tables of field constants (ntt.hip: twiddles, coset scales) ----
+// Table entries (twiddles, coset scales) are kept as their nine 29-bit limbs, 36 B each: a product takes them as they are
+// (re-slicing eight packed words into nine limbs was ~25 instructions in front of every twiddle product).
+struct __attribute__((packed, aligned(4))) Limbs9 { uint32_t l[9]; };
+__device__ __forceinline__ Fr tab_load(const uint32_t* tab, size_t i) {
+    const Limbs9 t = reinterpret_cast<const Limbs9*>(tab)[i];
+    Fr r;
+#pragma unroll
+    for (int k = 0; k < 9; k++) r.l[k] = t.l[k];
+    return r;
+}
+__device__ __forceinline__ void tab_store(uint32_t* tab, size_t i, const Fr& v) {
+    Limbs9 t;
+#pragma unroll
+    for (int k = 0; k < 9; k++) t.l[k] = v.l[k];
+    reinterpret_cast<Limbs9*>(tab)[i] = t;
+}
+
 // ---- packed points (internal form) via 16-byte loads; F::WORDS is a multiple of 4 ----
 template <class F>
 __device__ __forceinline__ typename F::T felt_load16(const uint32_t* w) {

@@ -21,6 +21,9 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs_dev, int count, uint32_t 
 // (2^log_n > 2^10), or NULL for the context's grow-only "ntt_tmp" slot
 int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp = nullptr);
 int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
+// the elements of the domain of size 2^log_n as the transforms keep them resident (w^i for i < 2^log_n: internal form, nine limbs = 36
+// bytes each, devutil.cuh::tab_load) and 1 / 2^log_n in internal form
+int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements_dev, uint32_t size_inv9[9]);
 
 // The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
 enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_COUNT };

@@ -17,6 +17,7 @@
 #include "devutil.cuh"
 #include "hostgroup.hpp"
 #include "internal.hpp"
+#include "marlin_bytes.hpp"
 #include "marlin_lc.hpp"
 #include "sharednet.hpp"
 #include "hostfield64.hpp"
@@ -32,7 +33,6 @@ using namespace zk;
 namespace {
 
 struct Poly { char* p = nullptr; size_t n = 0; };        // n coefficients on the device
-struct Comm { Affine<G1Field> c, s; bool has_shift = false; };
 
 
 // ---- the oracles: the nine the prover sends, in the order their rounds commit (and serialise) them, then the index's twelve ----
@@ -115,49 +115,6 @@ struct Prover {
         return Poly{out, n + 1};
     }
 };
-
-void g1_tobytes(const Affine<G1Field>& a, std::vector<uint8_t>& out) {     // GroupAffine::write: x | y | infinity; zero() = (0, 1, true)
-    uint8_t b[48];
-    if (aff_is_inf<G1Field>(a)) {
-        out.insert(out.end(), 48, 0);
-        out.push_back(1); out.insert(out.end(), 47, 0);
-        out.push_back(1);
-        return;
-    }
-    fq_canonical_bytes(a.x, b); out.insert(out.end(), b, b + 48);
-    fq_canonical_bytes(a.y, b); out.insert(out.end(), b, b + 48);
-    out.push_back(0);
-}
-void comm_tobytes(const Comm& c, std::vector<uint8_t>& out) {              // marlin_pc::Commitment::write
-    g1_tobytes(c.c, out);
-    out.push_back(c.has_shift ? 1 : 0);
-    g1_tobytes(c.has_shift ? c.s : aff_inf<G1Field>(), out);
-}
-// projective -> affine for several points with ONE field inversion (the commitments of a round: 2 - 6 points, an inversion is ~400
-// products) in the 64-bit host field
-std::vector<Affine<G1Field>> batch_to_aff(const std::vector<zk_g1_projective>& pts) {
-    using H = Fq64Field;
-    const size_t n = pts.size();
-    std::vector<XYZZ<H>> x(n);
-    std::vector<typename H::T> pre(n);
-    typename H::T acc = H::one();
-    for (size_t i = 0; i < n; i++) {
-        x[i] = host64_proj_from_abi<H>((const uint64_t*)&pts[i]);
-        if (xyzz_is_inf<H>(x[i])) continue;
-        pre[i] = acc;
-        acc = H::mul(acc, x[i].zzz);
-    }
-    typename H::T inv = H::inv(acc);
-    std::vector<Affine<G1Field>> out(n);
-    for (size_t i = n; i-- > 0;) {
-        if (xyzz_is_inf<H>(x[i])) { out[i] = aff_inf<G1Field>(); continue; }
-        const typename H::T zi3 = H::mul(inv, pre[i]);
-        inv = H::mul(inv, x[i].zzz);
-        const typename H::T zi = H::mul(zi3, x[i].zz), zi2 = H::sqr(zi);
-        out[i] = aff_from_host64<G1Field>(Affine<H>{H::mul(x[i].x, zi2), H::mul(x[i].y, zi3)});
-    }
-    return out;
-}
 
 HF host_eval(const std::vector<HF>& c, const HF& x) {
     HF acc = HF::zero();

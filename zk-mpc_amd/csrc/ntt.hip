@@ -42,23 +42,6 @@ constexpr int NTT_THREADS = 1024;   // (512 / 256 threads per tile, two / four b
 constexpr int TILE_ELEMS = 4096;  // x 36 B = 144 KiB of LDS
 
 
-// Table entries (twiddles, coset scales) are kept as their nine 29-bit limbs, 36 B each: a product takes them as they are
-// (re-slicing eight packed words into nine limbs was ~25 instructions in front of every twiddle product).
-struct __attribute__((packed, aligned(4))) Limbs9 { uint32_t l[9]; };
-__device__ __forceinline__ Fr tab_load(const uint32_t* tab, size_t i) {
-    const Limbs9 t = reinterpret_cast<const Limbs9*>(tab)[i];
-    Fr r;
-#pragma unroll
-    for (int k = 0; k < 9; k++) r.l[k] = t.l[k];
-    return r;
-}
-__device__ __forceinline__ void tab_store(uint32_t* tab, size_t i, const Fr& v) {
-    Limbs9 t;
-#pragma unroll
-    for (int k = 0; k < 9; k++) t.l[k] = v.l[k];
-    reinterpret_cast<Limbs9*>(tab)[i] = t;
-}
-
 // out[i] = start * base^i  (internal form in, limb-form table out)
 __global__ void __launch_bounds__(256) k_powers(uint32_t* out, FrK base_k, FrK start_k, size_t n) {
     constexpr int CH = 32;
@@ -356,6 +339,14 @@ int get_domain(zk_ctx* ctx, uint32_t log_n, bool need_coset, zk_domain** out) {
 }
 
 }  // namespace
+
+int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements, uint32_t size_inv9[9]) {
+    zk_domain* d;
+    ZK_TRY(get_domain(ctx, log_n, false, &d));
+    *elements = d->tw;
+    for (int i = 0; i < 9; i++) size_inv9[i] = d->size_inv.l[i];
+    return ZK_OK;
+}
 
 void zk_domains_free(zk_ctx* ctx) {
     for (auto& kv : ctx->domains) {

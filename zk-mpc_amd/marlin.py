@@ -376,7 +376,10 @@ class IndexKeys:
 
 
 def native_index(keys: IndexKeys):
-    """The index as the C ABI's zk_marlin_index (include/zkmpc_hip.h): (struct, objects that must outlive the call)."""
+    """The index as the C ABI's zk_marlin_index (include/zkmpc_hip.h): (struct, objects that must outlive the call).  keys: an
+    IndexKeys, whose struct is filled here, or a NativeIndex, which holds the library's own."""
+    if isinstance(keys, NativeIndex):
+        return keys.view, keys
     index = keys.index
     d = _lib.MarlinIndex()
     d.num_constraints, d.num_variables = index.num_constraints, index.num_variables
@@ -396,12 +399,116 @@ def native_index(keys: IndexKeys):
     return d, (polys, d_iw, d_ix, ivk)
 
 
-def prove_native(keys: IndexKeys, assignment_dev: DevBuf, zk_rng, mask_on_device: bool = False) -> bytes:
+def _r1cs_host(num_instance: int, num_witness: int, a, b, c):
+    """The ABI's zk_r1cs_host over (row_ptr, col, coeff) triples as Context.r1cs_upload takes them: (struct, arrays to keep alive)."""
+    h, keep = _lib.R1csHost(), []
+    h.num_constraints = len(a[0]) - 1
+    h.num_instance, h.num_witness = num_instance, num_witness
+    for name, (rp, col, coeff) in zip("abc", (a, b, c)):
+        rp = np.ascontiguousarray(rp, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        coeff = np.ascontiguousarray(coeff, dtype=np.uint64)
+        keep += [rp, col, coeff]
+        setattr(h, name + "_row_ptr", rp.ctypes.data)
+        setattr(h, name + "_col", col.ctypes.data if col.size else None)
+        setattr(h, name + "_coeff", coeff.ctypes.data if coeff.size else None)
+    return h, keep
+
+
+def _info_dict(info) -> dict:
+    return {n: int(getattr(info, n)) for n, _ in _lib.MarlinIxInfo._fields_}
+
+
+def shape_info(num_instance: int, num_witness: int, a, b, c) -> dict:
+    """The sizes of the index of a system as the circuit gives it (zk_marlin_ix_info), on the host: no device, nothing built."""
+    import ctypes as C
+    h, _keep = _r1cs_host(num_instance, num_witness, a, b, c)
+    info = _lib.MarlinIxInfo()
+    if _lib.load().zk_diag_marlin_shape_host(C.byref(h), 0, None, None, None, 0, C.byref(info)) != _lib.ZK_OK:
+        raise _lib.ZkError("zk_diag_marlin_shape_host refused the system")
+    return _info_dict(info)
+
+
+def shape_host(num_instance: int, num_witness: int, a, b, c):
+    """zk_diag_marlin_shape_host: the integer half of the index on the host, no device.  -> (info dict, [A, B, C balanced and
+    sorted, then their transposes over H] as Csr)."""
+    import ctypes as C
+    h, _keep = _r1cs_host(num_instance, num_witness, a, b, c)
+    lib = _lib.load()
+    info = _lib.MarlinIxInfo()
+    if lib.zk_diag_marlin_shape_host(C.byref(h), 0, None, None, None, 0, C.byref(info)) != _lib.ZK_OK:
+        raise _lib.ZkError("zk_diag_marlin_shape_host refused the system")
+    mats = []
+    for which in range(6):
+        rows = info.num_constraints if which < 3 else info.h_size
+        cap = max(int(a[0][-1]) + int(b[0][-1]), int(c[0][-1]), 1)      # (balancing moves rows between A and B)
+        rp, col, coeff = np.zeros(rows + 1, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 4), np.uint64)
+        rc = lib.zk_diag_marlin_shape_host(C.byref(h), which, rp.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                           coeff.ctypes.data_as(C.c_void_p), cap, None)
+        if rc != _lib.ZK_OK:
+            raise _lib.ZkError("zk_diag_marlin_shape_host failed (%d)" % rc)
+        mats.append(Csr(rp, col[:rp[-1]], coeff[:rp[-1]]))
+    return _info_dict(info), mats
+
+
+class NativeIndex:
+    """Marlin::index as the library's one call (zk_marlin_index_build, csrc/marlin_index.hip) on matrices as to_matrices() gives
+    them -- (num_instance, num_witness, a, b, c) with (row_ptr, col, coeff) triples, neither padded nor square -- and an SRS.
+    Owns the handle; prove_native takes it in place of an IndexKeys."""
+
+    def __init__(self, ctx: Context, r1cs_host_arrays, srs: UniversalSrs):
+        import ctypes as C
+        self.ctx, self.srs = ctx, srs
+        h, _keep = _r1cs_host(*r1cs_host_arrays)
+        out = C.c_void_p()
+        ctx._ck(ctx.lib.zk_marlin_index_build(ctx.h, C.byref(h), srs.powers_g.h, C.byref(out)))
+        self.h = out
+        info = _lib.MarlinIxInfo()
+        ctx._ck(ctx.lib.zk_marlin_ix_info_get(self.h, C.byref(info)))
+        self.info = _info_dict(info)
+
+    @property
+    def view(self) -> "_lib.MarlinIndex":
+        import ctypes as C
+        return C.cast(self.ctx.lib.zk_marlin_ix_view(self.h), C.POINTER(_lib.MarlinIndex)).contents
+
+    def ivk_bytes(self) -> bytes:
+        import ctypes as C
+        v = self.view
+        ptr = C.c_void_p.from_address(C.addressof(v) + _lib.MarlinIndex.ivk_bytes.offset)      # (the field reads as a C string)
+        return C.string_at(ptr, v.ivk_len)
+
+    def pad_assignment(self, z_dev: DevBuf) -> DevBuf:
+        """The circuit's assignment (instance | witness) in the index's layout (zk_marlin_pad_assignment_dev)."""
+        import ctypes as C
+        out = self.ctx.alloc((self.info["num_instance"] + self.info["num_witness"]) * 32)
+        self.ctx._ck(self.ctx.lib.zk_marlin_pad_assignment_dev(self.ctx.h, self.h, C.c_void_p(z_dev.ptr), C.c_void_p(out.ptr)))
+        return out
+
+    def verifier_key(self, h, beta_h) -> "VerifierKey":
+        """zk_marlin_vk_from_index: the key's G1 parts from the SRS tables, h / beta_h as affine arrays in the ABI's form."""
+        import ctypes as C
+        g2 = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (h, beta_h)]
+        st = _lib.MarlinVkHost()
+        self.ctx._ck(self.ctx.lib.zk_marlin_vk_from_index(self.ctx.h, self.h, self.srs.powers_g.h, self.srs.powers_gamma_g.h,
+                                                          g2[0].ctypes.data_as(C.c_void_p), g2[1].ctypes.data_as(C.c_void_p), C.byref(st)))
+        part = lambda name, n: np.frombuffer(bytes(getattr(st, name)), dtype=np.uint64, count=n)
+        return VerifierKey.from_parts(self.ivk_bytes(), part("g", 12), part("gamma_g", 12), part("h", 24), part("beta_h", 24),
+                                      part("shift_h", 12), part("shift_k", 12))
+
+    def free(self):
+        if self.h:
+            self.ctx._ck(self.ctx.lib.zk_marlin_ix_free(self.ctx.h, self.h))
+            self.h = None
+
+
+def prove_native(keys, assignment_dev: DevBuf, zk_rng, mask_on_device: bool = False) -> bytes:
     """Marlin::prove through the library's single entry point zk_marlin_prove (csrc/marlin_prove.hip): the sequence of
-    tests/pyseq/marlin_seq.py::prove, on the host in C++.  Returns the CanonicalSerialize bytes of the proof."""
+    tests/pyseq/marlin_seq.py::prove, on the host in C++.  keys: an IndexKeys, or a NativeIndex (then the assignment is the padded
+    one: NativeIndex.pad_assignment).  Returns the CanonicalSerialize bytes of the proof."""
     import ctypes as C
     srs = keys.srs
-    ctx = keys.index.ctx
+    ctx = keys.ctx if isinstance(keys, NativeIndex) else keys.index.ctx
     d, _keep = native_index(keys)
     cap = ctx.lib.zk_marlin_proof_max_size()
     out = (C.c_uint8 * cap)()
