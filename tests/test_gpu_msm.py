@@ -319,8 +319,9 @@ def test_groth16_precomputed_key_matches_plain(ctx, n):
     pk0.free(); pk1.free()
 
 
-def test_msm_batch_pipeline(ctx):
-    """zk_msm_batch_dev: more jobs than scratch slots, both groups, an empty job, offsets; equal to the single calls."""
+def _batch_pipeline_jobs(ctx):
+    """A plain 300-point G1 table, a 64-point G2 table and eight jobs over them: more jobs than scratch slots, both groups, an empty
+    job, offsets.  (The uploads stay alive through the tables and vectors handed back with the jobs.)"""
     rng = O.Prng(4242)
     n = 300
     ks = [rng.fr() for _ in range(n)]
@@ -330,11 +331,92 @@ def test_msm_batch_pipeline(ctx):
     vecs = [ctx.upload(cv.fr_to_mont([rng.fr() for _ in range(n)])) for _ in range(4)]
     jobs = [(b1, 0, vecs[0].ptr, n), (b2, 0, vecs[1].ptr, 64), (b1, 5, vecs[2].ptr, 100), (b1, 0, vecs[3].ptr, 0),
             (b1, 0, vecs[3].ptr, n), (b2, 3, vecs[0].ptr, 61), (b1, 0, vecs[1].ptr, 1), (b1, 290, vecs[2].ptr, 10)]
+    return b1, b2, vecs, jobs, sc
+
+
+def test_msm_batch_pipeline(ctx):
+    """zk_msm_batch_dev: more jobs than scratch slots, both groups, an empty job, offsets; equal to the single calls."""
+    _, _, _, jobs, _ = _batch_pipeline_jobs(ctx)
     outs = ctx.msm_batch_dev(jobs)
     for (b, off, s, m), got in zip(jobs, outs):
         want = ctx.msm_dev(b, off, s, m)
         to_aff = cv.g1_projective_to_affine if b.group == 1 else cv.g2_projective_to_affine
         assert to_aff(got) == to_aff(want)
+
+
+# What ctx.timers() holds for the MSM stages after the batches of test_msm_phase_timers_by_path: {phase: launches timed}.  The
+# stages hang one timer per sort / accumulate / reduce they enqueue on the job (a group's on its first job) and finish() resolves
+# them; these counts were read off the library BEFORE the jobs came to own their timers and events, and any change of the stages
+# has to reproduce them: a phase that stops being timed, is timed twice, or a timer that is dropped unresolved shows here.
+_TIMER_COUNTS = {
+    # eight jobs, one of them empty, none over window multiples: the general branch, seven sorts / kernels / chains by group
+    "pipeline": {"msm_g1.sort": 5, "msm_g1.accum": 5, "msm_g1.reduce": 5, "msm_g2.sort": 2, "msm_g2.accum": 2, "msm_g2.reduce": 2},
+    # three jobs over window multiples: one group (a sort launch, an accumulate launch, a reduce chain for all three)
+    "group": {"msm_g1.sort": 1, "msm_g1.accum": 1, "msm_g1.reduce": 1},
+    # two jobs with one scalar vector over window multiples (G1: they qualify as a group, and a group sorts every job itself)
+    "same scalars, G1": {"msm_g1.sort": 1, "msm_g1.accum": 1, "msm_g1.reduce": 1},
+    # ... and over a G2 table (no groups in G2): the general branch, where the second job borrows the first one's sort
+    "borrowed sort, G2": {"msm_g2.sort": 1, "msm_g2.accum": 2, "msm_g2.reduce": 2},
+}
+
+
+def _check_timers(ctx, label, want):
+    got = {k: v for k, v in ctx.timers().items() if k.startswith(("msm_g1.", "msm_g2."))}
+    print(label, {k: got[k][1] for k in sorted(got)}, {k: round(got[k][0], 4) for k in sorted(got)})
+    assert {k: c for k, (_, c) in got.items()} == want, label
+    assert all(ms > 0 for ms, _ in got.values()), (label, got)
+
+
+def test_msm_phase_timers_by_path(ctx):
+    """The phase timers of the MSM stages (ctx.set_profiling: msm_g1.* / msm_g2.* of ctx.timers()) on every path that hangs them on a
+    job: a single MSM in G1 and in G2 (sort, accumulate and reduce once each), the batch's general branch, a group, two jobs over
+    one scalar vector in G1 (a group) and in G2 (a borrowed sort).  Exact counts, every time positive, every sum the single call's."""
+    rs = np.random.RandomState(515)
+
+    def rand_mont(m):
+        a = rs.randint(0, 1 << 62, size=(m, 4), dtype=np.uint64)
+        a[:, 3] &= np.uint64((1 << 60) - 1)
+        return a
+
+    def same_as_single_calls(jobs, outs):
+        for (b, off, s, m), got in zip(jobs, outs):
+            to_aff = cv.g1_projective_to_affine if b.group == 1 else cv.g2_projective_to_affine
+            assert to_aff(got) == to_aff(ctx.msm_dev(b, off, s, m))
+        ctx.timers()                                         # (the single calls' own)
+
+    b1, b2, vecs, jobs, sc = _batch_pipeline_jobs(ctx)
+    dk = ctx.upload(rand_mont(4096))
+    tab = ctx.fixed_base(dk.ptr, 4096, 1, mont1(1))
+    tab.precompute()
+    tab2 = ctx.fixed_base(dk.ptr, 256, 2, mont1(1))
+    tab2.precompute()
+    assert ctx.lib.zk_bases_window_bits(tab.h) > 0 and ctx.lib.zk_bases_window_bits(tab2.h) > 0
+    sv = [ctx.upload(rand_mont(4096)) for _ in range(3)]
+    ctx.set_profiling(True)
+    try:
+        ctx.timers()
+        one = [ctx.msm_dev(b1, 0, vecs[0].ptr, 300)]
+        _check_timers(ctx, "one G1 MSM", {"msm_g1.sort": 1, "msm_g1.accum": 1, "msm_g1.reduce": 1})
+        one.append(ctx.msm_dev(b2, 0, vecs[1].ptr, 64))
+        _check_timers(ctx, "one G2 MSM", {"msm_g2.sort": 1, "msm_g2.accum": 1, "msm_g2.reduce": 1})
+        cases = [("pipeline", jobs),
+                 ("group", [(tab, 0, v.ptr, 4096) for v in sv]),
+                 ("same scalars, G1", [(tab, 0, sv[0].ptr, 4000), (tab, 7, sv[0].ptr, 4000)]),
+                 ("borrowed sort, G2", [(tab2, 0, sv[1].ptr, 249), (tab2, 7, sv[1].ptr, 249)])]
+        for label, js in cases:
+            outs = ctx.msm_batch_dev(js)
+            _check_timers(ctx, label, _TIMER_COUNTS[label])
+            same_as_single_calls(js, outs)
+            if js is jobs:                                   # its first two jobs are the two single MSMs above
+                assert cv.g1_projective_to_affine(one[0]) == cv.g1_projective_to_affine(outs[0])
+                assert cv.g2_projective_to_affine(one[1]) == cv.g2_projective_to_affine(outs[1])
+    finally:
+        ctx.set_profiling(False)
+        ctx.timers()
+    for d in sv + vecs + [dk, sc]:
+        d.free()
+    for b in (tab, tab2, b1, b2):
+        b.free()
 
 
 def test_msm_batch_more_jobs_than_any_numbered_range(ctx):

@@ -385,11 +385,7 @@ int upload_table(zk_ctx* ctx, const ZkHostTable& t, size_t n, uint32_t** raw_out
         if (rc == ZK_OK) rc = zk_xfer_stream(ctx, &xs);
         if (rc == ZK_OK) rc = zk_bases_import_launch(ctx, b, raw, xs);
         if (rc == ZK_OK) {
-            hipEvent_t ev = nullptr;                         // (an event per upload: tables are uploaded once)
-            hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(ev, xs);
-            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ev, 0);
-            if (ev) (void)hipEventDestroy(ev);
+            const hipError_t e = zk_streams_follow(xs, &ctx->stream, 1);      // (the context stream behind the import; an event per upload: tables are uploaded once)
             if (e != hipSuccess) { ctx->last_error = std::string("base table upload: ") + hipGetErrorString(e); rc = ZK_ERR_HIP; }
         }
         if (rc != ZK_OK && xs) (void)hipStreamSynchronize(xs);

@@ -89,7 +89,6 @@ extern "C" int zk_ctx_destroy(zk_ctx* ctx) {
     for (auto st : ctx->aux) (void)hipStreamDestroy(st);
     if (ctx->acc_stream) (void)hipStreamDestroy(ctx->acc_stream);
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-    if (ctx->next.ready) (void)hipEventDestroy(ctx->next.ready);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return ZK_OK;
@@ -295,6 +294,35 @@ int zk_scratch_zeroed(zk_ctx* ctx, const char* name, size_t bytes, void** out) {
         ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return ZK_OK;
+}
+
+// ---- phase timer ----
+ZkPhaseTimer::ZkPhaseTimer(zk_ctx* c, hipStream_t st) : ctx(c), stream(st ? st : c->stream) { enabled = c->profiling; }
+void ZkPhaseTimer::begin(const char* name) {
+    if (!enabled) return;
+    ev.emplace_back();
+    ev.back().name = name;
+    (void)ev.back().begin.record(stream);
+}
+void ZkPhaseTimer::end() {
+    if (!enabled || ev.empty()) return;
+    (void)ev.back().end.record(stream);
+}
+void ZkPhaseTimer::resolve() {
+    if (!enabled || resolved) return;
+    resolved = true;
+    // wait for each phase's own end event, never for the stream: the accumulate stream holds the kernels of ALL in-flight
+    // jobs, and synchronising it from the first job's finish() made the host wait for the whole proof (the host-side
+    // chains of create_proof then started after the GPU had gone idle: +1.1 ms per proof with the timers on)
+    for (auto& e : ev) {
+        float ms = 0;
+        if (e.begin && e.end && hipEventSynchronize(e.end.get()) == hipSuccess &&
+            hipEventElapsedTime(&ms, e.begin.get(), e.end.get()) == hipSuccess) {
+            std::lock_guard<std::mutex> lk(ctx->mu);           // (the host halves of a group's jobs resolve side by side)
+            ctx->timers[e.name].ms += ms;
+            ctx->timers[e.name].count += 1;
+        }
+    }
 }
 
 extern "C" int zk_set_profiling(zk_ctx* ctx, int on) {

@@ -4,6 +4,7 @@
 // mpc-net/src/multi.rs:419-443).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "stream_order.hpp"
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
@@ -169,7 +170,7 @@ struct zk_ctx {
         const void *pk = nullptr, *r = nullptr;      // ... together with the key, the constraint system and the length it was announced for
         size_t m = 0;
         void* dev = nullptr;                  // where its copy lives
-        hipEvent_t ready = nullptr;
+        ZkEvent ready;
         int slot = 0;                         // which of the two "prove_z" slots the CURRENT proof reads
         bool matches(const void* z_host, const void* pk_, const void* r_, size_t m_) const {
             return host == z_host && dev && pk == pk_ && r == r_ && m == m_;

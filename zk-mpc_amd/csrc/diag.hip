@@ -86,22 +86,18 @@ extern "C" int zk_diag_int_mad_peak(zk_ctx* ctx, int launches, double* best_mads
     uint64_t* out;
     ZK_TRY(zk_scratch(ctx, "diag_out", (size_t)blocks * threads * 8, (void**)&out));
     hipStream_t st = ctx->stream;
-    hipEvent_t e0, e1;
-    ZK_HIP(ctx, hipEventCreate(&e0));
-    ZK_HIP(ctx, hipEventCreate(&e1));
+    ZkEvent e0(0), e1(0);                                          // (flags 0: events that keep time)
     const double mads = (double)blocks * threads * DIAG_ITERS * DIAG_CH;
     std::vector<double> rate;
     int rc = ZK_OK;
     for (int i = -2; i < launches && rc == ZK_OK; i++) {           // two untimed launches first (clocks, code upload)
-        if (hipEventRecord(e0, st) != hipSuccess) rc = ZK_ERR_HIP;
+        if (e0.record(st) != hipSuccess) rc = ZK_ERR_HIP;
         hipLaunchKernelGGL(k_diag_mad64, blocks, threads, 0, st, out, 3u, 5u);
-        if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) rc = ZK_ERR_HIP;
+        if (e1.record(st) != hipSuccess || hipEventSynchronize(e1.get()) != hipSuccess) rc = ZK_ERR_HIP;
         float ms = 0;
-        if (rc == ZK_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK && hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) rc = ZK_ERR_HIP;
         if (rc == ZK_OK && i >= 0 && ms > 0) rate.push_back(mads / (ms * 1e-3));
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (rc != ZK_OK || rate.empty()) ZK_FAIL(ctx, ZK_ERR_HIP, "zk_diag_int_mad_peak: timing failed");
     std::sort(rate.begin(), rate.end());
     if (best_mads_per_s) *best_mads_per_s = rate.back();

@@ -87,12 +87,11 @@ struct ZkG16Flight {
     ZkMsmJob J[5];
     ZkMsmJob* const g1[4] = {&J[1], &J[2], &J[3], &J[4]};      // the four G1 jobs, as the group calls take them
     enum Stage : uint8_t { NONE, SORTED, ACCUMULATED, REDUCED } at[5] = {NONE, NONE, NONE, NONE, NONE};
-    hipEvent_t wm_done = nullptr;      // recorded behind the witness map: gates the first accumulate kernel (and a late sort of L)
+    ZkEvent wm_done;                   // recorded behind the witness map: gates the first accumulate kernel (and a late sort of L)
     bool grouped = false;              // jobs 1..4 go / went out as one group launch
     bool beyond_sort_z() const { return at[1] || at[2] || at[3] || at[4]; }      // (then zk_presort_free drains more than the sort stream)
     ZkG16Flight(const zk_pk* pk_, const zk_r1cs* r_, const void* z_, void* h_) : pk(pk_), r(r_), z(z_), h(h_) {}
     ZkG16Flight(const ZkG16Flight&) = delete; ZkG16Flight& operator=(const ZkG16Flight&) = delete;      // (g1 points into this object)
-    ~ZkG16Flight() { if (wm_done) (void)hipEventDestroy(wm_done); }
 };
 
 // the context's helper streams: aux[0..k) and the accumulate stream (created on first use)

@@ -50,11 +50,7 @@ int zk_prover_streams(zk_ctx* ctx, size_t k) {
 }
 
 int zk_behind_context_stream(zk_ctx* ctx, const hipStream_t* waiters, int count) {
-    if (count <= 0) return ZK_OK;
-    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } e0;      // destroyed on every exit path
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(e0.e, ctx->stream));
-    for (int k = 0; k < count; k++) ZK_HIP(ctx, hipStreamWaitEvent(waiters[k], e0.e, 0));
+    ZK_HIP(ctx, zk_streams_follow(ctx->stream, waiters, count));
     return ZK_OK;
 }
 
@@ -137,21 +133,22 @@ int witness_map_and_h(zk_ctx* ctx, ZkG16Flight& F, const ZkG16Jobs& T, ZkPhaseTi
             ZK_TRY(rc);
         }
         ZK_TRY(T.prepare(ctx, 4, &F.J[4], ZK_SLOT_G16));
-        ZK_HIP(ctx, hipEventCreateWithFlags(&F.wm_done, hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(F.wm_done, ctx->stream));
-        if (behind && behind->J[4].accum_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, behind->J[4].accum_done, 0));
-        if (behind && behind->J[4].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, behind->J[4].reduce_done, 0));
+        ZK_HIP(ctx, F.wm_done.record(ctx->stream));
+        if (behind) {
+            ZK_HIP(ctx, behind->J[4].accumulated_at.order(ctx->stream));
+            ZK_HIP(ctx, behind->J[4].reduced_at.order(ctx->stream));
+        }
         ZK_TRY(zk_msm_enqueue_sort(ctx, &F.J[4], ctx->stream, nullptr));
         F.at[4] = Stage::SORTED;
     }
-    if (!behind) ZK_HIP(ctx, hipStreamWaitEvent(ctx->acc_stream, F.wm_done, 0));
+    if (!behind) ZK_HIP(ctx, hipStreamWaitEvent(ctx->acc_stream, F.wm_done.get(), 0));
     return ZK_OK;
 }
 
 // L's sort after the witness map where L does not share the z jobs' (it is not needed before the fourth accumulate kernel)
 int sort_l_late(zk_ctx* ctx, ZkG16Flight& F, hipStream_t st) {
     if (F.at[3] >= Stage::SORTED) return ZK_OK;
-    if (F.wm_done) ZK_HIP(ctx, hipStreamWaitEvent(st, F.wm_done, 0));
+    if (F.wm_done) ZK_HIP(ctx, hipStreamWaitEvent(st, F.wm_done.get(), 0));
     ZK_TRY(zk_msm_enqueue_sort(ctx, &F.J[3], st, nullptr));
     F.at[3] = Stage::SORTED;
     return ZK_OK;
@@ -199,15 +196,14 @@ int collect(zk_ctx* ctx, ZkG16Flight& F, zk_g1_projective out_g1[4], zk_g2_proje
 int enqueue_front(zk_ctx* ctx, const ZkG16Flight& C, ZkG16Flight& N, const ZkG16Jobs& T) {
     const StreamPlan P = stream_plan(ctx, PLAN_FRONT);
     if (N.z == ctx->next.dev && ctx->next.ready) {      // announced from the host: its upload runs on the copy stream
-        ZK_HIP(ctx, hipStreamWaitEvent(P.sort_z, ctx->next.ready, 0));
-        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next.ready, 0));
+        ZK_HIP(ctx, hipStreamWaitEvent(P.sort_z, ctx->next.ready.get(), 0));
+        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->next.ready.get(), 0));
     }
     // a reduce chain reads its job's segment tables (k_fold: ctr / heavy live in the sort scratch of the job's slot).  The
     // next proof's z-sort rewrites slot 1, whose products the four z jobs share: it waits for THEIR chains (not for the H
     // job's, the last one: the z-sort is meant to run under that tail); the next H-sort rewrites slot 5 and waits for the
     // H job's chain.
-    for (int k = 0; k < 4; k++)
-        if (C.J[k].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(P.sort_z, C.J[k].reduce_done, 0));
+    for (int k = 0; k < 4; k++) ZK_HIP(ctx, C.J[k].reduced_at.order(P.sort_z));
     ZK_TRY(sort_z(ctx, N, T, P.sort_z, true));
     ZK_TRY(witness_map_and_h(ctx, N, T, nullptr, &C));
     // A SMALL proof (its four G1 jobs one group): the next proof's whole device chain goes out as well -- accumulate launches and

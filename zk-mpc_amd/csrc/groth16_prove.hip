@@ -122,7 +122,7 @@ extern "C" int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1
         // waited for the copy)
         z = nx.dev;
         nx.slot ^= 1;
-        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, nx.ready, 0));
+        ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, nx.ready.get(), 0));
         ZK_TRY(zk_next_z_drop(ctx, false));
     } else {
         // Not the announced assignment (or announced for another key / system / length: the upload may be shorter than m).  A
@@ -136,13 +136,12 @@ extern "C" int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1
     }
     if (z_next_host) {
         if (!ctx->copy_stream) ZK_HIP(ctx, zk_stream_create(&ctx->copy_stream, false));
-        if (!nx.ready) ZK_HIP(ctx, hipEventCreateWithFlags(&nx.ready, hipEventDisableTiming));
         void* zn;
         // the other slot: its last reader was the previous proof, which has delivered its bytes
         ZK_TRY(zk_scratch(ctx, nx.slot ? "prove_z0" : "prove_z1", m * 32, &zn));
         if (zk_host_is_pinned(z_next_host)) {
             ZK_HIP(ctx, hipMemcpyAsync(zn, z_next_host, m * 32, hipMemcpyHostToDevice, ctx->copy_stream));
-            ZK_HIP(ctx, hipEventRecord(nx.ready, ctx->copy_stream));
+            ZK_HIP(ctx, nx.ready.record(ctx->copy_stream));
         } else {
             // pageable: staged through the ring now (the call returns behind the host copy) on the ring's DMA stream ALONE -- no
             // fence with the context stream in either direction (the slot's last reader has delivered its bytes; the consumer waits
@@ -152,7 +151,7 @@ extern "C" int zk_groth16_prove_queued(zk_ctx* ctx, const zk_pk* pk, const zk_r1
             ZK_TRY(zk_xfer_h2d_fn(ctx, zn, m * 32, fill, false, nullptr));
             hipStream_t xs;
             ZK_TRY(zk_xfer_stream(ctx, &xs));
-            ZK_HIP(ctx, hipEventRecord(nx.ready, xs));
+            ZK_HIP(ctx, nx.ready.record(xs));
         }
         nx.host = z_next_host;
         nx.z = nx.dev = zn;

@@ -2,11 +2,15 @@
 #pragma once
 #include "ctx.hpp"
 #include "ec.cuh"
+#include "msm_digits.cuh"
+#include "stream_order.hpp"
 #include <stddef.h>
 #include <stdint.h>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // ntt.hip
@@ -157,15 +161,15 @@ void zk_bases_precompute_finish(ZkPrecompJob* j, bool keep);
 int zk_msm_run(zk_ctx* ctx, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n,
                void* out_host_projective);
 
-// event-based phase timer (two hipEventRecord per phase on the given stream; resolved lazily)
+// event-based phase timer (core.hip; two hipEventRecord per phase on the given stream; resolved lazily)
 struct ZkPhaseTimer {
     zk_ctx* ctx;
     hipStream_t stream;
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> ev;
+    struct Phase { std::string name; ZkEvent begin{0}, end{0}; };      // (flags 0: events that keep time)
+    std::vector<Phase> ev;
     bool enabled;
     bool resolved = false;
     explicit ZkPhaseTimer(zk_ctx* c, hipStream_t st = nullptr);
-    ~ZkPhaseTimer();
     void begin(const char* name);
     void end();
     void resolve();  // waits for the recorded end events (not for the stream) and accumulates into ctx->timers
@@ -208,7 +212,19 @@ static_assert(ZK_SLOT_RUN + 1 <= ZK_SLOT_G16 && ZK_SLOT_G16 + ZK_SLOT_G16_COUNT 
               ZK_SLOT_AHEAD + ZK_SLOT_AHEAD_COUNT <= ZK_SLOT_G16_BATCH && ZK_SLOT_G16_BATCH + ZK_SLOT_G16_COUNT <= ZK_SLOT_END,
               "the MSM scratch slot ranges overlap");
 
-// An MSM in flight (msm.hip): prepare -> enqueue_sort -> enqueue_accum -> enqueue_reduce -> finish.
+// What a finished sort leaves for the accumulate kernel and the reduce chain (msm_digits.cuh has the two descriptors).  A job that
+// borrows another job's sort takes the whole set.
+struct ZkSortProducts {
+    uint32_t *sorted = nullptr, *order = nullptr, *ctr = nullptr;
+    SegDesc* desc = nullptr;
+    HeavyDesc *heavy = nullptr, *heavy2 = nullptr;
+};
+
+// An MSM in flight (msm.hip): prepare -> enqueue_sort -> enqueue_accum -> enqueue_reduce -> finish.  Each enqueue ends by setting
+// the job's mark of that stage (stream_order.hpp: ZkStageMark) on its stream -- sorted_at once the sort products are final,
+// accumulated_at behind the accumulate kernel, reduced_at behind the copy of the partial sums to the host -- and whoever needs a
+// stage done calls the mark's order(st): a wait, or nothing where st is the mark's own stream.  The job owns its events and
+// timers: it moves, it does not copy.
 struct ZkMsmJob {
     int group = 1, slot = 0;
     ZkPin pin = {ZK_PIN_OF_SLOT, 0};  // pinned result buffer; OF_SLOT: the slot's.  Jobs enqueued without a host wait in between need their own
@@ -224,22 +240,18 @@ struct ZkMsmJob {
     uint32_t stride = 0;              // 32-bit words between consecutive points of bases_dev (the packed 2 * WORDS, or zk_bases::pre_stride)
     const uint32_t* bases_dev = nullptr;
     const void* scalars = nullptr;
-    hipStream_t stream = nullptr;     // the stream the reduce phase (and the copy to hw) is on
-    hipStream_t sort_stream = nullptr, accum_stream = nullptr;   // where sort_done / accum_done were recorded: a consumer on the same stream needs no wait (3.9 us of host time each)
-    hipEvent_t sort_done = nullptr;   // recorded once sorted/desc/order are final
-    hipEvent_t accum_done = nullptr;  // recorded after the accumulate kernel
-    hipEvent_t reduce_done = nullptr; // recorded after the copy of the partial sums to the host: what finish() waits for
+    ZkStageMark sorted_at, accumulated_at;
+    ZkStageMark reduced_at;           // what finish() waits for (its stream: where the reduce chain and the copy to hw are)
     uint32_t* hw = nullptr;           // partial window sums (XYZZ, internal form) in pinned host memory
-    // the sort products, so that a later job over the same scalar vector can reuse them
-    uint32_t *sorted = nullptr, *order = nullptr, *ctr = nullptr;
-    void *desc = nullptr, *heavy = nullptr, *heavy2 = nullptr;
+    ZkSortProducts sort;              // kept so that a later job over the same scalar vector can reuse them
     size_t max_heavy2 = 0, max_heavy_segs = 0, max_groups = 0;
-    std::vector<ZkPhaseTimer*> timers;
+    std::vector<std::unique_ptr<ZkPhaseTimer>> timers;      // one per stage enqueued (a group's: on its first job); finish() resolves them
+    ZkPhaseTimer* add_timer(zk_ctx* ctx, hipStream_t st) { timers.push_back(std::make_unique<ZkPhaseTimer>(ctx, st)); return timers.back().get(); }
     // several scalar vectors over one table (zk_msm_prepare_multi): n = mcount * mn scalars, vector k at scalars + k * mstride
     // elements; Wb = mcount bucket sets of the vector's geometry back to back
     size_t mcount = 0, mn = 0, mstride = 0;
-    ~ZkMsmJob();
 };
+static_assert(!std::is_copy_constructible<ZkMsmJob>::value && std::is_move_constructible<ZkMsmJob>::value, "a ZkMsmJob owns its events and timers");
 int zk_msm_prepare(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n, int slot);
 int zk_msm_enqueue_sort(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJob* share_sort);
 int zk_msm_enqueue_accum(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st);
@@ -314,7 +326,7 @@ int zk_g1_sub_launch(zk_ctx* ctx, const uint32_t* a_affine_dev, const uint32_t* 
 // msm_sort.hip: the bucket sort (msm_digits.cuh declares its interface)
 
 // msm_g2pair.hip: the G2 accumulate kernel with two lanes per point addition
-void zk_launch_accum_g2pair(hipStream_t st, size_t segments, const uint32_t* bases, const uint32_t* sorted, const void* desc,
+void zk_launch_accum_g2pair(hipStream_t st, size_t segments, const uint32_t* bases, const uint32_t* sorted, const SegDesc* desc,
                             const uint32_t* order, const uint32_t* ctr, uint32_t* sums, bool quads);
 // test hooks (diag.hip): one small launch over a padded case array, the real device functions of the file that defines it.
 // `lanes` is a whole number of waves; in / out hold in_w / out_w words per case (diag.hip documents the layouts).
@@ -322,7 +334,7 @@ void zk_diag_launch_fq2_pair(hipStream_t st, int op, const uint32_t* in, uint32_
 void zk_diag_launch_g1_dual(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes);    // msm.hip
 void zk_diag_launch_f7l(hipStream_t st, int op, const uint32_t* in, uint32_t* out, unsigned lanes);        // she.hip
 struct ZkG2PairReduce {   // the arguments of msm.hip's reduce chain
-    const void *heavy, *heavy2; const uint32_t* ctr; uint32_t* done;
+    const HeavyDesc *heavy, *heavy2; const uint32_t* ctr; uint32_t* done;
     uint32_t *sums, *rowP, *colP, *bits;
     uint32_t log_nb, n_win, light_blocks, heavy_blocks;
     bool quads = false;          // a small job: the fold on lane quads (the grid kernels choose by the bucket count)

@@ -139,15 +139,7 @@ k_scatter(const uint32_t* dig, size_t n, uint32_t W, uint32_t NB, const uint32_t
 }
 
 
-// ---- segments -------------------------------------------------------------------------------
-// A bucket with cnt points is cut into max(1, ceil(cnt / SEG)) segments.  Single-segment buckets
-// write their sum straight to sums[key]; the segments of a split ("heavy") bucket write partial
-// sums to sums[n_keys + ...] and k_fold adds them up.  SEG is ~4x the mean bucket size, so
-// for uniformly random scalars no bucket is split; splitting is what keeps 0/1-heavy witness
-// vectors, repeated scalars and a nearly empty top window from serialising on one thread.
-struct SegDesc { uint32_t start, len, dst; };
-// parent: HEAVY_NONE, or -- for the group of a bucket that is folded in two levels -- the index of its second-level entry
-struct HeavyDesc { uint32_t key, first, nseg, parent; };
+// ---- segments (SegDesc, HeavyDesc: msm_digits.cuh) --------------------------------------------
 constexpr uint32_t HEAVY_NONE = 0xffffffffu;
 
 // One block per window: exclusive scans of counts (-> offs) and of the per-bucket segment counts.
@@ -870,7 +862,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     const bool g1 = F::WORDS == 12;
     const size_t n = job->n;
     const bool share_merged = share && share->Wb == 1 && share->W > 1;       // entries are table indices w * n_tab + tab_off + i
-    if (share && share->n == n && share->scalars == job->scalars && share->sorted && share->Wb == job->Wb &&
+    if (share && share->n == n && share->scalars == job->scalars && share->sort.sorted && share->Wb == job->Wb &&
         share->mcount == job->mcount && share->mstride == job->mstride &&
         share->n_tab == job->n_tab && (share->tab_off == job->tab_off || share_merged) && share->c == job->c &&
         share->M == job->M && share->lvl_stride == job->lvl_stride) {
@@ -879,12 +871,9 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         // the base pointer -- the entries index the table linearly
         if (share->tab_off != job->tab_off)
             job->bases_dev = job->bases_dev + ((ptrdiff_t)job->tab_off - (ptrdiff_t)share->tab_off) * (ptrdiff_t)job->stride;
-        job->sorted = share->sorted; job->desc = share->desc; job->order = share->order; job->ctr = share->ctr; job->heavy = share->heavy;
-        job->heavy2 = share->heavy2;
-        ZK_HIP(ctx, hipEventCreateWithFlags(&job->sort_done, hipEventDisableTiming));
-        if (share->sort_stream != st) ZK_HIP(ctx, hipStreamWaitEvent(st, share->sort_done, 0));
-        ZK_HIP(ctx, hipEventRecord(job->sort_done, st));
-        job->sort_stream = st;
+        job->sort = share->sort;
+        ZK_HIP(ctx, share->sorted_at.order(st));
+        ZK_HIP(ctx, job->sorted_at.set(st));
         return ZK_OK;
     }
     MsmBufs<F> b;
@@ -904,8 +893,8 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     uint32_t* hist = b.small + 72;
     uint32_t* bin_start = hist + (seg + 1);
     uint32_t* bin_cursor = bin_start + (seg + 1);
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    job->timers.push_back(tm);
+    const ZkSortProducts products{b.sorted, b.order, ctr, b.desc, b.heavy, b.heavy2};      // the job's once the sort is enqueued
+    ZkPhaseTimer* tm = job->add_timer(ctx, st);
     tm->begin(g1 ? "msm_g1.sort" : "msm_g2.sort");
     const bool one_block = !job->mcount && merged && (size_t)W * n <= SS_MAX_ENTRIES && NB <= SS_MAX_NB && seg <= SS_MAX_SEG;      // k_sort_small: writes all of ctr itself
     const uint32_t grp_base = (uint32_t)(nbuck + job->max_heavy_segs);       // where the group sums of two-level buckets live in `sums`
@@ -938,10 +927,8 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
                            b.dig, b.sorted, b.desc, b.heavy, b.heavy2, b.order, ctr});
         ZK_HIP(ctx, hipGetLastError());
         tm->end();
-        job->sorted = b.sorted; job->desc = b.desc; job->order = b.order; job->ctr = ctr; job->heavy = b.heavy; job->heavy2 = b.heavy2;
-        ZK_HIP(ctx, hipEventCreateWithFlags(&job->sort_done, hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(job->sort_done, st));
-        job->sort_stream = st;
+        job->sort = products;
+        ZK_HIP(ctx, job->sorted_at.set(st));
         return ZK_OK;
     }
     // The ~13 launches of the sort as ONE graph launch from the third sort with the same arguments on (core.hip: zk_graph_run): a
@@ -982,10 +969,8 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         return ZK_OK;
     }));
     tm->end();
-    job->sorted = b.sorted; job->desc = b.desc; job->order = b.order; job->ctr = ctr; job->heavy = b.heavy; job->heavy2 = b.heavy2;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&job->sort_done, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(job->sort_done, st));
-    job->sort_stream = st;
+    job->sort = products;
+    ZK_HIP(ctx, job->sorted_at.set(st));
     return ZK_OK;
 }
 
@@ -999,41 +984,36 @@ int msm_enqueue_accum_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     const bool g1 = F::WORDS == 12;
     MsmBufs<F> b;
     ZK_TRY(msm_bufs_t<F>(ctx, job, b, false));
-    if (job->sort_stream != st) ZK_HIP(ctx, hipStreamWaitEvent(st, job->sort_done, 0));
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    job->timers.push_back(tm);
+    ZK_HIP(ctx, job->sorted_at.order(st));
+    ZkPhaseTimer* tm = job->add_timer(ctx, st);
     tm->begin(g1 ? "msm_g1.accum" : "msm_g2.accum");
     const unsigned accum_blocks = (unsigned)((job->max_segs + 255) / 256);      // one lane per segment (blocks beyond ctr[2] return at once)
+    const ZkSortProducts& s = job->sort;
     // G2 runs on lane pairs (msm_g2pair.hip): the one-lane-per-addition form needs the whole register file and is slower
     if constexpr (F::WORDS == 12) {
         if (job->stride == 64)      // limb-form table with both signs (fixed_base.hip::k_repack_limbs)
-            hipLaunchKernelGGL((k_accum<F, true>), accum_blocks, 256, 0, st, job->bases_dev, job->sorted,
-                               (const SegDesc*)job->desc, job->order, job->ctr, b.sums, job->stride);
+            hipLaunchKernelGGL((k_accum<F, true>), accum_blocks, 256, 0, st, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, job->stride);
         else
-            hipLaunchKernelGGL((k_accum<F, false>), accum_blocks, 256, 0, st, job->bases_dev, job->sorted,
-                               (const SegDesc*)job->desc, job->order, job->ctr, b.sums, job->stride);
+            hipLaunchKernelGGL((k_accum<F, false>), accum_blocks, 256, 0, st, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, job->stride);
     }
     else
-        zk_launch_accum_g2pair(st, job->max_segs, job->bases_dev, job->sorted, job->desc, job->order, job->ctr, b.sums, msm_latency_bound(job));
+        zk_launch_accum_g2pair(st, job->max_segs, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, msm_latency_bound(job));
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
-    ZK_HIP(ctx, hipEventCreateWithFlags(&job->accum_done, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(job->accum_done, st));
-    job->accum_stream = st;
+    ZK_HIP(ctx, job->accumulated_at.set(st));
     return ZK_OK;
 }
 
 template <class F>
 int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     constexpr size_t XW = 4 * F::WORDS;
-    job->stream = st;
+    job->reduced_at.stream = st;      // (finish() falls back on it where the chain below does not get as far as the mark)
     if (job->n == 0) return ZK_OK;
     const bool g1 = F::WORDS == 12;
     MsmBufs<F> b;
     ZK_TRY(msm_bufs_t<F>(ctx, job, b, false));
-    if (job->accum_stream != st) ZK_HIP(ctx, hipStreamWaitEvent(st, job->accum_done, 0));
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    job->timers.push_back(tm);
+    ZK_HIP(ctx, job->accumulated_at.order(st));
+    ZkPhaseTimer* tm = job->add_timer(ctx, st);
     tm->begin(g1 ? "msm_g1.reduce" : "msm_g2.reduce");
     // (a small grid: every block of the chain waits for a wave slot beside the running accumulate kernel, and a uniform input has
     // nothing to fold at all; the blocks stride over the heavy list)
@@ -1041,12 +1021,12 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     const unsigned heavy_blocks = (unsigned)std::min<size_t>(job->max_heavy, 256);
     if constexpr (F::WORDS != 12) {
         // G2: the same chain on lane pairs (msm_g2pair.hip)
-        ZkG2PairReduce a{job->heavy, job->heavy2, job->ctr, b.fold_done, b.sums, b.rowP, b.colP, b.bits, job->log_nb, job->Wb * job->red_win, 2 * light_blocks, heavy_blocks};
+        ZkG2PairReduce a{job->sort.heavy, job->sort.heavy2, job->sort.ctr, b.fold_done, b.sums, b.rowP, b.colP, b.bits, job->log_nb, job->Wb * job->red_win, 2 * light_blocks, heavy_blocks};
         a.quads = msm_latency_bound(job);
         ZK_TRY(zk_launch_reduce_g2pair(ctx, st, a));
     } else {
-        hipLaunchKernelGGL(k_fold<F>, light_blocks + heavy_blocks, 64, 64 * XW * 4, st, (const HeavyDesc*)job->heavy, (const HeavyDesc*)job->heavy2,
-                           (const uint32_t*)job->ctr, b.fold_done, b.sums, light_blocks);
+        hipLaunchKernelGGL(k_fold<F>, light_blocks + heavy_blocks, 64, 64 * XW * 4, st, job->sort.heavy, job->sort.heavy2, job->sort.ctr, b.fold_done,
+                           b.sums, light_blocks);
         const GridSrc src{{(const uint32_t*)b.sums, nullptr, nullptr, nullptr}, 0u};
         const uint32_t n_win = job->Wb * job->red_win;
         if (((size_t)n_win << job->log_nb) <= RED_DUAL_MAX_BUCKETS) {
@@ -1069,8 +1049,7 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     ZK_TRY(zk_pinned(ctx, key, std::max<size_t>((size_t)64 * 17, nbits) * XW * 4, (void**)&job->hw));
     ZK_HIP(ctx, hipMemcpyAsync(job->hw, b.bits, nbits * XW * 4, hipMemcpyDeviceToHost, st));
     // finish() waits for this event, not for the stream: later jobs' reduce phases may be queued behind on the same stream
-    ZK_HIP(ctx, hipEventCreateWithFlags(&job->reduce_done, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(job->reduce_done, st));
+    ZK_HIP(ctx, job->reduced_at.set(st));
     return ZK_OK;
 }
 
@@ -1108,11 +1087,10 @@ static int msm_enqueue_sort_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count,
         a.n_tab = job->n_tab; a.tab_off = job->tab_off; a.lm = LevelMap{0, 0, 0};
         a.grp_base = (uint32_t)((size_t)job->Wb * job->NB + job->max_heavy_segs);
         a.dig = b.dig; a.sorted = b.sorted; a.desc = b.desc; a.heavy = b.heavy; a.heavy2 = b.heavy2; a.order = b.order; a.ctr = b.small + 64;
-        job->sorted = b.sorted; job->desc = b.desc; job->order = b.order; job->ctr = b.small + 64; job->heavy = b.heavy; job->heavy2 = b.heavy2;
+        job->sort = ZkSortProducts{b.sorted, b.order, b.small + 64, b.desc, b.heavy, b.heavy2};
         nb_max = std::max(nb_max, job->NB);
     }
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    jobs[0]->timers.push_back(tm);
+    ZkPhaseTimer* tm = jobs[0]->add_timer(ctx, st);
     tm->begin("msm_g1.sort");
     if (!ctx->lds_attr_done[ZK_LDS_SORT_SMALL_GROUP]) {
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_sort_small_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)SS_MAX_NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4)));
@@ -1122,11 +1100,7 @@ static int msm_enqueue_sort_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count,
     hipLaunchKernelGGL(k_sort_small_group, count, SS_NT, lds, st, g);
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
-    for (int k = 0; k < count; k++) {
-        ZK_HIP(ctx, hipEventCreateWithFlags(&jobs[k]->sort_done, hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(jobs[k]->sort_done, st));
-        jobs[k]->sort_stream = st;
-    }
+    for (int k = 0; k < count; k++) ZK_HIP(ctx, jobs[k]->sorted_at.set(st));
     return ZK_OK;
 }
 
@@ -1137,7 +1111,7 @@ static bool msm_group_ok(ZkMsmJob* const* jobs, int count) {
     if (count < 2 || count > MSM_GROUP_MAX) return false;
     for (int k = 0; k < count; k++) {
         const ZkMsmJob* j = jobs[k];
-        if (j->group != 1 || j->n == 0 || j->Wb != 1 || j->M || j->log_nb != jobs[0]->log_nb || (j->stride == 64) != (jobs[0]->stride == 64) || !j->sort_done) return false;
+        if (j->group != 1 || j->n == 0 || j->Wb != 1 || j->M || j->log_nb != jobs[0]->log_nb || (j->stride == 64) != (jobs[0]->stride == 64) || !j->sorted_at.done) return false;
         // (a job that fills the chip by itself gains nothing from company: Marlin rounds, same box, limit 2^21 / 2^23 / 2^24 digits --
         // |H| = 2^16 11.4 / 10.6 / -, 2^17 16.2 / 14.8 / -, 2^18 22.0 / 21.7 / 21.0, 2^19 34.8 / 35.0 / 34.9, 2^20 62.9 / - / 64.1 ms)
         if ((size_t)j->n * j->W > ((size_t)1 << 23)) return false;
@@ -1153,13 +1127,12 @@ static int msm_enqueue_accum_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count
         ZkMsmJob* job = jobs[k];
         MsmBufs<F> b;
         ZK_TRY(msm_bufs_t<F>(ctx, job, b, false));
-        if (job->sort_stream != st) ZK_HIP(ctx, hipStreamWaitEvent(st, job->sort_done, 0));
-        g.j[k] = AccumArgs{job->bases_dev, job->sorted, (const SegDesc*)job->desc, job->order, job->ctr, b.sums, job->stride};
+        ZK_HIP(ctx, job->sorted_at.order(st));
+        g.j[k] = AccumArgs{job->bases_dev, job->sort.sorted, job->sort.desc, job->sort.order, job->sort.ctr, b.sums, job->stride};
         max_segs = std::max(max_segs, job->max_segs);
     }
     for (int k = count; k < MSM_GROUP_MAX; k++) g.j[k] = g.j[0];
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    jobs[0]->timers.push_back(tm);
+    ZkPhaseTimer* tm = jobs[0]->add_timer(ctx, st);
     tm->begin("msm_g1.accum");
     // a group that cannot give every SIMD a wave (<= 2^18 digits = 2^15 segments of 8 in all): a lane pair per segment (ec_dual.cuh)
     size_t digits = 0;
@@ -1175,11 +1148,7 @@ static int msm_enqueue_accum_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count
     }
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
-    for (int k = 0; k < count; k++) {
-        ZK_HIP(ctx, hipEventCreateWithFlags(&jobs[k]->accum_done, hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(jobs[k]->accum_done, st));
-        jobs[k]->accum_stream = st;
-    }
+    for (int k = 0; k < count; k++) ZK_HIP(ctx, jobs[k]->accumulated_at.set(st));
     return ZK_OK;
 }
 
@@ -1192,11 +1161,11 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     size_t max_heavy = 0;
     for (int k = 0; k < count; k++) {
         ZkMsmJob* job = jobs[k];
-        job->stream = st;
+        job->reduced_at.stream = st;
         MsmBufs<F> b;
         ZK_TRY(msm_bufs_t<F>(ctx, job, b, false));
-        if (job->accum_stream != st) ZK_HIP(ctx, hipStreamWaitEvent(st, job->accum_done, 0));
-        fg.j[k] = FoldArgs{(const HeavyDesc*)job->heavy, (const HeavyDesc*)job->heavy2, (const uint32_t*)job->ctr, b.fold_done, b.sums};
+        ZK_HIP(ctx, job->accumulated_at.order(st));
+        fg.j[k] = FoldArgs{job->sort.heavy, job->sort.heavy2, job->sort.ctr, b.fold_done, b.sums};
         src.p[k] = b.sums;
         max_heavy = std::max(max_heavy, job->max_heavy);
     }
@@ -1212,8 +1181,7 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     ZK_TRY(zk_scratch(ctx, nm, grid_col_points(gg) * XW * 4, (void**)&colP));
     snprintf(nm, sizeof nm, "msm_grp_bits.%d", jobs[0]->slot);
     ZK_TRY(zk_scratch(ctx, nm, (size_t)count * nout * XW * 4, (void**)&bits));
-    ZkPhaseTimer* tm = new ZkPhaseTimer(ctx, st);
-    jobs[0]->timers.push_back(tm);
+    ZkPhaseTimer* tm = jobs[0]->add_timer(ctx, st);
     tm->begin("msm_g1.reduce");
     const unsigned light_blocks = (unsigned)std::min<size_t>((max_heavy + 63) / 64, 128);
     const unsigned heavy_blocks = (unsigned)std::min<size_t>(max_heavy, 256);
@@ -1234,8 +1202,7 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     ZK_HIP(ctx, hipMemcpyAsync(hw, bits, (size_t)count * nout * XW * 4, hipMemcpyDeviceToHost, st));
     for (int k = 0; k < count; k++) {
         jobs[k]->hw = hw + (size_t)k * nout * XW;
-        ZK_HIP(ctx, hipEventCreateWithFlags(&jobs[k]->reduce_done, hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(jobs[k]->reduce_done, st));
+        ZK_HIP(ctx, jobs[k]->reduced_at.set(st));
     }
     return ZK_OK;
 }
@@ -1290,9 +1257,9 @@ int msm_finish_t(zk_ctx* ctx, ZkMsmJob* job, void* out_host) {
         host_write_projective<F>(aff_inf<F>(), (uint64_t*)out_host);
         return ZK_OK;
     }
-    if (job->reduce_done) ZK_HIP(ctx, hipEventSynchronize(job->reduce_done));
-    else ZK_HIP(ctx, hipStreamSynchronize(job->stream));
-    for (auto* t : job->timers) t->resolve();
+    if (job->reduced_at.done) ZK_HIP(ctx, hipEventSynchronize(job->reduced_at.done.get()));
+    else ZK_HIP(ctx, hipStreamSynchronize(job->reduced_at.stream));
+    for (auto& t : job->timers) t->resolve();
     using H = typename Host64Of<F>::type;
     auto window_sum = [&](uint32_t w) { return msm_set_sum<F>(job, w); };
     XYZZ<H> total = xyzz_inf<H>();
@@ -1358,9 +1325,9 @@ template <class F>
 int msm_finish_multi_t(zk_ctx* ctx, ZkMsmJob* job, void* outs) {
     using H = typename Host64Of<F>::type;
     using P = typename std::conditional<F::WORDS == 12, zk_g1_projective, zk_g2_projective>::type;
-    if (job->reduce_done) ZK_HIP(ctx, hipEventSynchronize(job->reduce_done));
-    else ZK_HIP(ctx, hipStreamSynchronize(job->stream));
-    for (auto* t : job->timers) t->resolve();
+    if (job->reduced_at.done) ZK_HIP(ctx, hipEventSynchronize(job->reduced_at.done.get()));
+    else ZK_HIP(ctx, hipStreamSynchronize(job->reduced_at.stream));
+    for (auto& t : job->timers) t->resolve();
     const size_t count = job->mcount, nwin = job->Wb / count;
     auto one = [&](size_t k) {
         XYZZ<H> total = xyzz_inf<H>();
@@ -1496,47 +1463,6 @@ __global__ void __launch_bounds__(64) k_diag_g1_dual(const uint32_t* __restrict_
 }
 
 }  // namespace
-
-// ---- phase timer ----
-ZkPhaseTimer::ZkPhaseTimer(zk_ctx* c, hipStream_t st) : ctx(c), stream(st ? st : c->stream) { enabled = c->profiling; }
-ZkPhaseTimer::~ZkPhaseTimer() {
-    for (auto& e : ev) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
-}
-void ZkPhaseTimer::begin(const char* name) {
-    if (!enabled) return;
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, stream);
-    ev.push_back({name, {a, b}});
-}
-void ZkPhaseTimer::end() {
-    if (!enabled || ev.empty()) return;
-    (void)hipEventRecord(ev.back().second.second, stream);
-}
-void ZkPhaseTimer::resolve() {
-    if (!enabled || resolved) return;
-    resolved = true;
-    // wait for each phase's own end event, never for the stream: the accumulate stream holds the kernels of ALL in-flight
-    // jobs, and synchronising it from the first job's finish() made the host wait for the whole proof (the host-side
-    // chains of create_proof then started after the GPU had gone idle: +1.1 ms per proof with the timers on)
-    for (auto& e : ev) {
-        float ms = 0;
-        if (hipEventSynchronize(e.second.second) == hipSuccess &&
-            hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) {
-            std::lock_guard<std::mutex> lk(ctx->mu);           // (the host halves of a group's jobs resolve side by side)
-            ctx->timers[e.first].ms += ms;
-            ctx->timers[e.first].count += 1;
-        }
-    }
-}
-
-ZkMsmJob::~ZkMsmJob() {
-    for (auto* t : timers) delete t;
-    if (accum_done) (void)hipEventDestroy(accum_done);
-    if (sort_done) (void)hipEventDestroy(sort_done);
-    if (reduce_done) (void)hipEventDestroy(reduce_done);
-}
 
 int zk_msm_prepare(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n, int slot) {
     if (bases->group == 1) return msm_prepare_t<G1Field>(ctx, job, bases, base_offset, scalars_dev, n, slot);

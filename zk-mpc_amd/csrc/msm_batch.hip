@@ -27,15 +27,18 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
     ZK_TRY(zk_prover_streams(ctx, 2));
     constexpr size_t SLOTS = 3;
     hipStream_t s_acc = ctx->acc_stream, s_sort = ctx->aux[0], s_sort2 = ctx->aux[1];
-    hipEvent_t e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    ZK_HIP(ctx, hipEventRecord(e0, ctx->stream));        // the scalars were produced on the context stream
-    ZK_HIP(ctx, hipStreamWaitEvent(s_sort, e0, 0));
-    ZK_HIP(ctx, hipStreamWaitEvent(s_acc, e0, 0));
-    ZK_HIP(ctx, hipStreamWaitEvent(s_sort2, e0, 0));
+    const hipStream_t behind[3] = {s_sort, s_acc, s_sort2};
+    ZK_TRY(zk_behind_context_stream(ctx, behind, 3));    // the scalars were produced on the context stream
     std::vector<size_t> perm(n_jobs);
     for (size_t k = 0; k < n_jobs; k++) perm[k] = k;
     std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return lens[a] > lens[b]; });
+    // Every exit from here on -- the two regular ones and any error in the middle of the enqueue loops -- leaves through this drain,
+    // which runs after the jobs are gone: what was enqueued reads the scratch slots and the caller's scalar vectors
+    struct Drain {
+        hipStream_t st[4]; int n = 0;
+        void over(std::initializer_list<hipStream_t> l) { n = 0; for (hipStream_t s : l) st[n++] = s; }      // (a branch names its streams, in order)
+        ~Drain() { for (int k = 0; k < n; k++) (void)hipStreamSynchronize(st[k]); }
+    } drain;
     std::vector<ZkMsmJob> jobs(n_jobs);
     // G1 jobs of up to 2^23 digits over tables of window multiples (the commitments of a Marlin round up to |H| = 2^18: 4 - 7 jobs) go
     // in GROUPS of up to four: sorts one behind the other, then one accumulate launch and one launch per level
@@ -49,6 +52,7 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
                     (b->pre_stride == 64) == (bases[0]->pre_stride == 64) && lens[k] * ((255 + b->c_pre - 1) / b->c_pre) <= ((size_t)1 << 23);
         }
         if (small) {
+            drain.over({s_sort, s_sort2, s_acc, ctx->stream});
             int rc = ZK_OK;
             constexpr size_t GM = 4;
             for (size_t g0 = 0; g0 < n_jobs && rc == ZK_OK; g0 += GM) {
@@ -84,7 +88,7 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
                         bool in_fit = false;
                         for (size_t f = 0; f < nfit; f++) in_fit = in_fit || fit[f] == grp[p];
                         hipStream_t ss = in_fit ? s_sort : others[nother++ % (nfit ? 3 : 4)];
-                        if (g0 && jobs[k - GM].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(ss, jobs[k - GM].reduce_done, 0));
+                        if (g0) ZK_HIP(ctx, jobs[k - GM].reduced_at.order(ss));
                         if (!in_fit) rc = zk_msm_enqueue_sort(ctx, &jobs[k], ss, nullptr);
                     }
                     if (rc == ZK_OK && nfit) rc = zk_msm_enqueue_sort_group(ctx, fit, (int)nfit, s_sort);
@@ -106,16 +110,12 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
                 for (size_t k = 0; k < n_jobs; k++) { jp[k] = &jobs[k]; op[k] = outs[perm[k]]; }
                 rc = zk_msm_finish_many(ctx, jp.data(), op.data(), (int)n_jobs);
             }
-            (void)hipStreamSynchronize(s_sort);
-            (void)hipStreamSynchronize(s_sort2);
-            (void)hipStreamSynchronize(s_acc);
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipEventDestroy(e0);
             return rc;
         }
     }
     std::vector<int> owner(n_jobs), sharer(n_jobs, -1);          // whose sort a job uses (itself unless it borrows), and who borrows a job's sort
     for (size_t k = 0; k < n_jobs; k++) owner[k] = (int)k;
+    drain.over({s_sort, s_acc, ctx->stream});
     int rc = ZK_OK;
     for (size_t k = 0; k < n_jobs && rc == ZK_OK; k++) {
         const size_t j = perm[k];
@@ -123,11 +123,10 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
         rc = zk_msm_prepare(ctx, &jobs[k], bases[j], base_offsets ? base_offsets[j] : 0, scalars_dev[j], lens[j], ZK_SLOT_G16 + (int)(k % SLOTS));
         // the slot's previous user must be through its reduce chain (k_fold reads the sort scratch, the chain the sums) before
         // this job's sort rewrites the slot; that job's accumulate kernel is then done as well
-        if (rc == ZK_OK && k >= SLOTS && jobs[k - SLOTS].reduce_done) ZK_HIP(ctx, hipStreamWaitEvent(s_sort, jobs[k - SLOTS].reduce_done, 0));
+        if (rc == ZK_OK && k >= SLOTS) ZK_HIP(ctx, jobs[k - SLOTS].reduced_at.order(s_sort));
         // ... and so must a job that borrowed that user's sort (its accumulate kernel reads the sorted entries, its k_fold the
         // segment tables of the slot)
-        if (rc == ZK_OK && k >= SLOTS && sharer[k - SLOTS] >= 0 && jobs[sharer[k - SLOTS]].reduce_done)
-            ZK_HIP(ctx, hipStreamWaitEvent(s_sort, jobs[sharer[k - SLOTS]].reduce_done, 0));
+        if (rc == ZK_OK && k >= SLOTS && sharer[k - SLOTS] >= 0) ZK_HIP(ctx, jobs[sharer[k - SLOTS]].reduced_at.order(s_sort));
         // the same scalar vector as the previous job of the batch (a degree-bounded oracle's commitment and its shifted copy):
         // one sort for both
         const ZkMsmJob* share = nullptr;
@@ -145,10 +144,6 @@ extern "C" int zk_msm_batch_dev(zk_ctx* ctx, size_t n_jobs, const zk_bases* cons
         if (rc == ZK_OK) rc = zk_msm_enqueue_reduce(ctx, &jobs[k], ctx->stream);
     }
     for (size_t k = 0; k < n_jobs && rc == ZK_OK; k++) rc = zk_msm_finish(ctx, &jobs[k], outs[perm[k]]);
-    (void)hipStreamSynchronize(s_sort);
-    (void)hipStreamSynchronize(s_acc);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipEventDestroy(e0);
     return rc;
     ZK_API_END
 }
@@ -174,13 +169,8 @@ int zk_msm_early_begin(zk_ctx* ctx, int count, const zk_bases* bases, const size
     zk_msm_spec_drop(ctx);                                   // (msm_host.hip's speculative jobs use the same scratch slots and pinned buffers)
     ZK_TRY(zk_prover_streams(ctx, 1));
     hipStream_t s_acc = ctx->acc_stream, s_sort = ctx->aux[0];
-    hipEvent_t e0;
-    ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(e0, ctx->stream);          // the coefficients were produced on the context stream
-    if (e == hipSuccess) e = hipStreamWaitEvent(s_sort, e0, 0);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s_acc, e0, 0);
-    (void)hipEventDestroy(e0);
-    ZK_HIP(ctx, e);
+    const hipStream_t behind[2] = {s_sort, s_acc};
+    ZK_TRY(zk_behind_context_stream(ctx, behind, 2));        // the coefficients were produced on the context stream
     std::unique_ptr<ZkEarlyMsm> em(new ZkEarlyMsm());
     em->count = count;
     int rc = ZK_OK;

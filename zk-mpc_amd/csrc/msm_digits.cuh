@@ -52,6 +52,16 @@ ZK_HD uint32_t level_bucket(uint32_t mag, const LevelMap& lm, uint32_t& eoff) {
 
 }  // namespace zk
 
+// ---- what a sort hands to the accumulate kernels and the fold kernels (msm.hip, msm_g2pair.hip) ----
+// A bucket with cnt points is cut into max(1, ceil(cnt / SEG)) segments.  Single-segment buckets
+// write their sum straight to sums[key]; the segments of a split ("heavy") bucket write partial
+// sums to sums[n_keys + ...] and k_fold adds them up.  SEG is ~4x the mean bucket size, so
+// for uniformly random scalars no bucket is split; splitting is what keeps 0/1-heavy witness
+// vectors, repeated scalars and a nearly empty top window from serialising on one thread.
+struct SegDesc { uint32_t start, len, dst; };
+// parent: HEAVY_NONE, or -- for the group of a bucket that is folded in two levels -- the index of its second-level entry
+struct HeavyDesc { uint32_t key, first, nseg, parent; };
+
 // What msm_sort.hip::zk_msm_group needs to know about one MSM: the scalars, the window plan, how a digit becomes a bucket id and a
 // table entry, and where the results go.
 struct ZkGroupArgs {

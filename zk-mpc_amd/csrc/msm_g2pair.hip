@@ -29,8 +29,6 @@ using namespace zk;
 
 namespace {
 
-struct SegDesc { uint32_t start, len, dst; };   // msm.hip
-
 using B = FqField;
 constexpr int L = FqParams::L;
 constexpr int FW = FqParams::W;   // packed words per Fq: 12
@@ -311,7 +309,6 @@ __device__ __forceinline__ XP lds_get_pair(const uint32_t* lds, uint32_t tid) {
     return xyzz_load<FP>(w);
 }
 
-struct HeavyDesc { uint32_t key, first, nseg, parent; };   // msm.hip
 constexpr uint32_t HEAVY_NONE = 0xffffffffu;
 constexpr uint32_t FOLD_LIGHT = 8;
 
@@ -500,24 +497,24 @@ __global__ void __launch_bounds__(64) k_diag_fq2_pair(const uint32_t* __restrict
 }  // namespace
 
 // One pair of lanes per segment: `segments` logical threads.
-void zk_launch_accum_g2pair(hipStream_t st, size_t segments, const uint32_t* bases, const uint32_t* sorted, const void* desc,
+void zk_launch_accum_g2pair(hipStream_t st, size_t segments, const uint32_t* bases, const uint32_t* sorted, const SegDesc* desc,
                             const uint32_t* order, const uint32_t* ctr, uint32_t* sums, bool quads) {
     if (quads) {
         const unsigned blocks = (unsigned)((segments + 63) / 64);
-        hipLaunchKernelGGL(k_accum_g2pair<4>, blocks, 256, 0, st, bases, sorted, (const SegDesc*)desc, order, ctr, sums);
+        hipLaunchKernelGGL(k_accum_g2pair<4>, blocks, 256, 0, st, bases, sorted, desc, order, ctr, sums);
         return;
     }
     const unsigned blocks = (unsigned)((segments + 127) / 128);
-    hipLaunchKernelGGL(k_accum_g2pair<2>, blocks, 256, 0, st, bases, sorted, (const SegDesc*)desc, order, ctr, sums);
+    hipLaunchKernelGGL(k_accum_g2pair<2>, blocks, 256, 0, st, bases, sorted, desc, order, ctr, sums);
 }
 
 // The G2 reduce chain of msm.hip::msm_enqueue_reduce_t, same buffers and geometry, on lane pairs.
 int zk_launch_reduce_g2pair(zk_ctx* ctx, hipStream_t st, const ZkG2PairReduce& a) {
     if (a.quads)
-        hipLaunchKernelGGL(k_fold_g2pair<4>, 2 * a.light_blocks + a.heavy_blocks, 64, 64 * 4 * FW * 4, st, (const HeavyDesc*)a.heavy, (const HeavyDesc*)a.heavy2,
+        hipLaunchKernelGGL(k_fold_g2pair<4>, 2 * a.light_blocks + a.heavy_blocks, 64, 64 * 4 * FW * 4, st, a.heavy, a.heavy2,
                            a.ctr, a.done, a.sums, 2 * a.light_blocks);
     else
-        hipLaunchKernelGGL(k_fold_g2pair<2>, a.light_blocks + a.heavy_blocks, 64, 64 * 4 * FW * 4, st, (const HeavyDesc*)a.heavy, (const HeavyDesc*)a.heavy2,
+        hipLaunchKernelGGL(k_fold_g2pair<2>, a.light_blocks + a.heavy_blocks, 64, 64 * 4 * FW * 4, st, a.heavy, a.heavy2,
                            a.ctr, a.done, a.sums, a.light_blocks);
     if (((size_t)a.n_win << a.log_nb) <= RED_QUAD_MAX_BUCKETS) {
         const GridGeom gg = make_grid_geom(a.log_nb, a.n_win, RedG2Quad::PTS);

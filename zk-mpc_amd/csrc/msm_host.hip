@@ -85,12 +85,7 @@ struct ZkMsmSpec {
         hipStream_t side;
         ZK_TRY(zk_side_stream(ctx, &side));
         ZK_HIP(ctx, hipMemcpyAsync(copy, scalars, n_ * 32, hipMemcpyDeviceToDevice, ctx->stream));
-        hipEvent_t e0;
-        ZK_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(e0, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(side, e0, 0);
-        (void)hipEventDestroy(e0);
-        ZK_HIP(ctx, e);
+        ZK_HIP(ctx, zk_streams_follow(ctx->stream, &side, 1));
         int rc = ZK_OK;
         for (int k = 0; k < cnt && rc == ZK_OK; k++) {
             std::unique_ptr<Job> j(new Job());
