@@ -209,12 +209,36 @@ int zk_bases_download_g2(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n
  * (ec/src/models/short_weierstrass_jacobian.rs:847-883); n points back to back, no length prefix. */
 size_t zk_point_serialized_size(int group, int compressed);      /* 48 / 96 (G1), 96 / 192 (G2) */
 int zk_bases_serialize(zk_ctx* ctx, const zk_bases* b, size_t offset, size_t n, int compressed, uint8_t* out_host);
-/* GroupAffine::deserialize_unchecked (:930-942) on n uncompressed points, plus an on-curve check (error instead of
+/* THE RULE every entry point that reads a point's bytes holds them to (these loaders, zk_pk_deserialize, zk_kzg_srs_deserialize,
+ * their checked forms, the Groth16 and Marlin verifiers, zk_points_deserialize_host): one byte string per point.
+ *  1. Every base-field element on the wire is below q, whatever the flags say (Fp::read -> from_repr -> is_valid,
+ *     ff/src/fields/macros.rs:464-474, 573-578); on G2, c0 and c1 each.                                       -> NONCANONICAL
+ *  2. Flag bits exist only in the last byte of the last element; bit 7 of any other element's last byte must be 0 (the reference
+ *     reads those with EmptyFlags), and its bit 6 already makes the value at least q.                                -> FLAGS
+ *  3. Both flags at once (0xC0) are invalid (SWFlags::from_u8, serialize/src/flags.rs:125-136).                      -> FLAGS
+ *  4. The infinity flag stands over exactly what the serializer writes: x = 0 compressed, (0, 1) uncompressed.       -> FLAGS
+ *     The one place where the rule is stricter than the reference, whose GroupAffine::deserialize
+ *     (short_weierstrass_jacobian.rs:915-919) drops a valid x under the flag; it is what the Marlin verifier already asked.
+ *  5. Uncompressed: the sign flag is refused (FLAGS), and (x, y) satisfies y^2 = x^3 + b.                            -> CURVE
+ *  6. Compressed: x^3 + b is a square (CURVE), and y is the root whose "greater than its negative" bit (Fq: y > q - y; Fq2: on c1,
+ *     on c0 when c1 = 0) equals the sign flag.  y = 0 has the bit 0 and, as in get_point_from_x, is y under either flag.
+ * A point that breaks several rules has the status of the first in the order NONCANONICAL, FLAGS, CURVE.
+ * A loader fails with ZK_ERR_ARG and zk_last_error names the rule ("not below q", "flag bits", "not on the curve"); a verifier answers
+ * ok = 0 for that proof with ZK_OK, as for a point off the curve. */
+#define ZK_POINT_OK 0
+#define ZK_POINT_NONCANONICAL 1
+#define ZK_POINT_FLAGS 2
+#define ZK_POINT_CURVE 3
+/* GroupAffine::deserialize_unchecked (:930-942) on n uncompressed points, held to the rule above (error instead of
  * a silently wrong table); no subgroup check (zk_bases_deserialize_checked makes one). */
 int zk_bases_deserialize_uncompressed(zk_ctx* ctx, int group, const uint8_t* bytes_host, size_t n, zk_bases** out);
 /* GroupAffine::deserialize (:888-905) on n compressed points: y from x by a square root in Fq / Fq2 (get_point_from_x,
- * :110-125), sign from the flag; error if an x is not on the curve; no subgroup check (zk_bases_deserialize_checked makes one). */
+ * :110-125), sign from the flag; error for bytes the rule above refuses; no subgroup check (zk_bases_deserialize_checked makes one). */
 int zk_bases_deserialize_compressed(zk_ctx* ctx, int group, const uint8_t* bytes_host, size_t n, zk_bases** out);
+/* The same two decoders compiled for the host (no device, no context): n points of group 1 / 2 in the compressed (!= 0) or the
+ * uncompressed form -> status[i] = ZK_POINT_*, out_affine[i] = the point as zk_g1_affine / zk_g2_affine (all zero: infinity, and
+ * whenever status[i] != ZK_POINT_OK).  ZK_ERR_ARG: a group other than 1 or 2, a null pointer with n > 0. */
+int zk_points_deserialize_host(int group, int compressed, const uint8_t* bytes, size_t n, void* out_affine, uint8_t* status);
 
 /* ---- subgroup membership (is_in_correct_subgroup_assuming_on_curve, short_weierstrass_jacobian.rs:146-149: r P == O) ----
  * The reference makes this test on every point it deserialises (GroupAffine::deserialize / deserialize_uncompressed, :888-940).  Here

@@ -234,6 +234,7 @@ PROTOTYPES = {
     "zk_bases_serialize": (_I, [_P, _P, _SZ, _SZ, _I, _P]),
     "zk_bases_deserialize_uncompressed": (_I, [_P, _I, _P, _SZ, C.POINTER(_P)]),
     "zk_bases_deserialize_compressed": (_I, [_P, _I, _P, _SZ, C.POINTER(_P)]),
+    "zk_points_deserialize_host": (_I, [_I, _I, _P, _SZ, _P, _P]),
     "zk_msm_batch_dev": (_I, [_P, _SZ, _P, _P, _P, _P, _P]),
     "zk_vk_serialized_size": (_SZ, [_P, _I]),
     "zk_pk_serialized_size": (_SZ, [_P, _I]),

@@ -1158,6 +1158,22 @@ def in_subgroup_host(points, group: int) -> np.ndarray:
     return out[:pts.shape[0]]
 
 
+POINT_OK, POINT_NONCANONICAL, POINT_FLAGS, POINT_CURVE = 0, 1, 2, 3      # ZK_POINT_*: the first rule a point's bytes break
+
+
+def points_deserialize_host(data: bytes, n: int, group: int, compressed: bool):
+    """zk_points_deserialize_host: the loaders' two decoders on the host.  -> (points (n, 12) / (n, 24) uint64 in the ABI's form, all
+    zero for infinity and for a refused point; status (n,) uint8 of POINT_*)."""
+    lib = _lib.load()
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
+    assert buf.size == n * lib.zk_point_serialized_size(group, int(bool(compressed)))
+    pts = np.zeros((max(n, 1), 12 if group == 1 else 24), dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    _ck_host(lib.zk_points_deserialize_host(group, int(bool(compressed)), _ptr(buf) if n else None, n, _ptr(pts), _ptr(status)),
+             "zk_points_deserialize_host")
+    return pts[:n], status[:n]
+
+
 def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes, check_subgroup: bool = False) -> bool:
     """Groth16::verify of one proof through the host arithmetic, on a host view of the VerifyingKey (points as uint64 arrays in the
     ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery.  check_subgroup: A, B, C also pass

@@ -10,6 +10,7 @@
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "internal.hpp"
+#include "hostgroup.hpp"
 #include <string.h>
 
 using namespace zk;
@@ -57,6 +58,39 @@ template <> __host__ __device__ Fq curve_b<G1Field>() { return fp_one<FqParams>(
 template <> __host__ __device__ Fq2 curve_b<G2Field>() { return Fq2{fp_zero<FqParams>(), fp_const<FqParams>(FqParams::G2_B_C1)}; }
 
 constexpr uint32_t FLAG_POSITIVE = 1u << 31, FLAG_INFINITY = 1u << 30;   // bits 7 / 6 of the last byte
+constexpr uint32_t FLAG_BOTH = FLAG_POSITIVE | FLAG_INFINITY;
+
+// ---- the rule for a point's bytes (include/zkmpc_hip.h states it in full): what the first violation is, in this order ----
+enum PointStatus : uint32_t { PT_OK = ZK_POINT_OK, PT_NONCANONICAL = ZK_POINT_NONCANONICAL, PT_FLAGS = ZK_POINT_FLAGS, PT_CURVE = ZK_POINT_CURVE };
+
+// The 384-bit value of one element with `value_mask` on its last word is below q.  fp_unpack keeps bits 0..376 only, so the bits
+// above are looked at here; the rest is one borrow chain over the 13 limbs.
+__host__ __device__ __forceinline__ bool fq_words_below_q(const uint32_t* w, uint32_t value_mask) {
+    if ((w[11] & value_mask) >> 25) return false;
+    const Fq c = fp_unpack<FqParams>(w);
+    int32_t borrow = 0;
+#pragma unroll
+    for (int k = 0; k < FqParams::L; k++) borrow = ((int32_t)c.l[k] - (int32_t)FqParams::P[k] + borrow) >> 29;
+    return borrow < 0;
+}
+// NE elements of 12 words: every value below q (rule 1); bit 7 of an element that is not the last is a flag with no place
+// (rule 2: its bit 6 already made the value at least q)
+template <int NE>
+__host__ __device__ __forceinline__ uint32_t elements_status(const uint32_t* w) {
+    bool below = true, clean = true;
+#pragma unroll
+    for (int e = 0; e < NE; e++) {
+        const bool last = e == NE - 1;
+        below = below && fq_words_below_q(w + 12 * e, last ? ~FLAG_BOTH : ~FLAG_POSITIVE);
+        clean = clean && (last || !(w[12 * e + 11] & FLAG_POSITIVE));
+    }
+    return !below ? PT_NONCANONICAL : !clean ? PT_FLAGS : PT_OK;
+}
+__host__ __device__ __forceinline__ bool words_are(const uint32_t* w, int n, uint32_t first) {
+    bool same = w[0] == first;
+    for (int k = 1; k < n; k++) same = same && w[k] == 0;
+    return same;
+}
 
 template <class F, bool COMPRESSED>
 __global__ void __launch_bounds__(256) k_serialize(const uint32_t* bases, size_t n, uint32_t* out) {
@@ -83,27 +117,45 @@ __global__ void __launch_bounds__(256) k_serialize(const uint32_t* bases, size_t
     }
 }
 
+// Uncompressed points (GroupAffine::deserialize_unchecked, :930-942, held to the rule): x | y with the flags in y's last byte.
+// One point from its 2 FW words; its status, and the point at infinity unless the status is PT_OK.
+template <class F>
+__host__ __device__ uint32_t uncompressed_point(const uint32_t* in, Affine<F>* out) {
+    constexpr int FW = Ser<F>::FW;
+    uint32_t w[2 * FW];
+#pragma unroll
+    for (int k = 0; k < 2 * FW; k++) w[k] = in[k];
+    const uint32_t flags = w[2 * FW - 1] & FLAG_BOTH;
+    w[2 * FW - 1] &= ~FLAG_BOTH;
+    Affine<F> p;
+    p.x = F::zero();
+    p.y = F::zero();
+    uint32_t st = elements_status<2 * FW / 12>(in);
+    if (st == PT_OK && (flags & FLAG_POSITIVE)) st = PT_FLAGS;   // the uncompressed form never carries the sign flag
+    if (st == PT_OK && (flags & FLAG_INFINITY)) {
+        if (!words_are(w, FW, 0) || !words_are(w + FW, FW, 1)) st = PT_FLAGS;   // GroupAffine::zero() = (0, 1, infinity), nothing else
+    } else if (st == PT_OK) {
+        p.x = Ser<F>::from_words(w);
+        p.y = Ser<F>::from_words(w + FW);
+        // y^2 = x^3 + b, so that garbage is not silently taken for a point (deserialize_unchecked itself does not check)
+        typename F::T lhs = F::sqr(p.y), rhs = F::add(F::mul(F::sqr(p.x), p.x), curve_b<F>());
+        if (!F::eq(lhs, rhs)) {
+            st = PT_CURVE;
+            p.x = F::zero();
+            p.y = F::zero();
+        }
+    }
+    *out = p;
+    return st;
+}
+// bad: one word for the whole table, bit (status - 1) for every status that occurred
 template <class F>
 __global__ void __launch_bounds__(256) k_deserialize_uncompressed(const uint32_t* in, size_t n, uint32_t* bases, uint32_t* bad) {
     constexpr int FW = Ser<F>::FW;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        uint32_t w[2 * FW];
-#pragma unroll
-        for (int k = 0; k < 2 * FW; k++) w[k] = in[i * 2 * FW + k];
-        uint32_t flags = w[2 * FW - 1] & (FLAG_POSITIVE | FLAG_INFINITY);
-        w[2 * FW - 1] &= ~(FLAG_POSITIVE | FLAG_INFINITY);
         Affine<F> p;
-        if (flags & FLAG_INFINITY) {
-            p.x = F::zero();
-            p.y = F::zero();
-        } else {
-            p.x = Ser<F>::from_words(w);
-            p.y = Ser<F>::from_words(w + FW);
-            // y^2 = x^3 + b, so that garbage is not silently taken for a point (deserialize_unchecked itself does not check)
-            typename F::T lhs = F::sqr(p.y), rhs = F::add(F::mul(F::sqr(p.x), p.x), curve_b<F>());
-            if (!F::eq(lhs, rhs)) atomicOr(bad, 1u);
-        }
-        if (flags & FLAG_POSITIVE) atomicOr(bad, 2u);          // the uncompressed form never carries the sign flag
+        const uint32_t st = uncompressed_point<F>(in + i * 2 * FW, &p);
+        if (st != PT_OK) atomicOr(bad, 1u << (st - 1));
         aff_store16<F>(bases, i, p);
     }
 }
@@ -167,42 +219,46 @@ __host__ __device__ __forceinline__ bool field_sqrt(const Fq& a, Fq* out) { retu
 __host__ __device__ __forceinline__ bool field_sqrt(const Fq2& a, Fq2* out) { return fq2_sqrt(a, out); }
 
 // Compressed points (GroupAffine::deserialize, :888-905 without the subgroup check): x with the flags in its last byte.
-// One point from its FW words; false (and the point at infinity) if x is not the abscissa of a curve point.
+// One point from its FW words; its status, and the point at infinity unless the status is PT_OK.
 template <class F>
-__host__ __device__ bool decompress_point(const uint32_t* in, Affine<F>* out) {
+__host__ __device__ uint32_t decompress_point(const uint32_t* in, Affine<F>* out) {
     constexpr int FW = Ser<F>::FW;
     uint32_t w[FW];
 #pragma unroll
     for (int k = 0; k < FW; k++) w[k] = in[k];
-    const uint32_t flags = w[FW - 1] & (FLAG_POSITIVE | FLAG_INFINITY);
-    w[FW - 1] &= ~(FLAG_POSITIVE | FLAG_INFINITY);
+    const uint32_t flags = w[FW - 1] & FLAG_BOTH;
+    w[FW - 1] &= ~FLAG_BOTH;
     Affine<F> p;
     p.x = F::zero();
     p.y = F::zero();
-    bool good = true;
-    if (!(flags & FLAG_INFINITY)) {
+    uint32_t st = elements_status<FW / 12>(in);
+    if (st == PT_OK && flags == FLAG_BOTH) st = PT_FLAGS;          // SWFlags::from_u8: UnexpectedFlags
+    if (st == PT_OK && (flags & FLAG_INFINITY)) {
+        if (!words_are(w, FW, 0)) st = PT_FLAGS;                    // the serializer writes x = 0 under the flag, nothing else
+    } else if (st == PT_OK) {
         p.x = Ser<F>::from_words(w);
         typename F::T y, rhs = F::add(F::mul(F::sqr(p.x), p.x), curve_b<F>());
         if (!field_sqrt(rhs, &y)) {
-            good = false;
+            st = PT_CURVE;
             p.x = F::zero();
         } else {
             const bool positive = (flags & FLAG_POSITIVE) != 0;
-            p.y = (Ser<F>::gt_neg(y) != positive) ? F::neg(y) : y;
+            p.y = (Ser<F>::gt_neg(y) != positive) ? F::neg(y) : y;   // y = 0 under either flag, as get_point_from_x has it
         }
     }
     *out = p;
-    return good;
+    return st;
 }
-// bad: one word for the whole table; bad_each (optional): one word per point, for callers that answer per point
+// bad: one word for the whole table, bit (status - 1) for every status that occurred; bad_each (optional): one word per point,
+// non-zero for a refused one, for callers that answer per point
 template <class F>
 __global__ void __launch_bounds__(64) k_deserialize_compressed(const uint32_t* in, size_t n, uint32_t* bases, uint32_t* bad, uint32_t* bad_each) {
     constexpr int FW = Ser<F>::FW;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         Affine<F> p;
-        const bool good = decompress_point<F>(in + i * FW, &p);
-        if (!good) atomicOr(bad, 1u);
-        if (bad_each) bad_each[i] = good ? 0u : 1u;
+        const uint32_t st = decompress_point<F>(in + i * FW, &p);
+        if (st != PT_OK) atomicOr(bad, 1u << (st - 1));
+        if (bad_each) bad_each[i] = st != PT_OK ? 1u : 0u;
         aff_store16<F>(bases, i, p);
     }
 }
@@ -248,8 +304,11 @@ int deserialize_t(zk_ctx* ctx, int group, const uint8_t* bytes, size_t n, int co
         if (h) {
             (void)hipFree(b->dev);
             delete b;
-            ZK_FAIL(ctx, ZK_ERR_ARG, h & 1 ? "zk_bases_deserialize_uncompressed: a point is not on the curve (SerializationError::InvalidData)"
-                                           : "zk_bases_deserialize_uncompressed: unexpected flag bits");
+            const std::string who = compressed ? "zk_bases_deserialize_compressed: " : "zk_bases_deserialize_uncompressed: ";
+            const uint32_t nc = 1u << (PT_NONCANONICAL - 1), fl = 1u << (PT_FLAGS - 1);
+            ZK_FAIL(ctx, ZK_ERR_ARG, who + (h & nc   ? "a field element is not below q (SerializationError::InvalidData)"
+                                            : h & fl ? "unexpected flag bits (SerializationError::UnexpectedFlags)"
+                                                     : "a point is not on the curve (SerializationError::InvalidData)"));
         }
     }
     *out = b;
@@ -270,12 +329,36 @@ int zk_decompress_launch(zk_ctx* ctx, int group, const uint32_t* in_dev, size_t 
 bool zk_host_decompress_g1(const uint8_t in[48], Affine<G1Field>* out) {
     uint32_t w[12];
     memcpy(w, in, 48);
-    return decompress_point<G1Field>(w, out);
+    return decompress_point<G1Field>(w, out) == PT_OK;
 }
 bool zk_host_decompress_g2(const uint8_t in[96], Affine<G2Field>* out) {
     uint32_t w[24];
     memcpy(w, in, 96);
-    return decompress_point<G2Field>(w, out);
+    return decompress_point<G2Field>(w, out) == PT_OK;
+}
+
+namespace {
+template <class F>
+void points_deserialize_host_t(int compressed, const uint8_t* bytes, size_t n, void* out_affine, uint8_t* status) {
+    constexpr int FW = Ser<F>::FW;
+    const size_t per = (size_t)FW * (compressed ? 1 : 2);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w[2 * FW];
+        memcpy(w, bytes + i * per * 4, per * 4);
+        Affine<F> p;
+        status[i] = (uint8_t)(compressed ? decompress_point<F>(w, &p) : uncompressed_point<F>(w, &p));
+        host_aff_to_abi<F>((uint64_t*)out_affine + i * F::WORDS, p);
+    }
+}
+}  // namespace
+
+extern "C" int zk_points_deserialize_host(int group, int compressed, const uint8_t* bytes, size_t n, void* out_affine, uint8_t* status) {
+    ZK_API_BEGIN_NOCTX
+    if ((group != 1 && group != 2) || (n && (!bytes || !out_affine || !status))) return ZK_ERR_ARG;
+    if (group == 2) points_deserialize_host_t<G2Field>(compressed, bytes, n, out_affine, status);
+    else points_deserialize_host_t<G1Field>(compressed, bytes, n, out_affine, status);
+    return ZK_OK;
+    ZK_API_END
 }
 
 extern "C" size_t zk_point_serialized_size(int group, int compressed) {
