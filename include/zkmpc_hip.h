@@ -940,6 +940,16 @@ int zk_diag_g1_ntt_host(const zk_g1_affine* points, uint32_t log_n, size_t count
  * joint chain) -- what the host tail of a Groth16 proof runs for keys made by zk_groth16_setup.  Equal to zk_g1_mul for every point of
  * the prime-order subgroup; kept apart from it because ProjectiveCurve::mul (zk_g1_mul) is defined on the whole curve. */
 int zk_diag_g1_mul_glv(const zk_g1_projective* a, const zk_fr* k, zk_g1_projective* out);
+/* Test hook: one small open of the collaborative provers (csrc/sharednet.hpp) as party `self` sees it, on the host and through the
+ * codec alone -- no context, no device, no transport.  A message is nf scalars, n1 G1 and n2 G2 points in ABI form back to back
+ * (4 / 18 / 36 words); shares[lane][party] are the messages' items: lane 0 the shares, whose messages are concatenated and summed
+ * into `opened` (one message); lanes = 2: lane 1 the MAC shares, from which every party's [leader ? opened : 0] - mac is formed,
+ * concatenated and summed.  What a peer's slot holds is validated (scalars below r; points canonical, Z = 0 or 1, on the curve and,
+ * with `subgroup`, in the prime-order subgroup), the slot of `self` is not.  *verdict: ZK_OK, ZK_ERR_STATE (a peer's payload was
+ * refused; `opened` is not written) or ZK_ERR_MAC (a delta sum did not vanish).  Returns ZK_ERR_ARG for a null pointer, no items,
+ * self outside the parties or lanes outside 1 .. 2. */
+int zk_diag_small_open_host(int parties, int self, int lanes, int subgroup, size_t nf, size_t n1, size_t n2, const uint64_t* shares,
+                            uint64_t* opened, int* verdict);
 
 #ifdef __cplusplus
 }

@@ -203,6 +203,51 @@ def test_collaborative_prove_spdz(n_parties, n):
     assert all(c for _, c in res)
 
 
+@pytest.mark.parametrize("which", ["r", "s"])
+def test_spdz_fused_open_catches_a_moved_mac_share_of_r_or_s(which):
+    """The MAC check of the fused small open (s + y, r + y, r delta, A, B1, B2 in one exchange): the last party's MAC share of r
+    (or s) is off by one.  The vector opens of the Beaver product do not see r or s, so this is the check that has to fail: in
+    the one-call entry and in the Python sequence, for every party.  The untampered call right after, on the same contexts,
+    returns the predicted proof."""
+    n_parties, n = 2, 6
+    rng = O.Prng(2600 + ord(which))
+    w0, w1 = rng.fr(), rng.fr()
+    r1cs, z = O.mul_chain_r1cs(n, w0, w1)
+    td = O.Trapdoor(rng.fr(), rng.fr(), rng.fr(), rng.fr(), rng.fr(), rng.fr(), rng.fr())
+    r, s = rng.fr(), rng.fr()
+    zs = additive_shares(z, n_parties, rng, public_prefix=2)
+    zm = additive_shares(z, n_parties, rng, public_prefix=2)
+    rsh, ssh = O.additive_share(r, n_parties, rng), O.additive_share(s, n_parties, rng)
+    rm, sm = O.additive_share(r, n_parties, rng), O.additive_share(s, n_parties, rng)
+    tdm = td_mont(td)
+
+    def fn(p, ctx, net):
+        party = mpc.SpdzParty(ctx, net=net)
+        dr = ctx.r1cs_mul_chain(n)
+        pk = ctx.groth16_setup(dr, *[tdm[i] for i in range(7)])
+        dzs, dzm = ctx.upload(cv.fr_to_mont(zs[p])), ctx.upload(cv.fr_to_mont(zm[p]))
+        lanes = (dzs.ptr, dzm.ptr)
+        rr, ss = (mont1(rsh[p]), mont1(rm[p])), (mont1(ssh[p]), mont1(sm[p]))
+        off = int(p == n_parties - 1)
+        bad_r = (rr[0], mont1((rm[p] + off) % O.R_MOD)) if which == "r" else rr
+        bad_s = (ss[0], mont1((sm[p] + off) % O.R_MOD)) if which == "s" else ss
+        caught = []
+        for call in (party.create_proof_shared_spdz_native, party.create_proof_shared_spdz):
+            try:
+                call(pk, dr, lanes, bad_r, bad_s)
+                caught.append(False)
+            except mpc.MacCheckError as e:
+                caught.append("vector open" not in str(e))          # not the Beaver product's check: that one never sees r or s
+        return caught, party.create_proof_shared_spdz_native(pk, dr, lanes, rr, ss)
+
+    res = run_parties(n_parties, fn)
+    assert all(caught == [True, True] for caught, _ in res)
+    cr = OC.R1cs(2, n + 1, *OC.mul_chain_csr(n))
+    zmnt = cv.fr_to_mont(z)
+    want = OC.groth16_predict(cr, tdm, zmnt, OC.witness_map(cr, zmnt), mont1(r), mont1(s))
+    assert all(len(proof) == 192 and proof == want for _, proof in res)
+
+
 def test_distnet_nccl_single_rank():
     """The bench's N>1 plumbing (torch.distributed/nccl transport over device tensors, share generation on the
     device) exercised with a 1-rank process group: the 1-party "collaborative" proof must equal the local one."""

@@ -328,6 +328,7 @@ PROTOTYPES = {
     "zk_marlin_pad_assignment_dev": (_I, [_P, _P, _P, _P]),
     "zk_marlin_vk_from_index": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "zk_diag_marlin_shape_host": (_I, [_P, _I, _P, _P, _P, _SZ, _P]),
+    "zk_diag_small_open_host": (_I, [_I, _I, _I, _I, _SZ, _SZ, _SZ, _P, _P, C.POINTER(_I)]),
 }
 
 _lib = None

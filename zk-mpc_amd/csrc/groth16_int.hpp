@@ -228,14 +228,10 @@ class ZkProofTail {
 
 // ---- the ABI's affine structs (x | y in the reference's Montgomery words) as host-field points; a coordinate word is valid below q ----
 inline zk::Affine<zk::Fq64Field> zk_host_g1(const zk_g1_affine* p) {
-    uint32_t w[24];
-    memcpy(w, p, 96);
-    return zk::Affine<zk::Fq64Field>{zk::Fq64Field::load(w), zk::Fq64Field::load(w + 12)};
+    return zk::Affine<zk::Fq64Field>{zk::host64_coord<zk::Fq64Field>(p->x.l), zk::host64_coord<zk::Fq64Field>(p->y.l)};
 }
 inline zk::Affine<zk::Fq264Field> zk_host_g2(const zk_g2_affine* p) {
-    uint32_t w[48];
-    memcpy(w, p, 192);
-    return zk::Affine<zk::Fq264Field>{zk::Fq264Field::load(w), zk::Fq264Field::load(w + 24)};
+    return zk::Affine<zk::Fq264Field>{zk::host64_coord<zk::Fq264Field>((const uint64_t*)p->x), zk::host64_coord<zk::Fq264Field>((const uint64_t*)p->y)};
 }
 inline bool zk_words_below_q(const uint64_t* l, int n_fq) {
     for (int i = 0; i < n_fq; i++)

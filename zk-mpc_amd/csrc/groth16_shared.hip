@@ -7,82 +7,11 @@ using namespace zk;
 
 // ---- the collaborative prover as ONE entry point ---------------------------------------------------------------------------------
 // create_proof::<MpcPairingEngine, C> over additive shares (src/groth16.rs:68-183): what mpc.py::Party.create_proof_shared
-// sequences from ~40 calls, for a host that cannot call Python.  The transport is the caller's (zk_net_vtable: the reference's
-// MpcNet::broadcast_bytes on its TCP mesh, mpc-net/src/lib.rs:60-64) for the small opens; the two vector opens of the Beaver
-// product go through the vtable's open_sum_fr_dev or, when that is NULL, through the context's own RCCL communicator
-// (zk_open_sum_fr_dev).  Opens happen in the fused order of create_proof_shared: the nine small opens of the three
-// GroupShare::scale calls (share/group.rs:72-111, DummyGroupTripleSource) and of Proof::reveal travel in two exchanges; every
-// opened value is the reference's, and so are the 192 bytes.
-namespace {
-
-__global__ void __launch_bounds__(256) k_vec_add_const(const void* a, FrK k, void* out, size_t n) {
-    const Fr kk = frk(k);
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        fr_store(out, i, fr_add(fr_load(a, i), kk));
-}
-
-__global__ void __launch_bounds__(256) k_vec_neg(const void* a, void* out, size_t n) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        fr_store(out, i, fr_sub(fp_zero<FrParams>(), fr_load(a, i)));
-}
-
-}  // namespace
-
-int zk_shared_spdz_open_vec(ZkSharedNet& nt, const void* sh, const void* mac, size_t n, void* out, void* dx) {
-    zk_ctx* ctx = nt.ctx;
-    ZK_TRY(nt.open_vec(sh, n, out));
-    if (ctx->party_id == 0) {
-        ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_SUB, out, mac, dx, n));
-    } else {
-        hipLaunchKernelGGL(k_vec_neg, zk_grid(n, 256), 256, 0, ctx->stream, mac, dx, n);
-        ZK_HIP(ctx, hipGetLastError());
-    }
-    ZK_TRY(nt.open_vec(dx, n, dx));
-    int zero = 0;
-    ZK_TRY(zk_fr_vec_is_zero_dev(ctx, dx, n, &zero));
-    if (!zero) ZK_FAIL(ctx, ZK_ERR_MAC, "SPDZ MAC check failed on a vector open");
-    return ZK_OK;
-}
-
-int zk_shared_beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
-                         const void* const tx[2], const void* const ty[2], const void* const tz[2], const char* tag) {
-    zk_ctx* ctx = nt.ctx;
-    const bool dummy = !tx[0] && !ty[0] && !tz[0];
-    for (int l = 0; l < lanes; l++)
-        if (dummy ? (tx[l] || ty[l] || tz[l]) : (!tx[l] || !ty[l] || !tz[l])) ZK_FAIL(ctx, ZK_ERR_ARG, "batch_mul: give a whole Beaver triple (every lane) or none");
-    void *sxl[2], *oyl[2], *sx, *oy, *dx;
-    char nm[64];
-    auto buf = [&](const char* what, int l, void** p) { snprintf(nm, sizeof nm, "%s.%s%d", tag, what, l); return zk_scratch(ctx, nm, n * 32, p); };
-    for (int l = 0; l < lanes; l++) { ZK_TRY(buf("sxl", l, &sxl[l])); ZK_TRY(buf("oyl", l, &oyl[l])); }
-    ZK_TRY(buf("sx", 0, &sx)); ZK_TRY(buf("oy", 0, &oy)); ZK_TRY(buf("dx", 0, &dx));
-    const Fr one_ext = fp_mul<FrParams>(fp_one<FrParams>(), fp_const<FrParams>(FrParams::INT_TO_EXT));
-    for (int l = 0; l < lanes; l++) {
-        if (dummy) {                                      // DummyFieldTripleSource: the leader holds 1 (in both lanes), the rest 0 (wire/field.rs:49-63)
-            if (nt.leader()) {
-                hipLaunchKernelGGL(k_vec_add_const, zk_grid(n, 256), 256, 0, ctx->stream, x[l], to_frk(one_ext), sxl[l], n);
-                hipLaunchKernelGGL(k_vec_add_const, zk_grid(n, 256), 256, 0, ctx->stream, y[l], to_frk(one_ext), oyl[l], n);
-                ZK_HIP(ctx, hipGetLastError());
-            } else {
-                ZK_HIP(ctx, hipMemcpyAsync(sxl[l], x[l], n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-                ZK_HIP(ctx, hipMemcpyAsync(oyl[l], y[l], n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-        } else {
-            ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_ADD, x[l], tx[l], sxl[l], n));
-            ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_ADD, y[l], ty[l], oyl[l], n));
-        }
-    }
-    if (lanes == 1) {
-        ZK_TRY(nt.open_vec(sxl[0], n, sx));               // open(s + x), open(o + y)
-        ZK_TRY(nt.open_vec(oyl[0], n, oy));
-    } else {
-        ZK_TRY(zk_shared_spdz_open_vec(nt, sxl[0], sxl[1], n, sx, dx));
-        ZK_TRY(zk_shared_spdz_open_vec(nt, oyl[0], oyl[1], n, oy, dx));
-    }
-    // the local tail; the shift of sx * oy lands on the leader in BOTH lanes (mac_share = 1 there)
-    for (int l = 0; l < lanes; l++) ZK_TRY(zk_beaver_combine_dev(ctx, sx, oy, tx[l], ty[l], tz[l], out[l], n));
-    return ZK_OK;
-}
-
+// sequences from ~40 calls, for a host that cannot call Python.  This file is the protocol; the transport, the Beaver product
+// with its vector opens and the small open (wire layout, validation of peers' payloads, MAC check) are sharednet.hpp's.  Opens
+// happen in the fused order of create_proof_shared: the nine small opens of the three GroupShare::scale calls
+// (share/group.rs:72-111, DummyGroupTripleSource) and of Proof::reveal travel in two small opens; every opened value is the
+// reference's, and so are the 192 bytes.
 namespace {
 
 using SH1 = Fq64Field;
@@ -96,9 +25,7 @@ template <int LANES>
 int prove_shared_impl(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void* const z[2], const zk_fr* const rs[2],
                       const zk_fr* const ss[2], const void* const tx[2], const void* const ty[2], const void* const tz[2],
                       const zk_net_vtable* net, uint8_t proof[192], uint64_t* bytes_sent) {
-    const bool dummy = !tx[0] && !ty[0] && !tz[0];
-    for (int l = 0; l < LANES; l++)
-        if (dummy ? (tx[l] || ty[l] || tz[l]) : (!tx[l] || !ty[l] || !tz[l])) ZK_FAIL(ctx, ZK_ERR_ARG, "prove_shared: give a whole Beaver triple (every lane) or none");
+    if (zk_shared_triple_given(LANES, tx, ty, tz) < 0) ZK_FAIL(ctx, ZK_ERR_ARG, "prove_shared: give a whole Beaver triple (every lane) or none");
     const bool leader = ctx->party_id == 0;
     const size_t D = (size_t)1 << r->log_d;
     ZkSharedNet nt{ctx, net};
@@ -150,65 +77,18 @@ int prove_shared_impl(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void
         g1_b[l] = xyzz_add<SH1>(xyzz_add<SH1>(xyzz_add<SH1>(f_s_g1[l].get(), pub1(pk->b0_g1)), b1_acc), pub1(pk->beta_g1));
         g2_b[l] = xyzz_add<SH2>(xyzz_add<SH2>(xyzz_add<SH2>(f_s_g2[l].get(), pub2(pk->b0_g2)), b2_acc), pub2(pk->beta_g2));
     }
-    // first exchange: open(o + y) for o = s, r (y = the leader's 1: the dummy group triple; from_add_shared: mac = share), open(s + x)
-    // for the three scaled points (x = 0) and the reveal of B.  SPDZ: a second exchange of [leader ? opened : 0] - mac, all zero.
-    constexpr size_t MW = 2 * 4 + 3 * 18 + 36;
+    // the fused open: open(o + y) for o = s, r (y = the leader's 1: the dummy group triple; from_add_shared: mac = share), open(s + x)
+    // for the three scaled points (x = 0) and the reveal of B
     const Fr y = leader ? fp_mul<FrParams>(fp_one<FrParams>(), fp_const<FrParams>(FrParams::INT_TO_EXT)) : fp_zero<FrParams>();
-    auto pack = [&](int l, uint64_t* msg) {
-        host_store_ext<FrParams>(msg, fp_add<FrParams>(host_load_ext<FrParams>(ss[l]->l), y));
-        host_store_ext<FrParams>(msg + 4, fp_add<FrParams>(host_load_ext<FrParams>(rs[l]->l), y));
-        host64_write_projective<SH1>(xyzz_to_affine<SH1>(r_g1[l]), msg + 8);
-        host64_write_projective<SH1>(xyzz_to_affine<SH1>(g_a[l]), msg + 26);
-        host64_write_projective<SH1>(xyzz_to_affine<SH1>(g1_b[l]), msg + 44);
-        host64_write_projective<SH2>(xyzz_to_affine<SH2>(g2_b[l]), msg + 62);
-    };
-    struct Opened { Fr f[2]; SX1 g[3]; SX2 B; };
-    auto sum = [&](const std::vector<uint8_t>& all, Opened& o) -> int {
-        o.f[0] = o.f[1] = fp_zero<FrParams>();
-        o.g[0] = o.g[1] = o.g[2] = xyzz_inf<SH1>();
-        o.B = xyzz_inf<SH2>();
-        for (int p = 0; p < nt.parties(); p++) {
-            uint64_t w[MW];
-            memcpy(w, all.data() + (size_t)p * sizeof w, sizeof w);
-            for (int k = 0; k < 2; k++) {
-                if (!zk_fr_words_valid(w + 4 * k)) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a non-canonical field element");
-                o.f[k] = fp_add<FrParams>(o.f[k], host_load_ext<FrParams>(w + 4 * k));
-            }
-            // points from a peer: canonical coordinates, on the curve; the malicious-security prover also checks the subgroup
-            // (GroupAffine::deserialize behind MpcSerNet::broadcast, channel.rs:12-28).  A party's own message is its own output.
-            bool pts_ok = true;
-            const bool peer = p != ctx->party_id;
-            for (int k = 0; k < 3; k++)
-                o.g[k] = xyzz_add<SH1>(o.g[k], peer ? host64_peer_point<SH1>(w + 8 + 18 * k, LANES == 2, pts_ok) : host64_proj_from_abi<SH1>(w + 8 + 18 * k));
-            o.B = xyzz_add<SH2>(o.B, peer ? host64_peer_point<SH2>(w + 62, LANES == 2, pts_ok) : host64_proj_from_abi<SH2>(w + 62));
-            if (!pts_ok) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a point that is not a valid group element");
-        }
-        return ZK_OK;
-    };
-    uint64_t msg[MW];
-    std::vector<uint8_t> all;
-    Opened op;
-    pack(0, msg);
-    ZK_TRY(nt.gather((const uint8_t*)msg, sizeof msg, all));
-    ZK_TRY(sum(all, op));
-    if (LANES == 2) {
-        // [leader ? x : 0] - mac for every opened value, published and summed: SpdzFieldShare / SpdzGroupShare batch_open's check
-        uint64_t mm[MW], dm[MW];
-        pack(1, mm);
-        for (int k = 0; k < 2; k++)
-            host_store_ext<FrParams>(dm + 4 * k, fp_sub<FrParams>(leader ? op.f[k] : fp_zero<FrParams>(), host_load_ext<FrParams>(mm + 4 * k)));
-        for (int k = 0; k < 3; k++)
-            host64_write_projective<SH1>(xyzz_to_affine<SH1>(xyzz_add<SH1>(leader ? op.g[k] : xyzz_inf<SH1>(), xyzz_neg<SH1>(host64_proj_from_abi<SH1>(mm + 8 + 18 * k)))), dm + 8 + 18 * k);
-        host64_write_projective<SH2>(xyzz_to_affine<SH2>(xyzz_add<SH2>(leader ? op.B : xyzz_inf<SH2>(), xyzz_neg<SH2>(host64_proj_from_abi<SH2>(mm + 62)))), dm + 62);
-        Opened chk;
-        ZK_TRY(nt.gather((const uint8_t*)dm, sizeof dm, all));
-        ZK_TRY(sum(all, chk));
-        bool ok = fp_is_zero<FrParams>(chk.f[0]) && fp_is_zero<FrParams>(chk.f[1]) && xyzz_is_inf<SH2>(chk.B);
-        for (int k = 0; k < 3; k++) ok = ok && xyzz_is_inf<SH1>(chk.g[k]);
-        if (!ok) ZK_FAIL(ctx, ZK_ERR_MAC, "SPDZ MAC check failed on a fused open");
-    }
-    const Fr oy_s = op.f[0], oy_r = op.f[1];
-    const SX1 sx_rd = op.g[0], sx_a = op.g[1], sx_b = op.g[2];
+    auto plus_y = [&](const zk_fr* v) { zk_fr o; host_store_ext<FrParams>(o.l, fp_add<FrParams>(host_load_ext<FrParams>(v->l), y)); return o; };
+    auto abi1 = [](const SX1& p) { zk_g1_projective o; host64_write_projective<SH1>(xyzz_to_affine<SH1>(p), (uint64_t*)&o); return o; };
+    auto abi2 = [](const SX2& p) { zk_g2_projective o; host64_write_projective<SH2>(xyzz_to_affine<SH2>(p), (uint64_t*)&o); return o; };
+    auto point1 = [](const zk_g1_projective& p) { return host64_proj_from_abi<SH1>((const uint64_t*)&p); };
+    ZkSmallItems fused[2], opened;
+    for (int l = 0; l < LANES; l++) fused[l] = {{plus_y(ss[l]), plus_y(rs[l])}, {abi1(r_g1[l]), abi1(g_a[l]), abi1(g1_b[l])}, {abi2(g2_b[l])}};
+    ZK_TRY(zk_shared_open_small(nt, LANES, fused, &opened));
+    const Fr oy_s = host_load_ext<FrParams>(opened.fr[0].l), oy_r = host_load_ext<FrParams>(opened.fr[1].l);
+    const SX1 sx_rd = point1(opened.g1[0]), sx_a = point1(opened.g1[1]), sx_b = point1(opened.g1[2]);
     // the local part of GroupShare::scale behind its two opens: z - sx*y (+ sx*oy on the leader), z = 0, y = [leader]; both SPDZ
     // lanes hold the same value (key 1)
     auto scale_finish = [&](const SX1& sxp, const Fr& oyv) {
@@ -224,33 +104,15 @@ int prove_shared_impl(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, const void
     const SX1 part2 = scale_finish(sx_b, oy_r);                          // r B1                 (:161)
     SX1 t = xyzz_add<SH1>(p1.get(), part2);
     t = xyzz_add<SH1>(t, xyzz_neg<SH1>(p0.get()));
-    SX1 g_c[2];
-    for (int l = 0; l < LANES; l++) g_c[l] = xyzz_add<SH1>(xyzz_add<SH1>(t, l_acc[l]), h_acc[l]);      // :169-174
-    uint64_t cmsg[18];
-    host64_write_projective<SH1>(xyzz_to_affine<SH1>(g_c[0]), cmsg);
-    ZK_TRY(nt.gather((const uint8_t*)cmsg, sizeof cmsg, all));          // Proof::reveal of C (A and B were opened above)
-    bool c_ok = true;
-    auto sum_g1 = [&](const std::vector<uint8_t>& v) {
-        SX1 acc = xyzz_inf<SH1>();
-        for (int p = 0; p < nt.parties(); p++) {
-            uint64_t w[18];
-            memcpy(w, v.data() + (size_t)p * sizeof w, sizeof w);
-            acc = xyzz_add<SH1>(acc, p != ctx->party_id ? host64_peer_point<SH1>(w, LANES == 2, c_ok) : host64_proj_from_abi<SH1>(w));
-        }
-        return acc;
-    };
-    const SX1 C = sum_g1(all);
-    if (!c_ok) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a point that is not a valid group element");
-    if (LANES == 2) {
-        host64_write_projective<SH1>(xyzz_to_affine<SH1>(xyzz_add<SH1>(leader ? C : xyzz_inf<SH1>(), xyzz_neg<SH1>(g_c[1]))), cmsg);
-        ZK_TRY(nt.gather((const uint8_t*)cmsg, sizeof cmsg, all));
-        const SX1 dsum = sum_g1(all);
-        if (!c_ok) ZK_FAIL(ctx, ZK_ERR_STATE, "prove_shared: a party sent a point that is not a valid group element");
-        if (!xyzz_is_inf<SH1>(dsum)) ZK_FAIL(ctx, ZK_ERR_MAC, "SPDZ MAC check failed on the reveal of C");
-    }
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<SH1>(sx_a)), proof);
-    g2_serialize(aff_from_host64<G2Field>(xyzz_to_affine<SH2>(op.B)), proof + 48);
-    g1_serialize(aff_from_host64<G1Field>(xyzz_to_affine<SH1>(C)), proof + 144);
+    ZkSmallItems c_share[2], c_opened;                                   // Proof::reveal of C (A and B were opened above)
+    for (int l = 0; l < LANES; l++) c_share[l].g1 = {abi1(xyzz_add<SH1>(xyzz_add<SH1>(t, l_acc[l]), h_acc[l]))};      // :169-174
+    ZK_TRY(zk_shared_open_small(nt, LANES, c_share, &c_opened));
+    // (opened points come normalised: zz = zzz = 1 or all zero, so x and y are the affine point)
+    const SX2 B = host64_proj_from_abi<SH2>((const uint64_t*)&opened.g2[0]);
+    const SX1 C = point1(c_opened.g1[0]);
+    g1_serialize(aff_from_host64<G1Field>(Affine<SH1>{sx_a.x, sx_a.y}), proof);
+    g2_serialize(aff_from_host64<G2Field>(Affine<SH2>{B.x, B.y}), proof + 48);
+    g1_serialize(aff_from_host64<G1Field>(Affine<SH1>{C.x, C.y}), proof + 144);
     if (bytes_sent) *bytes_sent = nt.bytes;
     return ZK_OK;
 }

@@ -30,15 +30,10 @@ int mul_t(const uint64_t* a, const zk_fr* k, uint64_t* out) {
 template <class H>
 Affine<H> aff_from_abi64(const uint64_t* p) {
     constexpr int FE = H::WORDS / 2;
-    uint32_t w[H::WORDS];
     bool zero = true;
     for (int i = 0; i < 2 * FE; i++) zero = zero && p[i] == 0;
     if (zero) return aff_inf<H>();
-    auto get = [&](const uint64_t* src) {
-        for (int i = 0; i < FE; i++) { w[2 * i] = (uint32_t)src[i]; w[2 * i + 1] = (uint32_t)(src[i] >> 32); }
-        return H::load(w);
-    };
-    return Affine<H>{get(p), get(p + FE)};
+    return Affine<H>{host64_coord<H>(p), host64_coord<H>(p + FE)};
 }
 }  // namespace
 

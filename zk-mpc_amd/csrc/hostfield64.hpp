@@ -6,6 +6,7 @@
 // running the 29-bit device representation on the host.
 #pragma once
 #include <stdint.h>
+#include <vector>
 #include "ec.cuh"
 
 namespace zk {
@@ -200,19 +201,46 @@ inline void host64_write_projective(const Affine<H>& a, uint64_t* out) {
     put(out + 2 * FE, H::one());
 }
 
+// one coordinate of a C-ABI point
+template <class H>
+inline typename H::T host64_coord(const uint64_t* src) {
+    uint32_t w[H::WORDS];
+    for (int i = 0; i < H::WORDS / 2; i++) { w[2 * i] = (uint32_t)src[i]; w[2 * i + 1] = (uint32_t)(src[i] >> 32); }
+    return H::load(w);
+}
 // C-ABI Jacobian (X,Y,Z) -> XYZZ over the host field
 template <class H>
 inline XYZZ<H> host64_proj_from_abi(const uint64_t* p) {
     constexpr int FE = H::WORDS / 2;
-    uint32_t w[H::WORDS];
-    auto get = [&](const uint64_t* src) {
-        for (int i = 0; i < FE; i++) { w[2 * i] = (uint32_t)src[i]; w[2 * i + 1] = (uint32_t)(src[i] >> 32); }
-        return H::load(w);
-    };
-    typename H::T z = get(p + 2 * FE);
+    typename H::T z = host64_coord<H>(p + 2 * FE);
     if (H::is_zero(z)) return xyzz_inf<H>();
     typename H::T zz = H::sqr(z);
-    return XYZZ<H>{get(p), get(p + FE), zz, H::mul(zz, z)};
+    return XYZZ<H>{host64_coord<H>(p), host64_coord<H>(p + FE), zz, H::mul(zz, z)};
+}
+
+// XYZZ -> affine for several points with ONE field inversion (an inversion is ~400 products)
+template <class H>
+inline std::vector<Affine<H>> host64_batch_to_affine(const std::vector<XYZZ<H>>& x) {
+    const size_t n = x.size();
+    std::vector<typename H::T> pre(n);
+    typename H::T acc = H::one();
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        if (xyzz_is_inf<H>(x[i])) continue;
+        pre[i] = acc;
+        acc = H::mul(acc, x[i].zzz);
+        any = true;
+    }
+    typename H::T inv = any ? H::inv(acc) : acc;                                  // (nothing but infinity: nothing to invert)
+    std::vector<Affine<H>> out(n);
+    for (size_t i = n; i-- > 0;) {
+        if (xyzz_is_inf<H>(x[i])) { out[i] = aff_inf<H>(); continue; }
+        const typename H::T zi3 = H::mul(inv, pre[i]);
+        inv = H::mul(inv, x[i].zzz);
+        const typename H::T zi = H::mul(zi3, x[i].zz), zi2 = H::sqr(zi);
+        out[i] = Affine<H>{H::mul(x[i].x, zi2), H::mul(x[i].y, zi3)};
+    }
+    return out;
 }
 
 // ---- a point that arrives from a PEER (the collaborative provers' small opens) ---------------------------------------------
@@ -236,16 +264,11 @@ template <> struct Host64Curve<Fq264Field> {
 template <class H>
 inline XYZZ<H> host64_peer_point(const uint64_t* p, bool subgroup, bool& ok) {
     constexpr int FE = H::WORDS / 2;
-    uint32_t w[H::WORDS];
-    auto get = [&](const uint64_t* src) {
-        for (int i = 0; i < FE; i++) { w[2 * i] = (uint32_t)src[i]; w[2 * i + 1] = (uint32_t)(src[i] >> 32); }
-        return H::load(w);
-    };
     if (!Host64Curve<H>::words_valid(p) || !Host64Curve<H>::words_valid(p + FE) || !Host64Curve<H>::words_valid(p + 2 * FE)) { ok = false; return xyzz_inf<H>(); }
-    const typename H::T z = get(p + 2 * FE);
+    const typename H::T z = host64_coord<H>(p + 2 * FE);
     if (H::is_zero(z)) return xyzz_inf<H>();
     if (!H::eq(z, H::one())) { ok = false; return xyzz_inf<H>(); }
-    const typename H::T x = get(p), y = get(p + FE);
+    const typename H::T x = host64_coord<H>(p), y = host64_coord<H>(p + FE);
     if (!H::eq(H::sqr(y), H::add(H::mul(H::sqr(x), x), Host64Curve<H>::b()))) { ok = false; return xyzz_inf<H>(); }
     const XYZZ<H> pt{x, y, H::one(), H::one()};
     if (subgroup) {

@@ -29,29 +29,13 @@ inline void comm_tobytes(const Comm& c, std::vector<uint8_t>& out) {            
     out.push_back(c.has_shift ? 1 : 0);
     g1_tobytes(c.has_shift ? c.s : aff_inf<G1Field>(), out);
 }
-// projective -> affine for several points with ONE field inversion (the commitments of a round: 2 - 6 points, an inversion is ~400
-// products) in the 64-bit host field
+// projective -> affine for several points with ONE field inversion (the commitments of a round: 2 - 6 points) in the 64-bit host field
 inline std::vector<Affine<G1Field>> batch_to_aff(const std::vector<zk_g1_projective>& pts) {
     using H = Fq64Field;
-    const size_t n = pts.size();
-    std::vector<XYZZ<H>> x(n);
-    std::vector<typename H::T> pre(n);
-    typename H::T acc = H::one();
-    for (size_t i = 0; i < n; i++) {
-        x[i] = host64_proj_from_abi<H>((const uint64_t*)&pts[i]);
-        if (xyzz_is_inf<H>(x[i])) continue;
-        pre[i] = acc;
-        acc = H::mul(acc, x[i].zzz);
-    }
-    typename H::T inv = H::inv(acc);
-    std::vector<Affine<G1Field>> out(n);
-    for (size_t i = n; i-- > 0;) {
-        if (xyzz_is_inf<H>(x[i])) { out[i] = aff_inf<G1Field>(); continue; }
-        const typename H::T zi3 = H::mul(inv, pre[i]);
-        inv = H::mul(inv, x[i].zzz);
-        const typename H::T zi = H::mul(zi3, x[i].zz), zi2 = H::sqr(zi);
-        out[i] = aff_from_host64<G1Field>(Affine<H>{H::mul(x[i].x, zi2), H::mul(x[i].y, zi3)});
-    }
+    std::vector<XYZZ<H>> x(pts.size());
+    for (size_t i = 0; i < pts.size(); i++) x[i] = host64_proj_from_abi<H>((const uint64_t*)&pts[i]);
+    std::vector<Affine<G1Field>> out;
+    for (const Affine<H>& a : host64_batch_to_affine<H>(x)) out.push_back(aff_from_host64<G1Field>(a));
     return out;
 }
 

@@ -20,7 +20,6 @@
 #include "marlin_bytes.hpp"
 #include "marlin_lc.hpp"
 #include "sharednet.hpp"
-#include "hostfield64.hpp"
 #include <algorithm>
 #include <chrono>
 #include <future>
@@ -33,7 +32,6 @@ using namespace zk;
 namespace {
 
 struct Poly { char* p = nullptr; size_t n = 0; };        // n coefficients on the device
-
 
 // ---- the oracles: the nine the prover sends, in the order their rounds commit (and serialise) them, then the index's twelve ----
 enum Oracle : int {
@@ -191,66 +189,6 @@ struct Laps {
 
 struct Term { HF c; Oracle o; };                // o = O_NONE: the constant term (LCTerm::One)
 using LinComb = std::vector<Term>;
-
-// Opens of O(1) values on the caller's transport, batched into ONE exchange: scalars and G1 points of this party's share lane
-// (AdditiveFieldShare / AdditiveGroupShare::open: the sum over parties).  LANES = 2 (SPDZ): frs[1] / g1s[1] are the MAC shares;
-// a second exchange publishes [leader ? opened : 0] - mac for every item and every sum must vanish (SpdzFieldShare::batch_open,
-// SpdzGroupShare::open: share/spdz.rs:177-196,312-336, key alpha = 1 held by the leader) -- otherwise ZK_ERR_MAC.
-template <int LANES>
-int open_small(ZkSharedNet& nt, const std::vector<HF> frs[2], const std::vector<zk_g1_projective> g1s[2], std::vector<HF>& out_fr,
-               std::vector<zk_g1_projective>& out_g1) {
-    using H1 = Fq64Field;
-    using X1 = XYZZ<H1>;
-    zk_ctx* ctx = nt.ctx;
-    const size_t nf = frs[0].size(), ng = g1s[0].size(), words = 4 * nf + 18 * ng;
-    out_fr.assign(nf, HF::zero());
-    out_g1.resize(ng);
-    if (!words) return ZK_OK;
-    std::vector<uint64_t> msg(words);
-    std::vector<uint8_t> all;
-    std::vector<X1> og(ng);
-    auto exchange = [&](std::vector<HF>& f, std::vector<X1>& g) -> int {
-        ZK_TRY(nt.gather((const uint8_t*)msg.data(), words * 8, all));
-        f.assign(nf, HF::zero());
-        g.assign(ng, xyzz_inf<H1>());
-        std::vector<uint64_t> w(words);
-        for (int p = 0; p < nt.parties(); p++) {
-            memcpy(w.data(), all.data() + (size_t)p * words * 8, words * 8);
-            for (size_t i = 0; i < nf; i++) {      // what arrives from a peer: < r
-                if (!zk_fr_words_valid(&w[4 * i])) ZK_FAIL(ctx, ZK_ERR_STATE, "collaborative prover: a party sent a non-canonical field element");
-                zk_fr a;
-                memcpy(a.l, &w[4 * i], 32);
-                f[i] = f[i] + HF::from_abi(a);
-            }
-            bool pts_ok = true;                      // a peer's points: canonical, on the curve, (malicious prover) in the subgroup
-            const bool peer = p != ctx->party_id;
-            for (size_t i = 0; i < ng; i++)
-                g[i] = xyzz_add<H1>(g[i], peer ? host64_peer_point<H1>(&w[4 * nf + 18 * i], LANES == 2, pts_ok) : host64_proj_from_abi<H1>(&w[4 * nf + 18 * i]));
-            if (!pts_ok) ZK_FAIL(ctx, ZK_ERR_STATE, "collaborative prover: a party sent a point that is not a valid group element");
-        }
-        return ZK_OK;
-    };
-    for (size_t i = 0; i < nf; i++) { zk_fr a = frs[0][i].abi(); memcpy(&msg[4 * i], a.l, 32); }
-    for (size_t i = 0; i < ng; i++) memcpy(&msg[4 * nf + 18 * i], &g1s[0][i], 144);
-    ZK_TRY(exchange(out_fr, og));
-    if (LANES == 2) {
-        const bool leader = nt.leader();
-        for (size_t i = 0; i < nf; i++) { zk_fr a = ((leader ? out_fr[i] : HF::zero()) - frs[1][i]).abi(); memcpy(&msg[4 * i], a.l, 32); }
-        for (size_t i = 0; i < ng; i++) {
-            const X1 d = xyzz_add<H1>(leader ? og[i] : xyzz_inf<H1>(), xyzz_neg<H1>(host64_proj_from_abi<H1>((const uint64_t*)&g1s[1][i])));
-            host64_write_projective<H1>(xyzz_to_affine<H1>(d), &msg[4 * nf + 18 * i]);
-        }
-        std::vector<HF> cf;
-        std::vector<X1> cg;
-        ZK_TRY(exchange(cf, cg));
-        bool ok = true;
-        for (auto& v : cf) ok = ok && v.is_zero();
-        for (auto& v : cg) ok = ok && xyzz_is_inf<H1>(v);
-        if (!ok) ZK_FAIL(ctx, ZK_ERR_MAC, "SPDZ MAC check failed on an opened commitment / evaluation / witness");
-    }
-    for (size_t i = 0; i < ng; i++) host64_write_projective<H1>(xyzz_to_affine<H1>(og[i]), (uint64_t*)&out_g1[i]);
-    return ZK_OK;
-}
 
 // What the caller of a prover entry point hands over (lanes [0] = share / plain, [1] = MAC share under SPDZ)
 struct MarlinArgs {
@@ -411,19 +349,18 @@ struct Marlin : MarlinArgs {
                     c.pt = t;
                 }
         if (shared) {                                                            // first_comms.publicize() (lib.rs:180,205,228)
-            std::vector<HF> nofr[2], ofr;
-            std::vector<zk_g1_projective> pts[2], opened;
+            ZkSmallItems pts[2], opened;
             std::vector<Acc*> what;
             for (Oracle o : os) {
                 if (!ORACLES[o].shared) continue;
                 for (int which = 0; which < 2; which++) {
                     if (!acc[0][which][o].has) continue;
-                    for (int lane = 0; lane < LANES; lane++) pts[lane].push_back(acc[lane][which][o].pt);
+                    for (int lane = 0; lane < LANES; lane++) pts[lane].g1.push_back(acc[lane][which][o].pt);
                     what.push_back(&acc[0][which][o]);
                 }
             }
-            ZK_TRY(open_small<LANES>(nt, nofr, pts, ofr, opened));
-            for (size_t i = 0; i < what.size(); i++) what[i]->pt = opened[i];
+            ZK_TRY(zk_shared_open_small(nt, LANES, pts, &opened));
+            for (size_t i = 0; i < what.size(); i++) what[i]->pt = opened.g1[i];
         }
         std::vector<uint8_t> bytes;
         std::vector<zk_g1_projective> all;
@@ -658,11 +595,11 @@ struct Marlin : MarlinArgs {
         ZK_TRY(zk_poly_evaluate_batch_dev(ctx, refs.data(), pts.data(), refs.size(), vals.data()));
         for (size_t i = 0; i < want.size(); i++) *want[i].value = HF::from_abi(vals[i]);
         if (shared) {
-            std::vector<HF> frs[2] = {{z_b_beta, g_1_beta}, {}}, ofr;
-            if (LANES == 2) frs[1] = {HF::from_abi(vals[want.size()]), HF::from_abi(vals[want.size() + 1])};
-            std::vector<zk_g1_projective> nog[2], og;
-            ZK_TRY(open_small<LANES>(nt, frs, nog, ofr, og));
-            z_b_beta = ofr[0]; g_1_beta = ofr[1];
+            ZkSmallItems frs[2], opened;
+            frs[0].fr = {z_b_beta.abi(), g_1_beta.abi()};
+            if (LANES == 2) frs[1].fr = {vals[want.size()], vals[want.size() + 1]};
+            ZK_TRY(zk_shared_open_small(nt, LANES, frs, &opened));
+            z_b_beta = HF::from_abi(opened.fr[0]); g_1_beta = HF::from_abi(opened.fr[1]);
         }
         const HF ba = beta * alpha, one = HF::one();
         HF d[3];                                                                  // a_denom, b_denom, c_denom
@@ -793,12 +730,11 @@ struct Marlin : MarlinArgs {
                 wl[l] = w;
             }
             if (q_shared[q]) {                                                   // the witness (and random_v) of a shared combination: opened
-                std::vector<HF> frs[2], ofr;
-                std::vector<zk_g1_projective> pts[2], og;
-                for (int l = 0; l < LANES; l++) { pts[l].push_back(wl[l]); if (has_rv[q]) frs[l].push_back(rvs[q]); }
-                ZK_TRY(open_small<LANES>(nt, frs, pts, ofr, og));
-                wl[0] = og[0];
-                if (has_rv[q]) rvs[q] = ofr[0];
+                ZkSmallItems mine[2], opened;
+                for (int l = 0; l < LANES; l++) { mine[l].g1.push_back(wl[l]); if (has_rv[q]) mine[l].fr.push_back(rvs[q].abi()); }
+                ZK_TRY(zk_shared_open_small(nt, LANES, mine, &opened));
+                wl[0] = opened.g1[0];
+                if (has_rv[q]) rvs[q] = HF::from_abi(opened.fr[0]);
             }
             wits.push_back(wl[0]);
         }
