@@ -24,20 +24,26 @@ __device__ __forceinline__ Fr fr_mul(const Fr& a, const Fr& b) { return fp_mul<F
 __device__ __forceinline__ Fr fr_add(const Fr& a, const Fr& b) { return fp_add<FrParams>(a, b); }
 __device__ __forceinline__ Fr fr_sub(const Fr& a, const Fr& b) { return fp_sub<FrParams>(a, b); }
 
-// ---- a field constant passed to a kernel by value (internal form: nine limbs) ----
-struct FrK { uint32_t l[9]; };
-__device__ __forceinline__ Fr frk(const FrK& k) {
+// ---- the nine limbs of an internal-form element as plain words: kernel arguments, job structs, chunk totals, table entries ----
+ZK_HD Fr limbs_get(const uint32_t* l) {
     Fr r;
 #pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = k.l[i];
+    for (int i = 0; i < 9; i++) r.l[i] = l[i];
     return r;
 }
-inline FrK to_frk(const uint32_t* l) {
+ZK_HD void limbs_put(uint32_t* l, const Fr& v) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) l[i] = v.l[i];
+}
+
+// ---- a field constant passed to a kernel by value (internal form: nine limbs) ----
+struct FrK { uint32_t l[9]; };
+__device__ __forceinline__ Fr frk(const FrK& k) { return limbs_get(k.l); }
+inline FrK to_frk(const Fr& a) {
     FrK k;
-    for (int i = 0; i < 9; i++) k.l[i] = l[i];
+    limbs_put(k.l, a);
     return k;
 }
-inline FrK to_frk(const Fr& a) { return to_frk(a.l); }
 
 // ---- tables of field constants (ntt.hip: twiddles, coset scales) ----
 // Table entries (twiddles, coset scales) are kept as their nine 29-bit limbs, 36 B each: a product takes them as they are
@@ -45,16 +51,59 @@ inline FrK to_frk(const Fr& a) { return to_frk(a.l); }
 struct __attribute__((packed, aligned(4))) Limbs9 { uint32_t l[9]; };
 __device__ __forceinline__ Fr tab_load(const uint32_t* tab, size_t i) {
     const Limbs9 t = reinterpret_cast<const Limbs9*>(tab)[i];
-    Fr r;
-#pragma unroll
-    for (int k = 0; k < 9; k++) r.l[k] = t.l[k];
-    return r;
+    return limbs_get(t.l);
 }
 __device__ __forceinline__ void tab_store(uint32_t* tab, size_t i, const Fr& v) {
     Limbs9 t;
-#pragma unroll
-    for (int k = 0; k < 9; k++) t.l[k] = v.l[k];
+    limbs_put(t.l, v);
     reinterpret_cast<Limbs9*>(tab)[i] = t;
+}
+
+// ---- a [9][256] LDS tile of a 256-thread block, limb-major (a wave's b32 accesses hit 64 consecutive words): column get and put ----
+__device__ __forceinline__ Fr tile_get(const uint32_t (*t)[256], uint32_t col) {
+    Fr r;
+#pragma unroll
+    for (int k = 0; k < 9; k++) r.l[k] = t[k][col];
+    return r;
+}
+__device__ __forceinline__ void tile_put(uint32_t (*t)[256], uint32_t col, const Fr& v) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) t[k][col] = v.l[k];
+}
+
+// ---- the recurrences of poly.hip's scans, one copy each ----
+// Horner over c[lo .. hi) from the top: acc <- acc z + c[i], with each(i, acc) after every step (the division writes Q_i there)
+template <class Each>
+__device__ __forceinline__ Fr horner_fold(const void* c, size_t lo, size_t hi, const Fr& z, Fr acc, Each each) {
+    for (size_t i = hi; i > lo; i--) {
+        acc = fr_add(fr_mul(acc, z), fr_load(c, i - 1));
+        each(i - 1, acc);
+    }
+    return acc;
+}
+__device__ __forceinline__ Fr horner_fold(const void* c, size_t lo, size_t hi, const Fr& z, Fr acc) {
+    return horner_fold(c, lo, hi, z, acc, [](size_t, const Fr&) {});
+}
+// Montgomery's trick over v[lo .. hi) (ext form), zeros stay zero (ff/src/fields/mod.rs:632-658).  Forward: scratch[i] = the
+// product of the non-zero elements before i, internal form; returns the chunk's total (one for a chunk of zeros).  Backward: with
+// inv = 1 / total, v[i] <- 1 / v[i].
+__device__ __forceinline__ Fr inv_chunk_fwd(const void* v, size_t lo, size_t hi, uint32_t* scratch) {
+    Fr run = fp_one<FrParams>();
+    for (size_t i = lo; i < hi; i++) {
+        fr_store(scratch, i, run);
+        Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
+        if (!fp_is_zero<FrParams>(x)) run = fr_mul(run, x);
+    }
+    return run;
+}
+__device__ __forceinline__ void inv_chunk_bwd(void* v, size_t lo, size_t hi, const uint32_t* scratch, Fr inv) {
+    for (size_t i = hi; i-- > lo;) {
+        Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
+        if (fp_is_zero<FrParams>(x)) continue;
+        Fr xi = fr_mul(inv, fr_load(scratch, i));                            // 1/x, internal form
+        inv = fr_mul(inv, x);
+        fr_store(v, i, fp_int_to_ext<FrParams>(xi));
+    }
 }
 
 // ---- packed points (internal form) via 16-byte loads; F::WORDS is a multiple of 4 ----

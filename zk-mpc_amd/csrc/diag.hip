@@ -174,8 +174,8 @@ __global__ void __launch_bounds__(64) k_diag_fr_lazy(const uint32_t* __restrict_
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t* w = in + (size_t)c * nin * 9;
     uint32_t* o = out + (size_t)c * nout * 9;
-    auto ld = [&](int k) { Fr a; for (int i = 0; i < 9; i++) a.l[i] = w[k * 9 + i]; return a; };
-    auto st = [&](int k, const Fr& a) { for (int i = 0; i < 9; i++) o[k * 9 + i] = a.l[i]; };
+    auto ld = [&](int k) { return limbs_get(w + k * 9); };
+    auto st = [&](int k, const Fr& a) { limbs_put(o + k * 9, a); };
     if constexpr (OP == 0) st(0, frl_reduce(ld(0)));
     if constexpr (OP == 1) st(0, frl_norm(ld(0)));
     if constexpr (OP == 2) st(0, frl_sub<2>(ld(0), ld(1)));

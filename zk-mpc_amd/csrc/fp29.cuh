@@ -463,6 +463,18 @@ ZK_HD Fp<P> fp_pow_limbs(const Fp<P>& a, const uint32_t* e, int nlimbs) {
     return r;
 }
 
+// a^e for a 64-bit exponent: the one square-and-multiply of the host's Fr (hostfr.hpp) and of the powers kernel (poly.hip)
+template <class P>
+ZK_HD Fp<P> fp_pow_u64(const Fp<P>& a, uint64_t e) {
+    Fp<P> r = fp_one<P>();
+    bool started = false;
+    for (int b = 63; b >= 0; b--) {
+        if (started) r = fp_sqr<P>(r);
+        if ((e >> b) & 1) { r = started ? fp_mul<P>(r, a) : a; started = true; }
+    }
+    return r;
+}
+
 // Internal-form inverse by Fermat (a != 0): a^(p-2).  Input/ouput internal form.
 template <class P>
 ZK_HD Fp<P> fp_inv(const Fp<P>& a) {

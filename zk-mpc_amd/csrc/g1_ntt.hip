@@ -11,7 +11,7 @@
 //     entry e of lane l at ((e 48 + i) 64 + l).  48 KiB per block of one wave: three blocks per CU.
 //   * twiddles are 2^(k-1) raw 256-bit scalars (canonical Fr) computed on the host once per size and direction.
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "g1_ntt.cuh"
 #include "hostfield64.hpp"
 #include "hostgroup.hpp"
@@ -99,8 +99,7 @@ __global__ void __launch_bounds__(256) k_g1_sub(const uint32_t* __restrict__ a, 
 
 // w^t for t < 2^(log_n - 1) as raw scalars (canonical integers, 8 words each); w the domain generator of ntt.hip or its inverse
 std::vector<uint32_t> twiddle_words(uint32_t log_n, int inverse_root) {
-    Fr w = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-    for (uint32_t i = 0; i < (uint32_t)FR_TWO_ADICITY - log_n; i++) w = fp_sqr<FrParams>(w);
+    Fr w = HF::domain_root(log_n).v;
     if (inverse_root) w = fp_inv<FrParams>(w);
     const size_t half = log_n ? (size_t)1 << (log_n - 1) : 1;
     std::vector<uint32_t> out(half * 8);

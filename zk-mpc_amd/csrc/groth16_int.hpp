@@ -10,7 +10,7 @@
 //   groth16_multi.hip    one prover's MSMs spread over several devices
 //   groth16_shared.hip   create_proof over additive / SPDZ shares as one call
 #pragma once
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "hostgroup.hpp"
 #include "hostfield64.hpp"
 #include "internal.hpp"

@@ -13,44 +13,10 @@ using namespace zk;
 
 namespace {
 
-Fr host_fr_from_u64(uint64_t v) {
-    Fr t = fp_zero<FrParams>();
-    t.l[0] = (uint32_t)(v & MASK29);
-    t.l[1] = (uint32_t)((v >> 29) & MASK29);
-    t.l[2] = (uint32_t)(v >> 58);
-    return fp_canon_to_int<FrParams>(t);
-}
-
-Fr host_fr_pow(const Fr& a, uint64_t e) {
-    Fr r = fp_one<FrParams>();
-    bool started = false;
-    for (int b = 63; b >= 0; b--) {
-        if (started) r = fp_sqr<FrParams>(r);
-        if ((e >> b) & 1) { r = started ? fp_mul<FrParams>(r, a) : a; started = true; }
-    }
-    return r;
-}
-
-void host_batch_inverse(std::vector<Fr>& v) {  // Montgomery's trick (ff/src/fields/mod.rs:597-659); zeros stay zero
-    std::vector<Fr> pre(v.size());
-    Fr run = fp_one<FrParams>();
-    for (size_t i = 0; i < v.size(); i++) {
-        pre[i] = run;
-        if (!fp_is_zero<FrParams>(v[i])) run = fp_mul<FrParams>(run, v[i]);
-    }
-    Fr inv = fp_inv<FrParams>(run);
-    for (size_t i = v.size(); i-- > 0;) {
-        if (fp_is_zero<FrParams>(v[i])) continue;
-        Fr t = fp_mul<FrParams>(inv, pre[i]);
-        inv = fp_mul<FrParams>(inv, v[i]);
-        v[i] = t;
-    }
-}
-
 // upload a host vector of internal-form Fr as reference-form device vector
-int upload_fr(zk_ctx* ctx, const std::vector<Fr>& v, const char* slot, void** dev) {
+int upload_fr(zk_ctx* ctx, const std::vector<HF>& v, const char* slot, void** dev) {
     std::vector<uint32_t> packed(v.size() * 8 + 8);
-    for (size_t i = 0; i < v.size(); i++) fp_pack<FrParams>(&packed[8 * i], fp_int_to_ext<FrParams>(v[i]));
+    for (size_t i = 0; i < v.size(); i++) fp_pack<FrParams>(&packed[8 * i], fp_int_to_ext<FrParams>(v[i].v));
     ZK_TRY(zk_scratch(ctx, slot, v.size() * 32 + 32, dev));
     ZK_HIP(ctx, hipMemcpyAsync(*dev, packed.data(), v.size() * 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -58,9 +24,9 @@ int upload_fr(zk_ctx* ctx, const std::vector<Fr>& v, const char* slot, void** de
 }
 
 template <class F>
-Affine<F> host_gen_mul(const Affine<F>& g, const Fr& k_int) {
+Affine<F> host_gen_mul(const Affine<F>& g, const HF& k) {
     uint32_t kw[8];
-    fp_pack<FrParams>(kw, fp_int_to_canon<FrParams>(k_int));
+    k.canon_words(kw);
     return xyzz_to_affine<F>(xyzz_scalar_mul<F>(g, kw, 8));
 }
 
@@ -192,59 +158,54 @@ extern "C" int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r, const zk_fr* alph
                                 const zk_fr* delta_, const zk_fr* tau_, const zk_fr* g1_k, const zk_fr* g2_k, zk_pk** out) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !r || !alpha_ || !beta_ || !gamma_ || !delta_ || !tau_ || !g1_k || !g2_k || !out) return ZK_ERR_ARG;
-    auto ld = [](const zk_fr* x) { return fp_ext_to_int<FrParams>(host_load_ext<FrParams>(x->l)); };
-    const Fr alpha = ld(alpha_), beta = ld(beta_), gamma = ld(gamma_), delta = ld(delta_), t = ld(tau_);
-    const Fr one = fp_one<FrParams>();
+    const HF alpha = HF::from_abi(*alpha_), beta = HF::from_abi(*beta_), gamma = HF::from_abi(*gamma_), delta = HF::from_abi(*delta_), t = HF::from_abi(*tau_);
+    const HF one = HF::one();
     const size_t D = (size_t)1 << r->log_d, nc = r->nc, ni = r->ni;
     const size_t nvars = (ni - 1) + r->nw;
-    if (fp_is_zero<FrParams>(gamma) || fp_is_zero<FrParams>(delta)) ZK_FAIL(ctx, ZK_ERR_ARG, "setup: gamma/delta must be non-zero");
+    if (gamma.is_zero() || delta.is_zero()) ZK_FAIL(ctx, ZK_ERR_ARG, "setup: gamma/delta must be non-zero");
 
     // domain constants
-    Fr w = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-    for (uint32_t i = 0; i < (uint32_t)FR_TWO_ADICITY - r->log_d; i++) w = fp_sqr<FrParams>(w);
-    const Fr size_inv = fp_inv<FrParams>(host_fr_from_u64(D));
-    const Fr zt = fp_sub<FrParams>(host_fr_pow(t, D), one);  // evaluate_vanishing_polynomial(t)
-    if (fp_is_zero<FrParams>(zt)) ZK_FAIL(ctx, ZK_ERR_ARG, "setup: tau lies in the evaluation domain");
+    const HF w = HF::domain_root(r->log_d), size_inv = HF::from_u64(D).inv();
+    const HF zt = t.pow(D) - one;  // evaluate_vanishing_polynomial(t)
+    if (zt.is_zero()) ZK_FAIL(ctx, ZK_ERR_ARG, "setup: tau lies in the evaluation domain");
 
     // evaluate_all_lagrange_coefficients(t): u_i = (zt/D) w^i / (t - w^i)   (radix2/mod.rs:116-165)
-    std::vector<Fr> u(D), den(D);
+    std::vector<HF> u(D), den(D);
     {
-        Fr l = fp_mul<FrParams>(zt, size_inv), rr = one;
+        HF l = zt * size_inv, rr = one;
         for (size_t i = 0; i < D; i++) {
-            den[i] = fp_sub<FrParams>(t, rr);
+            den[i] = t - rr;
             u[i] = l;
-            l = fp_mul<FrParams>(l, w);
-            rr = fp_mul<FrParams>(rr, w);
+            l = l * w;
+            rr = rr * w;
         }
-        host_batch_inverse(den);
-        for (size_t i = 0; i < D; i++) u[i] = fp_mul<FrParams>(u[i], den[i]);
+        HF::batch_inverse(den.data(), D);
+        for (size_t i = 0; i < D; i++) u[i] = u[i] * den[i];
         den.clear(); den.shrink_to_fit();
     }
     // instance_map_with_evaluation (r1cs_to_qap.rs:47-92)
-    std::vector<Fr> a(nvars + 1, fp_zero<FrParams>()), b(nvars + 1, fp_zero<FrParams>()), c(nvars + 1, fp_zero<FrParams>());
+    std::vector<HF> a(nvars + 1, HF::zero()), b(nvars + 1, HF::zero()), c(nvars + 1, HF::zero());
     for (size_t i = 0; i < ni; i++) a[i] = u[nc + i];
-    std::vector<Fr>* abc[3] = {&a, &b, &c};
+    std::vector<HF>* abc[3] = {&a, &b, &c};
     for (int k = 0; k < 3; k++) {
         const auto& m = r->m[k];
         auto& dst = *abc[k];
         for (size_t i = 0; i < nc; i++)
-            for (uint32_t e = m.h_row_ptr[i]; e < m.h_row_ptr[i + 1]; e++) {
-                Fr term = m.all_one ? u[i] : fp_mul<FrParams>(u[i], m.h_coeff[e]);
-                dst[m.h_col[e]] = fp_add<FrParams>(dst[m.h_col[e]], term);
-            }
+            for (uint32_t e = m.h_row_ptr[i]; e < m.h_row_ptr[i + 1]; e++)
+                dst[m.h_col[e]] = dst[m.h_col[e]] + (m.all_one ? u[i] : u[i] * HF{m.h_coeff[e]});
     }
-    const Fr gamma_inv = fp_inv<FrParams>(gamma), delta_inv = fp_inv<FrParams>(delta);
-    std::vector<Fr> gamma_abc(ni), l(nvars + 1 - ni);
+    const HF gamma_inv = gamma.inv(), delta_inv = delta.inv();
+    std::vector<HF> gamma_abc(ni), l(nvars + 1 - ni);
     for (size_t i = 0; i <= nvars; i++) {
-        Fr s = fp_add<FrParams>(fp_add<FrParams>(fp_mul<FrParams>(beta, a[i]), fp_mul<FrParams>(alpha, b[i])), c[i]);
-        if (i < ni) gamma_abc[i] = fp_mul<FrParams>(s, gamma_inv);
-        else l[i - ni] = fp_mul<FrParams>(s, delta_inv);
+        const HF s = beta * a[i] + alpha * b[i] + c[i];
+        if (i < ni) gamma_abc[i] = s * gamma_inv;
+        else l[i - ni] = s * delta_inv;
     }
     c.clear(); c.shrink_to_fit();
-    std::vector<Fr> hq(D - 1);
+    std::vector<HF> hq(D - 1);
     {
-        Fr p = fp_mul<FrParams>(zt, delta_inv);
-        for (size_t i = 0; i + 1 < D; i++) { hq[i] = p; p = fp_mul<FrParams>(p, t); }
+        HF p = zt * delta_inv;
+        for (size_t i = 0; i + 1 < D; i++) { hq[i] = p; p = p * t; }
     }
     // H over coset values (zk_pk::h_eval).  With H_i = t^i zt / delta for i <= D-2 and zinv = 1 / Z(g):
     //   h_eval[j]     = zinv sum_i M_ij H_i,  M_ij = g^-i w^-ij / D: the ifft of (zinv zt / delta) (t/g)^i, i <= D-2, then 0
@@ -258,29 +219,27 @@ extern "C" int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r, const zk_fr* alph
         if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 0; }
         eval_h = zk_key_tables_bytes(nvars + 1, zk_mul_levels_for_key(ctx, nvars + 1), 6) <= mem_free / 2;
     }
-    std::vector<Fr> he, le;
+    std::vector<HF> he, le;
     if (eval_h) {
-        uint32_t zw[9];
-        ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zw));
-        Fr zinv;
-        for (int i = 0; i < 9; i++) zinv.l[i] = zw[i];
-        const Fr k = fp_mul<FrParams>(zinv, delta_inv), t_top = host_fr_pow(t, D - 1);
-        std::vector<Fr> nv(nc);                                       // -zinv V_r for the rows of C
-        Fr rr = one;
+        HF zinv;
+        ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, &zinv.v));
+        const HF k = zinv * delta_inv, t_top = t.pow(D - 1);
+        std::vector<HF> nv(nc);                                       // -zinv V_r for the rows of C
+        HF rr = one;
         for (size_t i = 0; i < nc; i++) {
-            nv[i] = fp_mul<FrParams>(fp_mul<FrParams>(u[i], k), fp_sub<FrParams>(one, fp_mul<FrParams>(t_top, rr)));
-            rr = fp_mul<FrParams>(rr, w);
+            nv[i] = u[i] * k * (one - t_top * rr);
+            rr = rr * w;
         }
-        le.assign(nvars + 1, fp_zero<FrParams>());
+        le.assign(nvars + 1, HF::zero());
         for (size_t i = ni; i <= nvars; i++) le[i] = l[i - ni];
         const auto& mc = r->m[2];
         for (size_t i = 0; i < nc; i++)
             for (uint32_t e = mc.h_row_ptr[i]; e < mc.h_row_ptr[i + 1]; e++)
-                le[mc.h_col[e]] = fp_add<FrParams>(le[mc.h_col[e]], mc.all_one ? nv[i] : fp_mul<FrParams>(nv[i], mc.h_coeff[e]));
-        he.assign(D, fp_zero<FrParams>());
-        const Fr q = fp_mul<FrParams>(t, fp_const<FrParams>(FrParams::GENERATOR_INV));
-        Fr p = fp_mul<FrParams>(zinv, fp_mul<FrParams>(zt, delta_inv));
-        for (size_t i = 0; i + 1 < D; i++) { he[i] = p; p = fp_mul<FrParams>(p, q); }
+                le[mc.h_col[e]] = le[mc.h_col[e]] + (mc.all_one ? nv[i] : nv[i] * HF{mc.h_coeff[e]});
+        he.assign(D, HF::zero());
+        const HF q = t * HF{fp_const<FrParams>(FrParams::GENERATOR_INV)};
+        HF p = zinv * (zt * delta_inv);
+        for (size_t i = 0; i + 1 < D; i++) { he[i] = p; p = p * q; }
     }
     u.clear(); u.shrink_to_fit();
 
@@ -309,9 +268,8 @@ extern "C" int zk_groth16_setup(zk_ctx* ctx, const zk_r1cs* r, const zk_fr* alph
     if (rc != ZK_OK) { zk_pk_free(ctx, pk); return rc; }
     pk->points_in_subgroup = true;            // every point of this key is a scalar multiple of a generator
 
-    const Fr k1 = ld(g1_k), k2 = ld(g2_k);
-    const Affine<G1Field> g1 = host_gen_mul<G1Field>(g1_gen(), k1);
-    const Affine<G2Field> g2 = host_gen_mul<G2Field>(g2_gen(), k2);
+    const Affine<G1Field> g1 = host_gen_mul<G1Field>(g1_gen(), HF::from_abi(*g1_k));
+    const Affine<G2Field> g2 = host_gen_mul<G2Field>(g2_gen(), HF::from_abi(*g2_k));
     pk->alpha_g1 = host_gen_mul<G1Field>(g1, alpha);
     pk->beta_g1 = host_gen_mul<G1Field>(g1, beta);
     pk->delta_g1 = host_gen_mul<G1Field>(g1, delta);
@@ -460,17 +418,15 @@ extern "C" int zk_pk_derive_eval_h(zk_ctx* ctx, zk_pk* pk, const zk_r1cs* r) {
     } tb{ctx};
 
     // the pre-scales zinv g^(-i) / D (i < D) and zinv / D as raw scalars
-    uint32_t zw[9];
-    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zw));
-    Fr c;
-    for (int i = 0; i < 9; i++) c.l[i] = zw[i];
-    c = fp_mul<FrParams>(c, fp_inv<FrParams>(host_fr_from_u64(D)));
+    HF c;
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, &c.v));
+    c = c * HF::from_u64(D).inv();
     {
         std::vector<uint32_t> sc((D + 1) * 8);
-        const Fr ginv = fp_const<FrParams>(FrParams::GENERATOR_INV);
-        Fr p = c;
-        for (size_t i = 0; i < D; i++) { fp_pack<FrParams>(&sc[8 * i], fp_int_to_canon<FrParams>(p)); p = fp_mul<FrParams>(p, ginv); }
-        fp_pack<FrParams>(&sc[8 * D], fp_int_to_canon<FrParams>(c));
+        const HF ginv{fp_const<FrParams>(FrParams::GENERATOR_INV)};
+        HF p = c;
+        for (size_t i = 0; i < D; i++) { p.canon_words(&sc[8 * i]); p = p * ginv; }
+        c.canon_words(&sc[8 * D]);
         DevBuf d_sc, work, scr, W, K;
         const uint32_t* tw;
         ZK_TRY(upload_words(ctx, &d_sc, sc));

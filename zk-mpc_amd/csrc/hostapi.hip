@@ -4,6 +4,7 @@
 //   CanonicalSerialize for points (:847-883), Fp256 add/sub/mul, from_repr / into_repr.
 #include "../../include/zkmpc_hip.h"
 #include "ctx.hpp"
+#include "hostfr.hpp"
 #include "hostgroup.hpp"
 #include "hostfield64.hpp"
 #include "frlazy.cuh"
@@ -135,21 +136,16 @@ extern "C" int zk_fr_mul(const zk_fr* a, const zk_fr* b, zk_fr* out) {
 extern "C" int zk_fr_inverse(const zk_fr* a, zk_fr* out) {
     ZK_API_BEGIN_NOCTX   // Field::inverse; zero has no inverse (macros.rs:389-443)
     if (!a || !out) return ZK_ERR_ARG;
-    Fr x = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a->l));
-    if (fp_is_zero<FrParams>(x)) return ZK_ERR_ARG;
-    host_store_ext<FrParams>(out->l, fp_int_to_ext<FrParams>(fp_inv<FrParams>(x)));
+    const HF x = HF::from_abi(*a);
+    if (x.is_zero()) return ZK_ERR_ARG;
+    *out = x.inv().abi();
     return ZK_OK;
     ZK_API_END
 }
 extern "C" int zk_fr_pow(const zk_fr* a, uint64_t e, zk_fr* out) {
     ZK_API_BEGIN_NOCTX   // Field::pow for a 64-bit exponent
     if (!a || !out) return ZK_ERR_ARG;
-    Fr x = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a->l)), r = fp_one<FrParams>();
-    for (int b = 63; b >= 0; b--) {
-        r = fp_sqr<FrParams>(r);
-        if ((e >> b) & 1) r = fp_mul<FrParams>(r, x);
-    }
-    host_store_ext<FrParams>(out->l, fp_int_to_ext<FrParams>(r));
+    *out = HF::from_abi(*a).pow(e).abi();
     return ZK_OK;
     ZK_API_END
 }
@@ -256,8 +252,8 @@ extern "C" int zk_fq_lazy_raw(int op, const uint32_t* in, uint32_t* out) {
 extern "C" int zk_fr_lazy_raw(int op, const uint32_t* in, uint32_t* out) {
     ZK_API_BEGIN_NOCTX
     if (!in || !out) return ZK_ERR_ARG;
-    auto ld = [&](int k) { Fr a; for (int i = 0; i < 9; i++) a.l[i] = in[9 * k + i]; return a; };
-    auto st = [&](int k, const Fr& a) { for (int i = 0; i < 9; i++) out[9 * k + i] = a.l[i]; };
+    auto ld = [&](int k) { return limbs_get(in + 9 * k); };
+    auto st = [&](int k, const Fr& a) { limbs_put(out + 9 * k, a); };
     switch (op) {
         case 0: st(0, frl_reduce(ld(0))); break;
         case 1: st(0, frl_norm(ld(0))); break;

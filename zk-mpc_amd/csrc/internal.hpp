@@ -24,10 +24,14 @@ int zk_ntt_launch_batch(zk_ctx* ctx, void* const* bufs_dev, int count, uint32_t 
 // count is (up to 65535 transforms per launch).  tmp: room for min(count, 65535) 2^log_n elements for transforms of more than one pass
 // (2^log_n > 2^10), or NULL for the context's grow-only "ntt_tmp" slot
 int zk_ntt_launch_strided(zk_ctx* ctx, void* base, size_t count, size_t stride, uint32_t log_n, int inverse, int coset, void* tmp = nullptr);
-int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]);  // 1/(g^N - 1), internal form
+int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, zk::Fr* out);  // 1/(g^N - 1), internal form
 // the elements of the domain of size 2^log_n as the transforms keep them resident (w^i for i < 2^log_n: internal form, nine limbs = 36
 // bytes each, devutil.cuh::tab_load) and 1 / 2^log_n in internal form
-int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements_dev, uint32_t size_inv9[9]);
+int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements_dev, zk::Fr* size_inv);
+// poly.hip: out[i] = start * base^i for i < n, base and start in internal form, on ctx->stream; out holds n elements in the
+// reference's form (32 bytes each) or n table entries (36 bytes each, tab_load)
+enum ZkFrForm { ZK_FR_EXT = 0, ZK_FR_TABLE = 1 };
+int zk_fr_powers_launch(zk_ctx* ctx, const zk::Fr& base, const zk::Fr& start, size_t n, void* out, ZkFrForm form);
 
 // The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
 enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_COUNT };
@@ -40,16 +44,16 @@ bool zk_fr_words_valid(const uint64_t l[4]);
 // core.hip: a launch-bound sequence on ONE stream as a captured graph from its third use with the same key (see there)
 int zk_graph_run(zk_ctx* ctx, const std::string& key, hipStream_t st, const std::function<int()>& enqueue);
 int zk_vec_op_launch(zk_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n);
-int zk_vec_scale_launch(zk_ctx* ctx, const void* a, const uint32_t* k_int_form9, void* out, size_t n);
+int zk_vec_scale_launch(zk_ctx* ctx, const void* a, const zk::Fr& k_int, void* out, size_t n);      // constants: internal form
 // zk_fr_vec_is_zero_dev without the wait: *verdict points at a page-locked word that is 0 (all zero) or not once ctx->stream has
 // passed this point (slot 0..7: tests in flight)
 int zk_fr_vec_is_zero_launch(zk_ctx* ctx, const void* v, size_t n, int slot, const uint32_t** verdict);
 // out = rp (kc s + ka a + kb b) - z tp, element-wise (Marlin round 2); out may alias s
 int zk_fr_outer_q1_launch(zk_ctx* ctx, const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp,
-                          const uint32_t* ka_int9, const uint32_t* kb_int9, const uint32_t* kc_int9, void* out, size_t n);
+                          const zk::Fr& ka_int, const zk::Fr& kb_int, const zk::Fr& kc_int, void* out, size_t n);
 // out[i] = sum_t k_t p_t[i] (terms with i < ns[t]); constants in internal form; out may not alias a term
-int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const size_t* ns, const uint32_t (*k_int_form9)[9], void* out, size_t n_out);
-int zk_vec_sub_scale_launch(zk_ctx* ctx, const void* a, const void* b, const uint32_t* k_int_form9, void* out, size_t n);
+int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const size_t* ns, const zk::Fr* k_int, void* out, size_t n_out);
+int zk_vec_sub_scale_launch(zk_ctx* ctx, const void* a, const void* b, const zk::Fr& k_int, void* out, size_t n);
 
 // msm.hip
 struct zk_bases {

@@ -9,14 +9,14 @@
 //   prover.rs:653-698        a and b evaluations on the domain B              -> zk_marlin_round3_ab_evals_dev
 // All element-wise and HBM-bound: the ab kernel reads 12 vectors and writes 2 (448 B per element of B).
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "internal.hpp"
 
 using namespace zk;
 
 namespace {
 
-Fr host_int(const zk_fr* a) { return fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a->l)); }
+Fr host_int(const zk_fr* a) { return HF::from_abi(*a).v; }
 
 // out[i] = idx[i] == 0xFFFFFFFF ? 0 : src[idx[i]]
 __global__ void __launch_bounds__(256) k_gather(const void* src, const uint32_t* idx, size_t n, void* out) {

@@ -193,7 +193,7 @@ int build(zk_ctx* ctx, const zk_r1cs_host* m, const zk_bases* powers_g, zk_marli
 
     const uint32_t* elems;
     Fr n_inv;
-    ZK_TRY(zk_ntt_domain_elements(ctx, log_h, &elems, n_inv.l));
+    ZK_TRY(zk_ntt_domain_elements(ctx, log_h, &elems, &n_inv));
     ArithArgs args{};
     {
         const uint32_t* r = (const uint32_t*)rows.p;

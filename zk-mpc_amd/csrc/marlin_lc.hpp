@@ -1,48 +1,10 @@
-// marlin_lc.hpp -- what Marlin's prover and verifier must derive alike on the host: Fr values, the evaluation domains and the
+// marlin_lc.hpp -- what Marlin's prover and verifier must derive alike on the host (over hostfr.hpp's Fr): the evaluation domains and the
 // coefficients of AHPForR1CS::construct_linear_combinations (arkworks/marlin/src/ahp/mod.rs:112-290).  marlin_prove.hip builds its
 // query set from them and marlin_verify.hip its pairing equations: one statement, so the two cannot drift.
 #pragma once
-#include "devutil.cuh"
-#include "../../include/zkmpc_hip.h"
-#include <vector>
+#include "hostfr.hpp"
 
 namespace zk {
-
-// ---- Fr on the host (internal Montgomery form of the device arithmetic) ----
-struct HF {
-    Fr v;
-    static HF zero() { return HF{fp_zero<FrParams>()}; }
-    static HF one() { return HF{fp_one<FrParams>()}; }
-    static HF from_u64(uint64_t x) {
-        Fr t = fp_zero<FrParams>();
-        t.l[0] = (uint32_t)(x & MASK29); t.l[1] = (uint32_t)((x >> 29) & MASK29); t.l[2] = (uint32_t)(x >> 58);
-        return HF{fp_canon_to_int<FrParams>(t)};
-    }
-    static HF from_abi(const zk_fr& a) { return HF{fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a.l))}; }
-    zk_fr abi() const { zk_fr o; host_store_ext<FrParams>(o.l, fp_int_to_ext<FrParams>(v)); return o; }
-    HF operator+(const HF& b) const { return HF{fp_add<FrParams>(v, b.v)}; }
-    HF operator-(const HF& b) const { return HF{fp_sub<FrParams>(v, b.v)}; }
-    HF operator*(const HF& b) const { return HF{fp_mul<FrParams>(v, b.v)}; }
-    HF neg() const { return HF{fp_neg<FrParams>(v)}; }
-    HF inv() const { return HF{fp_inv<FrParams>(v)}; }
-    bool is_zero() const { return fp_is_zero<FrParams>(v); }
-    bool operator==(const HF& b) const { return fp_eq<FrParams>(v, b.v); }
-    HF pow(uint64_t e) const {
-        HF r = one();
-        bool started = false;
-        for (int b = 63; b >= 0; b--) {
-            if (started) r = r * r;
-            if ((e >> b) & 1) { r = started ? r * *this : *this; started = true; }
-        }
-        return r;
-    }
-    void bytes(std::vector<uint8_t>& out) const {          // Fp::write: into_repr(), little endian
-        uint32_t w[8];
-        canon_words(w);
-        for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) out.push_back((uint8_t)(w[i] >> (8 * b)));
-    }
-    void canon_words(uint32_t w[8]) const { fp_pack<FrParams>(w, fp_int_to_canon<FrParams>(v)); }   // the plain integer below r
-};
 
 struct Dom {
     size_t size; uint32_t log; HF gen;
@@ -50,9 +12,7 @@ struct Dom {
         log = 0;
         while (((size_t)1 << log) < num_coeffs) log++;
         size = (size_t)1 << log;
-        Fr w = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-        for (uint32_t i = 0; i < (uint32_t)FR_TWO_ADICITY - log; i++) w = fp_sqr<FrParams>(w);
-        gen = HF{w};
+        gen = HF::domain_root(log);
     }
     HF vanishing(const HF& t) const { return t.pow(size) - HF::one(); }
 };

@@ -23,7 +23,6 @@
 #include <algorithm>
 #include <chrono>
 #include <future>
-#include <array>
 #include <string>
 #include <vector>
 
@@ -476,9 +475,8 @@ struct Marlin : MarlinArgs {
         char* elems = P.dev("h_elems", n);
         char* ra = P.dev("r_alpha", n);
         ZK_TRY(P.rc);
-        { zk_fr g = H.gen.abi(), o = one.abi(), al = alpha.abi();
-          ZK_TRY(zk_fr_powers_dev(ctx, &g, &o, n, elems));
-          ZK_TRY(zk_fr_powers_dev(ctx, &o, &al, n, ra)); }                       // the constant vector alpha
+        ZK_TRY(zk_fr_powers_launch(ctx, H.gen.v, one.v, n, elems, ZK_FR_EXT));
+        ZK_TRY(zk_fr_powers_launch(ctx, one.v, alpha.v, n, ra, ZK_FR_EXT));      // the constant vector alpha
         P.op(ZK_OP_SUB, ra, elems, ra, n);
         ZK_TRY(P.rc);
         ZK_TRY(zk_fr_batch_inverse_dev(ctx, ra, n));
@@ -518,7 +516,7 @@ struct Marlin : MarlinArgs {
             Prover& Q = PL[l];
             // r(alpha, X) (eta_c z_a z_b + eta_a z_a + eta_b z_b) - z t on the multiplication domain (public * own value: local): one pass
             ZK_TRY(Q.rc);
-            ZK_TRY(zk_fr_outer_q1_launch(ctx, e_s[l], e_a[l], e_b[l], e_z[l], e_rp, e_tp, eta[0].v.l, eta[1].v.l, eta[2].v.l, e_s[l], MUL.size));
+            ZK_TRY(zk_fr_outer_q1_launch(ctx, e_s[l], e_a[l], e_b[l], e_z[l], e_rp, e_tp, eta[0].v, eta[1].v, eta[2].v, e_s[l], MUL.size));
             Q.ntt(e_s[l], MUL, 1);                                               // q_1 (prover.rs:517-541)
             Q.op(ZK_OP_ADD, e_s[l], mask[l], e_s[l], md + 1);
             hq[l] = Q.dev("h1_q", MUL.size - n); hr[l] = Q.dev("h1_r", n);
@@ -670,17 +668,15 @@ struct Marlin : MarlinArgs {
                 Prover& Q = PL[l];
                 char* comb = Q.dev("comb" + std::to_string(q), cn);
                 // one launch for the whole combination (vec_ops.hip::k_lincomb)
-                std::vector<const void*> tp; std::vector<size_t> tn; std::vector<std::array<uint32_t, 9>> tk;
+                std::vector<const void*> tp; std::vector<size_t> tn; std::vector<Fr> tk;
                 for (auto& t : terms) {
                     if (any_shared && !ORACLES[t.first].shared && !leader) continue;   // a public oracle in a shared combination: the leader's
                     const Poly& p = Q.polys[t.first];
                     tp.push_back(p.p); tn.push_back(p.n);
-                    std::array<uint32_t, 9> k;
-                    for (int i = 0; i < 9; i++) k[i] = t.second.v.l[i];
-                    tk.push_back(k);
+                    tk.push_back(t.second.v);
                 }
                 ZK_TRY(Q.rc);
-                ZK_TRY(zk_fr_lincomb_launch(ctx, (int)tp.size(), tp.data(), tn.data(), (const uint32_t (*)[9])tk.data(), comb, cn));
+                ZK_TRY(zk_fr_lincomb_launch(ctx, (int)tp.size(), tp.data(), tn.data(), tk.data(), comb, cn));
                 char* quo = Q.dev("quo" + std::to_string(q), cn);
                 ZK_TRY(Q.rc);
                 { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, comb, cn, &zz, quo, nullptr)); }

@@ -234,8 +234,8 @@ extern "C" int zk_mpc_divide_by_vanishing_on_coset_in_place(zk_ctx* ctx, void* e
     ZK_TRY(check_layout(ctx, lay));
     if (log_n > 28) ZK_FAIL(ctx, ZK_ERR_ARG, "NTT size unsupported (log_n > 28)");
     const size_t N = (size_t)1 << log_n;
-    uint32_t zinv[9];
-    ZK_TRY(zk_ntt_vanishing_inv(ctx, log_n, zinv));
+    Fr zinv;
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, log_n, &zinv));
     FieldView v{(char*)evals, *lay, ctx->party_id == 0};
     void* lane[2];
     ZK_TRY(lane_bufs(ctx, "mpc_fft", N, v.lanes(), lane));

@@ -19,7 +19,7 @@
 // Work: (N/2) log2 N butterflies (the last level of every pass multiplies by 1 and is skipped),
 // + N inter-pass twiddles per pass boundary.  Traffic: 2 * 32 B * N per pass + the swap pass.
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "frlazy.cuh"
 #include "internal.hpp"
 #include <algorithm>
@@ -40,28 +40,6 @@ namespace {
 constexpr int LOGM_MAX = 10;
 constexpr int NTT_THREADS = 1024;   // (512 / 256 threads per tile, two / four butterflies per lane and stage: 2^20 in 131 / 144 us against 126: round 5)
 constexpr int TILE_ELEMS = 4096;  // x 36 B = 144 KiB of LDS
-
-
-// out[i] = start * base^i  (internal form in, limb-form table out)
-__global__ void __launch_bounds__(256) k_powers(uint32_t* out, FrK base_k, FrK start_k, size_t n) {
-    constexpr int CH = 32;
-    size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    size_t i0 = t * CH;
-    if (i0 >= n) return;
-    Fr base = frk(base_k);
-    // base^i0 by square-and-multiply
-    Fr p = fp_one<FrParams>();
-    bool started = false;
-    for (int b = 63; b >= 0; b--) {
-        if (started) p = fp_sqr<FrParams>(p);
-        if ((i0 >> b) & 1) { p = started ? fr_mul(p, base) : base; started = true; }
-    }
-    p = fr_mul(p, frk(start_k));
-    for (int j = 0; j < CH && i0 + j < n; j++) {
-        tab_store(out, i0 + j, p);
-        p = fr_mul(p, base);
-    }
-}
 
 // LDS tile layout: limb-major, 9 x 29-bit limbs per element (36 B): lds[k * E + element].  Limb-major makes every
 // ds_read/ds_write_b32 of a wave hit 64 consecutive words (conflict-free); keeping the unpacked limbs avoids a
@@ -291,21 +269,9 @@ __global__ void __launch_bounds__(256) k_bitrev_scale(P buf, uint32_t log_n, FrK
     }
 }
 
-Fr host_pow_u64(const Fr& a, uint64_t e) {
-    Fr r = fp_one<FrParams>();
-    for (int b = 63; b >= 0; b--) {
-        r = fp_sqr<FrParams>(r);
-        if ((e >> b) & 1) r = fp_mul<FrParams>(r, a);
-    }
-    return r;
-}
-
-int build_powers(zk_ctx* ctx, uint32_t** out, const Fr& base, const Fr& start, size_t n) {
+int build_powers(zk_ctx* ctx, uint32_t** out, const HF& base, const HF& start, size_t n) {
     ZK_HIP(ctx, hipMalloc((void**)out, n * 36));
-    size_t threads = (n + 31) / 32;
-    hipLaunchKernelGGL(k_powers, (unsigned)((threads + 255) / 256), 256, 0, ctx->stream, *out, to_frk(base), to_frk(start), n);
-    ZK_HIP(ctx, hipGetLastError());
-    return ZK_OK;
+    return zk_fr_powers_launch(ctx, base.v, start.v, n, *out, ZK_FR_TABLE);
 }
 
 int get_domain(zk_ctx* ctx, uint32_t log_n, bool need_coset, zk_domain** out) {
@@ -317,22 +283,14 @@ int get_domain(zk_ctx* ctx, uint32_t log_n, bool need_coset, zk_domain** out) {
     if (!d) {
         d = new zk_domain();
         d->log_n = log_n;
-        // group_gen = two_adic_root^(2^(47 - log_n))   (ff get_root_of_unity; radix2/mod.rs:67-69)
-        Fr w = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-        for (uint32_t i = 0; i < (uint32_t)FR_TWO_ADICITY - log_n; i++) w = fp_sqr<FrParams>(w);
-        Fr n_int = fp_canon_to_int<FrParams>([&] { Fr t = fp_zero<FrParams>(); t.l[0] = (uint32_t)(n & MASK29); t.l[1] = (uint32_t)(n >> 29); return t; }());
-        d->size_inv = fp_inv<FrParams>(n_int);
-        Fr g = fp_const<FrParams>(FrParams::GENERATOR);
-        Fr gn = host_pow_u64(g, n);
-        d->zinv = fp_inv<FrParams>(fp_sub<FrParams>(gn, fp_one<FrParams>()));
-        ZK_TRY(build_powers(ctx, &d->tw, w, fp_one<FrParams>(), n));
+        d->size_inv = HF::from_u64(n).inv().v;
+        d->zinv = (HF{fp_const<FrParams>(FrParams::GENERATOR)}.pow(n) - HF::one()).inv().v;
+        ZK_TRY(build_powers(ctx, &d->tw, HF::domain_root(log_n), HF::one(), n));
         ctx->domains[log_n] = d;
     }
     if (need_coset && !d->cos) {
-        Fr g = fp_const<FrParams>(FrParams::GENERATOR);
-        Fr gi = fp_const<FrParams>(FrParams::GENERATOR_INV);
-        ZK_TRY(build_powers(ctx, &d->cos, g, fp_one<FrParams>(), n));
-        ZK_TRY(build_powers(ctx, &d->icos, gi, d->size_inv, n));
+        ZK_TRY(build_powers(ctx, &d->cos, HF{fp_const<FrParams>(FrParams::GENERATOR)}, HF::one(), n));
+        ZK_TRY(build_powers(ctx, &d->icos, HF{fp_const<FrParams>(FrParams::GENERATOR_INV)}, HF{d->size_inv}, n));
     }
     *out = d;
     return ZK_OK;
@@ -340,11 +298,11 @@ int get_domain(zk_ctx* ctx, uint32_t log_n, bool need_coset, zk_domain** out) {
 
 }  // namespace
 
-int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements, uint32_t size_inv9[9]) {
+int zk_ntt_domain_elements(zk_ctx* ctx, uint32_t log_n, const uint32_t** elements, Fr* size_inv) {
     zk_domain* d;
     ZK_TRY(get_domain(ctx, log_n, false, &d));
     *elements = d->tw;
-    for (int i = 0; i < 9; i++) size_inv9[i] = d->size_inv.l[i];
+    *size_inv = d->size_inv;
     return ZK_OK;
 }
 
@@ -524,7 +482,7 @@ extern "C" int zk_fr_divide_by_vanishing_on_coset_dev(zk_ctx* ctx, void* evals, 
     if (!ctx || !evals) return ZK_ERR_ARG;
     zk_domain* d;
     ZK_TRY(get_domain(ctx, log_n, false, &d));
-    return zk_vec_scale_launch(ctx, evals, d->zinv.l, evals, (size_t)1 << log_n);
+    return zk_vec_scale_launch(ctx, evals, d->zinv, evals, (size_t)1 << log_n);
     ZK_API_END
 }
 
@@ -538,16 +496,16 @@ extern "C" int zk_fr_divide_by_vanishing_on_coset_in_place(zk_ctx* ctx, zk_fr* e
     void* d;
     ZK_TRY(zk_scratch(ctx, "fft_host", N * 32, &d));
     ZK_TRY(zk_xfer_h2d(ctx, d, evals, N * 32));
-    ZK_TRY(zk_vec_scale_launch(ctx, d, dom->zinv.l, d, N));
+    ZK_TRY(zk_vec_scale_launch(ctx, d, dom->zinv, d, N));
     ZK_TRY(zk_xfer_d2h(ctx, evals, d, N * 32));
     return ZK_OK;
     ZK_API_END
 }
 
 // used by r1cs.hip: (ab - c) / Z(g) fused
-int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, uint32_t out9[9]) {
+int zk_ntt_vanishing_inv(zk_ctx* ctx, uint32_t log_n, Fr* out) {
     zk_domain* d;
     ZK_TRY(get_domain(ctx, log_n, false, &d));
-    for (int i = 0; i < 9; i++) out9[i] = d->zinv.l[i];
+    *out = d->zinv;
     return ZK_OK;
 }

@@ -19,7 +19,7 @@
 // replays every chunk from its now-known carry-in.  2n (evaluation: n) products, coalesced-by-chunk traffic, two or three
 // launches of fixed depth (~60 dependent multiply-adds) whatever n.
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "hostgroup.hpp"
 #include "internal.hpp"
 #include <vector>
@@ -29,17 +29,6 @@ using namespace zk;
 namespace {
 
 constexpr int INV_CH = 32;   // batch-inversion chunk per thread
-
-Fr host_int(const zk_fr* x) { return fp_ext_to_int<FrParams>(host_load_ext<FrParams>(x->l)); }
-Fr host_pow(const Fr& a, uint64_t e) {
-    Fr r = fp_one<FrParams>();
-    bool started = false;
-    for (int b = 63; b >= 0; b--) {
-        if (started) r = fp_sqr<FrParams>(r);
-        if ((e >> b) & 1) { r = started ? fp_mul<FrParams>(r, a) : a; started = true; }
-    }
-    return r;
-}
 
 // Division by X^N - 1: with the coefficients viewed as an m x N row-major matrix (row k = c[kN .. kN+N-1]) the quotient
 // is the column-wise exclusive suffix sum, q[k][j] = sum_{k' > k} c[k'][j], and the remainder is r[j] = c[0][j] + q[0][j].
@@ -73,24 +62,11 @@ __global__ void __launch_bounds__(256) k_divv_fill(const void* c, size_t n, size
     }
 }
 
-// Montgomery's trick on chunks of INV_CH; zeros stay zero (ff/src/fields/mod.rs:632-658).
+// Montgomery's trick on chunks of INV_CH (devutil.cuh: inv_chunk_fwd / inv_chunk_bwd around the chunk's one inversion).
 __global__ void __launch_bounds__(64) k_batch_inverse(void* v, size_t n, uint32_t* scratch) {
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t * INV_CH < n; t += (size_t)gridDim.x * blockDim.x) {
         size_t lo = t * INV_CH, hi = lo + INV_CH < n ? lo + INV_CH : n;
-        Fr run = fp_one<FrParams>();
-        for (size_t i = lo; i < hi; i++) {
-            fr_store(scratch, i, run);                                       // product of the non-zero elements before i (internal form)
-            Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
-            if (!fp_is_zero<FrParams>(x)) run = fr_mul(run, x);
-        }
-        Fr inv = fp_inv<FrParams>(run);
-        for (size_t i = hi; i-- > lo;) {
-            Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
-            if (fp_is_zero<FrParams>(x)) continue;
-            Fr xi = fr_mul(inv, fr_load(scratch, i));                        // 1/x, internal form
-            inv = fr_mul(inv, x);
-            fr_store(v, i, fp_int_to_ext<FrParams>(xi));
-        }
+        inv_chunk_bwd(v, lo, hi, scratch, fp_inv<FrParams>(inv_chunk_fwd(v, lo, hi, scratch)));
     }
 }
 
@@ -102,48 +78,29 @@ __global__ void __launch_bounds__(64) k_batch_inverse(void* v, size_t n, uint32_
 __global__ void __launch_bounds__(64) k_inv_fwd(const void* v, size_t n, size_t ch, uint32_t* scratch, uint32_t* totals) {
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t * ch < n; t += (size_t)gridDim.x * blockDim.x) {
         size_t lo = t * ch, hi = lo + ch < n ? lo + ch : n;
-        Fr run = fp_one<FrParams>();
-        for (size_t i = lo; i < hi; i++) {
-            fr_store(scratch, i, run);
-            Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
-            if (!fp_is_zero<FrParams>(x)) run = fr_mul(run, x);
-        }
-#pragma unroll
-        for (int k = 0; k < 9; k++) totals[t * 9 + k] = run.l[k];
+        limbs_put(totals + t * 9, inv_chunk_fwd(v, lo, hi, scratch));
     }
 }
 __global__ void __launch_bounds__(64) k_inv_bwd(void* v, size_t n, size_t ch, const uint32_t* scratch, const uint32_t* inv_totals) {
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t * ch < n; t += (size_t)gridDim.x * blockDim.x) {
         size_t lo = t * ch, hi = lo + ch < n ? lo + ch : n;
-        Fr inv;
-#pragma unroll
-        for (int k = 0; k < 9; k++) inv.l[k] = inv_totals[t * 9 + k];
-        for (size_t i = hi; i-- > lo;) {
-            Fr x = fp_ext_to_int<FrParams>(fr_load(v, i));
-            if (fp_is_zero<FrParams>(x)) continue;
-            Fr xi = fr_mul(inv, fr_load(scratch, i));
-            inv = fr_mul(inv, x);
-            fr_store(v, i, fp_int_to_ext<FrParams>(xi));
-        }
+        inv_chunk_bwd(v, lo, hi, scratch, limbs_get(inv_totals + t * 9));
     }
 }
 
-// out[i] = start * base^i
+// out[i] = start * base^i, base and start in internal form; FORM: what `out` holds (ZkFrForm)
 // (PC powers per lane: 32, or 8 for vectors of up to 2^16 -- the lane's chain is what a short launch lasts)
+template <int FORM>
 __global__ void __launch_bounds__(256) k_powers(void* out, FrK base_k, FrK start_k, size_t n, int PC) {
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     size_t i0 = t * (size_t)PC;
     if (i0 >= n) return;
     const Fr base = frk(base_k);
-    Fr p = fp_one<FrParams>();
-    bool started = false;
-    for (int b = 63; b >= 0; b--) {
-        if (started) p = fp_sqr<FrParams>(p);
-        if ((i0 >> b) & 1) { p = started ? fr_mul(p, base) : base; started = true; }
-    }
-    p = fr_mul(fp_int_to_ext<FrParams>(p), frk(start_k));                    // ext form of start * base^i0
+    Fr p = fr_mul(fp_pow_u64<FrParams>(base, i0), frk(start_k));
+    if (FORM == ZK_FR_EXT) p = fp_int_to_ext<FrParams>(p);
     for (int j = 0; j < PC && i0 + j < n; j++) {
-        fr_store(out, i0 + j, p);
+        if (FORM == ZK_FR_EXT) fr_store(out, i0 + j, p);
+        else tab_store((uint32_t*)out, i0 + j, p);
         p = fr_mul(p, base);
     }
 }
@@ -160,29 +117,18 @@ struct EvalJob {
     const void* c;
     size_t n;
     uint32_t first_block, nblocks, R, pad;
-    uint32_t z[9], lvl1[8][9], zspan[9], lvl2[8][9];       // internal form
+    Fr z, lvl1[8], zspan, lvl2[8];                         // internal form
 };
-__device__ __forceinline__ Fr limbs9(const uint32_t* l) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = l[i];
-    return r;
-}
 // h[0] <- sum_t h[t] * base^t over the 256 values of the block, base^(2^l) given as lvl[l]
-__device__ __forceinline__ Fr block_power_tree(uint32_t (*lds)[256], const uint32_t (*lvl)[9], Fr v) {
+__device__ __forceinline__ Fr block_power_tree(uint32_t (*lds)[256], const Fr* lvl, Fr v) {
     const uint32_t tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 9; k++) lds[k][tid] = v.l[k];
+    tile_put(lds, tid, v);
     __syncthreads();
     for (int l = 0; l < 8; l++) {
         const uint32_t d = 1u << l;
         if ((tid & (2 * d - 1)) == 0) {
-            Fr r;
-#pragma unroll
-            for (int k = 0; k < 9; k++) r.l[k] = lds[k][tid + d];
-            v = fr_add(v, fr_mul(r, limbs9(lvl[l])));
-#pragma unroll
-            for (int k = 0; k < 9; k++) lds[k][tid] = v.l[k];
+            v = fr_add(v, fr_mul(tile_get(lds, tid + d), lvl[l]));
+            tile_put(lds, tid, v);
         }
         __syncthreads();
     }
@@ -190,12 +136,9 @@ __device__ __forceinline__ Fr block_power_tree(uint32_t (*lds)[256], const uint3
 }
 __device__ __forceinline__ void eval_span(const EvalJob& J, void* partial) {
     __shared__ uint32_t lds[9][256];
-    const Fr z = limbs9(J.z);
     const size_t lo = ((size_t)(blockIdx.x - J.first_block) * 256 + threadIdx.x) * EV_CH;
     const size_t hi = lo + EV_CH < J.n ? lo + EV_CH : J.n;
-    Fr acc = fp_zero<FrParams>();
-    for (size_t i = hi; i > lo; i--) acc = fr_add(fr_mul(acc, z), fr_load(J.c, i - 1));
-    acc = block_power_tree(lds, J.lvl1, acc);
+    const Fr acc = block_power_tree(lds, J.lvl1, horner_fold(J.c, lo, hi, J.z, fp_zero<FrParams>()));
     if (threadIdx.x == 0) fr_store(partial, blockIdx.x, acc);
 }
 __global__ void __launch_bounds__(256) k_eval_spans(const EvalJob* jobs, uint32_t njobs, void* partial) {
@@ -207,11 +150,8 @@ __global__ void __launch_bounds__(256) k_eval_spans1(const EvalJob J, void* part
 __global__ void __launch_bounds__(256) k_eval_join(const EvalJob* jobs, const void* partial, void* out) {
     __shared__ uint32_t lds[9][256];
     const EvalJob& J = jobs[blockIdx.x];
-    const Fr zs = limbs9(J.zspan);
     const size_t lo = (size_t)threadIdx.x * J.R, hi = lo + J.R < J.nblocks ? lo + J.R : J.nblocks;
-    Fr acc = fp_zero<FrParams>();
-    for (size_t i = hi; i > lo; i--) acc = fr_add(fr_mul(acc, zs), fr_load(partial, J.first_block + i - 1));
-    acc = block_power_tree(lds, J.lvl2, acc);
+    const Fr acc = block_power_tree(lds, J.lvl2, horner_fold(partial, J.first_block + lo, J.first_block + hi, J.zspan, fp_zero<FrParams>()));
     if (threadIdx.x == 0) fr_store(out, blockIdx.x, acc);
 }
 
@@ -223,22 +163,15 @@ __global__ void __launch_bounds__(256) k_eval_join(const EvalJob* jobs, const vo
 // out[j + shift].  Depth ~ 2 EV_CH + 2 R + 3 * 8 multiply-adds (the recursive form this replaces: 3 x 64 per level, 3 to 4
 // levels, and a copy to the host at the bottom).
 // inclusive suffix scan over the block: returns I_t = sum_{u >= t} v_u M^(u - t), M^(2^l) = lvl[l]; buf: 2 x 9 x 256 words
-__device__ __forceinline__ Fr block_suffix_scan(uint32_t (*buf)[9][256], const uint32_t (*lvl)[9], Fr v) {
+__device__ __forceinline__ Fr block_suffix_scan(uint32_t (*buf)[9][256], const Fr* lvl, Fr v) {
     const uint32_t tid = threadIdx.x;
     int cur = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) buf[0][k][tid] = v.l[k];
+    tile_put(buf[0], tid, v);
     __syncthreads();
     for (int l = 0; l < 8; l++) {
         const uint32_t d = 1u << l;
-        if (tid + d < 256) {
-            Fr r;
-#pragma unroll
-            for (int k = 0; k < 9; k++) r.l[k] = buf[cur][k][tid + d];
-            v = fr_add(v, fr_mul(r, limbs9(lvl[l])));
-        }
-#pragma unroll
-        for (int k = 0; k < 9; k++) buf[cur ^ 1][k][tid] = v.l[k];
+        if (tid + d < 256) v = fr_add(v, fr_mul(tile_get(buf[cur], tid + d), lvl[l]));
+        tile_put(buf[cur ^ 1], tid, v);
         cur ^= 1;
         __syncthreads();
     }
@@ -246,17 +179,12 @@ __device__ __forceinline__ Fr block_suffix_scan(uint32_t (*buf)[9][256], const u
 }
 __global__ void __launch_bounds__(256) k_span_carries(const EvalJob J, const void* partial, void* carry, void* rem) {
     __shared__ uint32_t buf[2][9][256];
-    const Fr zs = limbs9(J.zspan);
+    const Fr zs = J.zspan;
     const uint32_t tid = threadIdx.x;
     const size_t lo = (size_t)tid * J.R, hi = lo + J.R < J.nblocks ? lo + J.R : J.nblocks;
-    Fr acc = fp_zero<FrParams>();
-    for (size_t i = hi; i > lo; i--) acc = fr_add(fr_mul(acc, zs), fr_load(partial, i - 1));
-    block_suffix_scan(buf, J.lvl2, acc);            // 8 levels: the final values sit in buf[0]
+    block_suffix_scan(buf, J.lvl2, horner_fold(partial, lo, hi, zs, fp_zero<FrParams>()));      // 8 levels: the final values sit in buf[0]
     Fr c = fp_zero<FrParams>();
-    if (tid + 1 < 256) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) c.l[k] = buf[0][k][tid + 1];
-    }
+    if (tid + 1 < 256) c = tile_get(buf[0], tid + 1);
     for (size_t i = hi; i > lo; i--) {
         fr_store(carry, i - 1, c);
         c = fr_add(fr_mul(c, zs), fr_load(partial, i - 1));
@@ -267,42 +195,40 @@ __global__ void __launch_bounds__(256) k_span_carries(const EvalJob J, const voi
 // (the remainder Q_0 goes to rem when asked for): one launch instead of three for the opening witnesses of a small Marlin proof.
 __global__ void __launch_bounds__(256) k_fill_spans(const EvalJob J, const void* carry, void* out, int shift, void* rem) {
     __shared__ uint32_t buf[2][9][256];
-    const Fr z = limbs9(J.z);
+    const Fr z = J.z;
     const uint32_t tid = threadIdx.x;
     const size_t lo = ((size_t)blockIdx.x * 256 + tid) * EV_CH;
     const size_t hi = lo + EV_CH < J.n ? lo + EV_CH : (lo < J.n ? J.n : lo);
     const Fr cin = carry ? fr_load(carry, blockIdx.x) : fp_zero<FrParams>();
-    Fr h = fp_zero<FrParams>();
-    for (size_t i = hi; i > lo; i--) h = fr_add(fr_mul(h, z), fr_load(J.c, i - 1));
-    if (tid == 255) h = fr_add(h, fr_mul(cin, limbs9(J.lvl1[0])));      // the span's carry-in enters behind its last chunk
+    Fr h = horner_fold(J.c, lo, hi, z, fp_zero<FrParams>());
+    if (tid == 255) h = fr_add(h, fr_mul(cin, J.lvl1[0]));              // the span's carry-in enters behind its last chunk
     block_suffix_scan(buf, J.lvl1, h);
     Fr acc = cin;
-    if (tid + 1 < 256) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) acc.l[k] = buf[0][k][tid + 1];
-    }
-    for (size_t i = hi; i > lo; i--) {
-        acc = fr_add(fr_mul(acc, z), fr_load(J.c, i - 1));
-        const long long o = (long long)(i - 1) + shift;
-        if (o >= 0) fr_store(out, (size_t)o, acc);
-    }
+    if (tid + 1 < 256) acc = tile_get(buf[0], tid + 1);
+    acc = horner_fold(J.c, lo, hi, z, acc, [&](size_t i, const Fr& q) {
+        const long long o = (long long)i + shift;
+        if (o >= 0) fr_store(out, (size_t)o, q);
+    });
     if (rem && blockIdx.x == 0 && tid == 0) fr_store(rem, 0, acc);         // Q_0 (an empty chunk 0 cannot occur: n >= 1)
 }
 
 }  // namespace
 
+int zk_fr_powers_launch(zk_ctx* ctx, const Fr& base, const Fr& start, size_t n, void* out, ZkFrForm form) {
+    if (!n) return ZK_OK;
+    const int pc = form == ZK_FR_EXT && n <= ((size_t)1 << 16) ? 8 : 32;
+    const unsigned blocks = (unsigned)(((n + pc - 1) / pc + 255) / 256);
+    if (form == ZK_FR_EXT) hipLaunchKernelGGL(k_powers<ZK_FR_EXT>, blocks, 256, 0, ctx->stream, out, to_frk(base), to_frk(start), n, pc);
+    else hipLaunchKernelGGL(k_powers<ZK_FR_TABLE>, blocks, 256, 0, ctx->stream, out, to_frk(base), to_frk(start), n, pc);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+
 extern "C" int zk_fr_powers_dev(zk_ctx* ctx, const zk_fr* base, const zk_fr* start, size_t n, void* out_dev) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !base || !start || (n && !out_dev)) return ZK_ERR_ARG;
     if (!n) return ZK_OK;
-    Fr b = host_int(base);
-    Fr s_ext = host_load_ext<FrParams>(start->l);   // kept in ext form: multiplied in after the int->ext conversion of base^i0
-    const int pc = n <= ((size_t)1 << 16) ? 8 : 32;
-    size_t threads = (n + pc - 1) / pc;
-    hipLaunchKernelGGL(k_powers, (unsigned)((threads + 255) / 256), 256, 0, ctx->stream, out_dev, to_frk(b),
-                       to_frk(fp_ext_to_int<FrParams>(s_ext)), n, pc);
-    ZK_HIP(ctx, hipGetLastError());
-    return ZK_OK;
+    return zk_fr_powers_launch(ctx, HF::from_abi(*base).v, HF::from_abi(*start).v, n, out_dev, ZK_FR_EXT);
     ZK_API_END
 }
 
@@ -326,17 +252,11 @@ extern "C" int zk_fr_batch_inverse_dev(zk_ctx* ctx, void* v_dev, size_t n) {
         ZK_HIP(ctx, hipMemcpyAsync(h, tot, chunks * 36, hipMemcpyDeviceToHost, ctx->stream));
         ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         // Montgomery's trick over the chunk totals (never zero: a chunk of zeros has total one)
-        std::vector<Fr> pre(chunks);
-        Fr run = fp_one<FrParams>();
-        auto tot_at = [&](size_t t) { Fr x; for (int k = 0; k < 9; k++) x.l[k] = h[t * 9 + k]; return x; };
-        for (size_t t = 0; t < chunks; t++) { pre[t] = run; run = fp_mul<FrParams>(run, tot_at(t)); }
-        Fr inv = fp_inv<FrParams>(run);
+        std::vector<HF> inv(chunks);
+        for (size_t t = 0; t < chunks; t++) inv[t] = HF::from_limbs(h + t * 9);
+        HF::batch_inverse(inv.data(), chunks);
         uint32_t* hi = h + chunks * 9;
-        for (size_t t = chunks; t-- > 0;) {
-            const Fr it = fp_mul<FrParams>(inv, pre[t]);
-            inv = fp_mul<FrParams>(inv, tot_at(t));
-            for (int k = 0; k < 9; k++) hi[t * 9 + k] = it.l[k];
-        }
+        for (size_t t = 0; t < chunks; t++) inv[t].limbs(hi + t * 9);
         ZK_HIP(ctx, hipMemcpyAsync(tot + chunks * 9, hi, chunks * 36, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_inv_bwd, zk_grid(chunks, 64, 8192), 64, 0, ctx->stream, v_dev, n, ch, (const uint32_t*)scr, (const uint32_t*)(tot + chunks * 9));
         ZK_HIP(ctx, hipGetLastError());
@@ -350,7 +270,7 @@ extern "C" int zk_fr_batch_inverse_dev(zk_ctx* ctx, void* v_dev, size_t n) {
 }
 
 namespace {
-void eval_job_fill(EvalJob& J, const void* c, size_t n, uint32_t first_block, const Fr& z) {
+void eval_job_fill(EvalJob& J, const void* c, size_t n, uint32_t first_block, const HF& z) {
     J.c = c;
     J.n = n;
     J.first_block = first_block;
@@ -358,13 +278,12 @@ void eval_job_fill(EvalJob& J, const void* c, size_t n, uint32_t first_block, co
     if (!J.nblocks) J.nblocks = 1;
     J.R = (J.nblocks + 255) / 256;
     J.pad = 0;
-    auto put = [](uint32_t* d, const Fr& v) { for (int k = 0; k < 9; k++) d[k] = v.l[k]; };
-    put(J.z, z);
-    Fr p = host_pow(z, EV_CH);
-    for (int l = 0; l < 8; l++) { put(J.lvl1[l], p); p = fp_sqr<FrParams>(p); }     // p ends as z^(EV_CH * 256) = z^SPAN
-    put(J.zspan, p);
-    p = host_pow(p, J.R);
-    for (int l = 0; l < 8; l++) { put(J.lvl2[l], p); p = fp_sqr<FrParams>(p); }
+    J.z = z.v;
+    HF p = z.pow(EV_CH);
+    for (int l = 0; l < 8; l++) { J.lvl1[l] = p.v; p = p.sqr(); }      // p ends as z^(EV_CH * 256) = z^SPAN
+    J.zspan = p.v;
+    p = p.pow(J.R);
+    for (int l = 0; l < 8; l++) { J.lvl2[l] = p.v; p = p.sqr(); }
 }
 }  // namespace
 
@@ -377,7 +296,7 @@ extern "C" int zk_poly_evaluate_batch_dev(zk_ctx* ctx, const zk_poly_ref* polys,
     uint32_t blocks = 0;
     for (size_t i = 0; i < count; i++) {
         if (polys[i].n && !polys[i].ptr) return ZK_ERR_ARG;
-        eval_job_fill(jobs[i], polys[i].ptr, polys[i].n, blocks, host_int(&points[i]));
+        eval_job_fill(jobs[i], polys[i].ptr, polys[i].n, blocks, HF::from_abi(points[i]));
         blocks += jobs[i].nblocks;
     }
     char* scr;
@@ -410,7 +329,7 @@ extern "C" int zk_poly_divide_by_linear_dev(zk_ctx* ctx, const void* coeffs_dev,
     ZK_API_BEGIN(ctx)
     if (!ctx || !z || (n && !coeffs_dev) || (n > 1 && !q_dev)) return ZK_ERR_ARG;
     EvalJob job;                                    // 680 B: travels as a kernel argument, no copy, nothing to keep alive
-    eval_job_fill(job, coeffs_dev, n, 0, host_int(z));
+    eval_job_fill(job, coeffs_dev, n, 0, HF::from_abi(*z));
     const uint32_t blocks = job.nblocks;
     char* scr;
     ZK_TRY(zk_scratch(ctx, "poly_divlin", (size_t)blocks * 64 + 32, (void**)&scr));

@@ -73,7 +73,7 @@ int upload_mat(zk_ctx* ctx, zk_r1cs::Mat& m, size_t nc, const uint32_t* rp, cons
     const Fr one = fp_one<FrParams>();
     m.all_one = true;
     for (size_t k = 0; k < m.nnz; k++) {
-        m.h_coeff[k] = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(coeff[k].l));
+        m.h_coeff[k] = HF::from_abi(coeff[k]).v;
         if (!fp_eq<FrParams>(m.h_coeff[k], one)) m.all_one = false;
     }
     ZK_HIP(ctx, hipMalloc((void**)&m.row_ptr, (nc + 1) * 4));
@@ -174,8 +174,8 @@ extern "C" int zk_mul_chain_assignment_dev(zk_ctx* ctx, size_t n, const zk_fr* w
     if (!ctx || !w0 || !w1 || !z_dev || n == 0) return ZK_ERR_ARG;
     // the chain is inherently sequential: computed on the host (input generation, not on the proving path)
     std::vector<Fr> w(n + 2);
-    w[0] = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(w0->l));
-    w[1] = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(w1->l));
+    w[0] = HF::from_abi(*w0).v;
+    w[1] = HF::from_abi(*w1).v;
     for (size_t i = 0; i < n; i++) w[i + 2] = fp_mul<FrParams>(w[i], w[i + 1]);
     std::vector<uint32_t> packed((n + 3) * 8);
     fp_pack<FrParams>(&packed[0], fp_int_to_ext<FrParams>(fp_one<FrParams>()));
@@ -211,8 +211,8 @@ extern "C" int zk_groth16_witness_map_pre_dev(zk_ctx* ctx, const zk_r1cs* r, con
 extern "C" int zk_groth16_witness_map_post_dev(zk_ctx* ctx, const zk_r1cs* r, void* ab, const void* c) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !r || !ab || !c) return ZK_ERR_ARG;
-    uint32_t zinv[9];
-    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zinv));
+    Fr zinv;
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, &zinv));
     ZK_TRY(zk_ntt_launch(ctx, ab, r->log_d, 1, 1));                                  // coset_ifft of ab  (:303)
     return zk_vec_sub_scale_launch(ctx, ab, c, zinv, ab, (size_t)1 << r->log_d);    // (. - c) / Z(g), c in coefficient form (:298-302)
     ZK_API_END
@@ -236,8 +236,8 @@ int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, co
     ZK_TRY(zk_ntt_launch_strided(ctx, a, 3 * count, D, r->log_d, 1, 0, tmp));    // ifft of every a, b, c (a | b | c are one strided run)
     ZK_TRY(zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 0, 1, tmp));    // coset_fft of every a and b
     ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, a, b, a, total));
-    uint32_t zinv[9];
-    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, zinv));
+    Fr zinv;
+    ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, &zinv));
     ZK_TRY(zk_ntt_launch_strided(ctx, a, count, D, r->log_d, 1, 1, tmp));        // coset_ifft of every product
     return zk_vec_sub_scale_launch(ctx, a, c, zinv, a, total);
 }

@@ -24,7 +24,7 @@
 // src/main.rs:99-114) goes through an O(N^2) schoolbook kernel.  Everything is integer-ALU bound
 // (1 352 v_mad_u64_u32 per 753-bit Montgomery product).
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "internal.hpp"
 
 #include <initializer_list>
@@ -438,10 +438,7 @@ __global__ void __launch_bounds__(256) k_she_fq_to_fr(const void* fq, void* out,
         for (int k = 0; k < L7; k++) {
             Fr limb = fp_zero<FrParams>();
             limb.l[0] = c.l[k];
-            Fr kk;
-#pragma unroll
-            for (int q = 0; q < 9; q++) kk.l[q] = FR_FOLD29[k][q];
-            acc = fr_add(acc, fr_mul(limb, kk));
+            acc = fr_add(acc, fr_mul(limb, fp_const<FrParams>(FR_FOLD29[k])));
         }
         fr_store(out, i, acc);
     }
@@ -767,14 +764,8 @@ static int she_fr_twist(zk_ctx* ctx, uint32_t log_n, bool inverse, void** out) {
     bool fresh = ctx->slots.find(name) == ctx->slots.end();
     ZK_TRY(zk_scratch(ctx, name, (size_t)n * 32, out));
     if (!fresh) return ZK_OK;
-    // root = TWO_ADIC_ROOT^(2^(47 - (log_n + 1))), computed on the host in the device's internal form
-    Fr z = fp_const<FrParams>(FrParams::TWO_ADIC_ROOT);
-    for (uint32_t i = 0; i < FR_TWO_ADICITY - (log_n + 1); i++) z = fp_sqr<FrParams>(z);
-    if (inverse) z = fp_inv<FrParams>(z);
-    zk_fr base, start;
-    host_store_ext<FrParams>(base.l, fp_int_to_ext<FrParams>(z));
-    host_store_ext<FrParams>(start.l, fp_int_to_ext<FrParams>(fp_one<FrParams>()));
-    return zk_fr_powers_dev(ctx, &base, &start, n, *out);
+    const HF z = HF::domain_root(log_n + 1);                             // the primitive 2n-th root
+    return zk_fr_powers_launch(ctx, inverse ? z.inv().v : z.v, fp_one<FrParams>(), n, *out, ZK_FR_EXT);
 }
 
 extern "C" int zk_she_encode_dev(zk_ctx* ctx, const void* plain_fr, void* out, size_t n, size_t batch) {

@@ -6,7 +6,7 @@
 // (share/additive.rs:124-131, share/field.rs:118-128).
 // HBM-bound: 96 B of traffic per element for a binary op (2 x 32 B in, 32 B out).
 #include "../../include/zkmpc_hip.h"
-#include "devutil.cuh"
+#include "hostfr.hpp"
 #include "frlazy.cuh"
 #include "internal.hpp"
 #include <algorithm>
@@ -130,14 +130,14 @@ int zk_vec_op_launch(zk_ctx* ctx, int op, const void* a, const void* b, void* ou
     return ZK_OK;
 }
 
-int zk_vec_scale_launch(zk_ctx* ctx, const void* a, const uint32_t* k9, void* out, size_t n) {
+int zk_vec_scale_launch(zk_ctx* ctx, const void* a, const Fr& k, void* out, size_t n) {
     if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(k_vec_scale, zk_grid(n, 256), 256, 0, ctx->stream, a, to_frk(k9), out, n);
+    hipLaunchKernelGGL(k_vec_scale, zk_grid(n, 256), 256, 0, ctx->stream, a, to_frk(k), out, n);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
 
-int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const size_t* ns, const uint32_t (*k9)[9], void* out, size_t n_out) {
+int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const size_t* ns, const Fr* k, void* out, size_t n_out) {
     if (n_out == 0) return ZK_OK;
     for (int t0 = 0; t0 < terms || t0 == 0; t0 += LINCOMB_MAX) {
         LinComb c{};
@@ -145,7 +145,7 @@ int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const si
         for (int t = 0; t < c.terms; t++) {
             c.p[t] = ps[t0 + t];
             c.n[t] = std::min(ns[t0 + t], n_out);
-            for (int i = 0; i < 9; i++) c.k[t].l[i] = k9[t0 + t][i];
+            c.k[t] = to_frk(k[t0 + t]);
         }
         hipLaunchKernelGGL(k_lincomb, zk_grid(n_out, 256), 256, 0, ctx->stream, c, out, n_out, t0 ? 1 : 0);
         ZK_HIP(ctx, hipGetLastError());
@@ -154,16 +154,16 @@ int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const si
 }
 
 int zk_fr_outer_q1_launch(zk_ctx* ctx, const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp,
-                          const uint32_t* ka9, const uint32_t* kb9, const uint32_t* kc9, void* out, size_t n) {
+                          const Fr& ka, const Fr& kb, const Fr& kc, void* out, size_t n) {
     if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(k_outer_q1, zk_grid(n, 256), 256, 0, ctx->stream, s, a, b, z, rp, tp, to_frk(ka9), to_frk(kb9), to_frk(kc9), out, n);
+    hipLaunchKernelGGL(k_outer_q1, zk_grid(n, 256), 256, 0, ctx->stream, s, a, b, z, rp, tp, to_frk(ka), to_frk(kb), to_frk(kc), out, n);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
 
-int zk_vec_sub_scale_launch(zk_ctx* ctx, const void* a, const void* b, const uint32_t* k9, void* out, size_t n) {
+int zk_vec_sub_scale_launch(zk_ctx* ctx, const void* a, const void* b, const Fr& k, void* out, size_t n) {
     if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(k_vec_sub_scale, zk_grid(n, 256), 256, 0, ctx->stream, a, b, to_frk(k9), out, n);
+    hipLaunchKernelGGL(k_vec_sub_scale, zk_grid(n, 256), 256, 0, ctx->stream, a, b, to_frk(k), out, n);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
@@ -178,8 +178,7 @@ extern "C" int zk_fr_vec_op_dev(zk_ctx* ctx, int op, const void* a, const void* 
 extern "C" int zk_fr_vec_scale_dev(zk_ctx* ctx, const void* a, const zk_fr* k, void* out, size_t n) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !k || (n && (!a || !out))) return ZK_ERR_ARG;
-    Fr kk = fp_ext_to_int<FrParams>(host_load_ext<FrParams>(k->l));
-    return zk_vec_scale_launch(ctx, a, kk.l, out, n);
+    return zk_vec_scale_launch(ctx, a, HF::from_abi(*k).v, out, n);
     ZK_API_END
 }
 
