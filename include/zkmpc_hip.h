@@ -765,6 +765,33 @@ int zk_groth16_prove_shared_spdz(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1
                                  const zk_fr r_lanes[2], const zk_fr s_lanes[2], const void* const tx_lanes_dev[2],
                                  const void* const ty_lanes_dev[2], const void* const tz_lanes_dev[2], const zk_net_vtable* net,
                                  uint8_t proof[192], uint64_t* bytes_sent);
+/* count collaborative proofs of ONE key and ONE constraint system in one call, with the exchanges of ONE proof: the count products
+ * of the witness maps are one Beaver product over count * D elements (two vector opens per call), and the two small opens carry
+ * the items of all proofs, ordered by proof within each kind (the first: 2 count scalars, 3 count G1 points, count G2 points; the
+ * second: count G1 points).  The exchanges do not grow with count; their payload does: *bytes_sent is count times a single call's.
+ * z_share_dev: count assignments of m = num_instance + num_witness elements back to back (assignment k at k * m), each as
+ * zk_groth16_prove_shared takes it; r_share / s_share: count scalars; tx / ty / tz_dev: count * D elements each (proof k's triple at
+ * k * D, D = 2^zk_r1cs_domain_log), or all NULL for DummyFieldTripleSource.  proofs_out: count * 192 bytes, proof k the bytes
+ * zk_groth16_prove_shared returns for (z_k, r_k, s_k, triple_k); every party writes the same bytes.  EVERY PARTY MUST PASS THE SAME
+ * count: the parties meet in exchanges whose sizes follow from it.  count = 1 is the single call.  The device work is that of
+ * zk_groth16_prove_batch_dev: launches that do not grow with count, the MSMs in chunks of proofs where count exceeds what one
+ * multi-vector job takes (the exchanges are not cut).  The buffers that grow with count are allocations of the call.
+ * ZK_ERR_ARG: count = 0, a null pointer, a partial triple, a key that does not match the system.  ZK_ERR_NOMEM: the working set
+ * (per proof and lane the assignment and 5 D elements, 6 D more per proof, one chunk's MSM scratch) does not fit 90 % of the free
+ * device memory -- decided before any device work and before the first exchange.  An announced next assignment
+ * (zk_groth16_hint_next_dev) is drained and dropped. */
+int zk_groth16_prove_shared_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, size_t count, const void* z_share_dev,
+                                  const zk_fr* r_share, const zk_fr* s_share, const void* tx_dev, const void* ty_dev,
+                                  const void* tz_dev, const zk_net_vtable* net, uint8_t* proofs_out, uint64_t* bytes_sent);
+/* The same over SPDZ shares (zk_groth16_prove_shared_spdz for count proofs): every share argument is a pair of lanes [0] = share,
+ * [1] = MAC share -- z_lanes_dev[l]: count assignments, r_lanes[l] / s_lanes[l]: count scalars, tx/ty/tz_lanes_dev[l]: count * D
+ * elements (or NULL / NULL lanes for the dummy triple source).  Every open of the batch is MAC-checked; if any check fails the
+ * call returns ZK_ERR_MAC and nothing is written to proofs_out. */
+int zk_groth16_prove_shared_spdz_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r1cs, size_t count,
+                                       const void* const z_lanes_dev[2], const zk_fr* const r_lanes[2], const zk_fr* const s_lanes[2],
+                                       const void* const tx_lanes_dev[2], const void* const ty_lanes_dev[2],
+                                       const void* const tz_lanes_dev[2], const zk_net_vtable* net, uint8_t* proofs_out,
+                                       uint64_t* bytes_sent);
 
 /* The collaborative Marlin prover as one call: MpcMarlin::prove (src/marlin.rs:56; arkworks/marlin/src/lib.rs:152-319 with
  * F = MpcField<Fr>) over this party's ADDITIVE shares.  z_share_dev = the party's share of the padded assignment (instance part

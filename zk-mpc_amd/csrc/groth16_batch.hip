@@ -21,19 +21,6 @@ namespace {
 
 constexpr size_t TAIL_TASKS = 16, PRE_TASKS = 8;
 
-// f(lo, hi) over [0, count) in at most `tasks` contiguous ranges on the context's pool (the first range on this thread)
-template <class Fn>
-void over_ranges(zk_ctx* ctx, size_t count, size_t tasks, const Fn& f) {
-    const size_t nt = std::min(count, tasks), per = (count + nt - 1) / nt;
-    std::vector<ZkTask<void>> ts;
-    for (size_t t = 1; t < nt; t++) {
-        const size_t lo = t * per, hi = std::min(count, lo + per);
-        if (lo < hi) ts.push_back(zk_async(ctx, [&f, lo, hi] { f(lo, hi); }));
-    }
-    f(0, std::min(count, per));
-    for (auto& t : ts) t.get();
-}
-
 // cnt proofs: z = their assignments (m elements each), h = their cnt quotients of D elements once front() has run on the context
 // stream (the first chunk enqueues the batched witness map there, beside its z sort); pre_ready() returns once the pre terms of tails[0..cnt) are complete
 int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, const char* z, const char* h, const std::function<int()>& front,
@@ -72,7 +59,7 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
     ZK_TRY(zk_msm_finish_multi(ctx, &J[3], l.data()));
     ZK_TRY(zk_msm_finish_multi(ctx, &J[4], hs.data()));
     pre_ready();
-    over_ranges(ctx, cnt, TAIL_TASKS, [&](size_t lo, size_t hi) {
+    zk_over_ranges(ctx, cnt, TAIL_TASKS, [&](size_t lo, size_t hi) {
         for (size_t k = lo; k < hi; k++) {
             zk_tail_chain_a(pk, &tails[k], a[k]);
             zk_tail_chain_b(pk, &tails[k], b1[k]);
@@ -83,49 +70,16 @@ int prove_chunk(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t cnt, cons
     return ZK_OK;
 }
 
-// device bytes the MSM jobs of a chunk of cnt proofs need: per job its sort (sorted entries, keys, values and the segment tables:
-// ~16 bytes per digit) and its bucket sums (with room for split buckets)
-size_t chunk_bytes(const zk_pk* pk, const zk_r1cs* r, size_t cnt) {
-    size_t bytes = 0;
-    for (const ZkG16Jobs::Job& j : ZkG16Jobs(pk, r, nullptr, nullptr).j) {
-        const size_t W = j.tab->pre ? (255 + j.tab->c_pre - 1) / j.tab->c_pre : 32;
-        const size_t XW = j.tab->group == 1 ? 48 : 96;
-        const size_t buckets = j.tab->pre ? ((size_t)1 << (j.tab->c_pre - 1)) : W * std::max<size_t>(j.n, 16);
-        bytes += cnt * (j.n * W * 16 + buckets * XW * 4 * 2);
-    }
-    return bytes;
-}
-
 // The key against the system, the proofs per MSM chunk, and the device memory: the assignments (count m elements: the caller's,
 // or the host form's upload) and the witness map's 6 count D elements (a | b | c and the transforms' scratch), plus one chunk's
 // MSM scratch, against 90 % of the free memory.
 int batch_plan(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size_t* chunk_out) {
     ZK_TRY(zk_groth16_key_matches(ctx, pk, r));
     const size_t m = r->ni + r->nw, D = (size_t)1 << r->log_d;
-    // proofs per chunk: every job's bucket spaces within what one multi job takes (zk_msm_multi_chunk)
-    size_t chunk = count;
-    for (const ZkG16Jobs::Job& j : ZkG16Jobs(pk, r, nullptr, nullptr).j) chunk = std::min(chunk, zk_msm_multi_chunk(j.tab, j.n));
-    size_t free_b = 0, total_b = 0;
-    ZK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const double need = (double)count * (double)(m + 6 * D) * 32.0 + (double)chunk_bytes(pk, r, chunk);
-    if (need > (double)(free_b / 10 * 9))
-        ZK_FAIL(ctx, ZK_ERR_NOMEM, "groth16 batch: the working set of " + std::to_string(count) + " proofs (" +
-                                       std::to_string((unsigned long long)(need / 1048576.0)) + " MiB) does not fit the free device memory (" +
-                                       std::to_string(free_b >> 20) + " MiB)");
-    *chunk_out = chunk;
-    return ZK_OK;
+    size_t bytes;
+    zk_g16_batch_chunk(pk, r, count, false, chunk_out, &bytes);
+    return zk_g16_batch_fits(ctx, count, (double)(m + 6 * D) * 32.0, bytes);
 }
-
-// a device allocation of this call only (the batch's buffers grow with count: not kept in the context's grow-only scratch arena)
-struct CallMem {
-    zk_ctx* ctx;
-    void* p = nullptr;
-    ~CallMem() {
-        if (!p) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(p);
-    }
-};
 
 int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size_t chunk, const void* z_dev, const zk_fr* r_,
               const zk_fr* s_, uint8_t* proofs_out) {
@@ -135,12 +89,12 @@ int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size
     ZK_TRY(zk_next_z_drop(ctx, true));
     if (count == 1) return zk_groth16_prove_dev(ctx, pk, r, z_dev, r_, s_, proofs_out);
     ZK_TRY(zk_prover_streams(ctx, 1));
-    CallMem wm{ctx};
+    ZkCallMem wm{ctx};
     ZK_HIP(ctx, hipMalloc(&wm.p, count * 6 * D * 32));
     std::vector<ZkTail> tails(count);
     // the terms of the tails that need no MSM result, beside the device work (prove_chunk waits for them before its tails)
     ZkTask<void> pre_task = zk_async(ctx, [&] {
-        over_ranges(ctx, count, PRE_TASKS, [&](size_t lo, size_t hi) {
+        zk_over_ranges(ctx, count, PRE_TASKS, [&](size_t lo, size_t hi) {
             for (size_t k = lo; k < hi; k++) {
                 zk_tail_begin(&r_[k], &s_[k], &tails[k]);
                 zk_tail_pre_a(pk, &tails[k]);
@@ -161,6 +115,34 @@ int run_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, size
 
 }  // namespace
 
+void zk_g16_batch_chunk(const zk_pk* pk, const zk_r1cs* r, size_t count, bool quotient_given, size_t* chunk_out, size_t* chunk_bytes) {
+    const ZkG16Jobs T(pk, r, nullptr, nullptr, true, quotient_given);
+    size_t chunk = count;
+    for (const ZkG16Jobs::Job& j : T.j) chunk = std::min(chunk, zk_msm_multi_chunk(j.tab, j.n));
+    // per job its sort (sorted entries, keys, values and the segment tables: ~16 bytes per digit) and its bucket sums (with room
+    // for split buckets)
+    size_t bytes = 0;
+    for (const ZkG16Jobs::Job& j : T.j) {
+        const size_t W = j.tab->pre ? (255 + j.tab->c_pre - 1) / j.tab->c_pre : 32;
+        const size_t XW = j.tab->group == 1 ? 48 : 96;
+        const size_t buckets = j.tab->pre ? ((size_t)1 << (j.tab->c_pre - 1)) : W * std::max<size_t>(j.n, 16);
+        bytes += chunk * (j.n * W * 16 + buckets * XW * 4 * 2);
+    }
+    *chunk_out = chunk;
+    *chunk_bytes = bytes;
+}
+
+int zk_g16_batch_fits(zk_ctx* ctx, size_t count, double per_proof, size_t chunk_bytes) {
+    size_t free_b = 0, total_b = 0;
+    ZK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    const double need = (double)count * per_proof + (double)chunk_bytes;
+    if (need > (double)(free_b / 10 * 9))
+        ZK_FAIL(ctx, ZK_ERR_NOMEM, "groth16 batch: the working set of " + std::to_string(count) + " proofs (" +
+                                       std::to_string((unsigned long long)(need / 1048576.0)) + " MiB) does not fit the free device memory (" +
+                                       std::to_string(free_b >> 20) + " MiB)");
+    return ZK_OK;
+}
+
 extern "C" int zk_groth16_prove_batch_dev(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs* r, size_t count, const void* z_dev, const zk_fr* r_,
                                           const zk_fr* s_, uint8_t* proofs_out) {
     ZK_API_BEGIN(ctx)
@@ -178,7 +160,7 @@ extern "C" int zk_groth16_prove_batch(zk_ctx* ctx, const zk_pk* pk, const zk_r1c
     size_t chunk;
     ZK_TRY(batch_plan(ctx, pk, r, count, &chunk));                 // before the upload: the assignments are part of the working set
     const size_t m = r->ni + r->nw;
-    CallMem z{ctx};
+    ZkCallMem z{ctx};
     ZK_HIP(ctx, hipMalloc(&z.p, count * m * 32));
     ZK_TRY(zk_xfer_h2d(ctx, z.p, z_host, count * m * 32, zk_host_is_pinned(z_host)));
     return run_batch(ctx, pk, r, count, chunk, z.p, r_, s_, proofs_out);

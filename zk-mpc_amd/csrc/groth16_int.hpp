@@ -8,7 +8,8 @@
 //   groth16_prove.hip    create_proof for a local prover                                           (src/groth16.rs:68-183)
 //   groth16_batch.hip    create_proof for many assignments of one key in one call
 //   groth16_multi.hip    one prover's MSMs spread over several devices
-//   groth16_shared.hip   create_proof over additive / SPDZ shares as one call
+//   groth16_shared.hip   create_proof over additive / SPDZ shares as one call (its host algebra: groth16_shared_int.hpp)
+//   groth16_shared_batch.hip  the same for many shared assignments of one key, with the exchanges of one proof
 #pragma once
 #include "hostfr.hpp"
 #include "hostgroup.hpp"
@@ -111,6 +112,11 @@ inline bool zk_g16_eval_h_enabled() {
 // r1cs.hip: the witness map of count assignments (count x m elements back to back) with launches that do not grow with count;
 // abc = room for 6 count D elements, the count quotients in its first count D on return
 int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc);
+// ... and its two halves, between which it multiplies (the collaborative batch prover puts the Beaver product there): pre leaves
+// abc = a | b on the coset and c in coefficient form (tmp: 3 count D elements of scratch), post turns the count products into the
+// count quotients (tmp: count D elements)
+int zk_groth16_witness_map_batch_pre(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc, void* tmp);
+int zk_groth16_witness_map_batch_post(zk_ctx* ctx, const zk_r1cs* r, size_t count, void* ab, const void* c, void* tmp);
 // r1cs.hip: the witness map that ends at e = a o b on the coset (two mat-vecs, ifft and coset_fft of a and b, the product): what the
 // H job of a key with h_eval multiplies (zk_pk::h_eval).  The batch form takes the same abc and leaves the count e vectors in its
 // first count D elements.
@@ -225,6 +231,36 @@ class ZkProofTail {
     void join();
     void finish(const zk_g1_projective& h_sum, const zk_g1_projective& l_sum, uint8_t proof[192], const zk::Affine<zk::G1Field>* l_const = nullptr);
 };
+
+// ---- what the batch provers share (groth16_batch.hip, groth16_shared_batch.hip) ----
+// f(lo, hi) over [0, count) in at most `tasks` contiguous ranges on the context's pool (the first range on this thread)
+template <class Fn>
+void zk_over_ranges(zk_ctx* ctx, size_t count, size_t tasks, const Fn& f) {
+    const size_t nt = std::min(count, tasks), per = (count + nt - 1) / nt;
+    std::vector<ZkTask<void>> ts;
+    for (size_t t = 1; t < nt; t++) {
+        const size_t lo = t * per, hi = std::min(count, lo + per);
+        if (lo < hi) ts.push_back(zk_async(ctx, [&f, lo, hi] { f(lo, hi); }));
+    }
+    f(0, std::min(count, per));
+    for (auto& t : ts) t.get();
+}
+// a device allocation of this call only (a batch's buffers grow with count: not kept in the context's grow-only scratch arena)
+struct ZkCallMem {
+    zk_ctx* ctx;
+    void* p = nullptr;
+    ~ZkCallMem() {
+        if (!p) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+    }
+};
+// groth16_batch.hip: the proofs per MSM chunk of a batch of count (every job's bucket spaces within what one multi job takes) and
+// the device bytes the five jobs of one such chunk need; quotient_given as in ZkG16Jobs
+void zk_g16_batch_chunk(const zk_pk* pk, const zk_r1cs* r, size_t count, bool quotient_given, size_t* chunk, size_t* chunk_bytes);
+// The batch provers' memory rule: count * per_proof bytes of buffers and one chunk's MSM scratch against 90 % of the free device
+// memory -- otherwise ZK_ERR_NOMEM, before any device work
+int zk_g16_batch_fits(zk_ctx* ctx, size_t count, double per_proof, size_t chunk_bytes);
 
 // ---- the ABI's affine structs (x | y in the reference's Montgomery words) as host-field points; a coordinate word is valid below q ----
 inline zk::Affine<zk::Fq64Field> zk_host_g1(const zk_g1_affine* p) {

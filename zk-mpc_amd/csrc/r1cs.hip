@@ -223,9 +223,20 @@ extern "C" int zk_groth16_witness_map_post_dev(zk_ctx* ctx, const zk_r1cs* r, vo
 // mat-vec launches, strided transforms (one launch per pass whatever count is), one product and one (. - c) / Z(g) launch over
 // count D elements.
 int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc) {
-    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, total = count * D;
+    const size_t total = count << r->log_d;
     char* a = (char*)abc;
     char *b = a + total * 32, *c = b + total * 32, *tmp = c + total * 32;
+    ZK_TRY(zk_groth16_witness_map_batch_pre(ctx, r, count, z, abc, tmp));
+    ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, a, b, a, total));
+    return zk_groth16_witness_map_batch_post(ctx, r, count, a, c, tmp);
+}
+
+// Its local half (zk_groth16_witness_map_pre_dev for count assignments): abc = a | b | c, count D elements each; a and b leave as
+// values on the coset, c as coefficients.  tmp: the transforms' scratch, 3 count D elements.
+int zk_groth16_witness_map_batch_pre(zk_ctx* ctx, const zk_r1cs* r, size_t count, const void* z, void* abc, void* tmp) {
+    const size_t D = (size_t)1 << r->log_d, m = r->ni + r->nw, total = count * D;
+    char* a = (char*)abc;
+    char *b = a + total * 32, *c = b + total * 32;
     const unsigned g = zk_grid(total, 256);
     for (int which = 0; which < 3; which++) {
         const auto& mt = r->m[which];
@@ -234,12 +245,17 @@ int zk_groth16_witness_map_batch(zk_ctx* ctx, const zk_r1cs* r, size_t count, co
     }
     ZK_HIP(ctx, hipGetLastError());
     ZK_TRY(zk_ntt_launch_strided(ctx, a, 3 * count, D, r->log_d, 1, 0, tmp));    // ifft of every a, b, c (a | b | c are one strided run)
-    ZK_TRY(zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 0, 1, tmp));    // coset_fft of every a and b
-    ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, a, b, a, total));
+    return zk_ntt_launch_strided(ctx, a, 2 * count, D, r->log_d, 0, 1, tmp);     // coset_fft of every a and b
+}
+
+// The half behind the product (zk_groth16_witness_map_post_dev for count products): ab = the count products on the coset, the count
+// quotients on return; c as the pre half left it.  tmp: count D elements.
+int zk_groth16_witness_map_batch_post(zk_ctx* ctx, const zk_r1cs* r, size_t count, void* ab, const void* c, void* tmp) {
+    const size_t D = (size_t)1 << r->log_d, total = count * D;
     Fr zinv;
     ZK_TRY(zk_ntt_vanishing_inv(ctx, r->log_d, &zinv));
-    ZK_TRY(zk_ntt_launch_strided(ctx, a, count, D, r->log_d, 1, 1, tmp));        // coset_ifft of every product
-    return zk_vec_sub_scale_launch(ctx, a, c, zinv, a, total);
+    ZK_TRY(zk_ntt_launch_strided(ctx, ab, count, D, r->log_d, 1, 1, tmp));       // coset_ifft of every product
+    return zk_vec_sub_scale_launch(ctx, ab, c, zinv, ab, total);
 }
 
 // The witness map for a key that carries h_eval (zk_pk::h_eval): it ends at e = a o b on the coset.  The rest of the map above -- c,

@@ -43,17 +43,43 @@ int zk_shared_triple_given(int lanes, const void* const tx[2], const void* const
     return dummy ? 0 : 1;
 }
 
+namespace {
+struct BeaverScratch { void *sxl[2], *oyl[2], *sx, *oy, *dx; };      // 2 * lanes + 3 vectors of n elements
+int beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
+               const void* const tx[2], const void* const ty[2], const void* const tz[2], const BeaverScratch& S);
+}  // namespace
+
 int zk_shared_beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
                          const void* const tx[2], const void* const ty[2], const void* const tz[2], const char* tag) {
     zk_ctx* ctx = nt.ctx;
-    const int given = zk_shared_triple_given(lanes, tx, ty, tz);
-    if (given < 0) ZK_FAIL(ctx, ZK_ERR_ARG, "batch_mul: give a whole Beaver triple (every lane) or none");
-    const bool dummy = !given;
-    void *sxl[2], *oyl[2], *sx, *oy, *dx;
+    if (zk_shared_triple_given(lanes, tx, ty, tz) < 0) ZK_FAIL(ctx, ZK_ERR_ARG, "batch_mul: give a whole Beaver triple (every lane) or none");
+    BeaverScratch S;
     char nm[64];
     auto buf = [&](const char* what, int l, void** p) { snprintf(nm, sizeof nm, "%s.%s%d", tag, what, l); return zk_scratch(ctx, nm, n * 32, p); };
-    for (int l = 0; l < lanes; l++) { ZK_TRY(buf("sxl", l, &sxl[l])); ZK_TRY(buf("oyl", l, &oyl[l])); }
-    ZK_TRY(buf("sx", 0, &sx)); ZK_TRY(buf("oy", 0, &oy)); ZK_TRY(buf("dx", 0, &dx));
+    for (int l = 0; l < lanes; l++) { ZK_TRY(buf("sxl", l, &S.sxl[l])); ZK_TRY(buf("oyl", l, &S.oyl[l])); }
+    ZK_TRY(buf("sx", 0, &S.sx)); ZK_TRY(buf("oy", 0, &S.oy)); ZK_TRY(buf("dx", 0, &S.dx));
+    return beaver_mul(nt, lanes, x, y, out, n, tx, ty, tz, S);
+}
+
+int zk_shared_beaver_mul_in(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
+                            const void* const tx[2], const void* const ty[2], const void* const tz[2], void* scratch) {
+    if (zk_shared_triple_given(lanes, tx, ty, tz) < 0) ZK_FAIL(nt.ctx, ZK_ERR_ARG, "batch_mul: give a whole Beaver triple (every lane) or none");
+    BeaverScratch S;
+    char* p = (char*)scratch;
+    auto cut = [&] { void* v = p; p += n * 32; return v; };
+    for (int l = 0; l < lanes; l++) { S.sxl[l] = cut(); S.oyl[l] = cut(); }
+    S.sx = cut(); S.oy = cut(); S.dx = cut();
+    return beaver_mul(nt, lanes, x, y, out, n, tx, ty, tz, S);
+}
+
+namespace {
+int beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
+               const void* const tx[2], const void* const ty[2], const void* const tz[2], const BeaverScratch& S) {
+    zk_ctx* ctx = nt.ctx;
+    const bool dummy = !zk_shared_triple_given(lanes, tx, ty, tz);
+    void* const* sxl = S.sxl;
+    void* const* oyl = S.oyl;
+    void *sx = S.sx, *oy = S.oy, *dx = S.dx;
     const Fr one_ext = fp_mul<FrParams>(fp_one<FrParams>(), fp_const<FrParams>(FrParams::INT_TO_EXT));
     for (int l = 0; l < lanes; l++) {
         if (dummy) {                                      // DummyFieldTripleSource: the leader holds 1 (in both lanes), the rest 0 (wire/field.rs:49-63)
@@ -81,6 +107,7 @@ int zk_shared_beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], con
     for (int l = 0; l < lanes; l++) ZK_TRY(zk_beaver_combine_dev(ctx, sx, oy, tx[l], ty[l], tz[l], out[l], n));
     return ZK_OK;
 }
+}  // namespace
 
 // ---- the small open's codec -------------------------------------------------------------------------------------------------------
 namespace zk_small {
@@ -94,37 +121,53 @@ void pack(const ZkSmallItems& it, uint64_t* msg) {
 }
 // one group's points of party p's message w added into acc; false: a peer's point is not a valid group element
 template <class H>
-bool add_points(const uint64_t* w, size_t n, bool peer, bool subgroup, std::vector<XYZZ<H>>& acc) {
+bool add_points(const uint8_t* msg, size_t n, bool peer, bool subgroup, std::vector<XYZZ<H>>& acc) {
     bool ok = true;
-    for (size_t i = 0; i < n; i++, w += 3 * H::WORDS / 2)
+    uint64_t w[3 * H::WORDS / 2];
+    for (size_t i = 0; i < n; i++, msg += sizeof w) {
+        memcpy(w, msg, sizeof w);
         acc[i] = xyzz_add<H>(acc[i], peer ? host64_peer_point<H>(w, subgroup, ok) : host64_proj_from_abi<H>(w));
+    }
     return ok;
 }
 template <class H, class P>
-void write_points(const std::vector<XYZZ<H>>& acc, std::vector<P>& out) {
+void write_points(const std::vector<XYZZ<H>>& acc, P* out) {
     const std::vector<Affine<H>> aff = host64_batch_to_affine<H>(acc);
-    out.resize(acc.size());
     for (size_t i = 0; i < acc.size(); i++) host64_write_projective<H>(aff[i], (uint64_t*)&out[i]);
 }
-Verdict sum(const uint8_t* all, int parties, int self, bool subgroup, size_t nf, size_t n1, size_t n2, ZkSmallItems* out) {
-    std::vector<uint64_t> w(words(nf, n1, n2));
-    std::vector<Fr> f(nf, fp_zero<FrParams>());
-    std::vector<XYZZ<H1>> g1(n1, xyzz_inf<H1>());
-    std::vector<XYZZ<H2>> g2(n2, xyzz_inf<H2>());
+template <class H, class P>
+void write_points(const std::vector<XYZZ<H>>& acc, std::vector<P>& out) {
+    out.resize(acc.size());
+    write_points<H, P>(acc, out.data());
+}
+Verdict sum_range(const uint8_t* all, int parties, int self, bool subgroup, size_t nf, size_t n1, size_t n2, const size_t lo[3],
+                  const size_t hi[3], ZkSmallItems* out) {
+    const size_t len = words(nf, n1, n2) * 8;
+    std::vector<Fr> f(hi[0] - lo[0], fp_zero<FrParams>());
+    std::vector<XYZZ<H1>> g1(hi[1] - lo[1], xyzz_inf<H1>());
+    std::vector<XYZZ<H2>> g2(hi[2] - lo[2], xyzz_inf<H2>());
     for (int p = 0; p < parties; p++) {
         const bool peer = p != self;
-        memcpy(w.data(), all + (size_t)p * w.size() * 8, w.size() * 8);
-        for (size_t i = 0; i < nf; i++) {
-            if (peer && !zk_fr_words_valid(&w[4 * i])) return BAD_SCALAR;
-            f[i] = fp_add<FrParams>(f[i], host_load_ext<FrParams>(&w[4 * i]));
+        const uint8_t* msg = all + (size_t)p * len;
+        for (size_t i = 0; i < f.size(); i++) {
+            uint64_t w[4];
+            memcpy(w, msg + 32 * (lo[0] + i), 32);
+            if (peer && !zk_fr_words_valid(w)) return BAD_SCALAR;
+            f[i] = fp_add<FrParams>(f[i], host_load_ext<FrParams>(w));
         }
-        if (!add_points<H1>(&w[4 * nf], n1, peer, subgroup, g1) || !add_points<H2>(&w[4 * nf + 18 * n1], n2, peer, subgroup, g2)) return BAD_POINT;
+        if (!add_points<H1>(msg + 32 * nf + 144 * lo[1], g1.size(), peer, subgroup, g1) ||
+            !add_points<H2>(msg + 32 * nf + 144 * n1 + 288 * lo[2], g2.size(), peer, subgroup, g2))
+            return BAD_POINT;
     }
-    out->fr.resize(nf);
-    for (size_t i = 0; i < nf; i++) host_store_ext<FrParams>(out->fr[i].l, f[i]);
-    write_points<H1>(g1, out->g1);
-    write_points<H2>(g2, out->g2);
+    for (size_t i = 0; i < f.size(); i++) host_store_ext<FrParams>(out->fr[lo[0] + i].l, f[i]);
+    write_points<H1>(g1, out->g1.data() + lo[1]);
+    write_points<H2>(g2, out->g2.data() + lo[2]);
     return OK;
+}
+Verdict sum(const uint8_t* all, int parties, int self, bool subgroup, size_t nf, size_t n1, size_t n2, ZkSmallItems* out) {
+    const size_t lo[3] = {0, 0, 0}, hi[3] = {nf, n1, n2};
+    out->fr.resize(nf); out->g1.resize(n1); out->g2.resize(n2);
+    return sum_range(all, parties, self, subgroup, nf, n1, n2, lo, hi, out);
 }
 template <class H, class P>
 void delta_points(bool leader, const std::vector<P>& opened, const std::vector<P>& mac, std::vector<P>& delta) {
@@ -161,7 +204,25 @@ int zk_shared_open_small(ZkSharedNet& nt, int lanes, const ZkSmallItems items[2]
     auto exchange = [&](const ZkSmallItems& mine, ZkSmallItems* sums) -> int {
         zk_small::pack(mine, msg.data());
         ZK_TRY(nt.gather((const uint8_t*)msg.data(), words * 8, all));
-        const zk_small::Verdict v = zk_small::sum(all.data(), nt.parties(), ctx->party_id, lanes == 2, nf, n1, n2, sums);
+        zk_small::Verdict v = zk_small::OK;
+        if (nt.parties() > 1 && n1 + n2 >= ZK_SMALL_PARALLEL_POINTS) {
+            // a batch's open: what peers sent is validated item by item (under SPDZ with the subgroup test), over ranges of items
+            const size_t tasks = std::min<size_t>(16, std::max(n1, n2));
+            std::vector<zk_small::Verdict> vs(tasks, zk_small::OK);
+            sums->fr.resize(nf); sums->g1.resize(n1); sums->g2.resize(n2);
+            std::vector<ZkTask<void>> ts;
+            auto part = [&](size_t t) {
+                const size_t lo[3] = {nf * t / tasks, n1 * t / tasks, n2 * t / tasks};
+                const size_t hi[3] = {nf * (t + 1) / tasks, n1 * (t + 1) / tasks, n2 * (t + 1) / tasks};
+                vs[t] = zk_small::sum_range(all.data(), nt.parties(), ctx->party_id, lanes == 2, nf, n1, n2, lo, hi, sums);
+            };
+            for (size_t t = 1; t < tasks; t++) ts.push_back(zk_async(ctx, [&part, t] { part(t); }));
+            part(0);
+            for (auto& t : ts) t.get();
+            for (const zk_small::Verdict x : vs) v = std::max(v, x);      // (a bad point outranks a bad scalar: either is ZK_ERR_STATE)
+        } else {
+            v = zk_small::sum(all.data(), nt.parties(), ctx->party_id, lanes == 2, nf, n1, n2, sums);
+        }
         if (v == zk_small::BAD_SCALAR) ZK_FAIL(ctx, ZK_ERR_STATE, "small open: a party sent a non-canonical field element");
         if (v == zk_small::BAD_POINT) ZK_FAIL(ctx, ZK_ERR_STATE, "small open: a party sent a point that is not a valid group element");
         return ZK_OK;

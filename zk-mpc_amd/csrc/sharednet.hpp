@@ -50,6 +50,10 @@ int zk_shared_triple_given(int lanes, const void* const tx[2], const void* const
 // lane).  out[l] may alias x[l].  scratch: 2 * lanes + 3 vectors of n elements, named by `tag` in the context's arena.
 int zk_shared_beaver_mul(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
                          const void* const tx[2], const void* const ty[2], const void* const tz[2], const char* tag);
+// The same with the scratch in a buffer of the caller's: (2 * lanes + 3) * n elements (a batch's product grows with its count and
+// is an allocation of that call, not of the arena)
+int zk_shared_beaver_mul_in(ZkSharedNet& nt, int lanes, const void* const x[2], const void* const y[2], void* const out[2], size_t n,
+                            const void* const tx[2], const void* const ty[2], const void* const tz[2], void* scratch);
 
 // ---- the small open: O(1) values per exchange, summed over the parties ----------------------------------------------------------
 // Items travel in ABI form, which is the wire form: fr | g1 | g2 at 4 / 18 / 36 words per item (mpc.py: Party._open_many).
@@ -67,10 +71,16 @@ void pack(const ZkSmallItems& items, uint64_t* msg);
 // must be: scalars below r; coordinates below q, Z = 0 or Montgomery one, on the curve and -- `subgroup`: under SPDZ -- in the prime-order
 // subgroup (hostfield64.hpp: host64_peer_point).  The slot of `self` is this party's own output and taken as is.
 Verdict sum(const uint8_t* all, int parties, int self, bool subgroup, size_t nf, size_t n1, size_t n2, ZkSmallItems* out);
+// The same for the items [lo[k], hi[k]) of each kind k = 0 (fr), 1 (g1), 2 (g2) alone, into *out sized for all of them already: items are
+// validated and summed one by one, so disjoint ranges may run side by side (zk_shared_open_small: a batch's open over the helper threads)
+Verdict sum_range(const uint8_t* all, int parties, int self, bool subgroup, size_t nf, size_t n1, size_t n2, const size_t lo[3],
+                  const size_t hi[3], ZkSmallItems* out);
 void mac_delta(bool leader, const ZkSmallItems& opened, const ZkSmallItems& mac, ZkSmallItems* delta);   // [leader ? opened : 0] - mac
 bool all_zero(const ZkSmallItems& items);
 }  // namespace zk_small
 // The driver: items[0] = this party's shares, ONE gather of 8 * words bytes, *opened = the sums (Additive{Field,Group}Share::open).  lanes = 2
 // (SPDZ): items[1] = the MAC shares; a second gather publishes the deltas and every sum must vanish (SpdzFieldShare::batch_open, SpdzGroupShare::
 // open, key alpha = 1 held by the leader) -- otherwise ZK_ERR_MAC.  An invalid payload from a peer is ZK_ERR_STATE.  No items: no exchange.
+// An open of ZK_SMALL_PARALLEL_POINTS points or more (a batch's) validates and sums over ranges of items on at most 16 helper threads.
+constexpr size_t ZK_SMALL_PARALLEL_POINTS = 8;
 int zk_shared_open_small(ZkSharedNet& nt, int lanes, const ZkSmallItems items[2], ZkSmallItems* opened);

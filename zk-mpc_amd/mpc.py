@@ -633,6 +633,29 @@ class Party:
         self.bytes_sent += int(sent.value)
         return out.tobytes()
 
+    def create_proofs_shared_native(self, pk, r1cs, z_shares, r_shares, s_shares, triple=None) -> list:
+        """count proofs over additive shares as ONE library call with the exchanges of ONE proof (zk_groth16_prove_shared_batch).
+        z_shares: device pointer of the count assignments back to back (assignment k at k * m elements); r_shares / s_shares: count
+        scalars; triple: three device pointers of count * D Beaver shares each, or None for dummy triples.  Every party must pass
+        the same count.  Returns the count proofs, proof k the bytes of create_proof_shared_native for (z_k, r_k, s_k, triple_k)."""
+        import ctypes as C
+        ctx = self.ctx
+        count = len(r_shares)
+        if len(s_shares) != count:
+            raise ValueError("create_proofs_shared_native: r_shares and s_shares hold one scalar per proof")
+        vt, errors, _keep = self._net_vtable()
+        r, s_ = _fr_array(r_shares), _fr_array(s_shares)
+        out = np.zeros(192 * count, dtype=np.uint8)
+        sent = C.c_uint64(0)
+        t = [C.c_void_p(int(x)) for x in triple] if triple is not None else [None, None, None]
+        rc = ctx.lib.zk_groth16_prove_shared_batch(ctx.h, pk.h, r1cs.h, count, C.c_void_p(int(z_shares)), r, s_, t[0], t[1], t[2],
+                                                   C.byref(vt) if self.net.n > 1 else None, out.ctypes.data_as(C.c_void_p), C.byref(sent))
+        if errors:
+            raise errors[0]
+        ctx._ck(rc)
+        self.bytes_sent += int(sent.value)
+        return [out[192 * k:192 * (k + 1)].tobytes() for k in range(count)]
+
     def marlin_prove_shared_native(self, keys, z_share, zk_rng, triple=None, mask_on_device=False) -> bytes:
         """MpcMarlin::prove over additive shares as ONE library call (zk_marlin_prove_shared): what a Rust host would bind.
         Arguments as marlin_prove_full (triple: three device pointers of |MUL| Beaver shares, or None for dummy triples);
@@ -646,6 +669,13 @@ class Party:
 
 class MacCheckError(RuntimeError):
     pass
+
+
+def _fr_array(values):
+    """A C array of zk_fr from a list of 4-limb Montgomery scalars (one element at least, so that an empty list still has an address)."""
+    from . import _lib
+    from .api import _fr_struct
+    return (_lib.Fr * max(len(values), 1))(*[_fr_struct(x) for x in values])
 
 
 class SpdzParty(Party):
@@ -785,6 +815,37 @@ class SpdzParty(Party):
         ctx._ck(rc)
         self.bytes_sent += int(sent.value)
         return out.tobytes()
+
+    def create_proofs_shared_spdz_native(self, pk, r1cs, z_shares, r_shares, s_shares, triple=None, out=None) -> list:
+        """count proofs over SPDZ shares as ONE library call with the exchanges of ONE proof (zk_groth16_prove_shared_spdz_batch).
+        z_shares = (share, MAC) device pointers of count assignments each; r_shares / s_shares = (share, MAC) lists of count scalars;
+        triple = ((x, x_mac), (y, y_mac), (z, z_mac)) device pointers of count * D elements each, or None.  out: a uint8 array of
+        192 * count bytes to write the proofs to (a failed MAC check -- MacCheckError -- leaves it as it was)."""
+        import ctypes as C
+        ctx = self.ctx
+        count = len(r_shares[0])
+        if any(len(v) != count for v in (r_shares[1], s_shares[0], s_shares[1])):
+            raise ValueError("create_proofs_shared_spdz_native: every lane of r_shares and s_shares holds one scalar per proof")
+        vt, errors, _keep = self._net_vtable()
+        P2 = C.c_void_p * 2
+        lanes = lambda v: P2(int(v[0]), int(v[1]))
+        keep = [_fr_array(v) for v in (r_shares[0], r_shares[1], s_shares[0], s_shares[1])]
+        addr = lambda a: C.cast(a, C.c_void_p).value
+        rl, sl = P2(addr(keep[0]), addr(keep[1])), P2(addr(keep[2]), addr(keep[3]))
+        t = [lanes((triple[k][0], triple[k][1])) for k in range(3)] if triple is not None else [None, None, None]
+        if out is None:
+            out = np.zeros(192 * count, dtype=np.uint8)
+        sent = C.c_uint64(0)
+        rc = ctx.lib.zk_groth16_prove_shared_spdz_batch(ctx.h, pk.h, r1cs.h, count, lanes(z_shares), rl, sl, t[0], t[1], t[2],
+                                                        C.byref(vt) if self.net.n > 1 else None, out.ctypes.data_as(C.c_void_p),
+                                                        C.byref(sent))
+        if errors:
+            raise errors[0]
+        if rc == -5:
+            raise MacCheckError((ctx.lib.zk_last_error(ctx.h) or b"").decode())
+        ctx._ck(rc)
+        self.bytes_sent += int(sent.value)
+        return [out[192 * k:192 * (k + 1)].tobytes() for k in range(count)]
 
     def marlin_prove_shared_spdz_native(self, keys, z_share, zk_rng, triple=None, mask_on_device=False) -> bytes:
         """The same over SPDZ shares (zk_marlin_prove_shared_spdz): z_share = (share, MAC) DevBufs, triple = ((x, x_mac), (y, y_mac),
