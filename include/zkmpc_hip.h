@@ -532,6 +532,51 @@ int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_i
 /* ... with the subgroup test on A, B, C (the host instantiation of the same code). */
 int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok);
 
+/* ---- aggregated Groth16 verification: count proofs of one key as ONE folded pairing product (csrc/verify_aggregate.hip) --------- */
+/* With 128-bit coefficients r_i the batch is accepted iff
+ *     prod_i e(r_i A_i, B_i) . e(sum_i r_i C_i, -delta) . e(sum_j s_j gamma_abc[j], -gamma) . e(s_0 alpha, -beta) = 1,
+ *     s_0 = sum_i r_i,  s_j = sum_i r_i x_{i,j} (mod r; x_{i,0} = 1),
+ * which is count + 3 Miller loops and ONE final exponentiation where zk_groth16_verify_batch runs 3 count and count.  If every proof
+ * is valid the product is one whatever the coefficients are; if one is not, it is one for about 2^-128 of the coefficient vectors.
+ * That bound holds only for coefficients the prover(s) could not predict: proofs (A, B, C_0 + D) and (A', B', C_1 - D) pass
+ * together under the coefficients (1, 1).  Draw them after the proofs arrived (zk_groth16_verify_aggregate draws from a seed).
+ * The subgroup test of Proof::deserialize ALWAYS runs on A, B, C (the fold's argument needs groups of prime order, and the Miller loop
+ * is not bilinear for a B outside G2): a valid proof whose A or C was moved by a point of the cofactor torsion gets 0 here, as from
+ * zk_groth16_verify_batch_checked, where zk_groth16_verify_batch answers 1.
+ *   coeffs   2 uint64 per proof (low, high), any values; a zero coefficient drops its proof from the check (the caller's business)
+ *   ok_all   1 iff every point decodes canonically, lies in its prime-order subgroup and the folded product is one
+ *   folded   (or NULL) the product's GT value in the ABI's form (exponent ZK_GT_EXPONENT_MULTIPLE (q^12 - 1) / r); all-zero words
+ *            when a point was rejected before the pairing
+ * ZK_ERR_ARG: what zk_groth16_verify_batch refuses, a null coeffs, count + 3 above 2^22 (one Miller lane per proof and three for
+ * the key).  The launches do not grow with count beyond the logarithmic re-launches of the two fold kernels.  The ninp + 2
+ * full-width multiplications of key points run on the host's helper threads under the device work; a key with very many public
+ * inputs would want a multi-vector MSM over gamma_abc instead, which is not built. */
+int zk_groth16_verify_aggregate_coeffs(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                       const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+/* The same arithmetic on the host: no device, no context (tests, O(1) batches). */
+int zk_groth16_verify_aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size_t inputs_per_proof,
+                                     const uint8_t* proofs, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+/* Coefficients from a 32-byte seed that the prover(s) must not have been able to predict (draw it after the proofs arrived): the
+ * library's ChaCha20 stream of the seed (zk_rng_from_seed with 20 rounds, zk_rng_next_u128 per proof: 16 bytes, low word first), a
+ * zero draw replaced by 1.  The draws for count proofs are a prefix of those for more. */
+int zk_verify_aggregate_coeffs_from_seed(const uint8_t seed[32], size_t count, uint64_t* coeffs_out);
+/* The seeded form.  ok_each (or NULL): all ones when ok_all = 1; otherwise the verdicts of zk_groth16_verify_batch_checked, which is
+ * run to locate the bad proofs.  Also ZK_ERR_ARG for a null seed. */
+int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each);
+/* PairingEngine::product_of_pairings for ONE long product: final_exponentiation(prod_{k < n} miller_loop(p[k], q[k])), the Miller
+ * loops one per lane, their values folded by k_fq12_fold (a wave per block: a serial product per lane, then a tree through LDS),
+ * the final exponentiation on the host; points as zk_pairing_products takes them.  n = 0, n above 2^22 or a null pointer: ZK_ERR_ARG. */
+int zk_pairing_product_long(zk_ctx* ctx, const zk_g1_affine* p, const zk_g2_affine* q, size_t n, zk_gt* out);
+/* Test hooks: the two fold kernels alone.  zk_diag_fq12_fold_dev: out = the product of in[0 .. n) through k_fq12_fold ALONE (it is
+ * re-launched until one value is left; 1 <= n <= 2^22, coordinate words below q); zk_diag_fq12_fold_span: the values one block takes.
+ * zk_diag_g1_scale_sum_dev: k_g1_scale_fold over n <= 2^22 points with 128-bit coefficients (2 uint64 each; NULL: the plain sum):
+ * scaled_out (or NULL) = coeffs[i] pts[i] as affine points, sum_out = their sum. */
+int zk_diag_fq12_fold_dev(zk_ctx* ctx, const zk_gt* in, size_t n, zk_gt* out);
+size_t zk_diag_fq12_fold_span(void);
+int zk_diag_g1_scale_sum_dev(zk_ctx* ctx, const zk_g1_affine* pts, const uint64_t* coeffs, size_t n, zk_g1_affine* scaled_out,
+                             zk_g1_projective* sum_out);
+
 /* ---- Marlin verification ------------------------------------------------------------------------------------------------------ */
 /* Marlin::verify (arkworks/marlin/src/lib.rs:324-442) with MarlinKZG10::check_combinations, for proofs as zk_marlin_prove writes them
  * (CanonicalSerialize of marlin::Proof).  The key is a host view: the IndexVerifierKey's bytes as the transcript absorbs them and

@@ -331,6 +331,14 @@ PROTOTYPES = {
     "zk_marlin_vk_from_index": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "zk_diag_marlin_shape_host": (_I, [_P, _I, _P, _P, _P, _SZ, _P]),
     "zk_diag_small_open_host": (_I, [_I, _I, _I, _I, _SZ, _SZ, _SZ, _P, _P, C.POINTER(_I)]),
+    "zk_groth16_verify_aggregate_coeffs": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_groth16_verify_aggregate_host": (_I, [_P, _SZ, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_verify_aggregate_coeffs_from_seed": (_I, [_P, _SZ, _P]),
+    "zk_groth16_verify_aggregate": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_pairing_product_long": (_I, [_P, _P, _P, _SZ, _P]),
+    "zk_diag_fq12_fold_dev": (_I, [_P, _P, _SZ, _P]),
+    "zk_diag_fq12_fold_span": (_SZ, []),
+    "zk_diag_g1_scale_sum_dev": (_I, [_P, _P, _P, _SZ, _P, _P]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@ All arithmetic happens in libzkmpc_hip.so; this file only moves buffers and chec
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -911,6 +912,54 @@ class Context:
         """Groth16::verify of one proof as create_proof returns it (device path)."""
         return bool(self.groth16_verify_batch(pk, np.asarray(inputs_mont, dtype=np.uint64).reshape(1, -1, 4), proof, check_subgroup)[0])
 
+    # ---- aggregated verification (csrc/verify_aggregate.hip) ----
+    def groth16_verify_aggregate(self, pk: "ProvingKey", inputs_mont: np.ndarray, proofs, seed: bytes = None, coeffs=None, each: bool = False):
+        """Many proofs of one key as ONE folded pairing product (count + 3 Miller loops, one final exponentiation); the subgroup test
+        always runs.  coeffs (count, 2) uint64 (low, high): zk_groth16_verify_aggregate_coeffs -> (ok_all, folded GT value (72,)).
+        Otherwise the seeded form, seed = 32 bytes the provers could not predict (None: os.urandom) -> ok_all, or with `each`
+        (ok_all, count verdicts: all ones, or those of groth16_verify_batch(check_subgroup=True) when the fold fails)."""
+        data, count, inp, buf = _aggregate_args(inputs_mont, proofs)
+        ok = C.c_int(0)
+        if coeffs is not None:
+            if seed is not None or each:
+                raise ValueError("groth16_verify_aggregate: coeffs excludes seed and each")
+            co = _coeff_array(coeffs, count)
+            folded = np.zeros(72, dtype=np.uint64)
+            self._ck(self.lib.zk_groth16_verify_aggregate_coeffs(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(co), C.byref(ok), _ptr(folded)))
+            return bool(ok.value), folded
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("a seed is 32 bytes")
+        ok_each = np.zeros(max(count, 1), dtype=np.int32) if each else None
+        self._ck(self.lib.zk_groth16_verify_aggregate(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), seed, C.byref(ok),
+                                                      _ptr(ok_each) if each else None))
+        return (bool(ok.value), ok_each[:count]) if each else bool(ok.value)
+
+    def pairing_product_long(self, p: np.ndarray, q: np.ndarray) -> np.ndarray:
+        """final_exponentiation(prod_k miller_loop(p[k], q[k])) of ONE long product: p (n, 12), q (n, 24) uint64 -> the GT value (72,)."""
+        p, q, _ = _pairing_args(p, q, 1)
+        out = np.zeros(72, dtype=np.uint64)
+        self._ck(self.lib.zk_pairing_product_long(self.h, _ptr(p), _ptr(q), p.shape[0], _ptr(out)))
+        return out
+
+    def diag_fq12_fold(self, values: np.ndarray) -> np.ndarray:
+        """Test hook: the product of the (n, 72) GT-form values through k_fq12_fold alone."""
+        v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 72)
+        out = np.zeros(72, dtype=np.uint64)
+        self._ck(self.lib.zk_diag_fq12_fold_dev(self.h, _ptr(v), v.shape[0], _ptr(out)))
+        return out
+
+    def diag_g1_scale_sum(self, points: np.ndarray, coeffs=None, scaled: bool = True):
+        """Test hook: k_g1_scale_fold over points (n, 12) with 128-bit coefficients (n, 2) uint64 (None: the plain sum) ->
+        (coeffs[i] points[i] as (n, 12) affine or None, the sum as a (18,) projective point)."""
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+        co = None if coeffs is None else _coeff_array(coeffs, pts.shape[0])
+        out = np.zeros((pts.shape[0], 12), dtype=np.uint64) if scaled else None
+        total = np.zeros(18, dtype=np.uint64)
+        self._ck(self.lib.zk_diag_g1_scale_sum_dev(self.h, _ptr(pts), None if co is None else _ptr(co), pts.shape[0],
+                                                   _ptr(out) if scaled else None, _ptr(total)))
+        return out, total
+
     def diag_fq12(self, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         """Test hook: the Fq12 tower on the device, one case (a[i], b[i]) per lane; a, b (n, 72) uint64."""
         cases = np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.uint64)
@@ -1054,6 +1103,11 @@ class ProvingKey:
         return groth16_verify_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont, proof,
                                    check_subgroup)
 
+    def verify_aggregate_host(self, inputs_mont, proofs, coeffs):
+        """groth16_verify_aggregate_host on this key's verifying-key parts -> (ok_all, folded)."""
+        return groth16_verify_aggregate_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont,
+                                             proofs, coeffs)
+
     def free(self):
         if self.h:
             self.ctx.lib.zk_pk_free(self.ctx.h, self.h)
@@ -1174,10 +1228,8 @@ def points_deserialize_host(data: bytes, n: int, group: int, compressed: bool):
     return pts[:n], status[:n]
 
 
-def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes, check_subgroup: bool = False) -> bool:
-    """Groth16::verify of one proof through the host arithmetic, on a host view of the VerifyingKey (points as uint64 arrays in the
-    ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery.  check_subgroup: A, B, C also pass
-    Proof::deserialize's subgroup test (zk_groth16_verify_host_checked)."""
+def _vk_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+    """A zk_vk_host over uint64 arrays in the ABI's form, and the gamma_abc array it points into (keep it alive for the call)."""
     vk = _lib.VkHost()
     abc = np.ascontiguousarray(gamma_abc_g1, dtype=np.uint64).reshape(-1, 12)
     for field, arr, n in (("alpha_g1", alpha_g1, 12), ("beta_g2", beta_g2, 24), ("gamma_g2", gamma_g2, 24), ("delta_g2", delta_g2, 24)):
@@ -1185,6 +1237,14 @@ def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inp
         assert arr.size == n
         C.memmove(C.addressof(getattr(vk, field)), arr.ctypes.data, n * 8)
     vk.gamma_abc_g1, vk.gamma_abc_len = abc.ctypes.data, abc.shape[0]
+    return vk, abc
+
+
+def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proof: bytes, check_subgroup: bool = False) -> bool:
+    """Groth16::verify of one proof through the host arithmetic, on a host view of the VerifyingKey (points as uint64 arrays in the
+    ABI's form, gamma_abc_g1 (num_instance, 12)); inputs_mont (num_instance - 1, 4) Montgomery.  check_subgroup: A, B, C also pass
+    Proof::deserialize's subgroup test (zk_groth16_verify_host_checked)."""
+    vk, _abc = _vk_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1)
     inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(-1, 4)
     if len(proof) != 192:
         raise ValueError("a proof is 192 bytes")
@@ -1193,3 +1253,47 @@ def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inp
     fn = _lib.load().zk_groth16_verify_host_checked if check_subgroup else _lib.load().zk_groth16_verify_host
     _ck_host(fn(C.byref(vk), _ptr(inp), inp.shape[0], _ptr(buf), C.byref(ok)), "zk_groth16_verify_host")
     return bool(ok.value)
+
+
+# ---- aggregated Groth16 verification: the host forms ----
+def _aggregate_args(inputs_mont, proofs):
+    data = b"".join(proofs) if isinstance(proofs, (list, tuple)) else bytes(proofs)
+    if len(data) % 192:
+        raise ValueError("proofs must be a whole number of 192-byte proofs")
+    count = len(data) // 192
+    inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(count, -1, 4) if count else np.zeros((0, 0, 4), np.uint64)
+    return data, count, inp, np.frombuffer(data, dtype=np.uint8)
+
+
+def _coeff_array(coeffs, count):
+    """(count, 2) uint64 (low, high) from such an array or from count Python integers below 2^128."""
+    if isinstance(coeffs, np.ndarray):
+        co = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 2)
+    else:
+        co = np.array([[int(c) & ((1 << 64) - 1), int(c) >> 64] for c in coeffs], dtype=np.uint64).reshape(-1, 2)
+    if co.shape[0] != count:
+        raise ValueError("one 128-bit coefficient per proof")
+    return co
+
+
+def verify_aggregate_coeffs_from_seed(seed: bytes, count: int) -> np.ndarray:
+    """zk_verify_aggregate_coeffs_from_seed: count 128-bit coefficients as (count, 2) uint64 (low, high), none of them zero."""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    out = np.zeros((count, 2), dtype=np.uint64)
+    _ck_host(_lib.load().zk_verify_aggregate_coeffs_from_seed(seed, count, _ptr(out) if count else None), "zk_verify_aggregate_coeffs_from_seed")
+    return out
+
+
+def groth16_verify_aggregate_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont, proofs, coeffs):
+    """zk_groth16_verify_aggregate_host: the folded check of count proofs through the host arithmetic, on a host view of the
+    VerifyingKey (as groth16_verify_host takes it); coeffs (count, 2) uint64 or count integers -> (ok_all, folded GT value (72,))."""
+    vk, _abc = _vk_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1)
+    data, count, inp, buf = _aggregate_args(inputs_mont, proofs)
+    co = _coeff_array(coeffs, count)
+    ok = C.c_int(0)
+    folded = np.zeros(72, dtype=np.uint64)
+    _ck_host(_lib.load().zk_groth16_verify_aggregate_host(C.byref(vk), count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(co), C.byref(ok), _ptr(folded)),
+             "zk_groth16_verify_aggregate_host")
+    return bool(ok.value), folded

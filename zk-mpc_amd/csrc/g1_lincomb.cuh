@@ -21,11 +21,12 @@ constexpr int LINCOMB_MAX_TERMS = 64;    // terms of a segment: one wave
 
 // Tab: void put(int e, const XYZZ<F>&), XYZZ<F> get(int e) for e < LINCOMB_TAB -- the device keeps it in LDS (an entry chosen by a
 // per-lane digit is an address there, not an index into a register array), the host in a local array.
-template <class F, class Tab>
-ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[8], Tab& tab) {
-    uint32_t kk[8], carry = 0;
+// NW: 32-bit words of k (8: the 256 raw bits above; 4: a 128-bit coefficient, half the windows -- verify_aggregate.hip)
+template <class F, class Tab, int NW = 8>
+ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[NW], Tab& tab) {
+    uint32_t kk[NW], carry = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
+    for (int i = 0; i < NW; i++) {
         const uint64_t t = (uint64_t)k[i] + 0x88888888u + carry;
         kk[i] = (uint32_t)t;
         carry = (uint32_t)(t >> 32);
@@ -40,12 +41,12 @@ ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[8], Tab& tab) {
     }
     XYZZ<F> acc = carry ? P : xyzz_inf<F>();
 #pragma unroll 1
-    for (int w = 63; w >= 0; w--) {
+    for (int w = 8 * NW - 1; w >= 0; w--) {
 #pragma unroll 1
         for (int j = 0; j < 4; j++) acc = xyzz_dbl<F>(acc);
-        const int d = (int)(kk[7] >> 28) - 8;
+        const int d = (int)(kk[NW - 1] >> 28) - 8;
 #pragma unroll
-        for (int i = 7; i > 0; i--) kk[i] = (kk[i] << 4) | (kk[i - 1] >> 28);
+        for (int i = NW - 1; i > 0; i--) kk[i] = (kk[i] << 4) | (kk[i - 1] >> 28);
         kk[0] <<= 4;
         const int m = d < 0 ? -d : d;
         XYZZ<F> t = tab.get(m ? m - 1 : 0);

@@ -34,7 +34,7 @@ enum ZkFrForm { ZK_FR_EXT = 0, ZK_FR_TABLE = 1 };
 int zk_fr_powers_launch(zk_ctx* ctx, const zk::Fr& base, const zk::Fr& start, size_t n, void* out, ZkFrForm form);
 
 // The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
-enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_COUNT };
+enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_SCALE_FOLD, ZK_LDS_COUNT };
 static_assert(ZK_LDS_COUNT <= sizeof(zk_ctx::lds_attr_done), "zk_ctx::lds_attr_done is too short");
 
 // rng.hip: four little-endian 64-bit words are a canonical field element (< r): what Fr::rand keeps and what a prover accepts from a peer
@@ -298,6 +298,7 @@ bool zk_host_in_subgroup_g2(const zk::Affine<zk::G2Field>& p);
 // pairing.hip: its Miller-loop and finish kernels for pairs that are on the device already (table form); lanes in one launch at most
 constexpr size_t ZK_PAIRING_MAX_LANES = (size_t)1 << 22;
 int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev);
+int zk_miller_ext_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev);   // ... points as the ABI's structs
 int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, const uint32_t* want_dev, const uint32_t* bad_dev, int* ok_dev);
 // g1_lincomb.hip: n_segments short linear combinations of G1 points in one launch, one term per lane.  Lane g holds point
 // point_index[g] of points_dev (table form; n_points of them) and the raw 256-bit scalar scalars_dev[8 g ..]; segment s is the lanes

@@ -170,6 +170,11 @@ int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, 
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
+int zk_miller_ext_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev) {
+    hipLaunchKernelGGL(k_miller<true>, blocks64(n), 64, 0, ctx->stream, p_dev, q_dev, n, ml_dev);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
 int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, const uint32_t* want_dev, const uint32_t* bad_dev, int* ok_dev) {
     hipLaunchKernelGGL(k_pairing_finish, blocks64(count), 64, 0, ctx->stream, ml_dev, pairs, count, (uint32_t*)nullptr, want_dev, bad_dev, ok_dev);
     ZK_HIP(ctx, hipGetLastError());
