@@ -1022,6 +1022,47 @@ int zk_diag_g1_mul_glv(const zk_g1_projective* a, const zk_fr* k, zk_g1_projecti
  * self outside the parties or lanes outside 1 .. 2. */
 int zk_diag_small_open_host(int parties, int self, int lanes, int subgroup, size_t nf, size_t n1, size_t n2, const uint64_t* shares,
                             uint64_t* opened, int* verdict);
+/* Test hook: which kernels an MSM job was sent to.  Every job whose reduce chain has been enqueued on the context leaves one record
+ * of what the dispatch code decided for it, each field stored at the place that decides it (csrc/msm.hip, csrc/msm_batch.hip,
+ * csrc/msm_g2pair.hip) -- plain stores on the host, nothing on the device.  The context keeps the last ZK_MSM_PLAN_RING records;
+ * older ones are dropped.  zk_diag_msm_plans copies the records since its previous call to out[0 .. cap), oldest first, stores their
+ * number in *n_out and forgets them (records beyond cap are forgotten too).  out may be NULL with cap = 0: forget all.
+ *   table          what the accumulate kernel gathers from
+ *   sort           which sort made the job's segments; BORROWED: another job's over the same scalar vector
+ *   accum / fold   the launch (one job or a group of jobs) and the lanes that share one point addition (1, 2 or 4)
+ *   reduce         the point policy of the grid reduce (csrc/msm_reduce.cuh)
+ *   jobs, vectors  jobs in the accumulate launch; scalar vectors in the job (zk_msm_*_multi_dev: more than one)
+ *   n              scalars of the job (all vectors); W windows of at most c bits, window w = scalar bits [off[w], off[w + 1]);
+ *                  Wb bucket sets (all vectors) of NB buckets; a reduce window has 2^log_nb buckets; M shifted copies of the table;
+ *                  seg = the longest segment one lane adds up before a fold (the bucket sort may settle on a shorter one) */
+#define ZK_MSM_PLAN_RING 64
+#define ZK_PLAN_TABLE_PLAIN 0        /* the points themselves: one bucket set per window */
+#define ZK_PLAN_TABLE_PACKED 1       /* window multiples, packed (96 | 192 bytes per point) */
+#define ZK_PLAN_TABLE_LINE 2         /* window multiples, one G1 point per 128-byte line */
+#define ZK_PLAN_TABLE_LIMBS 3        /* window multiples, G1 limbs with both signs (256 bytes per point) */
+#define ZK_PLAN_SORT_NONE 0
+#define ZK_PLAN_SORT_ONE_BLOCK 1
+#define ZK_PLAN_SORT_ONE_BLOCK_GROUP 2
+#define ZK_PLAN_SORT_COUNTING 3
+#define ZK_PLAN_SORT_BUCKET 4
+#define ZK_PLAN_SORT_BORROWED 5
+#define ZK_PLAN_LAUNCH_NONE 0
+#define ZK_PLAN_LAUNCH_SINGLE 1
+#define ZK_PLAN_LAUNCH_GROUP 2
+#define ZK_PLAN_RED_NONE 0
+#define ZK_PLAN_RED_G1 1
+#define ZK_PLAN_RED_G1_DUAL 2
+#define ZK_PLAN_RED_G2_PAIR 3
+#define ZK_PLAN_RED_G2_QUAD 4
+typedef struct {
+    uint32_t group, table, sort;
+    uint32_t accum_launch, accum_lanes, fold_launch, fold_lanes, reduce;
+    uint32_t jobs, vectors;
+    uint32_t c, W, Wb, NB, log_nb, M, seg;
+    uint32_t off[65];
+    uint64_t n;
+} zk_msm_plan;
+int zk_diag_msm_plans(zk_ctx* ctx, zk_msm_plan* out, size_t cap, size_t* n_out);
 
 #ifdef __cplusplus
 }

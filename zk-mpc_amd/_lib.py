@@ -85,6 +85,20 @@ class PkSubgroupReport(C.Structure):
     _fields_ = [("outside", C.c_size_t * 7), ("first", C.c_size_t * 7)]
 
 
+class MsmPlan(C.Structure):
+    """zk_msm_plan: what the dispatch code decided for one MSM job (zk_diag_msm_plans)."""
+    _fields_ = [(n, C.c_uint32) for n in ("group", "table", "sort", "accum_launch", "accum_lanes", "fold_launch", "fold_lanes", "reduce",
+                                          "jobs", "vectors", "c", "W", "Wb", "NB", "log_nb", "M", "seg")]
+    _fields_ += [("off", C.c_uint32 * 65), ("n", C.c_uint64)]
+
+
+MSM_PLAN_RING = 64
+PLAN_TABLE = ("plain", "packed", "line", "limbs")
+PLAN_SORT = ("none", "one_block", "one_block_group", "counting", "bucket", "borrowed")
+PLAN_LAUNCH = ("none", "single", "group")
+PLAN_REDUCE = ("none", "RedG1", "RedG1Dual", "RedG2Pair", "RedG2Quad")
+
+
 class R1csHost(C.Structure):
     _fields_ = [("num_constraints", C.c_size_t), ("num_instance", C.c_size_t), ("num_witness", C.c_size_t),
                 ("a_row_ptr", C.c_void_p), ("a_col", C.c_void_p), ("a_coeff", C.c_void_p),
@@ -339,6 +353,7 @@ PROTOTYPES = {
     "zk_diag_fq12_fold_dev": (_I, [_P, _P, _SZ, _P]),
     "zk_diag_fq12_fold_span": (_SZ, []),
     "zk_diag_g1_scale_sum_dev": (_I, [_P, _P, _P, _SZ, _P, _P]),
+    "zk_diag_msm_plans": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
 }
 
 _lib = None

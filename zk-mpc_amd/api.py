@@ -309,6 +309,21 @@ class Context:
         k = self.lib.zk_last_timers(self.h, names, 64, ms, cnt, 64)
         return {names.raw[i * 64:(i + 1) * 64].split(b"\0")[0].decode(): (float(ms[i]), int(cnt[i])) for i in range(k)}
 
+    def msm_plans(self) -> list:
+        """zk_diag_msm_plans: one dict per MSM job enqueued on this context since the previous call, oldest first -- which table form,
+        sort, accumulate and fold launch (and lanes per addition) and reduce policy the dispatch code chose, and the job's geometry."""
+        recs = (_lib.MsmPlan * _lib.MSM_PLAN_RING)()
+        k = C.c_size_t(0)
+        self._ck(self.lib.zk_diag_msm_plans(self.h, recs, _lib.MSM_PLAN_RING, C.byref(k)))
+        out = []
+        for r in recs[:k.value]:
+            d = {f: int(getattr(r, f)) for f, _ in _lib.MsmPlan._fields_ if f != "off"}
+            d.update(table=_lib.PLAN_TABLE[r.table], sort=_lib.PLAN_SORT[r.sort], reduce=_lib.PLAN_REDUCE[r.reduce],
+                     accum_launch=_lib.PLAN_LAUNCH[r.accum_launch], fold_launch=_lib.PLAN_LAUNCH[r.fold_launch],
+                     off=[int(x) for x in r.off[:r.W + 1]])
+            out.append(d)
+        return out
+
     # ---- Fr vectors ----
     def fr_vec_op_dev(self, op: int, a, b, out, n: int):
         self._ck(self.lib.zk_fr_vec_op_dev(self.h, op, C.c_void_p(int(a)), C.c_void_p(int(b)), C.c_void_p(int(out)), n))

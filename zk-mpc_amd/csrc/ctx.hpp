@@ -4,6 +4,7 @@
 // mpc-net/src/multi.rs:419-443).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/zkmpc_hip.h"
 #include "stream_order.hpp"
 #include <stdint.h>
 #include <stdio.h>
@@ -179,6 +180,12 @@ struct zk_ctx {
     } next;
     hipStream_t copy_stream = nullptr;        // the upload's stream
     int mul_levels = -1;                      // zk_msm_mul_levels: shifted copies the next proving key's tables get (-1: the default)
+    // zk_diag_msm_plans (diag.hip): what the dispatch code decided for the last MSM jobs, one record per job whose reduce chain was
+    // enqueued (msm.hip: msm_plan_commit).  Written and read by the thread inside an entry point of this context; host words only.
+    struct PlanRing {
+        zk_msm_plan rec[ZK_MSM_PLAN_RING];
+        uint64_t written = 0, read = 0;       // records ever committed / handed out or dropped: rec[k % ZK_MSM_PLAN_RING] holds record k
+    } plans;
     std::mutex mu;
     // timing of the most recent instrumented call (ms), filled when ZK_PROFILE env or explicit request
     struct Timer { float ms = 0; int count = 0; };

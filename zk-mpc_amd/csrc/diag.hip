@@ -273,6 +273,19 @@ extern "C" int zk_diag_fq2_pair_dev(zk_ctx* ctx, int op, const uint32_t* in, uin
                       });
     ZK_API_END
 }
+// The MSM jobs committed to the context's ring since the last call (msm.hip: msm_plan_commit), oldest first; no device work.
+extern "C" int zk_diag_msm_plans(zk_ctx* ctx, zk_msm_plan* out, size_t cap, size_t* n_out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || (cap && !out)) return ZK_ERR_ARG;
+    zk_ctx::PlanRing& r = ctx->plans;
+    if (r.written - r.read > ZK_MSM_PLAN_RING) r.read = r.written - ZK_MSM_PLAN_RING;      // the oldest were overwritten
+    size_t k = 0;
+    for (; r.read < r.written && k < cap; r.read++) out[k++] = r.rec[r.read % ZK_MSM_PLAN_RING];
+    r.read = r.written;
+    if (n_out) *n_out = k;
+    return ZK_OK;
+    ZK_API_END
+}
 extern "C" int zk_diag_f7l_dev(zk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n_cases) {
     ZK_API_BEGIN(ctx)
     if (!ctx || !in || !out || op < 0 || op > 8 || n_cases < 1 || n_cases > DIAG_MAX_CASES) return ZK_ERR_ARG;

@@ -254,6 +254,9 @@ struct ZkMsmJob {
     // several scalar vectors over one table (zk_msm_prepare_multi): n = mcount * mn scalars, vector k at scalars + k * mstride
     // elements; Wb = mcount bucket sets of the vector's geometry back to back
     size_t mcount = 0, mn = 0, mstride = 0;
+    // zk_diag_msm_plans: the choices made for this job (table, sort, accumulate, fold, reduce), each stored by the code that makes it;
+    // the enqueue of the reduce chain adds the geometry and commits the record to the context's ring (msm.hip: msm_plan_commit)
+    zk_msm_plan plan = {};
 };
 static_assert(!std::is_copy_constructible<ZkMsmJob>::value && std::is_move_constructible<ZkMsmJob>::value, "a ZkMsmJob owns its events and timers");
 int zk_msm_prepare(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars_dev, size_t n, int slot);
@@ -343,6 +346,7 @@ struct ZkG2PairReduce {   // the arguments of msm.hip's reduce chain
     uint32_t *sums, *rowP, *colP, *bits;
     uint32_t log_nb, n_win, light_blocks, heavy_blocks;
     bool quads = false;          // a small job: the fold on lane quads (the grid kernels choose by the bucket count)
+    zk_msm_plan* plan = nullptr; // the job's record (zk_diag_msm_plans): the fold's lanes and the reduce policy are stored where they are chosen
 };
 int zk_launch_reduce_g2pair(zk_ctx* ctx, hipStream_t st, const ZkG2PairReduce& a);
 constexpr uint32_t ZK_G2PAIR_RED_PTS = 128;   // points (lane pairs) per block of the G2 reduce kernels

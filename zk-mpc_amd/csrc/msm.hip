@@ -764,6 +764,19 @@ struct MsmBufs {
     HeavyDesc *heavy, *heavy2;
 };
 
+// zk_diag_msm_plans: the record of a job whose reduce chain is enqueued goes to the context's ring -- the choices its stages stored in
+// job->plan, and the geometry as the job holds it now (a batch may have shortened the segments after the prepare).  Host words only.
+void msm_plan_commit(zk_ctx* ctx, ZkMsmJob* job, uint32_t jobs_in_launch) {
+    zk_msm_plan& p = job->plan;
+    p.group = (uint32_t)job->group;
+    p.jobs = jobs_in_launch;
+    p.vectors = job->mcount ? (uint32_t)job->mcount : 1u;
+    p.n = job->n;
+    p.c = job->c; p.W = job->W; p.Wb = job->Wb; p.NB = job->NB; p.log_nb = job->log_nb; p.M = job->M; p.seg = job->seg;
+    for (int i = 0; i < 65; i++) p.off[i] = job->off[i];
+    ctx->plans.rec[ctx->plans.written++ % ZK_MSM_PLAN_RING] = p;
+}
+
 template <class F>
 int msm_prepare_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base_offset, const void* scalars, size_t n, int slot) {
     constexpr size_t XW = 4 * F::WORDS;
@@ -771,6 +784,7 @@ int msm_prepare_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base
     job->n = n;
     job->slot = slot;
     job->scalars = scalars;
+    job->plan = zk_msm_plan{};
     if (n == 0) return ZK_OK;
     if (base_offset + n > bases->n) ZK_FAIL(ctx, ZK_ERR_ARG, "msm: base range out of bounds");
     if (n >= ((size_t)1 << 27)) ZK_FAIL(ctx, ZK_ERR_ARG, "msm: n must be < 2^27");
@@ -798,6 +812,8 @@ int msm_prepare_t(zk_ctx* ctx, ZkMsmJob* job, const zk_bases* bases, size_t base
         job->bases_dev = bases->dev + base_offset * (2 * F::WORDS);
         job->stride = 2 * F::WORDS;
     }
+    job->plan.table = !merged ? ZK_PLAN_TABLE_PLAIN : job->stride == 64 ? ZK_PLAN_TABLE_LIMBS
+                      : (F::WORDS == 12 && job->stride == 32) ? ZK_PLAN_TABLE_LINE : ZK_PLAN_TABLE_PACKED;
     // Segment length: long enough that a typical bucket (mean n/NB points) is one segment, short enough that
     // (a) there are at least as many segments as resident lanes (2 waves per SIMD) and (b) the longest serial
     // chain -- seg mixed additions by one lane, ~9 us each -- stays a small part of the kernel.
@@ -872,6 +888,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         if (share->tab_off != job->tab_off)
             job->bases_dev = job->bases_dev + ((ptrdiff_t)job->tab_off - (ptrdiff_t)share->tab_off) * (ptrdiff_t)job->stride;
         job->sort = share->sort;
+        job->plan.sort = ZK_PLAN_SORT_BORROWED;
         ZK_HIP(ctx, share->sorted_at.order(st));
         ZK_HIP(ctx, job->sorted_at.set(st));
         return ZK_OK;
@@ -918,6 +935,7 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
     // window multiples with c = 20: 2^19 buckets whatever n is -- the bucket sort is correct for any total)
     if (one_block) {
         // a small MSM over window multiples: the whole sort in one block (k_sort_small)
+        job->plan.sort = ZK_PLAN_SORT_ONE_BLOCK;
         const size_t lds = ((size_t)NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4;
         if (!ctx->lds_attr_done[ZK_LDS_SORT_SMALL]) {
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_sort_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)SS_MAX_NB + 2 * SS_NT + (SS_MAX_SEG + 1) + 8) * 4)));
@@ -944,10 +962,13 @@ int msm_enqueue_sort_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st, const ZkMsmJo
         put(words, sizeof words);
         put(job->off, sizeof job->off);
     }
+    // (chosen out here: the enqueue below does not run when its graph is replayed)
+    const bool bucket_sort = job->mcount || (((size_t)W * n >= 65536 || NB > 65536) && zk_msm_group_supported(ga));
+    job->plan.sort = bucket_sort ? ZK_PLAN_SORT_BUCKET : ZK_PLAN_SORT_COUNTING;
     ZK_TRY(zk_graph_run(ctx, gkey, st, [&]() -> int {
         uint32_t flat_buckets = 0;
         if (!one_block) ZK_HIP(ctx, hipMemsetAsync(b.small, 0, (64 + 8 + 3 * (size_t)(seg + 1)) * 4, st));
-        if (job->mcount || (((size_t)W * n >= 65536 || NB > 65536) && zk_msm_group_supported(ga))) {
+        if (bucket_sort) {
             const uint32_t NBt = (uint32_t)nbuck;
             ZK_TRY(zk_msm_group(ctx, st, job->slot, ga));
             hipLaunchKernelGGL(k_build_segs, zk_grid(nbuck, 256, 512), 256, (seg + 1) * 4, st, b.offs, (const uint32_t*)nullptr, win_segs,
@@ -990,6 +1011,9 @@ int msm_enqueue_accum_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     const unsigned accum_blocks = (unsigned)((job->max_segs + 255) / 256);      // one lane per segment (blocks beyond ctr[2] return at once)
     const ZkSortProducts& s = job->sort;
     // G2 runs on lane pairs (msm_g2pair.hip): the one-lane-per-addition form needs the whole register file and is slower
+    const bool quads = !g1 && msm_latency_bound(job);
+    job->plan.accum_launch = ZK_PLAN_LAUNCH_SINGLE;
+    job->plan.accum_lanes = g1 ? 1u : quads ? 4u : 2u;
     if constexpr (F::WORDS == 12) {
         if (job->stride == 64)      // limb-form table with both signs (fixed_base.hip::k_repack_limbs)
             hipLaunchKernelGGL((k_accum<F, true>), accum_blocks, 256, 0, st, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, job->stride);
@@ -997,7 +1021,7 @@ int msm_enqueue_accum_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
             hipLaunchKernelGGL((k_accum<F, false>), accum_blocks, 256, 0, st, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, job->stride);
     }
     else
-        zk_launch_accum_g2pair(st, job->max_segs, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, msm_latency_bound(job));
+        zk_launch_accum_g2pair(st, job->max_segs, job->bases_dev, s.sorted, s.desc, s.order, s.ctr, b.sums, quads);
     ZK_HIP(ctx, hipGetLastError());
     tm->end();
     ZK_HIP(ctx, job->accumulated_at.set(st));
@@ -1023,13 +1047,18 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
         // G2: the same chain on lane pairs (msm_g2pair.hip)
         ZkG2PairReduce a{job->sort.heavy, job->sort.heavy2, job->sort.ctr, b.fold_done, b.sums, b.rowP, b.colP, b.bits, job->log_nb, job->Wb * job->red_win, 2 * light_blocks, heavy_blocks};
         a.quads = msm_latency_bound(job);
+        a.plan = &job->plan;
         ZK_TRY(zk_launch_reduce_g2pair(ctx, st, a));
     } else {
         hipLaunchKernelGGL(k_fold<F>, light_blocks + heavy_blocks, 64, 64 * XW * 4, st, job->sort.heavy, job->sort.heavy2, job->sort.ctr, b.fold_done,
                            b.sums, light_blocks);
         const GridSrc src{{(const uint32_t*)b.sums, nullptr, nullptr, nullptr}, 0u};
         const uint32_t n_win = job->Wb * job->red_win;
-        if (((size_t)n_win << job->log_nb) <= RED_DUAL_MAX_BUCKETS) {
+        const bool dual = ((size_t)n_win << job->log_nb) <= RED_DUAL_MAX_BUCKETS;
+        job->plan.fold_launch = ZK_PLAN_LAUNCH_SINGLE;
+        job->plan.fold_lanes = 1;
+        job->plan.reduce = dual ? ZK_PLAN_RED_G1_DUAL : ZK_PLAN_RED_G1;
+        if (dual) {
             const GridGeom gg = make_grid_geom(job->log_nb, n_win, RedG1Dual::PTS);
             hipLaunchKernelGGL(k_grid_l1<RedG1Dual>, gg.row_blocks + gg.col_blocks, RedG1Dual::NT, RedG1Dual::PTS * XW * 4, st, src, b.rowP, b.colP, gg);
             hipLaunchKernelGGL(k_grid_bits<RedG1Dual>, gg.n_win * job->nout, RedG1Dual::NT, RedG1Dual::PTS * XW * 4, st, (const uint32_t*)b.rowP,
@@ -1050,6 +1079,7 @@ int msm_enqueue_reduce_t(zk_ctx* ctx, ZkMsmJob* job, hipStream_t st) {
     ZK_HIP(ctx, hipMemcpyAsync(job->hw, b.bits, nbits * XW * 4, hipMemcpyDeviceToHost, st));
     // finish() waits for this event, not for the stream: later jobs' reduce phases may be queued behind on the same stream
     ZK_HIP(ctx, job->reduced_at.set(st));
+    msm_plan_commit(ctx, job, 1);
     return ZK_OK;
 }
 
@@ -1088,6 +1118,7 @@ static int msm_enqueue_sort_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count,
         a.grp_base = (uint32_t)((size_t)job->Wb * job->NB + job->max_heavy_segs);
         a.dig = b.dig; a.sorted = b.sorted; a.desc = b.desc; a.heavy = b.heavy; a.heavy2 = b.heavy2; a.order = b.order; a.ctr = b.small + 64;
         job->sort = ZkSortProducts{b.sorted, b.order, b.small + 64, b.desc, b.heavy, b.heavy2};
+        job->plan.sort = ZK_PLAN_SORT_ONE_BLOCK_GROUP;
         nb_max = std::max(nb_max, job->NB);
     }
     ZkPhaseTimer* tm = jobs[0]->add_timer(ctx, st);
@@ -1138,6 +1169,10 @@ static int msm_enqueue_accum_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int count
     size_t digits = 0;
     for (int k = 0; k < count; k++) digits += (size_t)jobs[k]->n * jobs[k]->W;
     const bool dual = digits <= ((size_t)1 << 18);
+    for (int k = 0; k < count; k++) {
+        jobs[k]->plan.accum_launch = ZK_PLAN_LAUNCH_GROUP;
+        jobs[k]->plan.accum_lanes = dual ? 2 : 1;
+    }
     const dim3 grid((unsigned)((max_segs + (dual ? 127 : 255)) / (dual ? 128 : 256)), (unsigned)count);
     if (jobs[0]->stride == 64) {
         if (dual) hipLaunchKernelGGL((k_accum_group<F, true, true>), grid, 256, 0, st, g);
@@ -1171,6 +1206,11 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
     }
     for (int k = count; k < MSM_GROUP_MAX; k++) { fg.j[k] = fg.j[0]; src.p[k] = src.p[0]; }
     const bool dual = ((size_t)count << jobs[0]->log_nb) <= RED_DUAL_MAX_BUCKETS;
+    for (int k = 0; k < count; k++) {
+        jobs[k]->plan.fold_launch = ZK_PLAN_LAUNCH_GROUP;
+        jobs[k]->plan.fold_lanes = dual ? 2 : 1;
+        jobs[k]->plan.reduce = dual ? ZK_PLAN_RED_G1_DUAL : ZK_PLAN_RED_G1;
+    }
     const GridGeom gg = make_grid_geom(jobs[0]->log_nb, (uint32_t)count, dual ? RedG1Dual::PTS : RedG1::PTS);
     const uint32_t nout = jobs[0]->nout;
     char nm[64];
@@ -1204,6 +1244,7 @@ static int msm_enqueue_reduce_group(zk_ctx* ctx, ZkMsmJob* const* jobs, int coun
         jobs[k]->hw = hw + (size_t)k * nout * XW;
         ZK_HIP(ctx, jobs[k]->reduced_at.set(st));
     }
+    for (int k = 0; k < count; k++) msm_plan_commit(ctx, jobs[k], (uint32_t)count);
     return ZK_OK;
 }
 

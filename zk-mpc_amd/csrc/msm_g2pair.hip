@@ -516,7 +516,13 @@ int zk_launch_reduce_g2pair(zk_ctx* ctx, hipStream_t st, const ZkG2PairReduce& a
     else
         hipLaunchKernelGGL(k_fold_g2pair<2>, a.light_blocks + a.heavy_blocks, 64, 64 * 4 * FW * 4, st, a.heavy, a.heavy2,
                            a.ctr, a.done, a.sums, a.light_blocks);
-    if (((size_t)a.n_win << a.log_nb) <= RED_QUAD_MAX_BUCKETS) {
+    const bool red_quads = ((size_t)a.n_win << a.log_nb) <= RED_QUAD_MAX_BUCKETS;
+    if (a.plan) {
+        a.plan->fold_launch = ZK_PLAN_LAUNCH_SINGLE;
+        a.plan->fold_lanes = a.quads ? 4 : 2;
+        a.plan->reduce = red_quads ? ZK_PLAN_RED_G2_QUAD : ZK_PLAN_RED_G2_PAIR;
+    }
+    if (red_quads) {
         const GridGeom gg = make_grid_geom(a.log_nb, a.n_win, RedG2Quad::PTS);
         const size_t lds = (size_t)2 * RedG2Quad::PTS * 4 * FW * 4;
         hipLaunchKernelGGL(k_grid_l1<RedG2Quad>, gg.row_blocks + gg.col_blocks, RedG2Quad::NT, lds, st, GridSrc{{(const uint32_t*)a.sums, nullptr, nullptr, nullptr}, 0u}, a.rowP, a.colP, gg);
