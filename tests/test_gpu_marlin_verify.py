@@ -85,6 +85,24 @@ def test_verify_batch_subgroup_test_rejects_cofactor_torsion(ctx):
     assert got.tolist() == [1, 0, 1]
 
 
+def test_verify_batch_timer_names(ctx):
+    """With profiling, one batch of one accepted proof leaves exactly these timers, each counted once: the laps by the host's clock,
+    the k_ phases by device events (tools/bench_marlin_verify.py reads them by name)."""
+    system = MC.fixture()["systems"][0]
+    inputs, good, verdict = MC.variant_args(system["variants"][0])
+    ctx.set_profiling(True)
+    try:
+        ctx.timers()
+        got_ok = DM.verify_batch(ctx, MC.vk_of(system), inputs[None], [good])
+        got = ctx.timers()
+    finally:
+        ctx.set_profiling(False)
+    print(sorted(got.items()))
+    assert verdict == 1 and got_ok.tolist() == [1]
+    names = ("parse", "decompress", "build", "device", "k_decompress", "k_lincomb", "k_pairing")
+    assert {k: c for k, (_, c) in got.items()} == {"marlin_verify." + w: 1 for w in names}
+
+
 def _raw_batch(ctx, vk, count, inputs, n_inputs, proofs, offsets, ok):
     """zk_marlin_verify_batch as the C ABI has it: the return code, nothing raised."""
     import ctypes as C

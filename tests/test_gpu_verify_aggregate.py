@@ -1,4 +1,4 @@
-"""Aggregated Groth16 verification on the device (csrc/verify_aggregate.hip): the two fold kernels alone against host arithmetic, word
+"""Aggregated Groth16 verification on the device (csrc/groth16_verify.hip, csrc/pairing.hip): the two fold kernels alone against host arithmetic, word
 for word; the long pairing product against the host's product of the same pairs; the aggregate against its host instantiation
 (which tests/test_verify_aggregate_host.py holds to the oracle)."""
 import functools
@@ -244,3 +244,21 @@ def test_aggregate_refuses(ctx, d8_batch):
     with pytest.raises(ZkError):
         ctx.groth16_verify_aggregate(up, inputs, proofs, seed=SEED)
     up.free()
+
+
+def test_aggregate_timer_names(ctx, d8_batch):
+    """With profiling, one aggregate call over one proof leaves exactly these timers, each counted once: the phases by device events,
+    the laps by the host's clock (tools/bench_verify_aggregate.py reads them by name)."""
+    pk, proofs, inputs, _, _ = d8_batch
+    coeffs = api.verify_aggregate_coeffs_from_seed(SEED, 1)
+    ctx.set_profiling(True)
+    try:
+        ctx.timers()
+        ok, _ = ctx.groth16_verify_aggregate(pk, inputs[:1], proofs[:1], coeffs=coeffs)
+        got = ctx.timers()
+    finally:
+        ctx.set_profiling(False)
+    print(sorted(got.items()))
+    assert ok is True
+    names = ("k_decompress", "k_subgroup", "k_scale", "k_miller", "k_fold", "host_sums", "wait_scale", "wait_miller", "host_finish")
+    assert {k: c for k, (_, c) in got.items()} == {"verify_aggregate." + w: 1 for w in names}

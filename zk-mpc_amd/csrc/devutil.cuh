@@ -154,6 +154,26 @@ __device__ __forceinline__ void xyzz_store16(uint32_t* base, size_t i, const XYZ
     felt_store16<F>(w + 3 * F::WORDS, p.zzz);
 }
 
+// ---- a G1 XYZZ entry in the LDS table of a one-wave block (g1_lincomb.hip, g1_ntt.hip, groth16_verify.hip) ----
+// Word-interleaved across the lanes: word i of entry e of lane l at ((e 48 + i) 64 + l) -- whatever entries the lanes pick, a
+// wave's access to word i is 64 distinct banks.
+constexpr int XW = 4 * G1Field::WORDS;      // 32-bit words of a packed G1 XYZZ point: 48
+struct ZkLdsTab {
+    uint32_t* base;            // the wave's table + this lane
+    __device__ __forceinline__ void put(int e, const XYZZ<G1Field>& p) {
+        uint32_t w[XW];
+        xyzz_store<G1Field>(w, p);
+#pragma unroll
+        for (int i = 0; i < XW; i++) base[(e * XW + i) * 64] = w[i];
+    }
+    __device__ __forceinline__ XYZZ<G1Field> get(int e) const {
+        uint32_t w[XW];
+#pragma unroll
+        for (int i = 0; i < XW; i++) w[i] = base[(e * XW + i) * 64];
+        return xyzz_load<G1Field>(w);
+    }
+};
+
 // ---- host conversions between the C-ABI structs (u64 limbs, ext Montgomery) and Fp ----
 template <class P>
 inline Fp<P> host_load_ext(const uint64_t* l) {  // raw bits of the external form

@@ -21,7 +21,7 @@ constexpr int LINCOMB_MAX_TERMS = 64;    // terms of a segment: one wave
 
 // Tab: void put(int e, const XYZZ<F>&), XYZZ<F> get(int e) for e < LINCOMB_TAB -- the device keeps it in LDS (an entry chosen by a
 // per-lane digit is an address there, not an index into a register array), the host in a local array.
-// NW: 32-bit words of k (8: the 256 raw bits above; 4: a 128-bit coefficient, half the windows -- verify_aggregate.hip)
+// NW: 32-bit words of k (8: the 256 raw bits above; 4: a 128-bit coefficient, half the windows -- groth16_verify.hip)
 template <class F, class Tab, int NW = 8>
 ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[NW], Tab& tab) {
     uint32_t kk[NW], carry = 0;

@@ -10,8 +10,7 @@
 //     (ZkLincombPack); the lanes left over in a wave join the segment before them with a zero scalar;
 //   * the per-lane multiplication is g1_lincomb.cuh: fixed signed 4-bit windows, the same doublings and one addition per window on
 //     every lane, table of 8 XYZZ entries per lane in LDS (8 x 192 B x 64 lanes = 96 KiB of the CU's 160), word-interleaved across the
-//     lanes: word i of entry e of lane l at ((e 48 + i) 64 + l) -- whatever entries the lanes pick, a wave's read of word i is 64
-//     distinct banks;
+//     lanes (devutil.cuh: ZkLdsTab);
 //   * a segmented tree over the wave through LDS with the complete addition (equal points double, opposite points cancel); the
 //     segment's first lane converts to affine (one inversion) and writes the point and an infinity flag.
 #include "../../include/zkmpc_hip.h"
@@ -27,24 +26,8 @@ using namespace zk;
 
 namespace {
 
-constexpr int XW = 4 * G1Field::WORDS;                                 // packed words of an XYZZ point: 48
 constexpr size_t LINCOMB_LDS = (size_t)LINCOMB_TAB * XW * 64 * 4;     // 98 304 bytes
 
-struct LdsTab {
-    uint32_t* base;            // the wave's table + this lane
-    __device__ __forceinline__ void put(int e, const XYZZ<G1Field>& p) {
-        uint32_t w[XW];
-        xyzz_store<G1Field>(w, p);
-#pragma unroll
-        for (int i = 0; i < XW; i++) base[(e * XW + i) * 64] = w[i];
-    }
-    __device__ __forceinline__ XYZZ<G1Field> get(int e) const {
-        uint32_t w[XW];
-#pragma unroll
-        for (int i = 0; i < XW; i++) w[i] = base[(e * XW + i) * 64];
-        return xyzz_load<G1Field>(w);
-    }
-};
 struct HostTab {
     XYZZ<Fq64Field> t[LINCOMB_TAB];
     void put(int e, const XYZZ<Fq64Field>& p) { t[e] = p; }
@@ -75,7 +58,7 @@ __global__ void __launch_bounds__(64) k_g1_lincomb(const uint32_t* __restrict__ 
         const uint32_t pi = point_index[g];
         if (pi < n_points) p = aff_load16<G1Field>(points, pi);
     }
-    LdsTab tab{lds + lane};
+    ZkLdsTab tab{lds + lane};
     XYZZ<G1Field> acc = lincomb_term<G1Field>(p, k, tab);
     // the segmented tree: after step s the lane at offset 0 mod 2 s of its segment holds the sum of its 2 s lanes
     uint32_t* red = lds;                                               // entry 0 of every lane's table, reused
@@ -86,7 +69,7 @@ __global__ void __launch_bounds__(64) k_g1_lincomb(const uint32_t* __restrict__ 
         __syncthreads();
         const bool act = (((g - s_lo) & (2 * s - 1)) == 0) && g + s < s_hi;
         if (act) {
-            LdsTab other{red + lane + s};
+            ZkLdsTab other{red + lane + s};
             acc = xyzz_add<G1Field>(acc, other.get(0));
         }
         __syncthreads();
@@ -96,12 +79,6 @@ __global__ void __launch_bounds__(64) k_g1_lincomb(const uint32_t* __restrict__ 
         aff_store16<G1Field>(out_aff, seg, xyzz_to_affine<G1Field>(acc));
         out_inf[seg] = xyzz_is_inf<G1Field>(acc) ? 1u : 0u;
     }
-}
-
-bool words_below_q(const uint64_t* l, int n_fq) {
-    for (int i = 0; i < n_fq; i++)
-        if (host64::cmp(l + 6 * i, host64::P) >= 0) return false;
-    return true;
 }
 
 // what both test hooks refuse
@@ -116,7 +93,7 @@ bool diag_args_ok(const zk_g1_affine* points, size_t n_points, const uint32_t* p
     for (size_t t = 0; t < seg_offsets[n_segments]; t++)
         if (point_index[t] >= n_points) return false;
     for (size_t i = 0; i < n_points; i++)
-        if (!words_below_q((const uint64_t*)&points[i], 2)) return false;
+        if (!zk_words_below_q((const uint64_t*)&points[i], 2)) return false;
     return true;
 }
 
@@ -148,7 +125,7 @@ int zk_g1_lincomb_launch(zk_ctx* ctx, const uint32_t* points_dev, size_t n_point
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_g1_lincomb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LINCOMB_LDS));
         ctx->lds_attr_done[ZK_LDS_LINCOMB] = true;
     }
-    hipLaunchKernelGGL(k_g1_lincomb, (unsigned)((n_lanes + 63) / 64), 64, LINCOMB_LDS, ctx->stream, points_dev, (uint32_t)n_points, point_index_dev,
+    hipLaunchKernelGGL(k_g1_lincomb, zk_blocks64(n_lanes), 64, LINCOMB_LDS, ctx->stream, points_dev, (uint32_t)n_points, point_index_dev,
                        scalars_dev, seg_offsets_dev, (uint32_t)n_segments, (uint32_t)n_lanes, out_affine_dev, out_is_inf_dev);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;

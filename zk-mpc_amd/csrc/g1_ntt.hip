@@ -7,8 +7,8 @@
 //     in HBM between the levels; zk_g1_batch_affine_launch normalises once at the end;
 //   * a butterfly is ~260 doublings and ~90 complete additions against two 192-byte loads and stores: compute-bound by three orders of
 //     magnitude, so a level is not fused with its neighbours and a lane's accesses are plain 16-byte ones;
-//   * the multiplication's table (four XYZZ entries per lane) is in LDS, word-interleaved across the wave like g1_lincomb.hip's: word i of
-//     entry e of lane l at ((e 48 + i) 64 + l).  48 KiB per block of one wave: three blocks per CU.
+//   * the multiplication's table (four XYZZ entries per lane) is in LDS, word-interleaved across the wave (devutil.cuh: ZkLdsTab).
+//     48 KiB per block of one wave: three blocks per CU.
 //   * twiddles are 2^(k-1) raw 256-bit scalars (canonical Fr) computed on the host once per size and direction.
 #include "../../include/zkmpc_hip.h"
 #include "hostfr.hpp"
@@ -23,24 +23,8 @@ using namespace zk;
 
 namespace {
 
-constexpr int XW = 4 * G1Field::WORDS;                                 // packed words of an XYZZ point: 48
 constexpr uint32_t DIAG_MAX_LOG = 12, DIAG_MAX_COUNT = 16;
 
-struct LdsTab {
-    uint32_t* base;            // the wave's table + this lane
-    __device__ __forceinline__ void put(int e, const XYZZ<G1Field>& p) {
-        uint32_t w[XW];
-        xyzz_store<G1Field>(w, p);
-#pragma unroll
-        for (int i = 0; i < XW; i++) base[(e * XW + i) * 64] = w[i];
-    }
-    __device__ __forceinline__ XYZZ<G1Field> get(int e) const {
-        uint32_t w[XW];
-#pragma unroll
-        for (int i = 0; i < XW; i++) w[i] = base[(e * XW + i) * 64];
-        return xyzz_load<G1Field>(w);
-    }
-};
 struct HostTab {
     XYZZ<Fq64Field> t[G1NTT_TAB];
     void put(int e, const XYZZ<Fq64Field>& p) { t[e] = p; }
@@ -67,7 +51,7 @@ __global__ void __launch_bounds__(64) k_g1_ntt_load(const uint32_t* __restrict__
     if (SCALE) {
         uint32_t k[8];
         load_scalar(k, scale.k, (size_t)scale.base[v] + (size_t)i * scale.step[v]);
-        LdsTab tab{lds + threadIdx.x};
+        ZkLdsTab tab{lds + threadIdx.x};
         p = g1_ntt_mul<G1Field>(p, k, tab);
     }
     xyzz_store16<G1Field>(work, (v << log_n) + g1_ntt_bitrev(i, log_n), p);
@@ -85,7 +69,7 @@ __global__ void __launch_bounds__(64) k_g1_ntt_level(uint32_t* __restrict__ work
     const size_t ia = (v << log_n) + lo, ib = ia + ((size_t)1 << s);
     load_scalar(w, tw, t);
     XYZZ<G1Field> a = xyzz_load16<G1Field>(work, ia), b = xyzz_load16<G1Field>(work, ib);
-    LdsTab tab{lds + threadIdx.x};
+    ZkLdsTab tab{lds + threadIdx.x};
     g1_ntt_butterfly<G1Field>(a, b, w, tab);
     xyzz_store16<G1Field>(work, ia, a);
     xyzz_store16<G1Field>(work, ib, b);
@@ -111,17 +95,11 @@ std::vector<uint32_t> twiddle_words(uint32_t log_n, int inverse_root) {
     return out;
 }
 
-bool words_below_q(const uint64_t* l, int n_fq) {
-    for (int i = 0; i < n_fq; i++)
-        if (host64::cmp(l + 6 * i, host64::P) >= 0) return false;
-    return true;
-}
-
 // what both test hooks refuse
 bool diag_args_ok(const zk_g1_affine* points, uint32_t log_n, size_t count, const zk_g1_affine* out) {
     if (!points || !out || log_n > DIAG_MAX_LOG || !count || count > DIAG_MAX_COUNT) return false;
     for (size_t i = 0; i < count << log_n; i++)
-        if (!words_below_q((const uint64_t*)&points[i], 2)) return false;
+        if (!zk_words_below_q((const uint64_t*)&points[i], 2)) return false;
     return true;
 }
 
@@ -143,11 +121,11 @@ int zk_g1_ntt_launch(zk_ctx* ctx, const uint32_t* in_dev, size_t n_in, size_t in
     const size_t n = (size_t)1 << log_n, total = count * n;
     if (!in_dev || !twiddles_dev || !work_xyzz_dev || log_n > 26 || !count || total > ((size_t)1 << 28) || n_in > n || (scale && (count > 2 || !scale->k)))
         return ZK_ERR_ARG;
-    const unsigned blocks = (unsigned)((total + 63) / 64);
+    const unsigned blocks = zk_blocks64(total);
     if (scale) hipLaunchKernelGGL(k_g1_ntt_load<true>, blocks, 64, 0, ctx->stream, in_dev, (uint32_t)n_in, in_vstride, *scale, log_n, total, work_xyzz_dev);
     else hipLaunchKernelGGL(k_g1_ntt_load<false>, blocks, 64, 0, ctx->stream, in_dev, (uint32_t)n_in, in_vstride, ZkG1NttScale{}, log_n, total, work_xyzz_dev);
     for (uint32_t s = 0; s < log_n; s++)
-        hipLaunchKernelGGL(k_g1_ntt_level, (unsigned)((total / 2 + 63) / 64), 64, 0, ctx->stream, work_xyzz_dev, twiddles_dev, log_n, s, total / 2);
+        hipLaunchKernelGGL(k_g1_ntt_level, zk_blocks64(total / 2), 64, 0, ctx->stream, work_xyzz_dev, twiddles_dev, log_n, s, total / 2);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }

@@ -10,11 +10,13 @@
 //   groth16_multi.hip    one prover's MSMs spread over several devices
 //   groth16_shared.hip   create_proof over additive / SPDZ shares as one call (its host algebra: groth16_shared_int.hpp)
 //   groth16_shared_batch.hip  the same for many shared assignments of one key, with the exchanges of one proof
+//   groth16_verify.hip   Groth16::verify on the host and of batches on the device, proof by proof or folded  (verifier.rs:13-61)
 #pragma once
 #include "hostfr.hpp"
 #include "hostgroup.hpp"
 #include "hostfield64.hpp"
 #include "internal.hpp"
+#include "pairing.cuh"
 #include "../../include/zkmpc_hip.h"
 #include <algorithm>
 #include <chrono>
@@ -61,11 +63,11 @@ struct zk_pk {
     uint32_t mul_levels = 0;
     zk::Affine<zk::G1Field> alpha_g1, beta_g1, delta_g1, a0, b0_g1;
     zk::Affine<zk::G2Field> beta_g2, delta_g2, gamma_g2, b0_g2;
-    // the verifier's constant e(alpha, beta) (pairing.hip), computed by the first verification of this key: the GT value as the
+    // the verifier's constant e(alpha, beta) (groth16_verify.hip), computed by the first verification of this key: the GT value as the
     // finish kernel compares it (12 Fq, internal form, packed)
     mutable std::mutex e_alpha_beta_mu;
     mutable bool have_e_alpha_beta = false;
-    mutable uint32_t e_alpha_beta[144];
+    mutable uint32_t e_alpha_beta[zk::FQ12_WORDS];
 };
 
 // The five MSM jobs of ONE proof, in ZkG16Jobs order (0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H), and how far each has been
@@ -262,17 +264,23 @@ void zk_g16_batch_chunk(const zk_pk* pk, const zk_r1cs* r, size_t count, bool qu
 // memory -- otherwise ZK_ERR_NOMEM, before any device work
 int zk_g16_batch_fits(zk_ctx* ctx, size_t count, double per_proof, size_t chunk_bytes);
 
-// ---- the ABI's affine structs (x | y in the reference's Montgomery words) as host-field points; a coordinate word is valid below q ----
+// ---- the ABI's affine structs (x | y in the reference's Montgomery words) and its GT value as host-field values (valid words:
+// zk_words_below_q) ----
 inline zk::Affine<zk::Fq64Field> zk_host_g1(const zk_g1_affine* p) {
     return zk::Affine<zk::Fq64Field>{zk::host64_coord<zk::Fq64Field>(p->x.l), zk::host64_coord<zk::Fq64Field>(p->y.l)};
 }
+inline zk::Fq12<zk::Fq264Field> zk_host_gt(const zk_gt* g) {
+    uint32_t w[zk::FQ12_WORDS];
+    memcpy(w, g, sizeof w);
+    return zk::fq12_from_ext<zk::Fq264Field>(w);
+}
+inline void zk_host_gt_out(zk_gt* g, const zk::Fq12<zk::Fq264Field>& f) {
+    uint32_t w[zk::FQ12_WORDS];
+    zk::fq12_to_ext<zk::Fq264Field>(w, f);
+    memcpy(g, w, sizeof w);
+}
 inline zk::Affine<zk::Fq264Field> zk_host_g2(const zk_g2_affine* p) {
     return zk::Affine<zk::Fq264Field>{zk::host64_coord<zk::Fq264Field>((const uint64_t*)p->x), zk::host64_coord<zk::Fq264Field>((const uint64_t*)p->y)};
-}
-inline bool zk_words_below_q(const uint64_t* l, int n_fq) {
-    for (int i = 0; i < n_fq; i++)
-        if (zk::host64::cmp(l + 6 * i, zk::host64::P) >= 0) return false;
-    return true;
 }
 
 namespace zk {

@@ -1,24 +1,26 @@
-// verify_aggregate.hip -- count Groth16 proofs of one key as ONE folded pairing product, and the two building blocks it needs: the
-// product of MANY Miller values and the sum of many G1 points that belong to no resident table.
+// groth16_verify.hip -- Groth16 verification: one proof on the host, a batch on the device proof by proof (zk_groth16_verify_batch),
+// and a batch as ONE folded pairing product (zk_groth16_verify_aggregate), with the building block the fold needs beyond pairing.hip:
+// the sum of many G1 points that belong to no resident table.
 //
-// Replaces (reference): nothing the reference has for Groth16 (Groth16::verify, arkworks/groth16/src/verifier.rs:13-61, is one
-// proof); the fold itself is the one of its KZG verifier (poly-commit/src/kzg10/mod.rs:345, batch_check: a random linear combination
-// of the equations, one product of pairings).  With coefficients r_i the batch holds iff
+// Replaces (reference):
+//   Groth16::verify (prepare_inputs, verify_proof_with_prepared_inputs)          arkworks/groth16/src/verifier.rs:13-61
+// and for the folded form nothing the reference has for Groth16 (Groth16::verify is one proof); the fold itself is the one of its
+// KZG verifier (poly-commit/src/kzg10/mod.rs:345, batch_check: a random linear combination of the equations, one product of
+// pairings).  With coefficients r_i the batch holds iff
 //     prod_i e(r_i A_i, B_i) . e(sum_i r_i C_i, -delta) . e(sum_j s_j gamma_abc[j], -gamma) . e(s_0 alpha, -beta) = 1
 //     s_0 = sum_i r_i,  s_j = sum_i r_i x_{i,j} (mod r)
-// count + 3 Miller loops and ONE final exponentiation (pairing.hip's batch form: 3 count and count).
+// count + 3 Miller loops and ONE final exponentiation (the batch form: 3 count and count).
 //
-//   k_fq12_fold       n packed Miller values -> ceil(n / FOLD_SPAN) partial products.  One wave per block; a lane multiplies its
-//                     FOLD_PER_LANE values serially (value b SPAN + 64 j + lane in round j: the wave reads 64 neighbours), then six
-//                     tree steps through LDS, words interleaved across the lanes (word i of lane l at 64 i + l: a wave's access to
-//                     one word is 64 distinct banks); lane 0 writes.  Lanes past n hold the Fq12 one.  The product is exact and
-//                     commutative: which lane multiplies which values does not show in the words that come out.
+//   k_verify_prepare  one proof per lane: gamma_abc[0] + sum x_i gamma_abc[i] by double-and-add (the usual handful of public
+//                     inputs; a key with very many would want the multi-vector MSM instead), and the proof's three pairs laid out.
+//                     Its scalar multiplication branches on scalar bits; it is microseconds beside the Miller loops.
 //   k_g1_scale_fold   per lane an affine point and a 128-bit coefficient -> r P in XYZZ by g1_lincomb.cuh's fixed signed windows
 //                     (32 windows; the digit selects a table entry in LDS and a sign, never the control flow), then either per
 //                     lane the affine point (the Miller loop's P array) or a wave tree of complete additions through LDS and one
 //                     XYZZ partial per block, or both.  Without coefficients it only sums (XYZZ partials or affine points).
-// The host re-launches each fold on its partials until at most 64 are left and finishes those itself: the sum in 64-bit limbs,
-// the product and final_exponentiation<Fq264Field> (0.6 ms; k_pairing_finish over the same partials, one lane, was measured at 18 ms).
+// Both device forms check their arguments (device_args_ok) and stage their proofs (stage_proofs) by the same code and run pairing.hip's
+// kernels behind it; the folded form ends in its zk_miller_product.  The host re-launches the sum on its partials until at most 64
+// are left and finishes those itself in 64-bit limbs.
 // Not built: a multi-vector MSM over the gamma_abc table for keys with very many public inputs -- the ninp + 2 full-width
 // multiplications of key points (s_0 alpha, s_j gamma_abc[j]) run on the context's helper threads under the device work.
 #include "../../include/zkmpc_hip.h"
@@ -33,101 +35,37 @@ using namespace zk;
 
 namespace {
 
-using D2 = Fq2Field;
 using H1 = Fq64Field;
 using H2 = Fq264Field;
-constexpr int GTW = 144;                                             // 32-bit words of a packed Fq12
-constexpr int XW = 4 * G1Field::WORDS;                               // ... of a packed XYZZ point: 48
-constexpr int FOLD_PER_LANE = 4;
-constexpr size_t FOLD_SPAN = 64 * (size_t)FOLD_PER_LANE;
 constexpr size_t MAX_LANES = ZK_PAIRING_MAX_LANES;
 constexpr size_t SCALE_LDS = (size_t)LINCOMB_TAB * XW * 64 * 4;      // the window tables: 98 304 bytes
 constexpr size_t SUM_LDS = (size_t)XW * 64 * 4;                      // the tree alone: 12 288 bytes
 
-inline unsigned blocks_of(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
-
-// ---- k_fq12_fold ------------------------------------------------------------------------------------------------------------------
-// ext: the ABI's form (the test hook's input and output); else packed internal words as k_miller writes them
-__device__ __forceinline__ Fq12<D2> fold_load(const uint32_t* w, bool ext) {
-    Fq12<D2> f;
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 3; j++) {
-            const Fq2 t = felt_load16<D2>(w + 24 * (3 * i + j));
-            f.c[i].c[j] = ext ? D2::ext_to_int(t) : t;
-        }
-    return f;
-}
-__device__ __forceinline__ void fold_store(uint32_t* w, const Fq12<D2>& f, bool ext) {
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 3; j++) felt_store16<D2>(w + 24 * (3 * i + j), ext ? D2::int_to_ext(f.c[i].c[j]) : f.c[i].c[j]);
-}
-__device__ __forceinline__ void fold_lds_put(uint32_t* lds, uint32_t lane, const Fq12<D2>& f) {
-    for (int c = 0; c < 6; c++) {
-        uint32_t w[24];
-        D2::store(w, f.c[c / 3].c[c % 3]);
-#pragma unroll
-        for (int i = 0; i < 24; i++) lds[(24 * c + i) * 64 + lane] = w[i];
+// ---- k_verify_prepare -------------------------------------------------------------------------------------------------------------
+// proof k: P[3 k .. 3 k + 2] = A, prepared inputs, C;  Q[3 k ..] = B, -gamma, -delta.  ac holds (A_k, C_k) at 2 k, 2 k + 1 and b
+// holds B_k (table form, from the decompression, with their off-curve flags bad_ac / bad_b); negs = -gamma | -delta.
+__global__ void __launch_bounds__(64) k_verify_prepare(size_t count, size_t ninp, const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ gamma_abc,
+                                                       const uint32_t* __restrict__ ac, const uint32_t* __restrict__ b, const uint32_t* __restrict__ negs,
+                                                       const uint32_t* __restrict__ bad_ac, const uint32_t* __restrict__ bad_b, uint32_t* __restrict__ P,
+                                                       uint32_t* __restrict__ Q, uint32_t* __restrict__ bad) {
+    const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    XYZZ<G1Field> acc = xyzz_from_affine<G1Field>(aff_load16<G1Field>(gamma_abc, 0));
+    for (size_t i = 0; i < ninp; i++) {
+        uint32_t kw[8];
+        fp_pack<FrParams>(kw, fp_ext_to_canon<FrParams>(fr_load(inputs, k * ninp + i)));
+        acc = xyzz_add<G1Field>(acc, xyzz_scalar_mul<G1Field>(aff_load16<G1Field>(gamma_abc, i + 1), kw, 8));
     }
-}
-__device__ __forceinline__ Fq12<D2> fold_lds_get(const uint32_t* lds, uint32_t lane) {
-    Fq12<D2> f;
-    for (int c = 0; c < 6; c++) {
-        uint32_t w[24];
-#pragma unroll
-        for (int i = 0; i < 24; i++) w[i] = lds[(24 * c + i) * 64 + lane];
-        f.c[c / 3].c[c % 3] = D2::load(w);
-    }
-    return f;
-}
-
-// block b: out[b] = the product of in[b SPAN .. min(n, (b + 1) SPAN)); the grid is ceil(n / SPAN) blocks of one wave
-__global__ void __launch_bounds__(64) k_fq12_fold(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out, int in_ext, int out_ext) {
-    __shared__ uint32_t lds[GTW * 64];
-    const uint32_t lane = threadIdx.x;
-    const size_t base = blockIdx.x * FOLD_SPAN;
-    const size_t have = n - base < FOLD_SPAN ? n - base : FOLD_SPAN;      // this block's values: the same on every lane
-    const int rounds = (int)((have + 63) / 64);
-    Fq12<D2> acc = fq12_one<D2>();
-#pragma unroll 1
-    for (int j = 0; j < rounds; j++) {
-        const size_t i = base + (size_t)j * 64 + lane;
-        Fq12<D2> f = fq12_one<D2>();
-        if (i < n) f = fold_load(in + i * GTW, in_ext != 0);
-        if (j == 0) acc = f; else fq12_mul<D2>(acc, acc, f);
-    }
-    // after step s the lanes at 0 mod 2 s hold the product of their 2 s lanes; lanes from `have` on hold one: steps beyond are skipped
-#pragma unroll 1
-    for (uint32_t s = 1; s < 64 && s < have; s <<= 1) {
-        const uint32_t pos = lane & (2 * s - 1);
-        if (pos == s) fold_lds_put(lds, lane, acc);
-        __syncthreads();
-        if (pos == 0) {
-            const Fq12<D2> f = fold_lds_get(lds, lane + s);
-            fq12_mul<D2>(acc, acc, f);
-        }
-        __syncthreads();
-    }
-    if (lane == 0) fold_store(out + (size_t)blockIdx.x * GTW, acc, out_ext != 0);
+    aff_store16<G1Field>(P, 3 * k, aff_load16<G1Field>(ac, 2 * k));
+    aff_store16<G1Field>(P, 3 * k + 1, xyzz_to_affine<G1Field>(acc));
+    aff_store16<G1Field>(P, 3 * k + 2, aff_load16<G1Field>(ac, 2 * k + 1));
+    aff_store16<G2Field>(Q, 3 * k, aff_load16<G2Field>(b, k));
+    aff_store16<G2Field>(Q, 3 * k + 1, aff_load16<G2Field>(negs, 0));
+    aff_store16<G2Field>(Q, 3 * k + 2, aff_load16<G2Field>(negs, 1));
+    bad[k] = bad_ac[2 * k] | bad_ac[2 * k + 1] | bad_b[k];
 }
 
 // ---- k_g1_scale_fold --------------------------------------------------------------------------------------------------------------
-// g1_lincomb.hip's layout: word i of entry e of lane l at ((e 48 + i) 64 + l)
-struct LdsTab {
-    uint32_t* base;            // the wave's table + this lane
-    __device__ __forceinline__ void put(int e, const XYZZ<G1Field>& p) {
-        uint32_t w[XW];
-        xyzz_store<G1Field>(w, p);
-#pragma unroll
-        for (int i = 0; i < XW; i++) base[(e * XW + i) * 64] = w[i];
-    }
-    __device__ __forceinline__ XYZZ<G1Field> get(int e) const {
-        uint32_t w[XW];
-#pragma unroll
-        for (int i = 0; i < XW; i++) w[i] = base[(e * XW + i) * 64];
-        return xyzz_load<G1Field>(w);
-    }
-};
-
 // lane g < n: point g in_step of `in` (affine table form, or XYZZ with in_xyzz) times coeffs[4 g ..] (128 bits, low word first;
 // coeffs = NULL: times one, and the launch needs SUM_LDS bytes of LDS only, else SCALE_LDS).  out_aff (or NULL): the n products as
 // affine points.  out_part (or NULL): one XYZZ sum per block.
@@ -135,7 +73,7 @@ __global__ void __launch_bounds__(64) k_g1_scale_fold(const uint32_t* __restrict
                                                       uint32_t n, uint32_t* __restrict__ out_aff, uint32_t* __restrict__ out_part) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x, g = blockIdx.x * 64u + lane;
-    LdsTab tab{lds + lane};
+    ZkLdsTab tab{lds + lane};
     XYZZ<G1Field> acc = xyzz_inf<G1Field>();
     if (coeffs) {
         Affine<G1Field> p = aff_inf<G1Field>();
@@ -145,7 +83,7 @@ __global__ void __launch_bounds__(64) k_g1_scale_fold(const uint32_t* __restrict
             const uint4 c = reinterpret_cast<const uint4*>(coeffs)[g];
             k[0] = c.x; k[1] = c.y; k[2] = c.z; k[3] = c.w;
         }
-        acc = lincomb_term<G1Field, LdsTab, 4>(p, k, tab);
+        acc = lincomb_term<G1Field, ZkLdsTab, 4>(p, k, tab);
         __syncthreads();                                               // (the tree reuses entry 0 of the tables)
     } else if (g < n) {
         acc = in_xyzz ? xyzz_load16<G1Field>(in, (size_t)g * in_step) : xyzz_from_affine<G1Field>(aff_load16<G1Field>(in, (size_t)g * in_step));
@@ -159,7 +97,7 @@ __global__ void __launch_bounds__(64) k_g1_scale_fold(const uint32_t* __restrict
         if (pos == s) tab.put(0, acc);
         __syncthreads();
         if (pos == 0) {
-            LdsTab other{lds + lane + s};
+            ZkLdsTab other{lds + lane + s};
             acc = xyzz_add<G1Field>(acc, other.get(0));
         }
         __syncthreads();
@@ -173,7 +111,7 @@ int scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_g1_scale_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCALE_LDS));
         ctx->lds_attr_done[ZK_LDS_SCALE_FOLD] = true;
     }
-    hipLaunchKernelGGL(k_g1_scale_fold, blocks_of(n, 64), 64, coeffs ? SCALE_LDS : SUM_LDS, ctx->stream, in, in_step, in_xyzz ? 1 : 0, coeffs, (uint32_t)n,
+    hipLaunchKernelGGL(k_g1_scale_fold, zk_blocks64(n), 64, coeffs ? SCALE_LDS : SUM_LDS, ctx->stream, in, in_step, in_xyzz ? 1 : 0, coeffs, (uint32_t)n,
                        out_aff, out_part);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
@@ -182,45 +120,14 @@ int scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in
 int g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** res) {
     while (*m > 64) {
         ZK_TRY(scale_fold_launch(ctx, a, 1, true, nullptr, *m, nullptr, b));
-        *m = (*m + 63) / 64;
+        *m = zk_blocks64(*m);
         std::swap(a, b);
     }
     *res = a;
     return ZK_OK;
 }
-// the m packed Miller values in `in` folded down to at most `limit` through the buffers a, b (room for m / SPAN + 1 values each)
-int fq12_fold_down(zk_ctx* ctx, const uint32_t* in, uint32_t* a, uint32_t* b, size_t* m, size_t limit, const uint32_t** res) {
-    while (*m > limit) {
-        hipLaunchKernelGGL(k_fq12_fold, blocks_of(*m, FOLD_SPAN), 64, 0, ctx->stream, in, *m, a, 0, 0);
-        ZK_HIP(ctx, hipGetLastError());
-        *m = (*m + FOLD_SPAN - 1) / FOLD_SPAN;
-        in = a;
-        std::swap(a, b);
-    }
-    *res = in;
-    return ZK_OK;
-}
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
-Fq12<H2> host_fq12_from_packed(const uint32_t* w) {
-    Fq12<H2> f;
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 3; j++) f.c[i].c[j] = H2::from_dev(D2::load(w + 24 * (3 * i + j)));
-    return f;
-}
-void host_gt_out(zk_gt* g, const Fq12<H2>& f) {
-    uint32_t w[GTW];
-    fq12_to_ext<H2>(w, f);
-    memcpy(g, w, sizeof w);
-}
-// FE(prod of the m packed values): the end of every device path here
-Fq12<H2> host_finish(const uint32_t* packed, size_t m) {
-    Fq12<H2> acc = fq12_one<H2>(), r;
-    for (size_t i = 0; i < m; i++) fq12_mul<H2>(acc, acc, host_fq12_from_packed(packed + i * GTW));
-    final_exponentiation<H2>(r, acc);
-    return r;
-}
-
 HF coeff_fr(const uint64_t* c) {      // lo + 2^64 hi
     static const HF two64 = HF::from_u64((uint64_t)1 << 32).sqr();
     return HF::from_u64(c[0]) + HF::from_u64(c[1]) * two64;
@@ -239,19 +146,151 @@ void coeff_words(const uint64_t* c, uint32_t k[8]) {
     k[4] = k[5] = k[6] = k[7] = 0;
 }
 
-struct HostLap {
-    zk_ctx* ctx;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char* what) {                    // with zk_set_profiling: host wall-clock since the lap before into "verify_aggregate.<what>"
-        if (!ctx->profiling) return;
-        const auto now = std::chrono::steady_clock::now();
-        auto& tm = ctx->timers[std::string("verify_aggregate.") + what];
-        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
-        tm.count += 1;
-        t = now;
+// the key's e(alpha, beta) as the finish kernel compares it (packed); computed once per key
+void pk_e_alpha_beta(const zk_pk* pk, uint32_t out[FQ12_WORDS]) {
+    std::lock_guard<std::mutex> g(pk->e_alpha_beta_mu);
+    if (!pk->have_e_alpha_beta) {
+        const Affine<H1> alpha = aff_to_host64<G1Field>(pk->alpha_g1);
+        const Affine<H2> beta = aff_to_host64<G2Field>(pk->beta_g2);
+        Fq12<H2> e;
+        pairing_product<H2>(e, &alpha, &beta, 1);
+        fq12_host_to_packed(pk->e_alpha_beta, e);
+        pk->have_e_alpha_beta = true;
     }
-};
+    memcpy(out, pk->e_alpha_beta, FQ12_WORDS * 4);
+}
 
+// ---- what the forms share: checks and staging ---------------------------------------------------------------------------------------
+bool inputs_below_r(const zk_fr* inputs, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!zk_fr_words_valid(inputs[i].l)) return false;
+    return true;
+}
+// a host verifying key for ninp public inputs: its parts there, gamma_abc of ninp + 1 points, every coordinate word below q
+bool vk_host_ok(const zk_vk_host* vk, size_t ninp) {
+    if (!vk || !vk->gamma_abc_g1 || vk->gamma_abc_len != ninp + 1) return false;
+    if (!zk_words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !zk_words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
+        !zk_words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !zk_words_below_q((const uint64_t*)&vk->delta_g2, 4))
+        return false;
+    for (size_t i = 0; i <= ninp; i++)
+        if (!zk_words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return false;
+    return true;
+}
+// one proof's bytes as A, B, C on the host; false: a point off its curve, or with check_subgroup outside its subgroup (the test of
+// Proof::deserialize: subgroup.cuh, host instantiation)
+bool host_proof_points(const uint8_t proof[192], bool check_subgroup, Affine<G1Field>* a, Affine<G2Field>* b, Affine<G1Field>* c) {
+    if (!zk_host_decompress_g1(proof, a) || !zk_host_decompress_g2(proof + 48, b) || !zk_host_decompress_g1(proof + 144, c)) return false;
+    return !check_subgroup || (zk_host_in_subgroup_g1(*a) && zk_host_in_subgroup_g2(*b) && zk_host_in_subgroup_g1(*c));
+}
+// what the device forms refuse of their key and arguments, in the words of the entry point `entry`
+int device_args_ok(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, size_t max_count,
+                   const char* entry) {
+    if (!ctx || !pk || !count || !proofs_host || count > max_count) return ZK_ERR_ARG;
+    if (!pk->gamma_abc || pk->gamma_abc->n == 0 || aff_is_inf<G2Field>(pk->gamma_g2))
+        ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": the key has no verifying-key parts (gamma_g2, gamma_abc_g1)");
+    if (pk->gamma_abc->n != ninp + 1) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": inputs_per_proof is not num_instance - 1");
+    if (ninp && !inputs_host) return ZK_ERR_ARG;
+    if (!inputs_below_r(inputs_host, count * ninp)) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": a public input is not below r");
+    return ZK_OK;
+}
+// The points of count proofs onto the device, for both device forms: the compressed (A_k, C_k) and the compressed B_k split out of
+// the proofs' bytes into *staging (the caller keeps it until it has waited for the stream: the uploads read it), uploaded and
+// decompressed into table form -- (*ac)[2 k], (*ac)[2 k + 1] = A_k, C_k and (*b)[k] = B_k -- and with check_subgroup tested for
+// membership, one launch over the 2 count G1 points and one over the count G2 points whatever count is.  bad_any: one word, cleared
+// here, set by a point off its curve or outside its subgroup.  bad_ac, bad_b (both or neither; else NULL): the same per point, 2 count
+// and count words, "outside the subgroup" ORed into the off-curve flags.  tm, lap (both, or NULL): the caller's timers; tm gets the
+// two decompress launches as "<lap->prefix>k_decompress" and the two subgroup launches as "<lap->prefix>k_subgroup".
+int stage_proofs(zk_ctx* ctx, size_t count, const uint8_t* proofs_host, bool check_subgroup, uint32_t* bad_any, uint32_t* bad_ac, uint32_t* bad_b,
+                 uint32_t** ac, uint32_t** b, std::vector<uint8_t>* staging, ZkPhaseTimer* tm = nullptr, ZkHostLap* lap = nullptr) {
+    const bool timed = tm && lap && tm->enabled;
+    staging->resize(count * 192);
+    uint8_t *g1c = staging->data(), *g2c = g1c + count * 2 * 48;
+    for (size_t k = 0; k < count; k++) {
+        const uint8_t* pr = proofs_host + k * 192;
+        memcpy(&g1c[(2 * k) * 48], pr, 48);
+        memcpy(&g2c[k * 96], pr + 48, 96);
+        memcpy(&g1c[(2 * k + 1) * 48], pr + 144, 48);
+    }
+    uint8_t *d_g1c, *d_g2c;
+    ZK_TRY(zk_scratch(ctx, "vfy_g1c", count * 2 * 48, (void**)&d_g1c));
+    ZK_TRY(zk_scratch(ctx, "vfy_g2c", count * 96, (void**)&d_g2c));
+    ZK_TRY(zk_scratch(ctx, "vfy_ac", count * 2 * 96, (void**)ac));
+    ZK_TRY(zk_scratch(ctx, "vfy_b", count * 192, (void**)b));
+    ZK_HIP(ctx, hipMemcpyAsync(d_g1c, g1c, count * 2 * 48, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(d_g2c, g2c, count * 96, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(ctx, hipMemsetAsync(bad_any, 0, 4, ctx->stream));
+    if (timed) tm->begin((std::string(lap->prefix) + "k_decompress").c_str());
+    ZK_TRY(zk_decompress_launch(ctx, 1, (const uint32_t*)d_g1c, 2 * count, *ac, bad_any, bad_ac));
+    ZK_TRY(zk_decompress_launch(ctx, 2, (const uint32_t*)d_g2c, count, *b, bad_any, bad_b));
+    if (timed) tm->end();
+    if (!check_subgroup) return ZK_OK;
+    if (timed) tm->begin((std::string(lap->prefix) + "k_subgroup").c_str());
+    ZK_TRY(zk_subgroup_launch(ctx, 1, *ac, 2 * count, bad_any, bad_ac, bad_ac != nullptr));
+    ZK_TRY(zk_subgroup_launch(ctx, 2, *b, count, bad_any, bad_b, bad_b != nullptr));
+    if (timed) tm->end();
+    return ZK_OK;
+}
+
+// ---- proof by proof -------------------------------------------------------------------------------------------------------------------
+// Groth16::verify on host values: e(A, B) e(prepared, -gamma) e(C, -delta) == e(alpha, beta)
+int verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok, bool check_subgroup) {
+    if (!proof || !ok || (n_inputs && !inputs) || !vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
+    *ok = 0;
+    Affine<G1Field> a, c;
+    Affine<G2Field> b;
+    if (!host_proof_points(proof, check_subgroup, &a, &b, &c)) return ZK_OK;
+    // prepare_inputs (verifier.rs:18-33)
+    XYZZ<H1> acc = xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[0]));
+    for (size_t i = 0; i < n_inputs; i++) {
+        uint32_t kw[8];
+        fr_abi_to_canon_words(inputs[i].l, kw);
+        acc = xyzz_add<H1>(acc, host64_scalar_mul<H1>(xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[i + 1])), kw));
+    }
+    const Affine<H1> P[3] = {aff_to_host64<G1Field>(a), xyzz_to_affine<H1>(acc), aff_to_host64<G1Field>(c)};
+    const Affine<H2> Q[3] = {aff_to_host64<G2Field>(b), aff_neg<H2>(zk_host_g2(&vk->gamma_g2)), aff_neg<H2>(zk_host_g2(&vk->delta_g2))};
+    Fq12<H2> lhs, rhs;
+    pairing_product<H2>(lhs, P, Q, 3);
+    const Affine<H1> alpha = zk_host_g1(&vk->alpha_g1);
+    const Affine<H2> beta = zk_host_g2(&vk->beta_g2);
+    pairing_product<H2>(rhs, &alpha, &beta, 1);
+    *ok = fq12_eq<H2>(lhs, rhs) ? 1 : 0;
+    return ZK_OK;
+}
+
+// the per-point flags of the staging (off the curve, with check_subgroup outside the subgroup) go into each proof's verdict by k_verify_prepare
+int verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, int* ok,
+                 bool check_subgroup) {
+    if (!ok) return ZK_ERR_ARG;
+    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES / 3, "zk_groth16_verify_batch"));
+    struct Consts { uint32_t negs[2 * 48]; uint32_t want[FQ12_WORDS]; } cs;      // the key's constants
+    aff_store<G2Field>(cs.negs, aff_neg<G2Field>(pk->gamma_g2));
+    aff_store<G2Field>(cs.negs + 48, aff_neg<G2Field>(pk->delta_g2));
+    pk_e_alpha_beta(pk, cs.want);
+
+    const size_t n = 3 * count;
+    uint32_t *d_in, *d_cs, *ac, *b, *flags, *P, *Q, *ml;
+    ZK_TRY(zk_scratch(ctx, "vfy_in", count * ninp * 32 + 32, (void**)&d_in));
+    ZK_TRY(zk_scratch(ctx, "vfy_cs", sizeof cs, (void**)&d_cs));
+    ZK_TRY(zk_scratch(ctx, "vfy_flags", (1 + 4 * count) * 4 + count * 4, (void**)&flags));      // any | bad_ac | bad_b | bad | ok
+    ZK_TRY(zk_pair_scratch(ctx, n, &P, &Q, &ml));
+    uint32_t *bad_any = flags, *bad_ac = flags + 1, *bad_b = bad_ac + 2 * count, *bad = bad_b + count;
+    int* d_ok = (int*)(bad + count);
+    hipStream_t st = ctx->stream;
+    if (ninp) ZK_HIP(ctx, hipMemcpyAsync(d_in, inputs_host, count * ninp * 32, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_cs, &cs, sizeof cs, hipMemcpyHostToDevice, st));
+    std::vector<uint8_t> staging;
+    ZK_TRY(stage_proofs(ctx, count, proofs_host, check_subgroup, bad_any, bad_ac, bad_b, &ac, &b, &staging));
+    hipLaunchKernelGGL(k_verify_prepare, zk_blocks64(count), 64, 0, st, count, ninp, (const uint32_t*)d_in, (const uint32_t*)pk->gamma_abc->dev,
+                       (const uint32_t*)ac, (const uint32_t*)b, (const uint32_t*)d_cs, (const uint32_t*)bad_ac, (const uint32_t*)bad_b, P, Q, bad);
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_TRY(zk_miller_launch(ctx, P, Q, n, ml));
+    ZK_TRY(zk_pairing_finish_launch(ctx, ml, 3, count, nullptr, d_cs + 2 * 48, bad, d_ok));
+    ZK_HIP(ctx, hipMemcpyAsync(ok, d_ok, count * sizeof(int), hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
+// ---- folded -----------------------------------------------------------------------------------------------------------------------------
 // what both aggregate forms refuse beyond their key's checks
 bool agg_args_ok(size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const uint64_t* coeffs, const int* ok_all) {
     if (!count || !proofs || !coeffs || !ok_all || count > MAX_LANES - 3 || (ninp && !inputs)) return false;
@@ -260,14 +299,7 @@ bool agg_args_ok(size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* 
 
 int aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const uint64_t* coeffs, int* ok_all,
                    zk_gt* folded) {
-    if (!vk || !agg_args_ok(count, inputs, ninp, proofs, coeffs, ok_all) || !vk->gamma_abc_g1 || vk->gamma_abc_len != ninp + 1) return ZK_ERR_ARG;
-    if (!zk_words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !zk_words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
-        !zk_words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !zk_words_below_q((const uint64_t*)&vk->delta_g2, 4))
-        return ZK_ERR_ARG;
-    for (size_t i = 0; i <= ninp; i++)
-        if (!zk_words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return ZK_ERR_ARG;
-    for (size_t i = 0; i < count * ninp; i++)
-        if (!zk_fr_words_valid(inputs[i].l)) return ZK_ERR_ARG;
+    if (!agg_args_ok(count, inputs, ninp, proofs, coeffs, ok_all) || !vk_host_ok(vk, ninp) || !inputs_below_r(inputs, count * ninp)) return ZK_ERR_ARG;
     *ok_all = 0;
     if (folded) memset(folded, 0, sizeof *folded);
     std::vector<Affine<H1>> P(count + 3);
@@ -277,8 +309,7 @@ int aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size
         const uint8_t* pr = proofs + i * 192;
         Affine<G1Field> a, c;
         Affine<G2Field> b;
-        if (!zk_host_decompress_g1(pr, &a) || !zk_host_decompress_g2(pr + 48, &b) || !zk_host_decompress_g1(pr + 144, &c)) return ZK_OK;
-        if (!(zk_host_in_subgroup_g1(a) && zk_host_in_subgroup_g2(b) && zk_host_in_subgroup_g1(c))) return ZK_OK;
+        if (!host_proof_points(pr, true, &a, &b, &c)) return ZK_OK;
         uint32_t k[8];
         coeff_words(coeffs + 2 * i, k);
         P[i] = xyzz_to_affine<H1>(host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(a)), k));
@@ -304,64 +335,34 @@ int aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size
     Fq12<H2> r;
     pairing_product<H2>(r, P.data(), Q.data(), count + 3);
     *ok_all = fq12_eq<H2>(r, fq12_one<H2>()) ? 1 : 0;
-    if (folded) host_gt_out(folded, r);
+    if (folded) zk_host_gt_out(folded, r);
     return ZK_OK;
 }
 
 int aggregate_dev(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, const uint64_t* coeffs,
                   int* ok_all, zk_gt* folded) {
-    if (!ctx || !pk || !agg_args_ok(count, inputs_host, ninp, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
-    if (!pk->gamma_abc || pk->gamma_abc->n == 0 || aff_is_inf<G2Field>(pk->gamma_g2))
-        ZK_FAIL(ctx, ZK_ERR_ARG, "zk_groth16_verify_aggregate: the key has no verifying-key parts (gamma_g2, gamma_abc_g1)");
-    if (pk->gamma_abc->n != ninp + 1) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_groth16_verify_aggregate: inputs_per_proof is not num_instance - 1");
-    for (size_t i = 0; i < count * ninp; i++)
-        if (!zk_fr_words_valid(inputs_host[i].l)) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_groth16_verify_aggregate: a public input is not below r");
+    if (!agg_args_ok(count, inputs_host, ninp, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
+    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES - 3, "zk_groth16_verify_aggregate"));
     *ok_all = 0;
     if (folded) memset(folded, 0, sizeof *folded);
-
-    // host staging as zk_groth16_verify_batch: the compressed G1 points (A_k, C_k), the compressed B_k
-    std::vector<uint8_t> g1c(count * 2 * 48), g2c(count * 96);
-    for (size_t k = 0; k < count; k++) {
-        const uint8_t* pr = proofs_host + k * 192;
-        memcpy(&g1c[(2 * k) * 48], pr, 48);
-        memcpy(&g2c[k * 96], pr + 48, 96);
-        memcpy(&g1c[(2 * k + 1) * 48], pr + 144, 48);
-    }
     std::vector<uint32_t> abc_w((ninp + 1) * 24);
     ZK_HIP(ctx, hipMemcpy(abc_w.data(), pk->gamma_abc->dev, abc_w.size() * 4, hipMemcpyDeviceToHost));
 
-    const size_t n = count + 3, n_part = (count + 63) / 64, n_fold = (n + FOLD_SPAN - 1) / FOLD_SPAN;
-    uint8_t *d_g1c, *d_g2c;
-    uint32_t *d_coef, *ac, *b, *flags, *P, *Q, *ml, *part_a, *part_b, *fold_a, *fold_b;
-    ZK_TRY(zk_scratch(ctx, "vfy_g1c", g1c.size(), (void**)&d_g1c));
-    ZK_TRY(zk_scratch(ctx, "vfy_g2c", g2c.size(), (void**)&d_g2c));
+    const size_t n = count + 3, n_part = zk_blocks64(count);
+    uint32_t *d_coef, *ac, *b, *flags, *P, *Q, *ml, *part_a, *part_b;
     ZK_TRY(zk_scratch(ctx, "agg_coef", count * 16, (void**)&d_coef));
-    ZK_TRY(zk_scratch(ctx, "vfy_ac", count * 2 * 96, (void**)&ac));
-    ZK_TRY(zk_scratch(ctx, "vfy_b", count * 192, (void**)&b));
     ZK_TRY(zk_scratch(ctx, "agg_flags", 4, (void**)&flags));
-    ZK_TRY(zk_scratch(ctx, "pair_p", n * 96, (void**)&P));
-    ZK_TRY(zk_scratch(ctx, "pair_q", n * 192, (void**)&Q));
-    ZK_TRY(zk_scratch(ctx, "pair_ml", n * GTW * 4, (void**)&ml));
+    ZK_TRY(zk_pair_scratch(ctx, n, &P, &Q, &ml));
+    ZK_TRY(zk_fold_scratch(ctx, n, nullptr, nullptr));        // (reserved now: zk_miller_product takes them with the kernels in flight)
     ZK_TRY(zk_scratch(ctx, "agg_part_a", n_part * XW * 4, (void**)&part_a));
     ZK_TRY(zk_scratch(ctx, "agg_part_b", (n_part / 64 + 1) * XW * 4, (void**)&part_b));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_a", n_fold * GTW * 4, (void**)&fold_a));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_b", (n_fold / FOLD_SPAN + 1) * GTW * 4, (void**)&fold_b));
     hipStream_t st = ctx->stream;
-    ZK_HIP(ctx, hipMemcpyAsync(d_g1c, g1c.data(), g1c.size(), hipMemcpyHostToDevice, st));
-    ZK_HIP(ctx, hipMemcpyAsync(d_g2c, g2c.data(), g2c.size(), hipMemcpyHostToDevice, st));
     ZK_HIP(ctx, hipMemcpyAsync(d_coef, coeffs, count * 16, hipMemcpyHostToDevice, st));
-    ZK_HIP(ctx, hipMemsetAsync(flags, 0, 4, st));
     ZkPhaseTimer tm(ctx);                         // with zk_set_profiling: "verify_aggregate.<phase>", device time by events
-    HostLap lap{ctx};
-    tm.begin("verify_aggregate.k_decompress");
-    ZK_TRY(zk_decompress_launch(ctx, 1, (const uint32_t*)d_g1c, 2 * count, ac, flags, nullptr));
-    ZK_TRY(zk_decompress_launch(ctx, 2, (const uint32_t*)d_g2c, count, b, flags, nullptr));
-    tm.end();
-    // ALWAYS: the fold's soundness argument needs prime-order groups, and the Miller loop is not bilinear for a B outside G2
-    tm.begin("verify_aggregate.k_subgroup");
-    ZK_TRY(zk_subgroup_launch(ctx, 1, ac, 2 * count, flags, nullptr));
-    ZK_TRY(zk_subgroup_launch(ctx, 2, b, count, flags, nullptr));
-    tm.end();
+    ZkHostLap lap{ctx, "verify_aggregate."};      // ... and host wall-clock since the lap before
+    // the subgroup tests ALWAYS: the fold's soundness argument needs prime-order groups, and the Miller loop is not bilinear for a B outside G2
+    std::vector<uint8_t> staging;
+    ZK_TRY(stage_proofs(ctx, count, proofs_host, true, flags, nullptr, nullptr, &ac, &b, &staging, &tm, &lap));      // "k_decompress", "k_subgroup"
     tm.begin("verify_aggregate.k_scale");
     ZK_TRY(scale_fold_launch(ctx, ac, 2, false, d_coef, count, P, nullptr));                    // r_i A_i -> P[0 .. count)
     ZK_HIP(ctx, hipMemcpyAsync(Q, b, count * 192, hipMemcpyDeviceToDevice, st));
@@ -418,24 +419,38 @@ int aggregate_dev(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* input
     tm.begin("verify_aggregate.k_miller");
     ZK_TRY(zk_miller_launch(ctx, P, Q, n, ml));
     tm.end();
-    size_t m = n;
-    const uint32_t* res;
-    tm.begin("verify_aggregate.k_fold");
-    ZK_TRY(fq12_fold_down(ctx, ml, fold_a, fold_b, &m, 64, &res));
-    tm.end();
-    std::vector<uint32_t> h_ml(m * GTW);
-    ZK_HIP(ctx, hipMemcpyAsync(h_ml.data(), res, h_ml.size() * 4, hipMemcpyDeviceToHost, st));
-    ZK_HIP(ctx, hipStreamSynchronize(st));
-    lap.lap("wait_miller");
-    const Fq12<H2> r = host_finish(h_ml.data(), m);
-    lap.lap("host_finish");
+    Fq12<H2> r;
+    ZK_TRY(zk_miller_product(ctx, ml, n, &r, &tm, &lap));      // "k_fold", "wait_miller", "host_finish"
     tm.resolve();
     *ok_all = fq12_eq<H2>(r, fq12_one<H2>()) ? 1 : 0;
-    if (folded) host_gt_out(folded, r);
+    if (folded) zk_host_gt_out(folded, r);
     return ZK_OK;
 }
 
 }  // namespace
+
+extern "C" int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
+    ZK_API_BEGIN_NOCTX
+    return verify_host(vk, inputs, n_inputs, proof, ok, false);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
+    ZK_API_BEGIN_NOCTX
+    return verify_host(vk, inputs, n_inputs, proof, ok, true);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                       const uint8_t* proofs_host, int* ok) {
+    ZK_API_BEGIN(ctx)
+    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, false);
+    ZK_API_END
+}
+extern "C" int zk_groth16_verify_batch_checked(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                               const uint8_t* proofs_host, int* ok) {
+    ZK_API_BEGIN(ctx)
+    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, true);
+    ZK_API_END
+}
 
 extern "C" int zk_groth16_verify_aggregate_coeffs(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                                   const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
@@ -480,62 +495,6 @@ extern "C" int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t 
     ZK_API_END
 }
 
-extern "C" int zk_pairing_product_long(zk_ctx* ctx, const zk_g1_affine* p, const zk_g2_affine* q, size_t n, zk_gt* out) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !p || !q || !out || !n || n > MAX_LANES) return ZK_ERR_ARG;
-    const size_t n_fold = (n + FOLD_SPAN - 1) / FOLD_SPAN;
-    uint32_t *dp, *dq, *ml, *fold_a, *fold_b;
-    ZK_TRY(zk_scratch(ctx, "pair_p", n * 96, (void**)&dp));
-    ZK_TRY(zk_scratch(ctx, "pair_q", n * 192, (void**)&dq));
-    ZK_TRY(zk_scratch(ctx, "pair_ml", n * GTW * 4, (void**)&ml));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_a", n_fold * GTW * 4, (void**)&fold_a));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_b", (n_fold / FOLD_SPAN + 1) * GTW * 4, (void**)&fold_b));
-    ZK_HIP(ctx, hipMemcpyAsync(dp, p, n * 96, hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP(ctx, hipMemcpyAsync(dq, q, n * 192, hipMemcpyHostToDevice, ctx->stream));
-    ZK_TRY(zk_miller_ext_launch(ctx, dp, dq, n, ml));
-    size_t m = n;
-    const uint32_t* res;
-    ZK_TRY(fq12_fold_down(ctx, ml, fold_a, fold_b, &m, 64, &res));
-    std::vector<uint32_t> h_ml(m * GTW);
-    ZK_HIP(ctx, hipMemcpyAsync(h_ml.data(), res, h_ml.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    host_gt_out(out, host_finish(h_ml.data(), m));
-    return ZK_OK;
-    ZK_API_END
-}
-
-extern "C" size_t zk_diag_fq12_fold_span(void) { return FOLD_SPAN; }
-
-extern "C" int zk_diag_fq12_fold_dev(zk_ctx* ctx, const zk_gt* in, size_t n, zk_gt* out) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !in || !out || !n || n > MAX_LANES) return ZK_ERR_ARG;
-    for (size_t i = 0; i < n; i++)
-        if (!zk_words_below_q((const uint64_t*)&in[i], 12)) return ZK_ERR_ARG;
-    const size_t n_fold = (n + FOLD_SPAN - 1) / FOLD_SPAN;
-    uint32_t *d_in, *a, *b;
-    ZK_TRY(zk_scratch(ctx, "pair_ml", n * GTW * 4, (void**)&d_in));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_a", n_fold * GTW * 4, (void**)&a));
-    ZK_TRY(zk_scratch(ctx, "agg_fold_b", (n_fold / FOLD_SPAN + 1) * GTW * 4, (void**)&b));
-    ZK_HIP(ctx, hipMemcpyAsync(d_in, in, n * GTW * 4, hipMemcpyHostToDevice, ctx->stream));
-    // the kernel alone, down to ONE value (n = 1: one launch all the same); the first launch reads, the last writes the ABI's form
-    const uint32_t* src = d_in;
-    size_t m = n;
-    bool first = true;
-    do {
-        const size_t m_out = (m + FOLD_SPAN - 1) / FOLD_SPAN;
-        hipLaunchKernelGGL(k_fq12_fold, blocks_of(m, FOLD_SPAN), 64, 0, ctx->stream, src, m, a, first ? 1 : 0, m_out == 1 ? 1 : 0);
-        ZK_HIP(ctx, hipGetLastError());
-        m = m_out;
-        src = a;
-        std::swap(a, b);
-        first = false;
-    } while (m > 1);
-    ZK_HIP(ctx, hipMemcpyAsync(out, src, GTW * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ZK_OK;
-    ZK_API_END
-}
-
 extern "C" int zk_diag_g1_scale_sum_dev(zk_ctx* ctx, const zk_g1_affine* pts, const uint64_t* coeffs, size_t n, zk_g1_affine* scaled_out,
                                         zk_g1_projective* sum_out) {
     ZK_API_BEGIN(ctx)
@@ -544,7 +503,7 @@ extern "C" int zk_diag_g1_scale_sum_dev(zk_ctx* ctx, const zk_g1_affine* pts, co
         if (!zk_words_below_q((const uint64_t*)&pts[i], 2)) return ZK_ERR_ARG;
     std::vector<uint32_t> w(n * 24);
     for (size_t i = 0; i < n; i++) aff_store<G1Field>(&w[24 * i], host_aff_from_abi<G1Field>((const uint64_t*)&pts[i]));
-    const size_t n_part = (n + 63) / 64;
+    const size_t n_part = zk_blocks64(n);
     uint32_t *d_pts, *d_coef = nullptr, *d_aff = nullptr, *part_a, *part_b;
     ZK_TRY(zk_scratch(ctx, "agg_diag_pts", n * 96, (void**)&d_pts));
     if (coeffs) ZK_TRY(zk_scratch(ctx, "agg_coef", n * 16, (void**)&d_coef));

@@ -3,6 +3,7 @@
 // The O(1)-per-proof group work of create_proof (src/groth16.rs:115-176) runs on the host with these.
 #pragma once
 #include "devutil.cuh"
+#include "hostfield64.hpp"
 #include <string.h>
 
 namespace zk {
@@ -126,3 +127,10 @@ inline XYZZ<F> host_scalar_mul(const XYZZ<F>& p, const uint32_t k[8]) {
 }
 
 }  // namespace zk
+
+// n_fq coordinates of the ABI's structs (six 64-bit words each, the reference's Montgomery form): every one below q
+inline bool zk_words_below_q(const uint64_t* l, int n_fq) {
+    for (int i = 0; i < n_fq; i++)
+        if (zk::host64::cmp(l + 6 * i, zk::host64::P) >= 0) return false;
+    return true;
+}

@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <atomic>
+#include <chrono>
 #include <functional>
 #include <memory>
 #include <string>
@@ -178,6 +179,23 @@ struct ZkPhaseTimer {
     void end();
     void resolve();  // waits for the recorded end events (not for the stream) and accumulates into ctx->timers
 };
+// host wall-clock laps: with zk_set_profiling, lap(what) adds the time since the lap before (or since construction) to the
+// context's timer "<prefix><what>" -- a lap includes whatever device work the host waited for
+struct ZkHostLap {
+    zk_ctx* ctx;
+    const char* prefix;        // "marlin.", "marlin_verify.", "verify_aggregate."
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char* what) {
+        if (!ctx->profiling) return;
+        const auto now = std::chrono::steady_clock::now();
+        auto& tm = ctx->timers[std::string(prefix) + what];
+        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
+        tm.count += 1;
+        t = now;
+    }
+};
+
+inline unsigned zk_blocks64(size_t n) { return (unsigned)((n + 63) / 64); }      // the grid of a launch with one lane per item, one wave per block
 
 // What a context's pinned host buffers are for (the kind of a ZkPin; ctx.hpp: zk_pinned).  idx says which one of the kind.
 enum ZkPinKind : uint8_t {
@@ -298,11 +316,27 @@ int zk_subgroup_launch(zk_ctx* ctx, int group, const uint32_t* table_dev, size_t
 bool zk_host_in_subgroup_g1(const zk::Affine<zk::G1Field>& p);      // ... and one point on the host (64-bit limbs)
 bool zk_host_in_subgroup_g2(const zk::Affine<zk::G2Field>& p);
 
-// pairing.hip: its Miller-loop and finish kernels for pairs that are on the device already (table form); lanes in one launch at most
+// pairing.hip: its kernels for every caller whose pairs are on the device already (its own entry points, groth16_verify.hip,
+// marlin_verify.hip); on ctx->stream, no wait.  Lanes in one launch at most:
 constexpr size_t ZK_PAIRING_MAX_LANES = (size_t)1 << 22;
-int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev);
-int zk_miller_ext_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev);   // ... points as the ABI's structs
-int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, const uint32_t* want_dev, const uint32_t* bad_dev, int* ok_dev);
+// the scratch of n pairs: "pair_p" (n G1 points), "pair_q" (n G2 points), "pair_ml" (n Miller values); a NULL pointer skips its slot
+int zk_pair_scratch(zk_ctx* ctx, size_t n, uint32_t** p_dev, uint32_t** q_dev, uint32_t** ml_dev);
+// n pairs, table form (ext: the ABI's structs, Montgomery words of the reference) -> n Miller values, packed (pairing.cuh: FQ12_WORDS each)
+int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev, bool ext = false);
+// product k of `pairs` consecutive Miller values, k < count, through the final exponentiation.  gt_dev (or NULL): the GT values in the
+// ABI's form.  ok_dev (or NULL): ok[k] = product k equals want_dev (packed, internal form) and bad_dev[k] (or NULL) is clear.
+int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, uint32_t* gt_dev, const uint32_t* want_dev,
+                             const uint32_t* bad_dev, int* ok_dev);
+// FE(the product of the n packed Miller values at ml_dev), n as large as a launch: folded on the device down to at most 64 partial
+// products (k_fq12_fold), those copied back, their product and the final exponentiation on the host (pairing.cuh over Fq264Field).
+// Waits for ctx->stream.  A caller that keeps timers passes both: with zk_set_profiling the fold launches go to tm as
+// "<lap->prefix>k_fold", the wait for the partials and the host's part to lap as "wait_miller" and "host_finish".
+// zk_fold_scratch: the fold's two buffers ("agg_fold_a" / "agg_fold_b") for n values.  zk_miller_product takes them itself; a caller
+// with device work in flight by then reserves them beforehand (a = b = NULL), because a slot that has to grow waits for the stream.
+namespace zk { template <class F2> struct Fq12; struct Fq264Field; }
+int zk_fold_scratch(zk_ctx* ctx, size_t n, uint32_t** a_dev, uint32_t** b_dev);
+int zk_miller_product(zk_ctx* ctx, const uint32_t* ml_dev, size_t n, zk::Fq12<zk::Fq264Field>* out, ZkPhaseTimer* tm = nullptr,
+                      ZkHostLap* lap = nullptr);
 // g1_lincomb.hip: n_segments short linear combinations of G1 points in one launch, one term per lane.  Lane g holds point
 // point_index[g] of points_dev (table form; n_points of them) and the raw 256-bit scalar scalars_dev[8 g ..]; segment s is the lanes
 // seg_offsets[s] .. seg_offsets[s + 1] - 1, which must lie in one wave of 64 (ZkLincombPack lays the lanes out so); seg_offsets[0] = 0,

@@ -171,21 +171,6 @@ struct MsmJobs {
     }
 };
 
-// with zk_set_profiling(ctx, 1): host wall-clock laps of the phases land in the context's timers as "marlin.<phase>" (a lap
-// includes whatever device work the host waited for)
-struct Laps {
-    zk_ctx* ctx; bool on;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    explicit Laps(zk_ctx* c) : ctx(c), on(c->profiling) {}
-    void lap(const char* what) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        auto& tm = ctx->timers[std::string("marlin.") + what];
-        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
-        tm.count += 1; t = now;
-    }
-};
-
 struct Term { HF c; Oracle o; };                // o = O_NONE: the constant term (LCTerm::One)
 using LinComb = std::vector<Term>;
 
@@ -210,7 +195,7 @@ template <int LANES>
 struct Marlin : MarlinArgs {
     zk_ctx* const ctx;
     const size_t max_degree; const char* zb[2];   // of the SRS; the (shares of the) padded assignment
-    Laps laps; ZkSharedNet nt; const bool leader;
+    ZkHostLap laps; ZkSharedNet nt; const bool leader;
     Prover PL[2]; Prover& P = PL[0];              // lane 0 also computes everything public
     const Dom H, K, X, B;
     const size_t n, ni, md, nwq;                  // |H|, |X|, the mask polynomial's degree (zk_bound = 1), coefficients of w
@@ -234,7 +219,7 @@ struct Marlin : MarlinArgs {
     Affine<G1Field> wit[2];                       // open_combinations: per query point the witness, and random_v if hiding
     bool has_rv[2] = {false, false}; HF rvs[2];
     Marlin(zk_ctx* c, const MarlinArgs& args)
-        : MarlinArgs(args), ctx(c), max_degree(powers_g->n - 1), zb{(const char*)z[0], LANES == 2 ? (const char*)z[1] : nullptr}, laps(c), nt{c, net},
+        : MarlinArgs(args), ctx(c), max_degree(powers_g->n - 1), zb{(const char*)z[0], LANES == 2 ? (const char*)z[1] : nullptr}, laps{c, "marlin."}, nt{c, net},
           leader(nt.leader()), PL{Prover{c, 0}, Prover{c, 1}}, H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * K.size - 3),
           n(H.size), ni(ix->num_instance), md(3 * n + 2 - 3), nwq(n + 1 - X.size), MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1)) {
         for (int l = 0; l < LANES; l++)

@@ -31,7 +31,6 @@ using namespace zk;
 namespace {
 
 using H2 = Fq264Field;
-constexpr int GTW = 144;
 constexpr size_t IVK_COMM = 2 * 97 + 1, IVK_LEN = 24 + 12 * IVK_COMM;      // marlin_pc::Commitment::write: comm | bool | shifted_comm
 
 // the points an equation refers to: the key's sixteen, then the proof's thirteen
@@ -69,11 +68,6 @@ bool on_curve_g2(const Affine<G2Field>& p) {
     const Affine<H2> a = aff_to_host64<G2Field>(p);
     return H2::eq(H2::sqr(a.y), H2::add(H2::mul(H2::sqr(a.x), a.x), Host64Curve<H2>::b()));
 }
-bool abi_words_below_q(const void* p, int n_fq) {
-    for (int i = 0; i < n_fq; i++)
-        if (host64::cmp((const uint64_t*)p + 6 * i, host64::P) >= 0) return false;
-    return true;
-}
 
 // what is wrong with the CALL (ZK_ERR_ARG): the key as the struct gives it
 bool load_key(const zk_marlin_vk_host* vk, Key* k) {
@@ -95,12 +89,12 @@ bool load_key(const zk_marlin_vk_host* vk, Key* k) {
     }
     const zk_g1_affine* g1s[4] = {&vk->g, &vk->gamma_g, &vk->shift_h, &vk->shift_k};
     for (int i = 0; i < 4; i++) {
-        if (!abi_words_below_q(g1s[i], 2)) return false;
+        if (!zk_words_below_q((const uint64_t*)g1s[i], 2)) return false;
         k->pts[KP_G + i] = host_aff_from_abi<G1Field>((const uint64_t*)g1s[i]);
     }
     for (int i = 0; i < (int)N_KEY_POINTS; i++)
         if (aff_is_inf<G1Field>(k->pts[i]) || !on_curve_g1(k->pts[i])) return false;
-    if (!abi_words_below_q(&vk->h, 4) || !abi_words_below_q(&vk->beta_h, 4)) return false;
+    if (!zk_words_below_q((const uint64_t*)&vk->h, 4) || !zk_words_below_q((const uint64_t*)&vk->beta_h, 4)) return false;
     k->h = host_aff_from_abi<G2Field>((const uint64_t*)&vk->h);
     const Affine<G2Field> bh = host_aff_from_abi<G2Field>((const uint64_t*)&vk->beta_h);
     if (aff_is_inf<G2Field>(k->h) || aff_is_inf<G2Field>(bh) || !on_curve_g2(k->h) || !on_curve_g2(bh)) return false;
@@ -309,12 +303,6 @@ Equations build_equations(const Key& key, const std::vector<HF>& x, const Parsed
 
 void r_words(uint32_t w[8]) { fp_pack<FrParams>(w, fp_const<FrParams>(FrParams::P)); }      // r itself, for the subgroup test
 
-// pairs = 2 products against this: the Fq12 one, packed internal words (k_pairing_finish's `want`)
-void packed_one(uint32_t w[GTW]) {
-    memset(w, 0, GTW * 4);
-    Fq2Field::store(w, Fq2Field::one());
-}
-
 // proof k of a batch: its Miller pairs (L_beta, h), (W_beta, -beta_h), (L_gamma, h), (W_gamma, -beta_h), and per PRODUCT the flag
 // that voids it: the host's structural verdict, a point off the curve, a point outside the subgroup (r P != O)
 __global__ void __launch_bounds__(64) k_marlin_pairs(size_t count, const uint32_t* __restrict__ lc_out, const uint32_t* __restrict__ lc_inf,
@@ -335,19 +323,6 @@ __global__ void __launch_bounds__(64) k_marlin_pairs(size_t count, const uint32_
     for (size_t i = 0; i < N_PROOF_POINTS; i++) b |= bad_pt[N_PROOF_POINTS * k + i] | (lc_inf[SEGS * k + 2 + i] ? 0u : 1u);
     bad[2 * k] = bad[2 * k + 1] = b ? 1u : 0u;
 }
-
-struct Lap {
-    zk_ctx* ctx;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char* what) {                    // with zk_set_profiling: host wall-clock of a phase into "marlin_verify.<phase>"
-        if (!ctx->profiling) return;
-        const auto now = std::chrono::steady_clock::now();
-        auto& tm = ctx->timers[std::string("marlin_verify.") + what];
-        tm.ms += (float)std::chrono::duration<double, std::milli>(now - t).count();
-        tm.count += 1;
-        t = now;
-    }
-};
 
 }  // namespace
 
@@ -398,7 +373,7 @@ extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, 
     std::vector<std::vector<HF>> xs(count);
     for (size_t k = 0; k < count; k++)
         if (!load_input(inputs_host + k * inputs_per_proof, inputs_per_proof, &xs[k])) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_verify_batch: a public input is not below r");
-    Lap lap{ctx};
+    ZkHostLap lap{ctx, "marlin_verify."};         // with zk_set_profiling: host wall-clock of a phase into "marlin_verify.<phase>"
 
     // 1. the bytes: structure on the host, the 13 count compressed points to the device (a proof without them: infinity)
     constexpr size_t NP = N_PROOF_POINTS, SEGS = 2 + NP;
@@ -421,7 +396,7 @@ extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, 
     ZK_TRY(zk_scratch(ctx, "mvfy_pts", n_pts * 96, (void**)&d_pts));
     // any | bad_pt (13 count) | host_bad (count) | bad (2 count) | ok (2 count)
     ZK_TRY(zk_scratch(ctx, "mvfy_flags", (1 + NP * count + count + 2 * count + 2 * count) * 4, (void**)&d_flags));
-    ZK_TRY(zk_scratch(ctx, "mvfy_g2", 2 * 192 + GTW * 4, (void**)&d_g2));
+    ZK_TRY(zk_scratch(ctx, "mvfy_g2", 2 * 192 + FQ12_WORDS * 4, (void**)&d_g2));
     uint32_t *bad_any = d_flags, *bad_pt = d_flags + 1, *d_host_bad = bad_pt + NP * count, *bad = d_host_bad + count;
     int* d_ok = (int*)(bad + 2 * count);
     hipStream_t st = ctx->stream;
@@ -479,19 +454,17 @@ extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, 
     pk.finish();
     lap.lap("build");
     // 3. the key's constants, the term lists; combinations; pairs; pairings
-    struct Consts { uint32_t g1[N_KEY_POINTS * 24]; uint32_t g2[2 * 48]; uint32_t one[GTW]; } cs;
+    struct Consts { uint32_t g1[N_KEY_POINTS * 24]; uint32_t g2[2 * 48]; uint32_t one[FQ12_WORDS]; } cs;
     for (int i = 0; i < (int)N_KEY_POINTS; i++) aff_store<G1Field>(cs.g1 + 24 * i, key.pts[i]);
     aff_store<G2Field>(cs.g2, key.h);
     aff_store<G2Field>(cs.g2 + 48, key.neg_beta_h);
-    packed_one(cs.one);
+    fq12_host_to_packed(cs.one, fq12_one<H2>());      // pairs = 2 products against the Fq12 one (k_pairing_finish's `want`)
     ZK_TRY(zk_scratch(ctx, "mvfy_idx", pk.point_index.size() * 4, (void**)&d_idx));
     ZK_TRY(zk_scratch(ctx, "mvfy_k", pk.scalars.size() * 4, (void**)&d_k));
     ZK_TRY(zk_scratch(ctx, "mvfy_off", pk.seg_off.size() * 4, (void**)&d_off));
     ZK_TRY(zk_scratch(ctx, "mvfy_lc", SEGS * count * 96, (void**)&d_lc));
     ZK_TRY(zk_scratch(ctx, "mvfy_lcinf", SEGS * count * 4, (void**)&d_lcinf));
-    ZK_TRY(zk_scratch(ctx, "pair_p", n_pairs * 96, (void**)&P));
-    ZK_TRY(zk_scratch(ctx, "pair_q", n_pairs * 192, (void**)&Q));
-    ZK_TRY(zk_scratch(ctx, "pair_ml", n_pairs * GTW * 4, (void**)&ml));
+    ZK_TRY(zk_pair_scratch(ctx, n_pairs, &P, &Q, &ml));
     ZK_HIP(ctx, hipMemcpyAsync(d_pts, cs.g1, sizeof cs.g1, hipMemcpyHostToDevice, st));
     ZK_HIP(ctx, hipMemcpyAsync(d_g2, cs.g2, sizeof cs.g2 + sizeof cs.one, hipMemcpyHostToDevice, st));
     ZK_HIP(ctx, hipMemcpyAsync(d_host_bad, host_bad.data(), count * 4, hipMemcpyHostToDevice, st));
@@ -502,11 +475,11 @@ extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, 
     ZK_TRY(zk_g1_lincomb_launch(ctx, d_pts, n_pts, d_idx, d_k, d_off, SEGS * count, pk.lanes(), d_lc, d_lcinf));
     tm.end();
     tm.begin("marlin_verify.k_pairing");
-    hipLaunchKernelGGL(k_marlin_pairs, (unsigned)((count + 63) / 64), 64, 0, st, count, (const uint32_t*)d_lc, (const uint32_t*)d_lcinf, (const uint32_t*)d_pts,
+    hipLaunchKernelGGL(k_marlin_pairs, zk_blocks64(count), 64, 0, st, count, (const uint32_t*)d_lc, (const uint32_t*)d_lcinf, (const uint32_t*)d_pts,
                        (const uint32_t*)d_g2, (const uint32_t*)d_host_bad, (const uint32_t*)bad_pt, P, Q, bad);
     ZK_HIP(ctx, hipGetLastError());
     ZK_TRY(zk_miller_launch(ctx, P, Q, n_pairs, ml));
-    ZK_TRY(zk_pairing_finish_launch(ctx, ml, 2, 2 * count, d_g2 + 2 * 48, bad, d_ok));
+    ZK_TRY(zk_pairing_finish_launch(ctx, ml, 2, 2 * count, nullptr, d_g2 + 2 * 48, bad, d_ok));
     tm.end();
     std::vector<int> ok2(2 * count);
     ZK_HIP(ctx, hipMemcpyAsync(ok2.data(), d_ok, 2 * count * sizeof(int), hipMemcpyDeviceToHost, st));

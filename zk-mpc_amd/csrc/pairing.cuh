@@ -33,6 +33,8 @@
 
 namespace zk {
 
+constexpr int FQ12_WORDS = 144;     // 32-bit words of an Fq12, packed or in the ABI's form (zk_gt)
+
 #define ZK_PAIR_FN __host__ __device__ __attribute__((noinline))
 
 // what the tower needs beyond the policy interface
@@ -313,4 +315,18 @@ template <class F2> ZK_PAIR_FN void pairing_product(Fq12<F2>& r, const Affine<ty
     final_exponentiation<F2>(r, acc);
 }
 
+// ---- packed form: the 144 words of the six Fq2Field coefficients in tower order, internal form -- what k_miller writes, what the
+// finish kernel's `want` and zk_pk::e_alpha_beta hold.  On the host an Fq12 is kept over Fq264Field. -----------------------------------
+inline Fq12<Fq264Field> fq12_host_from_packed(const uint32_t* w144) {
+    Fq12<Fq264Field> f;
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 3; j++) f.c[i].c[j] = Fq264Field::from_dev(Fq2Field::load(w144 + 24 * (3 * i + j)));
+    return f;
+}
+inline void fq12_host_to_packed(uint32_t* w144, const Fq12<Fq264Field>& f) {
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 3; j++) Fq2Field::store(w144 + 24 * (3 * i + j), Fq264Field::to_dev(f.c[i].c[j]));
+}
+
 }  // namespace zk
+

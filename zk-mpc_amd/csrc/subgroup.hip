@@ -95,7 +95,7 @@ bool report_clean(const zk_pk_subgroup_report& rep, int* part) {
 int zk_subgroup_launch(zk_ctx* ctx, int group, const uint32_t* table_dev, size_t n, uint32_t* bad_dev, uint32_t* bad_each_dev, bool or_each) {
     if (!n) return ZK_OK;
     if (n > ((size_t)1 << 37)) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_subgroup_launch: too many points for one launch");
-    const unsigned blocks = (unsigned)((n + 63) / 64);
+    const unsigned blocks = zk_blocks64(n);
     if (group == 2 && or_each) hipLaunchKernelGGL((k_subgroup<G2Field, true>), blocks, 64, 0, ctx->stream, table_dev, n, bad_dev, bad_each_dev);
     else if (group == 2) hipLaunchKernelGGL((k_subgroup<G2Field, false>), blocks, 64, 0, ctx->stream, table_dev, n, bad_dev, bad_each_dev);
     else if (or_each) hipLaunchKernelGGL((k_subgroup<G1Field, true>), blocks, 64, 0, ctx->stream, table_dev, n, bad_dev, bad_each_dev);
