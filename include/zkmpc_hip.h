@@ -614,6 +614,34 @@ int zk_marlin_verify_host(const zk_marlin_vk_host* vk, const zk_fr* inputs, size
 int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                            const uint8_t* proofs_host, const size_t* offsets, int* ok);
 
+/* ---- aggregated Marlin verification: count proofs of one key as ONE folded KZG check, on the host (csrc/marlin_verify.hip) ----------- */
+/* KZG10::batch_check (poly-commit/src/kzg10/mod.rs:345) over every opening equation of every proof.  Proof k has two, at q = beta and
+ * gamma: e(L_{k,q}, h) e(W_{k,q}, -beta_h) = 1.  With one 128-bit coefficient rho_{k,q} per EQUATION (coeffs: 2 uint64 per equation,
+ * low word first, equation 2 k + q: 2 count of them) the batch is accepted iff
+ *     e( sum rho_{k,q} L_{k,q}, h ) . e( sum rho_{k,q} W_{k,q}, -beta_h ) = 1,
+ * which is TWO Miller loops and ONE final exponentiation for the whole batch where Marlin::verify proof by proof runs 4 count and
+ * 2 count.  The first sum is taken point by point: each of a proof's 13 points occurs in one of its two term lists and gets one
+ * full-width scalar rho c mod r, the key's 16 points get one scalar each, summed over the batch: 13 count + 16 multiplications
+ * through the G1 endomorphism, and 2 count 128-bit ones for the second sum.  If every proof is valid the product is one whatever the
+ * coefficients are; if one is not, it is one for about 2^-128 of the coefficient vectors -- for coefficients the prover(s) could not
+ * predict: draw them after the proofs arrived (zk_verify_aggregate_coeffs_from_seed(seed, 2 count)).  A zero coefficient drops its
+ * equation.
+ * ok_all = 1 iff every proof parses, every point is canonical, on the curve and in the prime-order subgroup, and the product is one.
+ * The subgroup test of the 13 count proof points always runs (the fold's argument needs prime order, and so does the endomorphism).
+ * folded (or NULL) = the product in GT as computed: final_exponentiation's value to the power zk_gt_exponent_multiple(); all-zero when a
+ * proof's structure or a point was rejected, which ends the call before any multiplication.
+ * ZK_ERR_ARG: what zk_marlin_verify_batch refuses, a null coeffs / ok_all, count above 2^18, and a key point outside the prime-order
+ * subgroup (the endomorphism multiplies the key's points too).
+ * This is the host arithmetic: no device, no context, about 1.5 ms per proof.  A device form (the long sum as one term per lane) is
+ * not built. */
+int zk_marlin_verify_aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t inputs_per_proof, const uint8_t* proofs,
+                                    const size_t* offsets, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+/* Test hook: the per-term multiplication through the endomorphism that the sum above is written for a kernel with (csrc/g1_lincomb.cuh:
+ * lincomb_term_glv, instantiated over the host field).  n <= 2^22 points (coordinate words below q) with halves[8 i ..] = k1 | k2, four
+ * uint32 each: scaled_out (or NULL) = (k1 + k2 lambda) pts[i] as affine points, sum_out = their sum.  The halves are raw 128-bit values;
+ * the points must be in the prime-order subgroup for the result to be that multiple. */
+int zk_diag_g1_glv_sum_host(const zk_g1_affine* pts, const uint32_t* halves, size_t n, zk_g1_affine* scaled_out, zk_g1_projective* sum_out);
+
 /* ---- dense polynomials over Fr and KZG10 (row a14: the data-parallel pieces of the Marlin / poly-commit path) ---- */
 /* out[i] = start * base^i, i < n (device vector). */
 int zk_fr_powers_dev(zk_ctx* ctx, const zk_fr* base, const zk_fr* start, size_t n, void* out_dev);

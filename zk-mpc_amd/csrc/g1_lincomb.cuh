@@ -11,8 +11,10 @@
 // accumulator still is (the leading zero windows) or whose operands meet at equal x leaves the addition early or takes its
 // doubling arm, and sits masked while its neighbours run the general formulas.  The wave pays one full addition per window
 // either way (plus the doubling arm in the windows where some lane needs it), which is the cost the fixed schedule was chosen for.
+// lincomb_term_glv (below) is the same schedule at half the windows for points KNOWN to be in the subgroup (host instantiation only).
 #pragma once
 #include "ec.cuh"
+#include "hostfield64.hpp"
 
 namespace zk {
 
@@ -53,6 +55,73 @@ ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[NW], Tab& tab) {
         t.y = F::select(d < 0, F::neg(t.y), t.y);
         t.zz = F::select(m == 0, F::zero(), t.zz);          // a zero digit adds infinity
         acc = xyzz_add<F>(acc, t);
+    }
+    return acc;
+}
+
+// ---- one term through the endomorphism --------------------------------------------------------------------------------------------
+// (k1 + k2 lambda) P = k1 P + k2 phi(P) for P in the prime-order subgroup, phi(x, y) = (beta x, y) (hostfield64.hpp:
+// host64_scalar_mul_glv has the curve facts; host64_glv_split makes the halves, below 2^127 each for k < r).  The halves are 128 raw
+// bits each and any value up to 2^128 - 1 gives the right point: both are recoded as above (k + 0x88...8, 32 digits in [-8, 7] and a
+// carry digit), and the carries enter before the first window.  ONE table 1 P .. 8 P serves both: phi of an entry (X, Y, ZZ, ZZZ) is
+// (beta X, Y, ZZ, ZZZ), one product at the select.  The schedule is the same for every scalar -- seven table additions, the carry
+// addition, then 32 windows of four doublings and two complete additions, the second one's operand through phi -- against 64 windows
+// of four doublings and one addition for the plain term: about 200 group operations instead of 327.  On a point outside the subgroup
+// phi is not lambda and the result means nothing, but the arithmetic is the same complete formulas and ends.
+// Written in the form a one-term-per-lane kernel takes (digits select operands, never the control flow; GlvBeta<F> gives beta in
+// F's form); today it is instantiated over the host field only (zk_diag_g1_glv_sum_host) -- no kernel runs it yet.
+template <class F> struct GlvBeta;
+template <> struct GlvBeta<Fq64Field> {
+    static Fq64 get() { return Fq64Field::from_dev(fp_const<FqParams>(FqParams::BETA)); }
+};
+
+template <class F, class Tab>
+ZK_HD XYZZ<F> lincomb_term_glv(const Affine<F>& p, const uint32_t k1[4], const uint32_t k2[4], Tab& tab) {
+    uint32_t a[4], b[4], ca = 0, cb = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint64_t ta = (uint64_t)k1[i] + 0x88888888u + ca, tb = (uint64_t)k2[i] + 0x88888888u + cb;
+        a[i] = (uint32_t)ta;
+        ca = (uint32_t)(ta >> 32);
+        b[i] = (uint32_t)tb;
+        cb = (uint32_t)(tb >> 32);
+    }
+    const typename F::T beta = GlvBeta<F>::get();
+    const XYZZ<F> P = xyzz_from_affine<F>(p);
+    XYZZ<F> e = P;
+    tab.put(0, e);
+#pragma unroll 1
+    for (int i = 1; i < LINCOMB_TAB; i++) {
+        e = xyzz_add<F>(e, P);
+        tab.put(i, e);
+    }
+    // the carry digits: ca P + cb phi(P)
+    XYZZ<F> acc = P, t = P;
+    acc.zz = F::select(ca != 0, acc.zz, F::zero());
+    t.x = F::mul(t.x, beta);
+    t.zz = F::select(cb != 0, t.zz, F::zero());
+    acc = xyzz_add<F>(acc, t);
+#pragma unroll 1
+    for (int w = 31; w >= 0; w--) {
+#pragma unroll 1
+        for (int j = 0; j < 4; j++) acc = xyzz_dbl<F>(acc);
+        const int da = (int)(a[3] >> 28) - 8, db = (int)(b[3] >> 28) - 8;
+#pragma unroll
+        for (int i = 3; i > 0; i--) {
+            a[i] = (a[i] << 4) | (a[i - 1] >> 28);
+            b[i] = (b[i] << 4) | (b[i - 1] >> 28);
+        }
+        a[0] <<= 4;
+        b[0] <<= 4;
+#pragma unroll 1
+        for (int h = 0; h < 2; h++) {
+            const int d = h ? db : da, m = d < 0 ? -d : d;
+            t = tab.get(m ? m - 1 : 0);
+            if (h) t.x = F::mul(t.x, beta);
+            t.y = F::select(d < 0, F::neg(t.y), t.y);
+            t.zz = F::select(m == 0, F::zero(), t.zz);      // a zero digit adds infinity
+            acc = xyzz_add<F>(acc, t);
+        }
     }
     return acc;
 }

@@ -131,6 +131,37 @@ int zk_g1_lincomb_launch(zk_ctx* ctx, const uint32_t* points_dev, size_t n_point
     return ZK_OK;
 }
 
+// what the GLV hook refuses
+static bool glv_diag_args_ok(const zk_g1_affine* pts, const uint32_t* halves, size_t n, const zk_g1_projective* sum_out) {
+    if (!pts || !halves || !sum_out || !n || n > ((size_t)1 << 22)) return false;
+    for (size_t i = 0; i < n; i++)
+        if (!zk_words_below_q((const uint64_t*)&pts[i], 2)) return false;
+    return true;
+}
+
+extern "C" int zk_diag_g1_glv_sum_host(const zk_g1_affine* pts, const uint32_t* halves, size_t n, zk_g1_affine* scaled_out, zk_g1_projective* sum_out) {
+    ZK_API_BEGIN_NOCTX
+    if (!glv_diag_args_ok(pts, halves, n, sum_out)) return ZK_ERR_ARG;
+    using H = Fq64Field;
+    XYZZ<H> sum = xyzz_inf<H>();
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w[24];
+        memcpy(w, &pts[i], 96);
+        HostTab tab;
+        const XYZZ<H> t = lincomb_term_glv<H>(Affine<H>{H::load(w), H::load(w + 12)}, halves + 8 * i, halves + 8 * i + 4, tab);
+        sum = xyzz_add<H>(sum, t);
+        if (scaled_out) {
+            const Affine<H> a = xyzz_to_affine<H>(t);
+            H::store(w, a.x);
+            H::store(w + 12, a.y);
+            memcpy(&scaled_out[i], w, 96);
+        }
+    }
+    host64_write_projective<H>(xyzz_to_affine<H>(sum), (uint64_t*)sum_out);
+    return ZK_OK;
+    ZK_API_END
+}
+
 extern "C" int zk_diag_g1_lincomb_host(const zk_g1_affine* points, size_t n_points, const uint32_t* point_index, const uint32_t* scalars,
                                        const uint32_t* seg_offsets, size_t n_segments, zk_g1_affine* out) {
     ZK_API_BEGIN_NOCTX

@@ -229,7 +229,8 @@ def subgroup_consts():
     orders = [n for n in (Q_MOD * Q_MOD + 1 - (t2 + 3 * f2) // 2, Q_MOD * Q_MOD + 1 - (t2 - 3 * f2) // 2) if n % R_MOD == 0]
     assert len(orders) == 1 and _ec_mul(g2, orders[0], _Fq2) is None
     assert math.gcd(h1, orders[0] // R_MOD) == 1
-    return [("BETA2", beta2), ("PSI_CX", cx), ("PSI_CY", cy)]
+    # BETA itself: phi applied to a table entry (g1_lincomb.cuh: lincomb_term_glv)
+    return [("BETA", beta), ("BETA2", beta2), ("PSI_CX", cx), ("PSI_CY", cy)]
 
 
 def main():

@@ -128,10 +128,7 @@ int g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** res
 }
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
-HF coeff_fr(const uint64_t* c) {      // lo + 2^64 hi
-    static const HF two64 = HF::from_u64((uint64_t)1 << 32).sqr();
-    return HF::from_u64(c[0]) + HF::from_u64(c[1]) * two64;
-}
+HF coeff_fr(const uint64_t* c) { return HF::from_u128(c); }      // lo + 2^64 hi
 // s[0] = sum r_i, s[j + 1] = sum r_i x_{i,j} over the proofs [lo, hi)
 void coeff_sums(const uint64_t* coeffs, const zk_fr* inputs, size_t ninp, size_t lo, size_t hi, HF* s) {
     for (size_t j = 0; j <= ninp; j++) s[j] = HF::zero();

@@ -321,19 +321,27 @@ static const uint64_t GLV_BETA[6] = {0xdacd106da5847973ull, 0xd8fe2454bac2a79aul
 static const uint64_t GLV_LAMBDA[2] = {0x0a11800000000000ull, 0x452217cc90000001ull};                         // z^2 - 1, 127 bits
 }  // namespace host64
 
-inline XYZZ<Fq64Field> host64_scalar_mul_glv(const XYZZ<Fq64Field>& p, const uint32_t k[8]) {
-    using H = Fq64Field;
-    using X = XYZZ<H>;
+// k = k1 + k2 lambda: k2 = k / lambda, k1 = k mod lambda (bit-serial: the remainder stays below lambda < 2^127, so the shift cannot
+// overflow).  k1 is below 2^127 always, k2 too for k < r (any 256-bit k still splits: k2 then has up to 130 bits).  Shared by the
+// joint chain below and by whoever feeds g1_lincomb.cuh's lincomb_term_glv, which takes the low four words of each half.
+inline void host64_glv_split(const uint32_t k[8], uint32_t k1[8], uint32_t k2[8]) {
     typedef unsigned __int128 u128;
     const u128 lambda = ((u128)host64::GLV_LAMBDA[1] << 64) | host64::GLV_LAMBDA[0];
-    // k2 = k / lambda, k1 = k mod lambda (bit-serial: the remainder stays below lambda < 2^127, so the shift cannot overflow)
     u128 rem = 0;
-    uint32_t k2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 8; i++) k2[i] = 0;
     for (int i = 255; i >= 0; i--) {
         rem = (rem << 1) | ((k[i >> 5] >> (i & 31)) & 1u);
         if (rem >= lambda) { rem -= lambda; k2[i >> 5] |= 1u << (i & 31); }
     }
-    const uint32_t k1[8] = {(uint32_t)rem, (uint32_t)(rem >> 32), (uint32_t)(rem >> 64), (uint32_t)(rem >> 96), 0, 0, 0, 0};
+    k1[0] = (uint32_t)rem; k1[1] = (uint32_t)(rem >> 32); k1[2] = (uint32_t)(rem >> 64); k1[3] = (uint32_t)(rem >> 96);
+    k1[4] = k1[5] = k1[6] = k1[7] = 0;
+}
+
+inline XYZZ<Fq64Field> host64_scalar_mul_glv(const XYZZ<Fq64Field>& p, const uint32_t k[8]) {
+    using H = Fq64Field;
+    using X = XYZZ<H>;
+    uint32_t k1[8], k2[8];
+    host64_glv_split(k, k1, k2);
     int top = 255;                                   // the highest set bit of either half (k < r: <= 126; any 256-bit k still works)
     while (top > 0 && !(((k1[top >> 5] | k2[top >> 5]) >> (top & 31)) & 1u)) top--;
     H::T beta;

@@ -17,6 +17,11 @@ struct HF {
         t.l[0] = (uint32_t)(x & MASK29); t.l[1] = (uint32_t)((x >> 29) & MASK29); t.l[2] = (uint32_t)(x >> 58);
         return HF{fp_canon_to_int<FrParams>(t)};
     }
+    static HF from_u128(const uint64_t c[2]) {              // lo + 2^64 hi: a fold coefficient of the aggregated verifiers
+        static const HF two64 = from_u64((uint64_t)1 << 32).sqr();
+        return from_u64(c[0]) + from_u64(c[1]) * two64;
+    }
+    static HF from_canon_words(const uint32_t w[8]) { return HF{fp_canon_to_int<FrParams>(fp_unpack<FrParams>(w))}; }   // a plain integer below r
     static HF from_abi(const zk_fr& a) { return HF{fp_ext_to_int<FrParams>(host_load_ext<FrParams>(a.l))}; }
     zk_fr abi() const { zk_fr o; host_store_ext<FrParams>(o.l, fp_int_to_ext<FrParams>(v)); return o; }
     static HF from_limbs(const uint32_t* l) { return HF{limbs_get(l)}; }     // nine limbs, as the device keeps a constant

@@ -11,12 +11,15 @@
 // re-derives the transcript and turns (key, input, proof) into two lists of terms (point reference, Fr scalar), one per query point:
 //   L_q = sum_j xi^j (combination j of the commitments)  -  val_q g  -  random_v_q gamma_g  +  z_q W_q        (z = beta, gamma)
 // and the proof holds iff e(L_q, h) e(W_q, -beta_h) = 1 for both -- KZG10::check with the witness term moved to the left, so that G2
-// only ever sees the key's two points.  The two query points are NOT folded by a random coefficient (kzg10::batch_check takes an rng).
+// only ever sees the key's two points.  The two query points are NOT folded by a random coefficient (kzg10::batch_check takes an rng)
+// -- except by zk_marlin_verify_aggregate_host, which is that batch_check over every equation of a batch with the caller's
+// coefficients, on the host (the device form of it is not built).
 // The host back end evaluates the terms with host64_scalar_mul and pairing.cuh over Fq264Field; the device back end is
 // g1_lincomb.hip (one wave per proof) followed by pairing.hip's kernels as they are.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "fsrng.hpp"
+#include "groth16_int.hpp"
 #include "hostfield64.hpp"
 #include "hostgroup.hpp"
 #include "internal.hpp"
@@ -324,7 +327,88 @@ __global__ void __launch_bounds__(64) k_marlin_pairs(size_t count, const uint32_
     bad[2 * k] = bad[2 * k + 1] = b ? 1u : 0u;
 }
 
+// ---- folded, on the host ------------------------------------------------------------------------------------------------------------------
+// KZG10::batch_check (poly-commit/src/kzg10/mod.rs:345) over the 2 count opening equations: with rho_{k,q} = coeffs[2 (2 k + q) ..]
+// (128 bits)
+//     e( sum rho_{k,q} L_{k,q}, h ) . e( sum rho_{k,q} W_{k,q}, -beta_h ) = 1.
+// The first sum point by point: a proof's point occurs in ONE of its two term lists (fold_proof adds, so a builder that listed one
+// twice would still be right) and gets one full-width scalar rho c mod r; the key's sixteen occur in every proof's and get one scalar
+// each, summed over the batch: 13 count + 16 multiplications through the endomorphism (every point is in the subgroup by then).
+constexpr size_t AGG_MAX_COUNT = (size_t)1 << 18;      // 13 count + 16 terms below 2^22, the lane limit of the device's sum kernels
+void fold_proof(const Equations& eq, const uint64_t* coeffs4, HF proof_s[N_PROOF_POINTS], HF key_s[N_KEY_POINTS]) {
+    for (size_t i = 0; i < N_PROOF_POINTS; i++) proof_s[i] = HF::zero();
+    for (int q = 0; q < 2; q++) {
+        const HF rho = HF::from_u128(coeffs4 + 2 * q);
+        for (const Term& t : eq.q[q]) {
+            HF& into = t.point < N_KEY_POINTS ? key_s[t.point] : proof_s[t.point - N_KEY_POINTS];
+            into = into + rho * HF::from_canon_words(t.k);
+        }
+    }
+}
+
+int aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const size_t* offsets,
+                   const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
+    using H1 = Fq64Field;
+    if (!vk || !count || !proofs || !offsets || !coeffs || !ok_all || count > AGG_MAX_COUNT || (ninp && !inputs) || ninp > MAX_INPUTS) return ZK_ERR_ARG;
+    for (size_t k = 0; k < count; k++)
+        if (offsets[k + 1] < offsets[k]) return ZK_ERR_ARG;
+    Key key;
+    if (!load_key(vk, &key)) return ZK_ERR_ARG;
+    for (size_t i = 0; i < N_KEY_POINTS; i++)
+        if (!zk_host_in_subgroup_g1(key.pts[i])) return ZK_ERR_ARG;      // (the endomorphism multiplies the key's points too)
+    std::vector<std::vector<HF>> xs(count);
+    for (size_t k = 0; k < count; k++)
+        if (!load_input(inputs + k * ninp, ninp, &xs[k])) return ZK_ERR_ARG;
+    *ok_all = 0;
+    if (folded) memset(folded, 0, sizeof *folded);
+    // every proof's structure and points first: a rejection there ends the call before any multiplication, folded all-zero
+    std::vector<Parsed> prs(count);
+    std::vector<Affine<G1Field>> pts(count * N_PROOF_POINTS);
+    for (size_t k = 0; k < count; k++) {
+        prs[k] = parse_proof(proofs + offsets[k], offsets[k + 1] - offsets[k]);
+        if (!prs[k].ok) return ZK_OK;
+        for (size_t i = 0; i < N_PROOF_POINTS; i++) {
+            Affine<G1Field>& p = pts[k * N_PROOF_POINTS + i];
+            if (!zk_host_decompress_g1(prs[k].pt[i], &p) || !zk_host_in_subgroup_g1(p)) return ZK_OK;
+        }
+    }
+    HF key_s[N_KEY_POINTS];
+    for (HF& s : key_s) s = HF::zero();
+    XYZZ<H1> L = xyzz_inf<H1>(), W = xyzz_inf<H1>();
+    auto mul = [](const Affine<G1Field>& p, const HF& s) {
+        uint32_t k[8];
+        s.canon_words(k);
+        return host64_scalar_mul_glv(xyzz_from_affine<H1>(aff_to_host64<G1Field>(p)), k);
+    };
+    for (size_t k = 0; k < count; k++) {
+        const Affine<G1Field>* pk = &pts[k * N_PROOF_POINTS];
+        HF proof_s[N_PROOF_POINTS];
+        fold_proof(build_equations(key, xs[k], prs[k], pk), coeffs + 4 * k, proof_s, key_s);
+        for (size_t i = 0; i < N_PROOF_POINTS; i++) L = xyzz_add<H1>(L, mul(pk[i], proof_s[i]));
+        for (int q = 0; q < 2; q++) {
+            const uint64_t* c = coeffs + 4 * k + 2 * q;
+            const uint32_t kw[8] = {(uint32_t)c[0], (uint32_t)(c[0] >> 32), (uint32_t)c[1], (uint32_t)(c[1] >> 32), 0, 0, 0, 0};
+            W = xyzz_add<H1>(W, host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(pk[PP_WIT_BETA + q])), kw));
+        }
+    }
+    for (size_t i = 0; i < N_KEY_POINTS; i++) L = xyzz_add<H1>(L, mul(key.pts[i], key_s[i]));
+    const Affine<H1> p2[2] = {xyzz_to_affine<H1>(L), xyzz_to_affine<H1>(W)};
+    const Affine<H2> q2[2] = {aff_to_host64<G2Field>(key.h), aff_to_host64<G2Field>(key.neg_beta_h)};
+    Fq12<H2> e;
+    pairing_product<H2>(e, p2, q2, 2);
+    *ok_all = fq12_eq<H2>(e, fq12_one<H2>()) ? 1 : 0;
+    if (folded) zk_host_gt_out(folded, e);
+    return ZK_OK;
+}
+
 }  // namespace
+
+extern "C" int zk_marlin_verify_aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t inputs_per_proof, const uint8_t* proofs,
+                                               const size_t* offsets, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
+    ZK_API_BEGIN_NOCTX
+    return aggregate_host(vk, count, inputs, inputs_per_proof, proofs, offsets, coeffs, ok_all, folded);
+    ZK_API_END
+}
 
 extern "C" int zk_marlin_verify_host(const zk_marlin_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t* proof, size_t proof_len, int* ok) {
     ZK_API_BEGIN_NOCTX

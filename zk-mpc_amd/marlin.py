@@ -582,3 +582,56 @@ def verify_batch(ctx: Context, vk: VerifierKey, inputs, proofs) -> np.ndarray:
     ctx._ck(ctx.lib.zk_marlin_verify_batch(ctx.h, C.byref(vk.struct), count, inp.ctypes.data_as(C.c_void_p), inp.shape[1],
                                            buf.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), ok.ctypes.data_as(C.c_void_p)))
     return ok
+
+
+# ---- aggregated verification on the host: one folded KZG check per batch (csrc/marlin_verify.hip) -----------------------------------
+
+def _batch_args(inputs, proofs):
+    import ctypes as C
+    count = len(proofs)
+    inp = _verify_args(inputs, count)
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(p) for p in proofs])
+    buf = np.frombuffer(b"".join(bytes(p) for p in proofs) or b"\0", dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    return count, inp, p(inp), p(buf), p(offsets), (inp, buf, offsets)
+
+
+def _equation_coeffs(coeffs, count):
+    """(2 count, 2) uint64 (low, high), equation 2 k + q of proof k at q = beta, gamma: from such an array or 2 count integers."""
+    from .api import _coeff_array
+    try:
+        return _coeff_array(coeffs, 2 * count)
+    except ValueError:
+        raise ValueError("one 128-bit coefficient per EQUATION: two per proof")
+
+
+def verify_aggregate_host(vk: VerifierKey, inputs, proofs, coeffs):
+    """zk_marlin_verify_aggregate_host: the folded check through the host arithmetic (no device) -> (ok_all, folded)."""
+    import ctypes as C
+    count, inp, p_inp, p_buf, p_off, _keep = _batch_args(inputs, proofs)
+    co = _equation_coeffs(coeffs, count)
+    ok, folded = C.c_int(0), np.zeros(72, dtype=np.uint64)
+    rc = _lib.load().zk_marlin_verify_aggregate_host(C.byref(vk.struct), count, p_inp, inp.shape[1], p_buf, p_off, co.ctypes.data_as(C.c_void_p),
+                                                     C.byref(ok), folded.ctypes.data_as(C.c_void_p))
+    if rc != _lib.ZK_OK:
+        raise _lib.ZkError("zk_marlin_verify_aggregate_host failed (%d)" % rc)
+    return bool(ok.value), folded
+
+
+def diag_g1_glv_sum(points, halves, scaled: bool = True):
+    """Test hook (zk_diag_g1_glv_sum_host): sum_i (k1_i + k2_i lambda) points[i] by the per-term source of csrc/g1_lincomb.cuh over the
+    host field.  points (n, 12) uint64 affine, halves (n, 8) uint32 = k1 | k2 -> (the n products as (n, 12) affine or None, the sum
+    as a (18,) projective)."""
+    import ctypes as C
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    hv = np.ascontiguousarray(halves, dtype=np.uint32).reshape(-1, 8)
+    if hv.shape[0] != pts.shape[0]:
+        raise ValueError("one pair of halves per point")
+    out = np.zeros((pts.shape[0], 12), dtype=np.uint64) if scaled else None
+    total = np.zeros(18, dtype=np.uint64)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    rc = _lib.load().zk_diag_g1_glv_sum_host(p(pts), p(hv), pts.shape[0], p(out), p(total))
+    if rc != _lib.ZK_OK:
+        raise _lib.ZkError("zk_diag_g1_glv_sum_host failed (%d)" % rc)
+    return out, total
