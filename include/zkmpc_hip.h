@@ -614,7 +614,7 @@ int zk_marlin_verify_host(const zk_marlin_vk_host* vk, const zk_fr* inputs, size
 int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                            const uint8_t* proofs_host, const size_t* offsets, int* ok);
 
-/* ---- aggregated Marlin verification: count proofs of one key as ONE folded KZG check, on the host (csrc/marlin_verify.hip) ----------- */
+/* ---- aggregated Marlin verification: count proofs of one key as ONE folded KZG check, host and device forms (csrc/marlin_verify.hip) - */
 /* KZG10::batch_check (poly-commit/src/kzg10/mod.rs:345) over every opening equation of every proof.  Proof k has two, at q = beta and
  * gamma: e(L_{k,q}, h) e(W_{k,q}, -beta_h) = 1.  With one 128-bit coefficient rho_{k,q} per EQUATION (coeffs: 2 uint64 per equation,
  * low word first, equation 2 k + q: 2 count of them) the batch is accepted iff
@@ -632,10 +632,29 @@ int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t coun
  * proof's structure or a point was rejected, which ends the call before any multiplication.
  * ZK_ERR_ARG: what zk_marlin_verify_batch refuses, a null coeffs / ok_all, count above 2^18, and a key point outside the prime-order
  * subgroup (the endomorphism multiplies the key's points too).
- * This is the host arithmetic: no device, no context, about 1.5 ms per proof.  A device form (the long sum as one term per lane) is
- * not built. */
+ * This is the host arithmetic: no device, no context, about 1.5 ms per proof.  The device form follows. */
 int zk_marlin_verify_aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t inputs_per_proof, const uint8_t* proofs,
                                     const size_t* offsets, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+/* The same check with its two sums on the device, the contract above word for word (ok_all, folded, all-zero folded on a rejection before
+ * the pairing, a zero coefficient drops its equation, the ZK_ERR_ARG cases, count <= 2^18); a null ctx is also ZK_ERR_ARG.  The 13 count
+ * points are decompressed and tested for subgroup membership on the device (the key's 16 on the host), the host derives every proof's
+ * transcript and scalars on the context's helper threads, ONE launch with one term per lane takes the long sum over the 13 count + 16
+ * points (csrc/g1_term_fold.hip), one launch of k_g1_scale_fold the 2 count witnesses with their 128-bit coefficients, and the two sums
+ * go through the host's pairing -- the call zk_marlin_verify_aggregate_host ends in, so `folded` is the same words.  The launches do
+ * not grow with count beyond the logarithmic re-launches of the sum.  With zk_set_profiling: timers "marlin_verify_agg.<phase>". */
+int zk_marlin_verify_aggregate_coeffs(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                      const uint8_t* proofs_host, const size_t* offsets, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+/* The seeded form: the coefficients are zk_verify_aggregate_coeffs_from_seed(seed, 2 count) -- draw the seed after the proofs arrived.
+ * ok_each (or NULL): all ones when ok_all = 1; otherwise the verdicts of zk_marlin_verify_batch, which is run to locate the bad proofs
+ * (its r P tests make the same subgroup demand).  Also ZK_ERR_ARG for a null seed. */
+int zk_marlin_verify_aggregate(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                               const uint8_t* proofs_host, const size_t* offsets, const uint8_t seed[32], int* ok_all, int* ok_each);
+/* Test hook: the kernel of the long sum alone (csrc/g1_term_fold.hip: k_g1_term_fold, then the sum-down) over n <= 2^22 points
+ * (coordinate words below q) with words[8 i ..] per point.  mode 0 (FULL): a raw 256-bit scalar, low word first, never reduced, any
+ * curve point.  mode 1 (GLV): k1 | k2, four uint32 each, as zk_diag_g1_glv_sum_host takes them, for points of the prime-order subgroup.
+ * scaled_out (or NULL) = the n products as affine points, sum_out = their sum.  ZK_ERR_ARG for a mode that is not built. */
+int zk_diag_g1_term_sum_dev(zk_ctx* ctx, const zk_g1_affine* pts, const uint32_t* words, size_t n, int mode, zk_g1_affine* scaled_out,
+                            zk_g1_projective* sum_out);
 /* Test hook: the per-term multiplication through the endomorphism that the sum above is written for a kernel with (csrc/g1_lincomb.cuh:
  * lincomb_term_glv, instantiated over the host field).  n <= 2^22 points (coordinate words below q) with halves[8 i ..] = k1 | k2, four
  * uint32 each: scaled_out (or NULL) = (k1 + k2 lambda) pts[i] as affine points, sum_out = their sum.  The halves are raw 128-bit values;

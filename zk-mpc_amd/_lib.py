@@ -356,6 +356,9 @@ PROTOTYPES = {
     "zk_diag_msm_plans": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "zk_marlin_verify_aggregate_host": (_I, [_P, _SZ, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
     "zk_diag_g1_glv_sum_host": (_I, [_P, _P, _SZ, _P, _P]),
+    "zk_marlin_verify_aggregate_coeffs": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
+    "zk_marlin_verify_aggregate": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
+    "zk_diag_g1_term_sum_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P]),
 }
 
 _lib = None

@@ -144,7 +144,7 @@ struct zk_ctx {
     std::map<std::string, Slot> slots;
     std::map<ZkPin, Slot> pinned;   // pinned host staging: grown by zk_pinned alone, freed by zk_ctx_destroy alone
     std::map<uint32_t, zk_domain*> domains;  // keyed by log2(size)
-    bool lds_attr_done[8] = {};               // one-time per-context kernel attributes, by ZkLdsAttr (internal.hpp)
+    bool lds_attr_done[12] = {};              // one-time per-context kernel attributes, by ZkLdsAttr (internal.hpp)
     // core.hip: zk_graph_run -- a launch-bound sequence (the ~13 launches of a bucket sort) replayed as one captured graph.  Key = a
     // digest of everything the launches depend on, `scratch_gen` included (it moves whenever a scratch slot is allocated anew: every
     // graph that baked the old addresses in stops matching).

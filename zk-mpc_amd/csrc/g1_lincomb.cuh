@@ -11,7 +11,7 @@
 // accumulator still is (the leading zero windows) or whose operands meet at equal x leaves the addition early or takes its
 // doubling arm, and sits masked while its neighbours run the general formulas.  The wave pays one full addition per window
 // either way (plus the doubling arm in the windows where some lane needs it), which is the cost the fixed schedule was chosen for.
-// lincomb_term_glv (below) is the same schedule at half the windows for points KNOWN to be in the subgroup (host instantiation only).
+// lincomb_term_glv (below) is the same schedule at half the windows for points KNOWN to be in the subgroup (g1_term_fold.hip's GLV mode).
 #pragma once
 #include "ec.cuh"
 #include "hostfield64.hpp"
@@ -41,7 +41,9 @@ ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[NW], Tab& tab) {
         e = xyzz_add<F>(e, P);
         tab.put(i, e);
     }
-    XYZZ<F> acc = carry ? P : xyzz_inf<F>();
+    // the carry digit: P or infinity, by a field select (a ?: between two points cost the kernels a 108-byte stack object per lane)
+    XYZZ<F> acc = P;
+    acc.zz = F::select(carry != 0, acc.zz, F::zero());
 #pragma unroll 1
     for (int w = 8 * NW - 1; w >= 0; w--) {
 #pragma unroll 1
@@ -69,7 +71,7 @@ ZK_HD XYZZ<F> lincomb_term(const Affine<F>& p, const uint32_t k[NW], Tab& tab) {
 // of four doublings and one addition for the plain term: about 200 group operations instead of 327.  On a point outside the subgroup
 // phi is not lambda and the result means nothing, but the arithmetic is the same complete formulas and ends.
 // Written in the form a one-term-per-lane kernel takes (digits select operands, never the control flow; GlvBeta<F> gives beta in
-// F's form); today it is instantiated over the host field only (zk_diag_g1_glv_sum_host) -- no kernel runs it yet.
+// F's form): instantiated over the host field (zk_diag_g1_glv_sum_host) and over G1Field by g1_term_fold.hip's k_g1_term_fold.
 template <class F> struct GlvBeta;
 template <> struct GlvBeta<Fq64Field> {
     static Fq64 get() { return Fq64Field::from_dev(fp_const<FqParams>(FqParams::BETA)); }

@@ -105,8 +105,11 @@ __global__ void __launch_bounds__(64) k_g1_scale_fold(const uint32_t* __restrict
     if (lane == 0) xyzz_store16<G1Field>(out_part, blockIdx.x, acc);
 }
 
-// ---- launches -----------------------------------------------------------------------------------------------------------------------
-int scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in_xyzz, const uint32_t* coeffs, size_t n, uint32_t* out_aff, uint32_t* out_part) {
+}  // namespace
+
+// ---- launches (internal.hpp: the Marlin aggregate runs them too) --------------------------------------------------------------------
+int zk_g1_scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in_xyzz, const uint32_t* coeffs, size_t n, uint32_t* out_aff,
+                            uint32_t* out_part) {
     if (!ctx->lds_attr_done[ZK_LDS_SCALE_FOLD]) {
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_g1_scale_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCALE_LDS));
         ctx->lds_attr_done[ZK_LDS_SCALE_FOLD] = true;
@@ -117,15 +120,17 @@ int scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in
     return ZK_OK;
 }
 // the m XYZZ partials in a summed down to at most 64 (a and b: room for m and m / 64 + 1 points); *res says where they are
-int g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** res) {
+int zk_g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** res) {
     while (*m > 64) {
-        ZK_TRY(scale_fold_launch(ctx, a, 1, true, nullptr, *m, nullptr, b));
+        ZK_TRY(zk_g1_scale_fold_launch(ctx, a, 1, true, nullptr, *m, nullptr, b));
         *m = zk_blocks64(*m);
         std::swap(a, b);
     }
     *res = a;
     return ZK_OK;
 }
+
+namespace {
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
 HF coeff_fr(const uint64_t* c) { return HF::from_u128(c); }      // lo + 2^64 hi
@@ -361,12 +366,12 @@ int aggregate_dev(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* input
     std::vector<uint8_t> staging;
     ZK_TRY(stage_proofs(ctx, count, proofs_host, true, flags, nullptr, nullptr, &ac, &b, &staging, &tm, &lap));      // "k_decompress", "k_subgroup"
     tm.begin("verify_aggregate.k_scale");
-    ZK_TRY(scale_fold_launch(ctx, ac, 2, false, d_coef, count, P, nullptr));                    // r_i A_i -> P[0 .. count)
+    ZK_TRY(zk_g1_scale_fold_launch(ctx, ac, 2, false, d_coef, count, P, nullptr));                    // r_i A_i -> P[0 .. count)
     ZK_HIP(ctx, hipMemcpyAsync(Q, b, count * 192, hipMemcpyDeviceToDevice, st));
-    ZK_TRY(scale_fold_launch(ctx, ac + 24, 2, false, d_coef, count, nullptr, part_a));          // sum r_i C_i, a partial per wave
+    ZK_TRY(zk_g1_scale_fold_launch(ctx, ac + 24, 2, false, d_coef, count, nullptr, part_a));          // sum r_i C_i, a partial per wave
     size_t m_part = n_part;
     uint32_t* part;
-    ZK_TRY(g1_sum_down(ctx, part_a, part_b, &m_part, &part));
+    ZK_TRY(zk_g1_sum_down(ctx, part_a, part_b, &m_part, &part));
     tm.end();
 
     // under the device work: the coefficient sums over ranges of proofs, then the ninp + 2 multiplications of key points side by side
@@ -510,10 +515,10 @@ extern "C" int zk_diag_g1_scale_sum_dev(zk_ctx* ctx, const zk_g1_affine* pts, co
     hipStream_t st = ctx->stream;
     ZK_HIP(ctx, hipMemcpyAsync(d_pts, w.data(), n * 96, hipMemcpyHostToDevice, st));
     if (coeffs) ZK_HIP(ctx, hipMemcpyAsync(d_coef, coeffs, n * 16, hipMemcpyHostToDevice, st));
-    ZK_TRY(scale_fold_launch(ctx, d_pts, 1, false, d_coef, n, d_aff, part_a));
+    ZK_TRY(zk_g1_scale_fold_launch(ctx, d_pts, 1, false, d_coef, n, d_aff, part_a));
     size_t m = n_part;
     uint32_t* part;
-    ZK_TRY(g1_sum_down(ctx, part_a, part_b, &m, &part));
+    ZK_TRY(zk_g1_sum_down(ctx, part_a, part_b, &m, &part));
     std::vector<uint32_t> h_part(m * XW);
     ZK_HIP(ctx, hipMemcpyAsync(h_part.data(), part, h_part.size() * 4, hipMemcpyDeviceToHost, st));
     if (scaled_out) ZK_HIP(ctx, hipMemcpyAsync(w.data(), d_aff, n * 96, hipMemcpyDeviceToHost, st));

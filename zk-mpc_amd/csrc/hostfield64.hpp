@@ -328,10 +328,22 @@ inline void host64_glv_split(const uint32_t k[8], uint32_t k1[8], uint32_t k2[8]
     typedef unsigned __int128 u128;
     const u128 lambda = ((u128)host64::GLV_LAMBDA[1] << 64) | host64::GLV_LAMBDA[0];
     u128 rem = 0;
+    int start = 255;
     for (int i = 0; i < 8; i++) k2[i] = 0;
-    for (int i = 255; i >= 0; i--) {
+    // The bits from 127 up are the remainder after their steps whenever they are below lambda -- then every prefix of them is, and no
+    // step subtracted: always so for k < r (they are below 2^126 < lambda).  Half the steps; the aggregated Marlin check splits 13
+    // scalars per proof.  The steps themselves take no branch on the scalar.
+    if (!(k[7] >> 31)) {
+        u128 t = 0;
+        for (int i = 7; i >= 4; i--) t = (t << 32) | k[i];
+        t = (t << 1) | (k[3] >> 31);
+        if (t < lambda) { rem = t; start = 126; }
+    }
+    for (int i = start; i >= 0; i--) {
         rem = (rem << 1) | ((k[i >> 5] >> (i & 31)) & 1u);
-        if (rem >= lambda) { rem -= lambda; k2[i >> 5] |= 1u << (i & 31); }
+        const u128 ge = (u128)0 - (u128)(rem >= lambda);
+        rem -= lambda & ge;
+        k2[i >> 5] |= ((uint32_t)ge & 1u) << (i & 31);
     }
     k1[0] = (uint32_t)rem; k1[1] = (uint32_t)(rem >> 32); k1[2] = (uint32_t)(rem >> 64); k1[3] = (uint32_t)(rem >> 96);
     k1[4] = k1[5] = k1[6] = k1[7] = 0;

@@ -35,7 +35,11 @@ enum ZkFrForm { ZK_FR_EXT = 0, ZK_FR_TABLE = 1 };
 int zk_fr_powers_launch(zk_ctx* ctx, const zk::Fr& base, const zk::Fr& start, size_t n, void* out, ZkFrForm form);
 
 // The kernel groups whose hipFuncSetAttribute list runs once per context (zk_ctx::lds_attr_done, set by the site once its list succeeded)
-enum ZkLdsAttr { ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_SCALE_FOLD, ZK_LDS_COUNT };
+enum ZkLdsAttr {
+    ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_SCALE_FOLD,
+    ZK_LDS_TERM_FOLD_FULL, ZK_LDS_TERM_FOLD_GLV,      // g1_term_fold.hip: one slot per instantiation (an attribute belongs to ONE function)
+    ZK_LDS_COUNT
+};
 static_assert(ZK_LDS_COUNT <= sizeof(zk_ctx::lds_attr_done), "zk_ctx::lds_attr_done is too short");
 
 // rng.hip: four little-endian 64-bit words are a canonical field element (< r): what Fr::rand keeps and what a prover accepts from a peer
@@ -337,6 +341,23 @@ namespace zk { template <class F2> struct Fq12; struct Fq264Field; }
 int zk_fold_scratch(zk_ctx* ctx, size_t n, uint32_t** a_dev, uint32_t** b_dev);
 int zk_miller_product(zk_ctx* ctx, const uint32_t* ml_dev, size_t n, zk::Fq12<zk::Fq264Field>* out, ZkPhaseTimer* tm = nullptr,
                       ZkHostLap* lap = nullptr);
+// groth16_verify.hip: k_g1_scale_fold.  Lane g < n: point g in_step of `in` (affine table form, or XYZZ with in_xyzz) times the 128-bit
+// coeffs[4 g ..] (NULL: times one); out_aff (or NULL): the n products as affine points; out_part (or NULL): one XYZZ sum per block of
+// 64 lanes.  zk_g1_sum_down: the m XYZZ partials in a summed down to at most 64 (a and b: room for m and m / 64 + 1 points); *res says
+// where they are.  Both on ctx->stream, no wait.
+int zk_g1_scale_fold_launch(zk_ctx* ctx, const uint32_t* in, uint32_t in_step, bool in_xyzz, const uint32_t* coeffs, size_t n, uint32_t* out_aff,
+                            uint32_t* out_part);
+int zk_g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** res);
+// g1_term_fold.hip: k_g1_term_fold, the sum of many G1 terms with FULL-WIDTH scalars, one term per lane.  Lane g < n: point g in_step of
+// `in` (affine table form) times words[8 g ..] -- ZK_TERM_FULL: a raw 256-bit scalar, low word first, never reduced (any point);
+// ZK_TERM_GLV: k1 | k2, four words each, for (k1 + k2 lambda) P through the endomorphism (points of the prime-order subgroup only).
+// out_aff / out_part as above.  n <= 2^22.  On ctx->stream, no wait.  A mode that is not built: ZK_ERR_ARG.
+enum ZkTermMode : int { ZK_TERM_FULL = 0, ZK_TERM_GLV = 1 };
+// what zk_marlin_verify_aggregate runs: every point is in the subgroup by then, and the kernel alone is 1.44 - 1.48 times as fast as
+// ZK_TERM_FULL at 13 328 and 213 008 lanes (DESIGN 6 "Aggregated Marlin verification")
+constexpr int ZK_TERM_DEFAULT = ZK_TERM_GLV;
+int zk_g1_term_fold_launch(zk_ctx* ctx, int mode, const uint32_t* in, uint32_t in_step, const uint32_t* words, size_t n, uint32_t* out_aff,
+                           uint32_t* out_part);
 // g1_lincomb.hip: n_segments short linear combinations of G1 points in one launch, one term per lane.  Lane g holds point
 // point_index[g] of points_dev (table form; n_points of them) and the raw 256-bit scalar scalars_dev[8 g ..]; segment s is the lanes
 // seg_offsets[s] .. seg_offsets[s + 1] - 1, which must lie in one wave of 64 (ZkLincombPack lays the lanes out so); seg_offsets[0] = 0,

@@ -1,4 +1,5 @@
-// marlin_verify.hip -- Marlin::verify: one proof on the host (zk_marlin_verify_host), a batch on the device (zk_marlin_verify_batch).
+// marlin_verify.hip -- Marlin::verify: one proof on the host (zk_marlin_verify_host), a batch on the device (zk_marlin_verify_batch), a
+// batch as ONE folded KZG check on the host and on the device (zk_marlin_verify_aggregate*).
 //
 // Replaces (reference):
 //   Marlin::verify                                   arkworks/marlin/src/lib.rs:324-442
@@ -12,8 +13,10 @@
 //   L_q = sum_j xi^j (combination j of the commitments)  -  val_q g  -  random_v_q gamma_g  +  z_q W_q        (z = beta, gamma)
 // and the proof holds iff e(L_q, h) e(W_q, -beta_h) = 1 for both -- KZG10::check with the witness term moved to the left, so that G2
 // only ever sees the key's two points.  The two query points are NOT folded by a random coefficient (kzg10::batch_check takes an rng)
-// -- except by zk_marlin_verify_aggregate_host, which is that batch_check over every equation of a batch with the caller's
-// coefficients, on the host (the device form of it is not built).
+// -- except by the aggregate forms, which are that batch_check over every equation of a batch with the caller's coefficients:
+// zk_marlin_verify_aggregate_host on the host, zk_marlin_verify_aggregate_coeffs / zk_marlin_verify_aggregate with the two sums on
+// the device (g1_term_fold.hip for the long one, k_g1_scale_fold for the witnesses; sizes from marlin_agg_plan.hpp) and the pairing
+// of the two sums on the host.
 // The host back end evaluates the terms with host64_scalar_mul and pairing.cuh over Fq264Field; the device back end is
 // g1_lincomb.hip (one wave per proof) followed by pairing.hip's kernels as they are.
 #include "../../include/zkmpc_hip.h"
@@ -23,6 +26,7 @@
 #include "hostfield64.hpp"
 #include "hostgroup.hpp"
 #include "internal.hpp"
+#include "marlin_agg_plan.hpp"
 #include "marlin_lc.hpp"
 #include "pairing.cuh"
 #include <chrono>
@@ -334,7 +338,6 @@ __global__ void __launch_bounds__(64) k_marlin_pairs(size_t count, const uint32_
 // The first sum point by point: a proof's point occurs in ONE of its two term lists (fold_proof adds, so a builder that listed one
 // twice would still be right) and gets one full-width scalar rho c mod r; the key's sixteen occur in every proof's and get one scalar
 // each, summed over the batch: 13 count + 16 multiplications through the endomorphism (every point is in the subgroup by then).
-constexpr size_t AGG_MAX_COUNT = (size_t)1 << 18;      // 13 count + 16 terms below 2^22, the lane limit of the device's sum kernels
 void fold_proof(const Equations& eq, const uint64_t* coeffs4, HF proof_s[N_PROOF_POINTS], HF key_s[N_KEY_POINTS]) {
     for (size_t i = 0; i < N_PROOF_POINTS; i++) proof_s[i] = HF::zero();
     for (int q = 0; q < 2; q++) {
@@ -346,32 +349,57 @@ void fold_proof(const Equations& eq, const uint64_t* coeffs4, HF proof_s[N_PROOF
     }
 }
 
-int aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const size_t* offsets,
-                   const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
-    using H1 = Fq64Field;
+// what both forms refuse (ZK_ERR_ARG), and the key and the formatted inputs they then work on
+int agg_load(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const size_t* offsets,
+             const uint64_t* coeffs, const int* ok_all, Key* key, std::vector<std::vector<HF>>* xs) {
     if (!vk || !count || !proofs || !offsets || !coeffs || !ok_all || count > AGG_MAX_COUNT || (ninp && !inputs) || ninp > MAX_INPUTS) return ZK_ERR_ARG;
     for (size_t k = 0; k < count; k++)
         if (offsets[k + 1] < offsets[k]) return ZK_ERR_ARG;
-    Key key;
-    if (!load_key(vk, &key)) return ZK_ERR_ARG;
+    if (!load_key(vk, key)) return ZK_ERR_ARG;
     for (size_t i = 0; i < N_KEY_POINTS; i++)
-        if (!zk_host_in_subgroup_g1(key.pts[i])) return ZK_ERR_ARG;      // (the endomorphism multiplies the key's points too)
-    std::vector<std::vector<HF>> xs(count);
+        if (!zk_host_in_subgroup_g1(key->pts[i])) return ZK_ERR_ARG;      // (the endomorphism multiplies the key's points too)
+    xs->resize(count);
     for (size_t k = 0; k < count; k++)
-        if (!load_input(inputs + k * ninp, ninp, &xs[k])) return ZK_ERR_ARG;
+        if (!load_input(inputs + k * ninp, ninp, &(*xs)[k])) return ZK_ERR_ARG;
+    return ZK_OK;
+}
+// every proof's structure; false: one does not parse
+bool agg_parse(size_t count, const uint8_t* proofs, const size_t* offsets, std::vector<Parsed>* prs) {
+    prs->resize(count);
+    for (size_t k = 0; k < count; k++) {
+        (*prs)[k] = parse_proof(proofs + offsets[k], offsets[k + 1] - offsets[k]);
+        if (!(*prs)[k].ok) return false;
+    }
+    return true;
+}
+// the two sums through the pairing: the verdict and the folded value
+void agg_finish(const Key& key, const XYZZ<Fq64Field>& L, const XYZZ<Fq64Field>& W, int* ok_all, zk_gt* folded) {
+    using H1 = Fq64Field;
+    const Affine<H1> p2[2] = {xyzz_to_affine<H1>(L), xyzz_to_affine<H1>(W)};
+    const Affine<H2> q2[2] = {aff_to_host64<G2Field>(key.h), aff_to_host64<G2Field>(key.neg_beta_h)};
+    Fq12<H2> e;
+    pairing_product<H2>(e, p2, q2, 2);
+    *ok_all = fq12_eq<H2>(e, fq12_one<H2>()) ? 1 : 0;
+    if (folded) zk_host_gt_out(folded, e);
+}
+
+int aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const size_t* offsets,
+                   const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
+    using H1 = Fq64Field;
+    Key key;
+    std::vector<std::vector<HF>> xs;
+    ZK_TRY(agg_load(vk, count, inputs, ninp, proofs, offsets, coeffs, ok_all, &key, &xs));
     *ok_all = 0;
     if (folded) memset(folded, 0, sizeof *folded);
     // every proof's structure and points first: a rejection there ends the call before any multiplication, folded all-zero
-    std::vector<Parsed> prs(count);
+    std::vector<Parsed> prs;
+    if (!agg_parse(count, proofs, offsets, &prs)) return ZK_OK;
     std::vector<Affine<G1Field>> pts(count * N_PROOF_POINTS);
-    for (size_t k = 0; k < count; k++) {
-        prs[k] = parse_proof(proofs + offsets[k], offsets[k + 1] - offsets[k]);
-        if (!prs[k].ok) return ZK_OK;
+    for (size_t k = 0; k < count; k++)
         for (size_t i = 0; i < N_PROOF_POINTS; i++) {
             Affine<G1Field>& p = pts[k * N_PROOF_POINTS + i];
             if (!zk_host_decompress_g1(prs[k].pt[i], &p) || !zk_host_in_subgroup_g1(p)) return ZK_OK;
         }
-    }
     HF key_s[N_KEY_POINTS];
     for (HF& s : key_s) s = HF::zero();
     XYZZ<H1> L = xyzz_inf<H1>(), W = xyzz_inf<H1>();
@@ -392,12 +420,135 @@ int aggregate_host(const zk_marlin_vk_host* vk, size_t count, const zk_fr* input
         }
     }
     for (size_t i = 0; i < N_KEY_POINTS; i++) L = xyzz_add<H1>(L, mul(key.pts[i], key_s[i]));
-    const Affine<H1> p2[2] = {xyzz_to_affine<H1>(L), xyzz_to_affine<H1>(W)};
-    const Affine<H2> q2[2] = {aff_to_host64<G2Field>(key.h), aff_to_host64<G2Field>(key.neg_beta_h)};
-    Fq12<H2> e;
-    pairing_product<H2>(e, p2, q2, 2);
-    *ok_all = fq12_eq<H2>(e, fq12_one<H2>()) ? 1 : 0;
-    if (folded) zk_host_gt_out(folded, e);
+    agg_finish(key, L, W, ok_all, folded);
+    return ZK_OK;
+}
+
+// ---- folded, on the device ------------------------------------------------------------------------------------------------------------
+// The same check with the two sums on the device; every size from marlin_agg_plan.hpp (lane = point: a proof's eleven commitment points,
+// then every proof's two witnesses side by side, then the key's sixteen).  The host keeps what it is better at: the structure, the
+// transcripts and scalars (on the context's helper threads, split as zk_marlin_verify_batch splits them) and the pairing of the two
+// sums -- two Miller lanes and one final exponentiation are a fraction of a millisecond in 64-bit limbs and tens of milliseconds on
+// one lane of the device, and `folded` comes out of the very code the host form ends in.
+// mode: which instantiation of k_g1_term_fold takes the long sum (ZK_TERM_GLV splits every scalar with host64_glv_split first).
+void term_words(int mode, const HF& s, uint32_t out[8]) {
+    if (mode != ZK_TERM_GLV) { s.canon_words(out); return; }
+    uint32_t k[8], k1[8], k2[8];
+    s.canon_words(k);
+    host64_glv_split(k, k1, k2);                                      // k < r: both halves below 2^127
+    for (int i = 0; i < 4; i++) { out[i] = k1[i]; out[4 + i] = k2[i]; }
+}
+
+int aggregate_dev(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const size_t* offsets,
+                  const uint64_t* coeffs, int* ok_all, zk_gt* folded, int mode) {
+    using H1 = Fq64Field;
+    static_assert(AGG_PROOF_POINTS == N_PROOF_POINTS && AGG_KEY_POINTS == N_KEY_POINTS && AGG_COMM_POINTS == PP_WIT_BETA && PP_WIT_GAMMA == PP_WIT_BETA + 1,
+                  "marlin_agg_plan.hpp lays out other points than the equations name");
+    constexpr size_t NP = N_PROOF_POINTS;
+    if (!ctx) return ZK_ERR_ARG;
+    Key key;
+    std::vector<std::vector<HF>> xs;
+    ZK_TRY(agg_load(vk, count, inputs, ninp, proofs, offsets, coeffs, ok_all, &key, &xs));
+    *ok_all = 0;
+    if (folded) memset(folded, 0, sizeof *folded);
+    ZkHostLap lap{ctx, "marlin_verify_agg."};      // with zk_set_profiling: host wall-clock of a phase into "marlin_verify_agg.<phase>"
+    const ZkMarlinAggPlan pl = zk_marlin_agg_plan(count);
+
+    // 1. the bytes: structure on the host (a proof that does not parse ends the call), the 13 count compressed points to the device
+    std::vector<Parsed> prs;
+    if (!agg_parse(count, proofs, offsets, &prs)) return ZK_OK;
+    std::vector<uint8_t> comp(pl.comp_bytes);
+    for (size_t k = 0; k < count; k++)
+        for (size_t i = 0; i < NP; i++) memcpy(&comp[pl.lane_of(k, i) * 48], prs[k].pt[i], 48);
+    uint32_t key_w[N_KEY_POINTS * 24];
+    for (size_t j = 0; j < N_KEY_POINTS; j++) aff_store<G1Field>(key_w + 24 * j, key.pts[j]);
+    lap.lap("parse");
+    uint8_t* d_comp;
+    uint32_t *d_pts, *d_flag, *d_words, *d_coef, *tpart_a, *tpart_b, *wpart_a, *wpart_b;
+    ZK_TRY(zk_scratch(ctx, "magg_comp", pl.comp_bytes, (void**)&d_comp));
+    ZK_TRY(zk_scratch(ctx, "magg_pts", pl.pts_bytes, (void**)&d_pts));
+    ZK_TRY(zk_scratch(ctx, "magg_flag", pl.flags_bytes, (void**)&d_flag));
+    ZK_TRY(zk_scratch(ctx, "magg_words", pl.words_bytes, (void**)&d_words));
+    ZK_TRY(zk_scratch(ctx, "magg_coef", pl.coef_bytes, (void**)&d_coef));
+    ZK_TRY(zk_scratch(ctx, "term_part_a", pl.term.part_a * AGG_XYZZ_BYTES, (void**)&tpart_a));
+    ZK_TRY(zk_scratch(ctx, "term_part_b", pl.term.part_b * AGG_XYZZ_BYTES, (void**)&tpart_b));
+    ZK_TRY(zk_scratch(ctx, "magg_wpart_a", pl.wit.part_a * AGG_XYZZ_BYTES, (void**)&wpart_a));
+    ZK_TRY(zk_scratch(ctx, "magg_wpart_b", pl.wit.part_b * AGG_XYZZ_BYTES, (void**)&wpart_b));
+    hipStream_t st = ctx->stream;
+    ZkPhaseTimer tm(ctx);
+    ZK_HIP(ctx, hipMemcpyAsync(d_comp, comp.data(), pl.comp_bytes, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_pts + pl.key_first * 24, key_w, sizeof key_w, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(d_coef, coeffs, pl.coef_bytes, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemsetAsync(d_flag, 0, pl.flags_bytes, st));
+    tm.begin("marlin_verify_agg.k_decompress");
+    ZK_TRY(zk_decompress_launch(ctx, 1, (const uint32_t*)d_comp, pl.proof_lanes, d_pts, d_flag, nullptr));
+    tm.end();
+    // the subgroup tests ALWAYS (the key's sixteen were tested on the host): the fold's argument needs prime order, and so does ZK_TERM_GLV
+    tm.begin("marlin_verify_agg.k_subgroup");
+    ZK_TRY(zk_subgroup_launch(ctx, 1, d_pts, pl.proof_lanes, d_flag, nullptr));
+    tm.end();
+    // 2. the equations need the ordinates (the transcript absorbs x | y): back they come, with the verdict on the points
+    std::vector<uint32_t> pts_w(pl.proof_lanes * 24);
+    uint32_t bad = 0;
+    ZK_HIP(ctx, hipMemcpyAsync(pts_w.data(), d_pts, pts_w.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    lap.lap("decompress");
+    if (bad) { tm.resolve(); return ZK_OK; }      // a point off the curve or outside the subgroup: ok_all = 0, folded all-zero
+    // 3. sum rho W over the 2 count witnesses (adjacent in the buffer: coefficient 2 k + q meets its point), under the builders
+    tm.begin("marlin_verify_agg.k_scale_fold");
+    ZK_TRY(zk_g1_scale_fold_launch(ctx, d_pts + pl.wit_first * 24, 1, false, d_coef, pl.wit.lanes, nullptr, wpart_a));
+    size_t m_wit = pl.wit.blocks;
+    uint32_t* wpart;
+    ZK_TRY(zk_g1_sum_down(ctx, wpart_a, wpart_b, &m_wit, &wpart));
+    tm.end();
+    // 4. the builders, in ranges over the helper threads as zk_marlin_verify_batch has them; a range sums the key's scalars for itself
+    std::vector<uint32_t> words(pl.term.lanes * 8);
+    const size_t parts = count >= 64 ? 8 : 1;
+    std::vector<HF> key_part(parts * N_KEY_POINTS, HF::zero());
+    auto build_range = [&](size_t part) {
+        HF* key_s = &key_part[part * N_KEY_POINTS];
+        for (size_t k = count * part / parts; k < count * (part + 1) / parts; k++) {
+            Affine<G1Field> pts[NP];
+            for (size_t i = 0; i < NP; i++) pts[i] = aff_load<G1Field>(&pts_w[pl.lane_of(k, i) * 24]);
+            HF proof_s[NP];
+            fold_proof(build_equations(key, xs[k], prs[k], pts), coeffs + 4 * k, proof_s, key_s);
+            for (size_t i = 0; i < NP; i++) term_words(mode, proof_s[i], &words[8 * pl.lane_of(k, i)]);
+        }
+    };
+    {
+        std::vector<ZkTask<void>> tasks;
+        for (size_t p = 1; p < parts; p++) tasks.push_back(zk_async(ctx, [&build_range, p] { build_range(p); }));
+        build_range(0);
+        for (auto& t : tasks) t.get();
+    }
+    for (size_t j = 0; j < N_KEY_POINTS; j++) {
+        HF s = HF::zero();
+        for (size_t p = 0; p < parts; p++) s = s + key_part[p * N_KEY_POINTS + j];
+        term_words(mode, s, &words[8 * pl.key_lane(j)]);
+    }
+    lap.lap("build");
+    // 5. the long sum: one term per lane over the 13 count + 16 points
+    ZK_HIP(ctx, hipMemcpyAsync(d_words, words.data(), pl.words_bytes, hipMemcpyHostToDevice, st));
+    tm.begin("marlin_verify_agg.k_term_fold");
+    ZK_TRY(zk_g1_term_fold_launch(ctx, mode, d_pts, 1, d_words, pl.term.lanes, nullptr, tpart_a));
+    size_t m_term = pl.term.blocks;
+    uint32_t* tpart;
+    ZK_TRY(zk_g1_sum_down(ctx, tpart_a, tpart_b, &m_term, &tpart));
+    tm.end();
+    if (m_term != pl.term.left || m_wit != pl.wit.left) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_verify_aggregate: a sum-down left another count than its plan");
+    std::vector<uint32_t> h_t(m_term * XW), h_w(m_wit * XW);
+    ZK_HIP(ctx, hipMemcpyAsync(h_t.data(), tpart, h_t.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipMemcpyAsync(h_w.data(), wpart, h_w.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    lap.lap("device");
+    // 6. the last (at most 64) partials of each sum and the pairing, in 64-bit limbs
+    XYZZ<H1> L = xyzz_inf<H1>(), W = xyzz_inf<H1>();
+    for (size_t i = 0; i < m_term; i++) L = xyzz_add<H1>(L, xyzz_to_host64<G1Field>(xyzz_load<G1Field>(&h_t[i * XW])));
+    for (size_t i = 0; i < m_wit; i++) W = xyzz_add<H1>(W, xyzz_to_host64<G1Field>(xyzz_load<G1Field>(&h_w[i * XW])));
+    agg_finish(key, L, W, ok_all, folded);
+    lap.lap("host_pairing");
+    tm.resolve();
     return ZK_OK;
 }
 
@@ -572,5 +723,28 @@ extern "C" int zk_marlin_verify_batch(zk_ctx* ctx, const zk_marlin_vk_host* vk, 
     lap.lap("device");
     tm.resolve();
     return ZK_OK;
+    ZK_API_END
+}
+
+extern "C" int zk_marlin_verify_aggregate_coeffs(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                                 const uint8_t* proofs_host, const size_t* offsets, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
+    ZK_API_BEGIN(ctx)
+    return aggregate_dev(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, offsets, coeffs, ok_all, folded, ZK_TERM_DEFAULT);
+    ZK_API_END
+}
+
+extern "C" int zk_marlin_verify_aggregate(zk_ctx* ctx, const zk_marlin_vk_host* vk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                          const uint8_t* proofs_host, const size_t* offsets, const uint8_t seed[32], int* ok_all, int* ok_each) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !seed || !count || count > AGG_MAX_COUNT) return ZK_ERR_ARG;
+    std::vector<uint64_t> coeffs(4 * count);
+    ZK_TRY(zk_verify_aggregate_coeffs_from_seed(seed, 2 * count, coeffs.data()));
+    ZK_TRY(aggregate_dev(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, offsets, coeffs.data(), ok_all, nullptr, ZK_TERM_DEFAULT));
+    if (!ok_each) return ZK_OK;
+    if (*ok_all) {
+        for (size_t k = 0; k < count; k++) ok_each[k] = 1;
+        return ZK_OK;
+    }
+    return zk_marlin_verify_batch(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, offsets, ok_each);
     ZK_API_END
 }

@@ -635,3 +635,50 @@ def diag_g1_glv_sum(points, halves, scaled: bool = True):
     if rc != _lib.ZK_OK:
         raise _lib.ZkError("zk_diag_g1_glv_sum_host failed (%d)" % rc)
     return out, total
+
+
+# ---- aggregated verification on the device (csrc/marlin_verify.hip, csrc/g1_term_fold.hip) ---------------------------------------------
+
+TERM_FULL, TERM_GLV = 0, 1      # the modes of the long sum's kernel (csrc/internal.hpp: ZkTermMode)
+
+
+def verify_aggregate_coeffs(ctx: Context, vk: VerifierKey, inputs, proofs, coeffs, folded: bool = True):
+    """zk_marlin_verify_aggregate_coeffs: the folded check with its two sums on the device, arguments as verify_aggregate_host takes
+    them -> (ok_all, folded (72,) uint64 or None)."""
+    import ctypes as C
+    count, inp, p_inp, p_buf, p_off, _keep = _batch_args(inputs, proofs)
+    co = _equation_coeffs(coeffs, count)
+    ok, out = C.c_int(0), np.zeros(72, dtype=np.uint64) if folded else None
+    ctx._ck(ctx.lib.zk_marlin_verify_aggregate_coeffs(ctx.h, C.byref(vk.struct), count, p_inp, inp.shape[1], p_buf, p_off, co.ctypes.data_as(C.c_void_p),
+                                                      C.byref(ok), out.ctypes.data_as(C.c_void_p) if folded else None))
+    return bool(ok.value), out
+
+
+def verify_aggregate(ctx: Context, vk: VerifierKey, inputs, proofs, seed: bytes, each: bool = True):
+    """zk_marlin_verify_aggregate: the folded check under coefficients drawn from a 32-byte seed (draw it after the proofs arrived)
+    -> (ok_all, the count verdicts or None)."""
+    import ctypes as C
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    count, inp, p_inp, p_buf, p_off, _keep = _batch_args(inputs, proofs)
+    ok, ok_each = C.c_int(0), np.zeros(count, dtype=np.int32) if each else None
+    ctx._ck(ctx.lib.zk_marlin_verify_aggregate(ctx.h, C.byref(vk.struct), count, p_inp, inp.shape[1], p_buf, p_off, seed, C.byref(ok),
+                                               ok_each.ctypes.data_as(C.c_void_p) if each else None))
+    return bool(ok.value), ok_each
+
+
+def diag_g1_term_sum(ctx: Context, points, words, mode: int = TERM_FULL, scaled: bool = True):
+    """Test hook (zk_diag_g1_term_sum_dev): the kernel of the long sum alone.  points (n, 12) uint64 affine, words (n, 8) uint32 -- mode
+    TERM_FULL: a raw 256-bit scalar, low word first; TERM_GLV: k1 | k2 as diag_g1_glv_sum takes them -> (the n products as (n, 12)
+    affine or None, the sum as a (18,) projective)."""
+    import ctypes as C
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    wd = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 8)
+    if wd.shape[0] != pts.shape[0]:
+        raise ValueError("eight words per point")
+    out = np.zeros((pts.shape[0], 12), dtype=np.uint64) if scaled else None
+    total = np.zeros(18, dtype=np.uint64)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    ctx._ck(ctx.lib.zk_diag_g1_term_sum_dev(ctx.h, p(pts), p(wd), pts.shape[0], mode, p(out), p(total)))
+    return out, total
