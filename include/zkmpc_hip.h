@@ -733,6 +733,19 @@ typedef struct {
 size_t zk_marlin_proof_max_size(void);
 int zk_marlin_prove(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
                     const void* z_dev, zk_rng* zk_rng, int mask_on_device, uint8_t* proof_out, size_t cap, size_t* proof_len);
+/* count proofs of ONE index in one call (plain prover only): proof k is byte for byte what zk_marlin_prove writes for the padded
+ * assignment at z_dev + 32 * k * z_stride and the generator rngs[k], which is left in the state that call leaves it in.  The proofs
+ * of a chunk go through the rounds in lock-step -- one multi-vector MSM job per commitment, one host wait per step for the whole
+ * chunk -- so a small proof's latencies are shared among the proofs (DESIGN 5b'-m).  Proof k is written at proofs_out + k * slot
+ * (slot >= zk_marlin_proof_max_size()), its length to proof_lens[k].  count == 1 forwards to zk_marlin_prove.  The checks of
+ * zk_marlin_prove apply; also count >= 1 and z_stride >= the padded assignment's length (ZK_ERR_ARG).  A failing proof (an
+ * unsatisfied system, w not divisible by v_X, the inner sum-check) fails the call with ZK_ERR_STATE and zk_marlin_prove's text behind
+ * "proof <smallest failing index>: "; the output is unspecified then.  A batch whose single proof does not fit the free device
+ * memory fails with ZK_ERR_NOMEM.  The context stays usable after any failure.  ZK_MARLIN_BATCH_CHUNK in the environment (read at
+ * every call) caps the proofs per chunk. */
+int zk_marlin_prove_batch(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
+                          size_t count, const void* z_dev, size_t z_stride, zk_rng* const* rngs, int mask_on_device,
+                          uint8_t* proofs_out, size_t slot, size_t* proof_lens);
 
 /* Marlin::index (arkworks/marlin/src/lib.rs:101-146 over AHPForR1CS::index, ahp/indexer.rs:121-208 and ahp/constraint_systems.rs:23-264)
  * as one call, for matrices as to_matrices() gives them -- the zk_r1cs_host of zk_r1cs_upload, neither padded nor square:

@@ -276,6 +276,7 @@ PROTOTYPES = {
     "zk_marlin_round3_ab_evals_dev": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "zk_marlin_proof_max_size": (_SZ, []),
     "zk_marlin_prove": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "zk_marlin_prove_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _SZ, _P, _I, _P, _SZ, _P]),
     "zk_marlin_prove_shared": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "zk_marlin_prove_shared_spdz": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "zk_she_vec_op_dev": (_I, [_P, _I, _P, _P, _P, _SZ]),

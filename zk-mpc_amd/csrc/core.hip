@@ -350,3 +350,14 @@ extern "C" int zk_last_timers(zk_ctx* ctx, char* names, size_t name_stride, floa
     return k;
     ZK_API_END
 }
+
+// internal.hpp: ZkStage
+int ZkStage::put(const void* src, size_t bytes, const void** dev_out) {
+    const size_t at = (used + 255) & ~(size_t)255;
+    if (at + bytes > cap) ZK_FAIL(ctx, ZK_ERR_STATE, "ZkStage: a step uploads more than its owner reserved");
+    memcpy(host + at, src, bytes);
+    if (bytes) ZK_HIP(ctx, hipMemcpyAsync(dev + at, host + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *dev_out = dev + at;
+    used = at + bytes;
+    return ZK_OK;
+}

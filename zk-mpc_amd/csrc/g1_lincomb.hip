@@ -119,13 +119,14 @@ bool ZkLincombPack::add(const uint32_t* idx, const uint32_t* k8, size_t len) {
 }
 
 int zk_g1_lincomb_launch(zk_ctx* ctx, const uint32_t* points_dev, size_t n_points, const uint32_t* point_index_dev, const uint32_t* scalars_dev,
-                         const uint32_t* seg_offsets_dev, size_t n_segments, size_t n_lanes, uint32_t* out_affine_dev, uint32_t* out_is_inf_dev) {
+                         const uint32_t* seg_offsets_dev, size_t n_segments, size_t n_lanes, uint32_t* out_affine_dev, uint32_t* out_is_inf_dev,
+                         hipStream_t st) {
     if (!n_segments || !n_lanes || n_lanes > ((size_t)1 << 30) || n_segments > n_lanes || n_points > ((size_t)1 << 30)) return ZK_ERR_ARG;
     if (!ctx->lds_attr_done[ZK_LDS_LINCOMB]) {
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_g1_lincomb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LINCOMB_LDS));
         ctx->lds_attr_done[ZK_LDS_LINCOMB] = true;
     }
-    hipLaunchKernelGGL(k_g1_lincomb, zk_blocks64(n_lanes), 64, LINCOMB_LDS, ctx->stream, points_dev, (uint32_t)n_points, point_index_dev,
+    hipLaunchKernelGGL(k_g1_lincomb, zk_blocks64(n_lanes), 64, LINCOMB_LDS, st ? st : ctx->stream, points_dev, (uint32_t)n_points, point_index_dev,
                        scalars_dev, seg_offsets_dev, (uint32_t)n_segments, (uint32_t)n_lanes, out_affine_dev, out_is_inf_dev);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;

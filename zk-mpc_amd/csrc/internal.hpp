@@ -60,6 +60,61 @@ int zk_fr_outer_q1_launch(zk_ctx* ctx, const void* s, const void* a, const void*
 int zk_fr_lincomb_launch(zk_ctx* ctx, int terms, const void* const* ps, const size_t* ns, const zk::Fr* k_int, void* out, size_t n_out);
 int zk_vec_sub_scale_launch(zk_ctx* ctx, const void* a, const void* b, const zk::Fr& k_int, void* out, size_t n);
 
+// ---- the batched forms: count vectors of one length, proof k's at base + k * stride elements (marlin_prove_batch.hip) ----
+// What a step of a batch uploads -- per-proof constants, job arrays: page-locked host memory and a device buffer of the same size,
+// both the caller's.  put() copies `bytes` into the host half and enqueues their copy to the device half on ctx->stream; the
+// owner calls reset() only behind a host wait for that stream (the host half is rewritten then).
+struct ZkStage {
+    zk_ctx* ctx = nullptr;
+    char *host = nullptr, *dev = nullptr;
+    size_t cap = 0, used = 0;
+    void reset() { used = 0; }
+    int put(const void* src, size_t bytes, const void** dev_out);      // core.hip
+};
+// poly.hip: zk_poly_divide_by_vanishing_dev for count polynomials of n coefficients; sums: room for count * zk_poly_divv_sums_elems
+// elements (none wanted: 0).  On ctx->stream, no wait.
+size_t zk_poly_divv_sums_elems(size_t n, uint32_t log_domain);
+int zk_poly_divide_by_vanishing_strided(zk_ctx* ctx, const void* c, size_t c_stride, size_t n, uint32_t log_domain, size_t count, void* q, size_t q_stride,
+                                        void* rem, size_t rem_stride, void* sums);
+// poly.hip: p_k / (X - z_k) for count polynomials of n >= 2 coefficients, the quotients (n - 1 coefficients) at q + k * q_stride; a
+// polynomial of one span (n <= 4 096) is one launch whatever count is, a longer one three.  spans: room for 2 * count *
+// zk_poly_divlin_spans(n) elements.  The job array goes through `stage` (zk_poly_divlin_job_bytes each).  No wait.
+size_t zk_poly_divlin_spans(size_t n);
+size_t zk_poly_divlin_job_bytes();
+int zk_poly_divide_by_linear_strided(zk_ctx* ctx, const void* c, size_t c_stride, size_t n, const zk::Fr* z_int, size_t count, void* q, size_t q_stride,
+                                     void* spans, ZkStage* stage);
+// marlin_batch.hip: the element-wise kernels of the Marlin rounds over count vectors (strides in elements; n items each), on
+// ctx->stream, no wait.  tab: the step's per-proof constants on the device, proof k's row at tab + k * ts entries (devutil.cuh: FrK,
+// internal form unless a kernel says otherwise).
+namespace zk { struct FrK; }
+int zk_b_copy(zk_ctx* ctx, void* dst, size_t ds, const void* src, size_t ss, size_t n, size_t count);
+int zk_b_zero(zk_ctx* ctx, void* dst, size_t ds, size_t n, size_t count);
+int zk_b_op(zk_ctx* ctx, int op, const void* a, size_t sa, const void* b, size_t sb, void* out, size_t so, size_t n, size_t count);
+int zk_b_scale(zk_ctx* ctx, const void* a, size_t sa, const zk::FrK* tab, size_t ts, void* out, size_t so, size_t n, size_t count);      // a_k * tab_k[0]
+int zk_b_gather(zk_ctx* ctx, const void* src, size_t ss, const uint32_t* idx, size_t n, void* out, size_t so, size_t count);
+// out_k = p_k + r_k[0] (X^n - 1): n + 1 coefficients
+int zk_b_blind(zk_ctx* ctx, const void* p, size_t sp, size_t n, const void* r, size_t sr, void* out, size_t so, size_t count);
+// out_k[i] = tab_k[0] - e[i]; tab_k[0]: the bits of the constant's external form
+int zk_b_const_minus(zk_ctx* ctx, const zk::FrK* tab, size_t ts, const void* e, size_t n, void* out, size_t so, size_t count);
+// zk_fr_outer_q1_launch with tab_k = eta_a, eta_b, eta_c; every vector `stride` elements apart
+int zk_b_outer_q1(zk_ctx* ctx, const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp, size_t stride,
+                  const zk::FrK* tab, size_t ts, void* out, size_t n, size_t count);
+// zk_fr_lincomb_launch with tab_k[t] = the coefficient of term t (at most 16 terms); strides[t] = 0: one vector for every proof
+int zk_b_lincomb(zk_ctx* ctx, int terms, const void* const* ps, const size_t* strides, const size_t* ns, const zk::FrK* tab, size_t ts, void* out, size_t so,
+                 size_t n_out, size_t count);
+// round 3 (marlin.hip's zk_marlin_round3_f_evals_dev in its two halves around the inversion, and _ab_evals_dev): one row of
+// ZK_B_R3_ROW constants per proof, filled by zk_b_round3_row (alpha, beta, eta, vv = v_H(alpha) v_H(beta): internal form);
+// den: count * 3 k_size elements
+constexpr int ZK_B_R3_ROW = 11;
+void zk_b_round3_row(const zk::Fr& alpha, const zk::Fr& beta, const zk::Fr eta[3], const zk::Fr& vv, zk::FrK* row);
+int zk_b_round3_denoms(zk_ctx* ctx, const zk_marlin_matrix_evals on_k[3], size_t k_size, const zk::FrK* tab, void* den, size_t count);
+int zk_b_round3_f(zk_ctx* ctx, const zk_marlin_matrix_evals on_k[3], size_t k_size, const zk::FrK* tab, const void* inv, void* f, size_t f_stride, size_t count);
+int zk_b_round3_ab(zk_ctx* ctx, const zk_marlin_matrix_evals on_b[3], size_t b_size, const zk::FrK* tab, void* a_out, void* b_out, size_t stride, size_t count);
+// r1cs.hip: zk_r1cs_matvec_dev for count vectors (z_k at z + k * z_stride, the product at out + k * out_stride, out_len elements)
+struct zk_r1cs;
+int zk_r1cs_matvec_strided(zk_ctx* ctx, const zk_r1cs* r, int which, const void* z, size_t z_stride, size_t count, void* out, size_t out_stride,
+                           size_t out_len);
+
 // msm.hip
 struct zk_bases {
     int group = 1;             // 1 = G1, 2 = G2
@@ -214,6 +269,7 @@ enum ZkPinKind : uint8_t {
     ZK_PIN_STRIDED_UPLOAD,    // msm.hip: a strided host table gathered into the packed form
     ZK_PIN_INV_TOTALS,        // poly.hip: the block totals of a batch inversion
     ZK_PIN_ZERO_VERDICTS,     // vec_ops.hip: the verdicts of zk_fr_vec_is_zero_launch
+    ZK_PIN_MARLIN_BATCH,      // marlin_prove_batch.hip: idx 0 = what a step uploads (ZkStage), 1 = what it reads back
 };
 
 // The MSM scratch slots: the `slot` of zk_msm_prepare names the "msm_*.<slot>" scratch buffers, and two jobs on one slot share every
@@ -361,9 +417,10 @@ int zk_g1_term_fold_launch(zk_ctx* ctx, int mode, const uint32_t* in, uint32_t i
 // g1_lincomb.hip: n_segments short linear combinations of G1 points in one launch, one term per lane.  Lane g holds point
 // point_index[g] of points_dev (table form; n_points of them) and the raw 256-bit scalar scalars_dev[8 g ..]; segment s is the lanes
 // seg_offsets[s] .. seg_offsets[s + 1] - 1, which must lie in one wave of 64 (ZkLincombPack lays the lanes out so); seg_offsets[0] = 0,
-// seg_offsets[n_segments] = n_lanes.  Out: segment s as an affine point (table form) and its infinity flag.  On ctx->stream, no wait.
+// seg_offsets[n_segments] = n_lanes.  Out: segment s as an affine point (table form) and its infinity flag.  On st (NULL: ctx->stream), no wait.
 int zk_g1_lincomb_launch(zk_ctx* ctx, const uint32_t* points_dev, size_t n_points, const uint32_t* point_index_dev, const uint32_t* scalars_dev,
-                         const uint32_t* seg_offsets_dev, size_t n_segments, size_t n_lanes, uint32_t* out_affine_dev, uint32_t* out_is_inf_dev);
+                         const uint32_t* seg_offsets_dev, size_t n_segments, size_t n_lanes, uint32_t* out_affine_dev, uint32_t* out_is_inf_dev,
+                         hipStream_t st = nullptr);
 // The lane layout of such a launch, built on the host segment by segment: a segment that would straddle a wave starts the next one, and
 // the lanes left over join the segment before them with a zero scalar.  add() refuses more than 64 terms.
 struct ZkLincombPack {

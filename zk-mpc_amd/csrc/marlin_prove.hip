@@ -17,8 +17,7 @@
 #include "devutil.cuh"
 #include "hostgroup.hpp"
 #include "internal.hpp"
-#include "marlin_bytes.hpp"
-#include "marlin_lc.hpp"
+#include "marlin_prove_int.hpp"
 #include "sharednet.hpp"
 #include <algorithm>
 #include <chrono>
@@ -27,44 +26,9 @@
 #include <vector>
 
 using namespace zk;
+using namespace zk::marlin;      // marlin_prove_int.hpp: the oracle table and the host halves every Marlin prover shares
 
 namespace {
-
-struct Poly { char* p = nullptr; size_t n = 0; };        // n coefficients on the device
-
-// ---- the oracles: the nine the prover sends, in the order their rounds commit (and serialise) them, then the index's twelve ----
-enum Oracle : int {
-    O_W, O_Z_A, O_Z_B, O_MASK_POLY, O_T, O_G_1, O_H_1, O_G_2, O_H_2,
-    O_A_ROW, O_A_COL, O_A_VAL, O_A_ROW_COL, O_B_ROW, O_B_COL, O_B_VAL, O_B_ROW_COL, O_C_ROW, O_C_COL, O_C_VAL, O_C_ROW_COL,
-    N_ORACLES, N_PROVER = O_A_ROW, O_NONE = -1
-};
-enum IndexPart : int { ROW, COL, VAL, ROW_COL };                        // the index oracles of matrix m = 0 (A), 1 (B), 2 (C)
-constexpr Oracle index_of(int m, IndexPart part) { return Oracle(O_A_ROW + 4 * m + part); }
-static_assert(index_of(0, ROW_COL) == O_A_ROW_COL && index_of(1, VAL) == O_B_VAL && index_of(2, COL) == O_C_COL, "Oracle lists row, col, val, row_col per matrix");
-enum class Bound { None, H, K };            // degree bound: none, |H| - 2, |K| - 2
-enum class EarlyMsm { No, Plain, Always };  // may its MSM start before the round's batch: never / not over shares / in every mode
-// label: error texts | round that commits it, 1 - 3 (0: an index oracle) | hiding: committed with a blinding polynomial (bound 1) | shared:
-// witness-dependent (mpc.py: Party.SHARED_POLYS; t, g_2, h_2 and the index are public) | early: see Marlin::start_early
-struct OracleInfo { const char* label; int round; bool hiding; Bound bound; bool shared; EarlyMsm early; };
-constexpr OracleInfo index_oracle(const char* label) { return {label, 0, false, Bound::None, false, EarlyMsm::No}; }
-constexpr OracleInfo ORACLES[N_ORACLES] = {
-    {"w", 1, true, Bound::None, true, EarlyMsm::No},
-    {"z_a", 1, true, Bound::None, true, EarlyMsm::No},
-    {"z_b", 1, true, Bound::None, true, EarlyMsm::No},
-    {"mask_poly", 1, false, Bound::None, true, EarlyMsm::Plain},     // (over shares every lane's job stays in the batch)
-    {"t", 2, false, Bound::None, false, EarlyMsm::Always},
-    {"g_1", 2, true, Bound::H, true, EarlyMsm::No},
-    {"h_1", 2, false, Bound::None, true, EarlyMsm::No},
-    {"g_2", 3, false, Bound::K, false, EarlyMsm::Always},
-    {"h_2", 3, false, Bound::None, false, EarlyMsm::No},
-    index_oracle("a_row"), index_oracle("a_col"), index_oracle("a_val"), index_oracle("a_row_col"), index_oracle("b_row"), index_oracle("b_col"),
-    index_oracle("b_val"), index_oracle("b_row_col"), index_oracle("c_row"), index_oracle("c_col"), index_oracle("c_val"), index_oracle("c_row_col"),
-};
-std::vector<Oracle> round_oracles(int round) {
-    std::vector<Oracle> v;
-    for (int o = 0; o < N_PROVER; o++) if (ORACLES[o].round == round) v.push_back((Oracle)o);
-    return v;
-}
 
 // One lane -- 0: the share lane (or the plain prover), 1: the MAC lane of a SPDZ prover, own scratch names: its polynomials, the device calls on them
 struct Prover {
@@ -113,22 +77,6 @@ struct Prover {
     }
 };
 
-HF host_eval(const std::vector<HF>& c, const HF& x) {
-    HF acc = HF::zero();
-    for (size_t i = c.size(); i-- > 0;) acc = acc * x + c[i];
-    return acc;
-}
-std::vector<HF> host_div_linear(const std::vector<HF>& c, const HF& z) {   // quotient of p / (X - z)
-    std::vector<HF> q(c.size() > 1 ? c.size() - 1 : 0, HF::zero());
-    HF acc = HF::zero();
-    for (size_t i = c.size(); i-- > 1;) { acc = c[i] + acc * z; q[i - 1] = acc; }
-    return q;
-}
-void acc_scaled(std::vector<HF>& dst, const std::vector<HF>& src, const HF& k) {
-    if (dst.size() < src.size()) dst.resize(src.size(), HF::zero());
-    for (size_t i = 0; i < src.size(); i++) dst[i] = dst[i] + src[i] * k;
-}
-
 // sum_i c_i G_i for the three powers_of_gamma_g a hiding bound of 1 uses: on the host (a three-term MSM through the device
 // pipeline costs a full sort / accumulate / reduce round trip, ~0.5 ms; this is three scalar multiplications in 64-bit limbs), side
 // by side on the context's helper threads (0.2 ms each: three in a row were longer than the device batch of a small proof's round
@@ -171,9 +119,6 @@ struct MsmJobs {
     }
 };
 
-struct Term { HF c; Oracle o; };                // o = O_NONE: the constant term (LCTerm::One)
-using LinComb = std::vector<Term>;
-
 // What the caller of a prover entry point hands over (lanes [0] = share / plain, [1] = MAC share under SPDZ)
 struct MarlinArgs {
     const zk_marlin_index* ix;
@@ -209,7 +154,7 @@ struct Marlin : MarlinArgs {
     zk_g1_projective gamma_pts[3];                // powers_of_gamma_g: what a hiding bound of 1 uses
     // ---- what the steps hand on ----
     std::vector<HF> pub;                          // seed_transcript: the public input, its leading 1 included
-    struct Blinds { std::vector<HF> plain, shifted; } rands[N_ORACLES];   // commit_round: the blinding polynomials (index oracles: none)
+    Blinds rands[N_ORACLES];                      // commit_round: the blinding polynomials (index oracles: none)
     Comm comms[N_PROVER];                         // commit_round
     char *xb[2], *wq[2], *mask[2], *tmp[2];       // round 1 -> 2: x and w as coefficients, the mask polynomial, |H| elements of scratch
     HF alpha, eta[3], v_h_alpha;                  // round 1 / 2: challenges (eta: a, b, c), v_H(alpha)
@@ -229,7 +174,7 @@ struct Marlin : MarlinArgs {
         for (ZkEarlyMsm* em : early) if (em) (void)zk_msm_early_finish(ctx, em, nullptr);     // an error path: let them drain
         zk_rng_free(fs);
     }
-    bool bounded(Oracle o) const { return ORACLES[o].bound != Bound::None; }
+    bool bounded(Oracle o) const { return oracle_bounded(o); }
     size_t bound(Oracle o) const { return (ORACLES[o].bound == Bound::H ? n : K.size) - 2; }
     int lanes_rc() const { for (int l = 0; l < LANES; l++) if (PL[l].rc != ZK_OK) return PL[l].rc; return (int)ZK_OK; }
     HF sample_outside(const Dom& d) { HF t = P.next_fr(fs); while (d.vanishing(t).is_zero()) t = P.next_fr(fs); return t; }
@@ -377,11 +322,7 @@ struct Marlin : MarlinArgs {
         if (!shared || ni > 1) ZK_TRY(zk_memcpy_d2h(ctx, x.data(), from, ni * 32));
         pub.assign(ni, HF::one());
         for (size_t i = 1; i < ni; i++) pub[i] = HF::from_abi(x[i]);
-        std::vector<uint8_t> seed;
-        const char* name = "MARLIN-2019";
-        seed.insert(seed.end(), name, name + 11);
-        seed.insert(seed.end(), ix->ivk_bytes, ix->ivk_bytes + ix->ivk_len);
-        for (size_t i = 1; i < ni; i++) pub[i].bytes(seed);
+        const std::vector<uint8_t> seed = transcript_seed(ix, pub);
         ZK_TRY(zk_fsrng_new(seed.data(), seed.size(), &fs));
         laps.lap("setup");
         return ZK_OK;
@@ -561,7 +502,9 @@ struct Marlin : MarlinArgs {
     // The evaluations of the query set, absorbed, and the linear combinations over them.  In: oracles, challenges, pub.  Out: evaluations, queries, xi
     int evaluate() {
         // one batch (two launches, one copy back); z_b and g_1 are shared: every lane's evaluation, opened (`evaluations.publicize()`, lib.rs:296)
-        HF z_b_beta, g_1_beta, t_beta, g_2_gamma, row[3], col[3], row_col[3];    // row, col, row_col: of A, B, C at gamma
+        QueryValues qv;
+        HF &z_b_beta = qv.z_b_beta, &g_1_beta = qv.g_1_beta, &t_beta = qv.t_beta, &g_2_gamma = qv.g_2_gamma;
+        HF *const row = qv.row, *const col = qv.col, *const row_col = qv.row_col;      // of A, B, C at gamma
         struct Want { Oracle o; const HF* point; HF* value; };
         std::vector<Want> want = {{O_Z_B, &beta, &z_b_beta}, {O_G_1, &beta, &g_1_beta}, {O_T, &beta, &t_beta}, {O_G_2, &gamma, &g_2_gamma}};
         for (int m = 0; m < 3; m++) {
@@ -584,30 +527,14 @@ struct Marlin : MarlinArgs {
             ZK_TRY(zk_shared_open_small(nt, LANES, frs, &opened));
             z_b_beta = HF::from_abi(opened.fr[0]); g_1_beta = HF::from_abi(opened.fr[1]);
         }
-        const HF ba = beta * alpha, one = HF::one();
-        HF d[3];                                                                  // a_denom, b_denom, c_denom
-        for (int m = 0; m < 3; m++) d[m] = ba - alpha * row[m] - beta * col[m] + row_col[m];
         ZK_TRY(P.rc);
-        // construct_linear_combinations (ahp/mod.rs:112-290): the coefficients are marlin_lc.hpp's, shared with the verifier
-        MarlinLcIn in{alpha, {eta[0], eta[1], eta[2]}, beta, gamma, z_b_beta, t_beta, g_1_beta, g_2_gamma, {d[0], d[1], d[2]}, pub.data()};
-        const MarlinLc c = marlin_lc(H, K, X, in);
-        const HF da = d[0], db = d[1], dc = d[2];
-        const LinComb outer = {{one, O_MASK_POLY}, {c.z_a, O_Z_A}, {c.outer_c_zb, O_NONE}, {c.w, O_W}, {c.outer_c_x, O_NONE}, {c.h_1, O_H_1},
-                               {c.outer_c_g1, O_NONE}};
-        const LinComb inner = {{c.val[0], O_A_VAL}, {c.val[1], O_B_VAL}, {c.val[2], O_C_VAL}, {c.inner_c, O_NONE}, {c.h_2, O_H_2}};
-        auto denom_lc = [&](int m) {
-            return LinComb{{ba, O_NONE}, {alpha.neg(), index_of(m, ROW)}, {beta.neg(), index_of(m, COL)}, {one, index_of(m, ROW_COL)}};
-        };
-        // the query set, labels in alphabetic order: {g_1, outer_sumcheck, t, z_b} at beta, {a_denom, b_denom, c_denom, g_2, inner_sumcheck} at gamma
-        queries[0] = {{{one, O_G_1}}, outer, {{one, O_T}}, {{one, O_Z_B}}};
-        queries[1] = {denom_lc(0), denom_lc(1), denom_lc(2), {{one, O_G_2}}, inner};
-        evaluations = {da, db, dc, g_1_beta, g_2_gamma, t_beta, z_b_beta};      // a_denom, b_denom, c_denom, g_1, g_2, t, z_b
+        QuerySet qs = query_set(H, K, X, alpha, eta, beta, gamma, qv, pub.data());
+        evaluations = std::move(qs.evaluations);
+        queries[0] = std::move(qs.queries[0]); queries[1] = std::move(qs.queries[1]);
         std::vector<uint8_t> ev_bytes;
         for (const HF& e : evaluations) e.bytes(ev_bytes);
         ZK_TRY(zk_fsrng_absorb(fs, ev_bytes.data(), ev_bytes.size()));
-        uint64_t w[2];                                                            // u128::rand(&mut fs_rng).into()  (lib.rs:300)
-        ZK_TRY(zk_rng_next_u128(fs, w));
-        xi = HF::from_u64(w[0]) + HF::from_u64(w[1]) * HF::from_u64((uint64_t)1 << 32) * HF::from_u64((uint64_t)1 << 32);
+        ZK_TRY(opening_challenge(fs, &xi));
         laps.lap("evals+lc");
         return ZK_OK;
     }
@@ -624,26 +551,8 @@ struct Marlin : MarlinArgs {
         bool q_shared[2] = {false, false};
         for (int q = 0; q < 2; q++) {
             const HF z = points[q];
-            std::vector<std::pair<Oracle, HF>> terms;                            // polynomial -> accumulated coefficient (first-use order)
-            std::vector<HF> r_comb, sr, srw;
-            std::vector<std::pair<Oracle, HF>> shifted;
-            HF cj = one;                                                         // xi^j
-            for (const LinComb& lc : queries[q]) {
-                const HF c0 = cj;
-                cj = cj * xi;
-                for (const Term& t : lc) {
-                    if (t.o == O_NONE) continue;
-                    auto it = std::find_if(terms.begin(), terms.end(), [&](const std::pair<Oracle, HF>& e) { return e.first == t.o; });
-                    if (it == terms.end()) terms.push_back({t.o, t.c * c0}); else it->second = it->second + t.c * c0;
-                    acc_scaled(r_comb, rands[t.o].plain, t.c * c0);
-                }
-                if (lc.size() == 1 && bounded(lc[0].o)) {                        // a degree-bounded oracle queried by itself
-                    const HF c1 = cj;
-                    cj = cj * xi;
-                    shifted.push_back({lc[0].o, c1});
-                    acc_scaled(sr, rands[lc[0].o].shifted, c1);
-                }
-            }
+            const OpenPlan plan = open_plan(queries[q], xi, rands);
+            const std::vector<std::pair<Oracle, HF>>&terms = plan.terms, &shifted = plan.shifted;
             bool any_shared = false;
             for (auto& t : terms) any_shared = any_shared || (shared && ORACLES[t.first].shared);
             q_shared[q] = any_shared;
@@ -678,19 +587,13 @@ struct Marlin : MarlinArgs {
                 }
                 counts[q][l] = jobs.size() - first_job;
             }
-            bool hiding = false;
-            for (auto& v : r_comb) hiding = hiding || !v.is_zero();
-            if (hiding) {
-                extra[q].push_back(small_async(host_div_linear(r_comb, z)));
+            const OpenBlinds ob = open_blinds(plan, z, rands);
+            if (ob.hiding) {
+                extra[q].push_back(small_async(ob.plain_w));
                 has_rv[q] = true;
-                rvs[q] = host_eval(r_comb, z);
+                rvs[q] = ob.rv;
             }
-            for (auto& sh : shifted) {
-                const std::vector<HF>& sb = rands[sh.first].shifted;
-                if (!sb.empty()) acc_scaled(srw, host_div_linear(sb, z), sh.second);
-            }
-            if (!srw.empty()) extra[q].push_back(small_async(srw));
-            if (!shifted.empty() && has_rv[q]) rvs[q] = rvs[q] + host_eval(sr, z);
+            if (!ob.shifted_w.empty()) extra[q].push_back(small_async(ob.shifted_w));
         }
         ZK_TRY(lanes_rc());
         int orc = ZK_OK;
@@ -727,30 +630,7 @@ struct Marlin : MarlinArgs {
 
     // Proof::serialize (data_structures.rs:99-110, derive order).  In: comms, evaluations, wit, has_rv, rvs
     int serialize(uint8_t* proof_out, size_t cap, size_t* proof_len) {
-        std::vector<uint8_t> out;
-        auto u64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i))); };
-        auto g1c = [&](const Affine<G1Field>& p) { uint8_t b[48]; g1_serialize(p, b); out.insert(out.end(), b, b + 48); };
-        u64(3);
-        for (int round = 1; round <= 3; round++) {
-            const std::vector<Oracle> os = round_oracles(round);
-            u64(os.size());
-            for (Oracle o : os) {
-                const Comm& c = comms[o];
-                g1c(c.c);
-                out.push_back(c.has_shift ? 1 : 0);
-                if (c.has_shift) g1c(c.s);
-            }
-        }
-        u64(evaluations.size());
-        for (auto& e : evaluations) e.bytes(out);
-        u64(3); out.push_back(0); out.push_back(0); out.push_back(0);           // three EmptyMessage
-        u64(2);
-        for (int q = 0; q < 2; q++) {
-            g1c(wit[q]);
-            out.push_back(has_rv[q] ? 1 : 0);
-            if (has_rv[q]) rvs[q].bytes(out);
-        }
-        out.push_back(0);                                                        // BatchLCProof.evals = None
+        const std::vector<uint8_t> out = proof_bytes(comms, evaluations, wit, has_rv, rvs);
         if (out.size() > cap) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer too small");
         memcpy(proof_out, out.data(), out.size());
         *proof_len = out.size();
@@ -764,12 +644,9 @@ int marlin_impl(zk_ctx* ctx, const MarlinArgs& a, uint8_t* proof_out, size_t cap
     if (!ctx || !ix || !a.powers_g || !a.powers_gamma_g || !a.z[0] || (LANES == 2 && !a.z[1]) || !a.rng || !proof_out || !proof_len) return ZK_ERR_ARG;
     if (a.powers_g->group != 1 || a.powers_gamma_g->group != 1 || a.powers_gamma_g->n < 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: SRS tables");
     if (cap < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer smaller than zk_marlin_proof_max_size()");
-    if (ix->num_constraints != ix->num_variables) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: NonSquareMatrix");
-    if (ix->num_instance == 0 || (ix->num_instance & (ix->num_instance - 1))) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: InvalidPublicInputLength");
+    ZK_TRY(check_index_and_srs(ctx, ix, a.powers_g, a.powers_gamma_g));
     Marlin<LANES> m(ctx, a);
-    const size_t need = std::max(std::max(2 * m.n - 1, 3 * m.n - 1), std::max(m.n, 3 * m.K.size - 3));   // AHPForR1CS::max_degree (ahp/mod.rs:75-97)
-    if (m.max_degree < need) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: IndexTooLarge for this SRS");
-    if (m.B.size < 4 * m.K.size - 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: |K| < 4 is not supported by this entry point");
+    ZK_TRY(check_sizes(ctx, m.max_degree, m.n, m.K.size, m.B.size));
     ZK_TRY(m.seed_transcript());
     ZK_TRY(m.round1());
     ZK_TRY(m.round2());

@@ -1,0 +1,741 @@
+// marlin_prove_batch.hip -- count Marlin proofs of ONE index in one call (Marlin::prove, arkworks/marlin/src/lib.rs:152-319, for
+// count assignments).  Proof k is byte for byte what zk_marlin_prove writes for (z_k, rngs[k]), and rngs[k] is left as that call leaves it.
+//
+// A small proof leaves the device idle: every round ends in a chain of sort -> accumulate -> fold -> grid per commitment and a host
+// wait for the transcript.  A shorter chain does not remove the waits; they can only be shared.  Here the proofs of a chunk go
+// through seed -> round 1 -> round 2 -> round 3 -> evaluate -> open in lock-step:
+//   * every oracle and every intermediate of the chunk lives in one call-owned allocation, proof after proof at a fixed stride
+//     (Layout), so the multi-vector MSM jobs (msm.hip: zk_msm_prepare_multi), the strided transforms (ntt.hip) and the batched
+//     kernels (marlin_batch.hip, poly.hip, r1cs.hip) apply directly: the launches of a step do not grow with the chunk;
+//   * a round's commitments are one multi-vector job per (oracle, offset), each on a stream of its own, enqueued before any is
+//     collected; the blinding terms sum c_i powers_of_gamma_g[i] of all proofs (about 7 scalar multiplications per proof and step)
+//     are one zk_g1_lincomb_launch per step on a stream of its own once they are too many for the host's helper threads, which
+//     is where the single prover computes them (HOST_BLIND_MULS);
+//   * each proof keeps its own transcript, challenges and blinding scalars on the host; the per-proof host loops run over ranges of
+//     proofs on the context's pool (zk_over_ranges);
+//   * no MSM starts early (Marlin::start_early hides ONE proof's latency; the batch hides it by width).
+// The per-proof constants of a step (alpha, eta, beta, ..., the opening's coefficients) are a small device table written once per
+// step through a ZkStage.  The only per-proof launches are the device mask sampler (once per call and cheap).  A failing zero test
+// says that SOME proof of the chunk fails; which one, and with which text, is then found by running the single prover over the
+// chunk's proofs in order (the failures -- an unsatisfied system, w not divisible by v_X, the inner sum-check -- depend on the
+// assignment and the index alone, not on the randomness).
+#include "../../include/zkmpc_hip.h"
+#include "devutil.cuh"
+#include "groth16_int.hpp"
+#include "marlin_prove_int.hpp"
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+using namespace zk;
+using namespace zk::marlin;
+
+namespace {
+
+constexpr size_t HOST_TASKS = 16;
+// The blinding terms of a step go to the host's helper threads up to this many scalar multiplications (0.2 ms each on a core, sixteen
+// side by side: at most 2 ms, under the step's MSM jobs) and to the device beyond: k_g1_lincomb is one lane per term, about 4 ms
+// whatever the number of terms (measured at |H| = 2^10: three launches added 11.8 ms to a batch of two proofs)
+constexpr size_t HOST_BLIND_MULS = 160;
+constexpr int MAX_ROUND_JOBS = 4;                 // multi-vector jobs in flight in one step (ZK_SLOT_G16_BATCH has five slots)
+static_assert(MAX_ROUND_JOBS <= ZK_SLOT_G16_COUNT, "a step's jobs each take a scratch slot of their own");
+
+// count vectors of one length in the call's allocation: proof k's at p + k * stride elements
+struct Vec {
+    char* p = nullptr; size_t stride = 0;
+    char* at(size_t k) const { return p + k * stride * 32; }
+};
+
+// The sizes every step reads
+struct Shape {
+    const Dom H, K, X, B;
+    const size_t n, ni, md, nwq;                  // |H|, |X|, the mask polynomial's degree (zk_bound = 1), coefficients of w
+    const Dom MUL;                                // the multiplication domain of round 2
+    const size_t h1n, h2n, max_degree;
+    size_t index_n[12], cn[2];                    // the index polynomials' lengths; the longest polynomial opened at beta / at gamma
+    Shape(const zk_marlin_index* ix, const zk_bases* powers_g)
+        : H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * K.size - 3), n(H.size), ni(ix->num_instance), md(3 * n + 2 - 3),
+          nwq(n + 1 - X.size), MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1)), h1n(std::min(MUL.size - n, 2 * n + 2 - 1)), h2n(B.size - K.size),
+          max_degree(powers_g->n - 1) {
+        for (int i = 0; i < 12; i++) index_n[i] = ix->index_polys[i].n;
+        cn[0] = std::max(std::max(md + 1, h1n), n + 1);
+        cn[1] = std::max(h2n, K.size - 1);
+        for (int i = 0; i < 12; i++) cn[1] = std::max(cn[1], index_n[i]);
+    }
+    size_t bound(Oracle o) const { return (ORACLES[o].bound == Bound::H ? n : K.size) - 2; }
+    size_t oracle_n(Oracle o) const {
+        switch (o) {
+            case O_W: return nwq;
+            case O_Z_A: case O_Z_B: return n + 1;
+            case O_MASK_POLY: return md + 1;
+            case O_T: return n;
+            case O_G_1: return n - 1;
+            case O_H_1: return h1n;
+            case O_G_2: return K.size - 1;
+            case O_H_2: return h2n;
+            default: return index_n[o - O_A_ROW];
+        }
+    }
+};
+
+// Where everything of a chunk of C proofs lives: place() hands out the regions of one allocation in a fixed order (base = NULL:
+// the bytes it takes)
+struct Layout {
+    Vec rnd, mask, mask_q, mask_r, sums, z_a, z_b, xb, x_ev, w_ev, tmp, w_h, wq, wr, za_p, zb_p;       // round 1
+    Vec ra, mv[3], t_ev, e_r, e_t, e_a, e_b, e_s, e_z, zp, h1_q, h1_r, zt;                             // round 2
+    Vec den, f_ev, a_ev, b_ev, f_on_b, h2_q, h2_r;                                                     // round 3
+    Vec comb[2], quo[2], sw[2], spans, pub, lc_out, ntt_tmp;                                           // evaluate, open
+    char* elems = nullptr;                                                                             // the elements of H: one vector for every proof
+    size_t lc_segments = 0;
+    size_t place(char* base, size_t C, const Shape& s) {
+        size_t used = 0;
+        auto take = [&](size_t elems_) { char* p = base ? base + used : nullptr; used += (elems_ * 32 + 255) & ~(size_t)255; return p; };
+        auto vec = [&](Vec& v, size_t per) { v.stride = std::max<size_t>(per, 1); v.p = take(C * v.stride); };
+        const size_t n = s.n, Xs = s.X.size, M = s.MUL.size, Ks = s.K.size, Bs = s.B.size;
+        size_t sums_n = zk_poly_divv_sums_elems(s.md + 1, s.H.log);
+        sums_n = std::max(sums_n, zk_poly_divv_sums_elems(n + 1, s.X.log));
+        sums_n = std::max(sums_n, zk_poly_divv_sums_elems(M, s.H.log));
+        sums_n = std::max(sums_n, zk_poly_divv_sums_elems(Bs, s.K.log));
+        vec(rnd, 3 + s.md + 1); vec(mask, s.md + 1); vec(mask_q, s.md + 1 - n); vec(mask_r, n); vec(sums, sums_n);
+        vec(z_a, n); vec(z_b, n); vec(xb, Xs); vec(x_ev, n); vec(w_ev, n); vec(tmp, n); vec(w_h, n + 1); vec(wq, s.nwq); vec(wr, Xs);
+        vec(za_p, n + 1); vec(zb_p, n + 1);
+        vec(ra, n); for (Vec& v : mv) vec(v, n); vec(t_ev, n);
+        vec(e_r, M); vec(e_t, M); vec(e_a, M); vec(e_b, M); vec(e_s, M); vec(e_z, M); vec(zp, n + 1); vec(h1_q, M - n); vec(h1_r, n); vec(zt, 1);
+        vec(den, 3 * Ks); vec(f_ev, Ks); vec(a_ev, Bs); vec(b_ev, Bs); vec(f_on_b, Bs); vec(h2_q, Bs - Ks); vec(h2_r, Ks);
+        for (int q = 0; q < 2; q++) { vec(comb[q], s.cn[q]); vec(quo[q], s.cn[q]); }
+        vec(sw[0], n); vec(sw[1], Ks);
+        vec(spans, 2 * zk_poly_divlin_spans(std::max(s.cn[0], s.cn[1])));
+        vec(pub, s.ni);
+        lc_segments = 3 * C;
+        vec(lc_out, 10);                           // per proof: three affine points (96 bytes each) and their three flags
+        vec(ntt_tmp, std::max(std::max(M, Bs), n));
+        elems = take(n);
+        return used;
+    }
+};
+
+// One proof's host state: what crosses the steps
+struct One {
+    zk_rng* fs = nullptr;                         // the transcript
+    std::vector<HF> pub;
+    Blinds rands[N_ORACLES];
+    Comm comms[N_PROVER];
+    HF alpha, eta[3], v_h_alpha, beta, vv, gamma, xi;
+    QuerySet qs;
+    OpenPlan plan[2];
+    Affine<G1Field> wit[2];
+    bool has_rv[2] = {false, false}; HF rvs[2];
+    int rc = ZK_OK; std::string err;
+    One() = default;
+    One(const One&) = delete; One& operator=(const One&) = delete;
+    ~One() { zk_rng_free(fs); }
+};
+
+// A multi-vector job of a step and where its C points go
+struct StepJob { const char* scalars; size_t stride, len, off; std::vector<zk_g1_projective> out; };
+
+struct Chunk {
+    zk_ctx* const ctx;
+    const zk_marlin_index* const ix;
+    const zk_bases *const powers_g, *const powers_gamma_g;
+    const Shape& s;
+    const Layout& L;
+    ZkStage& stage;
+    char* const down;                             // page-locked: what a step reads back
+    const size_t C;                               // proofs in this chunk
+    const char* const z; const size_t zs;         // their assignments
+    zk_rng* const* const rngs;
+    const int mask_on_device;
+    const zk_g1_projective* const gamma_pts;      // powers_of_gamma_g[0 .. 2] on the host
+    std::vector<One> P;
+    Vec polys[N_PROVER];
+    const uint32_t* verdicts[3] = {nullptr, nullptr, nullptr};
+    static const char* const check_text[3];
+
+    Chunk(zk_ctx* c, const zk_marlin_index* ix_, const zk_bases* pg, const zk_bases* pgg, const Shape& s_, const Layout& L_, ZkStage& st, char* down_, size_t C_,
+          const char* z_, size_t zs_, zk_rng* const* rngs_, int mod, const zk_g1_projective* gp)
+        : ctx(c), ix(ix_), powers_g(pg), powers_gamma_g(pgg), s(s_), L(L_), stage(st), down(down_), C(C_), z(z_), zs(zs_), rngs(rngs_), mask_on_device(mod),
+          gamma_pts(gp), P(C_) {}
+
+    HF next_fr(zk_rng* r, int* rc) { zk_fr o; const int e = zk_rng_next_fr(r, &o); if (*rc == ZK_OK) *rc = e; return HF::from_abi(o); }
+    template <class Fn>
+    int each(const Fn& f) {                       // f(k) for every proof of the chunk, over ranges on the pool; the first failing proof's code
+        zk_over_ranges(ctx, C, HOST_TASKS, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) if (P[k].rc == ZK_OK) P[k].rc = f(k); });
+        for (size_t k = 0; k < C; k++)
+            if (P[k].rc != ZK_OK) { if (!P[k].err.empty()) ctx->last_error = P[k].err; return P[k].rc; }
+        return ZK_OK;
+    }
+    int ntt(const Vec& v, const Dom& d, int inverse) { return zk_ntt_launch_strided(ctx, v.p, C, v.stride, d.log, inverse, 0, L.ntt_tmp.p); }
+    // the zero-padded copies evaluate_over_domain transforms
+    int padded(const Vec& out, const Dom& d, const Vec& p, size_t pn) {
+        if (pn < d.size) ZK_TRY(zk_b_zero(ctx, out.p + 32 * pn, out.stride, d.size - pn, C));
+        return zk_b_copy(ctx, out.p, out.stride, p.p, p.stride, std::min(pn, d.size), C);
+    }
+    int divv(const Vec& c, size_t cn, const Dom& d, const Vec& q, const Vec& rem) {
+        return zk_poly_divide_by_vanishing_strided(ctx, c.p, c.stride, cn, d.log, C, q.p, q.stride, rem.p, rem.stride, L.sums.p);
+    }
+    // one row of `per` constants per proof, on the device
+    template <class Fn>
+    int table(size_t per, const Fn& fill, const FrK** out) {
+        std::vector<FrK> t(C * per);
+        for (size_t k = 0; k < C; k++) fill(k, &t[k * per]);
+        const void* d;
+        ZK_TRY(stage.put(t.data(), t.size() * sizeof(FrK), &d));
+        *out = (const FrK*)d;
+        return ZK_OK;
+    }
+    int check_later(int slot, const void* v, size_t count) { return zk_fr_vec_is_zero_launch(ctx, v, count, slot, &verdicts[slot]); }
+
+    // ---- a step's commitments: the multi-vector jobs side by side, the blinding terms of all proofs as one launch ----
+    // blind(k, seg): the coefficients over powers_of_gamma_g of proof k's segment seg < nseg (empty: none); their sums land in bl
+    template <class Blind>
+    int commit(std::vector<StepJob>& jobs, size_t nseg, const Blind& blind, std::vector<zk_g1_projective>& bl, std::vector<char>& has_bl) {
+        if (jobs.size() > (size_t)MAX_ROUND_JOBS) return ZK_ERR_STATE;
+        ZkHostLap laps{ctx, "marlin_batch.commit."};
+        hipStream_t st[MAX_ROUND_JOBS] = {ctx->aux[0], ctx->acc_stream, ctx->aux[1], ctx->stream};
+        ZK_TRY(zk_behind_context_stream(ctx, st, 3));                       // the scalars were produced on the context stream
+        ZkMsmJob J[MAX_ROUND_JOBS];
+        struct Streams {                           // declared after the jobs: every exit drains the streams before the jobs and their events go
+            zk_ctx* ctx;
+            ~Streams() {
+                (void)hipStreamSynchronize(ctx->aux[0]);
+                (void)hipStreamSynchronize(ctx->aux[1]);
+                (void)hipStreamSynchronize(ctx->aux[2]);
+                (void)hipStreamSynchronize(ctx->acc_stream);
+                (void)hipStreamSynchronize(ctx->stream);
+            }
+        } drain{ctx};
+        // the blinding terms sum c_i powers_of_gamma_g[i], segments of up to three terms: few of them on the host's helper threads under
+        // the device's work, as the single prover computes them; many as one launch on a stream of their own (canonical scalars),
+        // enqueued BEFORE the jobs: that stream waits for the context stream, which the shortest job's chain is about to join
+        bl.assign(C * nseg, zk_g1_projective{});
+        has_bl.assign(C * nseg, 0);
+        std::vector<std::vector<HF>> cs;
+        std::vector<size_t> where;
+        size_t muls = 0;
+        for (size_t k = 0; k < C; k++)
+            for (size_t sg = 0; sg < nseg; sg++) {
+                std::vector<HF> c = blind(k, sg);
+                if (c.empty()) continue;
+                if (c.size() > 3) return ZK_ERR_STATE;
+                muls += c.size();
+                cs.push_back(std::move(c));
+                where.push_back(k * nseg + sg);
+                has_bl[k * nseg + sg] = 1;
+            }
+        if (where.size() > L.lc_segments) return ZK_ERR_STATE;
+        const bool on_host = muls <= HOST_BLIND_MULS;
+        uint32_t* got = (uint32_t*)down;
+        hipStream_t side = ctx->aux[2];
+        ZkTask<void> host_blinds;                                            // (declared after everything its task references)
+        if (!where.empty() && on_host) {
+            host_blinds = zk_async(ctx, [&] {
+                zk_over_ranges(ctx, where.size(), HOST_TASKS, [&](size_t lo, size_t hi) {
+                    for (size_t i = lo; i < hi; i++) {
+                        zk_g1_projective acc{}, t, u;
+                        for (size_t j = 0; j < cs[i].size(); j++) {
+                            const zk_fr kk = cs[i][j].abi();
+                            zk_g1_mul(&gamma_pts[j], &kk, &t);
+                            if (j == 0) { acc = t; continue; }
+                            zk_g1_add(&acc, &t, &u);
+                            acc = u;
+                        }
+                        bl[where[i]] = acc;
+                    }
+                });
+            });
+        } else if (!where.empty()) {
+            ZkLincombPack pack;
+            for (size_t i = 0; i < where.size(); i++) {
+                uint32_t idx[3] = {0, 1, 2}, k8[24];
+                for (size_t j = 0; j < cs[i].size(); j++) cs[i][j].canon_words(k8 + 8 * j);
+                if (!pack.add(idx, k8, cs[i].size())) return ZK_ERR_STATE;
+            }
+            pack.finish();
+            const void *d_idx, *d_k, *d_off;
+            ZK_TRY(stage.put(pack.point_index.data(), pack.point_index.size() * 4, &d_idx));
+            ZK_TRY(stage.put(pack.scalars.data(), pack.scalars.size() * 4, &d_k));
+            ZK_TRY(stage.put(pack.seg_off.data(), pack.seg_off.size() * 4, &d_off));
+            ZK_TRY(zk_behind_context_stream(ctx, &side, 1));                  // the three uploads
+            uint32_t* o_aff = (uint32_t*)L.lc_out.p;
+            uint32_t* o_inf = o_aff + 24 * where.size();
+            ZK_TRY(zk_g1_lincomb_launch(ctx, powers_gamma_g->dev, 3, (const uint32_t*)d_idx, (const uint32_t*)d_k, (const uint32_t*)d_off, where.size(),
+                                        pack.lanes(), o_aff, o_inf, side));
+            ZK_HIP(ctx, hipMemcpyAsync(got, o_aff, where.size() * 100, hipMemcpyDeviceToHost, side));
+        }
+        laps.lap("blinds");
+        // longest first: the longest chain starts first, and the context stream (which also carries the blinding terms) takes the shortest
+        std::vector<size_t> order(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) order[j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return jobs[a].len > jobs[b].len; });
+        for (size_t p = 0; p < order.size(); p++) {
+            StepJob& j = jobs[order[p]];
+            j.out.assign(C, zk_g1_projective{});
+            if (!j.len) continue;                                            // an empty polynomial commits to the identity
+            ZK_TRY(zk_msm_prepare_multi(ctx, &J[p], powers_g, j.off, j.scalars, j.len, j.stride, C, ZK_SLOT_G16_BATCH + (int)p));
+            ZK_TRY(zk_msm_enqueue_sort(ctx, &J[p], st[p], nullptr));
+            ZK_TRY(zk_msm_enqueue_accum(ctx, &J[p], st[p]));
+            ZK_TRY(zk_msm_enqueue_reduce(ctx, &J[p], st[p]));
+        }
+        laps.lap("enqueue");
+        for (size_t p = 0; p < order.size(); p++)
+            if (jobs[order[p]].len) ZK_TRY(zk_msm_finish_multi(ctx, &J[p], jobs[order[p]].out.data()));
+        laps.lap("msm_wait");
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // everything of the step on the context stream (the zero test's verdict among it)
+        if (host_blinds.valid()) host_blinds.get();
+        else if (!where.empty()) {
+            ZK_HIP(ctx, hipStreamSynchronize(side));
+            for (size_t i = 0; i < where.size(); i++) {
+                if (got[24 * where.size() + i]) continue;                    // the identity
+                zk_g1_affine a;
+                host_aff_to_abi<G1Field>((uint64_t*)&a, aff_load<G1Field>(got + 24 * i));
+                zk_g1_from_affine(&a, &bl[where[i]]);
+            }
+        }
+        laps.lap("blinds_wait");
+        stage.reset();
+        return ZK_OK;
+    }
+    // Did a zero test of this step fail for some proof of the chunk?  Then the single prover names the proof and the reason.
+    int settle(int slot, size_t first_proof) {
+        if (!verdicts[slot] || *verdicts[slot] == 0) return ZK_OK;
+        std::vector<uint8_t> buf(zk_marlin_proof_max_size());
+        for (size_t k = 0; k < C; k++) {
+            size_t len = 0;
+            const int rc = zk_marlin_prove(ctx, ix, powers_g, powers_gamma_g, z + k * zs * 32, rngs[k], mask_on_device, buf.data(), buf.size(), &len);
+            if (rc == ZK_OK) continue;
+            ctx->last_error = "proof " + std::to_string(first_proof + k) + ": " + ctx->last_error;
+            return rc;
+        }
+        ZK_FAIL(ctx, ZK_ERR_STATE, std::string("zk_marlin_prove_batch: ") + check_text[slot] + " failed for the chunk, yet every proof of it passes alone");
+    }
+    // MarlinKZG10::commit for one round (marlin_pc/mod.rs:172-243) of every proof: blinding polynomials in the reference's rng order,
+    // the round's jobs, the round's bytes into each transcript
+    int commit_round(int round, size_t first_proof, int check_slot) {
+        const std::vector<Oracle> os = round_oracles(round);
+        ZK_TRY(each([&](size_t k) {
+            int rc = ZK_OK;
+            for (Oracle o : os) {
+                Blinds& r = P[k].rands[o];
+                if (ORACLES[o].hiding) for (int i = 0; i < 3; i++) r.plain.push_back(next_fr(rngs[k], &rc));
+                if (ORACLES[o].hiding && oracle_bounded(o)) for (int i = 0; i < 3; i++) r.shifted.push_back(next_fr(rngs[k], &rc));
+            }
+            return rc;
+        }));
+        std::vector<StepJob> jobs;
+        struct Dest { Oracle o; int which; };
+        std::vector<Dest> dest, segs;
+        for (Oracle o : os) {
+            const Vec& p = polys[o];
+            jobs.push_back({p.p, p.stride, s.oracle_n(o), 0, {}});
+            dest.push_back({o, 0});
+            if (oracle_bounded(o)) {
+                jobs.push_back({p.p, p.stride, s.oracle_n(o), s.max_degree - s.bound(o), {}});
+                dest.push_back({o, 1});
+            }
+            if (ORACLES[o].hiding) segs.push_back({o, 0});
+            if (ORACLES[o].hiding && oracle_bounded(o)) segs.push_back({o, 1});
+        }
+        std::vector<zk_g1_projective> bl;
+        std::vector<char> has_bl;
+        ZK_TRY(commit(jobs, segs.size(), [&](size_t k, size_t sg) { const Blinds& r = P[k].rands[segs[sg].o]; return segs[sg].which ? r.shifted : r.plain; }, bl,
+                      has_bl));
+        ZK_TRY(settle(check_slot, first_proof));
+        return each([&](size_t k) {
+            zk_g1_projective acc[2][N_PROVER]; bool has[2][N_PROVER] = {};
+            for (size_t j = 0; j < jobs.size(); j++) { acc[dest[j].which][dest[j].o] = jobs[j].out[k]; has[dest[j].which][dest[j].o] = true; }
+            for (size_t sg = 0; sg < segs.size(); sg++) {
+                if (!has_bl[k * segs.size() + sg]) continue;
+                zk_g1_projective& c = acc[segs[sg].which][segs[sg].o];
+                zk_g1_projective t;
+                zk_g1_add(&c, &bl[k * segs.size() + sg], &t);
+                c = t;
+            }
+            std::vector<uint8_t> bytes;
+            std::vector<zk_g1_projective> all;
+            for (Oracle o : os) {
+                all.push_back(acc[0][o]);
+                if (has[1][o]) all.push_back(acc[1][o]);
+            }
+            const std::vector<Affine<G1Field>> aff = batch_to_aff(all);
+            size_t ai = 0;
+            for (Oracle o : os) {
+                Comm& c = P[k].comms[o];
+                c.c = aff[ai++];
+                c.has_shift = has[1][o];
+                c.s = c.has_shift ? aff[ai++] : aff_inf<G1Field>();
+                comm_tobytes(c, bytes);
+            }
+            return zk_fsrng_absorb(P[k].fs, bytes.data(), bytes.size());      // to_bytes![comms, EmptyMessage]
+        });
+    }
+    HF sample_outside(size_t k, const Dom& d, int* rc) {
+        HF t = next_fr(P[k].fs, rc);
+        while (*rc == ZK_OK && d.vanishing(t).is_zero()) t = next_fr(P[k].fs, rc);
+        return t;
+    }
+
+    // The transcript seeds: PROTOCOL_NAME | index_vk | public_input (lib.rs:161-164)
+    int seed_transcripts() {
+        ZK_TRY(zk_b_copy(ctx, L.pub.p, L.pub.stride, z, zs, s.ni, C));
+        std::vector<zk_fr> x(C * s.ni);
+        ZK_TRY(zk_memcpy_d2h(ctx, x.data(), L.pub.p, C * s.ni * 32));
+        return each([&](size_t k) {
+            P[k].pub.assign(s.ni, HF::one());
+            for (size_t i = 1; i < s.ni; i++) P[k].pub[i] = HF::from_abi(x[k * s.ni + i]);
+            const std::vector<uint8_t> seed = transcript_seed(ix, P[k].pub);
+            return zk_fsrng_new(seed.data(), seed.size(), &P[k].fs);
+        });
+    }
+
+    // Round 1 (prover.rs:216-404)
+    int round1(size_t first_proof) {
+        const size_t n = s.n, md = s.md, host_n = mask_on_device ? 3 : 3 + md + 1;
+        {
+            std::vector<zk_fr> h(C * host_n);
+            std::vector<uint8_t> keys(C * 32);
+            ZK_TRY(each([&](size_t k) {
+                ZK_TRY(zk_rng_fill_fr(rngs[k], h.data() + k * host_n, host_n));
+                return mask_on_device ? zk_rng_fill_bytes(rngs[k], keys.data() + 32 * k, 32) : (int)ZK_OK;
+            }));
+            if (L.rnd.stride == host_n) ZK_TRY(zk_xfer_h2d(ctx, L.rnd.p, h.data(), C * host_n * 32));
+            else {
+                // (three scalars per proof: through the step's upload area, then spread to the proofs' strides)
+                const void* d;
+                ZK_TRY(stage.put(h.data(), C * host_n * 32, &d));
+                ZK_TRY(zk_b_copy(ctx, L.rnd.p, L.rnd.stride, d, host_n, host_n, C));
+                for (size_t k = 0; k < C; k++) ZK_TRY(zk_fr_random_dev(ctx, keys.data() + 32 * k, 0, L.rnd.at(k) + 96, md + 1));
+            }
+        }
+        ZK_TRY(zk_b_copy(ctx, L.mask.p, L.mask.stride, L.rnd.p + 96, L.rnd.stride, md + 1, C));
+        ZK_TRY(divv(L.mask, md + 1, s.H, L.mask_q, L.mask_r));
+        ZK_TRY(zk_b_op(ctx, ZK_OP_SUB, L.mask.p, L.mask.stride, L.mask_r.p, L.mask_r.stride, L.mask.p, L.mask.stride, 1, C));      // the sum over H becomes zero
+        polys[O_MASK_POLY] = L.mask;
+        ZK_TRY(zk_r1cs_matvec_strided(ctx, ix->r1cs, 0, z, zs, C, L.z_a.p, L.z_a.stride, n));
+        ZK_TRY(zk_r1cs_matvec_strided(ctx, ix->r1cs, 1, z, zs, C, L.z_b.p, L.z_b.stride, n));
+        ZK_TRY(zk_b_copy(ctx, L.xb.p, L.xb.stride, z, zs, s.X.size, C));
+        ZK_TRY(ntt(L.xb, s.X, 1));
+        ZK_TRY(padded(L.x_ev, s.H, L.xb, s.X.size));
+        ZK_TRY(ntt(L.x_ev, s.H, 0));
+        ZK_TRY(zk_b_gather(ctx, z, zs, ix->w_idx, n, L.w_ev.p, L.w_ev.stride, C));
+        ZK_TRY(zk_b_gather(ctx, L.x_ev.p, L.x_ev.stride, ix->x_idx, n, L.tmp.p, L.tmp.stride, C));
+        ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_SUB, L.w_ev.p, L.tmp.p, L.w_ev.p, C * n));
+        ZK_TRY(ntt(L.w_ev, s.H, 1));                                         // the three interpolations of the round
+        ZK_TRY(ntt(L.z_a, s.H, 1));
+        ZK_TRY(ntt(L.z_b, s.H, 1));
+        ZK_TRY(zk_b_blind(ctx, L.w_ev.p, L.w_ev.stride, n, L.rnd.p, L.rnd.stride, L.w_h.p, L.w_h.stride, C));
+        ZK_TRY(divv(L.w_h, n + 1, s.X, L.wq, L.wr));
+        ZK_TRY(check_later(0, L.wr.p, C * s.X.size));
+        ZK_TRY(zk_b_blind(ctx, L.z_a.p, L.z_a.stride, n, L.rnd.p + 32, L.rnd.stride, L.za_p.p, L.za_p.stride, C));
+        ZK_TRY(zk_b_blind(ctx, L.z_b.p, L.z_b.stride, n, L.rnd.p + 64, L.rnd.stride, L.zb_p.p, L.zb_p.stride, C));
+        polys[O_W] = L.wq; polys[O_Z_A] = L.za_p; polys[O_Z_B] = L.zb_p;
+        ZK_TRY(commit_round(1, first_proof, 0));
+        return each([&](size_t k) {
+            int rc = ZK_OK;
+            P[k].alpha = sample_outside(k, s.H, &rc);
+            for (HF& e : P[k].eta) e = next_fr(P[k].fs, &rc);
+            return rc;
+        });
+    }
+
+    // Round 2 (prover.rs:438-565)
+    int round2(size_t first_proof) {
+        const size_t n = s.n, M = s.MUL.size;
+        const HF one = HF::one();
+        const FrK *t_alpha, *t_vh, *t_eta;
+        ZK_TRY(table(1, [&](size_t k, FrK* r) { r[0] = to_frk(fp_int_to_ext<FrParams>(P[k].alpha.v)); }, &t_alpha));
+        ZK_TRY(table(1, [&](size_t k, FrK* r) { P[k].v_h_alpha = s.H.vanishing(P[k].alpha); r[0] = to_frk(P[k].v_h_alpha.v); }, &t_vh));
+        ZK_TRY(table(3, [&](size_t k, FrK* r) { for (int m = 0; m < 3; m++) r[m] = to_frk(P[k].eta[m].v); }, &t_eta));
+        ZK_TRY(zk_fr_powers_launch(ctx, s.H.gen.v, one.v, n, L.elems, ZK_FR_EXT));
+        ZK_TRY(zk_b_const_minus(ctx, t_alpha, 1, L.elems, n, L.ra.p, L.ra.stride, C));
+        ZK_TRY(zk_fr_batch_inverse_dev(ctx, L.ra.p, C * n));
+        ZK_TRY(zk_b_scale(ctx, L.ra.p, L.ra.stride, t_vh, 1, L.ra.p, L.ra.stride, n, C));      // r(alpha, X) on H (ahp/mod.rs:352-360)
+        {                                                                                       // calculate_t on the transposed matrices
+            const void* ps[3]; size_t strides[3], ns[3];
+            for (int which = 0; which < 3; which++) {
+                ZK_TRY(zk_r1cs_matvec_strided(ctx, ix->r1cs_t, which, L.ra.p, L.ra.stride, C, L.mv[which].p, L.mv[which].stride, n));
+                ps[which] = L.mv[which].p; strides[which] = L.mv[which].stride; ns[which] = n;
+            }
+            ZK_TRY(zk_b_lincomb(ctx, 3, ps, strides, ns, t_eta, 3, L.t_ev.p, L.t_ev.stride, n, C));
+        }
+        ZK_TRY(ntt(L.t_ev, s.H, 1));
+        ZK_TRY(ntt(L.ra, s.H, 1));
+        polys[O_T] = L.t_ev;
+        ZK_TRY(padded(L.e_r, s.MUL, L.ra, n));
+        ZK_TRY(padded(L.e_t, s.MUL, L.t_ev, n));
+        // z = w v_X + x
+        ZK_TRY(zk_b_zero(ctx, L.zp.p, L.zp.stride, n + 1, C));
+        ZK_TRY(zk_b_copy(ctx, L.zp.p + 32 * s.X.size, L.zp.stride, L.wq.p, L.wq.stride, s.nwq, C));
+        ZK_TRY(zk_b_op(ctx, ZK_OP_SUB, L.zp.p, L.zp.stride, L.wq.p, L.wq.stride, L.zp.p, L.zp.stride, s.nwq, C));
+        ZK_TRY(zk_b_op(ctx, ZK_OP_ADD, L.zp.p, L.zp.stride, L.xb.p, L.xb.stride, L.zp.p, L.zp.stride, s.X.size, C));
+        ZK_TRY(padded(L.e_a, s.MUL, L.za_p, n + 1));
+        ZK_TRY(padded(L.e_b, s.MUL, L.zb_p, n + 1));
+        ZK_TRY(padded(L.e_z, s.MUL, L.zp, n + 1));
+        for (const Vec* v : {&L.e_r, &L.e_t, &L.e_a, &L.e_b, &L.e_z}) ZK_TRY(ntt(*v, s.MUL, 0));
+        ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, L.e_a.p, L.e_b.p, L.e_s.p, C * M));           // z_a z_b: the one product of two witness vectors
+        ZK_TRY(zk_b_outer_q1(ctx, L.e_s.p, L.e_a.p, L.e_b.p, L.e_z.p, L.e_r.p, L.e_t.p, M, t_eta, 3, L.e_s.p, M, C));
+        ZK_TRY(ntt(L.e_s, s.MUL, 1));                                                          // q_1 (prover.rs:517-541)
+        ZK_TRY(zk_b_op(ctx, ZK_OP_ADD, L.e_s.p, L.e_s.stride, L.mask.p, L.mask.stride, L.e_s.p, L.e_s.stride, s.md + 1, C));
+        ZK_TRY(divv(L.e_s, M, s.H, L.h1_q, L.h1_r));
+        // the outer sum-check's zero test (prover.rs:547-550): the constant terms of the count remainders, laid back to back
+        ZK_TRY(zk_b_copy(ctx, L.zt.p, L.zt.stride, L.h1_r.p, L.h1_r.stride, 1, C));
+        ZK_TRY(check_later(1, L.zt.p, C));
+        polys[O_G_1] = Vec{L.h1_r.p + 32, L.h1_r.stride};
+        polys[O_H_1] = L.h1_q;
+        ZK_TRY(commit_round(2, first_proof, 1));
+        return each([&](size_t k) { int rc = ZK_OK; P[k].beta = sample_outside(k, s.H, &rc); return rc; });
+    }
+
+    // Round 3 (prover.rs:583-716)
+    int round3(size_t first_proof) {
+        const size_t Ks = s.K.size, Bs = s.B.size;
+        const FrK* tab;
+        ZK_TRY(table(ZK_B_R3_ROW, [&](size_t k, FrK* r) {
+            P[k].vv = P[k].v_h_alpha * s.H.vanishing(P[k].beta);
+            const Fr eta[3] = {P[k].eta[0].v, P[k].eta[1].v, P[k].eta[2].v};
+            zk_b_round3_row(P[k].alpha.v, P[k].beta.v, eta, P[k].vv.v, r);
+        }, &tab));
+        ZK_TRY(zk_b_round3_denoms(ctx, ix->on_k, Ks, tab, L.den.p, C));
+        ZK_TRY(zk_fr_batch_inverse_dev(ctx, L.den.p, C * 3 * Ks));          // zero denominators stay zero, as in ark_ff::batch_inversion
+        ZK_TRY(zk_b_round3_f(ctx, ix->on_k, Ks, tab, L.den.p, L.f_ev.p, L.f_ev.stride, C));
+        ZK_TRY(zk_b_round3_ab(ctx, ix->on_b, Bs, tab, L.a_ev.p, L.b_ev.p, Bs, C));
+        ZK_TRY(ntt(L.f_ev, s.K, 1));
+        polys[O_G_2] = Vec{L.f_ev.p + 32, L.f_ev.stride};
+        ZK_TRY(padded(L.f_on_b, s.B, L.f_ev, Ks));                         // a - b f on B itself (degree <= 4|K| - 4 < |B|)
+        ZK_TRY(ntt(L.f_on_b, s.B, 0));
+        ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_MUL, L.b_ev.p, L.f_on_b.p, L.b_ev.p, C * Bs));
+        ZK_TRY(zk_vec_op_launch(ctx, ZK_OP_SUB, L.a_ev.p, L.b_ev.p, L.a_ev.p, C * Bs));
+        ZK_TRY(ntt(L.a_ev, s.B, 1));
+        ZK_TRY(divv(L.a_ev, Bs, s.K, L.h2_q, L.h2_r));
+        ZK_TRY(check_later(2, L.h2_r.p, C * Ks));
+        polys[O_H_2] = L.h2_q;
+        ZK_TRY(commit_round(3, first_proof, 2));
+        return each([&](size_t k) { int rc = ZK_OK; P[k].gamma = next_fr(P[k].fs, &rc); return rc; });
+    }
+
+    Vec poly_of(Oracle o) const {
+        if (o < N_PROVER) return polys[o];
+        return Vec{(char*)ix->index_polys[o - O_A_ROW].ptr, 0};               // an index oracle: one vector for every proof
+    }
+
+    // The evaluations of every proof's query set in one batch (two launches, one copy back), absorbed; the linear combinations over them
+    int evaluate() {
+        struct Want { Oracle o; bool at_gamma; };
+        std::vector<Want> want = {{O_Z_B, false}, {O_G_1, false}, {O_T, false}, {O_G_2, true}};
+        for (int m = 0; m < 3; m++) for (IndexPart part : {ROW, COL, ROW_COL}) want.push_back({index_of(m, part), true});
+        const size_t W = want.size();
+        std::vector<zk_poly_ref> refs(C * W);
+        std::vector<zk_fr> pts(C * W), vals(C * W);
+        for (size_t k = 0; k < C; k++)
+            for (size_t i = 0; i < W; i++) {
+                const Vec v = poly_of(want[i].o);
+                refs[k * W + i] = zk_poly_ref{v.at(k), s.oracle_n(want[i].o)};
+                pts[k * W + i] = (want[i].at_gamma ? P[k].gamma : P[k].beta).abi();
+            }
+        ZK_TRY(zk_poly_evaluate_batch_dev(ctx, refs.data(), pts.data(), C * W, vals.data()));
+        return each([&](size_t k) {
+            One& p = P[k];
+            const zk_fr* v = &vals[k * W];
+            QueryValues qv;
+            qv.z_b_beta = HF::from_abi(v[0]); qv.g_1_beta = HF::from_abi(v[1]); qv.t_beta = HF::from_abi(v[2]); qv.g_2_gamma = HF::from_abi(v[3]);
+            for (int m = 0; m < 3; m++) {
+                qv.row[m] = HF::from_abi(v[4 + 3 * m]); qv.col[m] = HF::from_abi(v[5 + 3 * m]); qv.row_col[m] = HF::from_abi(v[6 + 3 * m]);
+            }
+            p.qs = query_set(s.H, s.K, s.X, p.alpha, p.eta, p.beta, p.gamma, qv, p.pub.data());
+            std::vector<uint8_t> ev_bytes;
+            for (const HF& e : p.qs.evaluations) e.bytes(ev_bytes);
+            ZK_TRY(zk_fsrng_absorb(p.fs, ev_bytes.data(), ev_bytes.size()));
+            ZK_TRY(opening_challenge(p.fs, &p.xi));
+            for (int q = 0; q < 2; q++) p.plan[q] = open_plan(p.qs.queries[q], p.xi, p.rands);
+            return (int)ZK_OK;
+        });
+    }
+
+    // open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340): the same oracles enter a combination for every proof, with
+    // coefficients of its own; per query point one combination, its witness quotient and the shifted witnesses of the bounded oracles
+    int open_combinations() {
+        std::vector<StepJob> jobs;
+        size_t njobs[2] = {0, 0};
+        for (int q = 0; q < 2; q++) {
+            const OpenPlan& p0 = P[0].plan[q];
+            const size_t T = p0.terms.size();
+            for (size_t k = 1; k < C; k++) {                                  // (the plan's shape depends on the query set alone)
+                const OpenPlan& pk = P[k].plan[q];
+                bool same = pk.terms.size() == T && pk.shifted.size() == p0.shifted.size();
+                for (size_t t = 0; same && t < T; t++) same = pk.terms[t].first == p0.terms[t].first;
+                for (size_t t = 0; same && t < p0.shifted.size(); t++) same = pk.shifted[t].first == p0.shifted[t].first;
+                if (!same) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_prove_batch: the proofs' opening plans differ");
+            }
+            if (p0.shifted.size() > 1) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_prove_batch: more than one shifted witness at a query point");
+            std::vector<const void*> ps(T); std::vector<size_t> strides(T), ns(T);
+            size_t cn = 0;
+            for (size_t t = 0; t < T; t++) {
+                const Vec v = poly_of(p0.terms[t].first);
+                ps[t] = v.p; strides[t] = v.stride; ns[t] = s.oracle_n(p0.terms[t].first);
+                cn = std::max(cn, ns[t]);
+            }
+            if (cn > s.cn[q] || cn < 2) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_prove_batch: a combination outgrows its buffer");
+            const FrK* coef;
+            ZK_TRY(table(T, [&](size_t k, FrK* r) { for (size_t t = 0; t < T; t++) r[t] = to_frk(P[k].plan[q].terms[t].second.v); }, &coef));
+            ZK_TRY(zk_b_lincomb(ctx, (int)T, ps.data(), strides.data(), ns.data(), coef, T, L.comb[q].p, L.comb[q].stride, cn, C));
+            std::vector<Fr> zpt(C);
+            for (size_t k = 0; k < C; k++) zpt[k] = (q ? P[k].gamma : P[k].beta).v;
+            ZK_TRY(zk_poly_divide_by_linear_strided(ctx, L.comb[q].p, L.comb[q].stride, cn, zpt.data(), C, L.quo[q].p, L.quo[q].stride, L.spans.p, &stage));
+            jobs.push_back({L.quo[q].p, L.quo[q].stride, cn - 1, 0, {}});
+            njobs[q] = 1;
+            for (auto& sh : p0.shifted) {
+                const Vec v = poly_of(sh.first);
+                const size_t pn = s.oracle_n(sh.first);
+                if (pn < 2) continue;
+                ZK_TRY(zk_poly_divide_by_linear_strided(ctx, v.p, v.stride, pn, zpt.data(), C, L.sw[q].p, L.sw[q].stride, L.spans.p, &stage));
+                const FrK* c1;
+                ZK_TRY(table(1, [&](size_t k, FrK* r) { r[0] = to_frk(P[k].plan[q].shifted[0].second.v); }, &c1));
+                ZK_TRY(zk_b_scale(ctx, L.sw[q].p, L.sw[q].stride, c1, 1, L.sw[q].p, L.sw[q].stride, pn - 1, C));
+                jobs.push_back({L.sw[q].p, L.sw[q].stride, pn - 1, s.max_degree - s.bound(sh.first), {}});
+                njobs[q]++;
+            }
+        }
+        // the blinding witnesses: per proof and query point the plain and the shifted one
+        std::vector<OpenBlinds> ob(C * 2);
+        ZK_TRY(each([&](size_t k) {
+            for (int q = 0; q < 2; q++) {
+                ob[2 * k + q] = open_blinds(P[k].plan[q], q ? P[k].gamma : P[k].beta, P[k].rands);
+                P[k].has_rv[q] = ob[2 * k + q].hiding;
+                if (ob[2 * k + q].hiding) P[k].rvs[q] = ob[2 * k + q].rv;
+            }
+            return (int)ZK_OK;
+        }));
+        // (at gamma nothing is hiding: g_2, h_2 and the index are committed without blinds)
+        for (size_t k = 0; k < C; k++)
+            if (ob[2 * k + 1].hiding || !ob[2 * k + 1].shifted_w.empty()) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_marlin_prove_batch: a blinding witness at gamma");
+        std::vector<zk_g1_projective> bl;
+        std::vector<char> has_bl;
+        ZK_TRY(commit(jobs, 2, [&](size_t k, size_t sg) { return sg == 0 ? ob[2 * k].plain_w : ob[2 * k].shifted_w; }, bl, has_bl));
+        return each([&](size_t k) {
+            std::vector<zk_g1_projective> wits;
+            size_t j = 0;
+            for (int q = 0; q < 2; q++) {
+                zk_g1_projective w = jobs[j].out[k];
+                for (size_t i = 1; i < njobs[q]; i++) { zk_g1_projective t; zk_g1_add(&w, &jobs[j + i].out[k], &t); w = t; }
+                for (size_t sg = 0; sg < 2 && q == 0; sg++) {
+                    if (!has_bl[2 * k + sg]) continue;
+                    zk_g1_projective t;
+                    zk_g1_add(&w, &bl[2 * k + sg], &t);
+                    w = t;
+                }
+                j += njobs[q];
+                wits.push_back(w);
+            }
+            const std::vector<Affine<G1Field>> wa = batch_to_aff(wits);
+            P[k].wit[0] = wa[0]; P[k].wit[1] = wa[1];
+            return (int)ZK_OK;
+        });
+    }
+
+    int run(size_t first_proof, uint8_t* proofs_out, size_t slot, size_t* proof_lens) {
+        ZkHostLap laps{ctx, "marlin_batch."};
+        ZK_TRY(seed_transcripts());
+        laps.lap("seed");
+        ZK_TRY(round1(first_proof));
+        laps.lap("round1");
+        ZK_TRY(round2(first_proof));
+        laps.lap("round2");
+        ZK_TRY(round3(first_proof));
+        laps.lap("round3");
+        ZK_TRY(evaluate());
+        laps.lap("evaluate");
+        ZK_TRY(open_combinations());
+        laps.lap("open");
+        return each([&](size_t k) {
+            const std::vector<uint8_t> out = proof_bytes(P[k].comms, P[k].qs.evaluations, P[k].wit, P[k].has_rv, P[k].rvs);
+            if (out.size() > slot) { P[k].err = "zk_marlin_prove_batch: output slot too small"; return (int)ZK_ERR_ARG; }
+            memcpy(proofs_out + k * slot, out.data(), out.size());
+            proof_lens[k] = out.size();
+            return (int)ZK_OK;
+        });
+    }
+};
+const char* const Chunk::check_text[3] = {"the divisibility of w by v_X", "the outer sum-check", "the inner sum-check"};
+
+// device bytes of one chunk's MSM scratch: per job in flight its sort (~16 bytes per digit) and its bucket sums (groth16_batch.hip's rule)
+size_t msm_bytes(const zk_bases* tab, size_t len, size_t chunk) {
+    const size_t W = tab->pre ? (255 + tab->c_pre - 1) / tab->c_pre : 32;
+    const size_t buckets = tab->pre ? ((size_t)1 << (tab->c_pre - 1)) : W * std::max<size_t>(len, 16);
+    return (size_t)MAX_ROUND_JOBS * chunk * (len * W * 16 + buckets * 48 * 4 * 2);
+}
+
+}  // namespace
+
+extern "C" int zk_marlin_prove_batch(zk_ctx* ctx, const zk_marlin_index* ix, const zk_bases* powers_g, const zk_bases* powers_gamma_g, size_t count,
+                                     const void* z_dev, size_t z_stride, zk_rng* const* rngs, int mask_on_device, uint8_t* proofs_out, size_t slot,
+                                     size_t* proof_lens) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !ix || !powers_g || !powers_gamma_g || !z_dev || !rngs || !proofs_out || !proof_lens) return ZK_ERR_ARG;
+    if (count == 0) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove_batch: count must be at least 1");
+    for (size_t k = 0; k < count; k++) if (!rngs[k]) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove_batch: a generator is missing");
+    if (slot < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove_batch: slot smaller than zk_marlin_proof_max_size()");
+    if (z_stride < ix->num_variables) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove_batch: z_stride is shorter than the padded assignment");
+    if (count == 1) return zk_marlin_prove(ctx, ix, powers_g, powers_gamma_g, z_dev, rngs[0], mask_on_device, proofs_out, slot, proof_lens);
+    ZkHostLap laps{ctx, "marlin_batch."};
+    ZK_TRY(check_index_and_srs(ctx, ix, powers_g, powers_gamma_g));
+    const Shape s(ix, powers_g);
+    ZK_TRY(check_sizes(ctx, s.max_degree, s.n, s.K.size, s.B.size));
+    // the chunk: what one multi-vector job takes, what fits the device, what the environment asks for
+    size_t chunk = count, longest = 0;
+    for (int o = 0; o < N_PROVER; o++) {
+        const size_t len = s.oracle_n((Oracle)o);
+        if (len) chunk = std::min(chunk, zk_msm_multi_chunk(powers_g, len));
+        longest = std::max(longest, len);
+    }
+    for (int q = 0; q < 2; q++) { chunk = std::min(chunk, zk_msm_multi_chunk(powers_g, s.cn[q] - 1)); longest = std::max(longest, s.cn[q] - 1); }
+    if (s.n > 2) chunk = std::min(chunk, zk_msm_multi_chunk(powers_g, s.n - 2));
+    if (s.K.size > 2) chunk = std::min(chunk, zk_msm_multi_chunk(powers_g, s.K.size - 2));
+    Layout L;
+    {
+        size_t free_b = 0, total_b = 0;
+        ZK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+        auto need = [&](size_t c) { return (double)L.place(nullptr, c, s) + (double)msm_bytes(powers_g, longest, c); };
+        while (chunk > 1 && need(chunk) > (double)(free_b / 10 * 9)) chunk = (chunk + 1) / 2;
+        if (need(chunk) > (double)(free_b / 10 * 9))
+            ZK_FAIL(ctx, ZK_ERR_NOMEM, "marlin batch: the working set of one proof (" + std::to_string((unsigned long long)(need(1) / 1048576.0)) +
+                                           " MiB) does not fit the free device memory (" + std::to_string(free_b >> 20) + " MiB)");
+    }
+    if (const char* e = getenv("ZK_MARLIN_BATCH_CHUNK")) {                  // read at every call: the seam between chunks at small shapes
+        const long v = atol(e);
+        if (v > 0) chunk = std::min(chunk, (size_t)v);
+    }
+    zk_presort_free(ctx);                                                    // (a Groth16 proof's jobs enqueued ahead use the streams this call waits on)
+    ZK_TRY(zk_prover_streams(ctx, 3));
+    zk_g1_projective gamma_pts[3];
+    {
+        zk_g1_affine g[3];
+        ZK_TRY(zk_bases_download_g1(ctx, powers_gamma_g, 0, 3, g));
+        for (int i = 0; i < 3; i++) zk_g1_from_affine(&g[i], &gamma_pts[i]);
+    }
+    ZkCallMem mem{ctx}, up{ctx};
+    const size_t bytes = L.place(nullptr, chunk, s);
+    ZK_HIP(ctx, hipMalloc(&mem.p, bytes));
+    L.place((char*)mem.p, chunk, s);
+    // what a step uploads: the job arrays of four divisions, the constants' tables, the blinding terms' lanes
+    ZkStage stage;
+    stage.ctx = ctx;
+    stage.cap = chunk * (4 * zk_poly_divlin_job_bytes() + 64 * sizeof(FrK) + 16 * 36 + 1024) + 65536;
+    const size_t down_bytes = chunk * 3 * 100 + 256;
+    ZK_HIP(ctx, hipMalloc(&up.p, stage.cap));
+    stage.dev = (char*)up.p;
+    ZK_TRY(zk_pinned(ctx, {ZK_PIN_MARLIN_BATCH, 0}, stage.cap, (void**)&stage.host));
+    char* down;
+    ZK_TRY(zk_pinned(ctx, {ZK_PIN_MARLIN_BATCH, 1}, down_bytes, (void**)&down));
+    laps.lap("plan+alloc");
+    for (size_t k0 = 0; k0 < count; k0 += chunk) {
+        const size_t cnt = std::min(chunk, count - k0);
+        stage.reset();
+        Chunk c(ctx, ix, powers_g, powers_gamma_g, s, L, stage, down, cnt, (const char*)z_dev + k0 * z_stride * 32, z_stride, rngs + k0, mask_on_device, gamma_pts);
+        const int rc = c.run(k0, proofs_out + k0 * slot, slot, proof_lens + k0);
+        (void)hipStreamSynchronize(ctx->stream);                             // every exit leaves nothing behind on the stream it enqueued on
+        ZK_TRY(rc);
+    }
+    return ZK_OK;
+    ZK_API_END
+}

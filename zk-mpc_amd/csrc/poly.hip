@@ -34,7 +34,7 @@ constexpr int INV_CH = 32;   // batch-inversion chunk per thread
 // is the column-wise exclusive suffix sum, q[k][j] = sum_{k' > k} c[k'][j], and the remainder is r[j] = c[0][j] + q[0][j].
 // Rows are cut into G groups of R; one thread owns one (group, column), so the work is O(n) for every N (a tiny N, like
 // the |X| = 2 of Marlin's w(X) / v_X, included).
-__global__ void __launch_bounds__(256) k_divv_sums(const void* c, size_t n, size_t N, size_t R, size_t G, void* sums) {
+__device__ __forceinline__ void divv_sums(const void* c, size_t n, size_t N, size_t R, size_t G, void* sums) {
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < G * N; t += (size_t)gridDim.x * blockDim.x) {
         size_t g = t / N, j = t - g * N;
         Fr acc = fp_zero<FrParams>();
@@ -45,9 +45,7 @@ __global__ void __launch_bounds__(256) k_divv_sums(const void* c, size_t n, size
         fr_store(sums, t, acc);
     }
 }
-
-__global__ void __launch_bounds__(256) k_divv_fill(const void* c, size_t n, size_t N, size_t R, size_t G, const void* sums, void* q,
-                                                   size_t nq, void* rem) {
+__device__ __forceinline__ void divv_fill(const void* c, size_t n, size_t N, size_t R, size_t G, const void* sums, void* q, size_t nq, void* rem) {
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < G * N; t += (size_t)gridDim.x * blockDim.x) {
         size_t g = t / N, j = t - g * N;
         Fr acc = fp_zero<FrParams>();
@@ -60,6 +58,24 @@ __global__ void __launch_bounds__(256) k_divv_fill(const void* c, size_t n, size
             acc = fr_add(acc, x);
         }
     }
+}
+__global__ void __launch_bounds__(256) k_divv_sums(const void* c, size_t n, size_t N, size_t R, size_t G, void* sums) { divv_sums(c, n, N, R, G, sums); }
+__global__ void __launch_bounds__(256) k_divv_fill(const void* c, size_t n, size_t N, size_t R, size_t G, const void* sums, void* q,
+                                                   size_t nq, void* rem) {
+    divv_fill(c, n, N, R, G, sums, q, nq, rem);
+}
+// ... for the polynomials of a batch, one per blockIdx.y: polynomial y at c + y * c_stride elements (n coefficients each), its group
+// sums at sums + y * G * N, its quotient and remainder at q + y * q_stride and rem + y * r_stride
+struct DivvStrides { size_t c, q, rem; };
+__global__ void __launch_bounds__(256) k_divv_sums_strided(const void* c, DivvStrides st, size_t n, size_t N, size_t R, size_t G, void* sums) {
+    const size_t y = blockIdx.y;
+    divv_sums((const char*)c + y * st.c * 32, n, N, R, G, (char*)sums + y * G * N * 32);
+}
+__global__ void __launch_bounds__(256) k_divv_fill_strided(const void* c, DivvStrides st, size_t n, size_t N, size_t R, size_t G, const void* sums,
+                                                           void* q, size_t nq, void* rem) {
+    const size_t y = blockIdx.y;
+    divv_fill((const char*)c + y * st.c * 32, n, N, R, G, sums ? (const char*)sums + y * G * N * 32 : nullptr, (char*)q + y * st.q * 32, nq,
+              (char*)rem + y * st.rem * 32);
 }
 
 // Montgomery's trick on chunks of INV_CH (devutil.cuh: inv_chunk_fwd / inv_chunk_bwd around the chunk's one inversion).
@@ -177,7 +193,8 @@ __device__ __forceinline__ Fr block_suffix_scan(uint32_t (*buf)[9][256], const F
     }
     return v;       // buf[cur] holds every thread's I_t
 }
-__global__ void __launch_bounds__(256) k_span_carries(const EvalJob J, const void* partial, void* carry, void* rem) {
+// (partial, carry: the job's own span values and carries, span b at index b)
+__device__ __forceinline__ void span_carries(const EvalJob& J, const void* partial, void* carry, void* rem) {
     __shared__ uint32_t buf[2][9][256];
     const Fr zs = J.zspan;
     const uint32_t tid = threadIdx.x;
@@ -191,9 +208,10 @@ __global__ void __launch_bounds__(256) k_span_carries(const EvalJob J, const voi
     }
     if (tid == 0 && rem) fr_store(rem, 0, c);
 }
+__global__ void __launch_bounds__(256) k_span_carries(const EvalJob J, const void* partial, void* carry, void* rem) { span_carries(J, partial, carry, rem); }
 // carry == nullptr: a polynomial of ONE span (<= 4 096 coefficients) -- its carry-in is zero and this launch is the whole division
 // (the remainder Q_0 goes to rem when asked for): one launch instead of three for the opening witnesses of a small Marlin proof.
-__global__ void __launch_bounds__(256) k_fill_spans(const EvalJob J, const void* carry, void* out, int shift, void* rem) {
+__device__ __forceinline__ void fill_spans(const EvalJob& J, const void* carry, void* out, int shift, void* rem) {
     __shared__ uint32_t buf[2][9][256];
     const Fr z = J.z;
     const uint32_t tid = threadIdx.x;
@@ -210,6 +228,18 @@ __global__ void __launch_bounds__(256) k_fill_spans(const EvalJob J, const void*
         if (o >= 0) fr_store(out, (size_t)o, q);
     });
     if (rem && blockIdx.x == 0 && tid == 0) fr_store(rem, 0, acc);         // Q_0 (an empty chunk 0 cannot occur: n >= 1)
+}
+__global__ void __launch_bounds__(256) k_fill_spans(const EvalJob J, const void* carry, void* out, int shift, void* rem) { fill_spans(J, carry, out, shift, rem); }
+// The array forms: the divisions of a batch, polynomials of ONE length at their own points.  k_span_carries_jobs: one block per job;
+// k_fill_spans_jobs: job blockIdx.y, span blockIdx.x, quotient y at out + y * out_stride elements.  partial and carry hold the jobs'
+// spans back to back (job y from jobs[y].first_block on), as k_eval_spans leaves them; carry == nullptr as above.
+__global__ void __launch_bounds__(256) k_span_carries_jobs(const EvalJob* jobs, const void* partial, void* carry) {
+    const EvalJob& J = jobs[blockIdx.x];
+    span_carries(J, (const char*)partial + (size_t)J.first_block * 32, (char*)carry + (size_t)J.first_block * 32, nullptr);
+}
+__global__ void __launch_bounds__(256) k_fill_spans_jobs(const EvalJob* jobs, const void* carry, void* out, size_t out_stride, int shift) {
+    const EvalJob& J = jobs[blockIdx.y];
+    fill_spans(J, carry ? (const char*)carry + (size_t)J.first_block * 32 : nullptr, (char*)out + blockIdx.y * out_stride * 32, shift, nullptr);
 }
 
 }  // namespace
@@ -354,13 +384,9 @@ extern "C" int zk_poly_divide_by_linear_dev(zk_ctx* ctx, const void* coeffs_dev,
     ZK_API_END
 }
 
-extern "C" int zk_poly_divide_by_vanishing_dev(zk_ctx* ctx, const void* coeffs_dev, size_t n, uint32_t log_domain, void* q_dev, void* r_dev) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !r_dev || (n && !coeffs_dev) || log_domain > 28) return ZK_ERR_ARG;
-    const size_t N = (size_t)1 << log_domain;
-    const size_t nq = n > N ? n - N : 0;
-    if (nq && !q_dev) return ZK_ERR_ARG;
-    if (coeffs_dev == q_dev || coeffs_dev == r_dev) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_poly_divide_by_vanishing_dev: outputs must not alias the input");
+namespace {
+// how zk_poly_divide_by_vanishing cuts the m = ceil(n / N) rows: G groups of R
+void divv_geometry(size_t n, size_t N, size_t* R_out, size_t* G_out) {
     size_t m = (n + N - 1) / N;
     if (m == 0) m = 1;
     size_t G = 65536 / N;
@@ -376,6 +402,20 @@ extern "C" int zk_poly_divide_by_vanishing_dev(zk_ctx* ctx, const void* coeffs_d
     }
     const size_t R = (m + G - 1) / G;
     G = (m + R - 1) / R;
+    *R_out = R;
+    *G_out = G;
+}
+}  // namespace
+
+extern "C" int zk_poly_divide_by_vanishing_dev(zk_ctx* ctx, const void* coeffs_dev, size_t n, uint32_t log_domain, void* q_dev, void* r_dev) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !r_dev || (n && !coeffs_dev) || log_domain > 28) return ZK_ERR_ARG;
+    const size_t N = (size_t)1 << log_domain;
+    const size_t nq = n > N ? n - N : 0;
+    if (nq && !q_dev) return ZK_ERR_ARG;
+    if (coeffs_dev == q_dev || coeffs_dev == r_dev) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_poly_divide_by_vanishing_dev: outputs must not alias the input");
+    size_t R, G;
+    divv_geometry(n, N, &R, &G);
     void* sums = nullptr;
     if (G > 1) {
         ZK_TRY(zk_scratch(ctx, "poly_divv_sums", G * N * 32, &sums));
@@ -385,6 +425,58 @@ extern "C" int zk_poly_divide_by_vanishing_dev(zk_ctx* ctx, const void* coeffs_d
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
     ZK_API_END
+}
+
+size_t zk_poly_divv_sums_elems(size_t n, uint32_t log_domain) {
+    size_t R, G;
+    divv_geometry(n, (size_t)1 << log_domain, &R, &G);
+    return G > 1 ? G << log_domain : 0;
+}
+
+int zk_poly_divide_by_vanishing_strided(zk_ctx* ctx, const void* c, size_t c_stride, size_t n, uint32_t log_domain, size_t count, void* q, size_t q_stride,
+                                        void* rem, size_t rem_stride, void* sums) {
+    const size_t N = (size_t)1 << log_domain, nq = n > N ? n - N : 0;
+    if (!c || !rem || !count || count > 65535 || (nq && !q) || c_stride < n || q_stride < nq || rem_stride < N) return ZK_ERR_ARG;
+    size_t R, G;
+    divv_geometry(n, N, &R, &G);
+    if (G > 1 && !sums) return ZK_ERR_ARG;
+    const DivvStrides st{c_stride, q_stride, rem_stride};
+    const dim3 grid(zk_grid(G * N, 256), (unsigned)count);
+    if (G > 1) hipLaunchKernelGGL(k_divv_sums_strided, grid, 256, 0, ctx->stream, c, st, n, N, R, G, sums);
+    hipLaunchKernelGGL(k_divv_fill_strided, grid, 256, 0, ctx->stream, c, st, n, N, R, G, (const void*)(G > 1 ? sums : nullptr), q, nq, rem);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+
+size_t zk_poly_divlin_spans(size_t n) { return (n + EV_SPAN - 1) / EV_SPAN; }
+size_t zk_poly_divlin_job_bytes() { return sizeof(EvalJob); }
+
+int zk_poly_divide_by_linear_strided(zk_ctx* ctx, const void* c, size_t c_stride, size_t n, const Fr* z_int, size_t count, void* q, size_t q_stride,
+                                     void* spans, ZkStage* stage) {
+    if (!c || !z_int || !q || !stage || n < 2 || !count || count > 65535 || c_stride < n || q_stride < n - 1) return ZK_ERR_ARG;
+    std::vector<EvalJob> jobs(count);
+    uint32_t blocks = 0;
+    for (size_t k = 0; k < count; k++) {
+        eval_job_fill(jobs[k], (const char*)c + k * c_stride * 32, n, blocks, HF{z_int[k]});
+        blocks += jobs[k].nblocks;
+    }
+    const uint32_t per = jobs[0].nblocks;
+    if (per > 1 && !spans) return ZK_ERR_ARG;
+    const void* jd;
+    ZK_TRY(stage->put(jobs.data(), count * sizeof(EvalJob), &jd));
+    const EvalJob* jdev = (const EvalJob*)jd;
+    const dim3 grid(per, (unsigned)count);
+    if (per == 1) {
+        hipLaunchKernelGGL(k_fill_spans_jobs, grid, 256, 0, ctx->stream, jdev, (const void*)nullptr, q, q_stride, -1);
+    } else {
+        void* partial = spans;
+        void* carry = (char*)spans + (size_t)blocks * 32;
+        hipLaunchKernelGGL(k_eval_spans, blocks, 256, 0, ctx->stream, jdev, (uint32_t)count, partial);
+        hipLaunchKernelGGL(k_span_carries_jobs, (unsigned)count, 256, 0, ctx->stream, jdev, (const void*)partial, carry);
+        hipLaunchKernelGGL(k_fill_spans_jobs, grid, 256, 0, ctx->stream, jdev, (const void*)carry, q, q_stride, -1);
+    }
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
 }
 
 extern "C" int zk_poly_mul_dev(zk_ctx* ctx, const void* a_dev, size_t na, const void* b_dev, size_t nb, void* out_dev) {

@@ -65,6 +65,27 @@ k_spmv_multi(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff
     }
 }
 
+// The same for count vectors, one per blockIdx.y: z_k at z + k * z_stride elements, the product at out + k * out_stride (the batch
+// Marlin prover's A z, B z and M^T r: rows of a few entries, so a row's indices are re-read per proof from the cache)
+__global__ void __launch_bounds__(256)
+k_spmv_strided(const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coeff, int all_one, const void* z, size_t z_stride, size_t nc,
+               size_t out_len, void* out, size_t out_stride) {
+    const char* zk = (const char*)z + blockIdx.y * z_stride * 32;
+    char* ok = (char*)out + blockIdx.y * out_stride * 32;
+    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < out_len; r += (size_t)gridDim.x * blockDim.x) {
+        Fr acc = fp_zero<FrParams>();
+        if (r < nc) {
+            uint32_t lo = row_ptr[r], hi = row_ptr[r + 1];
+            for (uint32_t k = lo; k < hi; k++) {
+                Fr v = fr_load(zk, col[k]);
+                if (!all_one) v = fr_mul(v, fr_load(coeff, k));
+                acc = fr_add(acc, v);
+            }
+        }
+        fr_store(ok, r, acc);
+    }
+}
+
 int upload_mat(zk_ctx* ctx, zk_r1cs::Mat& m, size_t nc, const uint32_t* rp, const uint32_t* col, const zk_fr* coeff) {
     m.nnz = rp[nc];
     m.h_row_ptr.assign(rp, rp + nc + 1);
@@ -115,6 +136,16 @@ extern "C" int zk_r1cs_matvec_dev(zk_ctx* ctx, const zk_r1cs* r, int which, cons
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
     ZK_API_END
+}
+
+int zk_r1cs_matvec_strided(zk_ctx* ctx, const zk_r1cs* r, int which, const void* z, size_t z_stride, size_t count, void* out, size_t out_stride,
+                           size_t out_len) {
+    if (!r || !z || !out || which < 0 || which > 2 || !count || count > 65535 || out_len < r->nc || out_stride < out_len) return ZK_ERR_ARG;
+    const auto& m = r->m[which];
+    hipLaunchKernelGGL(k_spmv_strided, dim3(zk_grid(out_len, 256), (unsigned)count), 256, 0, ctx->stream, m.row_ptr, m.col, m.coeff, m.all_one ? 1 : 0, z,
+                       z_stride, r->nc, out_len, out, out_stride);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
 }
 
 extern "C" uint32_t zk_r1cs_domain_log(const zk_r1cs* r) { return r ? r->log_d : 0; }

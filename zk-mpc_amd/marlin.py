@@ -518,6 +518,25 @@ def prove_native(keys, assignment_dev: DevBuf, zk_rng, mask_on_device: bool = Fa
     return bytes(out[:n.value])
 
 
+def prove_native_batch(keys, assignments_dev: DevBuf, z_stride: int, rngs, mask_on_device: bool = False) -> list:
+    """len(rngs) proofs of one index in one call (zk_marlin_prove_batch, csrc/marlin_prove_batch.hip): proof k is the bytes
+    prove_native returns for the padded assignment at assignments_dev + 32 * k * z_stride under rngs[k], which is left as that call
+    leaves it.  keys: an IndexKeys or a NativeIndex, as for prove_native.  Returns the proofs' bytes in order."""
+    import ctypes as C
+    srs = keys.srs
+    ctx = keys.ctx if isinstance(keys, NativeIndex) else keys.index.ctx
+    d, _keep = native_index(keys)
+    count = len(rngs)
+    slot = ctx.lib.zk_marlin_proof_max_size()
+    out = (C.c_uint8 * (slot * max(count, 1)))()
+    lens = (C.c_size_t * max(count, 1))()
+    handles = (C.c_void_p * max(count, 1))(*[r.h for r in rngs])
+    ctx._ck(ctx.lib.zk_marlin_prove_batch(ctx.h, C.byref(d), srs.powers_g.h, srs.powers_gamma_g.h, count, C.c_void_p(assignments_dev.ptr), z_stride,
+                                          handles, int(mask_on_device), out, slot, lens))
+    raw = bytes(out)
+    return [raw[k * slot:k * slot + lens[k]] for k in range(count)]
+
+
 # ---- Marlin::verify (csrc/marlin_verify.hip) --------------------------------------------------------------------------------------
 
 class VerifierKey:
