@@ -917,6 +917,45 @@ int zk_marlin_prove_shared_spdz(zk_ctx* ctx, const zk_marlin_index* index, const
                                 const void* const z_lanes_dev[2], zk_rng* zk_rng, int mask_on_device, const void* const tx_lanes[2],
                                 const void* const ty_lanes[2], const void* const tz_lanes[2], const zk_net_vtable* net,
                                 uint8_t* proof_out, size_t cap, size_t* proof_len, uint64_t* bytes_sent);
+/* count collaborative proofs of ONE index in one call, with the exchanges of ONE proof per chunk.  Proof k is byte for byte what
+ * zk_marlin_prove_shared[_spdz] writes at this party for (z_k, rngs[k], triple k, the same mask_on_device), rngs[k] is left as that call
+ * leaves it, and every party writes the same bytes.  z_k sits at z + 32 k z_stride in each lane; tx / ty / tz hold count |MUL| elements
+ * per lane, proof k's triple at k |MUL| (MUL: the multiplication domain of round 2), all NULL for the dummy source.  Proof k goes to
+ * proofs_out + k slot (slot >= zk_marlin_proof_max_size()), its length to proof_lens[k].  count == 1 forwards to the single call.  Every
+ * party must pass the same count, and the same ZK_MARLIN_BATCH_CHUNK if it sets one.
+ * The plan: behind the argument checks each party computes how many proofs its device holds at once -- zk_marlin_prove_batch's rule with
+ * the lanes and the Beaver product's scratch, (2 lanes + 3) C |MUL| elements; 0: not even one -- and publishes that number as 8
+ * little-endian bytes in ONE all_gather_bytes exchange; all proceed in chunks of the minimum, and a minimum of 0 makes every party
+ * return ZK_ERR_NOMEM before any device work.  The call's buffers are allocated before that exchange and a party that fails there
+ * publishes 0 (and returns its own error), so no party fails alone behind it.  Parties that share ONE device size their bounds against
+ * the same free memory: cap the chunk with ZK_MARLIN_BATCH_CHUNK there.  A call is 1 + chunks x (the single call's exchanges) exchanges, and *bytes_sent is
+ * count x the single call's figure plus these 8 bytes.
+ * The exchanges of a chunk of C proofs, in order (under SPDZ each is followed by its MAC exchange of the same layout; open_sum_fr_dev
+ * carries the vector opens, all_gather_bytes the small ones):
+ *   1. vector, C num_instance elements: the instance parts, proof after proof (absent with num_instance == 1)
+ *   2. small, G1 x 4C: the commitments of round 1 -- per proof w, z_a, z_b, mask_poly
+ *   3. vector, C |MUL| elements: the masked Beaver operand x + a, proof after proof;  4. the same for y + b
+ *   5. vector, C elements: the constant terms of the outer sum-check's remainders, proof after proof
+ *   6. small, G1 x 3C: the commitments of round 2 -- per proof g_1, g_1 shifted to its degree bound, h_1 (round 3 opens nothing)
+ *   7. small, scalars x 2C: the evaluations -- per proof z_b(beta), g_1(beta)
+ *   8. small, scalars x C then G1 x C: per proof random_v at beta; per proof the opening witness at beta (no scalars at all if no
+ *      proof's combination is hiding; hiding for some proofs of a chunk only is ZK_ERR_STATE)
+ * A small open's message is its scalars (4 words each) then its G1 points (18 words each, zk_g1_projective), each kind ordered by
+ * proof and within a proof as listed (csrc/marlin_shared_plan.hpp states this layout as code).
+ * Errors are the same at every party: the zero test of the outer sum-check is decided from the opened values, and the smallest k (counted
+ * over the whole call) with a non-zero constant term fails the call with ZK_ERR_STATE and the single prover's text behind "proof <k>: ",
+ * right behind exchange 5 of its chunk; the inner sum-check, which is public, is reported the same way; the divisibility of w by v_X
+ * cannot be tested over shares, as in the single call.  A failed MAC check of any open is ZK_ERR_MAC.  The proofs are held in memory of
+ * the call and written behind the last chunk: on any error proofs_out and proof_lens are untouched, the streams are drained and the
+ * context stays usable.  ZK_ERR_ARG: the checks of zk_marlin_prove_batch, a triple given in part, a missing lane. */
+int zk_marlin_prove_shared_batch(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
+                                 size_t count, const void* z_share_dev, size_t z_stride, zk_rng* const* rngs, int mask_on_device,
+                                 const void* tx, const void* ty, const void* tz, const zk_net_vtable* net,
+                                 uint8_t* proofs_out, size_t slot, size_t* proof_lens, uint64_t* bytes_sent);
+int zk_marlin_prove_shared_spdz_batch(zk_ctx* ctx, const zk_marlin_index* index, const zk_bases* powers_g, const zk_bases* powers_gamma_g,
+                                      size_t count, const void* const z_lanes_dev[2], size_t z_stride, zk_rng* const* rngs, int mask_on_device,
+                                      const void* const tx_lanes[2], const void* const ty_lanes[2], const void* const tz_lanes[2],
+                                      const zk_net_vtable* net, uint8_t* proofs_out, size_t slot, size_t* proof_lens, uint64_t* bytes_sent);
 
 /* ---- the trait surface for the COLLABORATIVE element types, on the caller's own slices (rows a6, a7, a8, a11) ----------------
  * Under E = MpcPairingEngine the unchanged create_proof (src/groth16.rs:68-183,240-306) calls the same four dispatch points with

@@ -279,6 +279,8 @@ PROTOTYPES = {
     "zk_marlin_prove_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _SZ, _P, _I, _P, _SZ, _P]),
     "zk_marlin_prove_shared": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "zk_marlin_prove_shared_spdz": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "zk_marlin_prove_shared_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _SZ, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "zk_marlin_prove_shared_spdz_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _SZ, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "zk_she_vec_op_dev": (_I, [_P, _I, _P, _P, _P, _SZ]),
     "zk_she_vec_scale_dev": (_I, [_P, _P, _P, _P, _SZ]),
     "zk_she_negacyclic_mul_dev": (_I, [_P, _P, _P, _P, _SZ, _SZ]),

@@ -85,23 +85,26 @@ int zk_poly_divide_by_linear_strided(zk_ctx* ctx, const void* c, size_t c_stride
                                      void* spans, ZkStage* stage);
 // marlin_batch.hip: the element-wise kernels of the Marlin rounds over count vectors (strides in elements; n items each), on
 // ctx->stream, no wait.  tab: the step's per-proof constants on the device, proof k's row at tab + k * ts entries (devutil.cuh: FrK,
-// internal form unless a kernel says otherwise).
+// internal form unless a kernel says otherwise).  The kernels that read a row of tab or a public per-proof operand take `proofs`
+// for a launch over shares: count = lanes * proofs vectors, lane after lane, vector v of proof v mod proofs (0: count proofs, one vector each).
 namespace zk { struct FrK; }
 int zk_b_copy(zk_ctx* ctx, void* dst, size_t ds, const void* src, size_t ss, size_t n, size_t count);
 int zk_b_zero(zk_ctx* ctx, void* dst, size_t ds, size_t n, size_t count);
 int zk_b_op(zk_ctx* ctx, int op, const void* a, size_t sa, const void* b, size_t sb, void* out, size_t so, size_t n, size_t count);
-int zk_b_scale(zk_ctx* ctx, const void* a, size_t sa, const zk::FrK* tab, size_t ts, void* out, size_t so, size_t n, size_t count);      // a_k * tab_k[0]
+int zk_b_scale(zk_ctx* ctx, const void* a, size_t sa, const zk::FrK* tab, size_t ts, void* out, size_t so, size_t n, size_t count,
+               size_t proofs = 0);      // a_k * tab_k[0]
 int zk_b_gather(zk_ctx* ctx, const void* src, size_t ss, const uint32_t* idx, size_t n, void* out, size_t so, size_t count);
 // out_k = p_k + r_k[0] (X^n - 1): n + 1 coefficients
 int zk_b_blind(zk_ctx* ctx, const void* p, size_t sp, size_t n, const void* r, size_t sr, void* out, size_t so, size_t count);
 // out_k[i] = tab_k[0] - e[i]; tab_k[0]: the bits of the constant's external form
 int zk_b_const_minus(zk_ctx* ctx, const zk::FrK* tab, size_t ts, const void* e, size_t n, void* out, size_t so, size_t count);
-// zk_fr_outer_q1_launch with tab_k = eta_a, eta_b, eta_c; every vector `stride` elements apart
+// zk_fr_outer_q1_launch with tab_k = eta_a, eta_b, eta_c; every vector `stride` elements apart (proofs: rp and tp are one vector per proof)
 int zk_b_outer_q1(zk_ctx* ctx, const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp, size_t stride,
-                  const zk::FrK* tab, size_t ts, void* out, size_t n, size_t count);
+                  const zk::FrK* tab, size_t ts, void* out, size_t n, size_t count, size_t proofs = 0);
 // zk_fr_lincomb_launch with tab_k[t] = the coefficient of term t (at most 16 terms); strides[t] = 0: one vector for every proof
+// (proofs: bit t of per_proof says that term t is one vector per proof, not one per lane and proof)
 int zk_b_lincomb(zk_ctx* ctx, int terms, const void* const* ps, const size_t* strides, const size_t* ns, const zk::FrK* tab, size_t ts, void* out, size_t so,
-                 size_t n_out, size_t count);
+                 size_t n_out, size_t count, size_t proofs = 0, unsigned per_proof = 0);
 // round 3 (marlin.hip's zk_marlin_round3_f_evals_dev in its two halves around the inversion, and _ab_evals_dev): one row of
 // ZK_B_R3_ROW constants per proof, filled by zk_b_round3_row (alpha, beta, eta, vv = v_H(alpha) v_H(beta): internal form);
 // den: count * 3 k_size elements

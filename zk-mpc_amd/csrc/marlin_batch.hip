@@ -25,6 +25,12 @@ namespace {
 __device__ __forceinline__ const char* vec_of(const void* base, size_t stride) { return (const char*)base + blockIdx.y * stride * 32; }
 __device__ __forceinline__ char* vec_of(void* base, size_t stride) { return (char*)base + blockIdx.y * stride * 32; }
 __device__ __forceinline__ Fr tab_of(const FrK* tab, size_t tab_stride, int k) { return frk(tab[blockIdx.y * tab_stride + k]); }
+// The forms over shares (LANES = true): a launch covers lanes * proofs vectors, lane after lane (marlin_prove_batch.hip lays the lanes of a
+// witness-dependent region next to each other at one stride), and vector y reads the constants' row and the public operands of proof
+// y mod proofs.  LANES = false is the plain batch's kernel: y is the proof.
+template <bool LANES> __device__ __forceinline__ unsigned proof_of(unsigned proofs) { return LANES ? blockIdx.y % proofs : blockIdx.y; }
+__device__ __forceinline__ const char* vec_at(const void* base, size_t stride, unsigned y) { return (const char*)base + y * stride * 32; }
+__device__ __forceinline__ Fr tab_at(const FrK* tab, size_t tab_stride, unsigned y, int k) { return frk(tab[y * tab_stride + k]); }
 
 __global__ void __launch_bounds__(256) k_b_copy(void* dst, size_t ds, const void* src, size_t ss, size_t n) {
     const uint4* s = reinterpret_cast<const uint4*>(vec_of(src, ss));
@@ -48,8 +54,9 @@ __global__ void __launch_bounds__(256) k_b_op(const void* a, size_t sa, const vo
     }
 }
 // out_y = a_y * tab_y[0] (the constant in internal form)
-__global__ void __launch_bounds__(256) k_b_scale(const void* a, size_t sa, const FrK* tab, size_t ts, void* out, size_t so, size_t n) {
-    const Fr kk = tab_of(tab, ts, 0);
+template <bool LANES>
+__global__ void __launch_bounds__(256) k_b_scale(const void* a, size_t sa, const FrK* tab, size_t ts, void* out, size_t so, size_t n, unsigned proofs) {
+    const Fr kk = tab_at(tab, ts, proof_of<LANES>(proofs), 0);
     const char* av = vec_of(a, sa);
     char* ov = vec_of(out, so);
     ZK_B_LOOP(i, n) fr_store(ov, i, fr_mul(fr_load(av, i), kk));
@@ -79,12 +86,15 @@ __global__ void __launch_bounds__(256) k_b_const_minus(const FrK* tab, size_t ts
     char* ov = vec_of(out, so);
     ZK_B_LOOP(i, n) fr_store(ov, i, fr_sub(c, fr_load(e, i)));
 }
-// k_outer_q1 with tab_y = eta_a, eta_b, eta_c; the six vectors of a proof stride elements apart each
+// k_outer_q1 with tab_y = eta_a, eta_b, eta_c; the six vectors of a proof stride elements apart each.  LANES: r(alpha, X) and t are
+// public, one vector per proof
+template <bool LANES>
 __global__ void __launch_bounds__(256) k_b_outer_q1(const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp,
-                                                    size_t stride, const FrK* tab, size_t ts, void* out, size_t n) {
-    const Fr fa = tab_of(tab, ts, 0), fb = tab_of(tab, ts, 1), fc = tab_of(tab, ts, 2);
-    const char *sv = vec_of(s, stride), *av = vec_of(a, stride), *bv = vec_of(b, stride), *zv = vec_of(z, stride), *rv = vec_of(rp, stride),
-               *tv = vec_of(tp, stride);
+                                                    size_t stride, const FrK* tab, size_t ts, void* out, size_t n, unsigned proofs) {
+    const unsigned pr = proof_of<LANES>(proofs);
+    const Fr fa = tab_at(tab, ts, pr, 0), fb = tab_at(tab, ts, pr, 1), fc = tab_at(tab, ts, pr, 2);
+    const char *sv = vec_of(s, stride), *av = vec_of(a, stride), *bv = vec_of(b, stride), *zv = vec_of(z, stride), *rv = vec_at(rp, stride, pr),
+               *tv = vec_at(tp, stride, pr);
     char* ov = vec_of(out, stride);
     ZK_B_LOOP(i, n) {
         Fr t = fr_add(fr_add(fr_mul(fr_load(sv, i), fc), fr_mul(fr_load(av, i), fa)), fr_mul(fr_load(bv, i), fb));
@@ -93,15 +103,19 @@ __global__ void __launch_bounds__(256) k_b_outer_q1(const void* s, const void* a
         fr_store(ov, i, fr_sub(t, u));
     }
 }
-// k_lincomb with tab_y[t] = the coefficient of term t; a term with stride 0 is one vector for every proof (an index oracle)
+// k_lincomb with tab_y[t] = the coefficient of term t; a term with stride 0 is one vector for every proof (an index oracle).  LANES: a
+// term whose bit is set in per_proof is public, one vector per proof (the leader's public oracles in a shared combination)
 constexpr int B_LINCOMB_MAX = 16;
-struct BLinComb { const void* p[B_LINCOMB_MAX]; size_t stride[B_LINCOMB_MAX]; size_t n[B_LINCOMB_MAX]; int terms; };
-__global__ void __launch_bounds__(256) k_b_lincomb(BLinComb c, const FrK* tab, size_t ts, void* out, size_t so, size_t n_out) {
+struct BLinComb { const void* p[B_LINCOMB_MAX]; size_t stride[B_LINCOMB_MAX]; size_t n[B_LINCOMB_MAX]; int terms; unsigned per_proof; };
+template <bool LANES>
+__global__ void __launch_bounds__(256) k_b_lincomb(BLinComb c, const FrK* tab, size_t ts, void* out, size_t so, size_t n_out, unsigned proofs) {
+    const unsigned pr = proof_of<LANES>(proofs);
     char* ov = vec_of(out, so);
     ZK_B_LOOP(i, n_out) {
         Fr acc = fp_zero<FrParams>();
         for (int t = 0; t < c.terms; t++)
-            if (i < c.n[t]) acc = fr_add(acc, fr_mul(fr_load(vec_of(c.p[t], c.stride[t]), i), tab_of(tab, ts, t)));
+            if (i < c.n[t])
+                acc = fr_add(acc, fr_mul(fr_load(vec_at(c.p[t], c.stride[t], LANES && (c.per_proof >> t & 1) ? pr : blockIdx.y), i), tab_at(tab, ts, pr, t)));
         fr_store(ov, i, acc);
     }
 }
@@ -199,10 +213,13 @@ int zk_b_op(zk_ctx* ctx, int op, const void* a, size_t sa, const void* b, size_t
     }
     return launched(ctx);
 }
-int zk_b_scale(zk_ctx* ctx, const void* a, size_t sa, const FrK* tab, size_t ts, void* out, size_t so, size_t n, size_t count) {
+// proofs = 0: count proofs, one vector each; otherwise count = lanes * proofs vectors, lane after lane
+int zk_b_scale(zk_ctx* ctx, const void* a, size_t sa, const FrK* tab, size_t ts, void* out, size_t so, size_t n, size_t count, size_t proofs) {
     dim3 g;
     if (!grid_of(n, count, &g)) return n ? (int)ZK_ERR_ARG : (int)ZK_OK;
-    hipLaunchKernelGGL(k_b_scale, g, 256, 0, ctx->stream, a, sa, tab, ts, out, so, n);
+    if (proofs && count % proofs) return ZK_ERR_ARG;
+    if (proofs) hipLaunchKernelGGL(k_b_scale<true>, g, 256, 0, ctx->stream, a, sa, tab, ts, out, so, n, (unsigned)proofs);
+    else hipLaunchKernelGGL(k_b_scale<false>, g, 256, 0, ctx->stream, a, sa, tab, ts, out, so, n, 0u);
     return launched(ctx);
 }
 int zk_b_gather(zk_ctx* ctx, const void* src, size_t ss, const uint32_t* idx, size_t n, void* out, size_t so, size_t count) {
@@ -224,20 +241,23 @@ int zk_b_const_minus(zk_ctx* ctx, const FrK* tab, size_t ts, const void* e, size
     return launched(ctx);
 }
 int zk_b_outer_q1(zk_ctx* ctx, const void* s, const void* a, const void* b, const void* z, const void* rp, const void* tp, size_t stride,
-                  const FrK* tab, size_t ts, void* out, size_t n, size_t count) {
+                  const FrK* tab, size_t ts, void* out, size_t n, size_t count, size_t proofs) {
     dim3 g;
-    if (!grid_of(n, count, &g) || stride < n) return ZK_ERR_ARG;
-    hipLaunchKernelGGL(k_b_outer_q1, g, 256, 0, ctx->stream, s, a, b, z, rp, tp, stride, tab, ts, out, n);
+    if (!grid_of(n, count, &g) || stride < n || (proofs && count % proofs)) return ZK_ERR_ARG;
+    if (proofs) hipLaunchKernelGGL(k_b_outer_q1<true>, g, 256, 0, ctx->stream, s, a, b, z, rp, tp, stride, tab, ts, out, n, (unsigned)proofs);
+    else hipLaunchKernelGGL(k_b_outer_q1<false>, g, 256, 0, ctx->stream, s, a, b, z, rp, tp, stride, tab, ts, out, n, 0u);
     return launched(ctx);
 }
 int zk_b_lincomb(zk_ctx* ctx, int terms, const void* const* ps, const size_t* strides, const size_t* ns, const FrK* tab, size_t ts, void* out, size_t so,
-                 size_t n_out, size_t count) {
+                 size_t n_out, size_t count, size_t proofs, unsigned per_proof) {
     dim3 g;
-    if (terms < 1 || terms > B_LINCOMB_MAX || !grid_of(n_out, count, &g) || so < n_out) return ZK_ERR_ARG;
+    if (terms < 1 || terms > B_LINCOMB_MAX || !grid_of(n_out, count, &g) || so < n_out || (proofs && count % proofs)) return ZK_ERR_ARG;
     BLinComb c{};
     c.terms = terms;
+    c.per_proof = per_proof;
     for (int t = 0; t < terms; t++) { c.p[t] = ps[t]; c.stride[t] = strides[t]; c.n[t] = std::min(ns[t], n_out); }
-    hipLaunchKernelGGL(k_b_lincomb, g, 256, 0, ctx->stream, c, tab, ts, out, so, n_out);
+    if (proofs) hipLaunchKernelGGL(k_b_lincomb<true>, g, 256, 0, ctx->stream, c, tab, ts, out, so, n_out, (unsigned)proofs);
+    else hipLaunchKernelGGL(k_b_lincomb<false>, g, 256, 0, ctx->stream, c, tab, ts, out, so, n_out, 0u);
     return launched(ctx);
 }
 

@@ -450,7 +450,7 @@ struct Marlin : MarlinArgs {
             ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, e_s[l], MUL.size, H.log, hq[l], hr[l]));
         }
         // the outer sum-check's zero test (prover.rs:547-550): over shares the constant term is opened
-        const char* const not_zero = "zk_marlin_prove: outer sum-check: the sum over H is not zero (unsatisfied constraint system)";
+        const char* const not_zero = OUTER_NOT_ZERO;
         char* zo = nullptr;
         if (!shared) ZK_TRY(check_later(hr[0], 1, not_zero));
         else ZK_TRY(open_dev(hr, 1, "zero", &zo));
@@ -489,7 +489,7 @@ struct Marlin : MarlinArgs {
         char* h2q = P.dev("h2_q", B.size - K.size); char* h2r = P.dev("h2_r", K.size);
         ZK_TRY(P.rc);
         ZK_TRY(zk_poly_divide_by_vanishing_dev(ctx, a_ev, B.size, K.log, h2q, h2r));
-        ZK_TRY(check_later(h2r, K.size, "zk_marlin_prove: inner sum-check: a - b f is not divisible by v_K"));
+        ZK_TRY(check_later(h2r, K.size, INNER_NOT_DIVISIBLE));
         for (int l = 0; l < LANES; l++) PL[l].polys[O_H_2] = Poly{h2q, B.size - K.size};
         laps.lap("polys");
         ZK_TRY(commit_round(3));

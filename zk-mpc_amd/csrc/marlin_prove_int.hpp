@@ -1,5 +1,5 @@
 // marlin_prove_int.hpp -- what the Marlin provers share (marlin_prove.hip: one proof, plain or over shares; marlin_prove_batch.hip:
-// count plain proofs of one index in lock-step): the oracle table, the host halves of the polynomial commitment's openings, the
+// count proofs of one index in lock-step, plain or over shares): the oracle table, the sum-checks' error texts, the host halves of the polynomial commitment's openings, the
 // entry points' argument checks, the transcript's seed, the query set with its linear combinations, and Proof::serialize.
 // Everything here is host code; nothing in it depends on how many proofs are in flight.
 #pragma once
@@ -52,6 +52,10 @@ inline std::vector<Oracle> round_oracles(int round) {
     return v;
 }
 inline bool oracle_bounded(Oracle o) { return ORACLES[o].bound != Bound::None; }
+
+// The sum-checks' failures, as every prover words them (a batch puts "proof <k>: " in front)
+constexpr const char* OUTER_NOT_ZERO = "zk_marlin_prove: outer sum-check: the sum over H is not zero (unsatisfied constraint system)";
+constexpr const char* INNER_NOT_DIVISIBLE = "zk_marlin_prove: inner sum-check: a - b f is not divisible by v_K";
 
 inline HF host_eval(const std::vector<HF>& c, const HF& x) {
     HF acc = HF::zero();

@@ -662,6 +662,14 @@ class Party:
         returns Proof::serialize's bytes -- the same bytes as tests/pyseq/mpc_seq.py::Party.marlin_prove_full(...).serialize()."""
         return _marlin_prove_native(self, keys, [z_share], zk_rng, triple, mask_on_device)
 
+    def marlin_prove_shared_batch_native(self, keys, z_shares, z_stride, rngs, triple=None, mask_on_device=False) -> list:
+        """len(rngs) collaborative proofs of ONE index as ONE library call with the exchanges of one proof per chunk
+        (zk_marlin_prove_shared_batch).  z_shares: device buffer of the shares of the padded assignments, assignment k at
+        k * z_stride elements; rngs[k]: this party's generator for proof k; triple: three device pointers of count * |MUL| Beaver
+        shares each (proof k's at k * |MUL|), or None for dummy triples.  Every party must pass the same count.  Returns the proofs,
+        proof k the bytes of marlin_prove_shared_native for (z_k, rngs[k], triple_k)."""
+        return _marlin_prove_batch_native(self, keys, [z_shares], z_stride, rngs, triple, mask_on_device, None)
+
 # ------------------------------------------------------------------------------------------------
 # SPDZ (malicious-majority backend): every share carries a MAC share; opens are MAC-checked
 # ------------------------------------------------------------------------------------------------
@@ -852,6 +860,13 @@ class SpdzParty(Party):
         (z, z_mac)) device pointers or None.  A failed MAC check raises MacCheckError."""
         return _marlin_prove_native(self, keys, list(z_share), zk_rng, triple, mask_on_device)
 
+    def marlin_prove_shared_spdz_batch_native(self, keys, z_shares, z_stride, rngs, triple=None, mask_on_device=False, out=None) -> list:
+        """The same over SPDZ shares (zk_marlin_prove_shared_spdz_batch): z_shares = (share, MAC) device buffers of the count
+        assignments each, triple = ((x, x_mac), (y, y_mac), (z, z_mac)) device pointers of count * |MUL| elements or None.  out: a
+        uint8 array of count * zk_marlin_proof_max_size() bytes to write the proofs to, proof k at k * zk_marlin_proof_max_size() (a
+        failed MAC check -- MacCheckError -- leaves it as it was).  Returns the list of the proofs' bytes."""
+        return _marlin_prove_batch_native(self, keys, list(z_shares), z_stride, rngs, triple, mask_on_device, out)
+
 
 def _marlin_prove_native(party, keys, z_lanes, zk_rng, triple, mask_on_device):
     import ctypes as C
@@ -882,3 +897,40 @@ def _marlin_prove_native(party, keys, z_lanes, zk_rng, triple, mask_on_device):
     ctx._ck(rc)
     party.bytes_sent += int(sent.value)
     return bytes(out[:n.value])
+
+
+def _marlin_prove_batch_native(party, keys, z_lanes, z_stride, rngs, triple, mask_on_device, out):
+    import ctypes as C
+    from . import marlin as DM
+    ctx = party.be.ctx
+    srs = keys.srs
+    d, _keep_index = DM.native_index(keys)
+    vt, errors, _keep = party._net_vtable()
+    net = C.byref(vt) if party.net.n > 1 else None
+    count = len(rngs)
+    slot = ctx.lib.zk_marlin_proof_max_size()
+    if out is None:
+        out = np.zeros(max(count, 1) * slot, dtype=np.uint8)
+    if out.dtype != np.uint8 or out.size < count * slot:
+        raise ValueError("marlin batch: out holds count * zk_marlin_proof_max_size() bytes")
+    lens, sent = (C.c_size_t * max(count, 1))(), C.c_uint64(0)
+    handles = (C.c_void_p * max(count, 1))(*[r.h for r in rngs])
+    ptr = lambda v: int(getattr(v, "ptr", v))
+    o = out.ctypes.data_as(C.c_void_p)
+    if len(z_lanes) == 1:
+        t = [C.c_void_p(ptr(x)) for x in triple] if triple is not None else [None, None, None]
+        rc = ctx.lib.zk_marlin_prove_shared_batch(ctx.h, C.byref(d), srs.powers_g.h, srs.powers_gamma_g.h, count, C.c_void_p(ptr(z_lanes[0])), z_stride,
+                                                  handles, int(mask_on_device), t[0], t[1], t[2], net, o, slot, lens, C.byref(sent))
+    else:
+        P2 = C.c_void_p * 2
+        lanes = lambda v: P2(ptr(v[0]), ptr(v[1]))
+        t = [lanes(triple[k]) for k in range(3)] if triple is not None else [None, None, None]
+        rc = ctx.lib.zk_marlin_prove_shared_spdz_batch(ctx.h, C.byref(d), srs.powers_g.h, srs.powers_gamma_g.h, count, lanes(z_lanes), z_stride,
+                                                       handles, int(mask_on_device), t[0], t[1], t[2], net, o, slot, lens, C.byref(sent))
+    if errors:
+        raise errors[0]
+    if rc == -5:
+        raise MacCheckError((ctx.lib.zk_last_error(ctx.h) or b"").decode())
+    ctx._ck(rc)
+    party.bytes_sent += int(sent.value)
+    return [out[k * slot:k * slot + lens[k]].tobytes() for k in range(count)]
