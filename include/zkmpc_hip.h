@@ -508,7 +508,7 @@ int zk_gt_mul(const zk_gt* a, const zk_gt* b, zk_gt* out);
  * inputs_per_proof public inputs (the instance without its leading 1; inputs_per_proof must be num_instance - 1 = the key's
  * gamma_abc_g1 length - 1); proofs_host: count x 192 bytes as the provers write them; ok[k] = 1 / 0.  A, B, C are decompressed on
  * the device; a proof whose bytes are not points of the curves gets ok = 0 (it is not an error of the call).  The prepared inputs
- * gamma_abc[0] + sum x_i gamma_abc[i] are one scalar-multiplication lane per proof, then 3 count Miller loops -- (A, B), (prepared,
+ * gamma_abc[0] + sum x_i gamma_abc[i] come from zk_groth16_prepare_inputs' kernel (below), then 3 count Miller loops -- (A, B), (prepared,
  * -gamma), (C, -delta) -- and count final exponentiations, each compared with e(alpha, beta), which is computed once per key and kept
  * on it.  No subgroup check on A, B, C (Proof::deserialize does one; so does zk_groth16_verify_batch_checked).  ZK_ERR_ARG: a key without verifying-key parts (zk_pk_upload:
  * its host view has no gamma), inputs_per_proof that does not match, an input that is not below r, a null pointer, count = 0. */
@@ -549,8 +549,7 @@ int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr* inputs, si
  *            when a point was rejected before the pairing
  * ZK_ERR_ARG: what zk_groth16_verify_batch refuses, a null coeffs, count + 3 above 2^22 (one Miller lane per proof and three for
  * the key).  The launches do not grow with count beyond the logarithmic re-launches of the two fold kernels.  The ninp + 2
- * full-width multiplications of key points run on the host's helper threads under the device work; a key with very many public
- * inputs would want a multi-vector MSM over gamma_abc instead, which is not built. */
+ * full-width multiplications of key points run on the host's helper threads under the device work. */
 int zk_groth16_verify_aggregate_coeffs(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                        const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
 /* The same arithmetic on the host: no device, no context (tests, O(1) batches). */
@@ -564,6 +563,53 @@ int zk_verify_aggregate_coeffs_from_seed(const uint8_t seed[32], size_t count, u
  * run to locate the bad proofs.  Also ZK_ERR_ARG for a null seed. */
 int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                 const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each);
+/* ---- the verifier's own key: arkworks' PreparedVerifyingKey resident on the device (csrc/groth16_vkey.hip) ------------------------
+ * A verifier has no proving key.  zk_vkey holds alpha, beta, gamma, delta, gamma_abc_g1 as a resident table, -gamma, -delta,
+ * e(alpha, beta) (prepare_verifying_key, arkworks/groth16/src/verifier.rs:9-16) and, for prepare_inputs, window multiples of every
+ * gamma_abc[j], j >= 1: m 16^w gamma_abc[j] for 64 windows and m = 1 .. 8, 48 KiB per public input, built at load in one launch.
+ * With them a prepared input costs at most 64 mixed additions per public input and no doubling.  The pk forms above are these forms
+ * on a zk_vkey the zk_pk owns (made by its first verification, freed with it): one implementation, the same verdicts.
+ *   zk_vkey_upload       from a host view; accepts exactly the keys zk_groth16_verify_host accepts and refuses a gamma_g2 at infinity
+ *   zk_vkey_deserialize  from the bytes zk_vk_serialize / zk_vkey_serialize / VerifyingKey::serialize[_uncompressed] write: alpha_g1 |
+ *                        beta_g2 | gamma_g2 | delta_g2 | u64 length | gamma_abc_g1.  Point bytes are held to THE RULE; truncated or
+ *                        trailing bytes or a length word that does not fit: ZK_ERR_ARG, no object
+ *   zk_vkey_from_pk      an independent copy of a resident proving key's verifying-key parts (ZK_ERR_ARG for a key without them)
+ * check_subgroup != 0: every point goes through the subgroup test (the tables on the device, single points of a host view on the
+ * host); a point outside is ZK_ERR_ARG with the part in zk_last_error.  After any failure *out is not written and nothing is left
+ * allocated. */
+typedef struct zk_vkey zk_vkey;
+int zk_vkey_upload(zk_ctx* ctx, const zk_vk_host* vk, int check_subgroup, zk_vkey** out);
+int zk_vkey_deserialize(zk_ctx* ctx, const uint8_t* bytes_host, size_t len, int compressed, int check_subgroup, zk_vkey** out);
+int zk_vkey_from_pk(zk_ctx* ctx, const zk_pk* pk, zk_vkey** out);
+size_t zk_vkey_serialized_size(const zk_vkey* vkey, int compressed);
+int zk_vkey_serialize(zk_ctx* ctx, const zk_vkey* vkey, int compressed, uint8_t* out_host, size_t cap);
+size_t zk_vkey_num_inputs(const zk_vkey* vkey);          /* gamma_abc_g1 length - 1 */
+int zk_vkey_free(zk_ctx* ctx, zk_vkey* vkey);
+/* The largest window table a key made on this context FROM NOW ON keeps, in bytes (default 256 MiB = 5461 public inputs;
+ * (size_t)-1 restores the default).  A key whose table would be larger keeps none, and its prepared inputs are count vectors of
+ * ninp scalars through zk_msm_g1_multi_dev over the resident gamma_abc table, gamma_abc[0] added afterwards: the same points. */
+int zk_groth16_prepare_table_limit(zk_ctx* ctx, size_t bytes);
+/* zk_groth16_verify_batch (check_subgroup = 0) / _checked (!= 0), zk_groth16_verify_aggregate_coeffs and zk_groth16_verify_aggregate
+ * on a zk_vkey: their contracts word for word -- verdicts, folded, the all-zero folded on an early rejection, a zero coefficient, the
+ * ZK_ERR_ARG cases, the count limits. */
+int zk_groth16_vkey_verify_batch(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                 const uint8_t* proofs_host, int check_subgroup, int* ok);
+int zk_groth16_vkey_verify_aggregate_coeffs(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                            const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
+int zk_groth16_vkey_verify_aggregate(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                     const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each);
+/* prepare_inputs (verifier.rs:18-33) as a step of its own: prepared_out[k] = gamma_abc[0] + sum_j inputs[k][j] gamma_abc[j + 1] for
+ * count input vectors (all-zero words: the point at infinity).  On the device k_g1_prepare_inputs: a proof is a power-of-two segment
+ * of lanes inside one wave, each lane adds its stripe of (input, window) table entries with the complete mixed addition, a tree of
+ * complete additions through LDS sums the segment.  ZK_ERR_ARG: a null pointer, count = 0 or above 2^22 / 3, inputs_per_proof that
+ * is not the key's, an input not below r.  The host form needs no device. */
+int zk_groth16_prepare_inputs(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                              zk_g1_affine* prepared_out);
+int zk_groth16_prepare_inputs_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, zk_g1_affine* out);
+/* verify_proof_with_prepared_inputs (verifier.rs:38-61) for count proofs: prepared[k] as zk_groth16_prepare_inputs gives it
+ * (coordinate words below q, else ZK_ERR_ARG; on the curve is the caller's business, as for zk_pairing_products). */
+int zk_groth16_vkey_verify_prepared(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_g1_affine* prepared, const uint8_t* proofs_host,
+                                    int check_subgroup, int* ok);
 /* PairingEngine::product_of_pairings for ONE long product: final_exponentiation(prod_{k < n} miller_loop(p[k], q[k])), the Miller
  * loops one per lane, their values folded by k_fq12_fold (a wave per block: a serial product per lane, then a tree through LDS),
  * the final exponentiation on the host; points as zk_pairing_products takes them.  n = 0, n above 2^22 or a null pointer: ZK_ERR_ARG. */

@@ -438,6 +438,17 @@ pub fn create_proof_local(pk: *const ZkPk, r1cs: *const ZkR1cs, full_assignment:
         s as *const Fr as *const ZkFr, proof.as_mut_ptr()) }));
     proof
 }
+// The verifier's side (INTEGRATION 2d) binds to a ZkVkey, not to a ZkPk: prepare_verifying_key(&vk) is zk_vkey_upload / zk_vkey_deserialize
+// (once per key; the handle is the PreparedVerifyingKey and the window table), prepare_inputs(&pvk, &inputs) is
+// zk_groth16_prepare_inputs (or zk_groth16_prepare_inputs_host without a device), verify_proof_with_prepared_inputs is
+// zk_groth16_vkey_verify_prepared, and Groth16::verify is zk_groth16_vkey_verify_batch with count = 1.
+pub fn verify_proofs(vkey: *const ZkVkey, inputs: &[Fr], inputs_per_proof: usize, proofs: &[u8], check_subgroup: bool) -> Vec<i32> {
+    let count = proofs.len() / 192;
+    let mut ok = vec![0i32; count];
+    CTX.with(|c| check(unsafe { zk_groth16_vkey_verify_batch(*c, vkey, count, inputs.as_ptr() as *const ZkFr, inputs_per_proof, proofs.as_ptr(),
+        check_subgroup as i32, ok.as_mut_ptr()) }));
+    ok
+}
 '''
 
 

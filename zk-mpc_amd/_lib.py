@@ -362,6 +362,20 @@ PROTOTYPES = {
     "zk_marlin_verify_aggregate_coeffs": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
     "zk_marlin_verify_aggregate": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
     "zk_diag_g1_term_sum_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P]),
+    "zk_vkey_upload": (_I, [_P, _P, _I, C.POINTER(_P)]),
+    "zk_vkey_deserialize": (_I, [_P, _P, _SZ, _I, _I, C.POINTER(_P)]),
+    "zk_vkey_from_pk": (_I, [_P, _P, C.POINTER(_P)]),
+    "zk_vkey_serialized_size": (_SZ, [_P, _I]),
+    "zk_vkey_serialize": (_I, [_P, _P, _I, _P, _SZ]),
+    "zk_vkey_num_inputs": (_SZ, [_P]),
+    "zk_vkey_free": (_I, [_P, _P]),
+    "zk_groth16_prepare_table_limit": (_I, [_P, _SZ]),
+    "zk_groth16_vkey_verify_batch": (_I, [_P, _P, _SZ, _P, _SZ, _P, _I, _P]),
+    "zk_groth16_vkey_verify_aggregate_coeffs": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_groth16_vkey_verify_aggregate": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_groth16_prepare_inputs": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
+    "zk_groth16_prepare_inputs_host": (_I, [_P, _P, _SZ, _P]),
+    "zk_groth16_vkey_verify_prepared": (_I, [_P, _P, _SZ, _P, _P, _I, _P]),
 }
 
 _lib = None

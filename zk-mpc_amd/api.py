@@ -919,8 +919,55 @@ class Context:
         inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(count, -1, 4) if count else np.zeros((0, 0, 4), np.uint64)
         buf = np.frombuffer(data, dtype=np.uint8)
         ok = np.zeros(count, dtype=np.int32)
+        if isinstance(pk, VerifyingKey):
+            self._ck(self.lib.zk_groth16_vkey_verify_batch(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), int(bool(check_subgroup)), _ptr(ok)))
+            return ok
         fn = self.lib.zk_groth16_verify_batch_checked if check_subgroup else self.lib.zk_groth16_verify_batch
         self._ck(fn(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(ok)))
+        return ok
+
+    # ---- the verifier's own key (csrc/groth16_vkey.hip) and prepare_inputs as a step of its own (csrc/g1_prepare_inputs.hip) ----
+    def vkey_upload(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, check_subgroup: bool = False) -> "VerifyingKey":
+        """zk_vkey_upload: a resident verifying key from a host view (points as uint64 arrays in the ABI's form, as groth16_verify_host takes them)."""
+        vk, _abc = _vk_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1)
+        h = C.c_void_p()
+        self._ck(self.lib.zk_vkey_upload(self.h, C.byref(vk), int(bool(check_subgroup)), C.byref(h)))
+        return VerifyingKey(self, h)
+
+    def vkey_deserialize(self, data: bytes, compressed: bool = True, check_subgroup: bool = False) -> "VerifyingKey":
+        """zk_vkey_deserialize: a resident verifying key from VerifyingKey::serialize[_uncompressed] bytes (check_subgroup: every point
+        also passes the subgroup test, as the reference's deserialize does)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = C.c_void_p()
+        self._ck(self.lib.zk_vkey_deserialize(self.h, _ptr(buf) if buf.size else None, buf.size, int(bool(compressed)), int(bool(check_subgroup)), C.byref(h)))
+        return VerifyingKey(self, h)
+
+    def groth16_prepare_table_limit(self, nbytes: int = None):
+        """zk_groth16_prepare_table_limit: the largest window table a verifying key made from now on keeps (None: the default, 256 MiB)."""
+        self._ck(self.lib.zk_groth16_prepare_table_limit(self.h, C.c_size_t(-1).value if nbytes is None else int(nbytes)))
+
+    def groth16_prepare_inputs(self, vkey: "VerifyingKey", inputs_mont: np.ndarray) -> np.ndarray:
+        """prepare_inputs for count input vectors: inputs_mont (count, num_instance - 1, 4) Montgomery -> (count, 12) affine points
+        gamma_abc[0] + sum_j x_j gamma_abc[j + 1] (all zero: infinity)."""
+        inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64)
+        if inp.ndim != 3 or inp.shape[2] != 4 or inp.shape[0] == 0:
+            raise ValueError("groth16_prepare_inputs: inputs_mont is (count, num_instance - 1, 4)")
+        out = np.zeros((inp.shape[0], 12), dtype=np.uint64)
+        self._ck(self.lib.zk_groth16_prepare_inputs(self.h, vkey.h, inp.shape[0], _ptr(inp) if inp.size else None, inp.shape[1], _ptr(out)))
+        return out
+
+    def groth16_verify_prepared(self, vkey: "VerifyingKey", prepared: np.ndarray, proofs, check_subgroup: bool = False) -> np.ndarray:
+        """verify_proof_with_prepared_inputs for many proofs: prepared (count, 12) as groth16_prepare_inputs gives it -> count verdicts."""
+        data = b"".join(proofs) if isinstance(proofs, (list, tuple)) else bytes(proofs)
+        if len(data) % 192:
+            raise ValueError("proofs must be a whole number of 192-byte proofs")
+        count = len(data) // 192
+        prep = np.ascontiguousarray(prepared, dtype=np.uint64).reshape(-1, 12)
+        if prep.shape[0] != count:
+            raise ValueError("one prepared input per proof")
+        buf = np.frombuffer(data, dtype=np.uint8)
+        ok = np.zeros(count, dtype=np.int32)
+        self._ck(self.lib.zk_groth16_vkey_verify_prepared(self.h, vkey.h, count, _ptr(prep), _ptr(buf), int(bool(check_subgroup)), _ptr(ok)))
         return ok
 
     def groth16_verify(self, pk: "ProvingKey", inputs_mont: np.ndarray, proof: bytes, check_subgroup: bool = False) -> bool:
@@ -935,19 +982,21 @@ class Context:
         (ok_all, count verdicts: all ones, or those of groth16_verify_batch(check_subgroup=True) when the fold fails)."""
         data, count, inp, buf = _aggregate_args(inputs_mont, proofs)
         ok = C.c_int(0)
+        vkey = isinstance(pk, VerifyingKey)      # (either key type: the pk forms run the same code on the vkey the key owns)
         if coeffs is not None:
             if seed is not None or each:
                 raise ValueError("groth16_verify_aggregate: coeffs excludes seed and each")
             co = _coeff_array(coeffs, count)
             folded = np.zeros(72, dtype=np.uint64)
-            self._ck(self.lib.zk_groth16_verify_aggregate_coeffs(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(co), C.byref(ok), _ptr(folded)))
+            fn = self.lib.zk_groth16_vkey_verify_aggregate_coeffs if vkey else self.lib.zk_groth16_verify_aggregate_coeffs
+            self._ck(fn(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(co), C.byref(ok), _ptr(folded)))
             return bool(ok.value), folded
         seed = os.urandom(32) if seed is None else bytes(seed)
         if len(seed) != 32:
             raise ValueError("a seed is 32 bytes")
         ok_each = np.zeros(max(count, 1), dtype=np.int32) if each else None
-        self._ck(self.lib.zk_groth16_verify_aggregate(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), seed, C.byref(ok),
-                                                      _ptr(ok_each) if each else None))
+        fn = self.lib.zk_groth16_vkey_verify_aggregate if vkey else self.lib.zk_groth16_verify_aggregate
+        self._ck(fn(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), seed, C.byref(ok), _ptr(ok_each) if each else None))
         return (bool(ok.value), ok_each[:count]) if each else bool(ok.value)
 
     def pairing_product_long(self, p: np.ndarray, q: np.ndarray) -> np.ndarray:
@@ -1123,9 +1172,39 @@ class ProvingKey:
         return groth16_verify_aggregate_host(self.vk_g1(0), self.vk_g2(0), self.vk_g2(2), self.vk_g2(1), self.download("gamma_abc_g1"), inputs_mont,
                                              proofs, coeffs)
 
+    def vkey(self) -> "VerifyingKey":
+        """zk_vkey_from_pk: an independent resident verifying key with this key's verifying-key parts."""
+        h = C.c_void_p()
+        self.ctx._ck(self.ctx.lib.zk_vkey_from_pk(self.ctx.h, self.h, C.byref(h)))
+        return VerifyingKey(self.ctx, h)
+
     def free(self):
         if self.h:
             self.ctx.lib.zk_pk_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class VerifyingKey:
+    """A resident Groth16 verifying key (zk_vkey: arkworks' PreparedVerifyingKey and the window table prepare_inputs reads); made by
+    Context.vkey_upload, Context.vkey_deserialize or ProvingKey.vkey, taken by Context.groth16_verify*, groth16_prepare_inputs."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+
+    @property
+    def num_inputs(self) -> int:
+        return self.ctx.lib.zk_vkey_num_inputs(self.h)
+
+    def serialize(self, compressed: bool = True) -> bytes:
+        """VerifyingKey::serialize / serialize_uncompressed: the bytes zk_vk_serialize writes for a proving key with these parts."""
+        n = self.ctx.lib.zk_vkey_serialized_size(self.h, int(bool(compressed)))
+        out = np.zeros(n, dtype=np.uint8)
+        self.ctx._ck(self.ctx.lib.zk_vkey_serialize(self.ctx.h, self.h, int(bool(compressed)), _ptr(out), n))
+        return out.tobytes()
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.zk_vkey_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -1268,6 +1347,15 @@ def groth16_verify_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inp
     fn = _lib.load().zk_groth16_verify_host_checked if check_subgroup else _lib.load().zk_groth16_verify_host
     _ck_host(fn(C.byref(vk), _ptr(inp), inp.shape[0], _ptr(buf), C.byref(ok)), "zk_groth16_verify_host")
     return bool(ok.value)
+
+
+def groth16_prepare_inputs_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, inputs_mont) -> np.ndarray:
+    """zk_groth16_prepare_inputs_host: gamma_abc[0] + sum_j x_j gamma_abc[j + 1] through the host arithmetic -> (12,) (all zero: infinity)."""
+    vk, _abc = _vk_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1)
+    inp = np.ascontiguousarray(inputs_mont, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros(12, dtype=np.uint64)
+    _ck_host(_lib.load().zk_groth16_prepare_inputs_host(C.byref(vk), _ptr(inp) if inp.size else None, inp.shape[0], _ptr(out)), "zk_groth16_prepare_inputs_host")
+    return out
 
 
 # ---- aggregated Groth16 verification: the host forms ----

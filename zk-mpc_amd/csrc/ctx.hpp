@@ -180,6 +180,7 @@ struct zk_ctx {
     } next;
     hipStream_t copy_stream = nullptr;        // the upload's stream
     int mul_levels = -1;                      // zk_msm_mul_levels: shifted copies the next proving key's tables get (-1: the default)
+    size_t prepare_table_limit = (size_t)256 << 20;      // zk_groth16_prepare_table_limit: the largest window table a verifying key made from now on keeps
     // zk_diag_msm_plans (diag.hip): what the dispatch code decided for the last MSM jobs, one record per job whose reduce chain was
     // enqueued (msm.hip: msm_plan_commit).  Written and read by the thread inside an entry point of this context; host words only.
     struct PlanRing {

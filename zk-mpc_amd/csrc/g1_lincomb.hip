@@ -4,8 +4,8 @@
 // Replaces (reference): the commitment arithmetic of MarlinKZG10::check_combinations -- LinearCombination over commitments,
 // accumulate_commitments_and_values (arkworks/poly-commit/src/marlin/mod.rs:33-118, :309-420, marlin_pc/mod.rs:342-400) -- and the
 // subgroup test of GroupAffine::deserialize (ec/src/models/short_weierstrass_jacobian.rs:171-183, :888-905: r P == O), as a batch.
-// The MSM pipeline (msm.hip) is for long vectors over one table; k_verify_prepare (pairing.hip) is one proof per lane with a branch
-// per scalar bit.  Here:
+// The MSM pipeline (msm.hip) is for long vectors over one table; k_g1_prepare_inputs (g1_prepare_inputs.hip) is for sums over ONE
+// table that carries its window multiples.  Here:
 //   * one TERM per lane, one wave per block.  The caller's segments are packed into waves so that none straddles one
 //     (ZkLincombPack); the lanes left over in a wave join the segment before them with a zero scalar;
 //   * the per-lane multiplication is g1_lincomb.cuh: fixed signed 4-bit windows, the same doublings and one addition per window on

@@ -63,12 +63,42 @@ struct zk_pk {
     uint32_t mul_levels = 0;
     zk::Affine<zk::G1Field> alpha_g1, beta_g1, delta_g1, a0, b0_g1;
     zk::Affine<zk::G2Field> beta_g2, delta_g2, gamma_g2, b0_g2;
-    // the verifier's constant e(alpha, beta) (groth16_verify.hip), computed by the first verification of this key: the GT value as the
-    // finish kernel compares it (12 Fq, internal form, packed)
-    mutable std::mutex e_alpha_beta_mu;
-    mutable bool have_e_alpha_beta = false;
-    mutable uint32_t e_alpha_beta[zk::FQ12_WORDS];
+    // the verifier's view of this key (groth16_vkey.hip: zk_pk_vkey), made by the first verification through the key under this
+    // mutex and freed with the key: the pk forms of the verifiers are the vkey forms on it
+    mutable std::mutex vkey_mu;
+    mutable zk_vkey* vkey = nullptr;
 };
+
+// arkworks' PreparedVerifyingKey (verifier.rs: prepare_verifying_key) resident on the device, and what prepare_inputs needs beyond it.
+struct zk_vkey {
+    zk::Affine<zk::G1Field> alpha_g1;
+    zk::Affine<zk::G2Field> beta_g2, gamma_g2, delta_g2, neg_gamma_g2, neg_delta_g2;
+    zk_bases* gamma_abc = nullptr;           // owned: ninp + 1 points, table form
+    std::vector<uint32_t> abc_host;          // the same words on the host (the folded form's key multiplications, gamma_abc[0])
+    // window multiples of gamma_abc[j], j >= 1 (g1_prepare_inputs.hip): entry ((j - 1) 64 + w) 8 + m - 1 = m 16^w gamma_abc[j], affine,
+    // table form.  NULL: the key has no public input, or the table would be larger than the context's limit when the key was made
+    // (zk_groth16_prepare_table_limit) -- then the sums go through the multi-vector MSM over gamma_abc.
+    uint32_t* win = nullptr;
+    bool points_in_subgroup = false;         // every point is known to be in its subgroup: the folded form's host multiplications take the endomorphism
+    uint32_t e_alpha_beta[zk::FQ12_WORDS];   // e(alpha, beta) as the finish kernel compares it (12 Fq, internal form, packed)
+    size_t ninp() const { return gamma_abc->n - 1; }
+};
+// groth16_vkey.hip.  zk_vkey_make: the object from its parts (g2s = beta, gamma, delta); abc is CONSUMED, on failure too.
+// zk_pk_vkey: the key's own vkey, built on first use; `entry` names the caller in the refusal of a key without verifying-key parts.
+int zk_vkey_make(zk_ctx* ctx, const zk::Affine<zk::G1Field>& alpha, const zk::Affine<zk::G2Field> g2s[3], zk_bases* abc, bool in_subgroup,
+                 zk_vkey** out);
+int zk_pk_vkey(zk_ctx* ctx, const zk_pk* pk, const char* entry, const zk_vkey** out);
+// groth16_verify.hip: a host verifying key for ninp public inputs -- its parts there, gamma_abc of ninp + 1 points, every coordinate
+// word below q (what zk_groth16_verify_host accepts)
+bool zk_vk_host_ok(const zk_vk_host* vk, size_t ninp);
+// g1_prepare_inputs.hip, on ctx->stream, no wait.  The table of a key's window multiples (abc_dev: ninp + 1 points; win_dev: ninp x
+// ZK_PREP_ENTRIES points), one entry per lane; and prepare_inputs for count proofs: inputs_dev = count x ninp elements in the
+// reference's form, digits_dev = room for as many recoded scalars (8 words each), out = count affine points and infinity flags.
+// win_dev may be NULL when ninp = 0.
+constexpr size_t ZK_PREP_WINDOWS = 64, ZK_PREP_ENTRIES = ZK_PREP_WINDOWS * 8;      // signed 4-bit digits: 64 windows x (1 .. 8) P
+int zk_g1_window_table_launch(zk_ctx* ctx, const uint32_t* abc_dev, size_t ninp, uint32_t* win_dev);
+int zk_g1_prepare_inputs_launch(zk_ctx* ctx, const uint32_t* inputs_dev, size_t count, size_t ninp, const uint32_t* win_dev, const uint32_t* abc_dev,
+                                uint32_t* digits_dev, uint32_t* out_aff_dev, uint32_t* out_inf_dev);
 
 // The five MSM jobs of ONE proof, in ZkG16Jobs order (0 = B in G2, 1 = A, 2 = B in G1, 3 = L, 4 = H), and how far each has been
 // enqueued.  run_msms drives its own proof's flight through the stages; one that was started AHEAD of its proof is owned by the

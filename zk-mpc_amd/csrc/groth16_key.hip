@@ -82,6 +82,7 @@ extern "C" int zk_pk_free(zk_ctx* ctx, zk_pk* pk) {
     zk_presort_free(ctx);
     zk_bases* all[9] = {pk->a, pk->b_g1, pk->b_g2, pk->h, pk->l, pk->gamma_abc, pk->l_pad, pk->h_eval, pk->l_eval_pad};
     for (auto* b : all) zk_bases_free(ctx, b);
+    zk_vkey_free(ctx, pk->vkey);
     delete pk;
     return ZK_OK;
     ZK_API_END

@@ -11,9 +11,11 @@
 //     s_0 = sum_i r_i,  s_j = sum_i r_i x_{i,j} (mod r)
 // count + 3 Miller loops and ONE final exponentiation (the batch form: 3 count and count).
 //
-//   k_verify_prepare  one proof per lane: gamma_abc[0] + sum x_i gamma_abc[i] by double-and-add (the usual handful of public
-//                     inputs; a key with very many would want the multi-vector MSM instead), and the proof's three pairs laid out.
-//                     Its scalar multiplication branches on scalar bits; it is microseconds beside the Miller loops.
+// Every device form runs on a zk_vkey (groth16_vkey.hip); the entry points that take a zk_pk are the same code on the vkey the key owns.
+// The prepared inputs gamma_abc[0] + sum x_i gamma_abc[i] of a batch are g1_prepare_inputs.hip's fixed-base kernel over the vkey's
+// window table (prepare_inputs_dev; a key too large for a table: zk_msm_g1_multi_dev over gamma_abc), also a public step of its own
+// (zk_groth16_prepare_inputs, zk_groth16_vkey_verify_prepared).
+//   k_verify_layout   one proof per lane: the proof's three pairs laid out for the Miller launch.
 //   k_g1_scale_fold   per lane an affine point and a 128-bit coefficient -> r P in XYZZ by g1_lincomb.cuh's fixed signed windows
 //                     (32 windows; the digit selects a table entry in LDS and a sign, never the control flow), then either per
 //                     lane the affine point (the Miller loop's P array) or a wave tree of complete additions through LDS and one
@@ -21,8 +23,8 @@
 // Both device forms check their arguments (device_args_ok) and stage their proofs (stage_proofs) by the same code and run pairing.hip's
 // kernels behind it; the folded form ends in its zk_miller_product.  The host re-launches the sum on its partials until at most 64
 // are left and finishes those itself in 64-bit limbs.
-// Not built: a multi-vector MSM over the gamma_abc table for keys with very many public inputs -- the ninp + 2 full-width
-// multiplications of key points (s_0 alpha, s_j gamma_abc[j]) run on the context's helper threads under the device work.
+// The folded form's key multiplications -- the ninp + 2 full-width multiplications s_0 alpha, s_j gamma_abc[j] -- run on the
+// context's helper threads under the device work, whatever ninp is (one MSM over gamma_abc in their place: DESIGN 6, not kept).
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "fsrng.hpp"
@@ -41,23 +43,18 @@ constexpr size_t MAX_LANES = ZK_PAIRING_MAX_LANES;
 constexpr size_t SCALE_LDS = (size_t)LINCOMB_TAB * XW * 64 * 4;      // the window tables: 98 304 bytes
 constexpr size_t SUM_LDS = (size_t)XW * 64 * 4;                      // the tree alone: 12 288 bytes
 
-// ---- k_verify_prepare -------------------------------------------------------------------------------------------------------------
+
+// ---- k_verify_layout --------------------------------------------------------------------------------------------------------------
 // proof k: P[3 k .. 3 k + 2] = A, prepared inputs, C;  Q[3 k ..] = B, -gamma, -delta.  ac holds (A_k, C_k) at 2 k, 2 k + 1 and b
-// holds B_k (table form, from the decompression, with their off-curve flags bad_ac / bad_b); negs = -gamma | -delta.
-__global__ void __launch_bounds__(64) k_verify_prepare(size_t count, size_t ninp, const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ gamma_abc,
-                                                       const uint32_t* __restrict__ ac, const uint32_t* __restrict__ b, const uint32_t* __restrict__ negs,
-                                                       const uint32_t* __restrict__ bad_ac, const uint32_t* __restrict__ bad_b, uint32_t* __restrict__ P,
-                                                       uint32_t* __restrict__ Q, uint32_t* __restrict__ bad) {
+// holds B_k (table form, from the decompression, with their off-curve flags bad_ac / bad_b); prep the prepared inputs; negs = -gamma | -delta.
+__global__ void __launch_bounds__(64) k_verify_layout(size_t count, const uint32_t* __restrict__ prep, const uint32_t* __restrict__ ac,
+                                                      const uint32_t* __restrict__ b, const uint32_t* __restrict__ negs,
+                                                      const uint32_t* __restrict__ bad_ac, const uint32_t* __restrict__ bad_b, uint32_t* __restrict__ P,
+                                                      uint32_t* __restrict__ Q, uint32_t* __restrict__ bad) {
     const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (k >= count) return;
-    XYZZ<G1Field> acc = xyzz_from_affine<G1Field>(aff_load16<G1Field>(gamma_abc, 0));
-    for (size_t i = 0; i < ninp; i++) {
-        uint32_t kw[8];
-        fp_pack<FrParams>(kw, fp_ext_to_canon<FrParams>(fr_load(inputs, k * ninp + i)));
-        acc = xyzz_add<G1Field>(acc, xyzz_scalar_mul<G1Field>(aff_load16<G1Field>(gamma_abc, i + 1), kw, 8));
-    }
     aff_store16<G1Field>(P, 3 * k, aff_load16<G1Field>(ac, 2 * k));
-    aff_store16<G1Field>(P, 3 * k + 1, xyzz_to_affine<G1Field>(acc));
+    aff_store16<G1Field>(P, 3 * k + 1, aff_load16<G1Field>(prep, k));
     aff_store16<G1Field>(P, 3 * k + 2, aff_load16<G1Field>(ac, 2 * k + 1));
     aff_store16<G2Field>(Q, 3 * k, aff_load16<G2Field>(b, k));
     aff_store16<G2Field>(Q, 3 * k + 1, aff_load16<G2Field>(negs, 0));
@@ -130,6 +127,16 @@ int zk_g1_sum_down(zk_ctx* ctx, uint32_t* a, uint32_t* b, size_t* m, uint32_t** 
     return ZK_OK;
 }
 
+bool zk_vk_host_ok(const zk_vk_host* vk, size_t ninp) {
+    if (!vk || !vk->gamma_abc_g1 || vk->gamma_abc_len != ninp + 1) return false;
+    if (!zk_words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !zk_words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
+        !zk_words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !zk_words_below_q((const uint64_t*)&vk->delta_g2, 4))
+        return false;
+    for (size_t i = 0; i <= ninp; i++)
+        if (!zk_words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return false;
+    return true;
+}
+
 namespace {
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
@@ -148,35 +155,22 @@ void coeff_words(const uint64_t* c, uint32_t k[8]) {
     k[4] = k[5] = k[6] = k[7] = 0;
 }
 
-// the key's e(alpha, beta) as the finish kernel compares it (packed); computed once per key
-void pk_e_alpha_beta(const zk_pk* pk, uint32_t out[FQ12_WORDS]) {
-    std::lock_guard<std::mutex> g(pk->e_alpha_beta_mu);
-    if (!pk->have_e_alpha_beta) {
-        const Affine<H1> alpha = aff_to_host64<G1Field>(pk->alpha_g1);
-        const Affine<H2> beta = aff_to_host64<G2Field>(pk->beta_g2);
-        Fq12<H2> e;
-        pairing_product<H2>(e, &alpha, &beta, 1);
-        fq12_host_to_packed(pk->e_alpha_beta, e);
-        pk->have_e_alpha_beta = true;
-    }
-    memcpy(out, pk->e_alpha_beta, FQ12_WORDS * 4);
-}
-
 // ---- what the forms share: checks and staging ---------------------------------------------------------------------------------------
 bool inputs_below_r(const zk_fr* inputs, size_t n) {
     for (size_t i = 0; i < n; i++)
         if (!zk_fr_words_valid(inputs[i].l)) return false;
     return true;
 }
-// a host verifying key for ninp public inputs: its parts there, gamma_abc of ninp + 1 points, every coordinate word below q
-bool vk_host_ok(const zk_vk_host* vk, size_t ninp) {
-    if (!vk || !vk->gamma_abc_g1 || vk->gamma_abc_len != ninp + 1) return false;
-    if (!zk_words_below_q((const uint64_t*)&vk->alpha_g1, 2) || !zk_words_below_q((const uint64_t*)&vk->beta_g2, 4) ||
-        !zk_words_below_q((const uint64_t*)&vk->gamma_g2, 4) || !zk_words_below_q((const uint64_t*)&vk->delta_g2, 4))
-        return false;
-    for (size_t i = 0; i <= ninp; i++)
-        if (!zk_words_below_q((const uint64_t*)&vk->gamma_abc_g1[i], 2)) return false;
-    return true;
+bool vk_host_ok(const zk_vk_host* vk, size_t ninp) { return zk_vk_host_ok(vk, ninp); }
+// prepare_inputs (verifier.rs:18-33) on host values
+XYZZ<H1> host_prepare(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs) {
+    XYZZ<H1> acc = xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[0]));
+    for (size_t i = 0; i < n_inputs; i++) {
+        uint32_t kw[8];
+        fr_abi_to_canon_words(inputs[i].l, kw);
+        acc = xyzz_add<H1>(acc, host64_scalar_mul<H1>(xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[i + 1])), kw));
+    }
+    return acc;
 }
 // one proof's bytes as A, B, C on the host; false: a point off its curve, or with check_subgroup outside its subgroup (the test of
 // Proof::deserialize: subgroup.cuh, host instantiation)
@@ -184,16 +178,20 @@ bool host_proof_points(const uint8_t proof[192], bool check_subgroup, Affine<G1F
     if (!zk_host_decompress_g1(proof, a) || !zk_host_decompress_g2(proof + 48, b) || !zk_host_decompress_g1(proof + 144, c)) return false;
     return !check_subgroup || (zk_host_in_subgroup_g1(*a) && zk_host_in_subgroup_g2(*b) && zk_host_in_subgroup_g1(*c));
 }
-// what the device forms refuse of their key and arguments, in the words of the entry point `entry`
-int device_args_ok(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, size_t max_count,
-                   const char* entry) {
-    if (!ctx || !pk || !count || !proofs_host || count > max_count) return ZK_ERR_ARG;
-    if (!pk->gamma_abc || pk->gamma_abc->n == 0 || aff_is_inf<G2Field>(pk->gamma_g2))
-        ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": the key has no verifying-key parts (gamma_g2, gamma_abc_g1)");
-    if (pk->gamma_abc->n != ninp + 1) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": inputs_per_proof is not num_instance - 1");
+// what prepare_inputs refuses of count input vectors, in the words of the entry point `entry`
+int inputs_ok(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const char* entry) {
+    if (vk->ninp() != ninp) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": inputs_per_proof is not num_instance - 1");
     if (ninp && !inputs_host) return ZK_ERR_ARG;
+    if (ninp && count > ((size_t)1 << 30) / ninp) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": more than 2^30 public inputs in one call");
     if (!inputs_below_r(inputs_host, count * ninp)) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": a public input is not below r");
     return ZK_OK;
+}
+// what the device forms refuse of their key and arguments, in the words of the entry point `entry` (a zk_pk without verifying-key
+// parts is refused where its vkey is asked for: zk_pk_vkey)
+int device_args_ok(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, size_t max_count,
+                   const char* entry) {
+    if (!ctx || !vk || !count || !proofs_host || count > max_count) return ZK_ERR_ARG;
+    return inputs_ok(ctx, vk, count, inputs_host, ninp, entry);
 }
 // The points of count proofs onto the device, for both device forms: the compressed (A_k, C_k) and the compressed B_k split out of
 // the proofs' bytes into *staging (the caller keeps it until it has waited for the stream: the uploads read it), uploaded and
@@ -241,13 +239,7 @@ int verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, cons
     Affine<G1Field> a, c;
     Affine<G2Field> b;
     if (!host_proof_points(proof, check_subgroup, &a, &b, &c)) return ZK_OK;
-    // prepare_inputs (verifier.rs:18-33)
-    XYZZ<H1> acc = xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[0]));
-    for (size_t i = 0; i < n_inputs; i++) {
-        uint32_t kw[8];
-        fr_abi_to_canon_words(inputs[i].l, kw);
-        acc = xyzz_add<H1>(acc, host64_scalar_mul<H1>(xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[i + 1])), kw));
-    }
+    const XYZZ<H1> acc = host_prepare(vk, inputs, n_inputs);
     const Affine<H1> P[3] = {aff_to_host64<G1Field>(a), xyzz_to_affine<H1>(acc), aff_to_host64<G1Field>(c)};
     const Affine<H2> Q[3] = {aff_to_host64<G2Field>(b), aff_neg<H2>(zk_host_g2(&vk->gamma_g2)), aff_neg<H2>(zk_host_g2(&vk->delta_g2))};
     Fq12<H2> lhs, rhs;
@@ -259,31 +251,75 @@ int verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, cons
     return ZK_OK;
 }
 
-// the per-point flags of the staging (off the curve, with check_subgroup outside the subgroup) go into each proof's verdict by k_verify_prepare
-int verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, int* ok,
-                 bool check_subgroup) {
+// prepare_inputs for count proofs on the device, on ctx->stream: prep = count affine points (table form), inf = count infinity flags.
+// A key with a window table (or without public inputs): k_g1_prepare_inputs, no wait.  A key too large for one: count vectors of
+// ninp scalars through zk_msm_g1_multi_dev over gamma_abc[1 ..] (inputs_ok keeps count * ninp within that call's limit; it cuts the
+// vectors into jobs itself), gamma_abc[0] added and the points normalised on the host -- the same points; that path waits.
+int prepare_inputs_dev(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, uint32_t* prep, uint32_t* inf) {
+    const size_t ninp = vk->ninp();
+    hipStream_t st = ctx->stream;
+    uint32_t *d_in = nullptr, *d_dig = nullptr;
+    if (ninp) {
+        ZK_TRY(zk_scratch(ctx, "vfy_in", count * ninp * 32 + 32, (void**)&d_in));
+        ZK_HIP(ctx, hipMemcpyAsync(d_in, inputs_host, count * ninp * 32, hipMemcpyHostToDevice, st));
+    }
+    if (!ninp || vk->win) {
+        if (ninp) ZK_TRY(zk_scratch(ctx, "vfy_digits", count * ninp * 32, (void**)&d_dig));
+        return zk_g1_prepare_inputs_launch(ctx, d_in, count, ninp, vk->win, vk->gamma_abc->dev, d_dig, prep, inf);
+    }
+    std::vector<zk_g1_projective> sums(count);
+    ZK_TRY(zk_msm_g1_multi_dev(ctx, vk->gamma_abc, 1, d_in, ninp, ninp, count, sums.data()));
+    const XYZZ<H1> g0 = xyzz_from_affine<H1>(aff_to_host64<G1Field>(aff_load<G1Field>(vk->abc_host.data())));
+    std::vector<XYZZ<H1>> x(count);
+    for (size_t k = 0; k < count; k++) x[k] = xyzz_add<H1>(host64_proj_from_abi<H1>((const uint64_t*)&sums[k]), g0);
+    const std::vector<Affine<H1>> a = host64_batch_to_affine<H1>(x);
+    std::vector<uint32_t> w(count * 24), fl(count);
+    for (size_t k = 0; k < count; k++) {
+        aff_store<G1Field>(&w[24 * k], aff_from_host64<G1Field>(a[k]));
+        fl[k] = aff_is_inf<H1>(a[k]) ? 1u : 0u;
+    }
+    ZK_HIP(ctx, hipMemcpyAsync(prep, w.data(), count * 96, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipMemcpyAsync(inf, fl.data(), count * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(ctx, hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
+// The per-point flags of the staging (off the curve, with check_subgroup outside the subgroup) go into each proof's verdict by
+// k_verify_layout.  prepared (or NULL): the caller's prepared inputs in place of inputs_host (verify_proof_with_prepared_inputs).
+int verify_batch(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const zk_g1_affine* prepared,
+                 const uint8_t* proofs_host, int* ok, bool check_subgroup, const char* entry) {
     if (!ok) return ZK_ERR_ARG;
-    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES / 3, "zk_groth16_verify_batch"));
+    std::vector<uint32_t> prep_w;
+    if (prepared) {
+        if (!ctx || !vk || !count || !proofs_host || count > MAX_LANES / 3) return ZK_ERR_ARG;
+        for (size_t k = 0; k < count; k++)
+            if (!zk_words_below_q((const uint64_t*)&prepared[k], 2)) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": a prepared input's coordinate is not below q");
+        prep_w.resize(count * 24);
+        for (size_t k = 0; k < count; k++) aff_store<G1Field>(&prep_w[24 * k], host_aff_from_abi<G1Field>((const uint64_t*)&prepared[k]));
+    } else {
+        ZK_TRY(device_args_ok(ctx, vk, count, inputs_host, ninp, proofs_host, MAX_LANES / 3, entry));
+    }
     struct Consts { uint32_t negs[2 * 48]; uint32_t want[FQ12_WORDS]; } cs;      // the key's constants
-    aff_store<G2Field>(cs.negs, aff_neg<G2Field>(pk->gamma_g2));
-    aff_store<G2Field>(cs.negs + 48, aff_neg<G2Field>(pk->delta_g2));
-    pk_e_alpha_beta(pk, cs.want);
+    aff_store<G2Field>(cs.negs, vk->neg_gamma_g2);
+    aff_store<G2Field>(cs.negs + 48, vk->neg_delta_g2);
+    memcpy(cs.want, vk->e_alpha_beta, sizeof cs.want);
 
     const size_t n = 3 * count;
-    uint32_t *d_in, *d_cs, *ac, *b, *flags, *P, *Q, *ml;
-    ZK_TRY(zk_scratch(ctx, "vfy_in", count * ninp * 32 + 32, (void**)&d_in));
+    uint32_t *d_cs, *ac, *b, *flags, *P, *Q, *ml, *prep;
     ZK_TRY(zk_scratch(ctx, "vfy_cs", sizeof cs, (void**)&d_cs));
-    ZK_TRY(zk_scratch(ctx, "vfy_flags", (1 + 4 * count) * 4 + count * 4, (void**)&flags));      // any | bad_ac | bad_b | bad | ok
+    ZK_TRY(zk_scratch(ctx, "vfy_flags", (1 + 5 * count) * 4 + count * 4, (void**)&flags));      // any | bad_ac | bad_b | bad | inf | ok
+    ZK_TRY(zk_scratch(ctx, "vfy_prep", count * 96, (void**)&prep));
     ZK_TRY(zk_pair_scratch(ctx, n, &P, &Q, &ml));
-    uint32_t *bad_any = flags, *bad_ac = flags + 1, *bad_b = bad_ac + 2 * count, *bad = bad_b + count;
-    int* d_ok = (int*)(bad + count);
+    uint32_t *bad_any = flags, *bad_ac = flags + 1, *bad_b = bad_ac + 2 * count, *bad = bad_b + count, *inf = bad + count;
+    int* d_ok = (int*)(inf + count);
     hipStream_t st = ctx->stream;
-    if (ninp) ZK_HIP(ctx, hipMemcpyAsync(d_in, inputs_host, count * ninp * 32, hipMemcpyHostToDevice, st));
     ZK_HIP(ctx, hipMemcpyAsync(d_cs, &cs, sizeof cs, hipMemcpyHostToDevice, st));
     std::vector<uint8_t> staging;
     ZK_TRY(stage_proofs(ctx, count, proofs_host, check_subgroup, bad_any, bad_ac, bad_b, &ac, &b, &staging));
-    hipLaunchKernelGGL(k_verify_prepare, zk_blocks64(count), 64, 0, st, count, ninp, (const uint32_t*)d_in, (const uint32_t*)pk->gamma_abc->dev,
-                       (const uint32_t*)ac, (const uint32_t*)b, (const uint32_t*)d_cs, (const uint32_t*)bad_ac, (const uint32_t*)bad_b, P, Q, bad);
+    if (prepared) ZK_HIP(ctx, hipMemcpyAsync(prep, prep_w.data(), count * 96, hipMemcpyHostToDevice, st));
+    else ZK_TRY(prepare_inputs_dev(ctx, vk, count, inputs_host, prep, inf));
+    hipLaunchKernelGGL(k_verify_layout, zk_blocks64(count), 64, 0, st, count, (const uint32_t*)prep, (const uint32_t*)ac, (const uint32_t*)b,
+                       (const uint32_t*)d_cs, (const uint32_t*)bad_ac, (const uint32_t*)bad_b, P, Q, bad);
     ZK_HIP(ctx, hipGetLastError());
     ZK_TRY(zk_miller_launch(ctx, P, Q, n, ml));
     ZK_TRY(zk_pairing_finish_launch(ctx, ml, 3, count, nullptr, d_cs + 2 * 48, bad, d_ok));
@@ -341,14 +377,13 @@ int aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size
     return ZK_OK;
 }
 
-int aggregate_dev(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, const uint64_t* coeffs,
-                  int* ok_all, zk_gt* folded) {
+int aggregate_dev(zk_ctx* ctx, const zk_vkey* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, const uint64_t* coeffs,
+                  int* ok_all, zk_gt* folded, const char* entry) {
     if (!agg_args_ok(count, inputs_host, ninp, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
-    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES - 3, "zk_groth16_verify_aggregate"));
+    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES - 3, entry));
     *ok_all = 0;
     if (folded) memset(folded, 0, sizeof *folded);
-    std::vector<uint32_t> abc_w((ninp + 1) * 24);
-    ZK_HIP(ctx, hipMemcpy(abc_w.data(), pk->gamma_abc->dev, abc_w.size() * 4, hipMemcpyDeviceToHost));
+    const std::vector<uint32_t>& abc_w = pk->abc_host;
 
     const size_t n = count + 3, n_part = zk_blocks64(count);
     uint32_t *d_coef, *ac, *b, *flags, *P, *Q, *ml, *part_a, *part_b;
@@ -441,23 +476,82 @@ extern "C" int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr*
     return verify_host(vk, inputs, n_inputs, proof, ok, true);
     ZK_API_END
 }
+extern "C" int zk_groth16_prepare_inputs_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, zk_g1_affine* out) {
+    ZK_API_BEGIN_NOCTX
+    if (!out || (n_inputs && !inputs) || !vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
+    host_aff_to_abi<G1Field>((uint64_t*)out, aff_from_host64<G1Field>(xyzz_to_affine<H1>(host_prepare(vk, inputs, n_inputs))));
+    return ZK_OK;
+    ZK_API_END
+}
+extern "C" int zk_groth16_prepare_inputs(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                         zk_g1_affine* prepared_out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !vkey || !count || !prepared_out || count > MAX_LANES / 3) return ZK_ERR_ARG;
+    ZK_TRY(inputs_ok(ctx, vkey, count, inputs_host, inputs_per_proof, "zk_groth16_prepare_inputs"));
+    uint32_t *prep, *inf;
+    ZK_TRY(zk_scratch(ctx, "vfy_prep", count * 96, (void**)&prep));
+    ZK_TRY(zk_scratch(ctx, "vfy_flags", count * 4, (void**)&inf));
+    ZK_TRY(prepare_inputs_dev(ctx, vkey, count, inputs_host, prep, inf));
+    std::vector<uint32_t> w(count * 24), fl(count);
+    ZK_HIP(ctx, hipMemcpyAsync(w.data(), prep, count * 96, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(fl.data(), inf, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < count; k++) {
+        const Affine<G1Field> a = aff_load<G1Field>(&w[24 * k]);
+        if ((fl[k] != 0) != aff_is_inf<G1Field>(a)) ZK_FAIL(ctx, ZK_ERR_STATE, "zk_groth16_prepare_inputs: the infinity flag and the point disagree");
+        host_aff_to_abi<G1Field>((uint64_t*)&prepared_out[k], a);
+    }
+    return ZK_OK;
+    ZK_API_END
+}
+
+extern "C" int zk_groth16_vkey_verify_batch(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                            const uint8_t* proofs_host, int check_subgroup, int* ok) {
+    ZK_API_BEGIN(ctx)
+    return verify_batch(ctx, vkey, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, check_subgroup != 0, "zk_groth16_vkey_verify_batch");
+    ZK_API_END
+}
+extern "C" int zk_groth16_vkey_verify_prepared(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_g1_affine* prepared, const uint8_t* proofs_host,
+                                               int check_subgroup, int* ok) {
+    ZK_API_BEGIN(ctx)
+    if (!prepared) return ZK_ERR_ARG;
+    return verify_batch(ctx, vkey, count, nullptr, 0, prepared, proofs_host, ok, check_subgroup != 0, "zk_groth16_vkey_verify_prepared");
+    ZK_API_END
+}
+extern "C" int zk_groth16_vkey_verify_aggregate_coeffs(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                                       const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
+    ZK_API_BEGIN(ctx)
+    return aggregate_dev(ctx, vkey, count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all, folded, "zk_groth16_vkey_verify_aggregate");
+    ZK_API_END
+}
+
+// ---- the forms on a proving key: the same code on the vkey the key owns ----------------------------------------------------------
 extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                        const uint8_t* proofs_host, int* ok) {
     ZK_API_BEGIN(ctx)
-    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, false);
+    if (!ctx || !pk || !count || !proofs_host || !ok) return ZK_ERR_ARG;
+    const zk_vkey* vk;
+    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_batch", &vk));
+    return verify_batch(ctx, vk, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, false, "zk_groth16_verify_batch");
     ZK_API_END
 }
 extern "C" int zk_groth16_verify_batch_checked(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                                const uint8_t* proofs_host, int* ok) {
     ZK_API_BEGIN(ctx)
-    return verify_batch(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok, true);
+    if (!ctx || !pk || !count || !proofs_host || !ok) return ZK_ERR_ARG;
+    const zk_vkey* vk;
+    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_batch", &vk));
+    return verify_batch(ctx, vk, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, true, "zk_groth16_verify_batch");
     ZK_API_END
 }
 
 extern "C" int zk_groth16_verify_aggregate_coeffs(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
                                                   const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
     ZK_API_BEGIN(ctx)
-    return aggregate_dev(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all, folded);
+    if (!ctx || !pk || !agg_args_ok(count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
+    const zk_vkey* vk;
+    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_aggregate", &vk));
+    return aggregate_dev(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all, folded, "zk_groth16_verify_aggregate");
     ZK_API_END
 }
 
@@ -481,19 +575,35 @@ extern "C" int zk_verify_aggregate_coeffs_from_seed(const uint8_t seed[32], size
     ZK_API_END
 }
 
-extern "C" int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                           const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each) {
-    ZK_API_BEGIN(ctx)
-    if (!seed || !count || count > MAX_LANES - 3) return ZK_ERR_ARG;
+// the seeded form on a vkey, in the words of the entry points agg / batch (the located verdicts are the checked batch form's)
+static int aggregate_seeded(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host,
+                            const uint8_t seed[32], int* ok_all, int* ok_each, const char* agg, const char* batch) {
     std::vector<uint64_t> coeffs(2 * count);
     ZK_TRY(zk_verify_aggregate_coeffs_from_seed(seed, count, coeffs.data()));
-    ZK_TRY(aggregate_dev(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, coeffs.data(), ok_all, nullptr));
+    ZK_TRY(aggregate_dev(ctx, vk, count, inputs_host, ninp, proofs_host, coeffs.data(), ok_all, nullptr, agg));
     if (!ok_each) return ZK_OK;
     if (*ok_all) {
         for (size_t i = 0; i < count; i++) ok_each[i] = 1;
         return ZK_OK;
     }
-    return zk_groth16_verify_batch_checked(ctx, pk, count, inputs_host, inputs_per_proof, proofs_host, ok_each);
+    return verify_batch(ctx, vk, count, inputs_host, ninp, nullptr, proofs_host, ok_each, true, batch);
+}
+extern "C" int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                           const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !pk || !seed || !count || count > MAX_LANES - 3) return ZK_ERR_ARG;
+    const zk_vkey* vk;
+    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_aggregate", &vk));
+    return aggregate_seeded(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, seed, ok_all, ok_each, "zk_groth16_verify_aggregate",
+                            "zk_groth16_verify_batch");
+    ZK_API_END
+}
+extern "C" int zk_groth16_vkey_verify_aggregate(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
+                                                const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each) {
+    ZK_API_BEGIN(ctx)
+    if (!seed || !count || count > MAX_LANES - 3) return ZK_ERR_ARG;
+    return aggregate_seeded(ctx, vkey, count, inputs_host, inputs_per_proof, proofs_host, seed, ok_all, ok_each, "zk_groth16_vkey_verify_aggregate",
+                            "zk_groth16_vkey_verify_batch");
     ZK_API_END
 }
 

@@ -39,18 +39,28 @@ int put_vec(zk_ctx* ctx, uint8_t*& p, const zk_bases* b, int compressed) {
     p += n * zk_point_serialized_size(b ? b->group : 1, compressed);
     return ZK_OK;
 }
-int get_points(zk_ctx* ctx, const uint8_t*& p, const uint8_t* end, int group, size_t n, int compressed, zk_bases** out) {
+// (checked: with the subgroup test of zk_bases_deserialize_checked)
+int get_points(zk_ctx* ctx, const uint8_t*& p, const uint8_t* end, int group, size_t n, int compressed, zk_bases** out, bool checked = false) {
     const size_t bytes = n * zk_point_serialized_size(group, compressed);
     if ((size_t)(end - p) < bytes) ZK_FAIL(ctx, ZK_ERR_ARG, "deserialize: truncated input");
-    ZK_TRY(compressed ? zk_bases_deserialize_compressed(ctx, group, p, n, out) : zk_bases_deserialize_uncompressed(ctx, group, p, n, out));
+    if (checked) ZK_TRY(zk_bases_deserialize_checked(ctx, group, p, n, compressed, out));
+    else ZK_TRY(compressed ? zk_bases_deserialize_compressed(ctx, group, p, n, out) : zk_bases_deserialize_uncompressed(ctx, group, p, n, out));
     p += bytes;
     return ZK_OK;
 }
-int get_vec(zk_ctx* ctx, const uint8_t*& p, const uint8_t* end, int group, int compressed, zk_bases** out) {
+int get_vec(zk_ctx* ctx, const uint8_t*& p, const uint8_t* end, int group, int compressed, zk_bases** out, bool checked = false) {
     uint64_t n;
     if (!get_u64(p, end, &n)) ZK_FAIL(ctx, ZK_ERR_ARG, "deserialize: truncated input");
     if (n > ((uint64_t)1 << 32)) ZK_FAIL(ctx, ZK_ERR_ARG, "deserialize: implausible vector length");
-    return get_points(ctx, p, end, group, (size_t)n, compressed, out);
+    return get_points(ctx, p, end, group, (size_t)n, compressed, out, checked);
+}
+// VerifyingKey::serialize: alpha_g1 | beta_g2 | gamma_g2 | delta_g2 (g2s) | Vec gamma_abc_g1
+int vk_write(zk_ctx* ctx, const Affine<G1Field>& alpha, const Affine<G2Field> g2s[3], const zk_bases* abc, int compressed, uint8_t* p) {
+    ZK_TRY((ser_small<G1Field, zk_g1_affine>(ctx, &alpha, 1, 1, compressed, p)));
+    p += zk_point_serialized_size(1, compressed);
+    ZK_TRY((ser_small<G2Field, zk_g2_affine>(ctx, g2s, 3, 2, compressed, p)));
+    p += 3 * zk_point_serialized_size(2, compressed);
+    return put_vec(ctx, p, abc, compressed);
 }
 template <class F>
 int points_to_host(zk_ctx* ctx, const zk_bases* b, Affine<F>* out) {
@@ -75,13 +85,47 @@ extern "C" int zk_vk_serialize(zk_ctx* ctx, const zk_pk* pk, int compressed, uin
     ZK_API_BEGIN(ctx)
     if (!ctx || !pk || !out) return ZK_ERR_ARG;
     if (cap < zk_vk_serialized_size(pk, compressed)) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_vk_serialize: buffer too small");
-    uint8_t* p = out;
-    ZK_TRY((ser_small<G1Field, zk_g1_affine>(ctx, &pk->alpha_g1, 1, 1, compressed, p)));
-    p += zk_point_serialized_size(1, compressed);
     const Affine<G2Field> g2s[3] = {pk->beta_g2, pk->gamma_g2, pk->delta_g2};
-    ZK_TRY((ser_small<G2Field, zk_g2_affine>(ctx, g2s, 3, 2, compressed, p)));
-    p += 3 * zk_point_serialized_size(2, compressed);
-    return put_vec(ctx, p, pk->gamma_abc, compressed);
+    return vk_write(ctx, pk->alpha_g1, g2s, pk->gamma_abc, compressed, out);
+    ZK_API_END
+}
+extern "C" size_t zk_vkey_serialized_size(const zk_vkey* vkey, int compressed) {
+    if (!vkey) return 0;
+    return zk_point_serialized_size(1, compressed) * (1 + vkey->gamma_abc->n) + zk_point_serialized_size(2, compressed) * 3 + 8;
+}
+extern "C" int zk_vkey_serialize(zk_ctx* ctx, const zk_vkey* vkey, int compressed, uint8_t* out, size_t cap) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !vkey || !out) return ZK_ERR_ARG;
+    if (cap < zk_vkey_serialized_size(vkey, compressed)) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_vkey_serialize: buffer too small");
+    const Affine<G2Field> g2s[3] = {vkey->beta_g2, vkey->gamma_g2, vkey->delta_g2};
+    return vk_write(ctx, vkey->alpha_g1, g2s, vkey->gamma_abc, compressed, out);
+    ZK_API_END
+}
+// VerifyingKey::deserialize / deserialize_uncompressed (check_subgroup) or their unchecked forms held to the curve equation
+extern "C" int zk_vkey_deserialize(zk_ctx* ctx, const uint8_t* bytes, size_t len, int compressed, int check_subgroup, zk_vkey** out) {
+    ZK_API_BEGIN(ctx)
+    if (!ctx || !bytes || !out) return ZK_ERR_ARG;
+    const uint8_t *p = bytes, *end = bytes + len;
+    const bool checked = check_subgroup != 0;
+    zk_bases *one1 = nullptr, *three2 = nullptr, *abc = nullptr;
+    const char* part = "alpha_g1";
+    int rc = get_points(ctx, p, end, 1, 1, compressed, &one1, checked);
+    if (rc == ZK_OK) { part = "beta_g2 | gamma_g2 | delta_g2"; rc = get_points(ctx, p, end, 2, 3, compressed, &three2, checked); }
+    if (rc == ZK_OK) { part = "gamma_abc_g1"; rc = get_vec(ctx, p, end, 1, compressed, &abc, checked); }
+    if (rc != ZK_OK) ctx->last_error = std::string("zk_vkey_deserialize: ") + part + ": " + ctx->last_error;
+    if (rc == ZK_OK && p != end) { ctx->last_error = "zk_vkey_deserialize: trailing bytes after the verifying key"; rc = ZK_ERR_ARG; }
+    Affine<G1Field> alpha;
+    Affine<G2Field> g2s[3];
+    if (rc == ZK_OK) rc = points_to_host<G1Field>(ctx, one1, &alpha);
+    if (rc == ZK_OK) rc = points_to_host<G2Field>(ctx, three2, g2s);
+    zk_bases_free(ctx, one1); zk_bases_free(ctx, three2);
+    if (rc != ZK_OK) {
+        const std::string why = ctx->last_error;
+        zk_bases_free(ctx, abc);
+        ctx->last_error = why;
+        return rc;
+    }
+    return zk_vkey_make(ctx, alpha, g2s, abc, checked, out);
     ZK_API_END
 }
 extern "C" int zk_pk_serialize(zk_ctx* ctx, const zk_pk* pk, int compressed, uint8_t* out, size_t cap) {

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api import Bases, Context, ProvingKey
+from .api import Bases, Context, ProvingKey, VerifyingKey
 
 _G1_QUERIES = ("a_query", "b_g1_query", "h_query", "l_query", "gamma_abc_g1")
 
@@ -25,6 +25,12 @@ def verifying_key_bytes(ctx: Context, pk: ProvingKey, compressed: bool = True) -
     out = _buf(n)
     ctx._ck(ctx.lib.zk_vk_serialize(ctx.h, pk.h, int(compressed), out, n))
     return bytes(out)
+
+
+def verifying_key_from_bytes(ctx: Context, data: bytes, compressed: bool = True, check_subgroup: bool = False) -> VerifyingKey:
+    """VerifyingKey::deserialize[_uncompressed] through zk_vkey_deserialize: a resident verifying key (api.VerifyingKey) from the
+    bytes verifying_key_bytes / VerifyingKey.serialize write.  check_subgroup: the reference's deserialize in full."""
+    return ctx.vkey_deserialize(data, compressed=compressed, check_subgroup=check_subgroup)
 
 
 def proving_key_bytes(ctx: Context, pk: ProvingKey, compressed: bool = True) -> bytes:
