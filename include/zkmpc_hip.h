@@ -610,6 +610,41 @@ int zk_groth16_prepare_inputs_host(const zk_vk_host* vk, const zk_fr* inputs, si
  * (coordinate words below q, else ZK_ERR_ARG; on the curve is the caller's business, as for zk_pairing_products). */
 int zk_groth16_vkey_verify_prepared(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_g1_affine* prepared, const uint8_t* proofs_host,
                                     int check_subgroup, int* ok);
+/* ---- one batch over SEVERAL verifying keys (csrc/groth16_verify_keys.hip; the grouping and every launch size: csrc/verify_keys_plan.hpp)
+ * An application that proves several circuits per round has a key per circuit and wants one verdict for the round's proofs.  A batch:
+ *   vkeys[0 .. n_keys)   the keys; the same handle may appear twice, the two entries are then separate keys; an entry that no proof
+ *                        names contributes nothing (no lanes, no host work)
+ *   key_of[0 .. count)   the index into vkeys of proof i's key, in any order
+ *   proofs_host          count x 192 bytes in the caller's order
+ *   inputs_host          the public inputs CONCATENATED in proof order: proof i contributes zk_vkey_num_inputs(vkeys[key_of[i]])
+ *                        elements; inputs_len is their total
+ * With 128-bit coefficients r_i the batch is accepted iff
+ *     prod_i e(r_i A_i, B_i) . prod_k [ e(sum_{key_of[i]=k} r_i C_i, -delta_k) . e(sum_j s_{k,j} gamma_abc_k[j], -gamma_k) . e(s_{k,0} alpha_k, -beta_k) ] = 1
+ * with s_{k,.} the single-key form's sums over the proofs of key k: count + 3 K' Miller loops for K' keys with a proof, and ONE final
+ * exponentiation where a call per key runs K'.  The sums of r_i C_i per key come from one kernel whose launches grow with the
+ * logarithm of count, never with the keys; the sum_k (ninp_k + 2) multiplications of key points run on the helper threads or, from
+ * 2048 of them on, as one launch (ZK_VFY_KEYS_MUL=host|dev in the environment forces either).
+ * ok, ok_all, folded and ok_each, the all-zero folded on an early rejection, a zero coefficient, the subgroup tests that ALWAYS run in
+ * the folded forms and the seeded form's fallback to the checked batch form are the single-key forms' contracts word for word; ok and
+ * ok_each are in the caller's order.  `folded` is the product over the keys (zk_gt_mul) of what zk_groth16_vkey_verify_aggregate_coeffs
+ * returns for each key's proofs with their coefficients: the final exponentiation is multiplicative.  A batch that names ONE key is
+ * the single-key form: the same code, kernels and launches.  The batch form stages the proofs once, prepares the inputs with one
+ * launch per used key (the only step that grows with K') and holds each proof to ITS key's e(alpha, beta).
+ * ZK_ERR_ARG, with the first offending index in zk_last_error and the outputs untouched: a null pointer (an entry of vkeys too),
+ * count = 0 or n_keys = 0, a key_of entry that is not below n_keys, an inputs_len that is not the total above, an input that is not
+ * below r, count + 3 K' above 2^22 in the folded forms, 3 count above 2^22 in the batch form. */
+int zk_groth16_vkeys_verify_batch(zk_ctx* ctx, const zk_vkey* const* vkeys, size_t n_keys, size_t count, const uint32_t* key_of,
+                                  const zk_fr* inputs_host, size_t inputs_len, const uint8_t* proofs_host, int check_subgroup, int* ok);
+int zk_groth16_vkeys_verify_aggregate_coeffs(zk_ctx* ctx, const zk_vkey* const* vkeys, size_t n_keys, size_t count, const uint32_t* key_of,
+                                             const zk_fr* inputs_host, size_t inputs_len, const uint8_t* proofs_host, const uint64_t* coeffs,
+                                             int* ok_all, zk_gt* folded);
+int zk_groth16_vkeys_verify_aggregate(zk_ctx* ctx, const zk_vkey* const* vkeys, size_t n_keys, size_t count, const uint32_t* key_of,
+                                      const zk_fr* inputs_host, size_t inputs_len, const uint8_t* proofs_host, const uint8_t seed[32],
+                                      int* ok_all, int* ok_each);
+/* The folded form on the host (no device, no context; tests, O(1) batches): vks[0 .. n_keys) host views, the same batch, value and
+ * refusals (without zk_last_error: there is no context to keep it). */
+int zk_groth16_verify_aggregate_keys_host(const zk_vk_host* vks, size_t n_keys, size_t count, const uint32_t* key_of, const zk_fr* inputs,
+                                          size_t inputs_len, const uint8_t* proofs, const uint64_t* coeffs, int* ok_all, zk_gt* folded);
 /* PairingEngine::product_of_pairings for ONE long product: final_exponentiation(prod_{k < n} miller_loop(p[k], q[k])), the Miller
  * loops one per lane, their values folded by k_fq12_fold (a wave per block: a serial product per lane, then a tree through LDS),
  * the final exponentiation on the host; points as zk_pairing_products takes them.  n = 0, n above 2^22 or a null pointer: ZK_ERR_ARG. */

@@ -376,6 +376,11 @@ PROTOTYPES = {
     "zk_groth16_prepare_inputs": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
     "zk_groth16_prepare_inputs_host": (_I, [_P, _P, _SZ, _P]),
     "zk_groth16_vkey_verify_prepared": (_I, [_P, _P, _SZ, _P, _P, _I, _P]),
+    # several keys in one call (csrc/groth16_verify_keys.hip): ctx, vkeys, n_keys, count, key_of, inputs, inputs_len, proofs, ...
+    "zk_groth16_vkeys_verify_batch": (_I, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _I, _P]),
+    "zk_groth16_vkeys_verify_aggregate_coeffs": (_I, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_groth16_vkeys_verify_aggregate": (_I, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "zk_groth16_verify_aggregate_keys_host": (_I, [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
 }
 
 _lib = None

@@ -999,6 +999,40 @@ class Context:
         self._ck(fn(self.h, pk.h, count, _ptr(inp), inp.shape[1], _ptr(buf), seed, C.byref(ok), _ptr(ok_each) if each else None))
         return (bool(ok.value), ok_each[:count]) if each else bool(ok.value)
 
+    # ---- one batch over several verifying keys (csrc/groth16_verify_keys.hip) ----
+    def verify_keys_batch(self, vkeys, key_of, inputs, proofs, check_subgroup: bool = False) -> np.ndarray:
+        """zk_groth16_vkeys_verify_batch: Groth16::verify for a batch whose proofs belong to several keys.  vkeys: VerifyingKey
+        objects; key_of[i]: the index into vkeys of proof i's key; inputs: one Montgomery array per proof (as many elements as its
+        key has public inputs) or their concatenation in proof order; proofs: count x 192 bytes.  -> count verdicts, caller's order."""
+        handles, ko, inp, count, buf = _keys_args(vkeys, key_of, inputs, proofs)
+        ok = np.zeros(max(count, 1), dtype=np.int32)
+        self._ck(self.lib.zk_groth16_vkeys_verify_batch(self.h, handles, len(vkeys), count, _ptr(ko), _ptr(inp) if inp.size else None, inp.shape[0],
+                                                        _ptr(buf) if count else None, int(bool(check_subgroup)), _ptr(ok)))
+        return ok[:count]
+
+    def verify_keys_aggregate(self, vkeys, key_of, inputs, proofs, seed: bytes = None, coeffs=None, each: bool = False):
+        """The same batch as ONE folded pairing product over all keys (one Miller loop per proof and three per used key, one
+        final exponentiation); the subgroup test always runs.  coeffs (count, 2) uint64 or count integers:
+        zk_groth16_vkeys_verify_aggregate_coeffs -> (ok_all, folded GT value (72,)), the product over the keys of the single-key
+        values.  Otherwise the seeded form (seed: 32 bytes the provers could not predict; None: os.urandom) -> ok_all, or with
+        `each` (ok_all, count verdicts in the caller's order)."""
+        handles, ko, inp, count, buf = _keys_args(vkeys, key_of, inputs, proofs)
+        ok = C.c_int(0)
+        args = (self.h, handles, len(vkeys), count, _ptr(ko), _ptr(inp) if inp.size else None, inp.shape[0], _ptr(buf) if count else None)
+        if coeffs is not None:
+            if seed is not None or each:
+                raise ValueError("verify_keys_aggregate: coeffs excludes seed and each")
+            co = _coeff_array(coeffs, count)
+            folded = np.zeros(72, dtype=np.uint64)
+            self._ck(self.lib.zk_groth16_vkeys_verify_aggregate_coeffs(*args, _ptr(co) if count else None, C.byref(ok), _ptr(folded)))
+            return bool(ok.value), folded
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("a seed is 32 bytes")
+        ok_each = np.zeros(max(count, 1), dtype=np.int32) if each else None
+        self._ck(self.lib.zk_groth16_vkeys_verify_aggregate(*args, seed, C.byref(ok), _ptr(ok_each) if each else None))
+        return (bool(ok.value), ok_each[:count]) if each else bool(ok.value)
+
     def pairing_product_long(self, p: np.ndarray, q: np.ndarray) -> np.ndarray:
         """final_exponentiation(prod_k miller_loop(p[k], q[k])) of ONE long product: p (n, 12), q (n, 24) uint64 -> the GT value (72,)."""
         p, q, _ = _pairing_args(p, q, 1)
@@ -1399,4 +1433,48 @@ def groth16_verify_aggregate_host(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_a
     folded = np.zeros(72, dtype=np.uint64)
     _ck_host(_lib.load().zk_groth16_verify_aggregate_host(C.byref(vk), count, _ptr(inp), inp.shape[1], _ptr(buf), _ptr(co), C.byref(ok), _ptr(folded)),
              "zk_groth16_verify_aggregate_host")
+    return bool(ok.value), folded
+
+
+# ---- one batch over several verifying keys ----
+def _keys_batch(key_of, inputs, proofs):
+    """-> (key_of as uint32, the inputs concatenated as (n, 4) uint64, count, the proofs' bytes as uint8)"""
+    data = b"".join(bytes(p) for p in proofs) if isinstance(proofs, (list, tuple)) else bytes(proofs)
+    if len(data) % 192:
+        raise ValueError("proofs must be a whole number of 192-byte proofs")
+    count = len(data) // 192
+    ko = np.ascontiguousarray(key_of, dtype=np.uint32).reshape(-1)
+    if ko.shape[0] != count:
+        raise ValueError("one key index per proof")
+    if isinstance(inputs, np.ndarray):
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1, 4)
+    else:
+        rows = [np.asarray(x, dtype=np.uint64).reshape(-1, 4) for x in inputs]
+        if len(rows) != count:
+            raise ValueError("one input array per proof (or one concatenated array)")
+        inp = np.ascontiguousarray(np.concatenate(rows, axis=0) if rows else np.zeros((0, 4), np.uint64))
+    return ko, inp, count, np.frombuffer(data, dtype=np.uint8)
+
+
+def _keys_args(vkeys, key_of, inputs, proofs):
+    vkeys = list(vkeys)
+    if not all(isinstance(v, VerifyingKey) for v in vkeys):
+        raise TypeError("vkeys holds VerifyingKey objects")
+    handles = (C.c_void_p * max(len(vkeys), 1))(*[v.h for v in vkeys])
+    return (handles,) + _keys_batch(key_of, inputs, proofs)
+
+
+def groth16_verify_aggregate_keys_host(vks, key_of, inputs, proofs, coeffs):
+    """zk_groth16_verify_aggregate_keys_host: the folded check of one batch over several keys through the host arithmetic.  vks: one
+    dict per key with alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 (as groth16_verify_host takes them); key_of, inputs, proofs
+    as Context.verify_keys_aggregate; coeffs (count, 2) uint64 or count integers -> (ok_all, folded GT value (72,))."""
+    views = [_vk_host(**vk) for vk in vks]      # (keeps every gamma_abc array alive for the call)
+    arr = (_lib.VkHost * max(len(views), 1))(*[v[0] for v in views])
+    ko, inp, count, buf = _keys_batch(key_of, inputs, proofs)
+    co = _coeff_array(coeffs, count)
+    ok = C.c_int(0)
+    folded = np.zeros(72, dtype=np.uint64)
+    _ck_host(_lib.load().zk_groth16_verify_aggregate_keys_host(arr, len(views), count, _ptr(ko) if count else None, _ptr(inp) if inp.size else None,
+                                                              inp.shape[0], _ptr(buf) if count else None, _ptr(co) if count else None,
+                                                              C.byref(ok), _ptr(folded)), "zk_groth16_verify_aggregate_keys_host")
     return bool(ok.value), folded

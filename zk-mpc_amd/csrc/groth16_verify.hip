@@ -30,6 +30,7 @@
 #include "fsrng.hpp"
 #include "g1_lincomb.cuh"
 #include "groth16_int.hpp"
+#include "groth16_verify_int.hpp"
 #include "pairing.cuh"
 #include <string.h>
 
@@ -137,7 +138,7 @@ bool zk_vk_host_ok(const zk_vk_host* vk, size_t ninp) {
     return true;
 }
 
-namespace {
+namespace zkvfy {      // (groth16_verify_int.hpp: groth16_verify_keys.hip runs the same steps over several keys)
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
 HF coeff_fr(const uint64_t* c) { return HF::from_u128(c); }      // lo + 2^64 hi
@@ -201,7 +202,7 @@ int device_args_ok(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* in
 // and count words, "outside the subgroup" ORed into the off-curve flags.  tm, lap (both, or NULL): the caller's timers; tm gets the
 // two decompress launches as "<lap->prefix>k_decompress" and the two subgroup launches as "<lap->prefix>k_subgroup".
 int stage_proofs(zk_ctx* ctx, size_t count, const uint8_t* proofs_host, bool check_subgroup, uint32_t* bad_any, uint32_t* bad_ac, uint32_t* bad_b,
-                 uint32_t** ac, uint32_t** b, std::vector<uint8_t>* staging, ZkPhaseTimer* tm = nullptr, ZkHostLap* lap = nullptr) {
+                 uint32_t** ac, uint32_t** b, std::vector<uint8_t>* staging, ZkPhaseTimer* tm, ZkHostLap* lap) {
     const bool timed = tm && lap && tm->enabled;
     staging->resize(count * 192);
     uint8_t *g1c = staging->data(), *g2c = g1c + count * 2 * 48;
@@ -464,7 +465,8 @@ int aggregate_dev(zk_ctx* ctx, const zk_vkey* pk, size_t count, const zk_fr* inp
     return ZK_OK;
 }
 
-}  // namespace
+}  // namespace zkvfy
+using namespace zkvfy;
 
 extern "C" int zk_groth16_verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok) {
     ZK_API_BEGIN_NOCTX

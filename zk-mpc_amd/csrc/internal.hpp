@@ -38,6 +38,7 @@ int zk_fr_powers_launch(zk_ctx* ctx, const zk::Fr& base, const zk::Fr& start, si
 enum ZkLdsAttr {
     ZK_LDS_NTT, ZK_LDS_SORT_SMALL, ZK_LDS_SORT_SMALL_GROUP, ZK_LDS_SORT_GROUP, ZK_LDS_SHE, ZK_LDS_LINCOMB, ZK_LDS_SCALE_FOLD,
     ZK_LDS_TERM_FOLD_FULL, ZK_LDS_TERM_FOLD_GLV,      // g1_term_fold.hip: one slot per instantiation (an attribute belongs to ONE function)
+    ZK_LDS_SCALE_FOLD_KEYED,                          // groth16_verify_keys.hip
     ZK_LDS_COUNT
 };
 static_assert(ZK_LDS_COUNT <= sizeof(zk_ctx::lds_attr_done), "zk_ctx::lds_attr_done is too short");
@@ -388,8 +389,9 @@ int zk_pair_scratch(zk_ctx* ctx, size_t n, uint32_t** p_dev, uint32_t** q_dev, u
 int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, size_t n, uint32_t* ml_dev, bool ext = false);
 // product k of `pairs` consecutive Miller values, k < count, through the final exponentiation.  gt_dev (or NULL): the GT values in the
 // ABI's form.  ok_dev (or NULL): ok[k] = product k equals want_dev (packed, internal form) and bad_dev[k] (or NULL) is clear.
+// want_slot_dev (or NULL): product k is held to value want_slot_dev[k] of want_dev instead of to its first one.
 int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, uint32_t* gt_dev, const uint32_t* want_dev,
-                             const uint32_t* bad_dev, int* ok_dev);
+                             const uint32_t* bad_dev, int* ok_dev, const uint32_t* want_slot_dev = nullptr);
 // FE(the product of the n packed Miller values at ml_dev), n as large as a launch: folded on the device down to at most 64 partial
 // products (k_fq12_fold), those copied back, their product and the final exponentiation on the host (pairing.cuh over Fq264Field).
 // Waits for ctx->stream.  A caller that keeps timers passes both: with zk_set_profiling the fold launches go to tm as

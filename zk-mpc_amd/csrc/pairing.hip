@@ -68,9 +68,11 @@ __global__ void __launch_bounds__(64) k_miller(const uint32_t* __restrict__ p, c
 }
 
 // gt (or NULL): count GT values in the ABI's form.  ok (or NULL): ok[k] = the product equals `want` (packed, internal form) and
-// bad[k] (or NULL) is clear.
+// bad[k] (or NULL) is clear.  want_slot (or NULL): product k is held to value want_slot[k] of `want` (several keys: each proof
+// against its key's e(alpha, beta)); without, every product to value 0.
 __global__ void __launch_bounds__(64) k_pairing_finish(const uint32_t* __restrict__ ml, size_t pairs, size_t count, uint32_t* __restrict__ gt,
-                                                       const uint32_t* __restrict__ want, const uint32_t* __restrict__ bad, int* __restrict__ ok) {
+                                                       const uint32_t* __restrict__ want, const uint32_t* __restrict__ bad, int* __restrict__ ok,
+                                                       const uint32_t* __restrict__ want_slot) {
     const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (k >= count) return;
     Fq12<D2> acc = fq12_load16(ml + k * pairs * FQ12_WORDS, false);
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(64) k_pairing_finish(const uint32_t* __restric
     final_exponentiation<D2>(r, acc);
     if (gt) fq12_to_ext<D2>(gt + k * FQ12_WORDS, r);
     if (ok) {
-        const Fq12<D2> w = fq12_load16(want, false);
+        const Fq12<D2> w = fq12_load16(want + (want_slot ? (size_t)want_slot[k] * FQ12_WORDS : 0), false);
         ok[k] = (fq12_eq<D2>(r, w) && !(bad && bad[k])) ? 1 : 0;
     }
 }
@@ -209,8 +211,8 @@ int zk_miller_launch(zk_ctx* ctx, const uint32_t* p_dev, const uint32_t* q_dev, 
     return ZK_OK;
 }
 int zk_pairing_finish_launch(zk_ctx* ctx, const uint32_t* ml_dev, size_t pairs, size_t count, uint32_t* gt_dev, const uint32_t* want_dev,
-                             const uint32_t* bad_dev, int* ok_dev) {
-    hipLaunchKernelGGL(k_pairing_finish, zk_blocks64(count), 64, 0, ctx->stream, ml_dev, pairs, count, gt_dev, want_dev, bad_dev, ok_dev);
+                             const uint32_t* bad_dev, int* ok_dev, const uint32_t* want_slot_dev) {
+    hipLaunchKernelGGL(k_pairing_finish, zk_blocks64(count), 64, 0, ctx->stream, ml_dev, pairs, count, gt_dev, want_dev, bad_dev, ok_dev, want_slot_dev);
     ZK_HIP(ctx, hipGetLastError());
     return ZK_OK;
 }
