@@ -1,4 +1,4 @@
-"""Groth16 verification on the device (csrc/groth16_verify.hip) on keys with 0, 1, 2, 3, 8 and 33 public inputs: zk_groth16_verify_batch
+"""Groth16 verification on the device (csrc/groth16_verify_keys.hip on a one-slot plan, csrc/groth16_verify.hip) on keys with 0, 1, 2, 3, 8 and 33 public inputs: zk_groth16_verify_batch
 plain and checked, zk_groth16_verify_aggregate with coefficients, with a seed and with the verdicts of each.  The proofs are forged
 from the trapdoor (groth16_verify_cases.py) for input vectors placed where k_verify_prepare's sum and the folded sum degenerate;
 their points come from the scalars alone (zk_fixed_base_*_dev, serialised on the device), so a batch of thousands costs

@@ -7,7 +7,9 @@ both settings of ZK_VFY_KEYS_MUL.  The shapes are the smallest at which the keye
 with boundaries at lanes 63, 64 and 128, one proof per key, a listed key without a proof beside a segment of 65, each grouped,
 interleaved and reversed; 70 keys of one proof and one of three (more keys than lanes in a wave); a key with 130 public inputs (the
 cut of a key's terms into segments of 64 on the device multiplication path).  Then proofs under the wrong key, a C moved by cofactor
-torsion, segment sums at infinity and the doubling branch of the tree, a key listed twice, one key alone, the refusals.
+torsion, segment sums at infinity and the doubling branch of the tree, a key listed twice, one key alone, the refusals.  The
+single-key entry points are the same code on a one-slot plan, so "one key alone" compares two routes into one implementation; what
+holds it to an independent value is the second level of the keyed sum at 4 097 proofs of one key, against the host form on 8 proofs.
 
 Keys and proofs: groth16_keys_cases.py; the points come from the fixed-base calls on the device."""
 import contextlib
@@ -293,6 +295,72 @@ def test_one_used_key_is_the_single_key_call(ctx):
             got = ctx.verify_keys_batch(vks, [k] * count, K.flat_inputs(given), blob, check_subgroup=check).tolist()
             assert got == want and got == ctx.groth16_verify_batch(vkeys[2], inp3, blob, check_subgroup=check).tolist()
         assert ctx.verify_keys_aggregate(vks, [k] * count, K.flat_inputs(given), blob, seed=SEED, each=True)[1].tolist() == want
+
+
+# ---- 6: the second level of the keyed sum ---------------------------------------------------------------------------------------------
+LONG = 64 * 64 + 1      # 65 partials behind level 0: the smallest run with a second level (XYZZ in, no coefficients, the tree alone)
+POOL = 8
+
+
+def long_run(ctx):
+    """Two keys (3 inputs and 1), POOL forged proofs each, and LONG coefficients below 2^100 for the long key's proofs plus one for the
+    lone proof of the other key.  The long key's proof n is pool member n % POOL under r[n], so by bilinearity its folded value is the
+    host form's on the POOL proofs under R_j = sum of r[n] over n % POOL == j (below 2^113).  Member 5's first input is spoiled in
+    `given`.  The expected values are computed once, by the host form alone."""
+    if "long" not in _DEV:
+        four_keys, four_vkeys = four(ctx)
+        keys, vkeys = [four_keys[2], four_keys[1]], [four_vkeys[2], four_vkeys[1]]
+        rng = O.Prng(0x4097)
+        key_of = [0] * POOL + [1] * POOL
+        xs, abcs = K.forge_batch(keys, key_of, rng)
+        data = device_batch(ctx, keys, key_of, abcs)
+        given = [G.spoil(x, 0) if i == 5 else x for i, x in enumerate(xs)]
+        r = [(rng.fr() % (1 << 100)) | 1 for _ in range(LONG + 1)]
+        big = [sum(r[j:LONG:POOL]) for j in range(POOL)]
+        assert all(0 < v < 1 << 128 for v in big) and sum(big) == sum(r[:LONG])
+        want = {}
+        for name, vecs in (("clean", xs), ("spoiled", given)):
+            a_ok, a = single_host(keys)(0, G.inputs_mont(vecs[:POOL]), data[:POOL], big)
+            b_ok, b = single_host(keys)(1, G.inputs_mont(vecs[POOL:POOL + 1]), data[POOL:POOL + 1], r[LONG:])
+            assert b_ok is True and a_ok is (name == "clean") and api.gt_is_one(a) == a_ok and a.any()
+            want[name] = (a, api.gt_mul(a, b))
+        _DEV["long"] = SimpleNamespace(keys=keys, vkeys=vkeys, xs=xs, given=given, data=data, r=r, want=want)
+    return _DEV["long"]
+
+
+@pytest.mark.parametrize("shape", ["one_key", "two_keys_grouped", "lone_proof_in_the_middle"])
+def test_the_second_level_of_the_keyed_sum(ctx, shape):
+    """4 097 proofs of one key: 65 partials, so the keyed kernel runs a second time on its own output.  Alone (also through the
+    single-key entry points, which plan one slot), with one proof of a second key behind it (the last wave of level 0 and wave 1 of
+    level 1 hold pieces of two slots), and with that proof in the middle of the caller's order (a permutation that is not the identity)."""
+    L = long_run(ctx)
+    at = {"one_key": None, "two_keys_grouped": LONG, "lone_proof_in_the_middle": 2000}[shape]
+    member = [(0, n % POOL, L.r[n]) for n in range(LONG)]      # (key, pool member, coefficient) per proof
+    if at is not None:
+        member.insert(at, (1, 0, L.r[LONG]))
+    key_of = [k for k, _, _ in member]
+    rows = [k * POOL + j for k, j, _ in member]
+    coeffs = [c for _, _, c in member]
+    blob = L.data[rows].tobytes()
+    vkeys = L.vkeys if at is not None else L.vkeys[:1]
+    for name, vecs in (("spoiled", L.given), ("clean", L.xs)):
+        pool_in = [K.flat_inputs([x]) for x in vecs]
+        inp = np.concatenate([pool_in[i] for i in rows])
+        want = L.want[name][0 if at is None else 1]
+        for mode in MUL_MODES:
+            with keys_mul(mode):
+                ok, folded = ctx.verify_keys_aggregate(vkeys, key_of, inp, blob, coeffs=coeffs)
+                if at is None:
+                    s_ok, s_folded = ctx.groth16_verify_aggregate(vkeys[0], inp.reshape(LONG, 3, 4), blob, coeffs=coeffs)
+                    assert s_ok is ok and np.array_equal(s_folded, folded), (name, mode)
+            assert ok is (name == "clean") and api.gt_is_one(folded) == ok, (name, mode)
+            assert np.array_equal(folded, want), (name, mode)
+        verdicts = [0 if (name == "spoiled" and i == 5) else 1 for i in rows]
+        assert ctx.verify_keys_batch(vkeys, key_of, inp, blob, check_subgroup=True).tolist() == verdicts
+        if at is None:
+            assert ctx.groth16_verify_batch(vkeys[0], inp.reshape(LONG, 3, 4), blob).tolist() == verdicts
+        ok, each = ctx.verify_keys_aggregate(vkeys, key_of, inp, blob, seed=SEED, each=True)
+        assert ok is (name == "clean") and each.tolist() == verdicts
 
 
 def test_refusals_name_the_index_and_leave_the_outputs_untouched(ctx):

@@ -1,4 +1,4 @@
-"""The pairing kernels (csrc/pairing.hip) and zk_groth16_verify_batch (csrc/groth16_verify.hip) on the device, exact against the host instantiation of the same
+"""The pairing kernels (csrc/pairing.hip) and zk_groth16_verify_batch (csrc/groth16_verify_keys.hip) on the device, exact against the host instantiation of the same
 templates (which tests/test_pairing_host.py holds to the oracle) and, at a few points, against the oracle itself."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""Aggregated Groth16 verification on the device (csrc/groth16_verify.hip, csrc/pairing.hip): the two fold kernels alone against host arithmetic, word
+"""Aggregated Groth16 verification on the device (csrc/groth16_verify_keys.hip, csrc/groth16_verify.hip, csrc/pairing.hip): the two fold kernels alone against host arithmetic, word
 for word; the long pairing product against the host's product of the same pairs; the aggregate against its host instantiation
 (which tests/test_verify_aggregate_host.py holds to the oracle)."""
 import functools

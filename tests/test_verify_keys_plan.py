@@ -1,6 +1,6 @@
 """CPU: zk-mpc_amd/csrc/verify_keys_plan.hpp, from which Groth16 verification over several keys (csrc/groth16_verify_keys.hip) takes
-the grouping of a batch by key and every index of the keyed sum.  tests/verify_keys_plan_main.cpp drives the header alone: the
-stable permutation, segment and input offsets, unused keys, every refusal, and a replay of every lane of every level -- the kernel's
+the grouping of a batch by key and every index of the keyed sum -- the single-key entry points included, which plan one slot.  tests/verify_keys_plan_main.cpp drives the header alone: the
+stable permutation, segment and input offsets, unused keys, the identity plan of one key, every refusal, and a replay of every lane of every level -- the kernel's
 own lane function, its tree step for step with integers for points, against buffers of exactly the plan's sizes.  Built with g++,
 plain and once under the address and undefined-behaviour sanitizers, so a lane outside its buffer is a report."""
 import os

@@ -1,6 +1,7 @@
 // Drives zk-mpc_amd/csrc/verify_keys_plan.hpp alone (tests/test_verify_keys_plan.py builds it with g++, once under the address and
 // undefined-behaviour sanitizers): the grouping of a batch by key, and a replay of every lane of every level of the keyed sum with
-// integers for points -- the kernel's own lane function (keyed_lane), its tree step for step, buffers of exactly the plan's sizes.
+// integers for points -- the kernel's own lane function (keyed_lane), its tree step for step, buffers of exactly the plan's sizes --
+// and the identity plan of one key without a key_of array against the plan of an all-zero key_of.
 #include "verify_keys_plan.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -136,6 +137,28 @@ static void check_batch(size_t n_keys, const std::vector<uint32_t>& key_of, cons
     }
 }
 
+static bool same_level(const Level& a, const Level& b) { return a.n == b.n && a.n_out == b.n_out && a.seg_off == b.seg_off && a.mis == b.mis; }
+
+// the identity plan (key_of = NULL: what the single-key entry points build) against make_plan on an all-zero key_of, under n_keys
+// listed keys: every field but perm and pos, which it does not materialise and proof_at stands in for
+static void check_identity(size_t n_keys, size_t count, const std::vector<size_t>& ninp) {
+    const std::vector<uint32_t> zeros(count, 0);
+    Plan a, b;
+    size_t bad = 0;
+    CHECK(make_plan(n_keys, count, zeros.data(), ninp.data(), count * ninp[0], &a, &bad) == PLAN_OK);
+    CHECK(make_plan(n_keys, count, nullptr, ninp.data(), count * ninp[0], &b, &bad) == PLAN_OK);
+    CHECK(!a.identity() && b.identity() && b.perm.empty() && b.pos.empty() && b.slots() == 1);
+    for (size_t g = 0; g < count; g++) CHECK(a.proof_at(g) == g && b.proof_at(g) == g && a.pos[g] == g);
+    CHECK(a.n_keys == b.n_keys && a.count == b.count && a.used == b.used && a.slot_of_key == b.slot_of_key && a.seg_off == b.seg_off);
+    CHECK(a.in_off == b.in_off && a.gin_off == b.gin_off && a.mul_terms == b.mul_terms && a.fin_off == b.fin_off);
+    CHECK(a.part_a == b.part_a && a.part_b == b.part_b && a.meta_words == b.meta_words && a.levels.size() == b.levels.size());
+    for (size_t l = 0; l < a.levels.size(); l++) CHECK(same_level(a.levels[l], b.levels[l]));
+    CHECK(a.fold_lanes() == b.fold_lanes() && a.batch_lanes() == b.batch_lanes());
+    // the refusals that do not read key_of
+    CHECK(make_plan(n_keys, count, nullptr, ninp.data(), count * ninp[0] + 1, &b, &bad) == PLAN_INPUTS_LEN && bad == count * ninp[0]);
+    CHECK(make_plan(n_keys, 0, nullptr, ninp.data(), 0, &b, &bad) == PLAN_EMPTY);
+}
+
 static std::vector<uint32_t> runs_to_keys(const std::vector<uint32_t>& runs, int order) {
     std::vector<uint32_t> g;
     for (size_t k = 0; k < runs.size(); k++)
@@ -173,6 +196,19 @@ int main() {
     check_batch(1, std::vector<uint32_t>(4097, 0), {2}, 2);                      // 65 partials, as the single-key form's sum-down
     check_batch(1, std::vector<uint32_t>((size_t)1 << 18, 0), {1}, 2);
     check_batch(2, runs_to_keys({(1u << 18) + 1, (1u << 12) + 65}, 2), {1, 0}, 3);
+    for (size_t count : {(size_t)1, (size_t)63, (size_t)64, (size_t)65, (size_t)4096, (size_t)4097, (size_t)1 << 18, ((size_t)1 << 18) + 1})
+        for (size_t n : {(size_t)0, (size_t)2}) {                                // one key without key_of: the identity plan
+            check_identity(1, count, {n});
+            check_identity(3, count, {n, 5, 1});
+        }
+    {
+        Plan p;
+        size_t bad = 0;
+        const size_t big[1] = {MAX_INPUTS / 2 + 1};
+        CHECK(make_plan(1, MAX_LANES + 1, nullptr, big, 0, &p, &bad) == PLAN_TOO_MANY);
+        CHECK(make_plan(1, 2, nullptr, big, 2 * big[0], &p, &bad) == PLAN_TOO_MANY);
+        CHECK(make_plan(1, 1, nullptr, big, big[0], &p, &bad) == PLAN_OK && p.identity() && p.in_off[1] == big[0]);
+    }
     for (int t = 0; t < 200; t++) {                                              // random batches
         const size_t n_keys = 1 + rnd() % 9, count = 1 + rnd() % 700;
         std::vector<uint32_t> ko(count);

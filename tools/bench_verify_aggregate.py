@@ -5,8 +5,8 @@ mul-chain key, 1024 proofs from zk_groth16_prove_batch, repeated to the larger c
 
   python tools/bench_verify_aggregate.py [--out profiles/verify_aggregate.jsonl] [--counts 1,64,1024,16384,65536] [--reps 5]
 
-The two entry points alternate in one process.  One JSON line per count: the median ms per call of each after a warm-up call, their
-ratio, and one profiled aggregate call split into its phases (zk_set_profiling: device time by events for the kernels, host
+The two entry points alternate in one process.  One JSON line per count: the median ms per call of each after a warm-up call, the
+spread (max - min) of each over its repetitions, their ratio, and one profiled aggregate call split into its phases (zk_set_profiling: device time by events for the kernels, host
 wall-clock for the host parts)."""
 import argparse
 import json
@@ -69,7 +69,8 @@ def main():
         ctx.set_profiling(False)
         rows.append({"circuit": "mul_chain_2p10", "count": count, "aggregate_ms": round(median(t_agg), 3), "checked_batch_ms": round(median(t_chk), 3),
                      "checked_over_aggregate": round(median(t_chk) / median(t_agg), 2), "aggregate_us_per_proof": round(median(t_agg) / count * 1e3, 2),
-                     "reps": a.reps, "aggregate_phases_ms": phases})
+                     "reps": a.reps, "spread_ms": {"aggregate": round(max(t_agg) - min(t_agg), 3), "checked_batch": round(max(t_chk) - min(t_chk), 3)},
+                     "aggregate_phases_ms": phases})
         print(json.dumps(rows[-1]), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:

@@ -8,7 +8,8 @@ K keys with --ninp public inputs each (alpha .. delta shared, gamma_abc of their
 proofs dealt evenly (proof i belongs to key i mod K), forged from the trapdoor, their points from the fixed-base calls.  The loop is
 given its sub-batches ready made: splitting the batch by key is not charged to it.  The several-key call and the loop ALTERNATE in one
 process; the call runs under both settings of ZK_VFY_KEYS_MUL (the sum_k (ninp_k + 2) = (ninp + 2) K multiplications of key points on the host's
-helper threads, or as one launch).  One JSON line per (K, count): the median ms of each after a warm-up, the spread (max - min) of
+helper threads, or as one launch); the loop runs with the variable unset, so at K = 1 it is the same call under the library's own
+rule.  One JSON line per (K, count): the median ms of each after a warm-up, the spread (max - min) of
 each over its repetitions, and one profiled several-key call split into its phases (zk_set_profiling)."""
 import argparse
 import json
@@ -111,6 +112,7 @@ def main():
                 return ctx.verify_keys_aggregate(vkeys, key_of, inputs, proofs, coeffs=coeffs)
 
             def loop():
+                os.environ.pop("ZK_VFY_KEYS_MUL", None)      # the single-key calls as a caller gets them: the rule decides
                 return all([ctx.groth16_verify_aggregate(v, i, p, coeffs=c)[0] for v, i, p, c in subs])
 
             assert several("host")[0] is True and several("dev")[0] is True and loop() is True      # warm-up, and the verdicts

@@ -10,7 +10,8 @@
 //   groth16_multi.hip    one prover's MSMs spread over several devices
 //   groth16_shared.hip   create_proof over additive / SPDZ shares as one call (its host algebra: groth16_shared_int.hpp)
 //   groth16_shared_batch.hip  the same for many shared assignments of one key, with the exchanges of one proof
-//   groth16_verify.hip   Groth16::verify on the host and of batches on the device, proof by proof or folded  (verifier.rs:13-61)
+//   groth16_verify.hip   Groth16::verify on the host, prepare_inputs, the staging of a batch's proofs        (verifier.rs:13-61)
+//   groth16_verify_keys.hip  batches on the device, proof by proof or folded, over one key or several in one call
 #pragma once
 #include "hostfr.hpp"
 #include "hostgroup.hpp"

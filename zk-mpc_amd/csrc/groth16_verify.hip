@@ -1,30 +1,19 @@
-// groth16_verify.hip -- Groth16 verification: one proof on the host, a batch on the device proof by proof (zk_groth16_verify_batch),
-// and a batch as ONE folded pairing product (zk_groth16_verify_aggregate), with the building block the fold needs beyond pairing.hip:
-// the sum of many G1 points that belong to no resident table.
+// groth16_verify.hip -- Groth16 verification: one proof on the host (zk_groth16_verify_host), prepare_inputs on the host and on the
+// device, and the steps that the batch forms of groth16_verify_keys.hip run for any number of keys: the checks of one key's
+// arguments, the staging of the proofs, and the sum of many G1 points that belong to no resident table.
 //
 // Replaces (reference):
 //   Groth16::verify (prepare_inputs, verify_proof_with_prepared_inputs)          arkworks/groth16/src/verifier.rs:13-61
-// and for the folded form nothing the reference has for Groth16 (Groth16::verify is one proof); the fold itself is the one of its
-// KZG verifier (poly-commit/src/kzg10/mod.rs:345, batch_check: a random linear combination of the equations, one product of
-// pairings).  With coefficients r_i the batch holds iff
-//     prod_i e(r_i A_i, B_i) . e(sum_i r_i C_i, -delta) . e(sum_j s_j gamma_abc[j], -gamma) . e(s_0 alpha, -beta) = 1
-//     s_0 = sum_i r_i,  s_j = sum_i r_i x_{i,j} (mod r)
-// count + 3 Miller loops and ONE final exponentiation (the batch form: 3 count and count).
 //
-// Every device form runs on a zk_vkey (groth16_vkey.hip); the entry points that take a zk_pk are the same code on the vkey the key owns.
 // The prepared inputs gamma_abc[0] + sum x_i gamma_abc[i] of a batch are g1_prepare_inputs.hip's fixed-base kernel over the vkey's
 // window table (prepare_inputs_dev; a key too large for a table: zk_msm_g1_multi_dev over gamma_abc), also a public step of its own
 // (zk_groth16_prepare_inputs, zk_groth16_vkey_verify_prepared).
-//   k_verify_layout   one proof per lane: the proof's three pairs laid out for the Miller launch.
 //   k_g1_scale_fold   per lane an affine point and a 128-bit coefficient -> r P in XYZZ by g1_lincomb.cuh's fixed signed windows
 //                     (32 windows; the digit selects a table entry in LDS and a sign, never the control flow), then either per
 //                     lane the affine point (the Miller loop's P array) or a wave tree of complete additions through LDS and one
 //                     XYZZ partial per block, or both.  Without coefficients it only sums (XYZZ partials or affine points).
-// Both device forms check their arguments (device_args_ok) and stage their proofs (stage_proofs) by the same code and run pairing.hip's
-// kernels behind it; the folded form ends in its zk_miller_product.  The host re-launches the sum on its partials until at most 64
-// are left and finishes those itself in 64-bit limbs.
-// The folded form's key multiplications -- the ninp + 2 full-width multiplications s_0 alpha, s_j gamma_abc[j] -- run on the
-// context's helper threads under the device work, whatever ninp is (one MSM over gamma_abc in their place: DESIGN 6, not kept).
+// The host re-launches the sum on its partials until at most 64 are left (zk_g1_sum_down) and finishes those itself in 64-bit limbs;
+// the folded Groth16 form takes r_i A_i from it, the Marlin aggregate and g1_term_fold.hip its sums.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "fsrng.hpp"
@@ -44,24 +33,6 @@ constexpr size_t MAX_LANES = ZK_PAIRING_MAX_LANES;
 constexpr size_t SCALE_LDS = (size_t)LINCOMB_TAB * XW * 64 * 4;      // the window tables: 98 304 bytes
 constexpr size_t SUM_LDS = (size_t)XW * 64 * 4;                      // the tree alone: 12 288 bytes
 
-
-// ---- k_verify_layout --------------------------------------------------------------------------------------------------------------
-// proof k: P[3 k .. 3 k + 2] = A, prepared inputs, C;  Q[3 k ..] = B, -gamma, -delta.  ac holds (A_k, C_k) at 2 k, 2 k + 1 and b
-// holds B_k (table form, from the decompression, with their off-curve flags bad_ac / bad_b); prep the prepared inputs; negs = -gamma | -delta.
-__global__ void __launch_bounds__(64) k_verify_layout(size_t count, const uint32_t* __restrict__ prep, const uint32_t* __restrict__ ac,
-                                                      const uint32_t* __restrict__ b, const uint32_t* __restrict__ negs,
-                                                      const uint32_t* __restrict__ bad_ac, const uint32_t* __restrict__ bad_b, uint32_t* __restrict__ P,
-                                                      uint32_t* __restrict__ Q, uint32_t* __restrict__ bad) {
-    const size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    aff_store16<G1Field>(P, 3 * k, aff_load16<G1Field>(ac, 2 * k));
-    aff_store16<G1Field>(P, 3 * k + 1, aff_load16<G1Field>(prep, k));
-    aff_store16<G1Field>(P, 3 * k + 2, aff_load16<G1Field>(ac, 2 * k + 1));
-    aff_store16<G2Field>(Q, 3 * k, aff_load16<G2Field>(b, k));
-    aff_store16<G2Field>(Q, 3 * k + 1, aff_load16<G2Field>(negs, 0));
-    aff_store16<G2Field>(Q, 3 * k + 2, aff_load16<G2Field>(negs, 1));
-    bad[k] = bad_ac[2 * k] | bad_ac[2 * k + 1] | bad_b[k];
-}
 
 // ---- k_g1_scale_fold --------------------------------------------------------------------------------------------------------------
 // lane g < n: point g in_step of `in` (affine table form, or XYZZ with in_xyzz) times coeffs[4 g ..] (128 bits, low word first;
@@ -138,19 +109,9 @@ bool zk_vk_host_ok(const zk_vk_host* vk, size_t ninp) {
     return true;
 }
 
-namespace zkvfy {      // (groth16_verify_int.hpp: groth16_verify_keys.hip runs the same steps over several keys)
+namespace zkvfy {      // (groth16_verify_int.hpp: the batch forms of groth16_verify_keys.hip run these steps)
 
 // ---- host halves --------------------------------------------------------------------------------------------------------------------
-HF coeff_fr(const uint64_t* c) { return HF::from_u128(c); }      // lo + 2^64 hi
-// s[0] = sum r_i, s[j + 1] = sum r_i x_{i,j} over the proofs [lo, hi)
-void coeff_sums(const uint64_t* coeffs, const zk_fr* inputs, size_t ninp, size_t lo, size_t hi, HF* s) {
-    for (size_t j = 0; j <= ninp; j++) s[j] = HF::zero();
-    for (size_t i = lo; i < hi; i++) {
-        const HF r = coeff_fr(coeffs + 2 * i);
-        s[0] = s[0] + r;
-        for (size_t j = 0; j < ninp; j++) s[j + 1] = s[j + 1] + r * HF::from_abi(inputs[i * ninp + j]);
-    }
-}
 void coeff_words(const uint64_t* c, uint32_t k[8]) {
     k[0] = (uint32_t)c[0]; k[1] = (uint32_t)(c[0] >> 32); k[2] = (uint32_t)c[1]; k[3] = (uint32_t)(c[1] >> 32);
     k[4] = k[5] = k[6] = k[7] = 0;
@@ -162,7 +123,6 @@ bool inputs_below_r(const zk_fr* inputs, size_t n) {
         if (!zk_fr_words_valid(inputs[i].l)) return false;
     return true;
 }
-bool vk_host_ok(const zk_vk_host* vk, size_t ninp) { return zk_vk_host_ok(vk, ninp); }
 // prepare_inputs (verifier.rs:18-33) on host values
 XYZZ<H1> host_prepare(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs) {
     XYZZ<H1> acc = xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[0]));
@@ -187,14 +147,7 @@ int inputs_ok(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_
     if (!inputs_below_r(inputs_host, count * ninp)) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": a public input is not below r");
     return ZK_OK;
 }
-// what the device forms refuse of their key and arguments, in the words of the entry point `entry` (a zk_pk without verifying-key
-// parts is refused where its vkey is asked for: zk_pk_vkey)
-int device_args_ok(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, size_t max_count,
-                   const char* entry) {
-    if (!ctx || !vk || !count || !proofs_host || count > max_count) return ZK_ERR_ARG;
-    return inputs_ok(ctx, vk, count, inputs_host, ninp, entry);
-}
-// The points of count proofs onto the device, for both device forms: the compressed (A_k, C_k) and the compressed B_k split out of
+// The points of count proofs onto the device, for every device form: the compressed (A_k, C_k) and the compressed B_k split out of
 // the proofs' bytes into *staging (the caller keeps it until it has waited for the stream: the uploads read it), uploaded and
 // decompressed into table form -- (*ac)[2 k], (*ac)[2 k + 1] = A_k, C_k and (*b)[k] = B_k -- and with check_subgroup tested for
 // membership, one launch over the 2 count G1 points and one over the count G2 points whatever count is.  bad_any: one word, cleared
@@ -232,10 +185,10 @@ int stage_proofs(zk_ctx* ctx, size_t count, const uint8_t* proofs_host, bool che
     return ZK_OK;
 }
 
-// ---- proof by proof -------------------------------------------------------------------------------------------------------------------
+// ---- one proof, and prepare_inputs -------------------------------------------------------------------------------------------------------------------
 // Groth16::verify on host values: e(A, B) e(prepared, -gamma) e(C, -delta) == e(alpha, beta)
 int verify_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, const uint8_t proof[192], int* ok, bool check_subgroup) {
-    if (!proof || !ok || (n_inputs && !inputs) || !vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
+    if (!proof || !ok || (n_inputs && !inputs) || !zk_vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
     *ok = 0;
     Affine<G1Field> a, c;
     Affine<G2Field> b;
@@ -285,186 +238,6 @@ int prepare_inputs_dev(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr
     return ZK_OK;
 }
 
-// The per-point flags of the staging (off the curve, with check_subgroup outside the subgroup) go into each proof's verdict by
-// k_verify_layout.  prepared (or NULL): the caller's prepared inputs in place of inputs_host (verify_proof_with_prepared_inputs).
-int verify_batch(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const zk_g1_affine* prepared,
-                 const uint8_t* proofs_host, int* ok, bool check_subgroup, const char* entry) {
-    if (!ok) return ZK_ERR_ARG;
-    std::vector<uint32_t> prep_w;
-    if (prepared) {
-        if (!ctx || !vk || !count || !proofs_host || count > MAX_LANES / 3) return ZK_ERR_ARG;
-        for (size_t k = 0; k < count; k++)
-            if (!zk_words_below_q((const uint64_t*)&prepared[k], 2)) ZK_FAIL(ctx, ZK_ERR_ARG, std::string(entry) + ": a prepared input's coordinate is not below q");
-        prep_w.resize(count * 24);
-        for (size_t k = 0; k < count; k++) aff_store<G1Field>(&prep_w[24 * k], host_aff_from_abi<G1Field>((const uint64_t*)&prepared[k]));
-    } else {
-        ZK_TRY(device_args_ok(ctx, vk, count, inputs_host, ninp, proofs_host, MAX_LANES / 3, entry));
-    }
-    struct Consts { uint32_t negs[2 * 48]; uint32_t want[FQ12_WORDS]; } cs;      // the key's constants
-    aff_store<G2Field>(cs.negs, vk->neg_gamma_g2);
-    aff_store<G2Field>(cs.negs + 48, vk->neg_delta_g2);
-    memcpy(cs.want, vk->e_alpha_beta, sizeof cs.want);
-
-    const size_t n = 3 * count;
-    uint32_t *d_cs, *ac, *b, *flags, *P, *Q, *ml, *prep;
-    ZK_TRY(zk_scratch(ctx, "vfy_cs", sizeof cs, (void**)&d_cs));
-    ZK_TRY(zk_scratch(ctx, "vfy_flags", (1 + 5 * count) * 4 + count * 4, (void**)&flags));      // any | bad_ac | bad_b | bad | inf | ok
-    ZK_TRY(zk_scratch(ctx, "vfy_prep", count * 96, (void**)&prep));
-    ZK_TRY(zk_pair_scratch(ctx, n, &P, &Q, &ml));
-    uint32_t *bad_any = flags, *bad_ac = flags + 1, *bad_b = bad_ac + 2 * count, *bad = bad_b + count, *inf = bad + count;
-    int* d_ok = (int*)(inf + count);
-    hipStream_t st = ctx->stream;
-    ZK_HIP(ctx, hipMemcpyAsync(d_cs, &cs, sizeof cs, hipMemcpyHostToDevice, st));
-    std::vector<uint8_t> staging;
-    ZK_TRY(stage_proofs(ctx, count, proofs_host, check_subgroup, bad_any, bad_ac, bad_b, &ac, &b, &staging));
-    if (prepared) ZK_HIP(ctx, hipMemcpyAsync(prep, prep_w.data(), count * 96, hipMemcpyHostToDevice, st));
-    else ZK_TRY(prepare_inputs_dev(ctx, vk, count, inputs_host, prep, inf));
-    hipLaunchKernelGGL(k_verify_layout, zk_blocks64(count), 64, 0, st, count, (const uint32_t*)prep, (const uint32_t*)ac, (const uint32_t*)b,
-                       (const uint32_t*)d_cs, (const uint32_t*)bad_ac, (const uint32_t*)bad_b, P, Q, bad);
-    ZK_HIP(ctx, hipGetLastError());
-    ZK_TRY(zk_miller_launch(ctx, P, Q, n, ml));
-    ZK_TRY(zk_pairing_finish_launch(ctx, ml, 3, count, nullptr, d_cs + 2 * 48, bad, d_ok));
-    ZK_HIP(ctx, hipMemcpyAsync(ok, d_ok, count * sizeof(int), hipMemcpyDeviceToHost, st));
-    ZK_HIP(ctx, hipStreamSynchronize(st));
-    return ZK_OK;
-}
-
-// ---- folded -----------------------------------------------------------------------------------------------------------------------------
-// what both aggregate forms refuse beyond their key's checks
-bool agg_args_ok(size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const uint64_t* coeffs, const int* ok_all) {
-    if (!count || !proofs || !coeffs || !ok_all || count > MAX_LANES - 3 || (ninp && !inputs)) return false;
-    return true;
-}
-
-int aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size_t ninp, const uint8_t* proofs, const uint64_t* coeffs, int* ok_all,
-                   zk_gt* folded) {
-    if (!agg_args_ok(count, inputs, ninp, proofs, coeffs, ok_all) || !vk_host_ok(vk, ninp) || !inputs_below_r(inputs, count * ninp)) return ZK_ERR_ARG;
-    *ok_all = 0;
-    if (folded) memset(folded, 0, sizeof *folded);
-    std::vector<Affine<H1>> P(count + 3);
-    std::vector<Affine<H2>> Q(count + 3);
-    XYZZ<H1> c_sum = xyzz_inf<H1>();
-    for (size_t i = 0; i < count; i++) {
-        const uint8_t* pr = proofs + i * 192;
-        Affine<G1Field> a, c;
-        Affine<G2Field> b;
-        if (!host_proof_points(pr, true, &a, &b, &c)) return ZK_OK;
-        uint32_t k[8];
-        coeff_words(coeffs + 2 * i, k);
-        P[i] = xyzz_to_affine<H1>(host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(a)), k));
-        Q[i] = aff_to_host64<G2Field>(b);
-        c_sum = xyzz_add<H1>(c_sum, host64_scalar_mul<H1>(xyzz_from_affine<H1>(aff_to_host64<G1Field>(c)), k));
-    }
-    std::vector<HF> s(ninp + 1);
-    coeff_sums(coeffs, inputs, ninp, 0, count, s.data());
-    XYZZ<H1> pi = xyzz_inf<H1>();
-    for (size_t j = 0; j <= ninp; j++) {
-        uint32_t k[8];
-        s[j].canon_words(k);
-        pi = xyzz_add<H1>(pi, host64_scalar_mul<H1>(xyzz_from_affine<H1>(zk_host_g1(&vk->gamma_abc_g1[j])), k));
-    }
-    uint32_t k0[8];
-    s[0].canon_words(k0);
-    P[count] = xyzz_to_affine<H1>(c_sum);
-    Q[count] = aff_neg<H2>(zk_host_g2(&vk->delta_g2));
-    P[count + 1] = xyzz_to_affine<H1>(pi);
-    Q[count + 1] = aff_neg<H2>(zk_host_g2(&vk->gamma_g2));
-    P[count + 2] = xyzz_to_affine<H1>(host64_scalar_mul<H1>(xyzz_from_affine<H1>(zk_host_g1(&vk->alpha_g1)), k0));
-    Q[count + 2] = aff_neg<H2>(zk_host_g2(&vk->beta_g2));
-    Fq12<H2> r;
-    pairing_product<H2>(r, P.data(), Q.data(), count + 3);
-    *ok_all = fq12_eq<H2>(r, fq12_one<H2>()) ? 1 : 0;
-    if (folded) zk_host_gt_out(folded, r);
-    return ZK_OK;
-}
-
-int aggregate_dev(zk_ctx* ctx, const zk_vkey* pk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host, const uint64_t* coeffs,
-                  int* ok_all, zk_gt* folded, const char* entry) {
-    if (!agg_args_ok(count, inputs_host, ninp, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
-    ZK_TRY(device_args_ok(ctx, pk, count, inputs_host, ninp, proofs_host, MAX_LANES - 3, entry));
-    *ok_all = 0;
-    if (folded) memset(folded, 0, sizeof *folded);
-    const std::vector<uint32_t>& abc_w = pk->abc_host;
-
-    const size_t n = count + 3, n_part = zk_blocks64(count);
-    uint32_t *d_coef, *ac, *b, *flags, *P, *Q, *ml, *part_a, *part_b;
-    ZK_TRY(zk_scratch(ctx, "agg_coef", count * 16, (void**)&d_coef));
-    ZK_TRY(zk_scratch(ctx, "agg_flags", 4, (void**)&flags));
-    ZK_TRY(zk_pair_scratch(ctx, n, &P, &Q, &ml));
-    ZK_TRY(zk_fold_scratch(ctx, n, nullptr, nullptr));        // (reserved now: zk_miller_product takes them with the kernels in flight)
-    ZK_TRY(zk_scratch(ctx, "agg_part_a", n_part * XW * 4, (void**)&part_a));
-    ZK_TRY(zk_scratch(ctx, "agg_part_b", (n_part / 64 + 1) * XW * 4, (void**)&part_b));
-    hipStream_t st = ctx->stream;
-    ZK_HIP(ctx, hipMemcpyAsync(d_coef, coeffs, count * 16, hipMemcpyHostToDevice, st));
-    ZkPhaseTimer tm(ctx);                         // with zk_set_profiling: "verify_aggregate.<phase>", device time by events
-    ZkHostLap lap{ctx, "verify_aggregate."};      // ... and host wall-clock since the lap before
-    // the subgroup tests ALWAYS: the fold's soundness argument needs prime-order groups, and the Miller loop is not bilinear for a B outside G2
-    std::vector<uint8_t> staging;
-    ZK_TRY(stage_proofs(ctx, count, proofs_host, true, flags, nullptr, nullptr, &ac, &b, &staging, &tm, &lap));      // "k_decompress", "k_subgroup"
-    tm.begin("verify_aggregate.k_scale");
-    ZK_TRY(zk_g1_scale_fold_launch(ctx, ac, 2, false, d_coef, count, P, nullptr));                    // r_i A_i -> P[0 .. count)
-    ZK_HIP(ctx, hipMemcpyAsync(Q, b, count * 192, hipMemcpyDeviceToDevice, st));
-    ZK_TRY(zk_g1_scale_fold_launch(ctx, ac + 24, 2, false, d_coef, count, nullptr, part_a));          // sum r_i C_i, a partial per wave
-    size_t m_part = n_part;
-    uint32_t* part;
-    ZK_TRY(zk_g1_sum_down(ctx, part_a, part_b, &m_part, &part));
-    tm.end();
-
-    // under the device work: the coefficient sums over ranges of proofs, then the ninp + 2 multiplications of key points side by side
-    const size_t tasks = std::min<size_t>(8, (count + 4095) / 4096);
-    std::vector<HF> part_s(tasks * (ninp + 1)), s(ninp + 1, HF::zero());
-    const size_t per = (count + tasks - 1) / tasks;
-    zk_over_ranges(ctx, tasks, tasks, [&](size_t lo, size_t hi) {
-        for (size_t t = lo; t < hi; t++) coeff_sums(coeffs, inputs_host, ninp, std::min(count, t * per), std::min(count, (t + 1) * per), &part_s[t * (ninp + 1)]);
-    });
-    for (size_t t = 0; t < tasks; t++)
-        for (size_t j = 0; j <= ninp; j++) s[j] = s[j] + part_s[t * (ninp + 1) + j];
-    std::vector<XYZZ<H1>> key_mul(ninp + 2);      // s_j gamma_abc[j], then s_0 alpha
-    auto mul_key = [&](size_t j) {
-        uint32_t k[8];
-        s[j <= ninp ? j : 0].canon_words(k);
-        const Affine<G1Field> p = j <= ninp ? aff_load<G1Field>(&abc_w[24 * j]) : pk->alpha_g1;
-        const XYZZ<H1> x = xyzz_from_affine<H1>(aff_to_host64<G1Field>(p));
-        key_mul[j] = pk->points_in_subgroup ? host64_scalar_mul_glv(x, k) : host64_scalar_mul<H1>(x, k);
-    };
-    {
-        std::vector<ZkTask<void>> ts;
-        for (size_t j = 1; j < ninp + 2; j++) ts.push_back(zk_async(ctx, [&mul_key, j] { mul_key(j); }));
-        mul_key(0);
-    }
-    lap.lap("host_sums");
-    // (only now: a copy into pageable memory waits for the stream, and the host work above is meant to run under the kernels)
-    std::vector<uint32_t> h_part(m_part * XW);
-    uint32_t bad = 0;
-    ZK_HIP(ctx, hipMemcpyAsync(h_part.data(), part, h_part.size() * 4, hipMemcpyDeviceToHost, st));
-    ZK_HIP(ctx, hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, st));
-    ZK_HIP(ctx, hipStreamSynchronize(st));
-    lap.lap("wait_scale");
-    if (bad) { tm.resolve(); return ZK_OK; }                       // a point off its curve or outside its subgroup: ok_all = 0, folded all-zero
-
-    XYZZ<H1> c_sum = xyzz_inf<H1>(), pi = xyzz_inf<H1>();
-    for (size_t i = 0; i < m_part; i++) c_sum = xyzz_add<H1>(c_sum, xyzz_to_host64<G1Field>(xyzz_load<G1Field>(&h_part[i * XW])));
-    for (size_t j = 0; j <= ninp; j++) pi = xyzz_add<H1>(pi, key_mul[j]);
-    struct Tail { uint32_t p[3 * 24]; uint32_t q[3 * 48]; } tail;
-    aff_store<G1Field>(tail.p, aff_from_host64<G1Field>(xyzz_to_affine<H1>(c_sum)));
-    aff_store<G1Field>(tail.p + 24, aff_from_host64<G1Field>(xyzz_to_affine<H1>(pi)));
-    aff_store<G1Field>(tail.p + 48, aff_from_host64<G1Field>(xyzz_to_affine<H1>(key_mul[ninp + 1])));
-    aff_store<G2Field>(tail.q, aff_neg<G2Field>(pk->delta_g2));
-    aff_store<G2Field>(tail.q + 48, aff_neg<G2Field>(pk->gamma_g2));
-    aff_store<G2Field>(tail.q + 96, aff_neg<G2Field>(pk->beta_g2));
-    ZK_HIP(ctx, hipMemcpyAsync(P + count * 24, tail.p, sizeof tail.p, hipMemcpyHostToDevice, st));
-    ZK_HIP(ctx, hipMemcpyAsync(Q + count * 48, tail.q, sizeof tail.q, hipMemcpyHostToDevice, st));
-    tm.begin("verify_aggregate.k_miller");
-    ZK_TRY(zk_miller_launch(ctx, P, Q, n, ml));
-    tm.end();
-    Fq12<H2> r;
-    ZK_TRY(zk_miller_product(ctx, ml, n, &r, &tm, &lap));      // "k_fold", "wait_miller", "host_finish"
-    tm.resolve();
-    *ok_all = fq12_eq<H2>(r, fq12_one<H2>()) ? 1 : 0;
-    if (folded) zk_host_gt_out(folded, r);
-    return ZK_OK;
-}
-
 }  // namespace zkvfy
 using namespace zkvfy;
 
@@ -480,7 +253,7 @@ extern "C" int zk_groth16_verify_host_checked(const zk_vk_host* vk, const zk_fr*
 }
 extern "C" int zk_groth16_prepare_inputs_host(const zk_vk_host* vk, const zk_fr* inputs, size_t n_inputs, zk_g1_affine* out) {
     ZK_API_BEGIN_NOCTX
-    if (!out || (n_inputs && !inputs) || !vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
+    if (!out || (n_inputs && !inputs) || !zk_vk_host_ok(vk, n_inputs) || !inputs_below_r(inputs, n_inputs)) return ZK_ERR_ARG;
     host_aff_to_abi<G1Field>((uint64_t*)out, aff_from_host64<G1Field>(xyzz_to_affine<H1>(host_prepare(vk, inputs, n_inputs))));
     return ZK_OK;
     ZK_API_END
@@ -507,63 +280,6 @@ extern "C" int zk_groth16_prepare_inputs(zk_ctx* ctx, const zk_vkey* vkey, size_
     ZK_API_END
 }
 
-extern "C" int zk_groth16_vkey_verify_batch(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                            const uint8_t* proofs_host, int check_subgroup, int* ok) {
-    ZK_API_BEGIN(ctx)
-    return verify_batch(ctx, vkey, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, check_subgroup != 0, "zk_groth16_vkey_verify_batch");
-    ZK_API_END
-}
-extern "C" int zk_groth16_vkey_verify_prepared(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_g1_affine* prepared, const uint8_t* proofs_host,
-                                               int check_subgroup, int* ok) {
-    ZK_API_BEGIN(ctx)
-    if (!prepared) return ZK_ERR_ARG;
-    return verify_batch(ctx, vkey, count, nullptr, 0, prepared, proofs_host, ok, check_subgroup != 0, "zk_groth16_vkey_verify_prepared");
-    ZK_API_END
-}
-extern "C" int zk_groth16_vkey_verify_aggregate_coeffs(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                                       const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
-    ZK_API_BEGIN(ctx)
-    return aggregate_dev(ctx, vkey, count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all, folded, "zk_groth16_vkey_verify_aggregate");
-    ZK_API_END
-}
-
-// ---- the forms on a proving key: the same code on the vkey the key owns ----------------------------------------------------------
-extern "C" int zk_groth16_verify_batch(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                       const uint8_t* proofs_host, int* ok) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !pk || !count || !proofs_host || !ok) return ZK_ERR_ARG;
-    const zk_vkey* vk;
-    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_batch", &vk));
-    return verify_batch(ctx, vk, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, false, "zk_groth16_verify_batch");
-    ZK_API_END
-}
-extern "C" int zk_groth16_verify_batch_checked(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                               const uint8_t* proofs_host, int* ok) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !pk || !count || !proofs_host || !ok) return ZK_ERR_ARG;
-    const zk_vkey* vk;
-    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_batch", &vk));
-    return verify_batch(ctx, vk, count, inputs_host, inputs_per_proof, nullptr, proofs_host, ok, true, "zk_groth16_verify_batch");
-    ZK_API_END
-}
-
-extern "C" int zk_groth16_verify_aggregate_coeffs(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                                  const uint8_t* proofs_host, const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !pk || !agg_args_ok(count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all)) return ZK_ERR_ARG;
-    const zk_vkey* vk;
-    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_aggregate", &vk));
-    return aggregate_dev(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, coeffs, ok_all, folded, "zk_groth16_verify_aggregate");
-    ZK_API_END
-}
-
-extern "C" int zk_groth16_verify_aggregate_host(const zk_vk_host* vk, size_t count, const zk_fr* inputs, size_t inputs_per_proof, const uint8_t* proofs,
-                                                const uint64_t* coeffs, int* ok_all, zk_gt* folded) {
-    ZK_API_BEGIN_NOCTX
-    return aggregate_host(vk, count, inputs, inputs_per_proof, proofs, coeffs, ok_all, folded);
-    ZK_API_END
-}
-
 extern "C" int zk_verify_aggregate_coeffs_from_seed(const uint8_t seed[32], size_t count, uint64_t* coeffs_out) {
     ZK_API_BEGIN_NOCTX
     if (!seed || (count && !coeffs_out)) return ZK_ERR_ARG;
@@ -574,38 +290,6 @@ extern "C" int zk_verify_aggregate_coeffs_from_seed(const uint8_t seed[32], size
         if (!(coeffs_out[2 * i] | coeffs_out[2 * i + 1])) coeffs_out[2 * i] = 1;
     }
     return ZK_OK;
-    ZK_API_END
-}
-
-// the seeded form on a vkey, in the words of the entry points agg / batch (the located verdicts are the checked batch form's)
-static int aggregate_seeded(zk_ctx* ctx, const zk_vkey* vk, size_t count, const zk_fr* inputs_host, size_t ninp, const uint8_t* proofs_host,
-                            const uint8_t seed[32], int* ok_all, int* ok_each, const char* agg, const char* batch) {
-    std::vector<uint64_t> coeffs(2 * count);
-    ZK_TRY(zk_verify_aggregate_coeffs_from_seed(seed, count, coeffs.data()));
-    ZK_TRY(aggregate_dev(ctx, vk, count, inputs_host, ninp, proofs_host, coeffs.data(), ok_all, nullptr, agg));
-    if (!ok_each) return ZK_OK;
-    if (*ok_all) {
-        for (size_t i = 0; i < count; i++) ok_each[i] = 1;
-        return ZK_OK;
-    }
-    return verify_batch(ctx, vk, count, inputs_host, ninp, nullptr, proofs_host, ok_each, true, batch);
-}
-extern "C" int zk_groth16_verify_aggregate(zk_ctx* ctx, const zk_pk* pk, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                           const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each) {
-    ZK_API_BEGIN(ctx)
-    if (!ctx || !pk || !seed || !count || count > MAX_LANES - 3) return ZK_ERR_ARG;
-    const zk_vkey* vk;
-    ZK_TRY(zk_pk_vkey(ctx, pk, "zk_groth16_verify_aggregate", &vk));
-    return aggregate_seeded(ctx, vk, count, inputs_host, inputs_per_proof, proofs_host, seed, ok_all, ok_each, "zk_groth16_verify_aggregate",
-                            "zk_groth16_verify_batch");
-    ZK_API_END
-}
-extern "C" int zk_groth16_vkey_verify_aggregate(zk_ctx* ctx, const zk_vkey* vkey, size_t count, const zk_fr* inputs_host, size_t inputs_per_proof,
-                                                const uint8_t* proofs_host, const uint8_t seed[32], int* ok_all, int* ok_each) {
-    ZK_API_BEGIN(ctx)
-    if (!seed || !count || count > MAX_LANES - 3) return ZK_ERR_ARG;
-    return aggregate_seeded(ctx, vkey, count, inputs_host, inputs_per_proof, proofs_host, seed, ok_all, ok_each, "zk_groth16_vkey_verify_aggregate",
-                            "zk_groth16_vkey_verify_batch");
     ZK_API_END
 }
 

@@ -15,6 +15,9 @@
 // where mis[s] counts the boundaries seg_off[1 .. s] that are no multiple of 64 (a boundary at a wave's edge cuts no wave in two).
 // The partials of a level are the lanes of the next one, with their own seg_off; the levels end once no slot has more than 64
 // partials, which the host adds.  The number of levels depends on the longest segment alone -- never on the number of keys.
+//
+// ONE key is the plan with one slot and the identity permutation: key_of = NULL puts every proof under key 0, and that plan does
+// not materialise perm and pos (Plan::identity; Plan::proof_at reads either kind).  The single-key entry points plan so.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -70,8 +73,8 @@ struct Plan {
     size_t n_keys = 0, count = 0;
     std::vector<uint32_t> used;            // slot -> key
     std::vector<uint32_t> slot_of_key;     // key -> slot, NO_SLOT for a key without a proof
-    std::vector<uint32_t> perm;            // grouped position -> proof
-    std::vector<uint32_t> pos;             // proof -> grouped position
+    std::vector<uint32_t> perm;            // grouped position -> proof (empty in the identity plan)
+    std::vector<uint32_t> pos;             // proof -> grouped position (empty in the identity plan)
     std::vector<uint32_t> seg_off;         // slots + 1, in grouped positions
     std::vector<size_t> in_off;            // count + 1: proof i's inputs are elements in_off[i] .. in_off[i + 1] - 1 of the caller's array
     std::vector<size_t> gin_off;           // slots + 1: the same per slot in the GROUPED input array (a slot's inputs are contiguous there)
@@ -82,6 +85,8 @@ struct Plan {
     size_t meta_words = 0;                 // seg_off | mis of every level back to back: level l at 2 l (slots + 1)
 
     size_t slots() const { return used.size(); }
+    bool identity() const { return perm.empty(); }                  // key_of = NULL: grouped position g holds proof g
+    size_t proof_at(size_t g) const { return perm.empty() ? g : perm[g]; }
     size_t fold_lanes() const { return count + 3 * slots(); }      // one Miller lane per proof, three per used key
     size_t batch_lanes() const { return 3 * count; }
     bool fold_fits() const { return fold_lanes() <= MAX_LANES; }
@@ -105,18 +110,19 @@ inline Level make_level(const std::vector<uint32_t>& seg_off, std::vector<uint32
     return lv;
 }
 
-// The plan of a batch.  ninp[k]: the public inputs of key k.  *bad: the first offending proof (PLAN_KEY_OF) or the length the
-// inputs should have (PLAN_INPUTS_LEN).  PLAN_TOO_MANY: count above MAX_LANES or more than MAX_INPUTS inputs -- no form takes that.
+// The plan of a batch.  ninp[k]: the public inputs of key k.  key_of = NULL: every proof under key 0, the identity plan.  *bad: the
+// first offending proof (PLAN_KEY_OF) or the length the inputs should have (PLAN_INPUTS_LEN).  PLAN_TOO_MANY: count above MAX_LANES or more than MAX_INPUTS inputs -- no form takes that.
 inline Refusal make_plan(size_t n_keys, size_t count, const uint32_t* key_of, const size_t* ninp, size_t inputs_len, Plan* p, size_t* bad) {
     *p = Plan();
     if (!n_keys || !count) return PLAN_EMPTY;
     if (count > MAX_LANES) return PLAN_TOO_MANY;
-    for (size_t i = 0; i < count; i++)
+    for (size_t i = 0; key_of && i < count; i++)
         if (key_of[i] >= n_keys) { *bad = i; return PLAN_KEY_OF; }
     p->n_keys = n_keys;
     p->count = count;
     std::vector<uint32_t> per_key(n_keys, 0);
-    for (size_t i = 0; i < count; i++) per_key[key_of[i]]++;
+    if (!key_of) per_key[0] = (uint32_t)count;
+    for (size_t i = 0; key_of && i < count; i++) per_key[key_of[i]]++;
     p->slot_of_key.assign(n_keys, NO_SLOT);
     p->seg_off.push_back(0);
     p->gin_off.push_back(0);
@@ -131,15 +137,18 @@ inline Refusal make_plan(size_t n_keys, size_t count, const uint32_t* key_of, co
     }
     if (p->gin_off.back() != inputs_len) { *bad = p->gin_off.back(); return PLAN_INPUTS_LEN; }
     std::vector<uint32_t> next(p->seg_off.begin(), p->seg_off.end() - 1);      // the next free grouped position of every slot
-    p->perm.resize(count);
-    p->pos.resize(count);
     p->in_off.resize(count + 1);
     p->in_off[0] = 0;
+    if (key_of) {
+        p->perm.resize(count);
+        p->pos.resize(count);
+    }
     for (size_t i = 0; i < count; i++) {
+        p->in_off[i + 1] = p->in_off[i] + ninp[key_of ? key_of[i] : 0];
+        if (!key_of) continue;
         const uint32_t g = next[p->slot_of_key[key_of[i]]]++;
         p->perm[g] = (uint32_t)i;
         p->pos[i] = g;
-        p->in_off[i + 1] = p->in_off[i] + ninp[key_of[i]];
     }
     std::vector<uint32_t> seg = p->seg_off, nxt;
     for (;;) {
