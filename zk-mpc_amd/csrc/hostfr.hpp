@@ -63,6 +63,17 @@ struct HF {
         for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) out.push_back((uint8_t)(w[i] >> (8 * b)));
     }
     void canon_words(uint32_t w[8]) const { fp_pack<FrParams>(w, fp_int_to_canon<FrParams>(v)); }   // the plain integer below r
+    // four little-endian 64-bit words are below r (is_valid, ff/src/fields/macros.rs:255-260; r from the generated constants, where
+    // rng.hip's zk_fr_words_valid has it typed in)
+    static bool words_below_r(const uint64_t l[4]) {
+        uint32_t r[8];
+        fp_pack<FrParams>(r, fp_const<FrParams>(FrParams::P));
+        for (int i = 3; i >= 0; i--) {
+            const uint64_t ri = r[2 * i] | ((uint64_t)r[2 * i + 1] << 32);
+            if (l[i] != ri) return l[i] < ri;
+        }
+        return false;
+    }
 };
 
 }  // namespace zk

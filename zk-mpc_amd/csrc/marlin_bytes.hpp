@@ -1,5 +1,5 @@
-// marlin_bytes.hpp -- a marlin_pc commitment as the reference writes it, shared by the prover (the transcript, marlin_prove.hip) and
-// the indexer (the IndexVerifierKey's bytes, marlin_index.hip).
+// marlin_bytes.hpp -- a marlin_pc commitment as the reference writes it: what the transcript absorbs (marlin_transcript.hpp, for the
+// provers and the verifier) and what the indexer writes into the IndexVerifierKey's bytes (marlin_index.hip).
 //   GroupAffine::write            ec/src/models/short_weierstrass_jacobian.rs:315-322
 //   marlin_pc::Commitment::write  poly-commit/src/marlin/marlin_pc/data_structures.rs:252-263
 #pragma once

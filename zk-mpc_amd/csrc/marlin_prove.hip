@@ -12,7 +12,8 @@
 // arithmetisation, index commitments) is a one-off set-up and stays with the caller, who hands over device-resident tables.
 //
 // Layout: ORACLES states once what each oracle is; MsmJobs is the argument list of one zk_msm_batch_dev call; Marlin<LANES> is one proof in
-// progress: its members are what crosses the rounds, its methods are the steps that marlin_impl runs in order.
+// progress: its ProofState (marlin_prove_int.hpp) and its device pointers are what crosses the rounds, its methods are the steps that
+// marlin_impl runs in order.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
 #include "hostgroup.hpp"
@@ -66,7 +67,6 @@ struct Prover {
         return out;
     }
     bool is_zero(const void* v, size_t n) { int z = 0; ck(zk_fr_vec_is_zero_dev(ctx, v, n, &z)); return z != 0; }
-    HF next_fr(zk_rng* r) { zk_fr o; ck(zk_rng_next_fr(r, &o)); return HF::from_abi(o); }
     // p + r (X^n - 1) for deg p < n: one more coefficient
     Poly blind(const char* poly, size_t n, const char* r_dev, const std::string& name) {
         char* out = dev(name, n + 1);
@@ -139,45 +139,29 @@ struct MarlinArgs {
 template <int LANES>
 struct Marlin : MarlinArgs {
     zk_ctx* const ctx;
-    const size_t max_degree; const char* zb[2];   // of the SRS; the (shares of the) padded assignment
+    const Shape s;
+    const char* zb[2];                            // the (shares of the) padded assignment
     ZkHostLap laps; ZkSharedNet nt; const bool leader;
     Prover PL[2]; Prover& P = PL[0];              // lane 0 also computes everything public
-    const Dom H, K, X, B;
-    const size_t n, ni, md, nwq;                  // |H|, |X|, the mask polynomial's degree (zk_bound = 1), coefficients of w
-    const Dom MUL;                                // the multiplication domain of round 2
     // divisibility / zero-sum checks whose verdict nothing waits for: the test is enqueued, the round's commitments go out behind it, the verdict
     // is read once the batch has synchronised the streams (a wait here left the device idle while the host prepared the batch: 0.1 - 0.15 ms per round)
     struct Pending { const uint32_t* verdict; const char* msg; };
     std::vector<Pending> pending;
     ZkEarlyMsm* early[N_PROVER] = {};             // MSMs started ahead of their round's batch (start_early), until commit_round collects them
-    zk_rng* fs = nullptr;                         // the transcript
     zk_g1_projective gamma_pts[3];                // powers_of_gamma_g: what a hiding bound of 1 uses
     // ---- what the steps hand on ----
-    std::vector<HF> pub;                          // seed_transcript: the public input, its leading 1 included
-    Blinds rands[N_ORACLES];                      // commit_round: the blinding polynomials (index oracles: none)
-    Comm comms[N_PROVER];                         // commit_round
+    ProofState ps;                                // the transcript, the challenges, the commitments, the openings' host halves
     char *xb[2], *wq[2], *mask[2], *tmp[2];       // round 1 -> 2: x and w as coefficients, the mask polynomial, |H| elements of scratch
-    HF alpha, eta[3], v_h_alpha;                  // round 1 / 2: challenges (eta: a, b, c), v_H(alpha)
-    HF beta, vv, gamma, xi;                       // round 2: challenge; round 3: v_H(alpha) v_H(beta), challenge; evaluate: challenge
-    std::vector<HF> evaluations;                  // evaluate: in the proof's (alphabetic) order
-    std::vector<LinComb> queries[2];              // evaluate: the combinations opened at beta / at gamma, in query-set order
-    Affine<G1Field> wit[2];                       // open_combinations: per query point the witness, and random_v if hiding
-    bool has_rv[2] = {false, false}; HF rvs[2];
     Marlin(zk_ctx* c, const MarlinArgs& args)
-        : MarlinArgs(args), ctx(c), max_degree(powers_g->n - 1), zb{(const char*)z[0], LANES == 2 ? (const char*)z[1] : nullptr}, laps{c, "marlin."}, nt{c, net},
-          leader(nt.leader()), PL{Prover{c, 0}, Prover{c, 1}}, H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * K.size - 3),
-          n(H.size), ni(ix->num_instance), md(3 * n + 2 - 3), nwq(n + 1 - X.size), MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1)) {
+        : MarlinArgs(args), ctx(c), s(ix, powers_g), zb{(const char*)z[0], LANES == 2 ? (const char*)z[1] : nullptr}, laps{c, "marlin."}, nt{c, net},
+          leader(nt.leader()), PL{Prover{c, 0}, Prover{c, 1}} {
         for (int l = 0; l < LANES; l++)
             for (int i = 0; i < 12; i++) PL[l].polys[O_A_ROW + i] = Poly{(char*)ix->index_polys[i].ptr, ix->index_polys[i].n};
     }
     ~Marlin() {
         for (ZkEarlyMsm* em : early) if (em) (void)zk_msm_early_finish(ctx, em, nullptr);     // an error path: let them drain
-        zk_rng_free(fs);
     }
-    bool bounded(Oracle o) const { return oracle_bounded(o); }
-    size_t bound(Oracle o) const { return (ORACLES[o].bound == Bound::H ? n : K.size) - 2; }
     int lanes_rc() const { for (int l = 0; l < LANES; l++) if (PL[l].rc != ZK_OK) return PL[l].rc; return (int)ZK_OK; }
-    HF sample_outside(const Dom& d) { HF t = P.next_fr(fs); while (d.vanishing(t).is_zero()) t = P.next_fr(fs); return t; }
     // sum_i c_i powers_of_gamma_g[i] on the context's helper threads (the blinding terms: ~1.2 ms of host scalar multiplications each,
     // under the device batch); the caller joins them before it returns
     ZkTask<zk_g1_projective> small_async(const std::vector<HF>& c) {
@@ -213,40 +197,39 @@ struct Marlin : MarlinArgs {
         // 2^18 21.8 -> 21.6; below that a round is a chain of latencies and the early job, which runs alone instead of in the round's
         // group launches (its own one-block sort, accumulate launch, reduce chain and host half), makes the proof LONGER:
         // 2^10 3.5 -> 4.2 ms, 2^12 4.3 -> 5.4, 2^14 6.1 -> 7.0, 2^16 9.5 -> 10.2
-        if (!early_on || H.size < ((size_t)1 << 18)) return ZK_OK;
+        if (!early_on || s.n < ((size_t)1 << 18)) return ZK_OK;
         if (ORACLES[o].early == EarlyMsm::No || (ORACLES[o].early == EarlyMsm::Plain && shared)) return ZK_OK;
         const Poly& p = P.polys[o];
         if (!p.n) return ZK_OK;
-        if (bounded(o) && p.n - 1 > bound(o)) return ZK_OK;                      // (commit_round reports it)
-        const size_t offs[2] = {0, bounded(o) ? max_degree - bound(o) : 0};
-        return zk_msm_early_begin(ctx, bounded(o) ? 2 : 1, powers_g, offs, p.p, p.n, &early[o]);
+        if (oracle_bounded(o) && p.n - 1 > s.bound(o)) return ZK_OK;                      // (commit_round reports it)
+        const size_t offs[2] = {0, oracle_bounded(o) ? s.max_degree - s.bound(o) : 0};
+        return zk_msm_early_begin(ctx, oracle_bounded(o) ? 2 : 1, powers_g, offs, p.p, p.n, &early[o]);
     }
     // MarlinKZG10::commit for one round (marlin_pc/mod.rs:172-243): blinding polynomials in the reference's rng order, all MSMs
     // of the round (every lane) as one pipelined batch; shared oracles' commitments opened; the round's bytes into the transcript;
     // then the verdicts of the round's pending checks
     int commit_round(int round) {
         const std::vector<Oracle> os = round_oracles(round);
+        ZK_TRY(ps.draw_blinds(round, rng));
         MsmJobs jobs;
         struct Acc { zk_g1_projective pt; bool has = false; } acc[2][2][N_PROVER];   // [lane][0 = comm / 1 = shifted]
         std::vector<Acc*> dest;                                                  // where the batch's points go, in job order
         ZkTask<zk_g1_projective> blind[2][N_PROVER];                             // [comm / shifted]: the blinding terms, under the device batch
         for (Oracle o : os) {
             const OracleInfo& oi = ORACLES[o];
-            Blinds& r = rands[o];
-            if (oi.hiding) for (int i = 0; i < 3; i++) r.plain.push_back(P.next_fr(rng));
-            if (oi.hiding && bounded(o)) for (int i = 0; i < 3; i++) r.shifted.push_back(P.next_fr(rng));
+            const Blinds& r = ps.rands[o];
             for (int lane = 0; lane < LANES; lane++) {
                 if (lane == 1 && !oi.shared) continue;                           // public oracles are the same on every lane: committed once
                 if (lane == 0 && early[o]) continue;                             // started early: collected below
                 const Poly& p = PL[lane].polys[o];
                 dest.push_back(&acc[lane][0][o]);
-                if (!bounded(o)) { jobs.add(powers_g, 0, p.p, p.n); continue; }
-                if (p.n - 1 > bound(o)) { ctx->last_error = std::string("zk_marlin_prove: ") + oi.label + " exceeds its degree bound"; return ZK_ERR_STATE; }
-                jobs.add_with_shift(powers_g, max_degree - bound(o), p.p, p.n);
+                if (!oracle_bounded(o)) { jobs.add(powers_g, 0, p.p, p.n); continue; }
+                if (p.n - 1 > s.bound(o)) { ctx->last_error = std::string("zk_marlin_prove: ") + oi.label + " exceeds its degree bound"; return ZK_ERR_STATE; }
+                jobs.add_with_shift(powers_g, s.max_degree - s.bound(o), p.p, p.n);
                 dest.push_back(&acc[lane][1][o]);
             }
             if (oi.hiding) blind[0][o] = small_async(r.plain);
-            if (oi.hiding && bounded(o)) blind[1][o] = small_async(r.shifted);
+            if (oi.hiding && oracle_bounded(o)) blind[1][o] = small_async(r.shifted);
         }
         ZK_TRY(lanes_rc());
         laps.lap("commit.prep");
@@ -259,7 +242,7 @@ struct Marlin : MarlinArgs {
             const int erc = zk_msm_early_finish(ctx, em, eop);
             if (brc == ZK_OK) brc = erc;
             acc[0][0][o] = {eo[0], true};
-            if (bounded(o)) acc[0][1][o] = {eo[1], true};
+            if (oracle_bounded(o)) acc[0][1][o] = {eo[1], true};
         }
         laps.lap("commit.msm");
         zk_g1_projective bl[2][N_PROVER]; bool blinded[2][N_PROVER] = {};
@@ -291,45 +274,35 @@ struct Marlin : MarlinArgs {
             ZK_TRY(zk_shared_open_small(nt, LANES, pts, &opened));
             for (size_t i = 0; i < what.size(); i++) what[i]->pt = opened.g1[i];
         }
-        std::vector<uint8_t> bytes;
         std::vector<zk_g1_projective> all;
         for (Oracle o : os) {
             all.push_back(acc[0][0][o].pt);
-            if (acc[0][1][o].has) all.push_back(acc[0][1][o].pt);
+            if (oracle_bounded(o)) all.push_back(acc[0][1][o].pt);
         }
-        const std::vector<Affine<G1Field>> aff = batch_to_aff(all);
-        size_t ai = 0;
-        for (Oracle o : os) {
-            Comm& c = comms[o];
-            c.c = aff[ai++];
-            c.has_shift = acc[0][1][o].has;
-            c.s = c.has_shift ? aff[ai++] : aff_inf<G1Field>();
-            comm_tobytes(c, bytes);
-        }
-        ZK_TRY(zk_fsrng_absorb(fs, bytes.data(), bytes.size()));                 // to_bytes![comms, EmptyMessage]
+        ps.commitments(round, all);
         return settle();
     }
 
     // The transcript seed: PROTOCOL_NAME | index_vk | public_input (lib.rs:161-164).  Over shares the instance part of the
-    // assignment is shared like the rest (from_public: the leader holds it) and opened here.  Out: gamma_pts, pub, fs
+    // assignment is shared like the rest (from_public: the leader holds it) and opened here.  Out: gamma_pts, ps seeded
     int seed_transcript() {
         zk_g1_affine g[3];
         ZK_TRY(zk_bases_download_g1(ctx, powers_gamma_g, 0, 3, g));
         for (int i = 0; i < 3; i++) zk_g1_from_affine(&g[i], &gamma_pts[i]);
+        const size_t ni = s.ni;
         std::vector<zk_fr> x(ni);
         const char* from = zb[0];
         if (shared && ni > 1) ZK_TRY(open_dev(zb, ni, "pub", (char**)&from));   // (ni = 1: no public input beside the constant 1, nothing to open)
         if (!shared || ni > 1) ZK_TRY(zk_memcpy_d2h(ctx, x.data(), from, ni * 32));
-        pub.assign(ni, HF::one());
-        for (size_t i = 1; i < ni; i++) pub[i] = HF::from_abi(x[i]);
-        const std::vector<uint8_t> seed = transcript_seed(ix, pub);
-        ZK_TRY(zk_fsrng_new(seed.data(), seed.size(), &fs));
+        ps.seed(ix, x.data(), ni);
         laps.lap("setup");
         return ZK_OK;
     }
 
     // Round 1 (prover.rs:216-404), every lane.  In: the assignment, the prover's rng.  Out: w, z_a, z_b, mask_poly committed; xb, wq, mask, tmp; alpha, eta
     int round1() {
+        const Dom &H = s.H, &X = s.X;
+        const size_t n = s.n, md = s.md, nwq = s.nwq;
         char* rnd = P.dev("rnd", 3 + md + 1);                                    // this party's (share of the) prover randomness: both lanes read it
         ZK_TRY(P.rc);
         const size_t host_n = mask_on_device ? 3 : 3 + md + 1;
@@ -387,8 +360,7 @@ struct Marlin : MarlinArgs {
         laps.lap("polys");
         ZK_TRY(commit_round(1));
         laps.lap("commit");
-        alpha = sample_outside(H);
-        for (HF& e : eta) e = P.next_fr(fs);
+        ps.challenges(1, s);
         laps.lap("round1");
         return ZK_OK;
     }
@@ -396,8 +368,9 @@ struct Marlin : MarlinArgs {
     // Round 2 (prover.rs:438-565).  In: alpha, eta; z_a, z_b, w (wq), x (xb), mask; tmp.  Out: t, g_1, h_1 committed; v_h_alpha; beta
     int round2() {
         // public: r(alpha, X) on H, t = sum_M eta_M M^T r, their evaluations over the multiplication domain (computed once)
-        const HF one = HF::one();
-        v_h_alpha = H.vanishing(alpha);
+        const Dom &H = s.H, &X = s.X, &MUL = s.MUL;
+        const size_t n = s.n, md = s.md, nwq = s.nwq;
+        const HF one = HF::one(), &alpha = ps.alpha, &v_h_alpha = ps.v_h_alpha, *const eta = ps.eta;
         char* elems = P.dev("h_elems", n);
         char* ra = P.dev("r_alpha", n);
         ZK_TRY(P.rc);
@@ -459,19 +432,20 @@ struct Marlin : MarlinArgs {
         if (!zero_sum) ZK_FAIL(ctx, ZK_ERR_STATE, not_zero);
         for (int l = 0; l < LANES; l++) {
             PL[l].polys[O_G_1] = Poly{hr[l] + 32, n - 1};
-            PL[l].polys[O_H_1] = Poly{hq[l], std::min(MUL.size - n, 2 * n + 2 - 1)};
+            PL[l].polys[O_H_1] = Poly{hq[l], s.h1n};
         }
         laps.lap("polys");
         ZK_TRY(commit_round(2));
         laps.lap("commit");
-        beta = sample_outside(H);
+        ps.challenges(2, s);
         laps.lap("round2");
         return ZK_OK;
     }
 
     // Round 3 (prover.rs:583-716): public values only.  In: alpha, eta, beta, v_h_alpha.  Out: g_2, h_2 committed; vv; gamma
     int round3() {
-        vv = v_h_alpha * H.vanishing(beta);
+        const Dom &K = s.K, &B = s.B;
+        const HF &alpha = ps.alpha, &beta = ps.beta, &vv = ps.vv, *const eta = ps.eta;
         char* f_ev = P.dev("f_ev", K.size);
         char* a_ev = P.dev("a_ev", B.size); char* b_ev = P.dev("b_ev", B.size);
         ZK_TRY(P.rc);
@@ -494,64 +468,47 @@ struct Marlin : MarlinArgs {
         laps.lap("polys");
         ZK_TRY(commit_round(3));
         laps.lap("commit");
-        gamma = P.next_fr(fs);
+        ps.challenges(3, s);
         laps.lap("round3");
         return ZK_OK;
     }
 
-    // The evaluations of the query set, absorbed, and the linear combinations over them.  In: oracles, challenges, pub.  Out: evaluations, queries, xi
+    // The evaluations of the query set, absorbed, and the linear combinations over them.  In: oracles, challenges.  Out: ps.qs, ps.xi, ps.plan
     int evaluate() {
         // one batch (two launches, one copy back); z_b and g_1 are shared: every lane's evaluation, opened (`evaluations.publicize()`, lib.rs:296)
-        QueryValues qv;
-        HF &z_b_beta = qv.z_b_beta, &g_1_beta = qv.g_1_beta, &t_beta = qv.t_beta, &g_2_gamma = qv.g_2_gamma;
-        HF *const row = qv.row, *const col = qv.col, *const row_col = qv.row_col;      // of A, B, C at gamma
-        struct Want { Oracle o; const HF* point; HF* value; };
-        std::vector<Want> want = {{O_Z_B, &beta, &z_b_beta}, {O_G_1, &beta, &g_1_beta}, {O_T, &beta, &t_beta}, {O_G_2, &gamma, &g_2_gamma}};
-        for (int m = 0; m < 3; m++) {
-            want.push_back({index_of(m, ROW), &gamma, &row[m]});
-            want.push_back({index_of(m, COL), &gamma, &col[m]});
-            want.push_back({index_of(m, ROW_COL), &gamma, &row_col[m]});
-        }
         std::vector<zk_poly_ref> refs;
         std::vector<zk_fr> pts;
-        for (const Want& w : want) { const Poly& p = P.polys[w.o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(w.point->abi()); }
+        for (const QueryValue& w : QUERY_VALUES) { const Poly& p = P.polys[w.o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(ps.point(w.at_gamma).abi()); }
+        static_assert(QUERY_VALUES[0].o == O_Z_B && QUERY_VALUES[1].o == O_G_1, "the two shared values come first");
         if (LANES == 2)                                                          // behind them: the MAC lane of the two shared ones
-            for (Oracle o : {O_Z_B, O_G_1}) { const Poly& p = PL[1].polys[o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(beta.abi()); }
+            for (Oracle o : {O_Z_B, O_G_1}) { const Poly& p = PL[1].polys[o]; refs.push_back(zk_poly_ref{p.p, p.n}); pts.push_back(ps.beta.abi()); }
         std::vector<zk_fr> vals(refs.size());
         ZK_TRY(zk_poly_evaluate_batch_dev(ctx, refs.data(), pts.data(), refs.size(), vals.data()));
-        for (size_t i = 0; i < want.size(); i++) *want[i].value = HF::from_abi(vals[i]);
         if (shared) {
             ZkSmallItems frs[2], opened;
-            frs[0].fr = {z_b_beta.abi(), g_1_beta.abi()};
-            if (LANES == 2) frs[1].fr = {vals[want.size()], vals[want.size() + 1]};
+            frs[0].fr = {vals[0], vals[1]};
+            if (LANES == 2) frs[1].fr = {vals[N_QUERY_VALUES], vals[N_QUERY_VALUES + 1]};
             ZK_TRY(zk_shared_open_small(nt, LANES, frs, &opened));
-            z_b_beta = HF::from_abi(opened.fr[0]); g_1_beta = HF::from_abi(opened.fr[1]);
+            vals[0] = opened.fr[0]; vals[1] = opened.fr[1];
         }
         ZK_TRY(P.rc);
-        QuerySet qs = query_set(H, K, X, alpha, eta, beta, gamma, qv, pub.data());
-        evaluations = std::move(qs.evaluations);
-        queries[0] = std::move(qs.queries[0]); queries[1] = std::move(qs.queries[1]);
-        std::vector<uint8_t> ev_bytes;
-        for (const HF& e : evaluations) e.bytes(ev_bytes);
-        ZK_TRY(zk_fsrng_absorb(fs, ev_bytes.data(), ev_bytes.size()));
-        ZK_TRY(opening_challenge(fs, &xi));
+        ps.evaluated(vals.data(), s);
         laps.lap("evals+lc");
         return ZK_OK;
     }
 
-    // open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340).  In: queries, xi, beta, gamma, rands.  Out: wit, has_rv, rvs.
+    // open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340).  In: ps.plan, the query points.  Out: ps.wit, ps.has_rv, ps.rvs.
     // Over shares: the witness of a share combination is a share of the witness.  A combination with a shared oracle in it runs on
     // every lane, public oracles entering it on the leader only (shift(): in both lanes, mac_share = 1 there), and its witness
     // (and random_v) is opened; a combination of public oracles only (the query point gamma) is computed alike by every party.
     int open_combinations() {
-        const HF points[2] = {beta, gamma}, one = HF::one();
         MsmJobs jobs;
         size_t counts[2][2] = {{0, 0}, {0, 0}};                                  // [query point][lane]
         std::vector<ZkTask<zk_g1_projective>> extra[2];                          // the blinding witnesses: host threads, joined after the batch
         bool q_shared[2] = {false, false};
         for (int q = 0; q < 2; q++) {
-            const HF z = points[q];
-            const OpenPlan plan = open_plan(queries[q], xi, rands);
+            const HF z = ps.point(q);
+            const OpenPlan& plan = ps.plan[q];
             const std::vector<std::pair<Oracle, HF>>&terms = plan.terms, &shifted = plan.shifted;
             bool any_shared = false;
             for (auto& t : terms) any_shared = any_shared || (shared && ORACLES[t.first].shared);
@@ -583,16 +540,12 @@ struct Marlin : MarlinArgs {
                     ZK_TRY(Q.rc);
                     { zk_fr zz = z.abi(); ZK_TRY(zk_poly_divide_by_linear_dev(ctx, p.p, p.n, &zz, wq2, nullptr)); }
                     Q.scale(wq2, sh.second, wq2, p.n - 1);
-                    jobs.add(powers_g, max_degree - bound(sh.first), wq2, p.n - 1);
+                    jobs.add(powers_g, s.max_degree - s.bound(sh.first), wq2, p.n - 1);
                 }
                 counts[q][l] = jobs.size() - first_job;
             }
-            const OpenBlinds ob = open_blinds(plan, z, rands);
-            if (ob.hiding) {
-                extra[q].push_back(small_async(ob.plain_w));
-                has_rv[q] = true;
-                rvs[q] = ob.rv;
-            }
+            const OpenBlinds ob = ps.blinds_at(q);
+            if (ob.hiding) extra[q].push_back(small_async(ob.plain_w));
             if (!ob.shifted_w.empty()) extra[q].push_back(small_async(ob.shifted_w));
         }
         ZK_TRY(lanes_rc());
@@ -615,25 +568,15 @@ struct Marlin : MarlinArgs {
             }
             if (q_shared[q]) {                                                   // the witness (and random_v) of a shared combination: opened
                 ZkSmallItems mine[2], opened;
-                for (int l = 0; l < LANES; l++) { mine[l].g1.push_back(wl[l]); if (has_rv[q]) mine[l].fr.push_back(rvs[q].abi()); }
+                for (int l = 0; l < LANES; l++) { mine[l].g1.push_back(wl[l]); if (ps.has_rv[q]) mine[l].fr.push_back(ps.rvs[q].abi()); }
                 ZK_TRY(zk_shared_open_small(nt, LANES, mine, &opened));
                 wl[0] = opened.g1[0];
-                if (has_rv[q]) rvs[q] = HF::from_abi(opened.fr[0]);
+                if (ps.has_rv[q]) ps.rvs[q] = HF::from_abi(opened.fr[0]);
             }
             wits.push_back(wl[0]);
         }
-        const std::vector<Affine<G1Field>> wa = batch_to_aff(wits);
-        wit[0] = wa[0]; wit[1] = wa[1];
+        ps.witnesses(wits.data());
         laps.lap("open");
-        return ZK_OK;
-    }
-
-    // Proof::serialize (data_structures.rs:99-110, derive order).  In: comms, evaluations, wit, has_rv, rvs
-    int serialize(uint8_t* proof_out, size_t cap, size_t* proof_len) {
-        const std::vector<uint8_t> out = proof_bytes(comms, evaluations, wit, has_rv, rvs);
-        if (out.size() > cap) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer too small");
-        memcpy(proof_out, out.data(), out.size());
-        *proof_len = out.size();
         return ZK_OK;
     }
 };
@@ -642,18 +585,17 @@ template <int LANES>
 int marlin_impl(zk_ctx* ctx, const MarlinArgs& a, uint8_t* proof_out, size_t cap, size_t* proof_len, uint64_t* bytes_sent) {
     const zk_marlin_index* ix = a.ix;
     if (!ctx || !ix || !a.powers_g || !a.powers_gamma_g || !a.z[0] || (LANES == 2 && !a.z[1]) || !a.rng || !proof_out || !proof_len) return ZK_ERR_ARG;
-    if (a.powers_g->group != 1 || a.powers_gamma_g->group != 1 || a.powers_gamma_g->n < 3) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: SRS tables");
-    if (cap < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer smaller than zk_marlin_proof_max_size()");
     ZK_TRY(check_index_and_srs(ctx, ix, a.powers_g, a.powers_gamma_g));
+    if (cap < zk_marlin_proof_max_size()) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer smaller than zk_marlin_proof_max_size()");
     Marlin<LANES> m(ctx, a);
-    ZK_TRY(check_sizes(ctx, m.max_degree, m.n, m.K.size, m.B.size));
+    ZK_TRY(check_sizes(ctx, m.s.max_degree, m.s.n, m.s.K.size, m.s.B.size));
     ZK_TRY(m.seed_transcript());
     ZK_TRY(m.round1());
     ZK_TRY(m.round2());
     ZK_TRY(m.round3());
     ZK_TRY(m.evaluate());
     ZK_TRY(m.open_combinations());
-    ZK_TRY(m.serialize(proof_out, cap, proof_len));
+    if (!m.ps.write(proof_out, cap, proof_len)) ZK_FAIL(ctx, ZK_ERR_ARG, "zk_marlin_prove: output buffer too small");
     if (bytes_sent) *bytes_sent = m.nt.bytes;
     return ZK_OK;
 }

@@ -11,8 +11,8 @@
 //     collected; the blinding terms sum c_i powers_of_gamma_g[i] of all proofs (about 7 scalar multiplications per proof and step)
 //     are one zk_g1_lincomb_launch per step on a stream of its own once they are too many for the host's helper threads, which
 //     is where the single prover computes them (HOST_BLIND_MULS);
-//   * each proof keeps its own transcript, challenges and blinding scalars on the host; the per-proof host loops run over ranges of
-//     proofs on the context's pool (zk_over_ranges);
+//   * each proof keeps its own transcript, challenges and blinding scalars on the host (marlin_prove_int.hpp: ProofState, the single
+//     prover's); the per-proof host loops run over ranges of proofs on the context's pool (zk_over_ranges);
 //   * no MSM starts early (Marlin::start_early hides ONE proof's latency; the batch hides it by width).
 // The per-proof constants of a step (alpha, eta, beta, ..., the opening's coefficients) are a small device table written once per
 // step through a ZkStage.  The only per-proof launches are the device mask sampler (once per call and cheap).  A failing zero test
@@ -63,38 +63,6 @@ struct Vec {
     char* at(size_t k) const { return p + k * stride * 32; }
 };
 
-// The sizes every step reads
-struct Shape {
-    const Dom H, K, X, B;
-    const size_t n, ni, md, nwq;                  // |H|, |X|, the mask polynomial's degree (zk_bound = 1), coefficients of w
-    const Dom MUL;                                // the multiplication domain of round 2
-    const size_t h1n, h2n, max_degree, nv;        // ...; the padded assignment's length
-    size_t index_n[12], cn[2];                    // the index polynomials' lengths; the longest polynomial opened at beta / at gamma
-    Shape(const zk_marlin_index* ix, const zk_bases* powers_g)
-        : H(ix->num_constraints), K(ix->num_non_zero), X(ix->num_instance), B(3 * K.size - 3), n(H.size), ni(ix->num_instance), md(3 * n + 2 - 3),
-          nwq(n + 1 - X.size), MUL(std::max(std::max(md + 1, n + 2 * n + 1), n + n + 1)), h1n(std::min(MUL.size - n, 2 * n + 2 - 1)), h2n(B.size - K.size),
-          max_degree(powers_g->n - 1), nv(ix->num_variables) {
-        for (int i = 0; i < 12; i++) index_n[i] = ix->index_polys[i].n;
-        cn[0] = std::max(std::max(md + 1, h1n), n + 1);
-        cn[1] = std::max(h2n, K.size - 1);
-        for (int i = 0; i < 12; i++) cn[1] = std::max(cn[1], index_n[i]);
-    }
-    size_t bound(Oracle o) const { return (ORACLES[o].bound == Bound::H ? n : K.size) - 2; }
-    size_t oracle_n(Oracle o) const {
-        switch (o) {
-            case O_W: return nwq;
-            case O_Z_A: case O_Z_B: return n + 1;
-            case O_MASK_POLY: return md + 1;
-            case O_T: return n;
-            case O_G_1: return n - 1;
-            case O_H_1: return h1n;
-            case O_G_2: return K.size - 1;
-            case O_H_2: return h2n;
-            default: return index_n[o - O_A_ROW];
-        }
-    }
-};
-
 // Where everything of a chunk of C proofs lives: place() hands out the regions of one allocation in a fixed order (base = NULL:
 // the bytes it takes).  Over shares a witness-dependent region holds lanes * C vectors, lane after lane; what is public holds C.
 struct Layout {
@@ -139,23 +107,6 @@ struct Layout {
     }
 };
 
-// One proof's host state: what crosses the steps
-struct One {
-    zk_rng* fs = nullptr;                         // the transcript
-    std::vector<HF> pub;
-    Blinds rands[N_ORACLES];
-    Comm comms[N_PROVER];
-    HF alpha, eta[3], v_h_alpha, beta, vv, gamma, xi;
-    QuerySet qs;
-    OpenPlan plan[2];
-    Affine<G1Field> wit[2];
-    bool has_rv[2] = {false, false}; HF rvs[2];
-    int rc = ZK_OK; std::string err;
-    One() = default;
-    One(const One&) = delete; One& operator=(const One&) = delete;
-    ~One() { zk_rng_free(fs); }
-};
-
 // A multi-vector job of a step over `vectors` vectors (C, or lanes * C for a shared oracle) and where its points go
 struct StepJob { const char* scalars; size_t stride, len, off, vectors; std::vector<zk_g1_projective> out; };
 
@@ -187,7 +138,7 @@ struct Chunk {
     const size_t V;                               // vectors of a witness-dependent region: lanes * C, lane after lane
     const size_t wrap;                            // what the kernels with a per-proof operand take as `proofs`: 0 in the plain batch, where vector k is proof k
     const zk_g1_projective* const gamma_pts;      // powers_of_gamma_g[0 .. 2] on the host
-    std::vector<One> P;
+    std::vector<ProofState> P;
     Vec polys[N_PROVER];                          // a shared oracle's (ORACLES[o].shared) over shares: V vectors
     Vec zv;                                       // the assignments, lane after lane
     ZkHostLap xl;                                 // over shares: the host's time between exchanges (local) and inside each kind of them
@@ -202,7 +153,6 @@ struct Chunk {
     // how many vectors an oracle's region holds, and the point of lane l of proof k among a job's
     size_t vectors_of(Oracle o) const { return shared && o < N_PROVER && ORACLES[o].shared ? V : C; }
 
-    HF next_fr(zk_rng* r, int* rc) { zk_fr o; const int e = zk_rng_next_fr(r, &o); if (*rc == ZK_OK) *rc = e; return HF::from_abi(o); }
     template <class Fn>
     int each(const Fn& f) {                       // f(k) for every proof of the chunk, over ranges on the pool; the first failing proof's code
         zk_over_ranges(ctx, C, HOST_TASKS, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) if (P[k].rc == ZK_OK) P[k].rc = f(k); });
@@ -396,15 +346,7 @@ struct Chunk {
     // of all proofs are opened in ONE exchange (first_comms.publicize(), lib.rs:180,205,228) before any transcript absorbs them.
     int commit_round(int round, size_t first_proof, int check_slot) {
         const std::vector<Oracle> os = round_oracles(round);
-        ZK_TRY(each([&](size_t k) {
-            int rc = ZK_OK;
-            for (Oracle o : os) {
-                Blinds& r = P[k].rands[o];
-                if (ORACLES[o].hiding) for (int i = 0; i < 3; i++) r.plain.push_back(next_fr(rngs[k], &rc));
-                if (ORACLES[o].hiding && oracle_bounded(o)) for (int i = 0; i < 3; i++) r.shifted.push_back(next_fr(rngs[k], &rc));
-            }
-            return rc;
-        }));
+        ZK_TRY(each([&](size_t k) { return P[k].draw_blinds(round, rngs[k]); }));
         std::vector<StepJob> jobs;
         struct Dest { Oracle o; int which; };
         std::vector<Dest> dest, segs;
@@ -453,8 +395,8 @@ struct Chunk {
             ZK_TRY(open_small(mine, &opened));
         }
         return each([&](size_t k) {
-            zk_g1_projective acc[2][N_PROVER]; bool has[2][N_PROVER] = {};
-            for (size_t j = 0; j < jobs.size(); j++) { acc[dest[j].which][dest[j].o] = jobs[j].out[k]; has[dest[j].which][dest[j].o] = true; }
+            zk_g1_projective acc[2][N_PROVER];
+            for (size_t j = 0; j < jobs.size(); j++) acc[dest[j].which][dest[j].o] = jobs[j].out[k];
             for (size_t sg = 0; sg < segs.size(); sg++) {
                 if (!has_bl[k * segs.size() + sg]) continue;
                 zk_g1_projective& c = acc[segs[sg].which][segs[sg].o];
@@ -463,29 +405,16 @@ struct Chunk {
                 c = t;
             }
             for (size_t i = 0; i < per; i++) acc[dest[open_jobs[i]].which][dest[open_jobs[i]].o] = opened.g1[plan::slot(which_open, plan::KIND_G1, k, i)];
-            std::vector<uint8_t> bytes;
             std::vector<zk_g1_projective> all;
             for (Oracle o : os) {
                 all.push_back(acc[0][o]);
-                if (has[1][o]) all.push_back(acc[1][o]);
+                if (oracle_bounded(o)) all.push_back(acc[1][o]);
             }
-            const std::vector<Affine<G1Field>> aff = batch_to_aff(all);
-            size_t ai = 0;
-            for (Oracle o : os) {
-                Comm& c = P[k].comms[o];
-                c.c = aff[ai++];
-                c.has_shift = has[1][o];
-                c.s = c.has_shift ? aff[ai++] : aff_inf<G1Field>();
-                comm_tobytes(c, bytes);
-            }
-            return zk_fsrng_absorb(P[k].fs, bytes.data(), bytes.size());      // to_bytes![comms, EmptyMessage]
+            P[k].commitments(round, all);
+            return (int)ZK_OK;
         });
     }
-    HF sample_outside(size_t k, const Dom& d, int* rc) {
-        HF t = next_fr(P[k].fs, rc);
-        while (*rc == ZK_OK && d.vanishing(t).is_zero()) t = next_fr(P[k].fs, rc);
-        return t;
-    }
+    int challenges(int round) { return each([&](size_t k) { P[k].challenges(round, s); return (int)ZK_OK; }); }
 
     // The transcript seeds: PROTOCOL_NAME | index_vk | public_input (lib.rs:161-164).  Over shares the instance part of an assignment is
     // shared like the rest (from_public: the leader holds it): the chunk's instance parts are gathered into one vector and opened once
@@ -506,12 +435,7 @@ struct Chunk {
             }
             ZK_TRY(zk_memcpy_d2h(ctx, x.data(), from, C * s.ni * 32));
         }
-        return each([&](size_t k) {
-            P[k].pub.assign(s.ni, HF::one());
-            for (size_t i = 1; i < s.ni; i++) P[k].pub[i] = HF::from_abi(x[k * s.ni + i]);
-            const std::vector<uint8_t> seed = transcript_seed(ix, P[k].pub);
-            return zk_fsrng_new(seed.data(), seed.size(), &P[k].fs);
-        });
+        return each([&](size_t k) { P[k].seed(ix, &x[k * s.ni], s.ni); return (int)ZK_OK; });
     }
 
     // Round 1 (prover.rs:216-404)
@@ -560,12 +484,7 @@ struct Chunk {
         ZK_TRY(zk_b_blind(ctx, L.z_b.p, L.z_b.stride, n, L.rnd.p + 64, L.rnd.stride, L.zb_p.p, L.zb_p.stride, V));
         polys[O_W] = L.wq; polys[O_Z_A] = L.za_p; polys[O_Z_B] = L.zb_p;
         ZK_TRY(commit_round(1, first_proof, 0));
-        return each([&](size_t k) {
-            int rc = ZK_OK;
-            P[k].alpha = sample_outside(k, s.H, &rc);
-            for (HF& e : P[k].eta) e = next_fr(P[k].fs, &rc);
-            return rc;
-        });
+        return challenges(1);
     }
 
     // Round 2 (prover.rs:438-565)
@@ -574,7 +493,7 @@ struct Chunk {
         const HF one = HF::one();
         const FrK *t_alpha, *t_vh, *t_eta;
         ZK_TRY(table(1, [&](size_t k, FrK* r) { r[0] = to_frk(fp_int_to_ext<FrParams>(P[k].alpha.v)); }, &t_alpha));
-        ZK_TRY(table(1, [&](size_t k, FrK* r) { P[k].v_h_alpha = s.H.vanishing(P[k].alpha); r[0] = to_frk(P[k].v_h_alpha.v); }, &t_vh));
+        ZK_TRY(table(1, [&](size_t k, FrK* r) { r[0] = to_frk(P[k].v_h_alpha.v); }, &t_vh));
         ZK_TRY(table(3, [&](size_t k, FrK* r) { for (int m = 0; m < 3; m++) r[m] = to_frk(P[k].eta[m].v); }, &t_eta));
         ZK_TRY(zk_fr_powers_launch(ctx, s.H.gen.v, one.v, n, L.elems, ZK_FR_EXT));
         ZK_TRY(zk_b_const_minus(ctx, t_alpha, 1, L.elems, n, L.ra.p, L.ra.stride, C));
@@ -631,7 +550,7 @@ struct Chunk {
         polys[O_G_1] = Vec{L.h1_r.p + 32, L.h1_r.stride};
         polys[O_H_1] = L.h1_q;
         ZK_TRY(commit_round(2, first_proof, 1));
-        return each([&](size_t k) { int rc = ZK_OK; P[k].beta = sample_outside(k, s.H, &rc); return rc; });
+        return challenges(2);
     }
 
     // Round 3 (prover.rs:583-716)
@@ -639,7 +558,6 @@ struct Chunk {
         const size_t Ks = s.K.size, Bs = s.B.size;
         const FrK* tab;
         ZK_TRY(table(ZK_B_R3_ROW, [&](size_t k, FrK* r) {
-            P[k].vv = P[k].v_h_alpha * s.H.vanishing(P[k].beta);
             const Fr eta[3] = {P[k].eta[0].v, P[k].eta[1].v, P[k].eta[2].v};
             zk_b_round3_row(P[k].alpha.v, P[k].beta.v, eta, P[k].vv.v, r);
         }, &tab));
@@ -658,7 +576,7 @@ struct Chunk {
         ZK_TRY(check_later(2, L.h2_r.p, C * Ks));
         polys[O_H_2] = L.h2_q;
         ZK_TRY(commit_round(3, first_proof, 2));
-        return each([&](size_t k) { int rc = ZK_OK; P[k].gamma = next_fr(P[k].fs, &rc); return rc; });
+        return challenges(3);
     }
 
     Vec poly_of(Oracle o) const {
@@ -670,10 +588,8 @@ struct Chunk {
     // Over shares z_b(beta) and g_1(beta) are shares: behind the share lane's values the MAC lane's of every proof, and all of them
     // opened in ONE exchange (`evaluations.publicize()`, lib.rs:296)
     int evaluate() {
-        struct Want { Oracle o; bool at_gamma; };
-        std::vector<Want> want = {{O_Z_B, false}, {O_G_1, false}, {O_T, false}, {O_G_2, true}};
-        for (int m = 0; m < 3; m++) for (IndexPart part : {ROW, COL, ROW_COL}) want.push_back({index_of(m, part), true});
-        const size_t W = want.size();
+        const QueryValue* const want = QUERY_VALUES;
+        const size_t W = N_QUERY_VALUES;
         namespace plan = zk::marlin_plan;
         const size_t mac_n = lanes > 1 ? plan::EV_ITEMS : 0, total = C * (W + mac_n);
         std::vector<zk_poly_ref> refs(total);
@@ -682,7 +598,7 @@ struct Chunk {
             for (size_t i = 0; i < W; i++) {
                 const Vec v = poly_of(want[i].o);
                 refs[k * W + i] = zk_poly_ref{v.at(k), s.oracle_n(want[i].o)};
-                pts[k * W + i] = (want[i].at_gamma ? P[k].gamma : P[k].beta).abi();
+                pts[k * W + i] = P[k].point(want[i].at_gamma).abi();
             }
             for (size_t i = 0; i < mac_n; i++) {                             // want[0], want[1]: z_b and g_1 at beta, in the open's order
                 refs[C * W + k * mac_n + i] = zk_poly_ref{poly_of(want[i].o).at(C + k), s.oracle_n(want[i].o)};
@@ -691,7 +607,8 @@ struct Chunk {
         }
         ZK_TRY(zk_poly_evaluate_batch_dev(ctx, refs.data(), pts.data(), total, vals.data()));
         if (shared) {
-            static_assert(plan::EV_Z_B_BETA == 0 && plan::EV_G_1_BETA == 1, "the evaluations' open lists z_b, g_1 as the query values do");
+            static_assert(QUERY_VALUES[plan::EV_Z_B_BETA].o == O_Z_B && QUERY_VALUES[plan::EV_G_1_BETA].o == O_G_1 && plan::EV_ITEMS == 2,
+                          "the evaluations' open lists z_b, g_1 as the query values do");
             ZkSmallItems mine[2], opened;
             for (int l = 0; l < lanes; l++) mine[l].fr.resize(C * plan::EV_ITEMS);
             for (size_t k = 0; k < C; k++)
@@ -703,22 +620,7 @@ struct Chunk {
             for (size_t k = 0; k < C; k++)
                 for (size_t i = 0; i < (size_t)plan::EV_ITEMS; i++) vals[k * W + i] = opened.fr[plan::slot(plan::OPEN_EVALS, plan::KIND_FR, k, i)];
         }
-        return each([&](size_t k) {
-            One& p = P[k];
-            const zk_fr* v = &vals[k * W];
-            QueryValues qv;
-            qv.z_b_beta = HF::from_abi(v[0]); qv.g_1_beta = HF::from_abi(v[1]); qv.t_beta = HF::from_abi(v[2]); qv.g_2_gamma = HF::from_abi(v[3]);
-            for (int m = 0; m < 3; m++) {
-                qv.row[m] = HF::from_abi(v[4 + 3 * m]); qv.col[m] = HF::from_abi(v[5 + 3 * m]); qv.row_col[m] = HF::from_abi(v[6 + 3 * m]);
-            }
-            p.qs = query_set(s.H, s.K, s.X, p.alpha, p.eta, p.beta, p.gamma, qv, p.pub.data());
-            std::vector<uint8_t> ev_bytes;
-            for (const HF& e : p.qs.evaluations) e.bytes(ev_bytes);
-            ZK_TRY(zk_fsrng_absorb(p.fs, ev_bytes.data(), ev_bytes.size()));
-            ZK_TRY(opening_challenge(p.fs, &p.xi));
-            for (int q = 0; q < 2; q++) p.plan[q] = open_plan(p.qs.queries[q], p.xi, p.rands);
-            return (int)ZK_OK;
-        });
+        return each([&](size_t k) { P[k].evaluated(&vals[k * W], s); return (int)ZK_OK; });
     }
 
     // open_combinations (marlin/mod.rs:213-306, marlin_pc/mod.rs:245-340): the same oracles enter a combination for every proof, with
@@ -763,7 +665,7 @@ struct Chunk {
             ZK_TRY(table(U, [&](size_t k, FrK* r) { for (size_t t = 0; t < U; t++) r[t] = to_frk(P[k].plan[q].terms[use[t]].second.v); }, &coef));
             ZK_TRY(zk_b_lincomb(ctx, (int)U, ps.data(), strides.data(), ns.data(), coef, U, L.comb[q].p, L.comb[q].stride, cn, cnt, proofs, per_proof));
             std::vector<Fr> zpt(cnt);
-            for (size_t v = 0; v < cnt; v++) zpt[v] = (q ? P[v % C].gamma : P[v % C].beta).v;
+            for (size_t v = 0; v < cnt; v++) zpt[v] = P[v % C].point(q).v;
             ZK_TRY(zk_poly_divide_by_linear_strided(ctx, L.comb[q].p, L.comb[q].stride, cn, zpt.data(), cnt, L.quo[q].p, L.quo[q].stride, L.spans.p, &stage));
             jobs.push_back({L.quo[q].p, L.quo[q].stride, cn - 1, 0, cnt, {}});
             njobs[q] = 1;
@@ -784,11 +686,7 @@ struct Chunk {
         // the blinding witnesses: per proof and query point the plain and the shifted one
         std::vector<OpenBlinds> ob(C * 2);
         ZK_TRY(each([&](size_t k) {
-            for (int q = 0; q < 2; q++) {
-                ob[2 * k + q] = open_blinds(P[k].plan[q], q ? P[k].gamma : P[k].beta, P[k].rands);
-                P[k].has_rv[q] = ob[2 * k + q].hiding;
-                if (ob[2 * k + q].hiding) P[k].rvs[q] = ob[2 * k + q].rv;
-            }
+            for (int q = 0; q < 2; q++) ob[2 * k + q] = P[k].blinds_at(q);
             return (int)ZK_OK;
         }));
         // (at gamma nothing is hiding: g_2, h_2 and the index are committed without blinds)
@@ -826,14 +724,13 @@ struct Chunk {
             ZK_TRY(open_small(mine, &opened));
         }
         return each([&](size_t k) {
-            std::vector<zk_g1_projective> wits;
+            zk_g1_projective wits[2];
             for (int q = 0; q < 2; q++) {
-                if (!q_shared[q]) { wits.push_back(witness(k, q, 0)); continue; }
-                wits.push_back(opened.g1[plan::slot(plan::OPEN_WITNESS, plan::KIND_G1, k, plan::WI_WITNESS_BETA)]);
+                if (!q_shared[q]) { wits[q] = witness(k, q, 0); continue; }
+                wits[q] = opened.g1[plan::slot(plan::OPEN_WITNESS, plan::KIND_G1, k, plan::WI_WITNESS_BETA)];
                 if (P[k].has_rv[q]) P[k].rvs[q] = HF::from_abi(opened.fr[plan::slot(plan::OPEN_WITNESS, plan::KIND_FR, k, plan::WI_RANDOM_V)]);
             }
-            const std::vector<Affine<G1Field>> wa = batch_to_aff(wits);
-            P[k].wit[0] = wa[0]; P[k].wit[1] = wa[1];
+            P[k].witnesses(wits);
             return (int)ZK_OK;
         });
     }
@@ -853,10 +750,7 @@ struct Chunk {
         ZK_TRY(open_combinations());
         laps.lap("open");
         return each([&](size_t k) {
-            const std::vector<uint8_t> out = proof_bytes(P[k].comms, P[k].qs.evaluations, P[k].wit, P[k].has_rv, P[k].rvs);
-            if (out.size() > A.slot) { P[k].err = "zk_marlin_prove_batch: output slot too small"; return (int)ZK_ERR_ARG; }
-            memcpy(A.proofs_out + k * A.slot, out.data(), out.size());
-            A.proof_lens[k] = out.size();
+            if (!P[k].write(A.proofs_out + k * A.slot, A.slot, &A.proof_lens[k])) { P[k].err = "zk_marlin_prove_batch: output slot too small"; return (int)ZK_ERR_ARG; }
             return (int)ZK_OK;
         });
     }

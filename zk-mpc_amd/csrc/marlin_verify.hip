@@ -9,7 +9,7 @@
 //   MarlinKZG10::check_combinations, accumulate_commitments_and_values, KZG10::check  poly-commit/src/marlin/mod.rs:309-420,
 //                                                    marlin_pc/mod.rs:342-400, kzg10/mod.rs:320-343
 // One equation builder, two back ends.  parse_proof reads the bytes (structure, canonical scalars and abscissae); build_equations
-// re-derives the transcript and turns (key, input, proof) into two lists of terms (point reference, Fr scalar), one per query point:
+// re-derives the challenges (marlin_transcript.hpp: the provers' transcript) and turns (key, input, proof) into two lists of terms (point reference, Fr scalar), one per query point:
 //   L_q = sum_j xi^j (combination j of the commitments)  -  val_q g  -  random_v_q gamma_g  +  z_q W_q        (z = beta, gamma)
 // and the proof holds iff e(L_q, h) e(W_q, -beta_h) = 1 for both -- KZG10::check with the witness term moved to the left, so that G2
 // only ever sees the key's two points.  The two query points are NOT folded by a random coefficient (kzg10::batch_check takes an rng)
@@ -21,13 +21,13 @@
 // g1_lincomb.hip (one wave per proof) followed by pairing.hip's kernels as they are.
 #include "../../include/zkmpc_hip.h"
 #include "devutil.cuh"
-#include "fsrng.hpp"
 #include "groth16_int.hpp"
 #include "hostfield64.hpp"
 #include "hostgroup.hpp"
 #include "internal.hpp"
 #include "marlin_agg_plan.hpp"
 #include "marlin_lc.hpp"
+#include "marlin_transcript.hpp"
 #include "pairing.cuh"
 #include <chrono>
 #include <string.h>
@@ -210,56 +210,23 @@ Parsed parse_proof(const uint8_t* p, size_t len) {
 struct Term { uint32_t point; uint32_t k[8]; };     // point: a KeyPoint, or N_KEY_POINTS + a ProofPoint; k: the plain integer below r
 struct Equations { std::vector<Term> q[2]; };       // at beta, at gamma
 
-HF next_fr(zkfs::FiatShamirRng& fs) {               // Fr::rand (zk_rng_next_fr)
-    for (;;) {
-        zk_fr o;
-        for (int i = 0; i < 4; i++) o.l[i] = fs.r.next_u64();
-        o.l[3] &= 0xffffffffffffffffull >> 3;
-        if (zk_fr_words_valid(o.l)) return HF::from_abi(o);
-    }
-}
-HF sample_outside(const Dom& d, zkfs::FiatShamirRng& fs) {
-    HF t = next_fr(fs);
-    while (d.vanishing(t).is_zero()) t = next_fr(fs);
-    return t;
-}
-void g1_to_bytes(const Affine<G1Field>& p, std::vector<uint8_t>& out) {       // GroupAffine::write: x | y | infinity; zero() = (0, 1, true)
-    const size_t at = out.size();
-    out.resize(at + 97, 0);
-    if (aff_is_inf<G1Field>(p)) { out[at + 48] = 1; out[at + 96] = 1; return; }
-    fq_canonical_bytes(p.x, &out[at]);
-    fq_canonical_bytes(p.y, &out[at + 48]);
-}
-
 // pts: the proof's thirteen points, decompressed (by either back end).  x: load_input's.
 Equations build_equations(const Key& key, const std::vector<HF>& x, const Parsed& pr, const Affine<G1Field>* pts) {
     const Dom H(key.num_constraints), K(key.num_non_zero), X(x.size());
-    std::vector<uint8_t> buf(11 + IVK_LEN);
-    memcpy(buf.data(), "MARLIN-2019", 11);
-    memcpy(buf.data() + 11, key.ivk, IVK_LEN);
-    for (size_t i = 1; i < x.size(); i++) x[i].bytes(buf);
-    zkfs::FiatShamirRng fs = zkfs::FiatShamirRng::from_seed(buf.data(), buf.size());
-    auto absorb_round = [&](int rnd, uint32_t first) {
-        buf.clear();
-        for (uint32_t o = first; o < first + (uint32_t)ROUND_LEN[rnd]; o++) {
-            const bool has = o == PP_G_1 || o == PP_G_2;
-            g1_to_bytes(pts[o], buf);
-            buf.push_back(has ? 1 : 0);
-            g1_to_bytes(has ? pts[o == PP_G_1 ? PP_G_1_SHIFTED : PP_G_2_SHIFTED] : aff_inf<G1Field>(), buf);
-        }
-        fs.absorb(buf);
-    };
+    marlin::Transcript fs(key.ivk, IVK_LEN, x);
+    Comm comms[PP_H_2 + 1];                                             // the nine commitments, a shifted one where the key has a degree bound
+    for (uint32_t o = PP_W; o <= PP_H_2; o++) {
+        comms[o].c = pts[o];
+        comms[o].has_shift = o == PP_G_1 || o == PP_G_2;
+        comms[o].s = comms[o].has_shift ? pts[o == PP_G_1 ? PP_G_1_SHIFTED : PP_G_2_SHIFTED] : aff_inf<G1Field>();
+    }
     MarlinLcIn in;
-    absorb_round(0, PP_W);
-    in.alpha = sample_outside(H, fs);
-    for (HF& e : in.eta) e = next_fr(fs);
-    absorb_round(1, PP_T);
-    in.beta = sample_outside(H, fs);
-    absorb_round(2, PP_G_2);
-    in.gamma = next_fr(fs);
-    fs.absorb(pr.ev_bytes, 32 * N_EVALS);
-    const uint64_t lo = fs.r.next_u64(), hi = fs.r.next_u64();        // u128::rand: the opening challenge
-    const HF two32 = HF::from_u64((uint64_t)1 << 32), xi = HF::from_u64(lo) + HF::from_u64(hi) * two32 * two32;
+    const marlin::Transcript::Round1 r1 = fs.round1(&comms[PP_W], ROUND_LEN[0], H);
+    in.alpha = r1.alpha;
+    for (int m = 0; m < 3; m++) in.eta[m] = r1.eta[m];
+    in.beta = fs.round2(&comms[PP_T], ROUND_LEN[1], H);
+    in.gamma = fs.round3(&comms[PP_G_2], ROUND_LEN[2]);
+    const HF xi = fs.evaluations(pr.ev_bytes, 32 * N_EVALS);
     in.z_b_beta = pr.ev[E_Z_B]; in.t_beta = pr.ev[E_T]; in.g_1_beta = pr.ev[E_G_1]; in.g_2_gamma = pr.ev[E_G_2];
     for (int m = 0; m < 3; m++) in.d[m] = pr.ev[E_A_DENOM + m];
     in.x = x.data();

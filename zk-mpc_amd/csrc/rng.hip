@@ -12,6 +12,7 @@
 #include "devutil.cuh"
 #include "fsrng.hpp"
 #include "internal.hpp"
+#include "marlin_transcript.hpp"
 #include <sys/random.h>
 
 using namespace zk;
@@ -158,17 +159,12 @@ extern "C" int zk_rng_next_u128(zk_rng* r, uint64_t out[2]) {
     return ZK_OK;
     ZK_API_END
 }
-// F::rand for Fr (ff/src/fields/arithmetic.rs:200-219): four u64 in limb order, the top 3 bits masked away, rejected unless
-// below the modulus; the accepted words ARE the element's in-memory (Montgomery) form.
+// F::rand for Fr (marlin_transcript.hpp: fr_rand)
 extern "C" int zk_rng_next_fr(zk_rng* r, zk_fr* out) {
     ZK_API_BEGIN_NOCTX
     if (!r || !out) return ZK_ERR_ARG;
-    for (;;) {
-        uint64_t l[4];
-        for (int i = 0; i < 4; i++) l[i] = r->fs.r.next_u64();
-        l[3] &= 0xffffffffffffffffull >> 3;
-        if (zk_fr_words_valid(l)) { memcpy(out->l, l, 32); return ZK_OK; }
-    }
+    *out = zk::marlin::fr_rand(r->fs.r);
+    return ZK_OK;
     ZK_API_END
 }
 // n x Fr::rand in a row (the 3 |H| coefficients of Marlin's mask polynomial are drawn this way, prover.rs:371-376).
